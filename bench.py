@@ -39,6 +39,12 @@ roofline: fp64 MFMA.  Top level = algorithmic flop of one step (T*N^3 for the fi
           with HIP events on the engine's stream; ``dominant_launch`` is the one stage that is exactly
           ONE kernel launch (K^-1 = L^-T L^-1), whose average duration is what the rocprofv3 kernel
           trace under profiles/ reports for the same command.
+--full  : a plain run sets up, warms up, times the steps and prints the line with the whole-step roofline.  --full adds
+          everything below: the extra stage-timer step (roofline.stages, chain_us_per_128, dominant_launch), and on one GPU
+          the CPU baseline, rmse_vs_oracle_headline (c2), rmse_vs_oracle and extra (c2, in a child process).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last one computed as DIR/<name>.npy (float64): mean and
+          sd (c1 / c2 on the grid, with the hyper-parameter history of rank 0's training; c3, c2full, c3cube likewise).
+          The inputs are seeded, so equal arguments give equal inputs from run to run.
 cpu_baseline: the CPU oracle (torch fp64 + autograd restatement of the reference, kind "port")
           timed on rank 0's host cores AT THE FULL SIZE of the workload: one Adam iteration (loss + backward +
           step) and one prediction, value = M / (T * t_iteration + t_predict).  Two smaller sizes are timed
@@ -561,6 +567,45 @@ def extra_configs(gpim):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, for comparing two builds output for output
+# ------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def step_outputs(workload, res, world, rec, T):
+    """The arrays a caller of the timed path receives from one step, by name (rank 0's view)."""
+    if workload in ("c2", "c1"):
+        # reconstructor.run(): mean and sd on the grid (one image per rank, gathered to rank 0) and the hyper-parameter
+        # history of rank 0's training -- its last T rows, i.e. those of the last step
+        pred = res.detach().cpu().numpy()
+        shape = ((world,) if world > 1 else ()) + tuple(rec.fulldims)
+        hp = rec.hyperparams
+        out = {"mean": pred[:, 0].reshape(shape), "sd": pred[:, 1].reshape(shape)}
+        for k in ("lengthscale", "variance", "noise"):
+            out[k] = np.asarray(hp[k][len(hp[k]) - T:], dtype=np.float64)
+        return out
+    if workload == "c3":
+        mean, sd = res
+        return {"mean": mean, "sd": sd}
+    if workload == "c2full":
+        mean, sd, nll = res
+        return {"mean": mean, "sd": sd, "nll": np.array([nll])}
+    mean, sd, hyp = res                                  # c3cube
+    return dict({"mean": mean, "sd": sd}, **{k: hyp[k] for k in ("variance", "lengthscale", "noise", "loss")})
+
+
+def dump_outputs(path, arrays):
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64, copy=False) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -569,10 +614,15 @@ def main():
     ap.add_argument("--workload", choices=["c2", "c1", "c3", "c2full", "c3cube"], default="c2")
     ap.add_argument("--iterations", type=int, default=None,
                     help="Adam iterations per step (the named workloads use 100 (c2) / 300 (c1) / 250 (c3))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip rmse_vs_oracle and the C1/C3/C4 extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the per-stage roofline step, "
+                         "the CPU baseline, the parity checks against the oracle and the other configs (extra)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip rmse_vs_oracle and the C1/C3/C4 extras")
     ap.add_argument("--extras-only", action="store_true",
-                    help="internal: print {rmse_vs_oracle, extra} as one JSON line and exit (run by the default "
+                    help="internal: print {rmse_vs_oracle, extra} as one JSON line and exit (run by a --full "
                          "command in a child process, so that a kernel trace of the parent holds the timed "
                          "workload's launches only)")
     args = ap.parse_args()
@@ -606,6 +656,7 @@ def main():
 
     stage_ms = {}
     nprob = 1                       # problems advancing together through every launch (c3: the lock-step batch)
+    rec = None                      # c2 / c1: the timed reconstructor
     if args.workload in ("c2", "c1"):
         # ---- build this rank's unit and move it to HBM (untimed)
         if args.workload == "c2":
@@ -683,17 +734,20 @@ def main():
     _settle_interpreter()          # (a full pass of the cyclic collector inside the timed region is harness time, see there)
     # The timed steps run with the stage timers OFF for every workload: c1 / c3 replay one captured iteration per Adam
     # step (which the timers would switch off), and the headline (c2, enqueued launch by launch) must not carry
-    # instrumentation the other lines do not.  The per-stage breakdown comes from ONE extra step after the timed ones,
-    # with the timers on (HIP events on the handle's stream around every stage).
+    # instrumentation the other lines do not.  The per-stage breakdown (--full) comes from ONE extra step after the timed
+    # ones, with the timers on (HIP events on the handle's stream around every stage).
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         res = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before the stage step: that one runs the same reconstructor again
+        dump_outputs(args.dump_outputs, step_outputs(args.workload, res, world, rec, T))
     stage_steps = 1
     ms_stage_step = None
-    if lib is not None:
+    if args.full and lib is not None:
         lib.gpimhip_timing_enable(h, 1)
         timers_clear(lib, h)
         fence()
@@ -737,9 +791,6 @@ def main():
             n3 = float(N) ** 3
             flop_step = T * n3 + 2.0 * n3 / 3.0 + float(N) ** 2 * M       # per GPU
             achieved = flop_step / (ms_step * 1e-3) / 1e12
-            stages = stage_breakdown(stage_ms, N, 1, M, ms_step, stage_steps)
-            lau_ms, lau_n = stage_ms["lauum"]
-            pot_ms, pot_n = stage_ms["potrf"]
             traffic = None
             pmc = os.path.join(ROOT, "profiles", "pmc_lauum.json")
             traffic_from = None
@@ -754,17 +805,20 @@ def main():
                 "scope": "whole step: algorithmic flop (T*N^3 + 2N^3/3 + N^2*M = %.4g per GPU) / ms_per_step" % flop_step,
                 "kernel": "chol_step_kernel / gemm_tiles_kernel (fp64 MFMA tile engine, every O(N^3) stage); largest "
                           "share of the step: factorisation + inverse (chol_step_kernel launches)",
-                "stages": stages,
-                "stages_from": "one extra step after the timed ones, stage timers on (%.1f ms; the timed steps run with "
-                               "the timers off)" % ms_stage_step,
-                "chain_us_per_128": chain_us(stage_ms, N),
-                "dominant_launch": {
-                    "kernel": lauum_kernel + " (K^-1 = L^-T L^-1: exactly one launch per Adam iteration, N^3/3 flop)",
-                    "launches": lau_n, "avg_launch_ms": lau_ms / max(lau_n, 1),
-                    "achieved": (n3 / 3 / (lau_ms / lau_n * 1e-3) / 1e12) if lau_n else None,
-                    "traffic": traffic},
             }
-            out["stages_ms_per_call"] = {k: (v[0] / v[1] if v[1] else None) for k, v in stage_ms.items()}
+            if stage_ms:                # --full: the extra step with the stage timers on
+                lau_ms, lau_n = stage_ms["lauum"]
+                out["roofline"].update({
+                    "stages": stage_breakdown(stage_ms, N, 1, M, ms_step, stage_steps),
+                    "stages_from": "one extra step after the timed ones, stage timers on (%.1f ms; the timed steps run with "
+                                   "the timers off)" % ms_stage_step,
+                    "chain_us_per_128": chain_us(stage_ms, N),
+                    "dominant_launch": {
+                        "kernel": lauum_kernel + " (K^-1 = L^-T L^-1: exactly one launch per Adam iteration, N^3/3 flop)",
+                        "launches": lau_n, "avg_launch_ms": lau_ms / max(lau_n, 1),
+                        "achieved": (n3 / 3 / (lau_ms / lau_n * 1e-3) / 1e12) if lau_n else None,
+                        "traffic": traffic}})
+                out["stages_ms_per_call"] = {k: (v[0] / v[1] if v[1] else None) for k, v in stage_ms.items()}
         elif args.workload == "c3cube":
             mean_c, sd_c, hyp = res
             assert mean_c.shape == (M,) and np.isfinite(mean_c).all() and np.isfinite(sd_c).all()
@@ -809,18 +863,21 @@ def main():
                                          % (N, M, T), "N": N, "M": M, "iterations": T, "kernel": "RBF", "slices": 64}
             flop_step = 64 * (T * float(N) ** 3 + 2.0 * float(N) ** 3 / 3.0 + float(N) ** 2 * M)
             achieved = flop_step / (ms_step * 1e-3) / 1e12 / world
-            pot_ms, pot_n = stage_ms["potrf"]
             out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
-                               "scope": "whole step per GPU: 64 x (T*N^3 + 2N^3/3 + N^2*M) flop / ms_per_step / n_gpus; "
-                                        "stages: one extra step with rank 0's slices as ONE lock-step batch of %d problems per launch "
-                                        "(share_of_step is relative to the concurrent timed step)" % nprob,
-                               "stages": stage_breakdown(stage_ms, N, nprob, M, ms_step, stage_steps),
-                               "stages_from": "one extra step after the timed ones (timers off in the timed steps: they "
-                                              "replay a captured iteration)",
-                               "chain_us_per_128": chain_us(stage_ms, N)}
-            out["stages_ms_per_call"] = {k: (v[0] / v[1] if v[1] else None) for k, v in stage_ms.items()}
-        if world == 1:
+                               "scope": "whole step per GPU: 64 x (T*N^3 + 2N^3/3 + N^2*M) flop / ms_per_step / n_gpus"}
+            if stage_ms:                # --full: the extra step with the stage timers on
+                out["roofline"]["scope"] += ("; stages: one extra step with rank 0's slices as ONE lock-step batch of %d "
+                                             "problems per launch (share_of_step is relative to the concurrent timed step)"
+                                             % nprob)
+                out["roofline"].update({"stages": stage_breakdown(stage_ms, N, nprob, M, ms_step, stage_steps),
+                                        "stages_from": "one extra step after the timed ones (timers off in the timed steps: "
+                                                       "they replay a captured iteration)",
+                                        "chain_us_per_128": chain_us(stage_ms, N)})
+                out["stages_ms_per_call"] = {k: (v[0] / v[1] if v[1] else None) for k, v in stage_ms.items()}
+        if world == 1 and not args.full:
+            out["cpu_baseline"] = None
+        elif world == 1:
             if args.no_cpu_baseline:
                 out["cpu_baseline"] = None
             elif args.workload == "c2":

@@ -53,8 +53,8 @@ def test_rccl_world1(ensure_built):
 @pytest.mark.parametrize("workload,extra", [("c3", ["--iterations", "5"]), ("c2", ["--iterations", "2"]),
                                             ("c1", ["--iterations", "5"]), ("c2full", [])])
 def test_bench_two_ranks(ensure_built, workload, extra):
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "1", "--warmup", "0"]
-                  + extra, 1500)
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "1", "--warmup", "0",
+                   "--full"] + extra, 1500)
     assert r.returncode == 0, r.stdout[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)

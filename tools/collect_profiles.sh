@@ -17,18 +17,18 @@ profiled() {  # profiled <name> <bench.py arguments...>
   name=$1; shift
   for k in 1 2; do
     rm -rf $O/${name}_stats
-    timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_stats -- python $R/bench.py "$@" --no-cpu-baseline > $O/${name}_line_profiled.json 2> $O/${name}_profiled.err
+    timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_stats -- python $R/bench.py --full "$@" --no-cpu-baseline > $O/${name}_line_profiled.json 2> $O/${name}_profiled.err
     [ -s $O/${name}_line_profiled.json ] && return 0
     mv $O/${name}_profiled.err $O/${name}_profiled.crash$k.err
   done
   return 1
 }
 profiled bench
-timeout 900 python $R/bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 900 python $R/bench.py --full > $O/bench_line.json 2> $O/bench.err
 # 1b. the configs north_star names as targets: C1 (128x128 spiral scan) and C3 (64 slices of 64x64), kernel stats + lines
 for wl in c1 c3; do
   profiled $wl --workload $wl
-  timeout 600 python $R/bench.py --workload $wl > $O/${wl}_line.json 2> $O/${wl}.err
+  timeout 600 python $R/bench.py --full --workload $wl > $O/${wl}_line.json 2> $O/${wl}.err
 done
 # 2. PMC passes on two training iterations at the bench size (separate runs, kernel trace only)
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE"; do
