@@ -7,9 +7,9 @@ directory on ``sys.path``: the names of the reference's package root that are on
 (gpim/__init__.py:1-5: ``utils``, ``reconstructor``, ``boptimizer``) and the sub-module paths that
 user code imports from (``gpim.gpreg.gpr``, ``gpim.gpbayes.boptim``, ``gpim.gpbayes.acqfunc``,
 ``gpim.kernels.pyro_kernels``, ``gpim.gprutils``) resolve to ``gpim_amd``.  ``skreconstructor``
-resolves to the engine's exact Kronecker-structured reconstructor (gpim_amd/skgpr.py); the GPyTorch-based
-vector-valued ``vreconstructor`` is outside the scope of this engine and raises
-NotImplementedError when called.
+resolves to the engine's exact Kronecker-structured reconstructor (gpim_amd/skgpr.py).  The vector-valued
+GP is ``gpim.gpreg.vgpr.vreconstructor`` (= ``gpim_amd.vreconstructor``); the package-root name ``vreconstructor``
+is still a stub that raises NotImplementedError and points there.
 """
 from gpim_amd import gprutils as utils            # noqa: F401
 from gpim_amd import gprutils                     # noqa: F401  (``from gpim import gprutils``)
@@ -21,8 +21,8 @@ from gpim_amd import __version__                  # noqa: F401
 def _out_of_scope(name):
     def ctor(*args, **kwargs):
         raise NotImplementedError(
-            "gpim.%s (GPyTorch structured-kernel / vector-valued GP) is outside the scope of the MI355X "
-            "engine; use gpim.reconstructor (exact or sparse=True)" % name)
+            "gpim.%s at the package root is not bound to the MI355X engine; the exact vector-valued GP is "
+            "gpim.gpreg.vgpr.vreconstructor (also gpim_amd.vreconstructor)" % name)
     ctor.__name__ = name
     return ctor
 

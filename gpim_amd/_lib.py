@@ -28,6 +28,14 @@ class ModelStruct(ctypes.Structure):
                 ("jitter", ctypes.c_double)]
 
 
+class VgpStruct(ctypes.Structure):
+    """gpimhip_vgp_t"""
+    _fields_ = [("tasks", ctypes.c_int32), ("rank", ctypes.c_int32), ("independent", ctypes.c_int32),
+                ("ls_softplus", ctypes.c_int32)]
+
+
+VGP_MAX_TASKS = 16
+
 _lib = None
 
 _PROTOS = {
@@ -128,6 +136,12 @@ _PROTOS = {
                                         c_dp]),
     "gpimhip_step_plan_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "gpimhip_vgp_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
+                                            c_dp, ctypes.c_int64, c_dp, c_dp, c_dp]),
+    "gpimhip_fit_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp, c_dp,
+                                       ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
+    "gpimhip_predict_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
+                                           c_dp, ctypes.c_int64, c_dp, c_dp, ctypes.c_int64, c_dp, c_dp]),
 }
 EXPORTS = tuple(_PROTOS)
 

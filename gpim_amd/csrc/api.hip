@@ -9,6 +9,7 @@
 #include <atomic>
 #include <mutex>
 #include "common.hpp"
+#include "vgp.hpp"
 
 // kernels implemented in the other translation units
 int launch_theta_raw(gpimhip_ctx* h, const gpimhip_model_t* m, const double* raw);
@@ -630,6 +631,7 @@ struct RunAhead {
 int vfe_finish_and_check(gpimhip_ctx* h) { return finish_and_check(h); }
 void vfe_release(gpimhip_ctx* h);
 void kron_release(gpimhip_ctx* h);
+void vgp_release(gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -689,6 +691,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     (void)hipStreamSynchronize(h->stream);
     vfe_release(h);
     kron_release(h);
+    vgp_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
     dev_free(h, &h->keys, h->keys_cap);
@@ -1532,6 +1535,184 @@ int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat
         return GPIMHIP_E_BADARG;
     HIP_TRY(hipSetDevice(h->device));
     return launch_thin_batch(h, vals, flat_idx, n, d, shape, dscale, max_out, keep_out, nkeep_out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// multi-output GP (gpimhip_vgp_nll_grad / gpimhip_fit_vgp / gpimhip_predict_vgp): T single-task blocks of the batched
+// engine, x_stride 0, whose per-problem theta comes from vgp_setup_kernel (vgp.hip)
+// ------------------------------------------------------------------------------------------
+struct VgpWs {
+    VgpDev* st = nullptr;
+    double* adam = nullptr;         // 2 x VGP_MAXP: Adam m, v
+    int32_t* iter = nullptr;
+    double* kb = nullptr; int64_t kb_cap = 0;        // T x np: K beta_t
+    double* pred = nullptr; int64_t pred_cap = 0;    // 2 x T x M: the blocks' mean and variance
+};
+void vgp_release(gpimhip_ctx* h) {
+    VgpWs* w = (VgpWs*)h->vgp;
+    if (!w) return;
+    dev_free(h, &w->st, 1);
+    dev_free(h, &w->adam, 2 * VGP_MAXP);
+    dev_free(h, &w->iter, 1);
+    dev_free(h, &w->kb, w->kb_cap);
+    dev_free(h, &w->pred, w->pred_cap);
+    delete w;
+    h->vgp = nullptr;
+}
+static int vgp_ws(gpimhip_ctx* h, int T, int64_t M, VgpWs** out) {
+    VgpWs* w = (VgpWs*)h->vgp;
+    if (!w) {
+        w = new VgpWs();
+        h->vgp = w;
+        GP_TRY(dev_alloc(h, &w->st, 1));
+        GP_TRY(dev_alloc(h, &w->adam, 2 * VGP_MAXP));
+        GP_TRY(dev_alloc(h, &w->iter, 1));
+    }
+    const int64_t kb = (int64_t)T * h->np, pr = 2 * (int64_t)T * M;
+    if (w->kb_cap < kb) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        dev_free(h, &w->kb, w->kb_cap);
+        w->kb_cap = 0;
+        GP_TRY(dev_alloc(h, &w->kb, kb));
+        w->kb_cap = kb;
+    }
+    if (w->pred_cap < pr) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        dev_free(h, &w->pred, w->pred_cap);
+        w->pred_cap = 0;
+        GP_TRY(dev_alloc(h, &w->pred, pr));
+        w->pred_cap = pr;
+    }
+    *out = w;
+    return GPIMHIP_OK;
+}
+static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
+                     int64_t N) {
+    if (!h || !m || !vg || !X || !Y || N < 1) return GPIMHIP_E_BADARG;
+    FP64_ONLY(h);
+    GP_TRY(check_model(m));
+    if (m->kernel != GPIMHIP_KERNEL_RBF && m->kernel != GPIMHIP_KERNEL_MATERN52) {
+        gpim_set_error("the multi-output GP takes the RBF or Matern52 kernel");
+        return GPIMHIP_E_BADARG;
+    }
+    if (vg->tasks < 1 || vg->tasks > GPIMHIP_VGP_MAX_TASKS || (!vg->independent && (vg->rank < 1 || vg->rank > vg->tasks)) ||
+        vgp_layout(*m, *vg).P > 256) {
+        gpim_set_error("the multi-output GP takes 1 .. 16 tasks and an IndexKernel rank of 1 .. tasks");
+        return GPIMHIP_E_BADARG;
+    }
+    if (h->refl.mask) {
+        gpim_set_error("the multi-output GP needs a handle without reflection blocks (gpimhip_set_reflection(h, 0, ...))");
+        return GPIMHIP_E_BADARG;
+    }
+    return GPIMHIP_OK;
+}
+// Loss and gradient at u (and, fit mode, one Adam step): setup -> z -> the T blocks' K, L, L^-1, z, beta -> K^-1 ->
+// gradient contraction -> K beta -> finalize.  Every launch reads its iteration-dependent values from the device.
+static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, VgpWs* w, const double* X,
+                    const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIterV fi) {
+    const int64_t np = h->np;
+    const int T = vg->tasks;
+    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st));
+    GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
+    GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
+    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
+    GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
+    GP_TRY(launch_vgp_kbeta(h, m, X, N, T, w->kb));
+    AdamStep st;
+    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi);
+}
+static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t M, VgpWs** w) {
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = vg->tasks;
+    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(ws_ensure_padded(h, N));
+    return vgp_ws(h, vg->tasks, M, w);
+}
+
+extern "C" {
+
+int gpimhip_vgp_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
+                         const double* Y, int64_t N, const double* u, double* loss_out, double* grad_out) {
+    GP_TRY(vgp_check(h, m, vg, X, Y, N));
+    if (!u) return GPIMHIP_E_BADARG;
+    VgpWs* w = nullptr;
+    GP_TRY(vgp_begin(h, vg, N, 0, &w));
+    GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, const_cast<double*>(u), 0, loss_out, grad_out, FinalizeIterV{nullptr, nullptr, 0, nullptr, nullptr}));
+    return finish_and_check(h);
+}
+
+int gpimhip_fit_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
+                    int64_t N, double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out) {
+    GP_TRY(vgp_check(h, m, vg, X, Y, N));
+    if (!u_inout || T < 0) return GPIMHIP_E_BADARG;
+    VgpWs* w = nullptr;
+    GP_TRY(vgp_begin(h, vg, N, 0, &w));
+    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
+    h->fit_completed = T;
+    if (T == 0) return finish_and_check(h);
+    GP_TRY(upload_bc_table(h, lr, T));
+    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * VGP_MAXP * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
+    const FinalizeIterV fi{w->iter, h->bc, T, hist_out, loss_out};
+    // one iteration captured into a hipGraph and replayed, as fit_impl does for the batched path
+    const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
+    const bool use_graph = T >= 8 && !h->timing && !getenv("GPIMHIP_NO_GRAPH") && npanel < EAGER_MIN_PANELS &&
+                           ensure_capture_stream(h);
+    if (use_graph) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipStream_t main_s = h->stream;
+        h->stream = h->capture_stream;
+        capture_lock(h);
+        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
+        int rc = GPIMHIP_OK;
+        if (e == hipSuccess) {
+            h->capturing = true;
+            rc = vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi);
+            h->capturing = false;
+            e = hipStreamEndCapture(h->capture_stream, &graph);
+        }
+        capture_unlock(h);
+        h->stream = main_s;
+        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        const bool inst_ok = e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (inst_ok) {
+            RunAhead ra(h, h->np);
+            hipError_t le = hipSuccess;
+            for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, main_s);
+            rc = finish_and_check(h);
+            (void)hipGraphExecDestroy(exec);
+            (void)hipGraphDestroy(graph);
+            HIP_TRY(le);
+            return rc;
+        }
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();                        // capture unavailable: plain launches below
+    }
+    RunAhead ra(h, h->np);
+    for (int t = 0; t < T && !ra.stop(t); ++t) GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi));
+    return finish_and_check(h);
+}
+
+int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
+                        const double* Y, int64_t N, const double* u, const double* Xs, int64_t M, double* mean_out,
+                        double* var_out) {
+    GP_TRY(vgp_check(h, m, vg, X, Y, N));
+    if (!u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
+    VgpWs* w = nullptr;
+    GP_TRY(vgp_begin(h, vg, N, M, &w));
+    const int T = vg->tasks;
+    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st));
+    GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
+    GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
+    double* mblk = w->pred;
+    double* vblk = w->pred + (int64_t)T * M;
+    GP_TRY(predict_cols(h, m, X, 0, N, T, Xs, M, mblk, vblk));
+    GP_TRY(launch_vgp_combine(h, T, M, w->st, mblk, vblk, mean_out, var_out));
+    return finish_and_check(h);
 }
 
 }  // extern "C"

@@ -184,6 +184,8 @@ struct gpimhip_ctx {
     void* vfe = nullptr;
     // structured (Kronecker) workspace, owned by kron.hip (KronWs*); released by kron_release()
     void* kron = nullptr;
+    // multi-output GP workspace, owned by api.hip (VgpWs); released by vgp_release()
+    void* vgp = nullptr;
     double* refine = nullptr; int64_t refine_cap = 0;    // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
 };

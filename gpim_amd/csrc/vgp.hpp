@@ -1,0 +1,58 @@
+// vgp.hpp -- shared declarations of the multi-output GP (vgp.hip kernels, api.hip drivers).
+#pragma once
+#include "common.hpp"
+
+#define VGP_MAXT GPIMHIP_VGP_MAX_TASKS
+#define VGP_MAXR GPIMHIP_VGP_MAX_TASKS      // IndexKernel rank <= T
+#define VGP_MAXP (4 * VGP_MAXT + GPIMHIP_MAX_DIM + 1 + (VGP_MAXR - 1) * VGP_MAXT)
+#define VGP_SWEEPS 12                      // Jacobi sweeps at most (quadratic convergence: T <= 16 needs < 10)
+
+// offsets of the raw vector u = [mu (T) | F (T x R) or r_o (T) | r_v (T, correlated only) | r_l (n_ls) | r_a (T) | r_g]
+struct VgpLayout { int mu, scale, diag, ls, noise, P; };
+__host__ __device__ inline VgpLayout vgp_layout(const gpimhip_model_t& m, const gpimhip_vgp_t& vg) {
+    VgpLayout L;
+    const int T = vg.tasks;
+    L.mu = 0;
+    L.scale = T;
+    if (vg.independent) {
+        L.diag = T;           // r_o is the diagonal of B
+        L.ls = 2 * T;
+    } else {
+        L.diag = T + T * vg.rank;
+        L.ls = L.diag + T;
+    }
+    L.noise = L.ls + m.n_ls;
+    L.P = L.noise + T + 1;
+    return L;
+}
+
+// state of one evaluation, written by vgp_setup_kernel (device memory)
+struct VgpDev {
+    double lam[VGP_MAXT];                 // eigenvalues of B~ = the blocks' kernel variances
+    double Q[VGP_MAXT * VGP_MAXT];        // eigenvectors, Q[a][t]
+    double P[VGP_MAXT * VGP_MAXT];        // S^-1/2 Q
+    double B[VGP_MAXT * VGP_MAXT];        // task covariance
+    double F[VGP_MAXT * VGP_MAXR];        // IndexKernel factor (correlated model)
+    double bdiag[VGP_MAXT], ddiag[VGP_MAXT];   // softplus(r_v or r_o) and its derivative
+    double s[VGP_MAXT], sqs[VGP_MAXT];    // noise per task and its square root
+    double dsa[VGP_MAXT], dsg;            // d s_a / d r_a, d s_a / d r_g
+    double mu[VGP_MAXT];
+    double ls[GPIMHIP_MAX_DIM], dls[GPIMHIP_MAX_DIM];
+};
+
+struct FinalizeIterV {
+    int32_t* iter;              // device counter (null: one evaluation)
+    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
+    int32_t T;
+    double* hist_base;          // T x n_ls or null
+    double* loss_base;          // T or null
+};
+
+int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st);
+int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st);
+int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, double* kb);
+int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
+                        const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
+                        double* loss_out, double* grad_out, FinalizeIterV fi);
+int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const double* mblk, const double* vblk,
+                       double* mean_out, double* var_out);

@@ -1,0 +1,257 @@
+"""
+vgpr.py -- ``vreconstructor``: exact GP regression of vector-valued functions (several outputs on one set of inputs).
+
+Same constructor, methods and return values as the reference's gpim/gpreg/vgpr.py:19-283 (GPyTorch ExactGP with a
+MultitaskKernel, or per-task ScaleKernels when ``independent=True``, and a rank-0 MultitaskGaussianLikelihood); the
+covariance C = B (x) K + diag(s) (x) I of the T tasks is split exactly into T single-task blocks that the MI355X engine
+factors in lock-step (include/gpimhip.h: gpimhip_fit_vgp / gpimhip_predict_vgp).
+
+Readings and deliberate differences, in one place:
+  * The IndexKernel factor F (T x 1) is drawn as ``torch.randn(T, 1)`` in float64 on the CPU generator right after
+    ``torch.manual_seed(seed)`` -- the reference's first random draw.  With ``use_gpu`` the reference draws on the CUDA
+    default tensor type, i.e. from another generator: its numbers can differ from these.
+  * Independent model: the reference sets ``kernel.batch_shape`` after the kernel is built, which does not reshape
+    ``raw_lengthscale``; the lengthscales are therefore shared by all tasks and only the output scales are per task.
+    GPyTorch is not available to check this reading against.
+  * The loss is -log N(vec Y | mu (x) 1, C) / (N T), GPyTorch's current ExactMarginalLogLikelihood; older GPyTorch
+    versions (the reference notebook's) divided by a smaller number.  Adam is invariant to the divisor up to its eps.
+  * Prediction returns the EXACT predictive mean and standard deviation of ``likelihood(model(Xtest))`` (noise
+    included) -- what the reference estimates from 100 ``rsample`` draws (vgpr.py:213-221; its sd carries a Monte-Carlo
+    error of roughly 7 %).  ``n_samples``, ``num_batches`` and ``max_root`` / ``maxroot`` are accepted and ignored.
+  * Matern52 uses the engine's form of the covariance function (csrc/kfun.hpp: r = sqrt(r2 + 1e-12)), which differs from
+    GPyTorch's by at most ~2.5e-12 per entry.
+"""
+import ctypes
+import time
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import gprutils
+
+_F64 = torch.float64
+_KERNELS = {"RBF": 0, "Matern52": 1}
+
+
+def _softplus(x):
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x > 20.0, x, np.log1p(np.exp(np.minimum(x, 20.0))))
+
+
+def _sigmoid(x):
+    return 1.0 / (1.0 + np.exp(-np.asarray(x, dtype=np.float64)))
+
+
+def raw_layout(T, n_ls, independent, rank=1):
+    """Offsets of u = [mu (T) | F (T x rank) or r_o (T) | r_v (T, correlated only) | r_l (n_ls) | r_a (T) | r_g]
+    (include/gpimhip.h): dict of slices, and the length P."""
+    o = {"mu": slice(0, T)}
+    if independent:
+        o["scale"] = slice(T, 2 * T)
+        p = 2 * T
+    else:
+        o["F"] = slice(T, T + T * rank)
+        o["rv"] = slice(T + T * rank, 2 * T + T * rank)
+        p = 2 * T + T * rank
+    o["ls"] = slice(p, p + n_ls)
+    o["noise"] = slice(p + n_ls, p + n_ls + T)
+    o["global"] = slice(p + n_ls + T, p + n_ls + T + 1)
+    return o, p + n_ls + T + 1
+
+
+def constrained(u, T, n_ls, independent, bounds=None, rank=1):
+    """Host restatement of the device maps: (mu, B, s, lengthscales) from the raw vector u (numpy float64)."""
+    u = np.asarray(u, dtype=np.float64)
+    o, _ = raw_layout(T, n_ls, independent, rank)
+    mu = u[o["mu"]].copy()
+    if independent:
+        B = np.diag(_softplus(u[o["scale"]]))
+    else:
+        F = u[o["F"]].reshape(T, rank)
+        B = F @ F.T + np.diag(_softplus(u[o["rv"]]))
+    r = u[o["ls"]]
+    if bounds is None:
+        ls = _softplus(r)
+    else:
+        lo, hi = bounds
+        ls = _sigmoid(r) * (hi - lo) + lo
+    s = (1e-4 + _softplus(u[o["noise"]])) + (1e-4 + _softplus(u[o["global"]][0]))
+    return mu, B, s, ls
+
+
+class vreconstructor:
+    """``vreconstructor(X, y, Xtest=None, kernel='RBF', lengthscale=None, independent=False, learning_rate=.1,
+    iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs)`` -- argument order and defaults of gpim/gpreg/vgpr.py:73-85.
+
+    X: (c, *dims) grid coordinates; y: (*dims, T) observations of T outputs (rows with a NaN output are dropped);
+    kernel: 'RBF' or 'Matern52'; lengthscale: [lower, upper] bounds (two scalars or two lists of c), or None (unbounded,
+    softplus); independent: per-task output scales instead of the task covariance.  ``isotropic=True`` gives one
+    lengthscale for all dimensions.  After training, ``task_covar`` (B), ``noise`` (s), ``mean_constants`` (mu) and
+    ``lengthscale`` hold the constrained parameters."""
+
+    def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, independent=False, learning_rate=.1,
+                 iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
+        self.precision = kwargs.get("precision", "double")
+        if self.precision == "single":
+            raise NotImplementedError("vreconstructor: precision='single' is not implemented by the MI355X engine "
+                                      "(the multi-output GP runs in double precision)")
+        if kernel not in _KERNELS:
+            raise NotImplementedError("vreconstructor: kernel %r is not implemented by the MI355X engine "
+                                      "('RBF' or 'Matern52'; the spectral-mixture kernel is out of scope)" % (kernel,))
+        self._handle = _lib.Handle()
+        self._dev = self._handle.device
+        torch.manual_seed(seed)
+        input_dim = np.ndim(y) - 1
+        Xt, yt = gprutils.prepare_training_data(X, y, vector_valued=True)
+        if Xt.shape[0] != yt.shape[0]:
+            raise ValueError("vreconstructor: %d input points but %d observation rows (NaN patterns of X and y differ)"
+                             % (Xt.shape[0], yt.shape[0]))
+        T = int(yt.shape[-1])
+        if T > _lib.VGP_MAX_TASKS:
+            raise ValueError("vreconstructor: at most %d outputs (got %d)" % (_lib.VGP_MAX_TASKS, T))
+        self.num_tasks = T
+        self.fulldims = (Xtest.shape[1:] if Xtest is not None else X.shape[1:]) + (T,)
+        self.X, self.y = Xt, yt
+        self.Xtest = gprutils.prepare_test_data(Xtest) if Xtest is not None else None
+        isotropic = bool(kwargs.get("isotropic"))
+        self.isotropic = isotropic
+        n_ls = 1 if isotropic else input_dim
+        self._n_ls = n_ls
+        m = _lib.ModelStruct()
+        m.kernel, m.dim, m.n_ls = _KERNELS[kernel], input_dim, n_ls
+        m.amp_lo, m.amp_hi, m.jitter = 0.0, 1.0, 0.0
+        self._bounds = None
+        if lengthscale is not None:
+            lo = np.broadcast_to(np.asarray(lengthscale[0], dtype=np.float64), (n_ls,)).copy()
+            hi = np.broadcast_to(np.asarray(lengthscale[1], dtype=np.float64), (n_ls,)).copy()
+            self._bounds = (lo, hi)
+            for k in range(n_ls):
+                m.ls_lo[k], m.ls_hi[k] = lo[k], hi[k]
+        self._mstruct = m
+        vg = _lib.VgpStruct()
+        vg.tasks, vg.rank, vg.independent, vg.ls_softplus = T, 1, int(bool(independent)), int(lengthscale is None)
+        self._vstruct = vg
+        self.independent = bool(independent)
+        _, P = raw_layout(T, n_ls, self.independent)
+        u = torch.zeros(P, dtype=_F64)
+        if not self.independent:        # IndexKernel covar_factor = randn(T, 1): the first draw after manual_seed(seed)
+            o, _ = raw_layout(T, n_ls, False)
+            u[o["F"]] = torch.randn(T, 1, dtype=_F64).reshape(-1)
+        self._u = u.to(self._dev)
+        self._Xd = self.X.to(self._dev, _F64).contiguous()
+        self._Yd = self.y.to(self._dev, _F64).t().contiguous()        # T x N, task-major
+        self.iterations = iterations
+        self.learning_rate = learning_rate
+        self.lscales = []
+        self.loss_all = []
+        self.hyperparams = {"lengthscale": self.lscales}
+        self.verbose = verbose
+
+    # ------------------------------------------------------------------ parameters
+    def _params(self):
+        return constrained(self._u.cpu().numpy(), self.num_tasks, self._n_ls, self.independent, self._bounds)
+
+    @property
+    def mean_constants(self):
+        return self._params()[0]
+
+    @property
+    def task_covar(self):
+        return self._params()[1]
+
+    @property
+    def noise(self):
+        return self._params()[2]
+
+    @property
+    def lengthscale(self):
+        return self._params()[3]
+
+    def nll_grad(self, u=None):
+        """Loss and gradient at the raw vector u (default: the current one) -- the engine's evaluation, for checks."""
+        u = self._u if u is None else torch.as_tensor(u, dtype=_F64).to(self._dev).contiguous()
+        loss = torch.empty(1, dtype=_F64, device=self._dev)
+        grad = torch.empty(u.numel(), dtype=_F64, device=self._dev)
+        _lib.check(self._handle.lib.gpimhip_vgp_nll_grad(
+            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
+            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
+        return float(loss.item()), grad.cpu().numpy()
+
+    # ------------------------------------------------------------------ training
+    def train(self, **kwargs):
+        """Adam on the negative log marginal likelihood (vgpr.py:141-182); a fresh optimiser state per call."""
+        if kwargs.get("learning_rate") is not None:
+            self.learning_rate = kwargs.get("learning_rate")
+        if kwargs.get("iterations") is not None:
+            self.iterations = kwargs.get("iterations")
+        if kwargs.get("verbose") is not None:
+            self.verbose = kwargs.get("verbose")
+        T = int(self.iterations)
+        if self.verbose:
+            print('Model training...')
+        start_time = time.time()
+        hist = torch.empty((max(T, 1), self._n_ls), dtype=_F64, device=self._dev)
+        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
+        rc = self._handle.lib.gpimhip_fit_vgp(
+            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
+            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist),
+            _lib.ptr(loss))
+        failed = rc == _lib.E_NOT_PD
+        if failed:
+            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
+        else:
+            _lib.check(rc)
+        hist_h, loss_h = hist[:T].cpu().numpy(), loss[:T].cpu().numpy()
+        dt = time.time() - start_time
+        for i in range(T):
+            self.lscales.append(hist_h[i].tolist())
+            self.loss_all.append(float(loss_h[i]))
+            if self.verbose == 2 and (i % 10 == 0 or i == T - 1):
+                print('iter: {} ...'.format(i),
+                      'loss: {} ...'.format(np.around(loss_h[i], 4)),
+                      'length: {} ...'.format(np.around(self.lscales[-1], 4)))
+        if failed:
+            _lib.check(rc)
+        if self.verbose:
+            if T > 10:
+                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
+            print('training completed in {} s'.format(np.round(dt, 2)))
+            if T > 0:
+                print('Final parameter values:\n',
+                      'lengthscale: {}'.format(np.around(self.lscales[-1], 4)))
+        return
+
+    # ------------------------------------------------------------------ prediction
+    def predict(self, Xtest=None, **kwargs):
+        """Exact predictive mean and standard deviation at Xtest, shape ``Xtest.shape[1:] + (T,)`` each."""
+        if Xtest is None and self.Xtest is None:
+            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
+            self.Xtest = self.X
+            self.fulldims = (self.X.shape[0], self.num_tasks)
+        elif Xtest is not None:
+            self.Xtest = gprutils.prepare_test_data(Xtest)
+            self.fulldims = Xtest.shape[1:] + (self.num_tasks,)
+        if kwargs.get("verbose") is not None:
+            self.verbose = kwargs.get("verbose")
+        if self.verbose:
+            print('Calculating predictive mean and uncertainty...')
+        Xs = self.Xtest.to(self._dev, _F64).contiguous()
+        M = Xs.shape[0]
+        mean = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
+        var = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
+        _lib.check(self._handle.lib.gpimhip_predict_vgp(
+            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
+            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean), _lib.ptr(var)))
+        sd = torch.sqrt(var)
+        mean, sd = mean.cpu().numpy().reshape(self.fulldims), sd.cpu().numpy().reshape(self.fulldims)
+        if self.verbose:
+            print("Done")
+        return mean, sd
+
+    def run(self):
+        """train() then predict(); returns mean, sd, hyperparams (vgpr.py:258-270)."""
+        self.train()
+        mean, sd = self.predict()
+        return mean, sd, self.hyperparams

@@ -163,6 +163,46 @@ int gpimhip_predict_exact_batched(gpimhip_handle h, const gpimhip_model_t* m,
                                   const double* u, const double* Xs, int64_t M,
                                   double* mean_out, double* var_out);
 
+/* ---- exact multi-output GP (vector-valued functions) ---------------------------------------
+ * Replaces GPyTorch's ExactGP with MultitaskKernel / MultitaskGaussianLikelihood as the reference's vreconstructor builds
+ * it (gpim/gpreg/vgpr.py:286-317 correlated, 320-354 independent).  T tasks share the N inputs X (vgpr.py:103-104: rows
+ * with any NaN output are dropped); Y is T x N, task-major (block a = the N values of task a).
+ *   C = B (x) K + diag(s) (x) I_N,   K = the RBF / Matern52 kernel at lengthscales l (no output scale of its own)
+ *   correlated:  B = F F^T + diag(softplus(r_v)), F: T x rank (gpytorch IndexKernel; the reference uses rank 1)
+ *   independent: B = diag(softplus(r_o))  (ScaleKernel(batch_shape=T); the lengthscales stay shared, vgpr.py:341-343)
+ *   s_a = (1e-4 + softplus(r_a)) + (1e-4 + softplus(r_g))   (rank-0 likelihood: per-task plus global noise)
+ *   l_k = ls_lo_k + (ls_hi_k - ls_lo_k) sigmoid(r_l,k)  (gpytorch Interval), or softplus(r_l,k) with ls_softplus != 0
+ *   mean: a constant mu_a per task
+ * Parameter vector (unconstrained, what Adam updates), P doubles:
+ *   u = [mu (T) | F (T x rank, row-major) or r_o (T) | r_v (T, correlated only) | r_l (n_ls) | r_a (T) | r_g]
+ * loss = -log N(vec Y | mu (x) 1, C) / (N T)  (gpytorch ExactMarginalLogLikelihood divides by the number of targets).
+ * The model's kernel field is GPIMHIP_KERNEL_RBF or GPIMHIP_KERNEL_MATERN52, dim / n_ls / ls_lo / ls_hi as for the
+ * single-task GP; amp_lo, amp_hi and jitter are not used (GPyTorch adds no jitter here).  More than 16 tasks, another
+ * kernel, or P > 256 -> GPIMHIP_E_BADARG.  Double-precision handles only.
+ * The engine splits C exactly into T single-task blocks lambda_t K + I and runs them in lock-step
+ * through the batched exact-GP path; the handle's batched workspace is sized for T problems of N points.
+ *   gpimhip_vgp_nll_grad   loss (1 double) and d loss / du (P doubles) at u     (vgpr.py:163-166: loss and backward)
+ *   gpimhip_fit_vgp        T_iter Adam iterations on u, no host synchronisation inside the loop (vgpr.py:155-176): fresh
+ *                          Adam state, lr, betas (0.9, 0.999), eps 1e-8; hist_out: T_iter x n_ls lengthscales AFTER each
+ *                          step (vgpr.py:169-174), loss_out: T_iter losses BEFORE each step (either may be NULL)
+ *   gpimhip_predict_vgp    the exact predictive mean and variance of likelihood(model(Xs)) (noise included) at M test
+ *                          points (NaN rows give NaN), M x T each (task fastest).  Replaces the 100-sample Monte-Carlo
+ *                          estimate of vgpr.py:213-221 by the quantities it estimates. */
+#define GPIMHIP_VGP_MAX_TASKS 16
+typedef struct {
+    int32_t tasks;          /* T, 1 .. GPIMHIP_VGP_MAX_TASKS                                        */
+    int32_t rank;           /* IndexKernel rank (correlated model), 1 .. T; ignored when independent */
+    int32_t independent;    /* 0: MultitaskKernel (vgprmodel), 1: per-task ScaleKernel (ivgprmodel)  */
+    int32_t ls_softplus;    /* 0: Interval(ls_lo, ls_hi) lengthscales, 1: unbounded (softplus)       */
+} gpimhip_vgp_t;
+int gpimhip_vgp_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
+                         const double* Y, int64_t N, const double* u, double* loss_out, double* grad_out);
+int gpimhip_fit_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
+                    int64_t N, double* u_inout, double lr, int32_t T_iter, double* hist_out, double* loss_out);
+int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
+                        const double* Y, int64_t N, const double* u, const double* Xs, int64_t M, double* mean_out,
+                        double* var_out);
+
 /* ---- sparse (inducing-point) GP, variational free energy ---------------------------------
  * Replaces pyro.contrib.gp.models.SparseGPRegression(approx="VFE") as constructed by
  * reconstructor(sparse=True) (gpim/gpreg/gpr.py:145-155; formulas SURVEY App. A.7).
