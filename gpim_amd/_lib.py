@@ -36,6 +36,15 @@ class VgpStruct(ctypes.Structure):
 
 VGP_MAX_TASKS = 16
 
+
+class SmStruct(ctypes.Structure):
+    """gpimhip_sm_t"""
+    _fields_ = [("dim", ctypes.c_int32), ("mixtures", ctypes.c_int32), ("ard", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+SM_MAX_MIXTURES = 16
+
 _lib = None
 
 _PROTOS = {
@@ -142,6 +151,14 @@ _PROTOS = {
                                        ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
     "gpimhip_predict_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
                                            c_dp, ctypes.c_int64, c_dp, c_dp, ctypes.c_int64, c_dp, c_dp]),
+    "gpimhip_sm_kmat": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, ctypes.c_int64, c_dp, ctypes.c_int64,
+                                       c_dp, c_dp, ctypes.c_int64]),
+    "gpimhip_sm_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
+                                           c_dp]),
+    "gpimhip_fit_sm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
+                                      ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
+    "gpimhip_predict_sm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
+                                          ctypes.c_int64, c_dp, c_dp]),
 }
 EXPORTS = tuple(_PROTOS)
 

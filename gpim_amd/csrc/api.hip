@@ -10,6 +10,7 @@
 #include <mutex>
 #include "common.hpp"
 #include "vgp.hpp"
+#include "sm.hpp"
 
 // kernels implemented in the other translation units
 int launch_theta_raw(gpimhip_ctx* h, const gpimhip_model_t* m, const double* raw);
@@ -632,6 +633,7 @@ int vfe_finish_and_check(gpimhip_ctx* h) { return finish_and_check(h); }
 void vfe_release(gpimhip_ctx* h);
 void kron_release(gpimhip_ctx* h);
 void vgp_release(gpimhip_ctx* h);
+void sm_release(gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -692,6 +694,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     vfe_release(h);
     kron_release(h);
     vgp_release(h);
+    sm_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
     dev_free(h, &h->keys, h->keys_cap);
@@ -721,7 +724,7 @@ int gpimhip_timing_enable(gpimhip_handle h, int enable) {
 }
 
 int gpimhip_timing_read(gpimhip_handle h, int stage, double* total_ms, int64_t* count) {
-    if (!h || stage < 0 || stage > 3 || !total_ms || !count) return GPIMHIP_E_BADARG;
+    if (!h || stage < 0 || stage > 5 || !total_ms || !count) return GPIMHIP_E_BADARG;
     HIP_TRY(hipStreamSynchronize(h->stream));
     double tot = 0.0;
     for (auto& pr : h->ev[stage]) {
@@ -1712,6 +1715,233 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
     double* vblk = w->pred + (int64_t)T * M;
     GP_TRY(predict_cols(h, m, X, 0, N, T, Xs, M, mblk, vblk));
     GP_TRY(launch_vgp_combine(h, T, M, w->st, mblk, vblk, mean_out, var_out));
+    return finish_and_check(h);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// spectral-mixture kernel (gpimhip_sm_kmat / gpimhip_sm_nll_grad / gpimhip_fit_sm / gpimhip_predict_sm): the general padded
+// exact-GP path at every N (no fused small-N trainer, no fused predict), with the covariance, the gradient contraction and
+// the finalize step of sm.hip.  Parameters, Adam state and history live here: P = 2 + Q (2 D + 1) exceeds GPIMHIP_MAX_PARAMS.
+// ------------------------------------------------------------------------------------------
+struct SmWs {
+    SmDev* st = nullptr;
+    double* adam = nullptr;                            // 2 x SM_MAXP: Adam m, v
+    int32_t* iter = nullptr;
+    double* sums = nullptr;                            // SM_MAXP: the gradient records added up over the tiles
+    double* csx = nullptr; int64_t csx_cap = 0;        // 2 Q dim x np: phases of the training points
+    double* csz = nullptr; int64_t csz_cap = 0;        // 2 Q dim x (test chunk): phases of the test points
+    double* part = nullptr; int64_t part_cap = 0;      // records x lower tiles
+};
+void sm_release(gpimhip_ctx* h) {
+    SmWs* w = (SmWs*)h->sm;
+    if (!w) return;
+    dev_free(h, &w->st, 1);
+    dev_free(h, &w->adam, 2 * SM_MAXP);
+    dev_free(h, &w->iter, 1);
+    dev_free(h, &w->sums, SM_MAXP);
+    dev_free(h, &w->csx, w->csx_cap);
+    dev_free(h, &w->csz, w->csz_cap);
+    dev_free(h, &w->part, w->part_cap);
+    delete w;
+    h->sm = nullptr;
+}
+template <typename T>
+static int sm_grow(gpimhip_ctx* h, T** p, int64_t* cap, int64_t want) {
+    if (*cap >= want) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    dev_free(h, p, *cap);
+    *cap = 0;
+    GP_TRY(dev_alloc(h, p, want));
+    *cap = want;
+    return GPIMHIP_OK;
+}
+// np_x: phase slots of the training points (0: none), mz: of the test points, ntile: lower tiles of the gradient records
+static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t mz, int64_t ntile, SmWs** out) {
+    SmWs* w = (SmWs*)h->sm;
+    if (!w) {       // the fixed buffers first; the workspace is published only once all of them exist
+        w = new SmWs();
+        int rc = dev_alloc(h, &w->st, 1);
+        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->adam, 2 * SM_MAXP);
+        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->iter, 1);
+        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->sums, SM_MAXP);
+        h->sm = w;
+        if (rc != GPIMHIP_OK) {
+            sm_release(h);
+            return rc;
+        }
+    }
+    const int64_t per = 2 * (int64_t)sm->mixtures * sm->dim;
+    GP_TRY(sm_grow(h, &w->csx, &w->csx_cap, per * np_x));
+    GP_TRY(sm_grow(h, &w->csz, &w->csz_cap, per * mz));
+    GP_TRY(sm_grow(h, &w->part, &w->part_cap, (int64_t)sm_layout(*sm).P * ntile));
+    *out = w;
+    return GPIMHIP_OK;
+}
+static int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N) {
+    if (!h || !sm || !X || N < 1) return GPIMHIP_E_BADARG;
+    FP64_ONLY(h);
+    if (sm->dim < 1 || sm->dim > GPIMHIP_MAX_DIM || sm->mixtures < 1 || sm->mixtures > GPIMHIP_SM_MAX_MIXTURES) {
+        gpim_set_error("the spectral-mixture kernel takes 1 .. 4 dimensions and 1 .. 16 mixtures");
+        return GPIMHIP_E_BADARG;
+    }
+    if (h->refl.mask) {
+        gpim_set_error("the spectral-mixture kernel needs a handle without reflection blocks (gpimhip_set_reflection(h, 0, ...))");
+        return GPIMHIP_E_BADARG;
+    }
+    return GPIMHIP_OK;
+}
+static int sm_begin(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, SmWs** w) {
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = 1;
+    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(ws_ensure_padded(h, N));
+    const int64_t nb = h->np / NB;
+    return sm_ws(h, sm, h->np, 0, nb * (nb + 1) / 2, w);
+}
+// u -> parameters, r = y - c, phases; K -> L^-1; z = L^-1 r, alpha = K^-1 r
+static int sm_factor(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* y, int64_t N,
+                     const double* u) {
+    const int64_t np = h->np, ld = h->ld;
+    GP_TRY(launch_sm_setup(h, sm, u, X, N, np, w->csx, y, h->ypad, w->st, h->theta));
+    { StageTimer t(h, 4); GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, np, nullptr, N, nullptr, np, w->st, h->A, ld, np, np, 1, 1)); }
+    GP_TRY(launch_potrf_inv(h, h->A, h->Tm, np, ld, h->info, rag_of(N, np)));
+    return solve_vectors(h, nullptr, X, 0, N, false);
+}
+// loss and gradient at u (fit mode: and one Adam step); every launch reads its iteration-dependent values from the device
+static int sm_iter(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* y, int64_t N, double* u,
+                   int do_adam, double* loss_out, double* grad_out, FinalizeIterS fi) {
+    const int64_t np = h->np;
+    GP_TRY(sm_factor(h, sm, w, X, y, N, u));
+    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
+    { StageTimer t(h, 5); GP_TRY(launch_sm_grad(h, sm, h->B, h->ld, X, N, w->csx, np, h->alpha, w->st, w->part, w->sums)); }
+    AdamStep st;
+    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi);
+}
+
+extern "C" {
+
+int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* Z, int64_t M,
+                    const double* u, double* out, int64_t ld) {
+    GP_TRY(sm_check(h, sm, X, N));
+    const bool sym = (Z == nullptr);
+    const int64_t Mv = sym ? N : M;
+    if (!u || !out || Mv < 1 || ld < Mv) return GPIMHIP_E_BADARG;
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = 1;
+    const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
+    SmWs* w = nullptr;
+    GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
+    GP_TRY(ws_ensure_predict(h, rp, cp));
+    const int64_t kld = h->ks_cols + 16;
+    GP_TRY(launch_sm_setup(h, sm, u, X, N, rp, w->csx, nullptr, nullptr, w->st, nullptr));
+    if (!sym) GP_TRY(launch_sm_setup(h, sm, u, Z, M, cp, w->csz, nullptr, nullptr, nullptr, nullptr));
+    GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, rp, Z, Mv, w->csz, cp, w->st, h->Ks, kld, rp, cp, sym ? 1 : 0, 0));
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), h->Ks, (size_t)kld * sizeof(double),
+                             (size_t)Mv * sizeof(double), (size_t)N, hipMemcpyDeviceToDevice, h->stream));
+    return GPIMHIP_OK;
+}
+
+int gpimhip_sm_nll_grad(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
+                        const double* u, double* loss_out, double* grad_out) {
+    GP_TRY(sm_check(h, sm, X, N));
+    if (!y || !u) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin(h, sm, N, &w));
+    GP_TRY(sm_iter(h, sm, w, X, y, N, const_cast<double*>(u), 0, loss_out, grad_out,
+                   FinalizeIterS{nullptr, nullptr, 0, nullptr, nullptr}));
+    return finish_and_check(h);
+}
+
+int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N, double* u_inout,
+                   double lr, int32_t T, double* hist_out, double* loss_out) {
+    GP_TRY(sm_check(h, sm, X, N));
+    if (!y || !u_inout || T < 0) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin(h, sm, N, &w));
+    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
+    h->fit_completed = T;
+    if (T == 0) return finish_and_check(h);
+    GP_TRY(upload_bc_table(h, lr, T));
+    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * SM_MAXP * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
+    const FinalizeIterS fi{w->iter, h->bc, T, hist_out, loss_out};
+    // one iteration captured into a hipGraph and replayed, as fit_impl does
+    const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
+    const bool use_graph = T >= 8 && !h->timing && !getenv("GPIMHIP_NO_GRAPH") && npanel < EAGER_MIN_PANELS &&
+                           ensure_capture_stream(h);
+    if (use_graph) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipStream_t main_s = h->stream;
+        h->stream = h->capture_stream;
+        capture_lock(h);
+        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
+        int rc = GPIMHIP_OK;
+        if (e == hipSuccess) {
+            h->capturing = true;
+            rc = sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi);
+            h->capturing = false;
+            e = hipStreamEndCapture(h->capture_stream, &graph);
+        }
+        capture_unlock(h);
+        h->stream = main_s;
+        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        const bool inst_ok = e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (inst_ok) {
+            RunAhead ra(h, h->np);
+            hipError_t le = hipSuccess;
+            for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, main_s);
+            rc = finish_and_check(h);
+            (void)hipGraphExecDestroy(exec);
+            (void)hipGraphDestroy(graph);
+            HIP_TRY(le);
+            return rc;
+        }
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();                        // capture unavailable: plain launches below
+    }
+    RunAhead ra(h, h->np);
+    for (int t = 0; t < T && !ra.stop(t); ++t) GP_TRY(sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi));
+    return finish_and_check(h);
+}
+
+int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
+                       const double* u, const double* Xs, int64_t M, double* mean_out, double* var_out) {
+    GP_TRY(sm_check(h, sm, X, N));
+    if (!y || !u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin(h, sm, N, &w));
+    const int64_t np = h->np;
+    const int nb = (int)(np / NB);
+    GP_TRY(sm_factor(h, sm, w, X, y, N, u));
+    // chunks of test points: the K* slab stays <= ~1 GiB (predict_cols)
+    int64_t mc = pad_to(M, NB);
+    mc = std::min(mc, std::max<int64_t>(NB, ((int64_t)1 << 27) / np / NB * NB));
+    GP_TRY(ws_ensure_predict(h, np, mc));
+    GP_TRY(sm_ws(h, sm, np, mc, (int64_t)nb * (nb + 1) / 2, &w));
+    const int64_t mcap = h->ks_cols, kld = mcap + 16;
+    for (int64_t m0 = 0; m0 < M; m0 += mc) {
+        const int64_t cnt = std::min(mc, M - m0);
+        const int64_t cpad = pad_to(cnt, NB);
+        const double* Zc = Xs + m0 * sm->dim;
+        GP_TRY(launch_sm_setup(h, sm, u, Zc, cnt, cpad, w->csz, nullptr, nullptr, nullptr, nullptr));
+        GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, np, Zc, cnt, w->csz, cpad, w->st, h->Ks, kld, np, cpad, 0, 0));
+        GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
+        GP_TRY(launch_sm_mean(h, h->mean_tmp, cnt, w->st, mean_out + m0));
+        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
+        g.sB = np * kld;
+        g.colpart = h->colpart;
+        g.ld_colpart = mcap;
+        g.sColpart = (int64_t)nb * mcap;
+        g.ntiles = (int)h->pred_ntiles;       // a ragged last chunk still sweeps all column tiles of the slab
+        g.chunk = deal_chunk(g.ntiles);
+        g.rag = rag_of(N, np);
+        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
+        GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
+    }
     return finish_and_check(h);
 }
 

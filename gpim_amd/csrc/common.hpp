@@ -165,7 +165,7 @@ struct gpimhip_ctx {
     DistPlan dplan;
     // optional stage timing (bench.py): HIP event pairs on the handle's stream
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6];
     // Adam bias-correction table for the fused small-N trainer
     double* bc = nullptr;
     int64_t bc_cap = 0;
@@ -186,6 +186,8 @@ struct gpimhip_ctx {
     void* kron = nullptr;
     // multi-output GP workspace, owned by api.hip (VgpWs); released by vgp_release()
     void* vgp = nullptr;
+    // spectral-mixture workspace, owned by api.hip (SmWs); released by sm_release()
+    void* sm = nullptr;
     double* refine = nullptr; int64_t refine_cap = 0;    // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
 };

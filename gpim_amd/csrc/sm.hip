@@ -1,0 +1,520 @@
+// sm.hip -- the spectral-mixture (SM) kernel of the reference's skreconstructor(kernel='Spectral') (gpim/gpreg/skgpr.py,
+// GPyTorch SpectralMixtureKernel) on the exact-GP engine: the factorisation, K^-1, the solves and the variance product are
+// the engine's own (api.hip: sm_iter); this file has the covariance-specific pieces.
+//
+//   k_q(tau) = E_q C_q,  E_q = exp(-2 pi^2 sum_d tau_d^2 s_qd^2),  C_q = prod_d cos(2 pi tau_d m_qd),  K = sum_q w_q k_q + noise I
+//
+//   sm_setup_kernel     raw u -> w, m, s, noise (softplus) and their derivatives; r = y - c into the padded right-hand side;
+//                       the per-point phases cos / sin(2 pi m_qd x_d), O(N Q d) -- the entries then need no cos / sin of
+//                       their own: cos(2 pi tau m) = cos a cos b + sin a sin b (angle addition, 2 FMAs)
+//   sm_kmat_kernel      K(X, X) lower tiles (noise on the diagonal, identity padding) or K(X, Z); one 128 x 128 tile per
+//                       workgroup, 16 entries per thread, mixtures one after another through LDS
+//   sm_grad_kernel      the contraction of G = K^-1 - alpha alpha^T against dK/dw_q, dK/dm_qd, dK/ds_qd (and tr G for the
+//                       noise): per lower tile one fixed-shape record of Q (2 D + 1) + 1 partial sums
+//   sm_sum_kernel       the records added up per component (one workgroup per component, fixed tree)
+//   sm_finalize_kernel  loss, gradient (c through sum alpha), chain rule, Adam step, history row
+// Every reduction has a fixed shape: results are bit-reproducible run to run.  Nothing is combined across workgroups inside
+// a launch.
+#include "kfun.hpp"
+#include "sm.hpp"
+
+#define SM_TWO_PI 6.283185307179586
+#define SM_PI2 9.869604401089358          // pi^2
+#define SM_NREC (SM_MAXQ * (2 * GPIMHIP_MAX_DIM + 1) + 1)
+// tile kernels: 1024 threads per 128 x 128 tile, thread (ty, tx) = (tid / 16, tid % 16) owns rows ty + 64 rr (rr < 2) and
+// columns tx * 2 + 32 h + e (h < 4, e < 2): 16 entries, so that the per-entry registers stay well inside the budget
+#define SM_RPT 2
+#define SM_EPT (SM_RPT * 8)
+
+__device__ __forceinline__ double sm_softplus(double x) { return x > 20.0 ? x : log1p(exp(x)); }
+__device__ __forceinline__ double sm_dsoftplus(double x) { return x > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-x)); }
+
+__device__ __forceinline__ double sm_wave_sum(double v) {
+    v += __shfl_xor(v, 32);
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 8);
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    return v;
+}
+
+// sum over the 256 threads of a workgroup in a fixed tree; red: 256 doubles of LDS; the result is valid in every thread
+__device__ __forceinline__ double sm_block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    if (tid < 64) {
+        double x = (red[tid] + red[tid + 128]) + (red[tid + 64] + red[tid + 192]);
+        x = sm_wave_sum(x);
+        if (tid == 0) red[0] = x;
+    }
+    __syncthreads();
+    return red[0];
+}
+
+__device__ __forceinline__ void sm_lower_tile(int q, int& i, int& j) {
+    i = (int)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
+    while ((int64_t)i * (i + 1) / 2 > q) --i;
+    while ((int64_t)(i + 1) * (i + 2) / 2 <= q) ++i;
+    j = q - (int)((int64_t)i * (i + 1) / 2);
+}
+
+// ------------------------------------------------------------------------------------------
+// setup: grid over the ldc phase slots; block 0 also writes the constrained parameters
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sm_setup_kernel(gpimhip_sm_t sm, const double* __restrict__ u, const double* __restrict__ P,
+                                                       int64_t n, int64_t ldc, double* __restrict__ cs,
+                                                       const double* __restrict__ y, double* __restrict__ ypad,
+                                                       SmDev* __restrict__ st, ThetaDev* __restrict__ theta) {
+    const SmLayout L = sm_layout(sm);
+    const int dim = sm.dim;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < ldc) {
+        if (y) ypad[i] = (i < n) ? y[i] - u[0] : 0.0;
+        for (int q = 0; q < L.Q; ++q)
+            for (int d = 0; d < dim; ++d) {
+                const double tpm = SM_TWO_PI * sm_softplus(u[L.m + q * L.D + (sm.ard ? d : 0)]);
+                double sv = 0.0, cv = 0.0;
+                if (i < n) sincos(tpm * P[i * dim + d], &sv, &cv);
+                cs[((int64_t)(q * dim + d) * 2 + 0) * ldc + i] = cv;
+                cs[((int64_t)(q * dim + d) * 2 + 1) * ldc + i] = sv;
+            }
+    }
+    if (blockIdx.x != 0 || threadIdx.x != 0 || !st) return;
+    double sw = 0.0;
+    st->c = u[0];
+    for (int q = 0; q < L.Q; ++q) {
+        st->w[q] = sm_softplus(u[L.w + q]);
+        st->dw[q] = sm_dsoftplus(u[L.w + q]);
+        sw += st->w[q];
+        for (int k = 0; k < L.D; ++k) {
+            const int j = q * L.D + k;
+            st->m[j] = sm_softplus(u[L.m + j]);
+            st->dm[j] = sm_dsoftplus(u[L.m + j]);
+            st->s[j] = sm_softplus(u[L.s + j]);
+            st->ds[j] = sm_dsoftplus(u[L.s + j]);
+        }
+        for (int d = 0; d < GPIMHIP_MAX_DIM; ++d) {
+            const double sv = (d < dim) ? st->s[q * L.D + (sm.ard ? d : 0)] : 0.0;
+            st->kap[q * GPIMHIP_MAX_DIM + d] = 2.0 * SM_PI2 * sv * sv;
+        }
+    }
+    st->noise = 1e-4 + sm_softplus(u[L.noise]);
+    st->dnoise = sm_dsoftplus(u[L.noise]);
+    if (theta) {       // what the engine's variance epilogue reads (predict_var_kernel): prior variance and noise
+        ThetaDev th;
+        th.var = sw;
+        for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+            th.ls[k] = 1.0;
+            th.inv_ls[k] = 1.0;
+            th.dls_du[k] = 0.0;
+        }
+        th.noise = st->noise;
+        th.alpha = 1.0;
+        th.diag_add = st->noise;
+        th.dvar_du = th.dnoise_du = th.dalpha_du = 0.0;
+        *theta = th;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// covariance build.  Tile (ci, cj): rows from X (ci), columns from Z (cj); threads 0 .. 255 stage the tile's 128 + 128
+// points, every thread's 16 entries are stored as 16-byte pairs like the engine's kmat_kernel.
+// ------------------------------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(1024) void sm_kmat_kernel(const double* __restrict__ X, int64_t N, const double* __restrict__ csx,
+                                                      int64_t ldx, const double* __restrict__ Z, int64_t M,
+                                                      const double* __restrict__ csz, int64_t ldz, int Q,
+                                                      const SmDev* __restrict__ st, double* __restrict__ out, int64_t ld, int ntc,
+                                                      int sym, int lower_only) {
+    __shared__ double xr[128][DIM], xc[128][DIM];
+    __shared__ double pr[128][2 * DIM], pc[128][2 * DIM];       // cos, sin per dimension of the current mixture
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    int ci, cj;
+    if (lower_only) sm_lower_tile(blockIdx.x, ci, cj);
+    else { ci = blockIdx.x / ntc; cj = blockIdx.x % ntc; }
+    const bool isrow = tid < 128;
+    const int loc = tid & 127;
+    const int64_t g = (int64_t)(isrow ? ci : cj) * 128 + loc;
+    const int64_t lim = isrow ? N : M;
+    const double* src = isrow ? X : Z;
+    const double* csrc = isrow ? csx : csz;
+    const int64_t lds_ = isrow ? ldx : ldz;
+    const bool stager = tid < 256;
+    if (stager)
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) (isrow ? xr : xc)[loc][d] = (g < lim) ? src[g * DIM + d] : 0.0;
+    double acc[SM_EPT];
+#pragma unroll
+    for (int e = 0; e < SM_EPT; ++e) acc[e] = 0.0;
+    for (int q = 0; q < Q; ++q) {
+        __syncthreads();
+        if (stager)
+#pragma unroll
+            for (int k = 0; k < 2 * DIM; ++k) (isrow ? pr : pc)[loc][k] = (g < lim) ? csrc[((int64_t)q * 2 * DIM + k) * lds_ + g] : 0.0;
+        __syncthreads();
+        const double wq = st->w[q];
+        double kap[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) kap[d] = st->kap[q * GPIMHIP_MAX_DIM + d];
+#pragma unroll
+        for (int rr = 0; rr < SM_RPT; ++rr) {
+            const int r = ty + 64 * rr;
+            double a[DIM], ac[DIM], as[DIM];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) {
+                a[d] = xr[r][d];
+                ac[d] = pr[r][2 * d];
+                as[d] = pr[r][2 * d + 1];
+            }
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) {
+                const int c = tx * 2 + 32 * (cc >> 1) + (cc & 1);
+                double arg = 0.0, cp = 1.0;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) {
+                    const double t = a[d] - xc[c][d];
+                    arg = fma(t * t, kap[d], arg);
+                    cp *= fma(ac[d], pc[c][2 * d], as[d] * pc[c][2 * d + 1]);
+                }
+                acc[rr * 8 + cc] = fma(wq, cp * kf_exp_neg(-arg), acc[rr * 8 + cc]);
+                __builtin_amdgcn_sched_barrier(0);      // one entry at a time: bounded registers (no spills at DIM 4)
+            }
+        }
+    }
+    const double noise = st->noise;
+    const bool interior = (int64_t)ci * 128 + 128 <= N && (int64_t)cj * 128 + 128 <= M && !(sym && ci == cj);
+#pragma unroll
+    for (int rr = 0; rr < SM_RPT; ++rr) {
+        const int64_t gi = (int64_t)ci * 128 + ty + 64 * rr;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            double2 v;
+            v.x = acc[rr * 8 + 2 * h];
+            v.y = acc[rr * 8 + 2 * h + 1];
+            if (!interior) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int64_t gj = (int64_t)cj * 128 + tx * 2 + 32 * h + e;
+                    double& k = e ? v.y : v.x;
+                    if (gi >= N || gj >= M) k = (sym && gi == gj) ? 1.0 : 0.0;
+                    else if (sym && gi == gj) k += noise;
+                }
+            }
+            *reinterpret_cast<double2*>(out + gi * ld + (int64_t)cj * 128 + tx * 2 + 32 * h) = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// gradient contraction over the lower tiles of K^-1 (G = K^-1 - alpha alpha^T, off-diagonal entries counted twice):
+//   rec[q]                  += sum G E_q C_q                                   (d/dw_q = this)
+//   rec[Q + q D + k]        += sum G tau_d sin_qd E_q prod_{e != d} cos_qe     (d/dm_qk: times -2 pi w_q)
+//   rec[Q + Q D + q D + k]  += sum G tau_d^2 E_q C_q                           (d/ds_qk: times -4 pi^2 s_qk w_q)
+//   rec[Q (2 D + 1)]        += sum_i G_ii                                      (d/dnoise)
+// (isotropic, D = 1: the per-dimension terms are added into k = 0).  part: component-major, part[k * ntile + tile].
+// ------------------------------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(1024) void sm_grad_kernel(const double* __restrict__ Kinv, int64_t ld, const double* __restrict__ X,
+                                                      int64_t N, const double* __restrict__ csx, int64_t ldx,
+                                                      const double* __restrict__ alpha, int Q, int ard,
+                                                      const SmDev* __restrict__ st, double* __restrict__ part) {
+    __shared__ double xr[128][DIM], xc[128][DIM];
+    __shared__ double pr[128][2 * DIM], pc[128][2 * DIM];
+    __shared__ double al_r[128], al_c[128];
+    __shared__ double red[16][SM_NREC];
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, lane = tid & 63, wave = tid >> 6;
+    const int D = ard ? DIM : 1;
+    const int nrec = Q * (2 * D + 1) + 1;
+    const int ntile = gridDim.x;
+    int ci, cj;
+    sm_lower_tile(blockIdx.x, ci, cj);
+    const bool isrow = tid < 128;
+    const int loc = tid & 127;
+    const int64_t g = (int64_t)(isrow ? ci : cj) * 128 + loc;
+    const bool stager = tid < 256;
+    if (stager) {
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) (isrow ? xr : xc)[loc][d] = (g < N) ? X[g * DIM + d] : 0.0;
+        (isrow ? al_r : al_c)[loc] = (g < N) ? alpha[g] : 0.0;
+    }
+    __syncthreads();
+    // G of this thread's entries is re-read from K^-1 for every mixture (the tile stays in the caches between mixtures): no
+    // per-entry value lives across the mixture loop, so the registers are bounded by one entry pair's temporaries
+    const bool interior = ci > cj && (int64_t)ci * 128 + 128 <= N;
+    double sdiag = 0.0;
+    for (int q = 0; q < Q; ++q) {
+        __syncthreads();
+        if (stager)
+#pragma unroll
+            for (int k = 0; k < 2 * DIM; ++k) (isrow ? pr : pc)[loc][k] = (g < N) ? csx[((int64_t)q * 2 * DIM + k) * ldx + g] : 0.0;
+        __syncthreads();
+        double kap[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) kap[d] = st->kap[q * GPIMHIP_MAX_DIM + d];
+        double s0 = 0.0, sm_[DIM], ss[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sm_[d] = ss[d] = 0.0;
+#pragma unroll 1
+        for (int p = 0; p < SM_EPT / 2; ++p) {       // entry pairs: row ty + 64 (p / 4), columns tx * 2 + 32 (p % 4) + {0, 1}
+            const int r = ty + 64 * (p >> 2), c0 = tx * 2 + 32 * (p & 3);
+            const int64_t gi = (int64_t)ci * 128 + r;
+            const double2 kv = *reinterpret_cast<const double2*>(Kinv + gi * ld + (int64_t)cj * 128 + c0);
+            double a[DIM], ac[DIM], as[DIM];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) {
+                a[d] = xr[r][d];
+                ac[d] = pr[r][2 * d];
+                as[d] = pr[r][2 * d + 1];
+            }
+            const double alr = al_r[r];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int c = c0 + e;
+                const int64_t gj = (int64_t)cj * 128 + c;
+                const double gv = (e ? kv.y : kv.x) - alr * al_c[c];
+                double wg = 2.0 * gv;
+                if (!interior) {
+                    if (gi >= N || gj > gi) wg = 0.0;
+                    else if (gi == gj) {
+                        wg = gv;
+                        if (q == 0) sdiag += gv;
+                    }
+                }
+                double t[DIM], t2[DIM], co[DIM], si[DIM];
+                double arg = 0.0;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) {
+                    t[d] = a[d] - xc[c][d];
+                    t2[d] = t[d] * t[d];
+                    arg = fma(t2[d], kap[d], arg);
+                    const double bc = pc[c][2 * d], bs = pc[c][2 * d + 1];
+                    co[d] = fma(ac[d], bc, as[d] * bs);
+                    si[d] = fma(as[d], bc, -(ac[d] * bs));
+                }
+                const double aw = wg * kf_exp_neg(-arg);
+                // products of the other dimensions' cosines (prefix x suffix)
+                double oth[DIM], pre = 1.0;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) {
+                    oth[d] = pre;
+                    pre *= co[d];
+                }
+                double suf = 1.0;
+#pragma unroll
+                for (int d = DIM - 1; d >= 0; --d) {
+                    oth[d] *= suf;
+                    suf *= co[d];
+                }
+                const double kc = aw * pre;
+                s0 += kc;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) {
+                    ss[d] = fma(kc, t2[d], ss[d]);
+                    sm_[d] = fma(aw * t[d], si[d] * oth[d], sm_[d]);
+                }
+            }
+        }
+        if (!ard) {
+#pragma unroll
+            for (int d = 1; d < DIM; ++d) {
+                sm_[0] += sm_[d];
+                ss[0] += ss[d];
+            }
+        }
+        {
+            const double v = sm_wave_sum(s0);
+            if (lane == 0) red[wave][q] = v;
+        }
+        for (int k = 0; k < D; ++k) {        // (D is DIM or 1: the register index stays static after unrolling by the compiler)
+            double vm = 0.0, vs = 0.0;
+#pragma unroll
+            for (int d = 0; d < DIM; ++d)
+                if (d == k) { vm = sm_[d]; vs = ss[d]; }
+            vm = sm_wave_sum(vm);
+            vs = sm_wave_sum(vs);
+            if (lane == 0) {
+                red[wave][Q + q * D + k] = vm;
+                red[wave][Q + Q * D + q * D + k] = vs;
+            }
+        }
+    }
+    {
+        const double v = sm_wave_sum(sdiag);
+        if (lane == 0) red[wave][nrec - 1] = v;
+    }
+    __syncthreads();
+    for (int k = tid; k < nrec; k += 1024) {
+        double v[16];
+#pragma unroll
+        for (int w = 0; w < 16; ++w) v[w] = red[w][k];
+#pragma unroll
+        for (int s = 8; s > 0; s >>= 1)
+#pragma unroll
+            for (int w = 0; w < s; ++w) v[w] += v[w + s];
+        part[(int64_t)k * ntile + blockIdx.x] = v[0];
+    }
+}
+
+// sums[k] = sum over the tiles of component k: one workgroup per component
+__global__ __launch_bounds__(256) void sm_sum_kernel(const double* __restrict__ part, int ntile, double* __restrict__ sums) {
+    __shared__ double red[256];
+    const int k = blockIdx.x;
+    double v = 0.0;
+    for (int t = threadIdx.x; t < ntile; t += 256) v += part[(int64_t)k * ntile + t];
+    v = sm_block_sum(v, red);
+    if (threadIdx.x == 0) sums[k] = v;
+}
+
+// ------------------------------------------------------------------------------------------
+// finalize: one workgroup of 256 threads.  loss = (|L^-1 r|^2 / 2 + sum log L_ii) / N + log(2 pi) / 2
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sm_finalize_kernel(gpimhip_sm_t sm, int64_t N, int64_t np, int nb,
+                                                          const double* __restrict__ sums, const double* __restrict__ z,
+                                                          const double* __restrict__ logdet_part,
+                                                          const double* __restrict__ alpha, const SmDev* __restrict__ st,
+                                                          double* __restrict__ u, double* __restrict__ adam_m,
+                                                          double* __restrict__ adam_v, int do_adam, AdamStep ast,
+                                                          double* __restrict__ loss_out, double* __restrict__ grad_out,
+                                                          FinalizeIterS fi, int32_t* __restrict__ info) {
+    __shared__ double red[256];
+    __shared__ int skip;
+    const int tid = threadIdx.x;
+    const SmLayout L = sm_layout(sm);
+    double q2 = 0.0, lg = 0.0, sa = 0.0;
+    for (int64_t i = tid; i < np; i += 256) q2 = fma(z[i], z[i], q2);
+    for (int k = tid; k < nb; k += 256) lg += logdet_part[k];
+    for (int64_t i = tid; i < N; i += 256) sa += alpha[i];
+    q2 = sm_block_sum(q2, red);
+    lg = sm_block_sum(lg, red);
+    sa = sm_block_sum(sa, red);
+    int it = 0;
+    double* hist_row = nullptr;
+    if (fi.iter) {       // (every thread reads the counter here; thread 0 advances it after the last barrier below)
+        it = *fi.iter;
+        ast.lr_over_bc1 = fi.bc[it];
+        ast.bc2_sqrt = fi.bc[fi.T + it];
+        loss_out = fi.loss_base ? fi.loss_base + it : nullptr;
+        hist_row = fi.hist_base ? fi.hist_base + (int64_t)it * L.P : nullptr;
+        if (tid == 0) {
+            // a factorisation of this training loop failed: u, the Adam state and the history stay as the previous
+            // iteration left them (the reference raises inside the Cholesky there)
+            skip = *info != 0;
+            if (skip) atomicMin(info + 1, it);
+        }
+    } else if (tid == 0) {
+        skip = 0;
+    }
+    __syncthreads();
+    if (skip) return;
+    const double h2n = 0.5 / (double)N;
+    if (tid < L.P) {
+        const int p = tid;
+        double g;
+        if (p == 0) {
+            g = -sa / (double)N;
+        } else if (p < L.m) {
+            const int q = p - L.w;
+            g = h2n * sums[q] * st->dw[q];
+        } else if (p < L.s) {
+            const int j = p - L.m, q = j / L.D;
+            g = h2n * (-SM_TWO_PI * st->w[q]) * sums[L.Q + j] * st->dm[j];
+        } else if (p < L.noise) {
+            const int j = p - L.s, q = j / L.D;
+            g = h2n * (-4.0 * SM_PI2 * st->s[j] * st->w[q]) * sums[L.Q + L.Q * L.D + j] * st->ds[j];
+        } else {
+            g = h2n * sums[L.Q * (2 * L.D + 1)] * st->dnoise;
+        }
+        if (grad_out) grad_out[p] = g;
+        if (do_adam) {       // torch.optim.Adam, the expressions of theta.hpp: finalize_step_ws
+            double mm = adam_m[p], vv = adam_v[p];
+            mm = mm + (g - mm) * (1.0 - ast.beta1);
+            vv = vv * ast.beta2 + (1.0 - ast.beta2) * g * g;
+            const double denom = sqrt(vv) / ast.bc2_sqrt + ast.eps;
+            const double un = u[p] + (-ast.lr_over_bc1) * (mm / denom);
+            u[p] = un;
+            adam_m[p] = mm;
+            adam_v[p] = vv;
+            if (hist_row) hist_row[p] = (p == 0) ? un : (p == L.noise ? 1e-4 + sm_softplus(un) : sm_softplus(un));
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double loss = (0.5 * q2 + lg) / (double)N + 0.5 * 1.8378770664093453;
+    if (loss_out) *loss_out = loss;
+    if (fi.iter) *fi.iter = it + 1;
+}
+
+__global__ void sm_mean_kernel(const double* __restrict__ mtmp, int64_t n, const SmDev* __restrict__ st,
+                               double* __restrict__ mean_out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) mean_out[j] = mtmp[j] + st->c;
+}
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+int launch_sm_setup(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, const double* P, int64_t n, int64_t ldc,
+                    double* cs, const double* y, double* ypad, SmDev* st, ThetaDev* theta) {
+    hipLaunchKernelGGL(sm_setup_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, h->stream, *sm, u, P, n, ldc, cs, y,
+                       ypad, st, theta);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_kmat(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* csx, int64_t ldx,
+                   const double* Z, int64_t M, const double* csz, int64_t ldz, const SmDev* st, double* out, int64_t ld,
+                   int64_t rows_pad, int64_t cols_pad, int sym, int lower_only) {
+    const int ntr = (int)(rows_pad / 128), ntc = (int)(cols_pad / 128);
+    const int64_t nblk = lower_only ? (int64_t)ntr * (ntr + 1) / 2 : (int64_t)ntr * ntc;
+    if (nblk <= 0) return GPIMHIP_OK;
+    if (sym) { Z = X; M = N; csz = csx; ldz = ldx; }
+#define SMK(DIM) hipLaunchKernelGGL(sm_kmat_kernel<DIM>, dim3((unsigned)nblk), dim3(1024), 0, h->stream, X, N, csx, ldx, Z, M, csz, \
+                                    ldz, sm->mixtures, st, out, ld, ntc, sym, lower_only)
+    switch (sm->dim) {
+        case 1: SMK(1); break;
+        case 2: SMK(2); break;
+        case 3: SMK(3); break;
+        default: SMK(4); break;
+    }
+#undef SMK
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_grad(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, int64_t ld, const double* X, int64_t N,
+                   const double* csx, int64_t ldx, const double* alpha, const SmDev* st, double* part, double* sums) {
+    const int nb = (int)(h->np / NB), ntile = nb * (nb + 1) / 2;
+    const SmLayout L = sm_layout(*sm);
+    const int nrec = L.Q * (2 * L.D + 1) + 1;
+#define SMG(DIM) hipLaunchKernelGGL(sm_grad_kernel<DIM>, dim3((unsigned)ntile), dim3(1024), 0, h->stream, Kinv, ld, X, N, csx, ldx, \
+                                    alpha, sm->mixtures, sm->ard, st, part)
+    switch (sm->dim) {
+        case 1: SMG(1); break;
+        case 2: SMG(2); break;
+        case 3: SMG(3); break;
+        default: SMG(4); break;
+    }
+#undef SMG
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_sum_kernel, dim3((unsigned)nrec), dim3(256), 0, h->stream, part, ntile, sums);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const double* sums, const SmDev* st, double* u,
+                       double* adam_m, double* adam_v, int do_adam, AdamStep ast, double* loss_out, double* grad_out,
+                       FinalizeIterS fi) {
+    hipLaunchKernelGGL(sm_finalize_kernel, dim3(1), dim3(256), 0, h->stream, *sm, N, h->np, (int)(h->np / NB), sums, h->z,
+                       h->logdet_part, h->alpha, st, u, adam_m, adam_v, do_adam, ast, loss_out, grad_out, fi, h->info);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_mean(gpimhip_ctx* h, const double* mtmp, int64_t n, const SmDev* st, double* mean_out) {
+    hipLaunchKernelGGL(sm_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, mtmp, n, st, mean_out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}

@@ -1,0 +1,50 @@
+// sm.hpp -- shared declarations of the spectral-mixture kernel (sm.hip kernels, api.hip drivers).
+#pragma once
+#include "common.hpp"
+
+#define SM_MAXQ GPIMHIP_SM_MAX_MIXTURES
+#define SM_MAXP (2 + SM_MAXQ * (2 * GPIMHIP_MAX_DIM + 1))
+
+// offsets of the raw vector u = [c | r_w (Q) | r_m (Q x D) | r_s (Q x D) | r_n]
+struct SmLayout { int Q, D, w, m, s, noise, P; };
+__host__ __device__ inline SmLayout sm_layout(const gpimhip_sm_t& sm) {
+    SmLayout L;
+    L.Q = sm.mixtures;
+    L.D = sm.ard ? sm.dim : 1;
+    L.w = 1;
+    L.m = 1 + L.Q;
+    L.s = L.m + L.Q * L.D;
+    L.noise = L.s + L.Q * L.D;
+    L.P = L.noise + 1;
+    return L;
+}
+
+// constrained parameters at the current u and their softplus derivatives (sm_setup_kernel, device memory)
+struct SmDev {
+    double c, noise, dnoise;
+    double w[SM_MAXQ], dw[SM_MAXQ];
+    double m[SM_MAXQ * GPIMHIP_MAX_DIM], dm[SM_MAXQ * GPIMHIP_MAX_DIM];
+    double s[SM_MAXQ * GPIMHIP_MAX_DIM], ds[SM_MAXQ * GPIMHIP_MAX_DIM];
+    double kap[SM_MAXQ * GPIMHIP_MAX_DIM];      // 2 pi^2 s^2, per data dimension (isotropic: replicated)
+};
+
+struct FinalizeIterS {
+    int32_t* iter;              // device counter (null: one evaluation)
+    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
+    int32_t T;
+    double* hist_base;          // T x P or null
+    double* loss_base;          // T or null
+};
+
+// phases: cs[((q * dim + d) * 2 + {0: cos, 1: sin}) * ldc + i] of 2 pi m_qd x_id, zero for n <= i < ldc
+int launch_sm_setup(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, const double* P, int64_t n, int64_t ldc,
+                    double* cs, const double* y, double* ypad, SmDev* st, ThetaDev* theta);
+int launch_sm_kmat(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* csx, int64_t ldx,
+                   const double* Z, int64_t M, const double* csz, int64_t ldz, const SmDev* st, double* out, int64_t ld,
+                   int64_t rows_pad, int64_t cols_pad, int sym, int lower_only);
+int launch_sm_grad(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, int64_t ld, const double* X, int64_t N,
+                   const double* csx, int64_t ldx, const double* alpha, const SmDev* st, double* part, double* sums);
+int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const double* sums, const SmDev* st, double* u,
+                       double* adam_m, double* adam_v, int do_adam, AdamStep ast, double* loss_out, double* grad_out,
+                       FinalizeIterS fi);
+int launch_sm_mean(gpimhip_ctx* h, const double* mtmp, int64_t n, const SmDev* st, double* mean_out);

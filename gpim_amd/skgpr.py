@@ -12,7 +12,8 @@ this engine does it EXACTLY -- for the RBF kernel through the Kronecker factoris
 gprutils.reflection_blocks + csrc/engine.hip: kmat_refl_kernel) -- with the model and parameterisation of
 ``gpim_amd.reconstructor`` (zero mean, Uniform priors on variance and lengthscales).  Same constructor shape and return values as the reference class;
 numbers are those of ``reconstructor(..., structured=True)``, i.e. of the exact GP -- not bit-comparable
-with an SKI run.
+with an SKI run.  ``kernel='Spectral'`` (GPyTorch's spectral-mixture kernel, for which the reference turns SKI off) returns
+the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse images included.
 """
 from .gpr import reconstructor
 
@@ -21,12 +22,18 @@ class skreconstructor(reconstructor):
     """``skreconstructor(X, y, Xtest=None, kernel='RBF', lengthscale=None, ski=True, learning_rate=.1,
     iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs)`` -- argument order and defaults of
     gpim/gpreg/skgpr.py:79-91.  ``ski``, ``grid_points_ratio``, ``max_root``, ``num_batches`` are accepted
-    and ignored (nothing is interpolated or batched); ``kernel``: 'RBF', 'Matern52', 'RationalQuadratic' ('Spectral' is out of
-    scope)."""
+    and ignored (nothing is interpolated or batched), and so is ``sparse``; ``kernel``: 'RBF', 'Matern52', 'RationalQuadratic',
+    or 'Spectral' (then the object is a ``gpim_amd.smgpr.smreconstructor``)."""
+
+    def __new__(cls, X, y, Xtest=None, kernel='RBF', *args, **kwargs):
+        if kernel == 'Spectral':
+            from .smgpr import smreconstructor
+            return smreconstructor(X, y, Xtest, kernel, *args, **kwargs)
+        return super().__new__(cls)
 
     def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, ski=True, learning_rate=.1,
                  iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
-        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures"):
+        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures", "sparse"):
             kwargs.pop(k, None)
         super().__init__(X, y, Xtest, kernel=kernel, lengthscale=lengthscale, sparse=False, indpoints=None,
                          learning_rate=learning_rate, iterations=iterations, use_gpu=use_gpu, verbose=verbose,

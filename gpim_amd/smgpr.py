@@ -1,0 +1,227 @@
+"""
+smgpr.py -- the spectral-mixture kernel of ``skreconstructor(kernel='Spectral')``: an exact GP on the observed points.
+
+Takes the ROLE of the reference's Spectral branch of gpim/gpreg/skgpr.py (lines 122-164, 209-220, 431-434: no SKI, GPyTorch's
+SpectralMixtureKernel, ConstantMean and GaussianLikelihood, initialised by ``initialize_from_data``).  The covariance, the
+gradient contraction and the Adam step are HIP launches of the MI355X engine (csrc/sm.hip; include/gpimhip.h:
+gpimhip_fit_sm / gpimhip_predict_sm); the factorisation, K^-1 and the solves are the engine's exact-GP path.
+
+Model (float64), Q mixtures, D = d or 1 (isotropic), tau = x_i - x_j:
+    k_q(tau) = exp(-2 pi^2 sum_d tau_d^2 s_qd^2) prod_d cos(2 pi tau_d m_qd),   K = sum_q w_q k_q + noise I
+    w, m, s = softplus(raw), noise = 1e-4 + softplus(r_n), constant mean c
+    u = [c | r_w (Q) | r_m (Q x D) | r_s (Q x D) | r_n]
+
+Readings and deliberate differences, in one place:
+  * GPyTorch is not available to check these readings against; they follow GPyTorch's documented semantics.
+  * Initialisation (``initial_raw``) restates ``SpectralMixtureKernel.initialize_from_data(X, y)`` in float64 on the CPU
+    generator right after ``torch.manual_seed(seed)`` -- the reference's first random draws: per dimension max_dist = the
+    range of X and min_dist = the smallest nonzero gap between sorted coordinates; s = 1 / |randn(Q, 1, D) max_dist|,
+    m = rand(Q, 1, D) 0.5 / min_dist, w = std(y) / Q (unbiased); raw values log(expm1(x)); c = 0, r_n = 0.  Isotropic
+    (D = 1): the largest range and the smallest gap over all dimensions (GPyTorch does not define that case cleanly).
+    With ``use_gpu`` the reference draws on the CUDA default tensor type, i.e. from another generator: its numbers can
+    differ from these.
+  * For N > 800 GPyTorch switches to CG / Lanczos for the solves and log-determinant, and ``fast_pred_var`` approximates
+    the predictive variance.  This engine is exact in both.
+  * ``num_batches``, ``max_root`` / ``maxroot``, ``grid_points_ratio``, ``ski`` and ``sparse`` are accepted and ignored;
+    ``precision='single'`` raises NotImplementedError.
+"""
+import ctypes
+import time
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import gprutils
+
+_F64 = torch.float64
+
+
+def _softplus(x):
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x > 20.0, x, np.log1p(np.exp(np.minimum(x, 20.0))))
+
+
+def raw_layout(Q, D):
+    """Offsets of u = [c | r_w (Q) | r_m (Q x D) | r_s (Q x D) | r_n] (include/gpimhip.h): dict of slices, and P."""
+    o = {"c": slice(0, 1), "w": slice(1, 1 + Q), "m": slice(1 + Q, 1 + Q + Q * D),
+         "s": slice(1 + Q + Q * D, 1 + Q + 2 * Q * D), "noise": slice(1 + Q + 2 * Q * D, 2 + Q + 2 * Q * D)}
+    return o, 2 + Q * (2 * D + 1)
+
+
+def constrained(u, Q, D):
+    """(c, w (Q,), m (Q, D), s (Q, D), noise) from the raw vector u (numpy float64)."""
+    u = np.asarray(u, dtype=np.float64)
+    o, _ = raw_layout(Q, D)
+    return (float(u[0]), _softplus(u[o["w"]]), _softplus(u[o["m"]]).reshape(Q, D), _softplus(u[o["s"]]).reshape(Q, D),
+            float(1e-4 + _softplus(u[o["noise"]])[0]))
+
+
+def initial_raw(X, y, Q=4, isotropic=False, seed=0):
+    """GPyTorch's SpectralMixtureKernel.initialize_from_data(X, y) in float64 after torch.manual_seed(seed) (module
+    docstring); X: (N, d) points, y: (N,) targets.  Returns the raw vector u (numpy float64, P entries)."""
+    X = torch.as_tensor(np.asarray(X, dtype=np.float64))
+    y = torch.as_tensor(np.asarray(y, dtype=np.float64)).reshape(-1)
+    d = X.shape[1]
+    D = 1 if isotropic else d
+    xs = X.sort(dim=0)[0]
+    max_dist = xs[-1] - xs[0]
+    gaps = xs[1:] - xs[:-1]
+    min_dist = torch.stack([gaps[:, k][gaps[:, k] != 0].min() for k in range(d)])
+    if isotropic:
+        max_dist, min_dist = max_dist.max().reshape(1), min_dist.min().reshape(1)
+    torch.manual_seed(seed)
+    scales = torch.randn(Q, 1, D, dtype=_F64).mul(max_dist).abs().reciprocal()
+    means = torch.rand(Q, 1, D, dtype=_F64).mul(0.5).div(min_dist)
+    weights = y.std().div(Q).expand(Q)
+
+    def inv_softplus(v):
+        return torch.log(torch.expm1(v))
+
+    _, P = raw_layout(Q, D)
+    u = torch.zeros(P, dtype=_F64)
+    o, _ = raw_layout(Q, D)
+    u[o["w"]] = inv_softplus(weights)
+    u[o["m"]] = inv_softplus(means).reshape(-1)
+    u[o["s"]] = inv_softplus(scales).reshape(-1)
+    return u.numpy()
+
+
+class smreconstructor:
+    """``skreconstructor(X, y, Xtest, kernel='Spectral', ...)`` -- argument order and defaults of gpim/gpreg/skgpr.py:79-91.
+    X: (c, *dims) grid coordinates (NaN rows dropped together with the NaN entries of y: sparse images are fine);
+    ``n_mixtures`` (default 4) and ``isotropic`` as in the reference.  ``lengthscale`` is not used by this kernel."""
+
+    def __init__(self, X, y, Xtest=None, kernel='Spectral', lengthscale=None, ski=True, learning_rate=.1,
+                 iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
+        self.precision = kwargs.get("precision", "double")
+        if self.precision == "single":
+            raise NotImplementedError("skreconstructor(kernel='Spectral'): precision='single' is not implemented by the "
+                                      "MI355X engine (the spectral-mixture path runs in double precision)")
+        self._handle = _lib.Handle()
+        self._dev = self._handle.device
+        self.fulldims = Xtest.shape[1:] if Xtest is not None else X.shape[1:]
+        Xt, yt = gprutils.prepare_training_data(X, y)
+        if Xt.shape[0] != yt.shape[0]:
+            raise ValueError("skreconstructor: %d input points but %d observations (NaN patterns of X and y differ)"
+                             % (Xt.shape[0], yt.shape[0]))
+        self.X, self.y = Xt, yt
+        self.Xtest = gprutils.prepare_test_data(Xtest) if Xtest is not None else None
+        d = int(Xt.shape[1])
+        Q = kwargs.get("n_mixtures") or 4
+        if not 1 <= Q <= _lib.SM_MAX_MIXTURES:
+            raise ValueError("skreconstructor: n_mixtures must be 1 .. %d (got %r)" % (_lib.SM_MAX_MIXTURES, Q))
+        self.isotropic = bool(kwargs.get("isotropic"))
+        self.num_mixtures, self._D = int(Q), 1 if self.isotropic else d
+        sm = _lib.SmStruct()
+        sm.dim, sm.mixtures, sm.ard = d, self.num_mixtures, 0 if self.isotropic else 1
+        self._sstruct = sm
+        u = initial_raw(Xt.numpy(), yt.numpy(), self.num_mixtures, self.isotropic, seed)
+        self._u = torch.from_numpy(u).to(self._dev)
+        self._Xd = self.X.to(self._dev, _F64).contiguous()
+        self._yd = self.y.to(self._dev, _F64).contiguous()
+        self.iterations = iterations
+        self.learning_rate = learning_rate
+        self.scales, self.means, self.weights, self.noise_all = [], [], [], []
+        self.loss_all = []
+        self.hyperparams = {"scales": self.scales, "means": self.means, "weights": self.weights,
+                            "noise": self.noise_all, "maxdim": max(self.fulldims)}
+        self.verbose = verbose
+
+    # ------------------------------------------------------------------ parameters
+    def _params(self):
+        return constrained(self._u.cpu().numpy(), self.num_mixtures, self._D)
+
+    def nll_grad(self, u=None):
+        """Loss and gradient at the raw vector u (default: the current one) -- the engine's evaluation, for checks."""
+        u = self._u if u is None else torch.as_tensor(np.asarray(u, dtype=np.float64)).to(self._dev).contiguous()
+        loss = torch.empty(1, dtype=_F64, device=self._dev)
+        grad = torch.empty(u.numel(), dtype=_F64, device=self._dev)
+        _lib.check(self._handle.lib.gpimhip_sm_nll_grad(
+            self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
+            _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
+        return float(loss.item()), grad.cpu().numpy()
+
+    # ------------------------------------------------------------------ training
+    def train(self, **kwargs):
+        """Adam on the negative log marginal likelihood (skgpr.py:175-220); a fresh optimiser state per call."""
+        if kwargs.get("learning_rate") is not None:
+            self.learning_rate = kwargs.get("learning_rate")
+        if kwargs.get("iterations") is not None:
+            self.iterations = kwargs.get("iterations")
+        if kwargs.get("verbose") is not None:
+            self.verbose = kwargs.get("verbose")
+        T = int(self.iterations)
+        Q, D = self.num_mixtures, self._D
+        o, P = raw_layout(Q, D)
+        if self.verbose:
+            print('Model training...')
+        start_time = time.time()
+        hist = torch.empty((max(T, 1), P), dtype=_F64, device=self._dev)
+        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
+        rc = self._handle.lib.gpimhip_fit_sm(
+            self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
+            _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist), _lib.ptr(loss))
+        failed = rc == _lib.E_NOT_PD
+        if failed:
+            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
+        else:
+            _lib.check(rc)
+        hist_h, loss_h = hist[:T].cpu().numpy(), loss[:T].cpu().numpy()
+        dt = time.time() - start_time
+        for i in range(T):
+            row = hist_h[i]
+            self.weights.append(row[o["w"]].copy())
+            self.scales.append((1.0 / np.sqrt(row[o["s"]])).reshape(Q, 1, D))
+            self.means.append((1.0 / row[o["m"]]).reshape(Q, 1, D))
+            self.noise_all.append(float(row[o["noise"]][0]))
+            self.loss_all.append(float(loss_h[i]))
+            if self.verbose == 2 and (i % 10 == 0 or i == T - 1):
+                print('iter: {} ...'.format(i), 'loss: {} ...'.format(np.around(loss_h[i], 4)),
+                      'noise: {} ...'.format(np.around(self.noise_all[-1], 7)))
+        if failed:
+            _lib.check(rc)
+        if self.verbose:
+            if T > 10:
+                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
+            print('training completed in {} s'.format(np.round(dt, 2)))
+            if T > 0:
+                print('Final parameter values:\n', 'weights: {}'.format(np.around(self.weights[-1], 4)),
+                      'noise: {}'.format(np.around(self.noise_all[-1], 7)))
+        return
+
+    # ------------------------------------------------------------------ prediction
+    def predict(self, Xtest=None, **kwargs):
+        """Exact predictive mean and standard deviation of likelihood(model(Xtest)) (noise included), shape fulldims."""
+        kwargs.pop("num_batches", None)
+        kwargs.pop("max_root", None)
+        if Xtest is None and self.Xtest is None:
+            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
+            self.Xtest = self.X
+            self.fulldims = (self.X.shape[0],)
+        elif Xtest is not None:
+            self.Xtest = gprutils.prepare_test_data(Xtest)
+            self.fulldims = Xtest.shape[1:]
+        if kwargs.get("verbose") is not None:
+            self.verbose = kwargs.get("verbose")
+        if self.verbose:
+            print('Calculating predictive mean and uncertainty...')
+        Xs = self.Xtest.to(self._dev, _F64).contiguous()
+        M = Xs.shape[0]
+        mean = torch.empty(M, dtype=_F64, device=self._dev)
+        var = torch.empty(M, dtype=_F64, device=self._dev)
+        _lib.check(self._handle.lib.gpimhip_predict_sm(
+            self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
+            _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean), _lib.ptr(var)))
+        sd = torch.sqrt(var)
+        mean, sd = mean.cpu().numpy().reshape(self.fulldims), sd.cpu().numpy().reshape(self.fulldims)
+        if self.verbose:
+            print("Done")
+        return mean, sd
+
+    def run(self):
+        """train() then predict(); returns mean, sd, hyperparams (skgpr.py:266-279)."""
+        self.train()
+        mean, sd = self.predict()
+        return mean, sd, self.hyperparams

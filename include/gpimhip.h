@@ -203,6 +203,39 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
                         const double* Y, int64_t N, const double* u, const double* Xs, int64_t M, double* mean_out,
                         double* var_out);
 
+/* ---- exact GP with the spectral-mixture kernel ---------------------------------------------
+ * Replaces GPyTorch's ExactGP with a SpectralMixtureKernel, a ConstantMean and a GaussianLikelihood as the reference's
+ * skreconstructor(kernel='Spectral') builds it (gpim/gpreg/skgpr.py:122-123: no SKI; gpim/kernels/gpytorch_kernels.py:65-70).
+ * Q mixtures, D = dim (ard != 0) or 1 (one mean / scale per mixture shared by all dimensions), tau = x_i - x_j:
+ *   k_q(tau) = exp(-2 pi^2 sum_d tau_d^2 s_qd^2) prod_d cos(2 pi tau_d m_qd);  K = sum_q w_q k_q + noise I
+ *   w = softplus(r_w), m = softplus(r_m), s = softplus(r_s), noise = 1e-4 + softplus(r_n), mean: a constant c
+ * Parameter vector (unconstrained, what Adam updates), P = 2 + Q (2 D + 1) doubles:
+ *   u = [c | r_w (Q) | r_m (Q x D, row-major) | r_s (Q x D) | r_n]
+ * loss = -log N(y | c 1, K) / N  (gpytorch ExactMarginalLogLikelihood).  Double-precision handles only; the handle must
+ * not have reflection blocks.  Q > GPIMHIP_SM_MAX_MIXTURES or dim outside 1 .. GPIMHIP_MAX_DIM -> GPIMHIP_E_BADARG.
+ *   gpimhip_sm_kmat      K(X, Z) (N x M) at u into out (leading dimension ld); Z == NULL: K(X, X) + noise I (N x N)
+ *   gpimhip_sm_nll_grad  loss (1 double) and d loss / du (P doubles) at u
+ *   gpimhip_fit_sm       T Adam iterations on u (skgpr.py:196-220), no host synchronisation inside the loop: fresh Adam
+ *                        state, lr, betas (0.9, 0.999), eps 1e-8; hist_out: T x P constrained values [c, w, m, s, noise]
+ *                        AFTER each step, loss_out: T losses BEFORE each step (either may be NULL)
+ *   gpimhip_predict_sm   the exact predictive mean (c included) and variance of likelihood(model(Xs)) (noise included) at M
+ *                        test points; NaN rows give NaN */
+#define GPIMHIP_SM_MAX_MIXTURES 16
+typedef struct {
+    int32_t dim;            /* input dimensions, 1 .. GPIMHIP_MAX_DIM                             */
+    int32_t mixtures;       /* Q, 1 .. GPIMHIP_SM_MAX_MIXTURES                                      */
+    int32_t ard;            /* 1: a mean and a scale per mixture and dimension; 0: per mixture      */
+    int32_t reserved;
+} gpimhip_sm_t;
+int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* Z, int64_t M,
+                    const double* u, double* out, int64_t ld);
+int gpimhip_sm_nll_grad(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
+                        const double* u, double* loss_out, double* grad_out);
+int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N, double* u_inout,
+                   double lr, int32_t T, double* hist_out, double* loss_out);
+int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
+                       const double* u, const double* Xs, int64_t M, double* mean_out, double* var_out);
+
 /* ---- sparse (inducing-point) GP, variational free energy ---------------------------------
  * Replaces pyro.contrib.gp.models.SparseGPRegression(approx="VFE") as constructed by
  * reconstructor(sparse=True) (gpim/gpreg/gpr.py:145-155; formulas SURVEY App. A.7).
@@ -463,7 +496,9 @@ int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64
  * stage: 0 = Cholesky (all launches of one factorisation, including the tile operations of the triangular inverse
  *            they host), 1 = what is left of the triangular inverse after the last step,
  *        2 = K^-1 = L^-T L^-1 (exactly one gemm_tiles_kernel<true,true,0> launch, N^3/3 flop),
- *        3 = predictive-variance product L^-1 K(X,X*) (one launch per test-point slab).
+ *        3 = predictive-variance product L^-1 K(X,X*) (one launch per test-point slab),
+ *        4 = spectral-mixture covariance build K(X, X) (gpimhip_sm_*: one launch per evaluation),
+ *        5 = spectral-mixture gradient contraction (its tile launch and the record sum).
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
