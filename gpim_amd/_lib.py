@@ -132,6 +132,9 @@ _PROTOS = {
                                          c_dp, c_dp]),
     "gpimhip_set_reflection": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), c_dp,
                                               ctypes.c_int64, ctypes.c_int64]),
+    "gpimhip_set_border": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, c_dp]),
+    "gpimhip_nll_grad_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, c_dp,
+                                                ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, c_dp]),
     "gpimhip_acquire_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
                                              c_dp, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_dp]),

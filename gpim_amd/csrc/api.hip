@@ -9,6 +9,7 @@
 #include <atomic>
 #include <mutex>
 #include "common.hpp"
+#include "border.hpp"
 #include "vgp.hpp"
 #include "sm.hpp"
 
@@ -455,6 +456,115 @@ int launch_lauum(gpimhip_ctx* h, const double* A, double* B, int64_t np, int64_t
     return launch_gemm(h, true, true, EPI_STORE, g);
 }
 
+// ------------------------------------------------------------------------------------------
+// border of the reflection blocks: the exact GP on the observed points of an incomplete grid (border.hip, DESIGN.md
+// section 11).  S = (A^-1)_mm has a handle of its own (`sub`: mp x mp workspace, factorisation plans, status word) that
+// enqueues on the model handle's stream, so the factorisation of S is the engine's own and rides in the captured iteration.
+// ------------------------------------------------------------------------------------------
+static BorderWs* bws(const gpimhip_ctx* h) { return (BorderWs*)h->border; }
+static bool border_on(const gpimhip_ctx* h) { return h->refl.mask && h->border && bws(h)->M > 0; }
+
+static void border_free_bufs(gpimhip_ctx* h, BorderWs* w) {
+    dev_free(h, &w->C, (int64_t)w->B * w->np * w->mp);
+    dev_free(h, &w->Y, (int64_t)w->B * w->np * w->mp);
+    dev_free(h, &w->tv, 2 * w->mp);
+    dev_free(h, &w->scal, 2);
+    dev_free(h, &w->tiles_y, w->n_y);
+    dev_free(h, &w->tiles_upd, w->n_upd);
+    dev_free(h, &w->R, w->mp * w->r_cols);
+    dev_free(h, &w->rsq, w->r_cols);
+    w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0;
+}
+void border_release(gpimhip_ctx* h) {
+    BorderWs* w = bws(h);
+    if (!w) return;
+    border_free_bufs(h, w);
+    if (w->sub) gpimhip_destroy(w->sub);
+    delete w;
+    h->border = nullptr;
+}
+
+// buffers for the workspace's np and batch (outside any capture: allocations and tile-list uploads synchronise)
+static int border_ensure(gpimhip_ctx* h) {
+    BorderWs* w = bws(h);
+    const int64_t mp = pad_to(w->M, NB);
+    if (!w->sub) {
+        GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
+        w->sub->nbatch = 1;
+    }
+    w->sub->stream = h->stream;
+    GP_TRY(ws_ensure_b(w->sub, w->M, 1, 1));
+    if (w->np == h->np && w->B == h->nbatch && w->mp == mp && w->C) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    border_free_bufs(h, w);
+    w->mp = mp; w->np = h->np; w->B = h->nbatch;
+    const int nb = (int)(h->np / NB), nm = (int)(mp / NB);
+    std::vector<TileDesc> ty, tu;
+    for (int ci = 0; ci < nb; ++ci)
+        for (int cj = 0; cj < nm; ++cj) ty.push_back({ci, cj, 0, cj + 1});       // L_S^-1 is lower triangular
+    lower_patch_order(tu, 0, nb, 0, nm);
+    w->n_y = (int)ty.size();
+    w->n_upd = (int)tu.size();
+    int rc = GPIMHIP_OK;
+    if ((rc = dev_alloc(h, &w->C, (int64_t)w->B * w->np * mp)) || (rc = dev_alloc(h, &w->Y, (int64_t)w->B * w->np * mp)) ||
+        (rc = dev_alloc(h, &w->tv, 2 * mp)) || (rc = dev_alloc(h, &w->scal, 2)) || (rc = dev_alloc(h, &w->tiles_y, w->n_y)) ||
+        (rc = dev_alloc(h, &w->tiles_upd, w->n_upd))) {
+        border_free_bufs(h, w);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(w->tiles_y, ty.data(), ty.size() * sizeof(TileDesc), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(w->tiles_upd, tu.data(), tu.size() * sizeof(TileDesc), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return GPIMHIP_OK;
+}
+static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
+    BorderWs* w = bws(h);
+    if (w->r_cols >= cols && w->R) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    dev_free(h, &w->R, w->mp * w->r_cols);
+    dev_free(h, &w->rsq, w->r_cols);
+    w->r_cols = 0;
+    int rc = GPIMHIP_OK;
+    if ((rc = dev_alloc(h, &w->R, w->mp * cols)) || (rc = dev_alloc(h, &w->rsq, cols))) {
+        dev_free(h, &w->R, w->mp * cols);
+        return rc;
+    }
+    w->r_cols = cols;
+    return GPIMHIP_OK;
+}
+
+// After the blocks' inverses are in h->B (launch_lauum): S, L_S^-1, Y_b = C_b L_S^-T, the corrected alpha, the two loss
+// scalars, and (training) B_b^-1 -= Y_b Y_b^T on the lower tiles.  nq: the points of the fundamental domain.
+static int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
+    BorderWs* w = bws(h);
+    gpimhip_ctx* sub = w->sub;
+    sub->stream = h->stream;                // (the capture stream while fit_impl records an iteration)
+    sub->capturing = h->capturing;
+    const int64_t mp = w->mp;
+    GP_TRY(launch_border_gather_s(h, w, h->B, h->ld, sub->A, sub->ld));
+    GP_TRY(launch_potrf_inv(sub, sub->A, sub->Tm, mp, sub->ld, sub->info, 0));      // (rag 0: every padding row is written)
+    GP_TRY(launch_border_tidy(h, w, sub->A, sub->ld));
+    GP_TRY(launch_border_gather_c(h, w, h->B, h->ld, nq));
+    {
+        // Y = C L_S^-T (NT: operand B is L_S^-1, shared by the blocks)
+        GemmArgs g = gemm_args(w->C, mp, sub->A, sub->ld, w->Y, mp, 1.0, 0.0, w->tiles_y, w->n_y, h->np);
+        g.sB = 0;
+        g.chunk = deal_chunk(g.ntiles);
+        GP_TRY(launch_gemm(h, false, false, EPI_STORE, g));
+    }
+    GP_TRY(launch_border_vectors(h, w, sub->A, sub->ld, sub->logdet_part, (int)(mp / NB), h->alpha));
+    if (update_inverse) {
+        // B_b^-1 -= Y_b Y_b^T (NT, subtracting epilogue: alpha = -1, beta = 1) on the tiles the gradient contraction reads
+        GemmArgs g = gemm_args(w->Y, mp, w->Y, mp, h->B, h->ld, -1.0, 1.0, w->tiles_upd, w->n_upd, h->np);
+        g.sA = g.sB = h->np * mp;
+        g.kfix0 = 0;
+        g.kfix1 = (int)(mp / NB);
+        g.chunk = deal_chunk(g.ntiles);
+        GP_TRY(launch_gemm(h, false, false, EPI_STORE, g));
+    }
+    return GPIMHIP_OK;
+}
+
 // N <= 128: the fused single-workgroup trainer (smalln.hip) replaces the blocked path
 static bool use_small_path(int64_t N) { return N <= NB && !getenv("GPIMHIP_NO_SMALLN"); }
 
@@ -535,12 +645,15 @@ static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double
     GP_TRY(factor_at_u(h, m, X, x_bs, N, u, carried, defer));
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
     if (h->refl.mask) {
+        const bool bd = border_on(h);
+        if (bd) GP_TRY(border_iter(h, N, true));
+        const double* bscal = bd ? bws(h)->scal : nullptr;
         GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, x_bs));
         if (tab)
             return launch_finalize_coupled(h, m, N, np, u, do_adam, st, nullptr, nullptr, nullptr, tab->iter, tab->bc, tab->T,
-                                           tab->hist_base, tab->loss_base);
+                                           tab->hist_base, tab->loss_base, bscal);
         return launch_finalize_coupled(h, m, N, np, u, do_adam, st, loss_out, grad_out, hist_row, nullptr, nullptr, 0, nullptr,
-                                       nullptr);
+                                       nullptr, bscal);
     }
     if (fused) {
         const double* ap = defer ? h->gemv_part : nullptr;
@@ -695,6 +808,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     kron_release(h);
     vgp_release(h);
     sm_release(h);
+    border_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
     dev_free(h, &h->keys, h->keys_cap);
@@ -799,6 +913,7 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
         return finish_and_check(h);
     }
     GP_TRY(ws_ensure_padded(h, N));
+    if (border_on(h)) GP_TRY(border_ensure(h));
     HIP_TRY(hipMemsetAsync(h->adam_m, 0, (size_t)B * MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->adam_v, 0, (size_t)B * MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->iter, 0, (size_t)B * sizeof(int32_t), h->stream));     // iteration counters
@@ -872,6 +987,8 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
     mc = std::min(mc, cap);
     GP_TRY(ws_ensure_predict(h, np, mc));
     const int64_t mcap = h->ks_cols, kld = mcap + 16;       // buffer strides follow the capacity
+    const bool bd = border_on(h);
+    if (bd) GP_TRY(border_ensure_r(h, mcap));
     for (int64_t m0 = 0; m0 < M; m0 += mc) {
         const int64_t cnt = std::min(mc, M - m0);
         const int64_t cpad = pad_to(cnt, NB);
@@ -886,7 +1003,8 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         if (!h->refl.mask) GP_TRY(launch_copy_slice(h, h->mean_tmp, mean_out + m0, cnt, mcap, M));
         // reflection blocks: the variance may be wanted for the first var_count test points only (it is invariant under
         // the reflections: a caller predicting on the training grid asks for it on the fundamental domain)
-        const int64_t nvar = (h->refl.mask && h->refl.var_count > 0) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
+        // (not with a border: the missing points break the symmetry of the variance)
+        const int64_t nvar = (h->refl.mask && h->refl.var_count > 0 && !bd) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
         if (nvar == 0) {
             GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, 0, mcap, mean_out, var_out));
             continue;
@@ -902,7 +1020,24 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         g.chunk = deal_chunk(g.ntiles);
         g.rag = h->fp32 ? 0 : rag_of(N, np);
         { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
-        if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out));
+        const double* radd = nullptr;
+        if (bd) {
+            // R = sum_b Y_b^T K*_b: the stacked blocks of Y and of the slab are (B np)-row matrices (TN, one problem)
+            BorderWs* w = bws(h);
+            w->sub->stream = h->stream;
+            GemmArgs gr = gemm_args(w->Y, w->mp, h->Ks, kld, w->R, w->r_cols, 1.0, 0.0, nullptr, 0, 0);
+            gr.sA = gr.sB = gr.sC = 0;
+            gr.rect_rows = (int)(w->mp / NB);
+            gr.rect_cols = (int)(cpad / NB);
+            gr.ntiles = gr.rect_rows * gr.rect_cols;
+            gr.kfix0 = 0;
+            gr.kfix1 = (int)((int64_t)B * np / NB);
+            gr.chunk = deal_chunk(gr.ntiles);
+            GP_TRY(launch_gemm(w->sub, true, true, EPI_STORE, gr));
+            GP_TRY(launch_border_colsumsq(h, w, cnt));
+            radd = w->rsq;
+        }
+        if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
         else GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
     return GPIMHIP_OK;
@@ -917,7 +1052,12 @@ static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
     const int64_t np = h->np;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
     GP_TRY(launch_pad_copy(h, y, N, h->ypad, np));
+    if (border_on(h)) GP_TRY(border_ensure(h));
     GP_TRY(factor_at_u(h, m, X, x_bs, N, u));
+    if (border_on(h)) {
+        GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np)));
+        GP_TRY(border_iter(h, N, false));
+    }
     GP_TRY(predict_cols(h, m, X, x_bs, N, B, Xs, M, mean_out, var_out));
     return finish_and_check(h);
 }
@@ -973,6 +1113,27 @@ int gpimhip_predict_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, co
         return GPIMHIP_E_BADARG;
     GP_TRY(check_model(m));
     return predict_impl(h, m, X, x_stride, y, N, B, u, Xs, M, mean_out, var_out);
+}
+
+int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
+                             int64_t N, int32_t B, const double* u, double* loss_out, double* grad_out) {
+    if (!h || !X || !y || !u || N < 1 || B < 1 || B > 65535 || !loss_out || !grad_out || (x_stride != 0 && x_stride < N * (m ? m->dim : 1)))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (!h->refl.mask || h->fp32) {
+        gpim_set_error("gpimhip_nll_grad_batched evaluates the coupled reflection blocks: needs reflection mode on a double-precision handle");
+        return GPIMHIP_E_BADARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = B;
+    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(ws_ensure_padded(h, N));
+    if (border_on(h)) GP_TRY(border_ensure(h));
+    GP_TRY(launch_pad_copy(h, y, N, h->ypad, h->np));
+    AdamStep st;
+    memset(&st, 0, sizeof(st));
+    GP_TRY(loss_grad_at_u(h, m, X, x_stride, N, const_cast<double*>(u), 0, st, loss_out, grad_out, nullptr));
+    return finish_and_check(h);
 }
 
 int gpimhip_acq(gpimhip_handle h, int32_t kind, const double* mean, const double* sd, int64_t M, double p0,
@@ -1502,6 +1663,24 @@ int gpimhip_set_reflection(gpimhip_handle h, int32_t mask, const double* twoc, c
     h->refl.n_total = mask ? n_total : 0;
     h->refl.var_count = mask ? var_count : 0;
     if (!mask) { h->refl.pb_off = 0; h->refl.pb_stride = 1; h->refl.nblocks_total = 0; h->refl.raw = 0; }
+    if (!mask && h->border) bws(h)->M = 0;
+    return GPIMHIP_OK;
+}
+
+int gpimhip_set_border(gpimhip_handle h, int32_t M, const int32_t* q, const double* coef) {
+    if (!h || M < 0 || (M > 0 && (!q || !coef))) return GPIMHIP_E_BADARG;
+    if (M > 0 && (!h->refl.mask || h->fp32 || h->refl.pb_stride != 1 || h->refl.raw)) {
+        gpim_set_error("gpimhip_set_border needs reflection mode (gpimhip_set_reflection) on a double-precision handle, unsharded");
+        return GPIMHIP_E_BADARG;
+    }
+    if (!h->border) {
+        if (M == 0) return GPIMHIP_OK;
+        h->border = new BorderWs();
+    }
+    BorderWs* w = bws(h);
+    w->M = M;
+    w->q = M ? q : nullptr;
+    w->coef = M ? coef : nullptr;
     return GPIMHIP_OK;
 }
 

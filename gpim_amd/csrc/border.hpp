@@ -1,0 +1,32 @@
+// border.hpp -- launches of the border form of the reflection blocks (border.hip; driven by api.hip: border_*).
+#pragma once
+#include "common.hpp"
+
+// What gpimhip_set_border leaves on the handle, and the border's own workspace (sized for the workspace's np).
+struct BorderWs {
+    int M = 0;                      // missing points (0: border off)
+    int64_t mp = 0;                 // M padded to 128
+    const int32_t* q = nullptr;     // (device, M) representative of missing point j in the fundamental domain
+    const double* coef = nullptr;   // (device, B x M) coefficient c_b(j) of missing point j in block b
+    gpimhip_ctx* sub = nullptr;     // handle of S: its own mp x mp workspace, factorisation plans and status word
+    int64_t np = 0;                 // the block order the buffers below are sized for
+    int B = 0;
+    double* C = nullptr;            // B x np x mp   C_b[:, j] = c_b(j) B_b^-1[:, q(j)]
+    double* Y = nullptr;            // B x np x mp   Y_b = C_b L_S^-T
+    double* tv = nullptr;           // 2 x mp: t = (A^-1 y~)_m, v = L_S^-1 t
+    double* scal = nullptr;         // 2: |v|^2, sum log (L_S)_ii
+    TileDesc* tiles_y = nullptr;    // Y = C L_S^-T: (np / 128) x (mp / 128) tiles, k-range [0, cj]
+    int n_y = 0;
+    TileDesc* tiles_upd = nullptr;  // B_b^-1 -= Y_b Y_b^T: the lower tiles of the block
+    int n_upd = 0;
+    double* R = nullptr;            // mp x r_cols: R = sum_b Y_b^T K*_b for one test chunk
+    double* rsq = nullptr;          // r_cols: column sums of squares of R
+    int64_t r_cols = 0;
+};
+
+int launch_border_gather_s(gpimhip_ctx* h, const BorderWs* w, const double* Binv, int64_t ld, double* S, int64_t lds);
+int launch_border_tidy(gpimhip_ctx* h, const BorderWs* w, double* Linv, int64_t lds);
+int launch_border_gather_c(gpimhip_ctx* h, const BorderWs* w, const double* Binv, int64_t ld, int64_t nq);
+int launch_border_vectors(gpimhip_ctx* h, const BorderWs* w, const double* Linv, int64_t lds, const double* logdet_part,
+                          int nbs, double* alpha);
+int launch_border_colsumsq(gpimhip_ctx* h, const BorderWs* w, int64_t cnt);

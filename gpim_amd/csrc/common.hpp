@@ -188,6 +188,8 @@ struct gpimhip_ctx {
     void* vgp = nullptr;
     // spectral-mixture workspace, owned by api.hip (SmWs); released by sm_release()
     void* sm = nullptr;
+    // border of the reflection blocks (missing points of an incomplete grid), owned by api.hip (BorderWs); border_release()
+    void* border = nullptr;
     double* refine = nullptr; int64_t refine_cap = 0;    // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
 };
@@ -258,10 +260,10 @@ int launch_grad_reduce_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const doub
                             int64_t N, int nb, const double* alpha, int64_t x_bs);
 int launch_finalize_coupled(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
                             AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                            const double* bc, int T, double* hist_base, double* loss_base);
+                            const double* bc, int T, double* hist_base, double* loss_base, const double* border_scal = nullptr);
 int launch_coupled_sums(gpimhip_ctx* h, int64_t np, double* out11);
 int launch_predict_coupled(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, int64_t nvar, int64_t mean_bs,
-                           double* mean_out, double* var_out);
+                           double* mean_out, double* var_out, const double* radd = nullptr);
 int launch_dist_finalize_dev(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, const double* red, const double* quad,
                              double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row);
 int launch_dist_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, const double* S, double q2, double lg,

@@ -1420,7 +1420,8 @@ __global__ __launch_bounds__(256) void finalize_coupled_kernel(gpimhip_model_t m
                                                                double* __restrict__ adam_m, double* __restrict__ adam_v,
                                                                int do_adam, AdamStep st, double* __restrict__ loss_out,
                                                                double* __restrict__ grad_out, double* __restrict__ hist_row,
-                                                               FinalizeIter fi, int32_t* __restrict__ info) {
+                                                               FinalizeIter fi, int32_t* __restrict__ info,
+                                                               const double* __restrict__ border_scal) {
     __shared__ double red[256];
     __shared__ double S[8];
     const int tid = threadIdx.x;
@@ -1443,6 +1444,10 @@ __global__ __launch_bounds__(256) void finalize_coupled_kernel(gpimhip_model_t m
         lg += block_sum_256(lb, red);
     }
     if (tid != 0) return;
+    if (border_scal) {          // border of the missing points (border.hip): - |L_S^-1 t|^2 and + log det L_S
+        q2 -= border_scal[0];
+        lg += border_scal[1];
+    }
     if (fi.iter) {
         const int it = *fi.iter;
         if (*info != 0) {
@@ -1461,13 +1466,13 @@ __global__ __launch_bounds__(256) void finalize_coupled_kernel(gpimhip_model_t m
 }
 int launch_finalize_coupled(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
                             AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                            const double* bc, int T, double* hist_base, double* loss_base) {
+                            const double* bc, int T, double* hist_base, double* loss_base, const double* border_scal) {
     const int nb = (int)(np / NB);
     FinalizeIter fi{iter, bc, T, hist_base, loss_base};
     hipLaunchKernelGGL(finalize_coupled_kernel, dim3(1), dim3(256), 0, h->stream, *m, h->refl.n_total > 0 ? h->refl.n_total : N * h->nbatch, np, nb,
                        nb * (nb + 1) / 2, h->nbatch,
                        h->grad_part, h->z, h->fp32 ? h->alpha : h->z, h->logdet_part, h->theta, u, h->adam_m, h->adam_v, do_adam,
-                       st, loss_out, grad_out, hist_row, fi, h->info);
+                       st, loss_out, grad_out, hist_row, fi, h->info, border_scal);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -1514,7 +1519,7 @@ int launch_coupled_sums(gpimhip_ctx* h, int64_t np, double* out11) {
 __global__ void predict_coupled_kernel(const double* __restrict__ colpart, int64_t ldp, int nb, int B, int64_t m0, int64_t mcount,
                                        int64_t nvar, const double* __restrict__ mean_tmp, int64_t mean_bs,
                                        const ThetaDev* __restrict__ th, double* __restrict__ mean_out, double* __restrict__ var_out,
-                                       int raw) {
+                                       int raw, const double* __restrict__ radd) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= mcount) return;
     double q = 0.0, mu = 0.0;
@@ -1524,12 +1529,13 @@ __global__ void predict_coupled_kernel(const double* __restrict__ colpart, int64
         mu += mean_tmp[b * mean_bs + j];
     }
     mean_out[m0 + j] = mu;
-    if (j < nvar) var_out[m0 + j] = raw ? q : clamp0_nan(th->var - q) + th->noise;
+    // radd (border of the missing points): + |sum_b Y_b^T k*_b|^2
+    if (j < nvar) var_out[m0 + j] = raw ? q : (radd ? clamp0_nan((th->var - q) + radd[j]) : clamp0_nan(th->var - q)) + th->noise;
 }
 int launch_predict_coupled(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, int64_t nvar, int64_t mean_bs,
-                           double* mean_out, double* var_out) {
+                           double* mean_out, double* var_out, const double* radd) {
     hipLaunchKernelGGL(predict_coupled_kernel, dim3((unsigned)((mcount + 255) / 256)), dim3(256), 0, h->stream, h->colpart, ldp,
-                       nb, h->nbatch, m0, mcount, nvar, h->mean_tmp, mean_bs, h->theta, mean_out, var_out, h->refl.raw);
+                       nb, h->nbatch, m0, mcount, nvar, h->mean_tmp, mean_bs, h->theta, mean_out, var_out, h->refl.raw, radd);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

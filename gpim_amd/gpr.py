@@ -157,8 +157,17 @@ class reconstructor:
         self.do_sparse = bool(sparse)
         self.do_structured = bool(kwargs.get("structured", False))
         self.do_symm = False
+        self.do_border = False
         self._kernel_name = kernel
-        if self.do_structured:
+        border = kwargs.get("_border")       # set by skreconstructor on an incomplete grid (gprutils.border_blocks)
+        if self.do_structured and border is not None:
+            # the reflection blocks of the completed grid with a border for its missing points (csrc/border.hip)
+            self.do_structured = False
+            self.do_symm = self.do_border = True
+            border["twoc"] = (ctypes.c_double * 4)(*border["twoc"])
+            border["n_total"] = border["n_obs"]          # the loss is that of the observed points
+            self._symm = border
+        elif self.do_structured:
             if self.do_sparse:
                 raise NotImplementedError("structured=True and sparse=True are mutually exclusive")
             if np.isnan(np.asarray(y)).any():
@@ -264,8 +273,13 @@ class reconstructor:
         u_b = self._u.repeat(S["B"]).contiguous()
         _lib.check(lib.gpimhip_set_reflection(h, S["mask"], S["twoc"], _lib.ptr(S["wts_d"]), S["n_total"], int(var_count)))
         try:
+            if self.do_border:
+                if "q_d" not in S:
+                    S["q_d"] = torch.from_numpy(S["q"]).to(self._dev)
+                    S["coef_d"] = self._to_device(np.ascontiguousarray(S["coef"]))
+                _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(S["q_d"].data_ptr()), _lib.ptr(S["coef_d"])))
             rc = fn(S["Xq_d"], S["ys_d"], S["Xq_d"].shape[0], S["B"], u_b)
-        finally:
+        finally:      # (also switches a border off)
             _lib.check(lib.gpimhip_set_reflection(h, 0, None, None, 0, 0))
         self._u.copy_(u_b[:self._u.numel()])
         return rc
@@ -401,7 +415,8 @@ class reconstructor:
                 _lib.ptr(mean), _lib.ptr(var))
         elif self.do_symm:
             S = self._symm
-            on_grid = self._Xtest_d.shape == self._Xd.shape and bool(torch.equal(self._Xtest_d, self._Xd))
+            on_grid = (not self.do_border and self._Xtest_d.shape == self._Xd.shape
+                       and bool(torch.equal(self._Xtest_d, self._Xd)))
             if on_grid:
                 # the training grid itself: the variance is invariant under the reflections -- computed on the fundamental
                 # domain (ordered first) and mirrored; the mean everywhere
@@ -493,6 +508,11 @@ class reconstructor:
                 self._handle.h, ctypes.byref(self._mstruct), self._spec.dim, self._axes_n, _lib.ptr(self._axes_d),
                 _lib.ptr(self._yd), _lib.ptr(self._u), ctypes.c_void_p(out.data_ptr()),
                 ctypes.c_void_p(out.data_ptr() + 8))
+        elif self.do_border:
+            # the coupled blocks with the border: one evaluation of what a training iteration computes
+            rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_nll_grad_batched(
+                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 8)))
         elif self.do_sparse:
             rc = self._handle.lib.gpimhip_vfe_nll_grad(
                 self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),

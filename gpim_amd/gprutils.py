@@ -147,3 +147,78 @@ def reflection_blocks(X, y, axes):
     return {"mask": mask, "twoc": twoc, "B": B, "Xq": Xq, "ys": ys, "wts": wts if nplanes.any() else None,
             "n_total": int(y.size), "dims": dims, "fund_flat": fund_flat, "rep": rep}
 
+
+def complete_grid(X, y):
+    """The complete product grid behind an incomplete one (gpim_amd extension: the border form of the reflection blocks,
+    reconstructor's exact GP on the observed points of an image or cube with missing pixels).
+
+    X (d, n_1, ..., n_d): grid coordinates with NaN at the missing points (what ``get_sparse_grid`` returns), y
+    (n_1, ..., n_d) with NaN at the same points.  Returns (axes, miss): the d coordinate vectors of the completed grid and
+    the flat (row-major) indices of the missing points.  Raises NotImplementedError when the observed coordinates do not
+    form a product grid, when some index along an axis has no observation, or when the NaN patterns of X and y differ."""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    d = X.shape[0]
+    if X.ndim != d + 1 or X.shape[1:] != y.shape:
+        raise NotImplementedError("grid completion needs coordinates of shape (d, n_1, ..., n_d) and y of shape (n_1, ..., n_d)")
+    missing = np.isnan(X).any(axis=0)
+    if not np.array_equal(missing, np.isnan(y)):
+        raise NotImplementedError("grid completion needs the same NaN pattern in X and y")
+    axes = []
+    for i in range(d):
+        vals = np.moveaxis(X[i], i, 0).reshape(X.shape[1 + i], -1)
+        obs = np.moveaxis(~missing, i, 0).reshape(X.shape[1 + i], -1)
+        if not obs.any(axis=1).all():
+            raise NotImplementedError("grid completion: an index along axis %d has no observation" % i)
+        first = np.argmax(obs, axis=1)
+        c = vals[np.arange(vals.shape[0]), first]
+        if not np.all((vals == c[:, None]) | ~obs):
+            raise NotImplementedError("grid completion needs a product grid (coordinate %d varying along axis %d only)" % (i, i))
+        axes.append(c)
+    return axes, np.flatnonzero(missing.ravel())
+
+
+def border_blocks(X, y):
+    """Reflection blocks of the completed grid plus the "border" of its missing points (gpim_amd extension; DESIGN.md
+    section 11).  The exact GP on the observed points is computed from the 2^r blocks B_b of A = K + (noise + jitter) I on
+    the completed grid and the M x M matrix S = (A^-1)_mm: A_oo^-1 embedded in the grid is A^-1 - A^-1 P_m S^-1 P_m^T A^-1.
+
+    Returns the dict of ``reflection_blocks`` for the completed grid with y = 0 at the missing points, and in addition: axes,
+    miss (flat indices of the M missing points), q (int32, M): each missing point's representative in the fundamental
+    domain (a row of Xq), coef (B, M): its coefficient in block b, (U^T e_j)_{b, q(j)} = chi_b(g_j) sqrt(|Stab_q|) / sqrt(B)
+    (0 where the point does not exist in the block), n_obs = the number of observations.
+    Raises NotImplementedError when the grid cannot be completed, ValueError when no axis is symmetric."""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    axes, miss = complete_grid(X, y)
+    Xc = np.array(np.meshgrid(*axes, indexing="ij"))
+    S = reflection_blocks(Xc, np.nan_to_num(y, nan=0.0), axes)
+    dims, B = S["dims"], S["B"]
+    idx = np.unravel_index(miss, y.shape)
+    q = S["rep"][miss].astype(np.int32)
+    # g_j: the reflections that take the representative to the point (bit j = the j-th reflected axis);
+    # stab: 2^(mirror planes the representative lies on)
+    gbits = np.zeros(len(miss), dtype=np.int64)
+    nplanes = np.zeros(len(miss), dtype=np.int64)
+    for j, k in enumerate(dims):
+        n = y.shape[k]
+        gbits |= (idx[k] > (n - 1) // 2).astype(np.int64) << j
+        nplanes += ((n % 2 == 1) & (idx[k] == n // 2)).astype(np.int64)
+    coef = np.empty((B, len(miss)))
+    for b in range(B):
+        chi = np.where(np.array([bin(int(g) & b).count("1") & 1 for g in gbits], dtype=bool), -1.0, 1.0) \
+            if len(miss) else np.empty(0)
+        present = np.ones(len(miss), dtype=bool)
+        for j, k in enumerate(dims):
+            if (b >> j) & 1:
+                present &= ~((y.shape[k] % 2 == 1) & (idx[k] == y.shape[k] // 2))
+        coef[b] = np.where(present, chi * 2.0 ** (0.5 * nplanes) / np.sqrt(B), 0.0)
+    S.update({"axes": axes, "miss": miss, "q": q, "coef": coef, "n_obs": int(y.size - len(miss))})
+    return S
+
+
+def border_flops(N, M, r):
+    """Per-iteration flop model of the border form against the dense exact GP on the N - M observed points
+    (DESIGN.md section 11): (F_border, F_dense) = (N^3 / 4^r + N^2 M / 2^r + N M^2 + M^3, (N - M)^3)."""
+    N, M = float(N), float(M)
+    return N ** 3 / 4.0 ** r + N * N * M / 2.0 ** r + N * M * M + M ** 3, (N - M) ** 3

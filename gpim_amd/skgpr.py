@@ -13,9 +13,19 @@ gprutils.reflection_blocks + csrc/engine.hip: kmat_refl_kernel) -- with the mode
 ``gpim_amd.reconstructor`` (zero mean, Uniform priors on variance and lengthscales).  Same constructor shape and return values as the reference class;
 numbers are those of ``reconstructor(..., structured=True)``, i.e. of the exact GP -- not bit-comparable
 with an SKI run.  ``kernel='Spectral'`` (GPyTorch's spectral-mixture kernel, for which the reference turns SKI off) returns
-the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse images included.
+the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse images included.  Incomplete grids (NaN in y)
+with the other kernels: the exact GP on the observed points, either as the reflection blocks of the completed grid with a
+border for the missing points (csrc/border.hip) or on the dense engine, whichever the flop model says is cheaper
+(``rec.solver``: 'border' or 'dense').
 """
+import numpy as np
+
+from . import gprutils
 from .gpr import reconstructor
+
+# the border form is chosen when its flop model is below this fraction of the dense model's (DESIGN.md section 11: at a
+# model ratio of 0.74 the border still ran 1.14x (128 x 128) and 1.31x (256 x 256) faster than dense)
+BORDER_FACTOR = 0.75
 
 
 class skreconstructor(reconstructor):
@@ -33,11 +43,30 @@ class skreconstructor(reconstructor):
 
     def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, ski=True, learning_rate=.1,
                  iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
-        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures", "sparse"):
+        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures", "sparse", "_border"):
             kwargs.pop(k, None)
+        solver, border = self._choose_solver(X, y, kernel)
         super().__init__(X, y, Xtest, kernel=kernel, lengthscale=lengthscale, sparse=False, indpoints=None,
                          learning_rate=learning_rate, iterations=iterations, use_gpu=use_gpu, verbose=verbose,
-                         seed=seed, structured=True, **kwargs)
+                         seed=seed, structured=solver != "dense", _border=border, **kwargs)
+        self.solver = solver
+
+    @staticmethod
+    def _choose_solver(X, y, kernel):
+        """('kronecker' | 'reflection', None) on a complete grid; on an incomplete one ('border', border_blocks(X, y)) when
+        the grid can be completed, has a symmetric axis and the border's flop model is below BORDER_FACTOR of the dense
+        exact GP's on the observed points, else ('dense', None)."""
+        yv = np.asarray(y, dtype=np.float64)
+        if not np.isnan(yv).any():
+            return ("kronecker" if kernel == "RBF" else "reflection"), None
+        if kernel not in ("RBF", "Matern52", "RationalQuadratic"):
+            return "dense", None
+        try:
+            S = gprutils.border_blocks(X, yv)
+        except (NotImplementedError, ValueError):
+            return "dense", None
+        f_border, f_dense = gprutils.border_flops(yv.size, len(S["miss"]), len(S["dims"]))
+        return ("border", S) if f_border < BORDER_FACTOR * f_dense else ("dense", None)
 
     def predict(self, Xtest=None, **kwargs):
         kwargs.pop("num_batches", None)

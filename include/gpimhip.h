@@ -471,6 +471,19 @@ int gpimhip_set_reflection(gpimhip_handle h, int32_t mask, const double* twoc, c
  *                                 [0..7] gradient sums, [8] sum log L_ii, [9] 1 if a factorisation failed, [10] sum
  *                                 |L^-1 y|^2.  After the all-reduce, gpimhip_dist_finalize_dev takes [0..9] and [10]. */
 int gpimhip_set_reflection_shard(gpimhip_handle h, int32_t pb_off, int32_t pb_stride, int32_t nblocks_total, int32_t raw);
+
+/* Border of the reflection blocks: the exact GP on the OBSERVED points of an incomplete grid (gpim_amd/skgpr.py; DESIGN.md
+ * section 11).  The blocks are those of the completed grid (y = 0 at the M missing points, n_total of
+ * gpimhip_set_reflection = the number of observations); missing point j has the representative q[j] (a point of the
+ * fundamental domain, device int32, M) and in block b the coefficient coef[b * M + j] (device, B x M) -- both as
+ * gpim_amd.gprutils.border_blocks returns them.  Valid only in reflection mode, double precision, unsharded; honoured by
+ * gpimhip_fit_exact_batched, gpimhip_predict_exact_batched and gpimhip_nll_grad_batched.  M = 0, or
+ * gpimhip_set_reflection(h, 0, ...), switches it off.  q and coef must stay valid while it is on.
+ *   gpimhip_nll_grad_batched  one loss / gradient evaluation of the coupled blocks in reflection mode (with the border when
+ *                             it is set) at u (B copies of the parameter vector); loss_out, grad_out: device. */
+int gpimhip_set_border(gpimhip_handle h, int32_t M, const int32_t* q, const double* coef);
+int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
+                             int64_t N, int32_t B, const double* u, double* loss_out, double* grad_out);
 int gpimhip_refl_sums(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, int32_t B,
                       const double* u, double* sums_out);
 
