@@ -972,9 +972,13 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
 }
 
 
+// Multi-output GP in reflection mode (vgp.hip): the batch is T tasks of nrep = 2^r consecutive problems each; predict_cols
+// sums each task's blocks and mixes the tasks (vgp_group_combine_kernel) into M x T outputs
+struct VgpGroup { int T, nrep; const VgpDev* st; };
+
 // posterior mean / variance at M test points from the factorised model in the workspace (theta, L^-1, alpha)
 static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, int B,
-                        const double* Xs, int64_t M, double* mean_out, double* var_out) {
+                        const double* Xs, int64_t M, double* mean_out, double* var_out, const VgpGroup* vgrp = nullptr) {
     const int64_t np = h->np;
     const int nb = (int)(np / NB);
     // few observations: one fused launch, K* stays in LDS (predict.hip)
@@ -995,7 +999,7 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         // the test grid Xs is shared by all problems of the batch (z stride 0)
         if (h->refl.mask)      // V_s^T k(X, x*): the block's rows against the test point and its mirror images, |G|^-1/2 each
             GP_TRY(launch_kmat_refl(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, h->Ks, kld, np, cpad, 0, x_bs, 0, np * kld,
-                                    1.0 / sqrt((double)(h->refl.nblocks_total > 0 ? h->refl.nblocks_total : B))));
+                                    1.0 / sqrt((double)(vgrp ? vgrp->nrep : h->refl.nblocks_total > 0 ? h->refl.nblocks_total : B))));
         else
             GP_TRY(launch_kmat(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, x_bs, 0,
                                np * kld));
@@ -1004,7 +1008,7 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         // reflection blocks: the variance may be wanted for the first var_count test points only (it is invariant under
         // the reflections: a caller predicting on the training grid asks for it on the fundamental domain)
         // (not with a border: the missing points break the symmetry of the variance)
-        const int64_t nvar = (h->refl.mask && h->refl.var_count > 0 && !bd) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
+        const int64_t nvar = (h->refl.mask && h->refl.var_count > 0 && !bd && !vgrp) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
         if (nvar == 0) {
             GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, 0, mcap, mean_out, var_out));
             continue;
@@ -1037,7 +1041,8 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
             GP_TRY(launch_border_colsumsq(h, w, cnt));
             radd = w->rsq;
         }
-        if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
+        if (vgrp) GP_TRY(launch_vgp_group_combine(h, vgrp->T, vgrp->nrep, nb, mcap, m0, cnt, vgrp->st, mean_out, var_out));
+        else if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
         else GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
     return GPIMHIP_OK;
@@ -1729,7 +1734,7 @@ struct VgpWs {
     VgpDev* st = nullptr;
     double* adam = nullptr;         // 2 x VGP_MAXP: Adam m, v
     int32_t* iter = nullptr;
-    double* kb = nullptr; int64_t kb_cap = 0;        // T x np: K beta_t
+    double* kb = nullptr; int64_t kb_cap = 0;        // T x np: K beta_t (reflection mode: T 2^r x np, K_b beta_{t,b})
     double* pred = nullptr; int64_t pred_cap = 0;    // 2 x T x M: the blocks' mean and variance
 };
 void vgp_release(gpimhip_ctx* h) {
@@ -1743,7 +1748,7 @@ void vgp_release(gpimhip_ctx* h) {
     delete w;
     h->vgp = nullptr;
 }
-static int vgp_ws(gpimhip_ctx* h, int T, int64_t M, VgpWs** out) {
+static int vgp_ws(gpimhip_ctx* h, int nprob, int T, int64_t M, VgpWs** out) {
     VgpWs* w = (VgpWs*)h->vgp;
     if (!w) {
         w = new VgpWs();
@@ -1752,7 +1757,7 @@ static int vgp_ws(gpimhip_ctx* h, int T, int64_t M, VgpWs** out) {
         GP_TRY(dev_alloc(h, &w->adam, 2 * VGP_MAXP));
         GP_TRY(dev_alloc(h, &w->iter, 1));
     }
-    const int64_t kb = (int64_t)T * h->np, pr = 2 * (int64_t)T * M;
+    const int64_t kb = (int64_t)nprob * h->np, pr = 2 * (int64_t)T * M;
     if (w->kb_cap < kb) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         dev_free(h, &w->kb, w->kb_cap);
@@ -1770,6 +1775,8 @@ static int vgp_ws(gpimhip_ctx* h, int T, int64_t M, VgpWs** out) {
     *out = w;
     return GPIMHIP_OK;
 }
+// the problems per task: 2^r in reflection mode (r = the reflected axes), else 1
+static int vgp_nrep(const gpimhip_ctx* h) { return h->refl.mask ? 1 << __builtin_popcount(h->refl.mask) : 1; }
 static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
                      int64_t N) {
     if (!h || !m || !vg || !X || !Y || N < 1) return GPIMHIP_E_BADARG;
@@ -1784,34 +1791,44 @@ static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp
         gpim_set_error("the multi-output GP takes 1 .. 16 tasks and an IndexKernel rank of 1 .. tasks");
         return GPIMHIP_E_BADARG;
     }
-    if (h->refl.mask) {
-        gpim_set_error("the multi-output GP needs a handle without reflection blocks (gpimhip_set_reflection(h, 0, ...))");
+    if (h->refl.mask && (h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw || border_on(h))) {
+        gpim_set_error("the multi-output GP in reflection mode needs all 2^r blocks on one handle (unsharded) and no border");
         return GPIMHIP_E_BADARG;
     }
     return GPIMHIP_OK;
 }
 // Loss and gradient at u (and, fit mode, one Adam step): setup -> z -> the T blocks' K, L, L^-1, z, beta -> K^-1 ->
 // gradient contraction -> K beta -> finalize.  Every launch reads its iteration-dependent values from the device.
+// Reflection mode: the same sequence on the T 2^r blocks A_{t,b} of N = N_q points each.
 static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, VgpWs* w, const double* X,
                     const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIterV fi) {
     const int64_t np = h->np;
     const int T = vg->tasks;
-    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st));
-    GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
+    const bool refl = h->refl.mask != 0;
+    const int nrep = vgp_nrep(h);
+    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, nrep));
+    if (refl) GP_TRY(launch_vgp_project_refl(h, Y, N, T, nrep, w->st));
+    else GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
     GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
-    GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
-    GP_TRY(launch_vgp_kbeta(h, m, X, N, T, w->kb));
+    if (refl) {
+        GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
+        GP_TRY(launch_vgp_kbeta_refl(h, m, X, N, T, nrep, w->kb));
+    } else {
+        GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
+        GP_TRY(launch_vgp_kbeta(h, m, X, N, T, w->kb));
+    }
     AdamStep st;
     st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
-    return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi);
+    return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi,
+                               refl ? nrep : 0);
 }
 static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t M, VgpWs** w) {
     HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = vg->tasks;
+    h->nbatch = vg->tasks * vgp_nrep(h);
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
     GP_TRY(ws_ensure_padded(h, N));
-    return vgp_ws(h, vg->tasks, M, w);
+    return vgp_ws(h, h->nbatch, vg->tasks, M, w);
 }
 
 extern "C" {
@@ -1887,7 +1904,15 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
     VgpWs* w = nullptr;
     GP_TRY(vgp_begin(h, vg, N, M, &w));
     const int T = vg->tasks;
-    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st));
+    if (h->refl.mask) {          // the blocks' posterior summed per task and mixed straight into the M x T outputs
+        const VgpGroup grp{T, vgp_nrep(h), w->st};
+        GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, grp.nrep));
+        GP_TRY(launch_vgp_project_refl(h, Y, N, T, grp.nrep, w->st));
+        GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
+        GP_TRY(predict_cols(h, m, X, 0, N, h->nbatch, Xs, M, mean_out, var_out, &grp));
+        return finish_and_check(h);
+    }
+    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, 1));
     GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
     GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
     double* mblk = w->pred;

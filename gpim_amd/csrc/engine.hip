@@ -12,6 +12,7 @@
 #include <cstring>
 #include <type_traits>
 #include "theta.hpp"
+#include "refl.hpp"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -1198,33 +1199,7 @@ int launch_dist_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, co
 // quadratic forms and log-determinants add up (finalize_coupled_kernel).  Cost of the O(N^3) stages: |G|^-2 of the dense
 // model -- 1/16 in two dimensions.  Exact up to rounding: an orthogonal change of basis.
 // ------------------------------------------------------------------------------------------
-struct ReflPair {
-    double dm2[GPIMHIP_MAX_DIM], dp2[GPIMHIP_MAX_DIM];       // squared scaled differences to z and to its mirror image
-};
-// the dimensions whose sign is -1 in the block of problem pb: bit j of pb belongs to the j-th reflected dimension
-__device__ __forceinline__ int refl_sign_dims(int mask, int pb) {
-    int sg = 0, j = 0;
-#pragma unroll
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k)
-        if ((mask >> k) & 1) {
-            if ((pb >> j) & 1) sg |= 1 << k;
-            ++j;
-        }
-    return sg;
-}
-// f(g, chi, r2) for every reflection g (a subset of mask, as a bit mask over the dimensions); constant trip counts and a
-// wave-uniform skip, so that everything stays in registers (unused dimensions hold zeros in p)
-template <typename F>
-__device__ __forceinline__ void refl_for_each(const ReflPair& p, int mask, int sg, F f) {
-#pragma unroll
-    for (int g = 0; g < (1 << GPIMHIP_MAX_DIM); ++g) {
-        if (g & ~mask) continue;
-        double r2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) r2 += ((g >> k) & 1) ? p.dp2[k] : p.dm2[k];
-        f(g, (__popc(g & sg) & 1) ? -1.0 : 1.0, r2);
-    }
-}
+// ReflPair, refl_sign_dims, refl_for_each: refl.hpp
 template <int KIND>
 __global__ __launch_bounds__(256) void kmat_refl_kernel(const double* __restrict__ X, int64_t N, const double* __restrict__ Z,
                                                         int64_t M, int d, const ThetaDev* __restrict__ th, double* __restrict__ out,

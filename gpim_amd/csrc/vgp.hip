@@ -9,8 +9,16 @@
 //   vgp_kbeta_kernel     (K beta_t)_i for all t (K regenerated, variance 1): the bilinear forms beta_t^T K beta_t'
 //   vgp_finalize_kernel  loss, gradient (no eigenvector derivatives), chain rule to u, Adam step, history row
 //   vgp_combine_kernel   the T x T mix of the blocks' posterior mean / variance
+// Reflection mode (gpimhip_set_reflection): on a complete grid each block A_t splits further into the
+// 2^r reflection blocks A_{t,b} = lambda_t K_b + I of engine.hip's symmetry-reduced model; problem t 2^r + b of the batch is
+// task t with sign pattern b, and each task's sums run over its 2^r consecutive problems:
+//   vgp_project_refl_kernel   z_{t,b} = sum_a P_at (ys_{a,b} - mu_a u_b), u_b = U 1
+//   vgp_kbeta_refl_kernel     K_b beta_{t,b} for all t (K_b regenerated as kmat_refl_kernel builds it, variance 1)
+//   vgp_finalize_kernel<1>    the finalize step with the per-task sums over the blocks and the grid's N
+//   vgp_group_combine_kernel  the blocks' posterior summed per task, then the mix of vgp_combine_kernel
 // Every reduction has a fixed shape: results are bit-reproducible run to run.
 #include "kfun.hpp"
+#include "refl.hpp"
 #include "vgp.hpp"
 
 // softplus as torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
@@ -33,7 +41,7 @@ __device__ __forceinline__ void vgp_lengthscale(const gpimhip_model_t& m, int ls
 // setup: one workgroup of 64 threads
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void vgp_setup_kernel(gpimhip_model_t m, gpimhip_vgp_t vg, const double* __restrict__ u,
-                                                       VgpDev* __restrict__ st, ThetaDev* __restrict__ theta) {
+                                                       VgpDev* __restrict__ st, ThetaDev* __restrict__ theta, int nrep) {
     __shared__ double A[VGP_MAXT][VGP_MAXT + 1];
     __shared__ double V[VGP_MAXT][VGP_MAXT + 1];
     __shared__ double cs[2];
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(64) void vgp_setup_kernel(gpimhip_model_t m, gpimhi
         th.alpha = 1.0;
         th.diag_add = 1.0;
         th.dvar_du = th.dnoise_du = th.dalpha_du = 0.0;
-        theta[t] = th;
+        for (int b = 0; b < nrep; ++b) theta[t * nrep + b] = th;      // (reflection mode: one problem per sign pattern)
     }
 }
 
@@ -224,6 +232,92 @@ __global__ __launch_bounds__(256) void vgp_kbeta_kernel(const double* __restrict
         for (int t = 0; t < T; ++t) kb[(int64_t)t * np + i] = (red[0][t][lane] + red[1][t][lane]) + (red[2][t][lane] + red[3][t][lane]);
 }
 
+// reflection mode: z_{t,b} = sum_a P_at (ys_{a,b} - mu_a u_b) with u_b = U 1 = sqrt(B) w_0 in block 0 and 0 in the others;
+// zero on the padding rows and where the point does not exist in the block (w_b = 0: an identity row of A_{t,b}).
+// grid (np / 256, T nrep); Y: T x nrep x N (task-major, then sign pattern); wts: the weights of block b at b N (or null: all 1)
+__global__ __launch_bounds__(256) void vgp_project_refl_kernel(const double* __restrict__ Y, int64_t N, int64_t np, int T,
+                                                               int nrep, const double* __restrict__ wts,
+                                                               const VgpDev* __restrict__ st, double* __restrict__ z) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int p = blockIdx.y, t = p / nrep, b = p % nrep;
+    if (i >= np) return;
+    double v = 0.0;
+    if (i < N) {
+        const double wb = wts ? wts[(int64_t)b * N + i] : 1.0;
+        const double ub = (b == 0) ? sqrt((double)nrep) * wb : 0.0;
+        if (wb != 0.0)
+            for (int a = 0; a < T; ++a)
+                v = fma(st->P[a * VGP_MAXT + t], Y[((int64_t)a * nrep + b) * N + i] - st->mu[a] * ub, v);
+    }
+    z[(int64_t)p * np + i] = v;
+}
+
+// reflection mode: kb[p][i] = sum_j K_b[i, j] beta_p[j] for the T problems p = t nrep + b of block b (grid.y), i < N, with
+// K_b[i, j] = w_b,i w_b,j sum_g chi_b(g) k(x_i, g x_j) at variance 1 -- regenerated the way kmat_refl_kernel builds it (the
+// rows of absent points come out 0; their beta is 0).  N^2 kernel evaluations over all blocks, as vgp_kbeta_kernel does
+// on the dense model.  One workgroup: 64 rows; the columns go through LDS 256 at a time, wave w taking the fourth w of
+// them; the four waves' sums are added in wave order.
+template <int KIND>
+__global__ __launch_bounds__(256) void vgp_kbeta_refl_kernel(const double* __restrict__ X, int64_t N, int d, int64_t np, int T,
+                                                             int nrep, ReflArgs refl, const ThetaDev* __restrict__ th,
+                                                             const double* __restrict__ beta, double* __restrict__ kb) {
+    __shared__ double xs[256][GPIMHIP_MAX_DIM];
+    __shared__ double ws[256];
+    __shared__ double bs[VGP_MAXT][256];
+    double (*red)[VGP_MAXT][64] = reinterpret_cast<double (*)[VGP_MAXT][64]>(&bs[0][0]);     // after the column loop
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y;
+    const int sg = refl_sign_dims(refl.mask, b);
+    const double* wts = refl.wts ? refl.wts + (int64_t)b * N : nullptr;
+    const ThetaDev t0 = th[0];
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    double a[GPIMHIP_MAX_DIM], cz[GPIMHIP_MAX_DIM];
+#pragma unroll
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+        a[k] = (k < d && i < N) ? X[i * d + k] / t0.ls[k] : 0.0;
+        cz[k] = (k < d) ? refl.twoc[k] / t0.ls[k] : 0.0;
+    }
+    const double wi = (wts && i < N) ? wts[i] : 1.0;
+    double acc[VGP_MAXT];
+#pragma unroll
+    for (int t = 0; t < VGP_MAXT; ++t) acc[t] = 0.0;
+    for (int64_t j0 = 0; j0 < N; j0 += 256) {
+        __syncthreads();
+        {
+            const int64_t j = j0 + tid;
+#pragma unroll
+            for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) xs[tid][k] = (k < d && j < N) ? X[j * d + k] / t0.ls[k] : 0.0;
+            ws[tid] = (wts && j < N) ? wts[j] : 1.0;
+            for (int t = 0; t < T; ++t) bs[t][tid] = (j < N) ? beta[((int64_t)t * nrep + b) * np + j] : 0.0;
+        }
+        __syncthreads();
+        const int jn = (int)((N - j0 < 256) ? (N - j0) : 256);
+        for (int jj = wave * 64; jj < wave * 64 + 64 && jj < jn; ++jj) {
+            ReflPair p;
+#pragma unroll
+            for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+                const double dm = a[k] - xs[jj][k], dp = (a[k] + xs[jj][k]) - cz[k];
+                p.dm2[k] = dm * dm;
+                p.dp2[k] = dp * dp;
+            }
+            double s = 0.0;
+            refl_for_each(p, refl.mask, sg, [&](int, double chi, double r2) { s = fma(chi, kfun_value<KIND>(r2, 1.0), s); });
+            const double k = s * ws[jj];
+#pragma unroll
+            for (int t = 0; t < VGP_MAXT; ++t)
+                if (t < T) acc[t] = fma(k, bs[t][jj], acc[t]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < VGP_MAXT; ++t)
+        if (t < T) red[wave][t][lane] = acc[t];
+    __syncthreads();
+    if (wave == 0 && i < N)
+        for (int t = 0; t < T; ++t)
+            kb[((int64_t)t * nrep + b) * np + i] = wi * ((red[0][t][lane] + red[1][t][lane]) + (red[2][t][lane] + red[3][t][lane]));
+}
+
 // NQ block sums of 256 threads at once (fixed tree); arr: NQ x 256 doubles of LDS; results in out[0 .. NQ)
 template <int NQ>
 __device__ __forceinline__ void vgp_sum_multi(const double* v, double* arr, double* out) {
@@ -256,9 +350,14 @@ __device__ __forceinline__ void vgp_sum_multi(const double* v, double* arr, doub
 //                 lg_t = sum log diag L_t, sig_t = sum_i beta_t,i;  pairs: H_tt' = beta_t^T beta_t', G_tt' = beta_t^T K beta_t'
 //   dL/dB_ab = 1/2 [sum_t P_at P_bt tr(M_t K) - (P G P^T)_ab],  dL/ds_a = 1/2 [sum_t P_at^2 tr(M_t) - (P H P^T)_aa]
 //   dL/dl_k  = 1/2 sum_t lambda_t Sg_t[1+k] / l_k,            dL/dmu_a = -sum_t P_at sig_t
+// REFL (reflection mode): task t is the nrep problems t nrep .. t nrep + nrep - 1; every per-task quantity is the sum over
+// them (each thread runs through the blocks in order before the fixed tree), sig_t = sum_b u_b^T beta_{t,b} =
+// sqrt(nrep) w_0^T beta_{t,0}; ntot = the grid's N (the dense model: ntot = N)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gpimhip_vgp_t vg, int64_t N, int64_t np, int nb,
-                                                           int ntile, const double* __restrict__ grad_part,
+template <bool REFL>
+__global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gpimhip_vgp_t vg, int64_t N, int64_t ntot,
+                                                           int64_t np, int nb, int ntile, int nrep, const double* __restrict__ wts,
+                                                           const double* __restrict__ grad_part,
                                                            const double* __restrict__ z, const double* __restrict__ logdet_part,
                                                            const double* __restrict__ beta, const double* __restrict__ kb,
                                                            const VgpDev* __restrict__ st, double* __restrict__ u,
@@ -278,13 +377,30 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
     const VgpLayout L = vgp_layout(m, vg);
     for (int t = 0; t < T; ++t) {
         double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        double w[2] = {0, 0};
+        if (REFL) {
+            for (int b = 0; b < nrep; ++b) {
+                const int64_t p = (int64_t)t * nrep + b;
+                const double* gp = grad_part + p * ntile * 8;
+                for (int q = tid; q < ntile; q += 256)
+                    for (int k = 0; k < 7; ++k) v[k] += gp[(int64_t)q * 8 + k];
+                const double* zt = z + p * np;
+                for (int64_t i = tid; i < np; i += 256) v[7] = fma(zt[i], zt[i], v[7]);
+                for (int k = tid; k < nb; k += 256) w[0] += logdet_part[p * nb + k];
+            }
+            const double* bt = beta + (int64_t)t * nrep * np;
+            const double sq = sqrt((double)nrep);
+            for (int64_t i = tid; i < N; i += 256) w[1] = fma(sq * (wts ? wts[i] : 1.0), bt[i], w[1]);
+            vgp_sum_multi<8>(v, arr, &Sg[t][0]);
+            vgp_sum_multi<2>(w, arr, &lgs[t][0]);
+            continue;
+        }
         const double* gp = grad_part + (int64_t)t * ntile * 8;
         for (int q = tid; q < ntile; q += 256)
             for (int k = 0; k < 7; ++k) v[k] += gp[(int64_t)q * 8 + k];
         const double* zt = z + (int64_t)t * np;
         for (int64_t i = tid; i < np; i += 256) v[7] = fma(zt[i], zt[i], v[7]);
         vgp_sum_multi<8>(v, arr, &Sg[t][0]);
-        double w[2] = {0, 0};
         for (int k = tid; k < nb; k += 256) w[0] += logdet_part[(int64_t)t * nb + k];
         const double* bt = beta + (int64_t)t * np;
         for (int64_t i = tid; i < N; i += 256) w[1] += bt[i];
@@ -301,13 +417,25 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
                 if (q >= npair) { pt[e] = -1; pu[e] = -1; continue; }
                 while (q >= T - t) { q -= T - t; ++t; }
                 pt[e] = t; pu[e] = t + q;
-                const double* bt = beta + (int64_t)t * np;
-                const double* bu = beta + (int64_t)(t + q) * np;
-                const double* ku = kb + (int64_t)(t + q) * np;
                 double h = 0.0, g = 0.0;
-                for (int64_t i = tid; i < N; i += 256) {
-                    h = fma(bt[i], bu[i], h);
-                    g = fma(bt[i], ku[i], g);
+                if (REFL) {          // H_tt' = sum_b beta_{t,b}^T beta_{t',b}, G_tt' = sum_b beta_{t,b}^T K_b beta_{t',b}
+                    for (int b = 0; b < nrep; ++b) {
+                        const double* bt = beta + ((int64_t)t * nrep + b) * np;
+                        const double* bu = beta + ((int64_t)(t + q) * nrep + b) * np;
+                        const double* ku = kb + ((int64_t)(t + q) * nrep + b) * np;
+                        for (int64_t i = tid; i < N; i += 256) {
+                            h = fma(bt[i], bu[i], h);
+                            g = fma(bt[i], ku[i], g);
+                        }
+                    }
+                } else {
+                    const double* bt = beta + (int64_t)t * np;
+                    const double* bu = beta + (int64_t)(t + q) * np;
+                    const double* ku = kb + (int64_t)(t + q) * np;
+                    for (int64_t i = tid; i < N; i += 256) {
+                        h = fma(bt[i], bu[i], h);
+                        g = fma(bt[i], ku[i], g);
+                    }
                 }
                 v[2 * e] = h;
                 v[2 * e + 1] = g;
@@ -340,7 +468,7 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
     }
     __syncthreads();
     if (skip) return;
-    const double inv_nt = 1.0 / ((double)N * (double)T);
+    const double inv_nt = 1.0 / ((double)ntot * (double)T);
     // (P G)_{a t'} -> X, then dL/dB and dL/ds
     if (tid < T * T) {
         const int a = tid / T, c = tid % T;
@@ -431,7 +559,7 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
         lg += lgs[t][0];
         q2 += Sg[t][7];
     }
-    const double loss = (0.5 * (double)N * slog + lg + 0.5 * q2) * inv_nt + 0.5 * 1.8378770664093453;
+    const double loss = (0.5 * (double)ntot * slog + lg + 0.5 * q2) * inv_nt + 0.5 * 1.8378770664093453;
     int it = 0;
     if (fi.iter) {
         it = *fi.iter;
@@ -475,17 +603,74 @@ __global__ __launch_bounds__(256) void vgp_combine_kernel(int T, int64_t M, cons
     }
 }
 
+// reflection mode, one chunk of test points: the blocks' posterior summed per task (mean_t = sum_b k*_{t,b}^T beta_{t,b},
+// var_t = lambda_t + 1 - sum_b |L_{t,b}^-1 k*_{t,b}|^2 over the nrep consecutive problems of task t; mean_tmp: ldp per
+// problem, colpart: nb x ldp per problem), then the mix of vgp_combine_kernel into rows m0 .. m0 + mcount of the M x T outputs
+__global__ __launch_bounds__(256) void vgp_group_combine_kernel(int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount,
+                                                                const double* __restrict__ colpart,
+                                                                const double* __restrict__ mean_tmp,
+                                                                const ThetaDev* __restrict__ th, const VgpDev* __restrict__ st,
+                                                                double* __restrict__ mean_out, double* __restrict__ var_out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= mcount) return;
+    double mb[VGP_MAXT], vb[VGP_MAXT];
+#pragma unroll
+    for (int t = 0; t < VGP_MAXT; ++t) {
+        mb[t] = vb[t] = 0.0;
+        if (t < T) {
+            double mu = 0.0, q = 0.0;
+            for (int b = 0; b < nrep; ++b) {
+                const int64_t p = (int64_t)t * nrep + b;
+                for (int ci = 0; ci < nb; ++ci) q += colpart[(p * nb + ci) * ldp + j];
+                mu += mean_tmp[p * ldp + j];
+            }
+            const ThetaDev& tt = th[t * nrep];
+            mb[t] = mu;
+            vb[t] = clamp0_nan(tt.var - q) + tt.noise;
+        }
+    }
+    for (int a = 0; a < T; ++a) {
+        double mu = 0.0, v = 0.0;
+#pragma unroll
+        for (int t = 0; t < VGP_MAXT; ++t)
+            if (t < T) {
+                const double q = st->Q[a * VGP_MAXT + t];
+                mu = fma(q, mb[t], mu);
+                v = fma(q * q, vb[t], v);
+            }
+        mean_out[(m0 + j) * T + a] = st->mu[a] + st->sqs[a] * mu;
+        var_out[(m0 + j) * T + a] = st->s[a] * v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st) {
-    hipLaunchKernelGGL(vgp_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, *vg, u, st, h->theta);
+int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep) {
+    hipLaunchKernelGGL(vgp_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, *vg, u, st, h->theta, nrep);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
 int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st) {
     hipLaunchKernelGGL(vgp_project_kernel, dim3((unsigned)((h->np + 255) / 256), T), dim3(256), 0, h->stream, Y, N, h->np, T, st,
                        h->ypad);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const VgpDev* st) {
+    hipLaunchKernelGGL(vgp_project_refl_kernel, dim3((unsigned)((h->np + 255) / 256), T * nrep), dim3(256), 0, h->stream, Y, N,
+                       h->np, T, nrep, h->refl.wts, st, h->ypad);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_kbeta_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, int nrep, double* kb) {
+    const dim3 grid((unsigned)((N + 63) / 64), nrep);
+    if (m->kernel == GPIMHIP_KERNEL_RBF)
+        hipLaunchKernelGGL(vgp_kbeta_refl_kernel<GPIMHIP_KERNEL_RBF>, grid, dim3(256), 0, h->stream, X, N, m->dim, h->np, T, nrep,
+                           h->refl, h->theta, h->alpha, kb);
+    else
+        hipLaunchKernelGGL(vgp_kbeta_refl_kernel<GPIMHIP_KERNEL_MATERN52>, grid, dim3(256), 0, h->stream, X, N, m->dim, h->np, T,
+                           nrep, h->refl, h->theta, h->alpha, kb);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -502,11 +687,16 @@ int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
 }
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
-                        double* loss_out, double* grad_out, FinalizeIterV fi) {
+                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep) {
     const int nb = (int)(h->np / NB);
-    hipLaunchKernelGGL(vgp_finalize_kernel, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, h->np, nb, nb * (nb + 1) / 2,
-                       h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u, adam_m, adam_v, do_adam, ast, loss_out, grad_out,
-                       (double*)nullptr, fi, h->info);
+    if (nrep > 0)
+        hipLaunchKernelGGL(vgp_finalize_kernel<true>, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, h->refl.n_total, h->np, nb,
+                           nb * (nb + 1) / 2, nrep, h->refl.wts, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u, adam_m,
+                           adam_v, do_adam, ast, loss_out, grad_out, (double*)nullptr, fi, h->info);
+    else
+        hipLaunchKernelGGL(vgp_finalize_kernel<false>, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, N, h->np, nb,
+                           nb * (nb + 1) / 2, 1, (const double*)nullptr, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u,
+                           adam_m, adam_v, do_adam, ast, loss_out, grad_out, (double*)nullptr, fi, h->info);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -514,6 +704,13 @@ int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const
                        double* mean_out, double* var_out) {
     hipLaunchKernelGGL(vgp_combine_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, T, M, st, mblk, vblk,
                        mean_out, var_out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_group_combine(gpimhip_ctx* h, int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount, const VgpDev* st,
+                             double* mean_out, double* var_out) {
+    hipLaunchKernelGGL(vgp_group_combine_kernel, dim3((unsigned)((mcount + 255) / 256)), dim3(256), 0, h->stream, T, nrep, nb, ldp,
+                       m0, mcount, h->colpart, h->mean_tmp, h->theta, st, mean_out, var_out);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

@@ -148,6 +148,22 @@ def reflection_blocks(X, y, axes):
             "n_total": int(y.size), "dims": dims, "fund_flat": fund_flat, "rep": rep}
 
 
+def reflection_blocks_multi(X, Y, axes):
+    """The reflection blocks of a multi-output GP on a COMPLETE grid (gpim_amd extension: vreconstructor's 'reflection'
+    solver).  X (d, n_1, ..., n_d), Y (n_1, ..., n_d, T), axes as for ``reflection_blocks``.
+
+    Returns the dict of ``reflection_blocks`` with ys of shape (T, B, Nq) -- task a in the adapted basis, task-major then
+    sign pattern -- and ones (B, Nq) = U 1, the basis change of the constant (sqrt(B) w_0 in block 0, 0 in the others; the
+    task means enter the blocks through it).  Raises ValueError if no axis is symmetric."""
+    Y = np.asarray(Y, dtype=np.float64)
+    T = Y.shape[-1]
+    S = reflection_blocks(X, np.ones(Y.shape[:-1]), axes)
+    ones = S["ys"]
+    S["ys"] = np.stack([reflection_blocks(X, Y[..., a], axes)["ys"] for a in range(T)]) if T else np.empty((0,) + ones.shape)
+    S["ones"] = ones
+    return S
+
+
 def complete_grid(X, y):
     """The complete product grid behind an incomplete one (gpim_amd extension: the border form of the reflection blocks,
     reconstructor's exact GP on the observed points of an image or cube with missing pixels).

@@ -20,6 +20,12 @@ Readings and deliberate differences, in one place:
     error of roughly 7 %).  ``n_samples``, ``num_batches`` and ``max_root`` / ``maxroot`` are accepted and ignored.
   * Matern52 uses the engine's form of the covariance function (csrc/kfun.hpp: r = sqrt(r2 + 1e-12)), which differs from
     GPyTorch's by at most ~2.5e-12 per entry.
+
+Solver (``rec.solver``), chosen from the data alone: 'reflection' when X is a complete product grid (no NaN in y) with at
+least one axis whose coordinates are symmetric about its centre -- each task block then splits further into the 2^r
+reflection blocks of gprutils.reflection_blocks_multi, 1 / 4^r of the dense flops and 1 / 2^r of its memory (DESIGN.md
+section 12); 'dense' for anything else (scattered points, rows with NaN, no symmetric axis).  Both compute the same model:
+the numbers agree to rounding.
 """
 import ctypes
 import time
@@ -30,6 +36,7 @@ import torch
 
 from . import _lib
 from . import gprutils
+from .gpr import reconstructor
 
 _F64 = torch.float64
 _KERNELS = {"RBF": 0, "Matern52": 1}
@@ -140,14 +147,53 @@ class vreconstructor:
             o, _ = raw_layout(T, n_ls, False)
             u[o["F"]] = torch.randn(T, 1, dtype=_F64).reshape(-1)
         self._u = u.to(self._dev)
-        self._Xd = self.X.to(self._dev, _F64).contiguous()
-        self._Yd = self.y.to(self._dev, _F64).t().contiguous()        # T x N, task-major
+        self._refl = self._reflection_blocks(X, y)
+        self.solver = "dense" if self._refl is None else "reflection"
+        if self._refl is None:
+            self._Xd = self.X.to(self._dev, _F64).contiguous()
+            self._Yd = self.y.to(self._dev, _F64).t().contiguous()        # T x N, task-major
+        else:       # the fundamental domain, the targets as T x 2^r x N_q, the weights tiled once per task (T 2^r x N_q)
+            S = self._refl
+            self._Xd = torch.from_numpy(np.ascontiguousarray(S["Xq"])).to(self._dev, _F64).contiguous()
+            self._Yd = torch.from_numpy(np.ascontiguousarray(S["ys"])).to(self._dev, _F64).contiguous()
+            self._wts_d = None if S["wts"] is None else \
+                torch.from_numpy(np.ascontiguousarray(np.tile(S["wts"], (T, 1)))).to(self._dev, _F64).contiguous()
+            self._twoc = (ctypes.c_double * 4)(*S["twoc"])
         self.iterations = iterations
         self.learning_rate = learning_rate
         self.lscales = []
         self.loss_all = []
         self.hyperparams = {"lengthscale": self.lscales}
         self.verbose = verbose
+
+    @staticmethod
+    def _reflection_blocks(X, y):
+        """gprutils.reflection_blocks_multi of the data when X (d, n_1, ..., n_d) is a product grid of y's shape, y has no
+        NaN and some axis is symmetric; otherwise None (the dense solver)."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if np.isnan(y).any() or np.isnan(X).any() or X.shape[1:] != y.shape[:-1]:
+            return None
+        try:
+            axes, _ = reconstructor._grid_axes(X)
+            return gprutils.reflection_blocks_multi(X, y, axes)
+        except (NotImplementedError, ValueError):
+            return None
+
+    def _engine(self, fn, *args):
+        """fn(h, m, vg, X, Y, N, *args) on the handle; in reflection mode (set around this call only) X is the fundamental
+        domain and Y the projected targets."""
+        lib, h = self._handle.lib, self._handle.h
+        call = lambda: fn(h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd), _lib.ptr(self._Yd),
+                          self._Xd.shape[0], *args)
+        S = self._refl
+        if S is None:
+            return call()
+        _lib.check(lib.gpimhip_set_reflection(h, S["mask"], self._twoc, _lib.ptr(self._wts_d), S["n_total"], 0))
+        try:
+            return call()
+        finally:
+            _lib.check(lib.gpimhip_set_reflection(h, 0, None, None, 0, 0))
 
     # ------------------------------------------------------------------ parameters
     def _params(self):
@@ -174,9 +220,7 @@ class vreconstructor:
         u = self._u if u is None else torch.as_tensor(u, dtype=_F64).to(self._dev).contiguous()
         loss = torch.empty(1, dtype=_F64, device=self._dev)
         grad = torch.empty(u.numel(), dtype=_F64, device=self._dev)
-        _lib.check(self._handle.lib.gpimhip_vgp_nll_grad(
-            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
-            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
+        _lib.check(self._engine(self._handle.lib.gpimhip_vgp_nll_grad, _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
         return float(loss.item()), grad.cpu().numpy()
 
     # ------------------------------------------------------------------ training
@@ -194,10 +238,8 @@ class vreconstructor:
         start_time = time.time()
         hist = torch.empty((max(T, 1), self._n_ls), dtype=_F64, device=self._dev)
         loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
-        rc = self._handle.lib.gpimhip_fit_vgp(
-            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
-            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist),
-            _lib.ptr(loss))
+        rc = self._engine(self._handle.lib.gpimhip_fit_vgp, _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist),
+                          _lib.ptr(loss))
         failed = rc == _lib.E_NOT_PD
         if failed:
             T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
@@ -241,9 +283,8 @@ class vreconstructor:
         M = Xs.shape[0]
         mean = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
         var = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
-        _lib.check(self._handle.lib.gpimhip_predict_vgp(
-            self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd),
-            _lib.ptr(self._Yd), self._Xd.shape[0], _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean), _lib.ptr(var)))
+        _lib.check(self._engine(self._handle.lib.gpimhip_predict_vgp, _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean),
+                                _lib.ptr(var)))
         sd = torch.sqrt(var)
         mean, sd = mean.cpu().numpy().reshape(self.fulldims), sd.cpu().numpy().reshape(self.fulldims)
         if self.verbose:

@@ -187,7 +187,13 @@ int gpimhip_predict_exact_batched(gpimhip_handle h, const gpimhip_model_t* m,
  *                          step (vgpr.py:169-174), loss_out: T_iter losses BEFORE each step (either may be NULL)
  *   gpimhip_predict_vgp    the exact predictive mean and variance of likelihood(model(Xs)) (noise included) at M test
  *                          points (NaN rows give NaN), M x T each (task fastest).  Replaces the 100-sample Monte-Carlo
- *                          estimate of vgpr.py:213-221 by the quantities it estimates. */
+ *                          estimate of vgpr.py:213-221 by the quantities it estimates.
+ * Reflection mode (gpimhip_set_reflection(h, mask, twoc, wts, n_total, 0) on a complete grid): each
+ * task block splits into the B = 2^popcount(mask) reflection blocks, T B problems in all, problem t B + b = task t with sign
+ * pattern b.  Then X is the fundamental domain (N = its N_q points), Y is T x B x N_q (task-major, then sign pattern:
+ * y_a in the adapted basis, gpim_amd.gprutils.reflection_blocks_multi), wts (or NULL) is T B x N_q -- the B x N_q weights
+ * repeated once per task -- and n_total the grid's N.  u, the loss, the gradient, hist_out / loss_out, Xs, mean_out and
+ * var_out (M x T) are as in dense mode.  A sharded handle (gpimhip_set_reflection_shard) or a border gives BADARG. */
 #define GPIMHIP_VGP_MAX_TASKS 16
 typedef struct {
     int32_t tasks;          /* T, 1 .. GPIMHIP_VGP_MAX_TASKS                                        */
@@ -455,6 +461,7 @@ int gpimhip_dist_finalize_dev(gpimhip_handle h, const gpimhip_model_t* m, int64_
  * var_count > 0: predictions compute the variance for the first var_count test points only (var_out keeps M entries; the
  * others are not written) -- the posterior variance is invariant under the reflections, so a caller predicting on the
  * training grid orders the fundamental domain first and mirrors the result (gpim_amd/gpr.py).
+ * The multi-output GP (gpimhip_vgp_nll_grad / gpimhip_fit_vgp / gpimhip_predict_vgp) honours the mode too: see there.
  * mask = 0 switches back.  Double precision only. */
 int gpimhip_set_reflection(gpimhip_handle h, int32_t mask, const double* twoc, const double* wts, int64_t n_total,
                            int64_t var_count);
