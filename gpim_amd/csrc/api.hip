@@ -467,13 +467,14 @@ static bool border_on(const gpimhip_ctx* h) { return h->refl.mask && h->border &
 static void border_free_bufs(gpimhip_ctx* h, BorderWs* w) {
     dev_free(h, &w->C, (int64_t)w->B * w->np * w->mp);
     dev_free(h, &w->Y, (int64_t)w->B * w->np * w->mp);
-    dev_free(h, &w->tv, 2 * w->mp);
-    dev_free(h, &w->scal, 2);
+    dev_free(h, &w->tv, 2 * w->mp * w->T);
+    dev_free(h, &w->scal, 2 * w->T);
+    dev_free(h, &w->uo, w->uo_n);
     dev_free(h, &w->tiles_y, w->n_y);
     dev_free(h, &w->tiles_upd, w->n_upd);
-    dev_free(h, &w->R, w->mp * w->r_cols);
-    dev_free(h, &w->rsq, w->r_cols);
-    w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0;
+    dev_free(h, &w->R, w->mp * w->r_cols * w->T);
+    dev_free(h, &w->rsq, w->r_cols * w->T);
+    w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0; w->uo_n = 0;
 }
 void border_release(gpimhip_ctx* h) {
     BorderWs* w = bws(h);
@@ -484,20 +485,19 @@ void border_release(gpimhip_ctx* h) {
     h->border = nullptr;
 }
 
-// buffers for the workspace's np and batch (outside any capture: allocations and tile-list uploads synchronise)
-static int border_ensure(gpimhip_ctx* h) {
+// buffers for the workspace's np and batch (outside any capture: allocations and tile-list uploads synchronise).
+// T: the borders in lock-step (the tasks of the multi-output GP: the batch is T 2^r blocks; otherwise 1)
+static int border_ensure(gpimhip_ctx* h, int T = 1) {
     BorderWs* w = bws(h);
     const int64_t mp = pad_to(w->M, NB);
-    if (!w->sub) {
-        GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
-        w->sub->nbatch = 1;
-    }
+    if (!w->sub) GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
+    w->sub->nbatch = T;
     w->sub->stream = h->stream;
-    GP_TRY(ws_ensure_b(w->sub, w->M, 1, 1));
-    if (w->np == h->np && w->B == h->nbatch && w->mp == mp && w->C) return GPIMHIP_OK;
+    GP_TRY(ws_ensure_b(w->sub, w->M, T, 1));
+    if (w->np == h->np && w->B == h->nbatch && w->T == T && w->mp == mp && w->C) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
     border_free_bufs(h, w);
-    w->mp = mp; w->np = h->np; w->B = h->nbatch;
+    w->mp = mp; w->np = h->np; w->B = h->nbatch; w->T = T;
     const int nb = (int)(h->np / NB), nm = (int)(mp / NB);
     std::vector<TileDesc> ty, tu;
     for (int ci = 0; ci < nb; ++ci)
@@ -507,7 +507,7 @@ static int border_ensure(gpimhip_ctx* h) {
     w->n_upd = (int)tu.size();
     int rc = GPIMHIP_OK;
     if ((rc = dev_alloc(h, &w->C, (int64_t)w->B * w->np * mp)) || (rc = dev_alloc(h, &w->Y, (int64_t)w->B * w->np * mp)) ||
-        (rc = dev_alloc(h, &w->tv, 2 * mp)) || (rc = dev_alloc(h, &w->scal, 2)) || (rc = dev_alloc(h, &w->tiles_y, w->n_y)) ||
+        (rc = dev_alloc(h, &w->tv, 2 * mp * T)) || (rc = dev_alloc(h, &w->scal, 2 * T)) || (rc = dev_alloc(h, &w->tiles_y, w->n_y)) ||
         (rc = dev_alloc(h, &w->tiles_upd, w->n_upd))) {
         border_free_bufs(h, w);
         return rc;
@@ -521,12 +521,12 @@ static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
     BorderWs* w = bws(h);
     if (w->r_cols >= cols && w->R) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    dev_free(h, &w->R, w->mp * w->r_cols);
-    dev_free(h, &w->rsq, w->r_cols);
+    dev_free(h, &w->R, w->mp * w->r_cols * w->T);
+    dev_free(h, &w->rsq, w->r_cols * w->T);
     w->r_cols = 0;
     int rc = GPIMHIP_OK;
-    if ((rc = dev_alloc(h, &w->R, w->mp * cols)) || (rc = dev_alloc(h, &w->rsq, cols))) {
-        dev_free(h, &w->R, w->mp * cols);
+    if ((rc = dev_alloc(h, &w->R, w->mp * cols * w->T)) || (rc = dev_alloc(h, &w->rsq, cols * w->T))) {
+        dev_free(h, &w->R, w->mp * cols * w->T);
         return rc;
     }
     w->r_cols = cols;
@@ -535,6 +535,7 @@ static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
 
 // After the blocks' inverses are in h->B (launch_lauum): S, L_S^-1, Y_b = C_b L_S^-T, the corrected alpha, the two loss
 // scalars, and (training) B_b^-1 -= Y_b Y_b^T on the lower tiles.  nq: the points of the fundamental domain.
+// With T borders (BorderWs::T) all of it runs per task in lock-step: sub factors the T matrices S_t as one batch.
 static int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
     BorderWs* w = bws(h);
     gpimhip_ctx* sub = w->sub;
@@ -546,9 +547,10 @@ static int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
     GP_TRY(launch_border_tidy(h, w, sub->A, sub->ld));
     GP_TRY(launch_border_gather_c(h, w, h->B, h->ld, nq));
     {
-        // Y = C L_S^-T (NT: operand B is L_S^-1, shared by the blocks)
+        // Y = C L_S^-T (NT: operand B is L_S^-1 of the problem's task, shared by the task's blocks)
         GemmArgs g = gemm_args(w->C, mp, sub->A, sub->ld, w->Y, mp, 1.0, 0.0, w->tiles_y, w->n_y, h->np);
-        g.sB = 0;
+        g.sB = sub->np * sub->ld;
+        g.bshift = __builtin_ctz((unsigned)(h->nbatch / w->T));         // (2^r blocks per task)
         g.chunk = deal_chunk(g.ntiles);
         GP_TRY(launch_gemm(h, false, false, EPI_STORE, g));
     }
@@ -829,7 +831,12 @@ int gpimhip_destroy(gpimhip_handle h) {
     return GPIMHIP_OK;
 }
 
-int64_t gpimhip_workspace_bytes(gpimhip_handle h) { return h ? h->bytes : 0; }
+// (with a border: the handle of S is part of the model's workspace)
+int64_t gpimhip_workspace_bytes(gpimhip_handle h) {
+    if (!h) return 0;
+    const BorderWs* w = bws(h);
+    return h->bytes + (w && w->sub ? w->sub->bytes : 0);
+}
 
 int gpimhip_timing_enable(gpimhip_handle h, int enable) {
     if (!h) return GPIMHIP_E_BADARG;
@@ -1026,22 +1033,27 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
         const double* radd = nullptr;
         if (bd) {
-            // R = sum_b Y_b^T K*_b: the stacked blocks of Y and of the slab are (B np)-row matrices (TN, one problem)
+            // R = sum_b Y_b^T K*_b: the stacked blocks of Y and of the slab are (B np)-row matrices (TN, one problem per
+            // border: sub's batch -- the multi-output GP's tasks, each with its 2^r blocks and K* at its own variance)
             BorderWs* w = bws(h);
             w->sub->stream = h->stream;
+            const int64_t brows = (int64_t)(B / w->T) * np;
             GemmArgs gr = gemm_args(w->Y, w->mp, h->Ks, kld, w->R, w->r_cols, 1.0, 0.0, nullptr, 0, 0);
-            gr.sA = gr.sB = gr.sC = 0;
+            gr.sA = brows * w->mp;
+            gr.sB = brows * kld;
+            gr.sC = w->mp * w->r_cols;
             gr.rect_rows = (int)(w->mp / NB);
             gr.rect_cols = (int)(cpad / NB);
             gr.ntiles = gr.rect_rows * gr.rect_cols;
             gr.kfix0 = 0;
-            gr.kfix1 = (int)((int64_t)B * np / NB);
+            gr.kfix1 = (int)(brows / NB);
             gr.chunk = deal_chunk(gr.ntiles);
             GP_TRY(launch_gemm(w->sub, true, true, EPI_STORE, gr));
             GP_TRY(launch_border_colsumsq(h, w, cnt));
             radd = w->rsq;
         }
-        if (vgrp) GP_TRY(launch_vgp_group_combine(h, vgrp->T, vgrp->nrep, nb, mcap, m0, cnt, vgrp->st, mean_out, var_out));
+        if (vgrp) GP_TRY(launch_vgp_group_combine(h, vgrp->T, vgrp->nrep, nb, mcap, m0, cnt, vgrp->st, mean_out, var_out, radd,
+                                                 bd ? bws(h)->r_cols : 0));
         else if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
         else GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
@@ -1791,8 +1803,8 @@ static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp
         gpim_set_error("the multi-output GP takes 1 .. 16 tasks and an IndexKernel rank of 1 .. tasks");
         return GPIMHIP_E_BADARG;
     }
-    if (h->refl.mask && (h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw || border_on(h))) {
-        gpim_set_error("the multi-output GP in reflection mode needs all 2^r blocks on one handle (unsharded) and no border");
+    if (h->refl.mask && (h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw)) {
+        gpim_set_error("the multi-output GP in reflection mode needs all 2^r blocks on one handle (unsharded)");
         return GPIMHIP_E_BADARG;
     }
     return GPIMHIP_OK;
@@ -1800,6 +1812,8 @@ static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp
 // Loss and gradient at u (and, fit mode, one Adam step): setup -> z -> the T blocks' K, L, L^-1, z, beta -> K^-1 ->
 // gradient contraction -> K beta -> finalize.  Every launch reads its iteration-dependent values from the device.
 // Reflection mode: the same sequence on the T 2^r blocks A_{t,b} of N = N_q points each.
+// With a border (gpimhip_set_border) the T borders S_t correct beta and the inverses after the K^-1
+// product; everything downstream reads the corrected ones.
 static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, VgpWs* w, const double* X,
                     const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIterV fi) {
     const int64_t np = h->np;
@@ -1807,10 +1821,12 @@ static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_
     const bool refl = h->refl.mask != 0;
     const int nrep = vgp_nrep(h);
     GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, nrep));
-    if (refl) GP_TRY(launch_vgp_project_refl(h, Y, N, T, nrep, w->st));
+    const bool bd = border_on(h);
+    if (refl) GP_TRY(launch_vgp_project_refl(h, Y, N, T, nrep, bd ? bws(h)->uo : nullptr, w->st));
     else GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
     GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
+    if (bd) GP_TRY(border_iter(h, N, true));
     if (refl) {
         GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
         GP_TRY(launch_vgp_kbeta_refl(h, m, X, N, T, nrep, w->kb));
@@ -1821,14 +1837,27 @@ static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_
     AdamStep st;
     st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
     return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi,
-                               refl ? nrep : 0);
+                               refl ? nrep : 0, bd ? bws(h)->scal : nullptr);
 }
 static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t M, VgpWs** w) {
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = vg->tasks * vgp_nrep(h);
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
     GP_TRY(ws_ensure_padded(h, N));
-    return vgp_ws(h, h->nbatch, vg->tasks, M, w);
+    GP_TRY(vgp_ws(h, h->nbatch, vg->tasks, M, w));
+    if (!border_on(h)) return GPIMHIP_OK;
+    // the T borders' buffers, and U 1_o for the task means (outside any capture; N = the points of the fundamental domain)
+    GP_TRY(border_ensure(h, vg->tasks));
+    BorderWs* b = bws(h);
+    const int nrep = vgp_nrep(h);
+    if (b->uo_n < (int64_t)nrep * N) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        dev_free(h, &b->uo, b->uo_n);
+        b->uo_n = 0;
+        GP_TRY(dev_alloc(h, &b->uo, (int64_t)nrep * N));
+        b->uo_n = (int64_t)nrep * N;
+    }
+    return launch_border_ones(h, b, N, nrep, b->uo);
 }
 
 extern "C" {
@@ -1907,8 +1936,13 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
     if (h->refl.mask) {          // the blocks' posterior summed per task and mixed straight into the M x T outputs
         const VgpGroup grp{T, vgp_nrep(h), w->st};
         GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, grp.nrep));
-        GP_TRY(launch_vgp_project_refl(h, Y, N, T, grp.nrep, w->st));
+        const bool bd = border_on(h);
+        GP_TRY(launch_vgp_project_refl(h, Y, N, T, grp.nrep, bd ? bws(h)->uo : nullptr, w->st));
         GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
+        if (bd) {       // the corrected beta and Y_{t,b} (the inverses themselves are not needed)
+            GP_TRY(launch_lauum(h, h->A, h->B, h->np, h->ld, rag_of(N, h->np)));
+            GP_TRY(border_iter(h, N, false));
+        }
         GP_TRY(predict_cols(h, m, X, 0, N, h->nbatch, Xs, M, mean_out, var_out, &grp));
         return finish_and_check(h);
     }

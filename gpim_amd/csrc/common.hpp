@@ -313,5 +313,7 @@ struct GemmArgs {
     int shape_div;                         // > 1: the launch shape is chosen for ntiles * batch / shape_div tiles (the sparse model's
                                            // lock-step batches: every model gets the tile shapes -- hence the bits -- of its own launch)
     int64_t sA, sB, sC, sColpart;          // per-problem (blockIdx.y) strides in elements
+    int bshift;                            // operand B of problem p is that of p >> bshift (double-precision engine: the 2^r blocks
+                                           // of one task of the multi-output GP share their border's L_S^-1; api.hip: border_iter)
 };
 int launch_gemm(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);

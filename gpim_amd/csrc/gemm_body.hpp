@@ -226,7 +226,7 @@ __device__ __forceinline__ void gemm_tile_core(GemmArgs g, TileDesc t, const int
     const bool dead = RAG && rag_row && qi + wm * WROWS >= 64;      // this wave's rows: no MFMAs, nothing stored
     // batch: by selects the problem; operands advance by their per-problem strides
     g.A += by * g.sA;
-    g.B += by * g.sB;
+    g.B += (by >> g.bshift) * g.sB;
     if (g.C) g.C += by * g.sC;
     if (g.colpart) g.colpart += by * g.sColpart;
 

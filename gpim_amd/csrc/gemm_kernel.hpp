@@ -208,7 +208,7 @@ __device__ __forceinline__ void gemm_tile_body_t(GemmArgs g, const int bx, const
     // batch: by selects the problem; operands advance by their per-problem strides.  The pointers of
     // GemmArgs are typed double* on the host side whatever the handle's precision.
     const R* gA = reinterpret_cast<const R*>(g.A) + by * g.sA;
-    const R* gB = reinterpret_cast<const R*>(g.B) + by * g.sB;
+    const R* gB = reinterpret_cast<const R*>(g.B) + (by >> g.bshift) * g.sB;
     R* gC = g.C ? reinterpret_cast<R*>(g.C) + by * g.sC : nullptr;
     if (g.colpart) g.colpart += by * g.sColpart;
 

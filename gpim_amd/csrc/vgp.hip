@@ -12,10 +12,14 @@
 // Reflection mode (gpimhip_set_reflection): on a complete grid each block A_t splits further into the
 // 2^r reflection blocks A_{t,b} = lambda_t K_b + I of engine.hip's symmetry-reduced model; problem t 2^r + b of the batch is
 // task t with sign pattern b, and each task's sums run over its 2^r consecutive problems:
-//   vgp_project_refl_kernel   z_{t,b} = sum_a P_at (ys_{a,b} - mu_a u_b), u_b = U 1
+//   vgp_project_refl_kernel   z_{t,b} = sum_a P_at (ys_{a,b} - mu_a u_b), u_b = U 1 (with a border: U 1_o)
 //   vgp_kbeta_refl_kernel     K_b beta_{t,b} for all t (K_b regenerated as kmat_refl_kernel builds it, variance 1)
 //   vgp_finalize_kernel<1>    the finalize step with the per-task sums over the blocks and the grid's N
 //   vgp_group_combine_kernel  the blocks' posterior summed per task, then the mix of vgp_combine_kernel
+// With a border (gpimhip_set_border; DESIGN.md section 13: an incomplete grid) the launches of border.hip correct beta and
+// the blocks' inverses per task between the K^-1 product and the gradient contraction; here only three things change: the
+// task means enter through U 1_o, the finalize step adds -|v_t|^2 and log det S_t per task, and the prediction adds
+// |sum_b Y_{t,b}^T k*_{t,b}|^2 to task t's variance before the mix.
 // Every reduction has a fixed shape: results are bit-reproducible run to run.
 #include "kfun.hpp"
 #include "refl.hpp"
@@ -235,8 +239,10 @@ __global__ __launch_bounds__(256) void vgp_kbeta_kernel(const double* __restrict
 // reflection mode: z_{t,b} = sum_a P_at (ys_{a,b} - mu_a u_b) with u_b = U 1 = sqrt(B) w_0 in block 0 and 0 in the others;
 // zero on the padding rows and where the point does not exist in the block (w_b = 0: an identity row of A_{t,b}).
 // grid (np / 256, T nrep); Y: T x nrep x N (task-major, then sign pattern); wts: the weights of block b at b N (or null: all 1)
+// uo (nrep x N, or null): with a border, u_b = (U 1_o)_b -- the means enter at the observed points only
 __global__ __launch_bounds__(256) void vgp_project_refl_kernel(const double* __restrict__ Y, int64_t N, int64_t np, int T,
                                                                int nrep, const double* __restrict__ wts,
+                                                               const double* __restrict__ uo,
                                                                const VgpDev* __restrict__ st, double* __restrict__ z) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int p = blockIdx.y, t = p / nrep, b = p % nrep;
@@ -244,7 +250,7 @@ __global__ __launch_bounds__(256) void vgp_project_refl_kernel(const double* __r
     double v = 0.0;
     if (i < N) {
         const double wb = wts ? wts[(int64_t)b * N + i] : 1.0;
-        const double ub = (b == 0) ? sqrt((double)nrep) * wb : 0.0;
+        const double ub = uo ? uo[(int64_t)b * N + i] : (b == 0) ? sqrt((double)nrep) * wb : 0.0;
         if (wb != 0.0)
             for (int a = 0; a < T; ++a)
                 v = fma(st->P[a * VGP_MAXT + t], Y[((int64_t)a * nrep + b) * N + i] - st->mu[a] * ub, v);
@@ -353,10 +359,13 @@ __device__ __forceinline__ void vgp_sum_multi(const double* v, double* arr, doub
 // REFL (reflection mode): task t is the nrep problems t nrep .. t nrep + nrep - 1; every per-task quantity is the sum over
 // them (each thread runs through the blocks in order before the fixed tree), sig_t = sum_b u_b^T beta_{t,b} =
 // sqrt(nrep) w_0^T beta_{t,0}; ntot = the grid's N (the dense model: ntot = N)
+// bscal (T x 2, or null): with a border, |v_t|^2 and sum log diag chol(S_t) -- q_t loses the first, lg_t gains the second
+// (beta is the corrected one, zero at the missing points in the original basis: sig_t, H and G need nothing else)
 // ------------------------------------------------------------------------------------------
 template <bool REFL>
 __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gpimhip_vgp_t vg, int64_t N, int64_t ntot,
                                                            int64_t np, int nb, int ntile, int nrep, const double* __restrict__ wts,
+                                                           const double* __restrict__ bscal,
                                                            const double* __restrict__ grad_part,
                                                            const double* __restrict__ z, const double* __restrict__ logdet_part,
                                                            const double* __restrict__ beta, const double* __restrict__ kb,
@@ -558,6 +567,10 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
     for (int t = 0; t < T; ++t) {
         lg += lgs[t][0];
         q2 += Sg[t][7];
+        if (REFL && bscal) {
+            lg += bscal[2 * t + 1];
+            q2 -= bscal[2 * t];
+        }
     }
     const double loss = (0.5 * (double)ntot * slog + lg + 0.5 * q2) * inv_nt + 0.5 * 1.8378770664093453;
     int it = 0;
@@ -606,9 +619,11 @@ __global__ __launch_bounds__(256) void vgp_combine_kernel(int T, int64_t M, cons
 // reflection mode, one chunk of test points: the blocks' posterior summed per task (mean_t = sum_b k*_{t,b}^T beta_{t,b},
 // var_t = lambda_t + 1 - sum_b |L_{t,b}^-1 k*_{t,b}|^2 over the nrep consecutive problems of task t; mean_tmp: ldp per
 // problem, colpart: nb x ldp per problem), then the mix of vgp_combine_kernel into rows m0 .. m0 + mcount of the M x T outputs
+// radd (T x ldr, or null): with a border, |sum_b Y_{t,b}^T k*_{t,b}|^2, which the missing points give back to var_t
 __global__ __launch_bounds__(256) void vgp_group_combine_kernel(int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount,
                                                                 const double* __restrict__ colpart,
                                                                 const double* __restrict__ mean_tmp,
+                                                                const double* __restrict__ radd, int64_t ldr,
                                                                 const ThetaDev* __restrict__ th, const VgpDev* __restrict__ st,
                                                                 double* __restrict__ mean_out, double* __restrict__ var_out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -626,6 +641,7 @@ __global__ __launch_bounds__(256) void vgp_group_combine_kernel(int T, int nrep,
             }
             const ThetaDev& tt = th[t * nrep];
             mb[t] = mu;
+            if (radd) q -= radd[(int64_t)t * ldr + j];
             vb[t] = clamp0_nan(tt.var - q) + tt.noise;
         }
     }
@@ -657,9 +673,9 @@ int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const 
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
-int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const VgpDev* st) {
+int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const double* uo, const VgpDev* st) {
     hipLaunchKernelGGL(vgp_project_refl_kernel, dim3((unsigned)((h->np + 255) / 256), T * nrep), dim3(256), 0, h->stream, Y, N,
-                       h->np, T, nrep, h->refl.wts, st, h->ypad);
+                       h->np, T, nrep, h->refl.wts, uo, st, h->ypad);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -687,15 +703,15 @@ int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
 }
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
-                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep) {
+                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep, const double* border_scal) {
     const int nb = (int)(h->np / NB);
     if (nrep > 0)
         hipLaunchKernelGGL(vgp_finalize_kernel<true>, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, h->refl.n_total, h->np, nb,
-                           nb * (nb + 1) / 2, nrep, h->refl.wts, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u, adam_m,
+                           nb * (nb + 1) / 2, nrep, h->refl.wts, border_scal, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u, adam_m,
                            adam_v, do_adam, ast, loss_out, grad_out, (double*)nullptr, fi, h->info);
     else
         hipLaunchKernelGGL(vgp_finalize_kernel<false>, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, N, h->np, nb,
-                           nb * (nb + 1) / 2, 1, (const double*)nullptr, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u,
+                           nb * (nb + 1) / 2, 1, (const double*)nullptr, (const double*)nullptr, h->grad_part, h->z, h->logdet_part, h->alpha, kb, st, u,
                            adam_m, adam_v, do_adam, ast, loss_out, grad_out, (double*)nullptr, fi, h->info);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
@@ -708,9 +724,9 @@ int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const
     return GPIMHIP_OK;
 }
 int launch_vgp_group_combine(gpimhip_ctx* h, int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount, const VgpDev* st,
-                             double* mean_out, double* var_out) {
+                             double* mean_out, double* var_out, const double* radd, int64_t ldr) {
     hipLaunchKernelGGL(vgp_group_combine_kernel, dim3((unsigned)((mcount + 255) / 256)), dim3(256), 0, h->stream, T, nrep, nb, ldp,
-                       m0, mcount, h->colpart, h->mean_tmp, h->theta, st, mean_out, var_out);
+                       m0, mcount, h->colpart, h->mean_tmp, radd, ldr, h->theta, st, mean_out, var_out);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

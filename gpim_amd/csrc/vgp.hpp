@@ -52,13 +52,14 @@ struct FinalizeIterV {
 // pattern b); launch_vgp_finalize takes 0 for the dense model
 int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep);
 int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st);
-int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const VgpDev* st);
+// uo / border_scal / radd: non-null with a border (BorderWs::uo, scal, rsq)
+int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const double* uo, const VgpDev* st);
 int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, double* kb);
 int launch_vgp_kbeta_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, int nrep, double* kb);
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
-                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep);
+                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep, const double* border_scal = nullptr);
 int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const double* mblk, const double* vblk,
                        double* mean_out, double* var_out);
 int launch_vgp_group_combine(gpimhip_ctx* h, int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount, const VgpDev* st,
-                             double* mean_out, double* var_out);
+                             double* mean_out, double* var_out, const double* radd = nullptr, int64_t ldr = 0);

@@ -233,6 +233,32 @@ def border_blocks(X, y):
     return S
 
 
+def border_blocks_multi(X, Y):
+    """The border form of a multi-output GP on an incomplete grid (gpim_amd extension: vreconstructor's 'border' solver,
+    DESIGN.md section 13).  X (d, n_1, ..., n_d) with NaN coordinates at the missing pixels, Y (n_1, ..., n_d, T) whose
+    NaN rows are exactly those pixels (a row with any NaN output counts as missing for every task).
+
+    Returns the dict of ``border_blocks`` with ys of shape (T, B, Nq) -- each task with 0 at the missing points in the
+    adapted basis, task-major then sign pattern, as in ``reflection_blocks_multi`` -- and ones (B, Nq) = U 1_o, the
+    basis change of the indicator of the OBSERVED points (the task means enter the blocks through it; unlike U 1 it has
+    components in every block: ones_b = (U 1)_b - sum_j coef[b, j] e_{q[j]}); n_obs = the number of observed rows.
+    Raises what ``border_blocks`` raises."""
+    X = np.asarray(X, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != X.ndim or X.shape[1:] != Y.shape[:-1]:
+        raise NotImplementedError("grid completion needs coordinates of shape (d, n_1, ..., n_d) and Y of shape (n_1, ..., n_d, T)")
+    T = Y.shape[-1]
+    missing = np.isnan(Y).any(axis=-1)
+    S = border_blocks(X, np.where(missing, np.nan, 0.0))
+    Xc = np.array(np.meshgrid(*S["axes"], indexing="ij"))
+    Y0 = np.where(missing[..., None], 0.0, Y)
+    ones = reflection_blocks(Xc, (~missing).astype(np.float64), S["axes"])["ys"]
+    S["ys"] = np.stack([reflection_blocks(Xc, Y0[..., a], S["axes"])["ys"] for a in range(T)]) if T \
+        else np.empty((0,) + ones.shape)
+    S["ones"] = ones
+    return S
+
+
 def border_flops(N, M, r):
     """Per-iteration flop model of the border form against the dense exact GP on the N - M observed points
     (DESIGN.md section 11): (F_border, F_dense) = (N^3 / 4^r + N^2 M / 2^r + N M^2 + M^3, (N - M)^3)."""

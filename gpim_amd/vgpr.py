@@ -21,11 +21,18 @@ Readings and deliberate differences, in one place:
   * Matern52 uses the engine's form of the covariance function (csrc/kfun.hpp: r = sqrt(r2 + 1e-12)), which differs from
     GPyTorch's by at most ~2.5e-12 per entry.
 
-Solver (``rec.solver``), chosen from the data alone: 'reflection' when X is a complete product grid (no NaN in y) with at
-least one axis whose coordinates are symmetric about its centre -- each task block then splits further into the 2^r
-reflection blocks of gprutils.reflection_blocks_multi, 1 / 4^r of the dense flops and 1 / 2^r of its memory (DESIGN.md
-section 12); 'dense' for anything else (scattered points, rows with NaN, no symmetric axis).  Both compute the same model:
-the numbers agree to rounding.
+Solver (``rec.solver``), chosen from the data alone unless the keyword ``solver`` forces one:
+  * 'reflection' when X is a complete product grid (no NaN in y) with at least one axis whose coordinates are symmetric
+    about its centre -- each task block then splits further into the 2^r reflection blocks of
+    gprutils.reflection_blocks_multi, 1 / 4^r of the dense flops and 1 / 2^r of its memory (DESIGN.md section 12);
+  * 'border' when the grid has missing pixels (rows of y with a NaN output, NaN coordinates in X) but can be completed: the
+    reflection blocks of the completed grid plus, per task, an M x M border for the M missing pixels
+    (gprutils.border_blocks_multi, csrc/border.hip).  Chosen when the flop model of
+    gprutils.border_flops is below skgpr.BORDER_FACTOR of the dense model's and at least VGP_BORDER_MIN_OBS rows are observed;
+  * 'dense' for anything else (scattered points, no symmetric axis, an image row or column without any observation, too
+    many missing pixels, small grids).
+All three compute the same model on the observed rows: the numbers agree to rounding.  ``solver='dense' | 'reflection' |
+'border'`` forces one; NotImplementedError if the data do not allow it.
 """
 import ctypes
 import time
@@ -37,6 +44,13 @@ import torch
 from . import _lib
 from . import gprutils
 from .gpr import reconstructor
+from .skgpr import BORDER_FACTOR
+
+# Below this many observed rows the border solver is not chosen automatically: the flop model knows neither the padding of
+# every block and border to 128 nor the border's extra launches (a 12 x 12 grid with one NaN has a model ratio of 0.066 and
+# is one padded tile per block either way).  Measured, not derived: the table of DESIGN.md section 13
+# (tests/tools/bench_vgp_border.py --floor).
+VGP_BORDER_MIN_OBS = 973
 
 _F64 = torch.float64
 _KERNELS = {"RBF": 0, "Matern52": 1}
@@ -95,7 +109,8 @@ class vreconstructor:
     X: (c, *dims) grid coordinates; y: (*dims, T) observations of T outputs (rows with a NaN output are dropped);
     kernel: 'RBF' or 'Matern52'; lengthscale: [lower, upper] bounds (two scalars or two lists of c), or None (unbounded,
     softplus); independent: per-task output scales instead of the task covariance.  ``isotropic=True`` gives one
-    lengthscale for all dimensions.  After training, ``task_covar`` (B), ``noise`` (s), ``mean_constants`` (mu) and
+    lengthscale for all dimensions; ``solver=None | 'dense' | 'reflection' | 'border'`` forces a solver (module docstring).
+    After training, ``task_covar`` (B), ``noise`` (s), ``mean_constants`` (mu) and
     ``lengthscale`` hold the constrained parameters."""
 
     def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, independent=False, learning_rate=.1,
@@ -147,8 +162,8 @@ class vreconstructor:
             o, _ = raw_layout(T, n_ls, False)
             u[o["F"]] = torch.randn(T, 1, dtype=_F64).reshape(-1)
         self._u = u.to(self._dev)
-        self._refl = self._reflection_blocks(X, y)
-        self.solver = "dense" if self._refl is None else "reflection"
+        self._refl, self.solver = self._choose_solver(X, y, kwargs.get("solver"))
+        self._border = self.solver == "border"
         if self._refl is None:
             self._Xd = self.X.to(self._dev, _F64).contiguous()
             self._Yd = self.y.to(self._dev, _F64).t().contiguous()        # T x N, task-major
@@ -159,6 +174,9 @@ class vreconstructor:
             self._wts_d = None if S["wts"] is None else \
                 torch.from_numpy(np.ascontiguousarray(np.tile(S["wts"], (T, 1)))).to(self._dev, _F64).contiguous()
             self._twoc = (ctypes.c_double * 4)(*S["twoc"])
+            if self._border:        # the missing pixels' representatives and coefficients, shared by the tasks
+                self._q_d = torch.from_numpy(np.ascontiguousarray(S["q"], dtype=np.int32)).to(self._dev)
+                self._coef_d = torch.from_numpy(np.ascontiguousarray(S["coef"])).to(self._dev, _F64).contiguous()
         self.iterations = iterations
         self.learning_rate = learning_rate
         self.lscales = []
@@ -180,9 +198,55 @@ class vreconstructor:
         except (NotImplementedError, ValueError):
             return None
 
+    @staticmethod
+    def _border_blocks(X, y):
+        """gprutils.border_blocks_multi of the data when y has NaN rows on a grid that can be completed and has a symmetric
+        axis; otherwise None."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if not np.isnan(y).any():
+            return None
+        try:
+            S = gprutils.border_blocks_multi(X, y)
+        except (NotImplementedError, ValueError):
+            return None
+        S["n_total"] = S["n_obs"]           # the loss is that of the observed rows
+        return S
+
+    @classmethod
+    def _choose_solver(cls, X, y, forced=None):
+        """(blocks or None, 'dense' | 'reflection' | 'border'): the rule of the module docstring."""
+        if forced not in (None, "dense", "reflection", "border"):
+            raise ValueError("vreconstructor: solver must be None, 'dense', 'reflection' or 'border' (got %r)" % (forced,))
+        if forced == "dense":
+            return None, "dense"
+        if forced == "reflection":
+            S = cls._reflection_blocks(X, y)
+            if S is None:
+                raise NotImplementedError("vreconstructor: solver='reflection' needs a complete product grid (no NaN) with "
+                                          "at least one symmetric axis")
+            return S, "reflection"
+        if forced == "border":
+            S = cls._border_blocks(X, y)
+            if S is None:
+                raise NotImplementedError("vreconstructor: solver='border' needs a product grid with missing pixels (NaN rows "
+                                          "of y, NaN coordinates of X), an observation at every index of every axis, and at "
+                                          "least one symmetric axis")
+            return S, "border"
+        S = cls._reflection_blocks(X, y)
+        if S is not None:
+            return S, "reflection"
+        S = cls._border_blocks(X, y)
+        if S is not None and S["n_obs"] >= VGP_BORDER_MIN_OBS:
+            # the same measured factor as skreconstructor's (the number of tasks cancels out of the ratio)
+            f_border, f_dense = gprutils.border_flops(S["n_obs"] + len(S["miss"]), len(S["miss"]), len(S["dims"]))
+            if f_border < BORDER_FACTOR * f_dense:
+                return S, "border"
+        return None, "dense"
+
     def _engine(self, fn, *args):
         """fn(h, m, vg, X, Y, N, *args) on the handle; in reflection mode (set around this call only) X is the fundamental
-        domain and Y the projected targets."""
+        domain and Y the projected targets; the 'border' solver sets the missing pixels as well."""
         lib, h = self._handle.lib, self._handle.h
         call = lambda: fn(h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd), _lib.ptr(self._Yd),
                           self._Xd.shape[0], *args)
@@ -191,8 +255,11 @@ class vreconstructor:
             return call()
         _lib.check(lib.gpimhip_set_reflection(h, S["mask"], self._twoc, _lib.ptr(self._wts_d), S["n_total"], 0))
         try:
+            if self._border:
+                _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(self._q_d.data_ptr()),
+                                                  _lib.ptr(self._coef_d)))
             return call()
-        finally:
+        finally:      # (also switches a border off)
             _lib.check(lib.gpimhip_set_reflection(h, 0, None, None, 0, 0))
 
     # ------------------------------------------------------------------ parameters

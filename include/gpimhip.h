@@ -193,7 +193,11 @@ int gpimhip_predict_exact_batched(gpimhip_handle h, const gpimhip_model_t* m,
  * pattern b.  Then X is the fundamental domain (N = its N_q points), Y is T x B x N_q (task-major, then sign pattern:
  * y_a in the adapted basis, gpim_amd.gprutils.reflection_blocks_multi), wts (or NULL) is T B x N_q -- the B x N_q weights
  * repeated once per task -- and n_total the grid's N.  u, the loss, the gradient, hist_out / loss_out, Xs, mean_out and
- * var_out (M x T) are as in dense mode.  A sharded handle (gpimhip_set_reflection_shard) or a border gives BADARG. */
+ * var_out (M x T) are as in dense mode.  A sharded handle (gpimhip_set_reflection_shard) gives BADARG.
+ * With a border (gpimhip_set_border; an incomplete grid) the three entry points compute the model of
+ * the OBSERVED rows: Y holds every task with 0 at the M missing points (gpim_amd.gprutils.border_blocks_multi), n_total is
+ * the number of observed rows, q and coef are shared by the tasks; the T borders S_t = (A_t^-1)_mm are handled in
+ * lock-step, and a border that is not positive definite ends training like a failed block. */
 #define GPIMHIP_VGP_MAX_TASKS 16
 typedef struct {
     int32_t tasks;          /* T, 1 .. GPIMHIP_VGP_MAX_TASKS                                        */
@@ -484,7 +488,8 @@ int gpimhip_set_reflection_shard(gpimhip_handle h, int32_t pb_off, int32_t pb_st
  * gpimhip_set_reflection = the number of observations); missing point j has the representative q[j] (a point of the
  * fundamental domain, device int32, M) and in block b the coefficient coef[b * M + j] (device, B x M) -- both as
  * gpim_amd.gprutils.border_blocks returns them.  Valid only in reflection mode, double precision, unsharded; honoured by
- * gpimhip_fit_exact_batched, gpimhip_predict_exact_batched and gpimhip_nll_grad_batched.  M = 0, or
+ * gpimhip_fit_exact_batched, gpimhip_predict_exact_batched, gpimhip_nll_grad_batched and, in reflection mode, by
+ * gpimhip_vgp_nll_grad, gpimhip_fit_vgp and gpimhip_predict_vgp (one border per task; see there).  M = 0, or
  * gpimhip_set_reflection(h, 0, ...), switches it off.  q and coef must stay valid while it is on.
  *   gpimhip_nll_grad_batched  one loss / gradient evaluation of the coupled blocks in reflection mode (with the border when
  *                             it is set) at u (B copies of the parameter vector); loss_out, grad_out: device. */
