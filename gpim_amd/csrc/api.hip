@@ -13,49 +13,6 @@
 #include "vgp.hpp"
 #include "sm.hpp"
 
-// kernels implemented in the other translation units
-int launch_theta_raw(gpimhip_ctx* h, const gpimhip_model_t* m, const double* raw);
-int launch_kmat(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Z,
-                int64_t M, const ThetaDev* theta, double diag_add, int use_theta_diag, double* out,
-                int64_t ld, int64_t rows_pad, int64_t cols_pad, int sym, int lower_only, int64_t x_bs,
-                int64_t z_bs, int64_t out_bs);
-int launch_pad_copy(gpimhip_ctx* h, const double* src, int64_t n, double* dst, int64_t np);
-int launch_diag_inv_copy(gpimhip_ctx* h, double* A, int64_t ld, int nb);
-int launch_pad_matrix_in(gpimhip_ctx* h, const double* src, int64_t n, int64_t ld, double* dst, int64_t np);
-int launch_pad_matrix_out_lower(gpimhip_ctx* h, const double* src, int64_t np, double* dst, int64_t n, int64_t ld);
-int launch_trmv_lower(gpimhip_ctx* h, const double* L, int64_t ld, int64_t np, const double* y, double* z);
-int launch_gemv_t(gpimhip_ctx* h, const double* A, int64_t ld, int64_t nrows, int64_t ncols, const double* x,
-                  double* out, int tri, int64_t a_bs, int64_t x_bs, int64_t o_bs);
-int launch_grad_reduce(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld,
-                       const double* X, int64_t N, int nb, const double* alpha, int64_t x_bs);
-int launch_kres(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, double* scratch,
-                int S, double* res);
-int launch_axpy(gpimhip_ctx* h, double* x, const double* d, int64_t n);
-int launch_gemv_t_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, const double* x, double* part, double* out);
-int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
-                           int64_t N, int nb, const double* alpha, int64_t x_bs, const double* alpha_part, double* u,
-                           int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                           const double* bc, int T, double* hist_base, double* loss_base, int carry_theta);
-int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
-                    AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                    const double* bc, int T, double* hist_base, double* loss_base, int carry_theta = 0);
-int launch_predict_var(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, double* var_out, int64_t M);
-int launch_copy_slice(gpimhip_ctx* h, const double* src, double* dst, int64_t n, int64_t s_bs, int64_t d_bs);
-int launch_acq(gpimhip_ctx* h, int kind, const double* mean, const double* sd, int64_t M, double p0, double p1,
-               const double* mask, double* out);
-int launch_nanmax(gpimhip_ctx* h, const double* x, int64_t n, double* out);
-int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
-                int64_t* count);
-int launch_topk_radix(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
-                      int64_t* count);
-int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* out);
-int launch_thin_batch(gpimhip_ctx* h, const double* vals, const int64_t* flat, int n, int d, const int64_t* shape,
-                      double dscale, int max_out, int32_t* keep_out, int32_t* nkeep_out);
-size_t sel_scratch_bytes();
-int launch_fit_small(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
-                     int N, double* u, const double* lr_over_bc1, const double* bc2_sqrt, int T, double* hist,
-                     double* loss, double* grad);
-
 static thread_local std::string g_err;
 void gpim_set_error(const std::string& s) { g_err = s; }
 
@@ -90,6 +47,17 @@ static void dev_free(gpimhip_ctx* h, T** p, int64_t count) {
         h->bytes -= count * (int64_t)sizeof(T);
         *p = nullptr;
     }
+}
+// grow-only buffer of *cap elements.  The stream is synchronised before the free: earlier launches may still read the buffer.
+template <typename T>
+static int dev_grow(gpimhip_ctx* h, T** p, int64_t* cap, int64_t want) {
+    if (*cap >= want) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    dev_free(h, p, *cap);
+    *cap = 0;
+    GP_TRY(dev_alloc(h, p, want));
+    *cap = want;
+    return GPIMHIP_OK;
 }
 
 // the N x N matrices hold floats on a single-precision handle: same element counts, half the doubles
@@ -392,10 +360,10 @@ static void side_refresh(gpimhip_ctx* h) {
 // interleave their Begin..EndCapture sections on it (the second BeginCapture would fail and that fit would
 // silently run un-graphed).  Capture itself is short (host-side recording of one iteration).
 static std::mutex g_capture_mutex[64];
-void capture_lock(gpimhip_ctx* h) { g_capture_mutex[h->device & 63].lock(); }
-void capture_unlock(gpimhip_ctx* h) { g_capture_mutex[h->device & 63].unlock(); }
+static void capture_lock(gpimhip_ctx* h) { g_capture_mutex[h->device & 63].lock(); }
+static void capture_unlock(gpimhip_ctx* h) { g_capture_mutex[h->device & 63].unlock(); }
 
-hipStream_t ensure_capture_stream(gpimhip_ctx* h) {
+static hipStream_t ensure_capture_stream(gpimhip_ctx* h) {
     side_refresh(h);
     if (!h->capture_stream && !h->capture_stream_tried) {
         h->capture_stream_tried = true;
@@ -476,7 +444,7 @@ static void border_free_bufs(gpimhip_ctx* h, BorderWs* w) {
     dev_free(h, &w->rsq, w->r_cols * w->T);
     w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0; w->uo_n = 0;
 }
-void border_release(gpimhip_ctx* h) {
+static void border_release(gpimhip_ctx* h) {
     BorderWs* w = bws(h);
     if (!w) return;
     border_free_bufs(h, w);
@@ -539,8 +507,7 @@ static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
 static int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
     BorderWs* w = bws(h);
     gpimhip_ctx* sub = w->sub;
-    sub->stream = h->stream;                // (the capture stream while fit_impl records an iteration)
-    sub->capturing = h->capturing;
+    sub->stream = h->stream;                // (the capture stream while run_fit_iterations records an iteration)
     const int64_t mp = w->mp;
     GP_TRY(launch_border_gather_s(h, w, h->B, h->ld, sub->A, sub->ld));
     GP_TRY(launch_potrf_inv(sub, sub->A, sub->Tm, mp, sub->ld, sub->info, 0));      // (rag 0: every padding row is written)
@@ -630,7 +597,7 @@ static int factor_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X
 
 // theta_carried: the training loop launched theta(u) once before its first iteration; every finalize step then leaves the
 // theta of the stepped parameters in h->theta (no theta launch inside the loop)
-struct IterTable { int32_t* iter; const double* bc; int T; double* hist_base; double* loss_base; bool theta_carried; };
+struct IterTable : FinalizeIter { bool theta_carried; };
 
 static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
                           double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out,
@@ -678,13 +645,7 @@ static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double
 
 // Fill the device table of Adam bias corrections (same libm pow() values for every path).
 int upload_bc_table(gpimhip_ctx* h, double lr, int T) {
-    if (h->bc_cap < 2 * (int64_t)T) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        dev_free(h, &h->bc, h->bc_cap);
-        h->bc_cap = 0;
-        GP_TRY(dev_alloc(h, &h->bc, 2 * (int64_t)T));
-        h->bc_cap = 2 * (int64_t)T;
-    }
+    GP_TRY(dev_grow(h, &h->bc, &h->bc_cap, 2 * (int64_t)T));
     h->bc_host.resize(2 * (size_t)T);
     for (int t = 1; t <= T; ++t) {
         h->bc_host[t - 1] = lr / (1.0 - pow(0.9, (double)t));
@@ -721,8 +682,8 @@ struct RunAhead {
     gpimhip_ctx* h;
     int period;
     bool armed[2] = {false, false};
-    RunAhead(gpimhip_ctx* h_, int64_t np) : h(h_), period(np >= 4096 ? 4 : 32) {
-        if (!h->pinned_info) {
+    RunAhead(gpimhip_ctx* h_, int64_t np, bool enabled) : h(h_), period(enabled ? (np >= 4096 ? 4 : 32) : 0) {
+        if (enabled && !h->pinned_info) {
             void* q = nullptr;
             if (hipHostMalloc(&q, 2 * sizeof(int32_t), hipHostMallocDefault) == hipSuccess) h->pinned_info = (int32_t*)q;
             for (auto& e : h->ra_ev)
@@ -731,7 +692,7 @@ struct RunAhead {
     }
     // call before enqueueing iteration t; returns true when the loop should stop
     bool stop(int t) {
-        if (!h->pinned_info || !h->ra_ev[0] || !h->ra_ev[1] || t == 0 || t % period) return false;
+        if (!period || !h->pinned_info || !h->ra_ev[0] || !h->ra_ev[1] || t == 0 || t % period) return false;
         const int slot = (t / period) & 1;
         if (armed[slot]) {
             (void)hipEventSynchronize(h->ra_ev[slot]);
@@ -744,11 +705,56 @@ struct RunAhead {
     }
 };
 
-int vfe_finish_and_check(gpimhip_ctx* h) { return finish_and_check(h); }
-void vfe_release(gpimhip_ctx* h);
-void kron_release(gpimhip_ctx* h);
-void vgp_release(gpimhip_ctx* h);
-void sm_release(gpimhip_ctx* h);
+// The training loop of every fit entry point (common.hpp).  Every iteration enqueues the same launches (the iteration
+// index lives on the device: FinalizeIter), so one iteration is captured into a hipGraph and replayed: ~10 us of host work
+// per iteration instead of one launch call per kernel.  Not used for very short fits, and for the dense engine
+// (FitLoop::dense_gates) neither while stage timing is on nor at large N, where the launch cost no longer matters and the
+// iteration is enqueued launch by launch on the caller's stream (ONE in-order stream: factor_at_u, loss_grad_at_u).
+// The capture lock is held from begin to end capture only, not during replay.
+int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<int()>& iteration) {
+    bool use_graph = T >= 8 && !getenv("GPIMHIP_NO_GRAPH");
+    if (loop.dense_gates) {
+        const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
+        use_graph = use_graph && !h->timing && npanel < EAGER_MIN_PANELS;
+    }
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (use_graph && ensure_capture_stream(h)) {
+        hipStream_t main_s = h->stream;
+        h->stream = h->capture_stream;
+        capture_lock(h);
+        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
+        int rc = GPIMHIP_OK;
+        if (e == hipSuccess) {
+            rc = iteration();
+            e = hipStreamEndCapture(h->capture_stream, &graph);
+        }
+        capture_unlock(h);
+        h->stream = main_s;
+        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+            if (graph) (void)hipGraphDestroy(graph);
+            graph = nullptr;
+            exec = nullptr;
+            (void)hipGetLastError();                        // capture unavailable: plain launches below
+        }
+    }
+    RunAhead ra(h, h->np, loop.run_ahead);
+    if (!exec) {
+        for (int t = 0; t < T && !ra.stop(t); ++t) GP_TRY(iteration());
+        return finish_and_check(h);
+    }
+    hipError_t le = hipSuccess;
+    for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, h->stream);
+    const int rc = finish_and_check(h);
+    (void)hipGraphExecDestroy(exec);
+    (void)hipGraphDestroy(graph);
+    HIP_TRY(le);
+    return rc;
+}
+
+static void vgp_release(gpimhip_ctx* h);
+static void sm_release(gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -930,52 +936,10 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
     // model, whose coupled finalize step is a launch of its own)
     const bool carry = !h->refl.mask && !getenv("GPIMHIP_NO_FUSED_FINALIZE");
     if (carry) GP_TRY(launch_theta(h, m, u));
-    IterTable tab{h->iter, h->bc, T, hist_out, loss_out, carry};
-    AdamStep st;
-    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
-    // Every iteration enqueues the same launches (the iteration index lives on the device), so one
-    // iteration is captured into a hipGraph and replayed: ~10 us of host work per iteration instead
-    // of one launch call per kernel.  Not used while stage timing is on or for very short fits.
-    // Large N: the launch cost no longer matters and the iteration is enqueued launch by launch on the caller's stream
-    // (ONE in-order stream: factor_at_u, loss_grad_at_u).
-    const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
-    const bool large = npanel >= EAGER_MIN_PANELS;
-    const bool use_graph = T >= 8 && !h->timing && !getenv("GPIMHIP_NO_GRAPH") && !large && ensure_capture_stream(h);
-    if (use_graph) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipStream_t main_s = h->stream;
-        h->stream = h->capture_stream;
-        capture_lock(h);
-        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
-        int rc = GPIMHIP_OK;
-        if (e == hipSuccess) {
-            h->capturing = true;
-            rc = loss_grad_at_u(h, m, X, x_bs, N, u, 1, st, nullptr, nullptr, nullptr, &tab);
-            h->capturing = false;
-            e = hipStreamEndCapture(h->capture_stream, &graph);
-        }
-        capture_unlock(h);
-        h->stream = main_s;
-        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        const bool inst_ok = e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        if (inst_ok) {
-            RunAhead ra(h, h->np);
-            hipError_t le = hipSuccess;
-            for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, main_s);
-            rc = finish_and_check(h);
-            (void)hipGraphExecDestroy(exec);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(le);
-            return rc;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();                        // capture unavailable: plain launches below
-    }
-    RunAhead ra(h, h->np);
-    for (int t = 0; t < T && !ra.stop(t); ++t)
-        GP_TRY(loss_grad_at_u(h, m, X, x_bs, N, u, 1, st, nullptr, nullptr, nullptr, &tab));
-    return finish_and_check(h);
+    const IterTable tab{{h->iter, h->bc, T, hist_out, loss_out}, carry};
+    const AdamStep st = adam_step_init();
+    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
+                              [&] { return loss_grad_at_u(h, m, X, x_bs, N, u, 1, st, nullptr, nullptr, nullptr, &tab); });
 }
 
 
@@ -1633,8 +1597,7 @@ int gpimhip_dist_finalize(gpimhip_handle h, const gpimhip_model_t* m, int64_t N,
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = 1;
     GP_TRY(launch_theta(h, m, u));
-    AdamStep st;
-    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8;
+    AdamStep st = adam_step_init();
     st.lr_over_bc1 = t > 0 ? lr / (1.0 - pow(0.9, (double)t)) : 0.0;
     st.bc2_sqrt = t > 0 ? sqrt(1.0 - pow(0.999, (double)t)) : 1.0;
     if (t == 1) {
@@ -1656,8 +1619,7 @@ int gpimhip_dist_finalize_dev(gpimhip_handle h, const gpimhip_model_t* m, int64_
     // the parameters and the Adam state are all this call needs
     if (!h->np) GP_TRY(ws_ensure_b(h, 1, 1, 0, false));
     GP_TRY(launch_theta(h, m, u));
-    AdamStep st;
-    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8;
+    AdamStep st = adam_step_init();
     st.lr_over_bc1 = t > 0 ? lr / (1.0 - pow(0.9, (double)t)) : 0.0;
     st.bc2_sqrt = t > 0 ? sqrt(1.0 - pow(0.999, (double)t)) : 1.0;
     if (t == 1) {
@@ -1749,7 +1711,7 @@ struct VgpWs {
     double* kb = nullptr; int64_t kb_cap = 0;        // T x np: K beta_t (reflection mode: T 2^r x np, K_b beta_{t,b})
     double* pred = nullptr; int64_t pred_cap = 0;    // 2 x T x M: the blocks' mean and variance
 };
-void vgp_release(gpimhip_ctx* h) {
+static void vgp_release(gpimhip_ctx* h) {
     VgpWs* w = (VgpWs*)h->vgp;
     if (!w) return;
     dev_free(h, &w->st, 1);
@@ -1770,20 +1732,8 @@ static int vgp_ws(gpimhip_ctx* h, int nprob, int T, int64_t M, VgpWs** out) {
         GP_TRY(dev_alloc(h, &w->iter, 1));
     }
     const int64_t kb = (int64_t)nprob * h->np, pr = 2 * (int64_t)T * M;
-    if (w->kb_cap < kb) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        dev_free(h, &w->kb, w->kb_cap);
-        w->kb_cap = 0;
-        GP_TRY(dev_alloc(h, &w->kb, kb));
-        w->kb_cap = kb;
-    }
-    if (w->pred_cap < pr) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        dev_free(h, &w->pred, w->pred_cap);
-        w->pred_cap = 0;
-        GP_TRY(dev_alloc(h, &w->pred, pr));
-        w->pred_cap = pr;
-    }
+    GP_TRY(dev_grow(h, &w->kb, &w->kb_cap, kb));
+    GP_TRY(dev_grow(h, &w->pred, &w->pred_cap, pr));
     *out = w;
     return GPIMHIP_OK;
 }
@@ -1815,7 +1765,7 @@ static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp
 // With a border (gpimhip_set_border) the T borders S_t correct beta and the inverses after the K^-1
 // product; everything downstream reads the corrected ones.
 static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, VgpWs* w, const double* X,
-                    const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIterV fi) {
+                    const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
     const int64_t np = h->np;
     const int T = vg->tasks;
     const bool refl = h->refl.mask != 0;
@@ -1834,8 +1784,7 @@ static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_
         GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
         GP_TRY(launch_vgp_kbeta(h, m, X, N, T, w->kb));
     }
-    AdamStep st;
-    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    const AdamStep st = adam_step_init();
     return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi,
                                refl ? nrep : 0, bd ? bws(h)->scal : nullptr);
 }
@@ -1850,13 +1799,7 @@ static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t
     GP_TRY(border_ensure(h, vg->tasks));
     BorderWs* b = bws(h);
     const int nrep = vgp_nrep(h);
-    if (b->uo_n < (int64_t)nrep * N) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        dev_free(h, &b->uo, b->uo_n);
-        b->uo_n = 0;
-        GP_TRY(dev_alloc(h, &b->uo, (int64_t)nrep * N));
-        b->uo_n = (int64_t)nrep * N;
-    }
+    GP_TRY(dev_grow(h, &b->uo, &b->uo_n, (int64_t)nrep * N));
     return launch_border_ones(h, b, N, nrep, b->uo);
 }
 
@@ -1868,7 +1811,7 @@ int gpimhip_vgp_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const gpimh
     if (!u) return GPIMHIP_E_BADARG;
     VgpWs* w = nullptr;
     GP_TRY(vgp_begin(h, vg, N, 0, &w));
-    GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, const_cast<double*>(u), 0, loss_out, grad_out, FinalizeIterV{nullptr, nullptr, 0, nullptr, nullptr}));
+    GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, const_cast<double*>(u), 0, loss_out, grad_out, FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
     return finish_and_check(h);
 }
 
@@ -1884,45 +1827,9 @@ int gpimhip_fit_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vg
     GP_TRY(upload_bc_table(h, lr, T));
     HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * VGP_MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
-    const FinalizeIterV fi{w->iter, h->bc, T, hist_out, loss_out};
-    // one iteration captured into a hipGraph and replayed, as fit_impl does for the batched path
-    const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
-    const bool use_graph = T >= 8 && !h->timing && !getenv("GPIMHIP_NO_GRAPH") && npanel < EAGER_MIN_PANELS &&
-                           ensure_capture_stream(h);
-    if (use_graph) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipStream_t main_s = h->stream;
-        h->stream = h->capture_stream;
-        capture_lock(h);
-        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
-        int rc = GPIMHIP_OK;
-        if (e == hipSuccess) {
-            h->capturing = true;
-            rc = vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi);
-            h->capturing = false;
-            e = hipStreamEndCapture(h->capture_stream, &graph);
-        }
-        capture_unlock(h);
-        h->stream = main_s;
-        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        const bool inst_ok = e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        if (inst_ok) {
-            RunAhead ra(h, h->np);
-            hipError_t le = hipSuccess;
-            for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, main_s);
-            rc = finish_and_check(h);
-            (void)hipGraphExecDestroy(exec);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(le);
-            return rc;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();                        // capture unavailable: plain launches below
-    }
-    RunAhead ra(h, h->np);
-    for (int t = 0; t < T && !ra.stop(t); ++t) GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi));
-    return finish_and_check(h);
+    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
+    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
+                              [&] { return vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi); });
 }
 
 int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
@@ -1972,7 +1879,7 @@ struct SmWs {
     double* csz = nullptr; int64_t csz_cap = 0;        // 2 Q dim x (test chunk): phases of the test points
     double* part = nullptr; int64_t part_cap = 0;      // records x lower tiles
 };
-void sm_release(gpimhip_ctx* h) {
+static void sm_release(gpimhip_ctx* h) {
     SmWs* w = (SmWs*)h->sm;
     if (!w) return;
     dev_free(h, &w->st, 1);
@@ -1984,16 +1891,6 @@ void sm_release(gpimhip_ctx* h) {
     dev_free(h, &w->part, w->part_cap);
     delete w;
     h->sm = nullptr;
-}
-template <typename T>
-static int sm_grow(gpimhip_ctx* h, T** p, int64_t* cap, int64_t want) {
-    if (*cap >= want) return GPIMHIP_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dev_free(h, p, *cap);
-    *cap = 0;
-    GP_TRY(dev_alloc(h, p, want));
-    *cap = want;
-    return GPIMHIP_OK;
 }
 // np_x: phase slots of the training points (0: none), mz: of the test points, ntile: lower tiles of the gradient records
 static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t mz, int64_t ntile, SmWs** out) {
@@ -2011,9 +1908,9 @@ static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t m
         }
     }
     const int64_t per = 2 * (int64_t)sm->mixtures * sm->dim;
-    GP_TRY(sm_grow(h, &w->csx, &w->csx_cap, per * np_x));
-    GP_TRY(sm_grow(h, &w->csz, &w->csz_cap, per * mz));
-    GP_TRY(sm_grow(h, &w->part, &w->part_cap, (int64_t)sm_layout(*sm).P * ntile));
+    GP_TRY(dev_grow(h, &w->csx, &w->csx_cap, per * np_x));
+    GP_TRY(dev_grow(h, &w->csz, &w->csz_cap, per * mz));
+    GP_TRY(dev_grow(h, &w->part, &w->part_cap, (int64_t)sm_layout(*sm).P * ntile));
     *out = w;
     return GPIMHIP_OK;
 }
@@ -2049,13 +1946,12 @@ static int sm_factor(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const doub
 }
 // loss and gradient at u (fit mode: and one Adam step); every launch reads its iteration-dependent values from the device
 static int sm_iter(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* y, int64_t N, double* u,
-                   int do_adam, double* loss_out, double* grad_out, FinalizeIterS fi) {
+                   int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
     const int64_t np = h->np;
     GP_TRY(sm_factor(h, sm, w, X, y, N, u));
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
     { StageTimer t(h, 5); GP_TRY(launch_sm_grad(h, sm, h->B, h->ld, X, N, w->csx, np, h->alpha, w->st, w->part, w->sums)); }
-    AdamStep st;
-    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    const AdamStep st = adam_step_init();
     return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi);
 }
 
@@ -2089,7 +1985,7 @@ int gpimhip_sm_nll_grad(gpimhip_handle h, const gpimhip_sm_t* sm, const double* 
     SmWs* w = nullptr;
     GP_TRY(sm_begin(h, sm, N, &w));
     GP_TRY(sm_iter(h, sm, w, X, y, N, const_cast<double*>(u), 0, loss_out, grad_out,
-                   FinalizeIterS{nullptr, nullptr, 0, nullptr, nullptr}));
+                   FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
     return finish_and_check(h);
 }
 
@@ -2105,45 +2001,8 @@ int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, co
     GP_TRY(upload_bc_table(h, lr, T));
     HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * SM_MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
-    const FinalizeIterS fi{w->iter, h->bc, T, hist_out, loss_out};
-    // one iteration captured into a hipGraph and replayed, as fit_impl does
-    const int npanel = (int)((h->np / NB + OUTER_W - 1) / OUTER_W);
-    const bool use_graph = T >= 8 && !h->timing && !getenv("GPIMHIP_NO_GRAPH") && npanel < EAGER_MIN_PANELS &&
-                           ensure_capture_stream(h);
-    if (use_graph) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipStream_t main_s = h->stream;
-        h->stream = h->capture_stream;
-        capture_lock(h);
-        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
-        int rc = GPIMHIP_OK;
-        if (e == hipSuccess) {
-            h->capturing = true;
-            rc = sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi);
-            h->capturing = false;
-            e = hipStreamEndCapture(h->capture_stream, &graph);
-        }
-        capture_unlock(h);
-        h->stream = main_s;
-        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        const bool inst_ok = e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        if (inst_ok) {
-            RunAhead ra(h, h->np);
-            hipError_t le = hipSuccess;
-            for (int t = 0; t < T && le == hipSuccess && !ra.stop(t); ++t) le = hipGraphLaunch(exec, main_s);
-            rc = finish_and_check(h);
-            (void)hipGraphExecDestroy(exec);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(le);
-            return rc;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();                        // capture unavailable: plain launches below
-    }
-    RunAhead ra(h, h->np);
-    for (int t = 0; t < T && !ra.stop(t); ++t) GP_TRY(sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi));
-    return finish_and_check(h);
+    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
+    return run_fit_iterations(h, T, FIT_LOOP_DENSE, [&] { return sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi); });
 }
 
 int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,

@@ -900,7 +900,6 @@ static int launch_solve_diag(gpimhip_ctx* h, double* A, int64_t ld, int j, int n
 // Tm != nullptr: A <- L^-1 (every training iteration and prediction inverts the factor right away, gpr.py:192-193,248):
 //                the tile operations of the triangular inverse ride in the step launches (plan_inverse), Tm is the
 //                np x np temporary of its T phases.
-int launch_potrf_steps_f32(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);   // cholstep32.hip
 int launch_potrf_steps(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info, double* Tm, int rag) {
     if (h->fp32) return launch_potrf_steps_f32(h, A, np, ld, info);
     const int nb = (int)(np / NB);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include <utility>
@@ -53,6 +54,24 @@ struct AdamStep {
     double lr_over_bc1;     // lr / (1 - beta1^t)
     double bc2_sqrt;        // sqrt(1 - beta2^t)
     double beta1, beta2, eps;
+};
+// Adam's constants with a neutral step (do_adam = 0, or the finalize step looks lr_over_bc1 / bc2_sqrt up by iteration)
+static inline AdamStep adam_step_init() {
+    AdamStep st;
+    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    return st;
+}
+
+// Iteration-indexed form of a finalize kernel (engine.hip, vgp.hip, sm.hip, kron.hip): when `iter` is given the Adam bias
+// corrections, the history row and the loss slot are looked up by the device-resident iteration counter, which the kernel
+// advances.  All T iterations then enqueue byte-identical launches, i.e. one captured hipGraph can be replayed
+// (run_fit_iterations).  Passed to the kernels by value: the members are the kernel-argument layout.
+struct FinalizeIter {
+    int32_t* iter;              // device counter (null: one evaluation with the by-value arguments)
+    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
+    int32_t T;
+    double* hist_base;          // T x (parameters of a history row) or null
+    double* loss_base;          // T or null
 };
 
 // A cached launch plan: tile lists of the level-by-level triangular inverse and of the K^-1 product at a given nb.
@@ -124,7 +143,6 @@ struct gpimhip_ctx {
     hipStream_t capture_stream = nullptr; // internal stream used only to capture one iteration into a hipGraph
     bool capture_stream_tried = false;    // the capture stream is created on first use
     int side_generation = 0;              // generation of the process-wide capture stream the pointer below belongs to (api.hip)
-    bool capturing = false;               // fit_impl is recording one iteration into a hipGraph
     // workspace (sized for np = padded N)
     int64_t np = 0;                 // padded matrix order the buffers are sized for
     int64_t ld = 0;                 // leading dimension (doubles) of A, B, Tm: np, or np + 16 (see ws_ensure_b)
@@ -232,11 +250,38 @@ static inline int gemv_tri_rc(int64_t np) {
     return (int)(rc < NB ? NB : (rc > 1024 ? 1024 : rc));
 }
 static inline int gemv_tri_chunks(int64_t np) { return (int)((np + gemv_tri_rc(np) - 1) / gemv_tri_rc(np)); }
+// api.hip
 int ws_ensure(gpimhip_ctx* h, int64_t N);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
 int plan_ensure(gpimhip_ctx* h, int nb);
-// cholstep.hip
+int check_model(const gpimhip_model_t* m);
+int launch_potrf(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);
+int launch_trtri(gpimhip_ctx* h, double* A, double* Tm, int64_t np, int64_t ld);
+int launch_potrf_inv(gpimhip_ctx* h, double* A, double* Tm, int64_t np, int64_t ld, int32_t* info, int rag);
+int launch_lauum(gpimhip_ctx* h, const double* A, double* B, int64_t np, int64_t ld, int rag);
+int upload_bc_table(gpimhip_ctx* h, double lr, int T);
+int finish_and_check(gpimhip_ctx* h);
+// The two ways in which the training loops differ (run_fit_iterations).  Both are observable -- they decide which launches
+// and copies a fit enqueues -- so each trainer keeps the row it had:
+//   dense_gates  the dense engine (exact / batched, multi-output, spectral mixture) replays a graph only with stage timing
+//                off (the timers record events around single launches) and below EAGER_MIN_PANELS outer panels (beyond,
+//                launch cost no longer matters).  The Kronecker and sparse trainers have neither stage timers nor a large-N
+//                regime of many long launches: any fit of T >= 8 is replayed.
+//   run_ahead    bounded run-ahead (api.hip: RunAhead) relies on the finalize kernel freezing u, the Adam state and the
+//                history at a failed factorisation; the Kronecker and sparse finalize kernels have not been checked for
+//                that, so their loops enqueue all T iterations.
+struct FitLoop { bool dense_gates, run_ahead; };
+static const FitLoop FIT_LOOP_DENSE = {true, true}, FIT_LOOP_PLAIN = {false, false};
+// Runs `iteration` (which enqueues one Adam iteration on h->stream and returns a GPIMHIP_* code) T times -- as one captured
+// hipGraph replayed T times where FitLoop allows, else launch by launch -- and returns finish_and_check().  During the
+// capture h->stream is the capture stream: the body must not synchronise, allocate or touch the legacy stream.
+int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<int()>& iteration);
+// vfe.hip, kron.hip
+void vfe_release(gpimhip_ctx* h);
+void kron_release(gpimhip_ctx* h);
+// cholstep.hip, cholstep32.hip
 int launch_potrf_steps(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info, double* Tm = nullptr, int rag = 0);
+int launch_potrf_steps_f32(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);
 void step_plan_release(gpimhip_ctx* h);
 int step_plan_ensure(gpimhip_ctx* h, int nb);
 int step_plan_ensure_inv(gpimhip_ctx* h, int nb);
@@ -249,7 +294,40 @@ int launch_colsumsq_acc(gpimhip_ctx* h, const double* W, int64_t ldw, int rows, 
 int launch_dist_trsv(gpimhip_ctx* h, const double* P, int64_t ld, const double* D, int nblk, int backward, const double* r0,
                      const double* r1, double* out);
 int launch_dist_rows_acc(gpimhip_ctx* h, const double* A, int64_t ld, int64_t rows, int w, const double* x, double* acc);
-// engine.hip (distributed training)
+// engine.hip
+int launch_theta_raw(gpimhip_ctx* h, const gpimhip_model_t* m, const double* raw);
+int launch_kmat(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Z,
+                int64_t M, const ThetaDev* theta, double diag_add, int use_theta_diag, double* out,
+                int64_t ld, int64_t rows_pad, int64_t cols_pad, int sym, int lower_only, int64_t x_bs,
+                int64_t z_bs, int64_t out_bs);
+int launch_pad_copy(gpimhip_ctx* h, const double* src, int64_t n, double* dst, int64_t np);
+int launch_diag_inv_copy(gpimhip_ctx* h, double* A, int64_t ld, int nb);
+int launch_pad_matrix_in(gpimhip_ctx* h, const double* src, int64_t n, int64_t ld, double* dst, int64_t np);
+int launch_pad_matrix_out_lower(gpimhip_ctx* h, const double* src, int64_t np, double* dst, int64_t n, int64_t ld);
+int launch_trmv_lower(gpimhip_ctx* h, const double* L, int64_t ld, int64_t np, const double* y, double* z);
+int launch_gemv_t(gpimhip_ctx* h, const double* A, int64_t ld, int64_t nrows, int64_t ncols, const double* x,
+                  double* out, int tri, int64_t a_bs, int64_t x_bs, int64_t o_bs);
+int launch_grad_reduce(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld,
+                       const double* X, int64_t N, int nb, const double* alpha, int64_t x_bs);
+int launch_kres(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, double* scratch,
+                int S, double* res);
+int launch_axpy(gpimhip_ctx* h, double* x, const double* d, int64_t n);
+int launch_gemv_t_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, const double* x, double* part, double* out);
+int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
+                           int64_t N, int nb, const double* alpha, int64_t x_bs, const double* alpha_part, double* u,
+                           int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
+                           const double* bc, int T, double* hist_base, double* loss_base, int carry_theta);
+int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
+                    AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
+                    const double* bc, int T, double* hist_base, double* loss_base, int carry_theta = 0);
+int launch_predict_var(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, double* var_out, int64_t M);
+int launch_copy_slice(gpimhip_ctx* h, const double* src, double* dst, int64_t n, int64_t s_bs, int64_t d_bs);
+int launch_acq(gpimhip_ctx* h, int kind, const double* mean, const double* sd, int64_t M, double p0, double p1,
+               const double* mask, double* out);
+int launch_nanmax(gpimhip_ctx* h, const double* x, int64_t n, double* out);
+int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
+                int64_t* count);
+// engine.hip (distributed training, reflection blocks)
 int launch_grad_reduce_tiles(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
                              int64_t N, int64_t np, const double* alpha, const TileDesc* tiles, int ntile, double* part);
 int launch_sum7(gpimhip_ctx* h, const double* part, int ntile, double* S);
@@ -270,6 +348,17 @@ int launch_dist_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, co
                          double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row);
 int launch_add_diag_theta(gpimhip_ctx* h, double* out, int64_t ld, int64_t row0, int64_t n, int64_t npad);
 int launch_theta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* u);
+// select.hip
+int launch_topk_radix(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
+                      int64_t* count);
+int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* out);
+int launch_thin_batch(gpimhip_ctx* h, const double* vals, const int64_t* flat, int n, int d, const int64_t* shape,
+                      double dscale, int max_out, int32_t* keep_out, int32_t* nkeep_out);
+size_t sel_scratch_bytes();
+// smalln.hip
+int launch_fit_small(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
+                     int N, double* u, const double* lr_over_bc1, const double* bc2_sqrt, int T, double* hist,
+                     double* loss, double* grad);
 // predict.hip
 bool fused_predict_fits(int64_t np);
 int launch_predict_fused(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
@@ -317,3 +406,4 @@ struct GemmArgs {
                                            // of one task of the multi-output GP share their border's L_S^-1; api.hip: border_iter)
 };
 int launch_gemm(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);
+int launch_gemm_f32(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);   // gemm32.hip

@@ -583,17 +583,6 @@ __device__ __forceinline__ void block_sum_256_multi(const double* v, double* arr
     __syncthreads();
 }
 
-// Iteration-indexed form: when `iter` is given the Adam bias corrections, the history row and the
-// loss slot are looked up by the device-resident iteration counter, which this kernel advances.  All
-// T iterations then enqueue byte-identical launches, i.e. one captured hipGraph can be replayed.
-struct FinalizeIter {
-    int32_t* iter;              // device counter (null: use the by-value arguments below)
-    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
-    int32_t T;
-    double* hist_base;          // T x P or null
-    double* loss_base;          // T or null
-};
-
 // everything the finalize step of one problem needs (pointers already offset to the problem by the caller)
 struct FinProblem {
     const double* grad_part; const double* z; const double* zb; const double* logdet_part;

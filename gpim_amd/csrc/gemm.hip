@@ -81,7 +81,6 @@ static int launch_one(gpimhip_ctx* h, const GemmArgs& g) {
 // for both element types in gemm_kernel.hpp and compiled in gemm32.hip.  The double kernels stay the hand-tuned
 // source of this file: instantiating the generic template for double gives the same instruction counts but a
 // schedule that is 0.5 - 0.9 % slower on the triangular inverse and the factorisation at N = 16384 (A/B on one box).
-int launch_gemm_f32(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);
 static int launch_gemm_f64(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g) {
     if (epi == EPI_STORE) {
         if (!a_km && !b_km) return launch_one<false, false, EPI_STORE>(h, g);   // NT

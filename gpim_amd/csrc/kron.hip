@@ -26,17 +26,10 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include "common.hpp"
 #include "kfun.hpp"
 #include "theta.hpp"
 #include "blocklds.hpp"      // wave_sum: DPP / readlane reduction (no LDS crossbar round trips)
-
-hipStream_t ensure_capture_stream(gpimhip_ctx* h);
-void capture_lock(gpimhip_ctx* h);
-void capture_unlock(gpimhip_ctx* h);
-int ws_ensure(gpimhip_ctx* h, int64_t N);
-int check_model(const gpimhip_model_t* m);
-int upload_bc_table(gpimhip_ctx* h, double lr, int T);
-int finish_and_check(gpimhip_ctx* h);
 
 #define KMAXD GPIMHIP_MAX_DIM
 
@@ -521,14 +514,12 @@ __global__ void kron_mdiag_kernel(KronDev dv) {
     if (a < n) dv.mdiag[dv.off[ax] + a] = dv.Mm[dv.moff[ax] + (int64_t)a * n + a];
 }
 
-struct KronIter { int32_t* iter; const double* bc; int32_t T; double* hist_base; double* loss_base; };
-
 __global__ __launch_bounds__(256) void kron_finalize_kernel(gpimhip_model_t m, KronDev dv, int nblk,
                                                             const double* __restrict__ part,
                                                             const ThetaDev* __restrict__ th, double* __restrict__ u,
                                                             double* __restrict__ adam_m, double* __restrict__ adam_v,
                                                             int do_adam, double* __restrict__ loss_out,
-                                                            double* __restrict__ grad_out, KronIter fi,
+                                                            double* __restrict__ grad_out, FinalizeIter fi,
                                                             int32_t* __restrict__ info) {
     __shared__ double red[256];
     __shared__ double tot[16];
@@ -681,7 +672,7 @@ static int kron_decompose(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, c
 }
 
 static int kron_loss_grad(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, const double* y, double* u, int do_adam,
-                          double* loss_out, double* grad_out, const KronIter* it) {
+                          double* loss_out, double* grad_out, const FinalizeIter* it) {
     const KronDev& dv = w.dev;
     GP_TRY(kron_decompose(h, w, m, u, y));
     // M_i = Q_i^T E_i Q_i  (two mode products on the n_i x n_i "tensor") and its diagonal
@@ -701,7 +692,7 @@ static int kron_loss_grad(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, c
         GP_TRY(modeprod(h, w.at, w.Z + (int64_t)i * w.N, dv.Mm + dv.moff[i], w.n[i], w.n[i], w.n[i], 0, 0, pre, post));
     }
     hipLaunchKernelGGL(kron_quad_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, w.at, w.Z, w.part);
-    KronIter fi{nullptr, nullptr, 0, nullptr, nullptr};
+    FinalizeIter fi{nullptr, nullptr, 0, nullptr, nullptr};
     if (it) fi = *it;
     hipLaunchKernelGGL(kron_finalize_kernel, dim3(1), dim3(256), 0, h->stream, *m, dv, w.nblk, w.part, h->theta, u,
                        h->adam_m, h->adam_v, do_adam, loss_out, grad_out, fi, h->info);
@@ -753,37 +744,10 @@ int gpimhip_fit_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, cons
     HIP_TRY(hipMemsetAsync(h->adam_m, 0, MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->adam_v, 0, MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->iter, 0, sizeof(int32_t), h->stream));
-    KronIter it{h->iter, h->bc, T, hist_out, loss_out};
-    // every iteration is the same ~4d + 8 small launches: capture one into a hipGraph and replay it
-    if (T >= 8 && !getenv("GPIMHIP_NO_GRAPH") && ensure_capture_stream(h)) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipStream_t main_s = h->stream;
-        h->stream = h->capture_stream;
-        capture_lock(h);
-        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
-        int rc = GPIMHIP_OK;
-        if (e == hipSuccess) {
-            rc = kron_loss_grad(h, *w, m, y, u_inout, 1, nullptr, nullptr, &it);
-            e = hipStreamEndCapture(h->capture_stream, &graph);
-        }
-        capture_unlock(h);
-        h->stream = main_s;
-        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            hipError_t le = hipSuccess;
-            for (int t = 0; t < T && le == hipSuccess; ++t) le = hipGraphLaunch(exec, main_s);
-            rc = finish_and_check(h);
-            (void)hipGraphExecDestroy(exec);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(le);
-            return rc;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-    }
-    for (int t = 0; t < T; ++t) GP_TRY(kron_loss_grad(h, *w, m, y, u_inout, 1, nullptr, nullptr, &it));
-    return finish_and_check(h);
+    const FinalizeIter it{h->iter, h->bc, T, hist_out, loss_out};
+    // every iteration is the same ~4d + 8 small launches
+    return run_fit_iterations(h, T, FIT_LOOP_PLAIN,
+                              [&] { return kron_loss_grad(h, *w, m, y, u_inout, 1, nullptr, nullptr, &it); });
 }
 
 int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void sm_finalize_kernel(gpimhip_sm_t sm, int64
                                                           double* __restrict__ u, double* __restrict__ adam_m,
                                                           double* __restrict__ adam_v, int do_adam, AdamStep ast,
                                                           double* __restrict__ loss_out, double* __restrict__ grad_out,
-                                                          FinalizeIterS fi, int32_t* __restrict__ info) {
+                                                          FinalizeIter fi, int32_t* __restrict__ info) {
     __shared__ double red[256];
     __shared__ int skip;
     const int tid = threadIdx.x;
@@ -506,7 +506,7 @@ int launch_sm_grad(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, i
 
 int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const double* sums, const SmDev* st, double* u,
                        double* adam_m, double* adam_v, int do_adam, AdamStep ast, double* loss_out, double* grad_out,
-                       FinalizeIterS fi) {
+                       FinalizeIter fi) {
     hipLaunchKernelGGL(sm_finalize_kernel, dim3(1), dim3(256), 0, h->stream, *sm, N, h->np, (int)(h->np / NB), sums, h->z,
                        h->logdet_part, h->alpha, st, u, adam_m, adam_v, do_adam, ast, loss_out, grad_out, fi, h->info);
     HIP_TRY(hipGetLastError());

@@ -28,14 +28,6 @@ struct SmDev {
     double kap[SM_MAXQ * GPIMHIP_MAX_DIM];      // 2 pi^2 s^2, per data dimension (isotropic: replicated)
 };
 
-struct FinalizeIterS {
-    int32_t* iter;              // device counter (null: one evaluation)
-    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
-    int32_t T;
-    double* hist_base;          // T x P or null
-    double* loss_base;          // T or null
-};
-
 // phases: cs[((q * dim + d) * 2 + {0: cos, 1: sin}) * ldc + i] of 2 pi m_qd x_id, zero for n <= i < ldc
 int launch_sm_setup(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, const double* P, int64_t n, int64_t ldc,
                     double* cs, const double* y, double* ypad, SmDev* st, ThetaDev* theta);
@@ -46,5 +38,5 @@ int launch_sm_grad(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, i
                    const double* csx, int64_t ldx, const double* alpha, const SmDev* st, double* part, double* sums);
 int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const double* sums, const SmDev* st, double* u,
                        double* adam_m, double* adam_v, int do_adam, AdamStep ast, double* loss_out, double* grad_out,
-                       FinalizeIterS fi);
+                       FinalizeIter fi);
 int launch_sm_mean(gpimhip_ctx* h, const double* mtmp, int64_t n, const SmDev* st, double* mean_out);

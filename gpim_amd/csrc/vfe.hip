@@ -27,28 +27,11 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <map>
+#include "common.hpp"
 #include "kfun.hpp"
 #include "theta.hpp"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
-
-int launch_kmat(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Z,
-                int64_t M, const ThetaDev* theta, double diag_add, int use_theta_diag, double* out,
-                int64_t ld, int64_t rows_pad, int64_t cols_pad, int sym, int lower_only, int64_t x_bs,
-                int64_t z_bs, int64_t out_bs);
-int launch_potrf(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);
-int launch_trtri(gpimhip_ctx* h, double* A, double* Tm, int64_t np, int64_t ld);
-int launch_potrf_inv(gpimhip_ctx* h, double* A, double* Tm, int64_t np, int64_t ld, int32_t* info, int rag);
-int launch_lauum(gpimhip_ctx* h, const double* A, double* B, int64_t np, int64_t ld, int rag);
-int launch_trmv_lower(gpimhip_ctx* h, const double* L, int64_t ld, int64_t np, const double* y, double* z);
-hipStream_t ensure_capture_stream(gpimhip_ctx* h);
-void capture_lock(gpimhip_ctx* h);
-void capture_unlock(gpimhip_ctx* h);
-int launch_gemv_t(gpimhip_ctx* h, const double* A, int64_t ld, int64_t nrows, int64_t ncols, const double* x,
-                  double* out, int tri, int64_t a_bs, int64_t x_bs, int64_t o_bs);
-int launch_pad_copy(gpimhip_ctx* h, const double* src, int64_t n, double* dst, int64_t np);
-int ws_ensure(gpimhip_ctx* h, int64_t N);
-int vfe_finish_and_check(gpimhip_ctx* h);
 
 // ------------------------------------------------------------------------------------------
 // workspace + tile lists of the sparse path
@@ -738,8 +721,6 @@ static int vfe_loss_grad(gpimhip_ctx* h, VfeWs& w, const gpimhip_model_t* m, con
     return GPIMHIP_OK;
 }
 
-int check_model(const gpimhip_model_t* m);
-
 // workspace for B models, h->nbatch = B until the call returns (VfeBatchScope), y (B x N) padded into w.yq
 struct VfeBatchScope {
     gpimhip_ctx* h;
@@ -777,52 +758,11 @@ static int fit_vfe_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
     HIP_TRY(hipMemsetAsync(w->adam_m, 0, na * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(w->adam_v, 0, na * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->iter, 0, B * sizeof(int32_t), h->stream));
-    // Adam bias-correction table (same libm pow() values as every other path)
-    if (h->bc_cap < 2 * (int64_t)T) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->bc) { (void)hipFree(h->bc); h->bytes -= h->bc_cap * (int64_t)sizeof(double); h->bc = nullptr; }
-        void* qq = nullptr;
-        if (hipMalloc(&qq, 2 * (size_t)T * sizeof(double)) != hipSuccess) return GPIMHIP_E_NOMEM;
-        h->bc = (double*)qq;
-        h->bc_cap = 2 * (int64_t)T;
-        h->bytes += h->bc_cap * (int64_t)sizeof(double);
-    }
-    h->bc_host.resize(2 * (size_t)T);
-    for (int t = 1; t <= T; ++t) {
-        h->bc_host[t - 1] = lr / (1.0 - pow(0.9, (double)t));
-        h->bc_host[T + t - 1] = sqrt(1.0 - pow(0.999, (double)t));
-    }
-    HIP_TRY(hipMemcpyAsync(h->bc, h->bc_host.data(), 2 * (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    VfeIter it{h->iter, h->bc, T, hist_theta, hist_xu, loss_out};
-    // every iteration is the same ~90 launches (iteration index and bias corrections live on the
-    // device): capture one into a hipGraph and replay it
-    if (T >= 8 && !getenv("GPIMHIP_NO_GRAPH") && ensure_capture_stream(h)) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipStream_t main_s = h->stream;
-        h->stream = h->capture_stream;
-        capture_lock(h);
-        hipError_t e = hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeRelaxed);
-        int rc = GPIMHIP_OK;
-        if (e == hipSuccess) {
-            rc = vfe_loss_grad(h, *w, m, q, u_inout, 1, &it, nullptr, nullptr);
-            e = hipStreamEndCapture(h->capture_stream, &graph);
-        }
-        capture_unlock(h);
-        h->stream = main_s;
-        if (rc != GPIMHIP_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            for (int t = 0; t < T; ++t) HIP_TRY(hipGraphLaunch(exec, main_s));
-            rc = vfe_finish_and_check(h);
-            (void)hipGraphExecDestroy(exec);
-            (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-    }
-    for (int t = 0; t < T; ++t) GP_TRY(vfe_loss_grad(h, *w, m, q, u_inout, 1, &it, nullptr, nullptr));
-    return vfe_finish_and_check(h);
+    GP_TRY(upload_bc_table(h, lr, T));
+    const VfeIter it{h->iter, h->bc, T, hist_theta, hist_xu, loss_out};
+    // every iteration is the same ~90 launches (iteration index and bias corrections live on the device)
+    return run_fit_iterations(h, T, FIT_LOOP_PLAIN,
+                              [&] { return vfe_loss_grad(h, *w, m, q, u_inout, 1, &it, nullptr, nullptr); });
 }
 
 static int predict_vfe_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
@@ -869,7 +809,7 @@ static int predict_vfe_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const doub
                            w.LW, ldk, w.c1, mp, cnt, h->theta, mean_out + m0, var_out + m0, mc, M);
     }
     HIP_TRY(hipGetLastError());
-    return vfe_finish_and_check(h);
+    return finish_and_check(h);
 }
 
 extern "C" {
@@ -884,7 +824,7 @@ int gpimhip_vfe_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const doubl
     GP_TRY(vfe_prepare(h, m, y, N, Mu, P, 1, &w));
     const VfeProb q{X, 0, N, Mu, P, P + Mu * m->dim};
     GP_TRY(vfe_loss_grad(h, *w, m, q, const_cast<double*>(u), 0, nullptr, loss_out, grad_out));
-    return vfe_finish_and_check(h);
+    return finish_and_check(h);
 }
 
 int gpimhip_fit_vfe(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,

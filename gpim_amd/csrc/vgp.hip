@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void vgp_finalize_kernel(gpimhip_model_t m, gp
                                                            double* __restrict__ adam_m, double* __restrict__ adam_v, int do_adam,
                                                            AdamStep ast, double* __restrict__ loss_out,
                                                            double* __restrict__ grad_out, double* __restrict__ hist_row,
-                                                           FinalizeIterV fi, int32_t* __restrict__ info) {
+                                                           FinalizeIter fi, int32_t* __restrict__ info) {
     __shared__ double arr[8 * 256];
     __shared__ double Sg[VGP_MAXT][8];           // [0..6] contraction, [7] q_t
     __shared__ double lgs[VGP_MAXT][2];          // lg_t, sig_t
@@ -703,7 +703,7 @@ int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
 }
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
-                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep, const double* border_scal) {
+                        double* loss_out, double* grad_out, FinalizeIter fi, int nrep, const double* border_scal) {
     const int nb = (int)(h->np / NB);
     if (nrep > 0)
         hipLaunchKernelGGL(vgp_finalize_kernel<true>, dim3(1), dim3(256), 0, h->stream, *m, *vg, N, h->refl.n_total, h->np, nb,

@@ -40,14 +40,7 @@ struct VgpDev {
     double ls[GPIMHIP_MAX_DIM], dls[GPIMHIP_MAX_DIM];
 };
 
-struct FinalizeIterV {
-    int32_t* iter;              // device counter (null: one evaluation)
-    const double* bc;           // [2*T]: lr/(1-beta1^t) then sqrt(1-beta2^t)
-    int32_t T;
-    double* hist_base;          // T x n_ls or null
-    double* loss_base;          // T or null
-};
-
+// (FinalizeIter::hist_base of launch_vgp_finalize: T x n_ls)
 // nrep: the problems per task -- 1 on the dense model, 2^r in reflection mode (h->refl; problem t nrep + b = task t, sign
 // pattern b); launch_vgp_finalize takes 0 for the dense model
 int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep);
@@ -58,7 +51,7 @@ int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
 int launch_vgp_kbeta_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, int nrep, double* kb);
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
-                        double* loss_out, double* grad_out, FinalizeIterV fi, int nrep, const double* border_scal = nullptr);
+                        double* loss_out, double* grad_out, FinalizeIter fi, int nrep, const double* border_scal = nullptr);
 int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const double* mblk, const double* vblk,
                        double* mean_out, double* var_out);
 int launch_vgp_group_combine(gpimhip_ctx* h, int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount, const VgpDev* st,

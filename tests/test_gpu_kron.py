@@ -102,6 +102,27 @@ def test_structured_reconstructor_run_vs_dense_oracle(gpim, shape):
     assert m2.shape == tuple(2 * n for n in shape) and np.isfinite(m2).all() and np.isfinite(s2).all()
 
 
+def test_graph_replay_equals_eager_launches(gpim, monkeypatch):
+    """reconstructor(structured=True), RBF: one captured iteration replayed (default) against the same launches enqueued
+    iteration by iteration (GPIMHIP_NO_GRAPH=1) -- the same bits in the histories and the posterior."""
+    R = smooth_grid((16, 12), seed=7)
+    Xf = gpim.utils.get_full_grid(R)
+    outs = []
+    for knob in (None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_GRAPH", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
+        rec = gpim.reconstructor(Xf, R, Xf, structured=True, kernel="RBF", learning_rate=0.05, iterations=30, verbose=0)
+        assert rec.do_structured
+        mean, sd, hyper = rec.run()
+        outs.append((mean, sd, np.asarray(hyper["lengthscale"]), np.asarray(hyper["noise"]), np.asarray(hyper["variance"]),
+                     np.asarray(rec.loss_all)))
+    assert all(np.isfinite(a).all() for a in outs[0])
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+
+
 def test_structured_equals_dense_hip_on_c5_slice(gpim):
     """One per-Ns slice of the C5 twin (10 x 10 x 64, N = 6400, fully observed): the structured solver
     against the dense HIP path (itself oracle-checked at this size in tests/test_gpu_regimes.py) --

@@ -92,6 +92,29 @@ def test_sparse_reconstructor_run(gpim, kernel):
     assert rec.model.Xu.shape == (rec._n_ind, 2)
 
 
+def test_graph_replay_equals_eager_launches(gpim, monkeypatch):
+    """reconstructor(sparse=True): one captured iteration replayed (default) against the same launches enqueued iteration by
+    iteration (GPIMHIP_NO_GRAPH=1) -- the same bits in the hyper-parameter, inducing-point and loss histories and the
+    posterior."""
+    R, _ = spiral_image(size=48, keep=0.3, seed=2)
+    X, Xf = gpim.utils.get_sparse_grid(R), gpim.utils.get_full_grid(R)
+    outs = []
+    for knob in (None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_GRAPH", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
+        rec = gpim.reconstructor(X, R, Xf, kernel="Matern52", lengthscale=[[1., 1.], [8., 8.]], sparse=True, indpoints=60,
+                                 learning_rate=0.05, iterations=30, verbose=0)
+        assert rec.do_sparse
+        mean, sd, hyper = rec.run()
+        outs.append((mean, sd, np.asarray(hyper["lengthscale"]), np.asarray(hyper["noise"]), np.asarray(hyper["variance"]),
+                     np.asarray(hyper["inducing_points"]), np.asarray(rec.loss_all)))
+    assert all(np.isfinite(a).all() for a in outs[0])
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+
+
 def test_sparse_default_indpoints_and_3d(gpim):
     """indpoints=None -> N // 10 (gpr.py:146-148); 3D input; second train() call warm-starts."""
     rng = np.random.default_rng(3)

@@ -123,6 +123,27 @@ def test_fit_matches_oracle_trajectory(N, isotropic):
     assert np.allclose(nz, rows[:, -1], rtol=1e-8, atol=0)
 
 
+def test_graph_replay_equals_eager_launches(monkeypatch):
+    """One captured iteration replayed (default) against the same launches enqueued iteration by iteration
+    (GPIMHIP_NO_GRAPH=1): the same bits in the loss and hyper-parameter histories, the raw parameters and the posterior."""
+    X, y = S.grid_data(300, 24, seed=5)
+    Xg, _ = scattered(X, y)
+    hs = []
+    for knob in (None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_GRAPH", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
+        rec = make(X, y, 3, False, learning_rate=0.05, iterations=30)
+        rec.train()
+        mean, sd = rec.predict(Xg)
+        hs.append((np.array(rec.loss_all), rec._u.cpu().numpy(), mean, sd, np.array(rec.hyperparams["weights"]),
+                   np.array(rec.hyperparams["means"]), np.array(rec.hyperparams["scales"]), np.array(rec.hyperparams["noise"])))
+    assert all(np.isfinite(a).all() for a in hs[0][:4])
+    for a, b in zip(*hs):
+        assert np.array_equal(a, b)
+
+
 def test_predict_matches_oracle_with_nan_rows():
     Q, d = 4, 2
     X, y = S.random_data(400, d, seed=9)

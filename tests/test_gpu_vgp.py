@@ -127,6 +127,28 @@ def test_runs_are_bitwise_identical():
         assert np.array_equal(a, b)
 
 
+def test_graph_replay_equals_eager_launches(monkeypatch):
+    """One captured iteration replayed (default; N = 260 is far below the large-N regime, 30 iterations >= 8) against the same
+    launches enqueued iteration by iteration (GPIMHIP_NO_GRAPH=1): the same bits in the histories, the parameters and the
+    posterior (tests/test_gpu_regimes.py has the exact GP's case)."""
+    X, Y = V.random_data(260, 5, 2, seed=2)
+    Xs = np.random.default_rng(0).uniform(0, 8, size=(2, 50))
+    hs = []
+    for knob in (None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_GRAPH", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
+        rec = make(X, Y, "Matern52", False, (0.5, 2.5), False, learning_rate=0.05, iterations=30)
+        assert rec.solver == "dense"
+        rec.train()
+        mean, sd = rec.predict(Xs)
+        hs.append((np.array(rec.hyperparams["lengthscale"]), np.array(rec.loss_all), rec._u.cpu().numpy(), mean, sd))
+    assert all(np.isfinite(a).all() for a in hs[0])
+    for a, b in zip(*hs):
+        assert np.array_equal(a, b)
+
+
 def test_invalid_arguments():
     import gpim_amd
     from gpim_amd import _lib

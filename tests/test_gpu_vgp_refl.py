@@ -149,6 +149,28 @@ def test_runs_are_bitwise_identical():
         assert np.array_equal(a, b)
 
 
+def test_graph_replay_equals_eager_launches(monkeypatch):
+    """solver='reflection': one captured iteration replayed (default) against the same launches enqueued iteration by
+    iteration (GPIMHIP_NO_GRAPH=1) -- the same bits in the histories, the parameters and the posterior."""
+    import gpim_amd
+    X, Y = grid_stack((15, 14), 5, seed=2)
+    hs = []
+    for knob in (None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_GRAPH", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
+        rec = gpim_amd.vreconstructor(X, Y, kernel="Matern52", lengthscale=[0.5, 2.5], learning_rate=0.05, iterations=30,
+                                      verbose=0)
+        assert rec.solver == "reflection"
+        rec.train()
+        mean, sd = rec.predict(X)
+        hs.append((np.array(rec.hyperparams["lengthscale"]), np.array(rec.loss_all), rec._u.cpu().numpy(), mean, sd))
+    assert all(np.isfinite(a).all() for a in hs[0])
+    for a, b in zip(*hs):
+        assert np.array_equal(a, b)
+
+
 def test_reflection_mode_rejects_sharded_handle():
     from gpim_amd import _lib
     X, Y = grid_stack((8, 8), 2, seed=1)
