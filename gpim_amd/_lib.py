@@ -4,6 +4,7 @@ ctypes binding of libgpimhip.so (include/gpimhip.h).
 The product path has no CPU fallback: if the shared library cannot be loaded, or no
 MI355X-class device is visible to torch, every entry point raises RuntimeError.
 """
+import contextlib
 import ctypes
 import os
 
@@ -273,3 +274,23 @@ def ptr(t):
         return None
     assert t.is_cuda and (t.is_contiguous() or (t.dim() == 2 and t.stride(1) == 1))
     return ctypes.c_void_p(t.data_ptr())
+
+
+@contextlib.contextmanager
+def reflection(handle, blocks, var_count=0, border=None, shard=None):
+    """The handle in reflection mode for the body of the ``with``, always reset on the way out (which also switches a
+    border and a shard off).  blocks: the device side of a blocks dict -- anything with ``mask``, ``twoc``, ``wts`` (device
+    tensor or None) and ``n_total``; var_count: variances wanted for the first var_count test points only; border:
+    (M, q_d, coef_d) of the M missing points (gpimhip_set_border); shard: (rank, world, B, raw) (gpimhip_set_reflection_shard)."""
+    lib, h = handle.lib, handle.h
+    mode = lambda *args: check(lib.gpimhip_set_reflection(h, *args))
+    mode(blocks.mask, blocks.twoc, ptr(blocks.wts), blocks.n_total, int(var_count))
+    try:
+        if border is not None:
+            M, q_d, coef_d = border
+            check(lib.gpimhip_set_border(h, M, None if q_d is None else ctypes.c_void_p(q_d.data_ptr()), ptr(coef_d)))
+        if shard is not None:
+            check(lib.gpimhip_set_reflection_shard(h, *(int(v) for v in shard)))
+        yield
+    finally:
+        mode(0, None, None, 0, 0)

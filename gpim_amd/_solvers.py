@@ -1,0 +1,271 @@
+"""
+_solvers.py -- the host layer between the reconstructors and the C ABI (include/gpimhip.h).
+
+  * ``HostDriver``: the training driver and the predict prologue / epilogue shared by reconstructor, vreconstructor and
+    smreconstructor; a class supplies its fit call, what it records per history row and its messages.
+  * ``DeviceBlocks``: the device side of a blocks dict (gprutils.reflection_blocks* / border_blocks*), entered with
+    ``_lib.reflection``.
+  * ``Dense`` / ``Sparse`` / ``Kron`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
+    fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out), each returning the
+    library's status.  ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
+    through the library handle) and reads ``o._Xd`` / ``o._yd`` / ``o._u`` as they are at the time of the call
+    (boptimizer swaps the training data between trainings).  A new path is one more class here and one more arm where
+    ``reconstructor.__init__`` builds ``self._solver``.
+"""
+import ctypes
+import time
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib, gprutils
+from ._lib import ptr
+
+_F64 = torch.float64
+
+
+class HostDriver:
+    """``train`` and the host side of ``predict``.  The class provides: ``_hist_width()``, ``_fit(T, hist, loss) -> rc``,
+    ``_record(i, row, loss_i, show)`` (appends to the histories; when ``show``, returns what the iteration line prints after
+    the loss), ``_print_final(T)``, ``_new_test_grid(Xtest)`` (sets ``fulldims``; Xtest None: the training points) and the class constants."""
+    _print_every, _avg_time_above = 10, 10      # verbose == 2 prints every n-th row; the average time is printed for T > n
+    _predict_banner = ('Calculating predictive mean and uncertainty...', '\n')
+    _np_out = np.float64
+
+    def _check_data(self):
+        pass
+
+    def train(self, **kwargs):
+        """Adam on the negative log marginal likelihood; every call starts a fresh optimiser while the hyper-parameters
+        persist (warm start), like the reference's train()."""
+        for k in ("learning_rate", "iterations", "verbose"):
+            if kwargs.get(k) is not None:
+                setattr(self, k, kwargs.get(k))
+        self._check_data()
+        T = int(self.iterations)
+        start_time = time.time()
+        if self.verbose:
+            print('Model training...')
+        hist = torch.empty((max(T, 1), self._hist_width()), dtype=_F64, device=self._dev)
+        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
+        rc = self._fit(T, hist, loss)
+        failed = rc == _lib.E_NOT_PD
+        if failed:
+            # the device loop froze the parameters at the failing iteration: keep the history up to it
+            # and raise what torch.linalg.cholesky raises there in the reference (gpr.py:192)
+            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
+        else:
+            _lib.check(rc)
+        hist_h, loss_h = hist[:T].cpu().numpy(), loss[:T].cpu().numpy()
+        dt = time.time() - start_time
+        for i in range(T):
+            show = self.verbose == 2 and (i % self._print_every == 0 or i == T - 1)
+            tail = self._record(i, hist_h[i], loss_h[i], show)
+            if show:
+                print('iter: {} ...'.format(i), 'loss: {} ...'.format(np.around(loss_h[i], 4)), *tail)
+        if failed:
+            _lib.check(rc)
+        if self.verbose:
+            if T > self._avg_time_above:
+                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
+            print('training completed in {} s'.format(np.round(dt, 2)))
+            self._print_final(T)
+
+    def run(self):
+        """train() then predict(); returns mean, sd, hyperparams like the reference's run()."""
+        self.train()
+        mean, sd = self.predict()
+        return mean, sd, self.hyperparams
+
+    def _predict_host(self, Xtest, kwargs, posterior):
+        """Resolves the test grid, calls ``posterior() -> (mean, var)`` device tensors, and returns (mean, sd) as numpy arrays
+        of shape ``fulldims`` plus the device pair (mean, sd)."""
+        if Xtest is None and self.Xtest is None:
+            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
+            self.Xtest = self.X
+            self._new_test_grid(None)
+        elif Xtest is not None:
+            self.Xtest = gprutils.prepare_test_data(Xtest, precision=self.precision)
+            self._new_test_grid(Xtest)
+        if kwargs.get("verbose") is not None:
+            self.verbose = kwargs.get("verbose")
+        if self.verbose:
+            print(self._predict_banner[0], end=self._predict_banner[1])
+        mean, var = posterior()
+        sd = var.sqrt()
+        mean_h = mean.cpu().numpy().reshape(self.fulldims).astype(self._np_out, copy=False)
+        sd_h = sd.cpu().numpy().reshape(self.fulldims).astype(self._np_out, copy=False)
+        if self.verbose:
+            print("Done")
+        return mean_h, sd_h, (mean, sd)
+
+
+class DeviceBlocks:
+    """A blocks dict S on the device: Xq, ys, wts (tiled once per task for a multi-output model) and the constants that
+    ``_lib.reflection`` passes on; ``upload_border`` adds the missing points' representatives and coefficients."""
+
+    def __init__(self, S, dev, tasks=None):
+        self.S, self.dev = S, dev
+        self.mask, self.n_total, self.B = S["mask"], S["n_total"], S["B"]
+        self.twoc = (ctypes.c_double * 4)(*S["twoc"])
+        self.Xq, self.ys = self._up(S["Xq"]), self._up(S["ys"])
+        wts = S["wts"] if tasks is None or S["wts"] is None else np.tile(S["wts"], (tasks, 1))
+        self.wts = None if wts is None else self._up(wts)
+        self.border = None
+
+    def _up(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, _F64).contiguous()
+
+    def upload_border(self):
+        self.q = torch.from_numpy(np.ascontiguousarray(self.S["q"], dtype=np.int32)).to(self.dev)
+        self.coef = self._up(self.S["coef"])
+        self.border = (len(self.S["miss"]), self.q, self.coef)
+
+
+def _head(o):
+    return o._handle.h, ctypes.byref(o._mstruct)
+
+
+def _loss_grad(out):
+    return ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 8)
+
+
+class Dense:
+    """The exact GP on the observed points (csrc/engine.hip)."""
+    sparse = structured = symm = border = False         # what reconstructor shows as do_sparse / do_structured / ...
+    xu_rows = None                                      # host rows of the inducing-input history of the latest fit (Sparse)
+
+    def attach(self, o):
+        """The device tensors a path uploads when the reconstructor is built (after its training and test data)."""
+
+    def new_test_grid(self, Xtest):
+        """predict() was given a new test grid."""
+
+    def fit(self, o, lr, T, hist, loss):
+        return o._handle.lib.gpimhip_fit_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), lr, T,
+                                               ptr(hist), ptr(loss))
+
+    def predict(self, o, Xs, mean, var):
+        return o._handle.lib.gpimhip_predict_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                                   Xs.shape[0], ptr(mean), ptr(var))
+
+    def predict_grid(self, o, mean, var):
+        return self.predict(o, o._Xtest_d, mean, var)
+
+    def nll_grad(self, o, out):
+        return o._handle.lib.gpimhip_nll_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), *_loss_grad(out))
+
+
+class Sparse(Dense):
+    """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""
+    sparse = True
+
+    def fit(self, o, lr, T, hist, loss):
+        hist_xu = torch.empty((max(T, 1), o._n_ind, o._spec.dim), dtype=_F64, device=o._dev)
+        rc = o._handle.lib.gpimhip_fit_vfe(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], o._n_ind, ptr(o._u), lr, T,
+                                           ptr(hist), ptr(hist_xu), ptr(loss))
+        self.xu_rows = hist_xu.cpu().numpy()
+        return rc
+
+    def predict(self, o, Xs, mean, var):
+        return o._handle.lib.gpimhip_predict_vfe(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], o._n_ind, ptr(o._u),
+                                                 ptr(Xs), Xs.shape[0], ptr(mean), ptr(var))
+
+    def nll_grad(self, o, out):
+        return o._handle.lib.gpimhip_vfe_nll_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], o._n_ind, ptr(o._u),
+                                                  *_loss_grad(out))
+
+
+class Kron(Dense):
+    """Exact GP through the Kronecker structure of the RBF covariance on a complete product grid (csrc/kron.hip)."""
+    structured = True
+
+    def __init__(self, axes, axes_n):
+        self.axes, self.axes_n = axes, axes_n
+        self.taxes = (axes, axes_n)                     # the test grid's axes: the training grid until told otherwise
+
+    def attach(self, o):
+        self.axes_d = o._to_device(np.concatenate(self.axes))
+
+    def new_test_grid(self, Xtest):
+        self.taxes = gprutils.grid_axes(Xtest)
+
+    def _grid(self, o):
+        return (*_head(o), o._spec.dim, self.axes_n, ptr(self.axes_d), ptr(o._yd), ptr(o._u))
+
+    def fit(self, o, lr, T, hist, loss):
+        return o._handle.lib.gpimhip_fit_kron(*self._grid(o), lr, T, ptr(hist), ptr(loss))
+
+    def predict(self, o, Xs, mean, var):
+        raise NotImplementedError("structured models predict on product grids (use predict())")
+
+    def predict_grid(self, o, mean, var):
+        taxes, tn = self.taxes
+        if int(np.prod([len(c) for c in taxes])) != mean.shape[0]:
+            raise NotImplementedError("structured=True predicts on product grids only")
+        return o._handle.lib.gpimhip_predict_kron(*self._grid(o), tn, ptr(o._to_device(np.concatenate(taxes))), ptr(mean),
+                                                  ptr(var))
+
+    def nll_grad(self, o, out):
+        return o._handle.lib.gpimhip_kron_nll_grad(*self._grid(o), *_loss_grad(out))
+
+
+class Reflection(Dense):
+    """Exact GP on a complete grid through its reflection blocks: 2^r dense blocks in one lock-step batch with shared
+    hyper-parameters (gprutils.reflection_blocks; csrc/engine.hip: kmat_refl_kernel).  With ``border``: the blocks of the
+    completed grid plus a border for its missing points (gprutils.border_blocks; csrc/border.hip)."""
+    symm = True
+
+    def __init__(self, S, border=False):
+        self.S, self.border, self.blocks, self.perm_d = S, border, None, None
+
+    def _call(self, o, fn, *args, var_count=0):
+        """fn(h, model, Xq, 0, ys, Nq, B, u_b, *args) with the handle in reflection mode; the B parameter slots hold one
+        vector, and the first comes back into ``o._u``.  The blocks go to the device on first use."""
+        if self.blocks is None:
+            self.blocks = DeviceBlocks(self.S, o._dev)
+        D = self.blocks
+        u_b = o._u.repeat(D.B).contiguous()
+        if self.border and D.border is None:
+            D.upload_border()
+        with _lib.reflection(o._handle, D, var_count, D.border):
+            rc = fn(*_head(o), ptr(D.Xq), 0, ptr(D.ys), D.Xq.shape[0], D.B, ptr(u_b), *args)
+        o._u.copy_(u_b[:o._u.numel()])
+        return rc
+
+    def fit(self, o, lr, T, hist, loss):
+        hist_b = torch.empty((self.S["B"],) + hist.shape, dtype=_F64, device=o._dev)
+        loss_b = torch.empty((self.S["B"],) + loss.shape, dtype=_F64, device=o._dev)
+        rc = self._call(o, o._handle.lib.gpimhip_fit_exact_batched, lr, T, ptr(hist_b), ptr(loss_b))
+        hist.copy_(hist_b[0])                           # every slot holds the same history
+        loss.copy_(loss_b[0])
+        return rc
+
+    def predict(self, o, Xs, mean, var, var_count=0):
+        return self._call(o, o._handle.lib.gpimhip_predict_exact_batched, ptr(Xs), Xs.shape[0], ptr(mean), ptr(var),
+                          var_count=var_count)
+
+    def predict_grid(self, o, mean, var):
+        Xt, S = o._Xtest_d, self.S
+        if self.border or Xt.shape != o._Xd.shape or not bool(torch.equal(Xt, o._Xd)):
+            return self.predict(o, Xt, mean, var)
+        # the training grid itself: the variance is invariant under the reflections -- computed on the fundamental
+        # domain (ordered first) and mirrored; the mean everywhere
+        M, nq = Xt.shape[0], len(S["fund_flat"])
+        if self.perm_d is None:
+            rest = np.setdiff1d(np.arange(M), S["fund_flat"], assume_unique=True)
+            self.perm_d = torch.from_numpy(np.concatenate([S["fund_flat"], rest])).to(o._dev)
+            self.rep_d = torch.from_numpy(S["rep"]).to(o._dev)
+        Xp = Xt[self.perm_d].contiguous()
+        mean_p, var_p = torch.empty_like(mean), torch.empty_like(var)
+        rc = self.predict(o, Xp, mean_p, var_p, var_count=nq)
+        mean[self.perm_d] = mean_p
+        torch.index_select(var_p[:nq], 0, self.rep_d, out=var)
+        return rc
+
+    def nll_grad(self, o, out):
+        if not self.border:         # the dense model of the same data
+            return Dense.nll_grad(self, o, out)
+        # the coupled blocks with the border: one evaluation of what a training iteration computes
+        return self._call(o, o._handle.lib.gpimhip_nll_grad_batched, *_loss_grad(out))

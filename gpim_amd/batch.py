@@ -34,33 +34,35 @@ def fit_predict_batch(Xs_list, ys_list, Xtest, kernel='RBF', lengthscale=None, l
             H.close()
 
 
-def _fit_predict_batch(H, Xs_list, ys_list, Xtest, kernel, lengthscale, learning_rate, iterations, seed, **kwargs):
-    dev = H.device
-    B = len(ys_list)
+def _prepare(name, dev, Xs_list, ys_list, kernel, lengthscale, **kwargs):
+    """What both batch fitters start from: the kernel spec, and the B problems' data on the device -- (spec, Xl, N, Xd,
+    x_stride, yd) with Xl the host rows per problem, Xd one shared (N, d) matrix (x_stride 0) or the (B, N, d) stack.
+    (prepare_training_data without ``precision`` returns float64 tensors: the device copies need no dtype.)"""
     y0 = np.asarray(ys_list[0])
-    input_dim = np.ndim(y0)
-    if lengthscale is None and not kwargs.get("isotropic"):
-        lmean = float(np.mean(y0.shape) / 2)
-        lengthscale = [[0. for _ in range(input_dim)], [lmean for _ in range(input_dim)]]
-    elif lengthscale is None:
-        lengthscale = [0., float(np.mean(y0.shape) / 2)]
-    spec = get_kernel(kernel, input_dim, lengthscale, amplitude=kwargs.get('amplitude'),
+    if lengthscale is None:
+        lengthscale = gprutils.default_lengthscale(y0.shape, kwargs.get("isotropic"))
+    spec = get_kernel(kernel, np.ndim(y0), lengthscale, amplitude=kwargs.get('amplitude'),
                       jitter=kwargs.get("jitter", 1.0e-5))
-    m = spec.struct()
-    P = spec.n_params
     shared_x = not isinstance(Xs_list, (list, tuple))
     Xl, yl = [], []
-    for b in range(B):
+    for b in range(len(ys_list)):
         Xb, yb = gprutils.prepare_training_data(Xs_list if shared_x else Xs_list[b], ys_list[b])
         Xl.append(Xb)
         yl.append(yb)
     N = yl[0].shape[0]
     if any(t.shape[0] != N for t in yl) or any(t.shape[0] != N for t in Xl):
-        raise ValueError("fit_predict_batch: every problem of a batch must have the same number of observations")
+        raise ValueError("%s: every problem of a batch must have the same number of observations" % name)
     same_x = all(torch.equal(Xl[0], t) for t in Xl[1:])
     Xd = (Xl[0] if same_x else torch.stack(Xl)).to(dev).contiguous()
-    x_stride = 0 if same_x else N * input_dim
     yd = torch.stack(yl).to(dev).contiguous()
+    return spec, Xl, N, Xd, 0 if same_x else N * np.ndim(y0), yd
+
+
+def _fit_predict_batch(H, Xs_list, ys_list, Xtest, kernel, lengthscale, learning_rate, iterations, seed, **kwargs):
+    dev = H.device
+    B = len(ys_list)
+    spec, _, N, Xd, x_stride, yd = _prepare("fit_predict_batch", dev, Xs_list, ys_list, kernel, lengthscale, **kwargs)
+    m, P = spec.struct(), spec.n_params
     # every slice is its own reconstructor(seed=seed): identical initial draw
     u0 = spec.draw_initial_u(torch.Generator().manual_seed(seed))
     u = u0.repeat(B, 1).to(dev).contiguous()
@@ -100,36 +102,10 @@ def _fit_predict_batch_sparse(H, Xs_list, ys_list, Xtest, indpoints, kernel, len
                               **kwargs):
     dev = H.device
     B = len(ys_list)
-    y0 = np.asarray(ys_list[0])
-    input_dim = np.ndim(y0)
-    if lengthscale is None and not kwargs.get("isotropic"):
-        lmean = float(np.mean(y0.shape) / 2)
-        lengthscale = [[0. for _ in range(input_dim)], [lmean for _ in range(input_dim)]]
-    elif lengthscale is None:
-        lengthscale = [0., float(np.mean(y0.shape) / 2)]
-    spec = get_kernel(kernel, input_dim, lengthscale, amplitude=kwargs.get('amplitude'),
-                      jitter=kwargs.get("jitter", 1.0e-5))
-    m = spec.struct()
-    P = spec.n_params
-    shared_x = not isinstance(Xs_list, (list, tuple))
-    Xl, yl = [], []
-    for b in range(B):
-        Xb, yb = gprutils.prepare_training_data(Xs_list if shared_x else Xs_list[b], ys_list[b])
-        Xl.append(Xb)
-        yl.append(yb)
-    N = yl[0].shape[0]
-    if any(t.shape[0] != N for t in yl) or any(t.shape[0] != N for t in Xl):
-        raise ValueError("fit_predict_batch_sparse: every problem of a batch must have the same number of observations")
+    spec, Xl, N, Xd, x_stride, yd = _prepare("fit_predict_batch_sparse", dev, Xs_list, ys_list, kernel, lengthscale, **kwargs)
+    m, P, input_dim = spec.struct(), spec.n_params, spec.dim
     # inducing inputs: every (N // indpoints)-th observation (reconstructor.__init__, gpim/gpreg/gpr.py:145-153)
-    if indpoints is None:
-        indpoints = N // 10
-        indpoints = indpoints + 1 if indpoints == 0 else indpoints
-    else:
-        indpoints = N if indpoints > N else indpoints
-    same_x = all(torch.equal(Xl[0], t) for t in Xl[1:])
-    Xd = (Xl[0] if same_x else torch.stack(Xl)).to(dev, _F64).contiguous()
-    x_stride = 0 if same_x else N * input_dim
-    yd = torch.stack(yl).to(dev, _F64).contiguous()
+    indpoints = gprutils.n_inducing(N, indpoints)
     u0 = spec.draw_initial_u(torch.Generator().manual_seed(seed))          # every slice: its own reconstructor(seed=seed)
     Mu = len(Xl[0][::N // indpoints])
     u = torch.stack([torch.cat([u0, Xl[b][::N // indpoints].reshape(-1).to(_F64)]) for b in range(B)]).to(dev).contiguous()

@@ -31,20 +31,16 @@ def _world():
     return 0, 1
 
 
-def _grid_axes(X):
-    from .gpr import reconstructor
-    return reconstructor._grid_axes(X)[0]
-
-
 class _Shard:
-    """This rank's blocks on its GPU: the handle in reflection mode, the fundamental domain, the projected observations."""
+    """This rank's blocks on its GPU: the handle, the fundamental domain, the projected observations; ``mode`` puts the
+    handle in reflection mode for a ``with`` block."""
 
     def __init__(self, X, y, spec, rank, world):
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
         if np.isnan(y).any():
             raise NotImplementedError("the symmetry-reduced model needs a fully observed grid (no NaN in y)")
-        S = gprutils.reflection_blocks(X, y, _grid_axes(X))
+        S = gprutils.reflection_blocks(X, y, gprutils.grid_axes(X)[0])
         self.S, self.B = S, S["B"]
         self.mine = list(range(rank, self.B, world))
         self.H = _lib.Handle()
@@ -52,8 +48,9 @@ class _Shard:
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, _F64).contiguous()
         self.Xq = to(S["Xq"])
         self.Nq = self.Xq.shape[0]
-        self.n_total = S["n_total"]
+        self.mask, self.n_total = S["mask"], S["n_total"]
         self.twoc = (ctypes.c_double * 4)(*S["twoc"])
+        self.wts = None
         if self.mine:
             self.ys = to(S["ys"][self.mine])
             self.wts = to(S["wts"][self.mine]) if S["wts"] is not None else None
@@ -61,14 +58,8 @@ class _Shard:
         self.P = spec.n_params
         self.rank, self.world = rank, world
 
-    def enter(self, raw=0, var_count=0):
-        lib, h = self.H.lib, self.H.h
-        _lib.check(lib.gpimhip_set_reflection(h, self.S["mask"], self.twoc, _lib.ptr(self.wts) if self.mine else None,
-                                              self.n_total, int(var_count)))
-        _lib.check(lib.gpimhip_set_reflection_shard(h, self.rank, self.world, self.B, int(raw)))
-
-    def leave(self):
-        _lib.check(self.H.lib.gpimhip_set_reflection(self.H.h, 0, None, None, 0, 0))
+    def mode(self, raw=0, var_count=0):
+        return _lib.reflection(self.H, self, var_count, shard=(self.rank, self.world, self.B, raw))
 
 
 def symm_gp_fit(X, y, kernel="Matern52", lengthscale=None, learning_rate=5e-2, iterations=100, seed=0, jitter=1e-5,
@@ -81,7 +72,7 @@ def symm_gp_fit(X, y, kernel="Matern52", lengthscale=None, learning_rate=5e-2, i
     y = np.asarray(y, dtype=np.float64)
     d = y.ndim
     if lengthscale is None:
-        lengthscale = [[0.0] * d, [float(np.mean(y.shape) / 2)] * d]
+        lengthscale = gprutils.default_lengthscale(y.shape)
     spec = KernelSpec(kernel, d, lengthscale, amplitude=amplitude, jitter=jitter)
     sh = shard if shard is not None else _Shard(X, y, spec, rank, world)
     lib, H, dev, P = sh.H.lib, sh.H, sh.dev, sh.P
@@ -92,8 +83,7 @@ def symm_gp_fit(X, y, kernel="Matern52", lengthscale=None, learning_rate=5e-2, i
     loss = torch.zeros((max(T, 1),), dtype=_F64, device=dev)
     sums = torch.zeros((11,), dtype=_F64, device=dev)
     back = torch.zeros((2,), dtype=_F64).pin_memory()
-    sh.enter()
-    try:
+    with sh.mode():
         for t in range(1, T + 1):
             if sh.mine:
                 u_b = u.repeat(len(sh.mine)).contiguous()
@@ -114,8 +104,6 @@ def symm_gp_fit(X, y, kernel="Matern52", lengthscale=None, learning_rate=5e-2, i
                 raise torch.linalg.LinAlgError("linalg.cholesky: the input is not positive-definite")
             if verbose and rank == 0 and (t == 1 or t % 10 == 0 or t == T):
                 print("iter: {} ... loss: {:.4f}".format(t - 1, float(back[1].item())))
-    finally:
-        sh.leave()
     hcpu = hist[:T].cpu().numpy()
     hyper = {"variance": hcpu[:, 0], "lengthscale": hcpu[:, 1:1 + spec.n_ls], "noise": hcpu[:, 1 + spec.n_ls],
              "loss": loss[:T].cpu().numpy()}
@@ -129,7 +117,7 @@ def symm_shard(X, y, kernel="Matern52", lengthscale=None, jitter=1e-5, amplitude
     y = np.asarray(y, dtype=np.float64)
     d = y.ndim
     if lengthscale is None:
-        lengthscale = [[0.0] * d, [float(np.mean(y.shape) / 2)] * d]
+        lengthscale = gprutils.default_lengthscale(y.shape)
     return _Shard(X, y, KernelSpec(kernel, d, lengthscale, amplitude=amplitude, jitter=jitter), rank, world)
 
 
@@ -143,7 +131,7 @@ def symm_gp_posterior(X, y, Xtest, u, kernel="Matern52", lengthscale=None, jitte
     y = np.asarray(y, dtype=np.float64)
     d = y.ndim
     if lengthscale is None:
-        lengthscale = [[0.0] * d, [float(np.mean(y.shape) / 2)] * d]
+        lengthscale = gprutils.default_lengthscale(y.shape)
     spec = KernelSpec(kernel, d, lengthscale, amplitude=amplitude, jitter=jitter)
     sh = shard if shard is not None else _Shard(X, y, spec, rank, world)
     lib, H, dev = sh.H.lib, sh.H, sh.dev
@@ -161,14 +149,11 @@ def symm_gp_posterior(X, y, Xtest, u, kernel="Matern52", lengthscale=None, jitte
     ud = torch.as_tensor(u, dtype=_F64).to(dev).contiguous()
     both = torch.zeros((2, M), dtype=_F64, device=dev)
     if sh.mine:
-        sh.enter(raw=1, var_count=nq)
-        try:
+        with sh.mode(raw=1, var_count=nq):
             u_b = ud.repeat(len(sh.mine)).contiguous()
             _lib.check(lib.gpimhip_predict_exact_batched(H.h, ctypes.byref(sh.m), _lib.ptr(sh.Xq), 0, _lib.ptr(sh.ys), sh.Nq,
                                                          len(sh.mine), _lib.ptr(u_b), _lib.ptr(Xt), M,
                                                          ctypes.c_void_p(both[0].data_ptr()), ctypes.c_void_p(both[1].data_ptr())))
-        finally:
-            sh.leave()
     if world > 1:
         dist.all_reduce(both, group=group)
     var, _, noise = spec.constrained(ud)

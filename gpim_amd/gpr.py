@@ -28,15 +28,12 @@ Deliberate differences from the reference, all on the outside of the numerics:
     (variances and the loss: float32 round-off times the conditioning), not bit-comparable to one.  Sparse and structured models, and the
     fused trainer for N <= 128, compute in double on either setting.
 """
-import ctypes
 import random
-import time
-import warnings
 
 import numpy as np
 import torch
 
-from . import _lib, gprutils
+from . import _lib, _solvers, gprutils
 from .kernels import get_kernel
 
 _F64 = torch.float64
@@ -106,7 +103,7 @@ class _ModelView:
         yield self._o._u
 
 
-class reconstructor:
+class reconstructor(_solvers.HostDriver):
     """
     Gaussian-process reconstruction of sparse 2D images and 3D/4D hyperspectral data.
 
@@ -154,36 +151,35 @@ class reconstructor:
         random.seed(seed)
         input_dim = np.ndim(y)
         self.X, self.y = gprutils.prepare_training_data(X, y, precision=self.precision)
-        self.do_sparse = bool(sparse)
-        self.do_structured = bool(kwargs.get("structured", False))
-        self.do_symm = False
-        self.do_border = False
         self._kernel_name = kernel
+        structured = bool(kwargs.get("structured", False))
         border = kwargs.get("_border")       # set by skreconstructor on an incomplete grid (gprutils.border_blocks)
-        if self.do_structured and border is not None:
+        if structured and border is not None:
             # the reflection blocks of the completed grid with a border for its missing points (csrc/border.hip)
-            self.do_structured = False
-            self.do_symm = self.do_border = True
-            border["twoc"] = (ctypes.c_double * 4)(*border["twoc"])
             border["n_total"] = border["n_obs"]          # the loss is that of the observed points
-            self._symm = border
-        elif self.do_structured:
-            if self.do_sparse:
+            self._solver = _solvers.Reflection(border, border=True)
+        elif structured:
+            if sparse:
                 raise NotImplementedError("structured=True and sparse=True are mutually exclusive")
             if np.isnan(np.asarray(y)).any():
                 raise NotImplementedError("structured=True needs a fully observed grid (no NaN in y)")
-            self._axes, self._axes_n = self._grid_axes(X)
-            if kernel != "RBF":
+            axes, axes_n = gprutils.grid_axes(X)
+            if kernel == "RBF":
+                self._solver = _solvers.Kron(axes, axes_n)
+            else:
                 # kernels that do not factorise over the axes (Matern52, RationalQuadratic): the reflection symmetry of the
                 # complete grid instead -- 2^r diagonal blocks of N / 2^r points each, r = the axes of even length
-                self.do_structured = False
-                self.do_symm = True
-                self._symm_setup(np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64))
-        if lengthscale is None and not kwargs.get("isotropic"):
-            lmean = float(np.mean(y.shape) / 2)
-            lengthscale = [[0. for _ in range(input_dim)], [lmean for _ in range(input_dim)]]
-        elif lengthscale is None and kwargs.get("isotropic"):
-            lengthscale = [0., float(np.mean(y.shape) / 2)]
+                try:
+                    S = gprutils.reflection_blocks(np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64), axes)
+                except ValueError as e:
+                    raise NotImplementedError("structured=True with kernel %r: %s" % (self._kernel_name, e))
+                self._solver = _solvers.Reflection(S)
+        else:
+            self._solver = _solvers.Sparse() if sparse else _solvers.Dense()
+        self.do_sparse = bool(sparse)
+        self.do_structured, self.do_symm, self.do_border = (self._solver.structured, self._solver.symm, self._solver.border)
+        if lengthscale is None:
+            lengthscale = gprutils.default_lengthscale(y.shape, kwargs.get("isotropic"))
         self._spec = get_kernel(kernel, input_dim, lengthscale, use_gpu,
                                 amplitude=kwargs.get('amplitude'), precision=self.precision,
                                 jitter=kwargs.get("jitter", 1.0e-5))
@@ -197,12 +193,7 @@ class reconstructor:
         if self.do_sparse:
             # inducing inputs: every (N // indpoints)-th observation, trainable (gpr.py:145-153)
             n = len(self.X)
-            if indpoints is None:
-                indpoints = n // 10
-                indpoints = indpoints + 1 if indpoints == 0 else indpoints
-            else:
-                indpoints = n if indpoints > n else indpoints
-            Xu = self.X[::n // indpoints]
+            Xu = self.X[::n // gprutils.n_inducing(n, indpoints)]
             if self.verbose == 2:
                 print("# of inducing points for sparse GP regression: {}".format(len(Xu)))
             self._n_ind = len(Xu)
@@ -212,9 +203,9 @@ class reconstructor:
         self._Xd = self._to_device(self.X)
         self._yd = self._to_device(self.y)
         self._Xtest_d = self._to_device(self.Xtest) if self.Xtest is not None else None
-        if self.do_structured:
-            self._axes_d = self._to_device(np.concatenate(self._axes))
-            self._taxes = self._grid_axes(Xtest) if Xtest is not None else (self._axes, self._axes_n)
+        self._solver.attach(self)
+        if Xtest is not None:
+            self._solver.new_test_grid(Xtest)
         self.learning_rate = learning_rate
         self.iterations = iterations
         self.indpoints_all = []
@@ -237,53 +228,6 @@ class reconstructor:
         return _ModelView(self)
 
     # ------------------------------------------------------------------ helpers
-    @staticmethod
-    def _grid_axes(X):
-        """Coordinate vectors of a product grid X (d, n_1, ..., n_d): X[i] must vary along axis i only
-        (what utils.get_full_grid returns, with or without ``extent`` / ``dense_x``)."""
-        X = np.asarray(X, dtype=np.float64)
-        d = X.shape[0]
-        if X.ndim != d + 1:
-            raise NotImplementedError("structured=True needs grid coordinates of shape (d, n_1, ..., n_d)")
-        axes = []
-        for i in range(d):
-            c = np.moveaxis(X[i], i, 0).reshape(X.shape[1 + i], -1)[:, 0].copy()
-            shape = [1] * d
-            shape[i] = -1
-            if not np.array_equal(X[i], np.broadcast_to(c.reshape(shape), X.shape[1:])):
-                raise NotImplementedError("structured=True needs a product grid (coordinate i varying along axis i only)")
-            axes.append(c)
-        return axes, (ctypes.c_int32 * d)(*[len(c) for c in axes])
-
-    def _symm_setup(self, X, y):
-        """The symmetry-reduced form of the model (gprutils.reflection_blocks; csrc/engine.hip: kmat_refl_kernel)."""
-        try:
-            S = gprutils.reflection_blocks(X, y, self._axes)
-        except ValueError as e:
-            raise NotImplementedError("structured=True with kernel %r: %s" % (self._kernel_name, e))
-        S["twoc"] = (ctypes.c_double * 4)(*S["twoc"])
-        self._symm = S
-
-    def _symm_call(self, fn, var_count=0):
-        """fn(Xq, ys, Nq, B, u_b) with the handle in reflection mode; the B parameter slots hold one vector."""
-        S, lib, h = self._symm, self._handle.lib, self._handle.h
-        if "Xq_d" not in S:
-            S["Xq_d"], S["ys_d"] = self._to_device(S["Xq"]), self._to_device(S["ys"])
-            S["wts_d"] = self._to_device(S["wts"]) if S["wts"] is not None else None
-        u_b = self._u.repeat(S["B"]).contiguous()
-        _lib.check(lib.gpimhip_set_reflection(h, S["mask"], S["twoc"], _lib.ptr(S["wts_d"]), S["n_total"], int(var_count)))
-        try:
-            if self.do_border:
-                if "q_d" not in S:
-                    S["q_d"] = torch.from_numpy(S["q"]).to(self._dev)
-                    S["coef_d"] = self._to_device(np.ascontiguousarray(S["coef"]))
-                _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(S["q_d"].data_ptr()), _lib.ptr(S["coef_d"])))
-            rc = fn(S["Xq_d"], S["ys_d"], S["Xq_d"].shape[0], S["B"], u_b)
-        finally:      # (also switches a border off)
-            _lib.check(lib.gpimhip_set_reflection(h, 0, None, None, 0, 0))
-        self._u.copy_(u_b[:self._u.numel()])
-        return rc
-
     def _no_swap(self, what):
         """structured=True models are built from the complete grid once (coordinate vectors of the Kronecker solver, the
         reflection blocks and projected observations of the symmetry-reduced one): swapping the training data through
@@ -305,180 +249,63 @@ class reconstructor:
         if X.shape[0] < 1:
             raise ValueError("no observations (all NaN)")
 
-    # ------------------------------------------------------------------ training
-    def train(self, **kwargs):
-        """Adam on the negative log marginal likelihood; every call starts a fresh optimiser
-        while the hyper-parameters persist (warm start), like gpr.py:170-217."""
-        if kwargs.get("learning_rate") is not None:
-            self.learning_rate = kwargs.get("learning_rate")
-        if kwargs.get("iterations") is not None:
-            self.iterations = kwargs.get("iterations")
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        self._check_data()
-        T, P = int(self.iterations), self._spec.n_params
-        start_time = time.time()
-        if self.verbose:
-            print('Model training...')
-        hist = torch.empty((max(T, 1), P), dtype=_F64, device=self._dev)
-        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
-        if self.do_structured:
-            rc = self._handle.lib.gpimhip_fit_kron(
-                self._handle.h, ctypes.byref(self._mstruct), self._spec.dim, self._axes_n, _lib.ptr(self._axes_d),
-                _lib.ptr(self._yd), _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist), _lib.ptr(loss))
-        elif self.do_symm:
-            Bs = self._symm["B"]
-            hist_b = torch.empty((Bs, max(T, 1), P), dtype=_F64, device=self._dev)
-            loss_b = torch.empty((Bs, max(T, 1)), dtype=_F64, device=self._dev)
-            rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_fit_exact_batched(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
-                float(self.learning_rate), T, _lib.ptr(hist_b), _lib.ptr(loss_b)))
-            hist, loss = hist_b[0], loss_b[0]
-        elif not self.do_sparse:
-            rc = self._handle.lib.gpimhip_fit_exact(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], _lib.ptr(self._u), float(self.learning_rate), T,
-                _lib.ptr(hist), _lib.ptr(loss))
-        else:
-            d = self._spec.dim
-            hist_xu = torch.empty((max(T, 1), self._n_ind, d), dtype=_F64, device=self._dev)
-            rc = self._handle.lib.gpimhip_fit_vfe(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], self._n_ind, _lib.ptr(self._u), float(self.learning_rate), T,
-                _lib.ptr(hist), _lib.ptr(hist_xu), _lib.ptr(loss))
-        failed = rc == _lib.E_NOT_PD
-        if failed:
-            # the device loop froze the parameters at the failing iteration: keep the history up to it
-            # and raise what torch.linalg.cholesky raises there in the reference (gpr.py:192)
-            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
-        else:
-            _lib.check(rc)
-        if self.do_sparse and T > 0:
-            self.indpoints_all.extend(list(hist_xu[:T].cpu().numpy()))
-        hist_h = hist[:T].cpu().numpy()
-        loss_h = loss[:T].cpu().numpy()
+    # ------------------------------------------------------------------ training (HostDriver.train)
+    _print_every, _avg_time_above = 100, 0
+    _predict_banner = ("Calculating predictive mean and variance...", " ")
+
+    def _hist_width(self):
+        return self._spec.n_params
+
+    def _fit(self, T, hist, loss):
+        return self._solver.fit(self, float(self.learning_rate), T, hist, loss)
+
+    def _record(self, i, row, loss_i, show):
         n_ls = self._spec.n_ls
-        for i in range(T):
-            row = hist_h[i]
-            self.lscales.append(float(row[1]) if self._spec.isotropic else row[1:1 + n_ls].tolist())
-            self.amp_all.append(float(row[0]))
-            self.noise_all.append(float(row[1 + n_ls]))
-            self.loss_all.append(float(loss_h[i]))
-            if self.verbose == 2 and (i % 100 == 0 or i == T - 1):
-                print('iter: {} ...'.format(i),
-                      'loss: {} ...'.format(np.around(loss_h[i], 4)),
-                      'amp: {} ...'.format(np.around(self.amp_all[-1], 4)),
-                      'length: {} ...'.format(np.around(self.lscales[-1], 4)),
-                      'noise: {} ...'.format(np.around(self.noise_all[-1], 7)))
-        if failed:
-            _lib.check(rc)
-        if self.verbose:
-            dt = time.time() - start_time
-            if T > 0:
-                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
-            print('training completed in {} s'.format(np.round(dt, 2)))
-            var, ls, noise = self._spec.constrained(self._u)
-            print('Final parameter values:\n',
-                  'amp: {}, lengthscale: {}, noise: {}'.format(
-                      np.around(var.item(), 4), np.around(ls.tolist(), 4), np.around(noise.item(), 7)))
-        return
+        if self._solver.xu_rows is not None:
+            self.indpoints_all.append(self._solver.xu_rows[i])
+        self.lscales.append(float(row[1]) if self._spec.isotropic else row[1:1 + n_ls].tolist())
+        self.amp_all.append(float(row[0]))
+        self.noise_all.append(float(row[1 + n_ls]))
+        self.loss_all.append(float(loss_i))
+        if show:
+            return ('amp: {} ...'.format(np.around(self.amp_all[-1], 4)),
+                    'length: {} ...'.format(np.around(self.lscales[-1], 4)),
+                    'noise: {} ...'.format(np.around(self.noise_all[-1], 7)))
+
+    def _print_final(self, T):
+        var, ls, noise = self._spec.constrained(self._u)
+        print('Final parameter values:\n',
+              'amp: {}, lengthscale: {}, noise: {}'.format(
+                  np.around(var.item(), 4), np.around(ls.tolist(), 4), np.around(noise.item(), 7)))
 
     # ------------------------------------------------------------------ prediction
+    def _new_test_grid(self, Xtest):
+        if Xtest is None:
+            self._Xtest_d = self._Xd
+        else:
+            self._Xtest_d = self._to_device(self.Xtest)
+            self.fulldims = Xtest.shape[1:]
+            self._solver.new_test_grid(Xtest)
+
+    def _posterior(self, predict, *Xs):
+        """(mean, var) device tensors from ``predict`` of the solver: at the rows Xs[0], or on the stored test grid."""
+        self._check_data()
+        M = (Xs[0] if Xs else self._Xtest_d).shape[0]
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        var = torch.empty((M,), dtype=_F64, device=self._dev)
+        _lib.check(predict(self, *Xs, mean, var))
+        return mean, var
+
     def predict(self, Xtest=None, **kwargs):
         """Posterior mean and standard deviation (noise included) on the test grid;
         returns numpy arrays shaped like the grid (gpr.py:219-255)."""
-        if Xtest is None and self.Xtest is None:
-            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
-            self.Xtest = self.X
-            self._Xtest_d = self._Xd
-        elif Xtest is not None:
-            self.Xtest = gprutils.prepare_test_data(Xtest, precision=self.precision)
-            self._Xtest_d = self._to_device(self.Xtest)
-            self.fulldims = Xtest.shape[1:]
-            if self.do_structured:
-                self._taxes = self._grid_axes(Xtest)
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        if self.verbose:
-            print("Calculating predictive mean and variance...", end=" ")
-        self._check_data()
-        M = self._Xtest_d.shape[0]
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        var = torch.empty((M,), dtype=_F64, device=self._dev)
-        if self.do_structured:
-            taxes, tn = self._taxes
-            if int(np.prod([len(c) for c in taxes])) != M:
-                raise NotImplementedError("structured=True predicts on product grids only")
-            rc = self._handle.lib.gpimhip_predict_kron(
-                self._handle.h, ctypes.byref(self._mstruct), self._spec.dim, self._axes_n, _lib.ptr(self._axes_d),
-                _lib.ptr(self._yd), _lib.ptr(self._u), tn, _lib.ptr(self._to_device(np.concatenate(taxes))),
-                _lib.ptr(mean), _lib.ptr(var))
-        elif self.do_symm:
-            S = self._symm
-            on_grid = (not self.do_border and self._Xtest_d.shape == self._Xd.shape
-                       and bool(torch.equal(self._Xtest_d, self._Xd)))
-            if on_grid:
-                # the training grid itself: the variance is invariant under the reflections -- computed on the fundamental
-                # domain (ordered first) and mirrored; the mean everywhere
-                if "perm_d" not in S:
-                    rest = np.setdiff1d(np.arange(M), S["fund_flat"], assume_unique=True)
-                    S["perm_d"] = torch.from_numpy(np.concatenate([S["fund_flat"], rest])).to(self._dev)
-                    S["rep_d"] = torch.from_numpy(S["rep"]).to(self._dev)
-                Xt = self._Xtest_d[S["perm_d"]].contiguous()
-                mean_p = torch.empty((M,), dtype=_F64, device=self._dev)
-                var_p = torch.empty((M,), dtype=_F64, device=self._dev)
-                nq = len(S["fund_flat"])
-                rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_predict_exact_batched(
-                    self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
-                    _lib.ptr(Xt), M, _lib.ptr(mean_p), _lib.ptr(var_p)), var_count=nq)
-                mean[S["perm_d"]] = mean_p
-                var = var_p[:nq][S["rep_d"]]
-            else:
-                rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_predict_exact_batched(
-                    self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
-                    _lib.ptr(self._Xtest_d), M, _lib.ptr(mean), _lib.ptr(var)))
-        elif not self.do_sparse:
-            rc = self._handle.lib.gpimhip_predict_exact(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], _lib.ptr(self._u), _lib.ptr(self._Xtest_d), M, _lib.ptr(mean), _lib.ptr(var))
-        else:
-            rc = self._handle.lib.gpimhip_predict_vfe(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], self._n_ind, _lib.ptr(self._u), _lib.ptr(self._Xtest_d), M, _lib.ptr(mean),
-                _lib.ptr(var))
-        _lib.check(rc)
-        sd = var.sqrt()
-        self._last_pred = (mean, sd)
-        mean_h = mean.cpu().numpy().reshape(self.fulldims).astype(self._np_out, copy=False)
-        sd_h = sd.cpu().numpy().reshape(self.fulldims).astype(self._np_out, copy=False)
-        if self.verbose:
-            print("Done")
+        mean_h, sd_h, self._last_pred = self._predict_host(Xtest, kwargs, lambda: self._posterior(self._solver.predict_grid))
         return mean_h, sd_h
 
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no
         change of the stored test grid.  Internal: the device-resident acquisition path of boptimizer."""
-        self._check_data()
-        M = Xrows_d.shape[0]
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        var = torch.empty((M,), dtype=_F64, device=self._dev)
-        if self.do_structured:
-            raise NotImplementedError("structured models predict on product grids (use predict())")
-        if self.do_symm:
-            # the reflection blocks, not the dense O(N^3) model of the same data
-            rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_predict_exact_batched(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
-                _lib.ptr(Xrows_d), M, _lib.ptr(mean), _lib.ptr(var)))
-        elif not self.do_sparse:
-            rc = self._handle.lib.gpimhip_predict_exact(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], _lib.ptr(self._u), _lib.ptr(Xrows_d), M, _lib.ptr(mean), _lib.ptr(var))
-        else:
-            rc = self._handle.lib.gpimhip_predict_vfe(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], self._n_ind, _lib.ptr(self._u), _lib.ptr(Xrows_d), M, _lib.ptr(mean),
-                _lib.ptr(var))
-        _lib.check(rc)
+        mean, var = self._posterior(self._solver.predict, Xrows_d)
         return mean, var.sqrt()
 
     def run(self, **kwargs):
@@ -501,28 +328,7 @@ class reconstructor:
     def loss_and_grad(self):
         """(loss, d loss/du) at the current hyper-parameters; used by the parity tests."""
         self._check_data()
-        P = self._u.numel()
-        out = torch.empty((1 + P,), dtype=_F64, device=self._dev)
-        if self.do_structured:
-            rc = self._handle.lib.gpimhip_kron_nll_grad(
-                self._handle.h, ctypes.byref(self._mstruct), self._spec.dim, self._axes_n, _lib.ptr(self._axes_d),
-                _lib.ptr(self._yd), _lib.ptr(self._u), ctypes.c_void_p(out.data_ptr()),
-                ctypes.c_void_p(out.data_ptr() + 8))
-        elif self.do_border:
-            # the coupled blocks with the border: one evaluation of what a training iteration computes
-            rc = self._symm_call(lambda Xq, ys, Nq, B, u_b: self._handle.lib.gpimhip_nll_grad_batched(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(Xq), 0, _lib.ptr(ys), Nq, B, _lib.ptr(u_b),
-                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 8)))
-        elif self.do_sparse:
-            rc = self._handle.lib.gpimhip_vfe_nll_grad(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], self._n_ind, _lib.ptr(self._u), ctypes.c_void_p(out.data_ptr()),
-                ctypes.c_void_p(out.data_ptr() + 8))
-        else:
-            rc = self._handle.lib.gpimhip_nll_grad(
-                self._handle.h, ctypes.byref(self._mstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd),
-                self._Xd.shape[0], _lib.ptr(self._u), ctypes.c_void_p(out.data_ptr()),
-                ctypes.c_void_p(out.data_ptr() + 8))
-        _lib.check(rc)
+        out = torch.empty((1 + self._u.numel(),), dtype=_F64, device=self._dev)
+        _lib.check(self._solver.nll_grad(self, out))
         o = out.cpu()
         return o[0].item(), o[1:].clone()

@@ -6,6 +6,8 @@ Host-side mirror of the data-prep part of the reference's gpim/gprutils.py:23-21
 lists, NaN filtering, full / sparse index grids.  Plotting and corruption helpers of the
 reference file (:213-938) are outside the hot path and not provided.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -87,6 +89,36 @@ def get_grid_indices(R, dense_x=1.):
     if np.ndim(R) > 3:
         raise NotImplementedError("Currently supports only 2D and 3D arrays")
     return get_full_grid(R, dense_x=np.float64(dense_x)), get_sparse_grid(R)
+
+
+def default_lengthscale(shape, isotropic=False):
+    """The lengthscale bounds used when none are given: [0, mean(shape) / 2], per dimension or one shared (isotropic)."""
+    lmean = float(np.mean(shape) / 2)
+    return [0., lmean] if isotropic else [[0.] * len(shape), [lmean] * len(shape)]
+
+
+def n_inducing(n, indpoints=None):
+    """The number of inducing inputs asked of n observations (reference gpr.py:145-153): n // 10 by default, at least 1 and
+    at most n; the inducing inputs themselves are X[::n // n_inducing(n, indpoints)]."""
+    return max(n // 10, 1) if indpoints is None else min(indpoints, n)
+
+
+def grid_axes(X):
+    """Coordinate vectors of a product grid X (d, n_1, ..., n_d): X[i] must vary along axis i only (what get_full_grid
+    returns, with or without ``extent`` / ``dense_x``).  Returns (axes, their lengths as a C int32 array)."""
+    X = np.asarray(X, dtype=np.float64)
+    d = X.shape[0]
+    if X.ndim != d + 1:
+        raise NotImplementedError("structured=True needs grid coordinates of shape (d, n_1, ..., n_d)")
+    axes = []
+    for i in range(d):
+        c = np.moveaxis(X[i], i, 0).reshape(X.shape[1 + i], -1)[:, 0].copy()
+        shape = [1] * d
+        shape[i] = -1
+        if not np.array_equal(X[i], np.broadcast_to(c.reshape(shape), X.shape[1:])):
+            raise NotImplementedError("structured=True needs a product grid (coordinate i varying along axis i only)")
+        axes.append(c)
+    return axes, (ctypes.c_int32 * d)(*[len(c) for c in axes])
 
 
 def reflection_blocks(X, y, axes):

@@ -67,8 +67,3 @@ class skreconstructor(reconstructor):
             return "dense", None
         f_border, f_dense = gprutils.border_flops(yv.size, len(S["miss"]), len(S["dims"]))
         return ("border", S) if f_border < BORDER_FACTOR * f_dense else ("dense", None)
-
-    def predict(self, Xtest=None, **kwargs):
-        kwargs.pop("num_batches", None)
-        kwargs.pop("max_root", None)
-        return super().predict(Xtest, **kwargs)

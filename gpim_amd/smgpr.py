@@ -26,14 +26,13 @@ Readings and deliberate differences, in one place:
     ``precision='single'`` raises NotImplementedError.
 """
 import ctypes
-import time
-import warnings
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import gprutils
+from ._solvers import HostDriver
 
 _F64 = torch.float64
 
@@ -88,7 +87,7 @@ def initial_raw(X, y, Q=4, isotropic=False, seed=0):
     return u.numpy()
 
 
-class smreconstructor:
+class smreconstructor(HostDriver):
     """``skreconstructor(X, y, Xtest, kernel='Spectral', ...)`` -- argument order and defaults of gpim/gpreg/skgpr.py:79-91.
     X: (c, *dims) grid coordinates (NaN rows dropped together with the NaN entries of y: sparse images are fine);
     ``n_mixtures`` (default 4) and ``isotropic`` as in the reference.  ``lengthscale`` is not used by this kernel."""
@@ -143,70 +142,36 @@ class smreconstructor:
             _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
         return float(loss.item()), grad.cpu().numpy()
 
-    # ------------------------------------------------------------------ training
-    def train(self, **kwargs):
-        """Adam on the negative log marginal likelihood (skgpr.py:175-220); a fresh optimiser state per call."""
-        if kwargs.get("learning_rate") is not None:
-            self.learning_rate = kwargs.get("learning_rate")
-        if kwargs.get("iterations") is not None:
-            self.iterations = kwargs.get("iterations")
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        T = int(self.iterations)
-        Q, D = self.num_mixtures, self._D
-        o, P = raw_layout(Q, D)
-        if self.verbose:
-            print('Model training...')
-        start_time = time.time()
-        hist = torch.empty((max(T, 1), P), dtype=_F64, device=self._dev)
-        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
-        rc = self._handle.lib.gpimhip_fit_sm(
+    # ------------------------------------------------------------------ training (HostDriver.train)
+    def _hist_width(self):
+        return raw_layout(self.num_mixtures, self._D)[1]
+
+    def _fit(self, T, hist, loss):
+        return self._handle.lib.gpimhip_fit_sm(
             self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
             _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist), _lib.ptr(loss))
-        failed = rc == _lib.E_NOT_PD
-        if failed:
-            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
-        else:
-            _lib.check(rc)
-        hist_h, loss_h = hist[:T].cpu().numpy(), loss[:T].cpu().numpy()
-        dt = time.time() - start_time
-        for i in range(T):
-            row = hist_h[i]
-            self.weights.append(row[o["w"]].copy())
-            self.scales.append((1.0 / np.sqrt(row[o["s"]])).reshape(Q, 1, D))
-            self.means.append((1.0 / row[o["m"]]).reshape(Q, 1, D))
-            self.noise_all.append(float(row[o["noise"]][0]))
-            self.loss_all.append(float(loss_h[i]))
-            if self.verbose == 2 and (i % 10 == 0 or i == T - 1):
-                print('iter: {} ...'.format(i), 'loss: {} ...'.format(np.around(loss_h[i], 4)),
-                      'noise: {} ...'.format(np.around(self.noise_all[-1], 7)))
-        if failed:
-            _lib.check(rc)
-        if self.verbose:
-            if T > 10:
-                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
-            print('training completed in {} s'.format(np.round(dt, 2)))
-            if T > 0:
-                print('Final parameter values:\n', 'weights: {}'.format(np.around(self.weights[-1], 4)),
-                      'noise: {}'.format(np.around(self.noise_all[-1], 7)))
-        return
+
+    def _record(self, i, row, loss_i, show):
+        Q, D = self.num_mixtures, self._D
+        o, _ = raw_layout(Q, D)
+        self.weights.append(row[o["w"]].copy())
+        self.scales.append((1.0 / np.sqrt(row[o["s"]])).reshape(Q, 1, D))
+        self.means.append((1.0 / row[o["m"]]).reshape(Q, 1, D))
+        self.noise_all.append(float(row[o["noise"]][0]))
+        self.loss_all.append(float(loss_i))
+        if show:
+            return ('noise: {} ...'.format(np.around(self.noise_all[-1], 7)),)
+
+    def _print_final(self, T):
+        if T > 0:
+            print('Final parameter values:\n', 'weights: {}'.format(np.around(self.weights[-1], 4)),
+                  'noise: {}'.format(np.around(self.noise_all[-1], 7)))
 
     # ------------------------------------------------------------------ prediction
-    def predict(self, Xtest=None, **kwargs):
-        """Exact predictive mean and standard deviation of likelihood(model(Xtest)) (noise included), shape fulldims."""
-        kwargs.pop("num_batches", None)
-        kwargs.pop("max_root", None)
-        if Xtest is None and self.Xtest is None:
-            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
-            self.Xtest = self.X
-            self.fulldims = (self.X.shape[0],)
-        elif Xtest is not None:
-            self.Xtest = gprutils.prepare_test_data(Xtest)
-            self.fulldims = Xtest.shape[1:]
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        if self.verbose:
-            print('Calculating predictive mean and uncertainty...')
+    def _new_test_grid(self, Xtest):
+        self.fulldims = (self.X.shape[0],) if Xtest is None else Xtest.shape[1:]
+
+    def _posterior(self):
         Xs = self.Xtest.to(self._dev, _F64).contiguous()
         M = Xs.shape[0]
         mean = torch.empty(M, dtype=_F64, device=self._dev)
@@ -214,14 +179,8 @@ class smreconstructor:
         _lib.check(self._handle.lib.gpimhip_predict_sm(
             self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
             _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean), _lib.ptr(var)))
-        sd = torch.sqrt(var)
-        mean, sd = mean.cpu().numpy().reshape(self.fulldims), sd.cpu().numpy().reshape(self.fulldims)
-        if self.verbose:
-            print("Done")
-        return mean, sd
+        return mean, var
 
-    def run(self):
-        """train() then predict(); returns mean, sd, hyperparams (skgpr.py:266-279)."""
-        self.train()
-        mean, sd = self.predict()
-        return mean, sd, self.hyperparams
+    def predict(self, Xtest=None, **kwargs):
+        """Exact predictive mean and standard deviation of likelihood(model(Xtest)) (noise included), shape fulldims."""
+        return self._predict_host(Xtest, kwargs, self._posterior)[:2]

@@ -35,15 +35,13 @@ All three compute the same model on the observed rows: the numbers agree to roun
 'border'`` forces one; NotImplementedError if the data do not allow it.
 """
 import ctypes
-import time
-import warnings
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import gprutils
-from .gpr import reconstructor
+from ._solvers import DeviceBlocks, HostDriver
 from .skgpr import BORDER_FACTOR
 
 # Below this many observed rows the border solver is not chosen automatically: the flop model knows neither the padding of
@@ -102,7 +100,7 @@ def constrained(u, T, n_ls, independent, bounds=None, rank=1):
     return mu, B, s, ls
 
 
-class vreconstructor:
+class vreconstructor(HostDriver):
     """``vreconstructor(X, y, Xtest=None, kernel='RBF', lengthscale=None, independent=False, learning_rate=.1,
     iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs)`` -- argument order and defaults of gpim/gpreg/vgpr.py:73-85.
 
@@ -163,20 +161,15 @@ class vreconstructor:
             u[o["F"]] = torch.randn(T, 1, dtype=_F64).reshape(-1)
         self._u = u.to(self._dev)
         self._refl, self.solver = self._choose_solver(X, y, kwargs.get("solver"))
-        self._border = self.solver == "border"
+        self._blocks = None
         if self._refl is None:
             self._Xd = self.X.to(self._dev, _F64).contiguous()
             self._Yd = self.y.to(self._dev, _F64).t().contiguous()        # T x N, task-major
         else:       # the fundamental domain, the targets as T x 2^r x N_q, the weights tiled once per task (T 2^r x N_q)
-            S = self._refl
-            self._Xd = torch.from_numpy(np.ascontiguousarray(S["Xq"])).to(self._dev, _F64).contiguous()
-            self._Yd = torch.from_numpy(np.ascontiguousarray(S["ys"])).to(self._dev, _F64).contiguous()
-            self._wts_d = None if S["wts"] is None else \
-                torch.from_numpy(np.ascontiguousarray(np.tile(S["wts"], (T, 1)))).to(self._dev, _F64).contiguous()
-            self._twoc = (ctypes.c_double * 4)(*S["twoc"])
-            if self._border:        # the missing pixels' representatives and coefficients, shared by the tasks
-                self._q_d = torch.from_numpy(np.ascontiguousarray(S["q"], dtype=np.int32)).to(self._dev)
-                self._coef_d = torch.from_numpy(np.ascontiguousarray(S["coef"])).to(self._dev, _F64).contiguous()
+            self._blocks = DeviceBlocks(self._refl, self._dev, tasks=T)
+            self._Xd, self._Yd = self._blocks.Xq, self._blocks.ys
+            if self.solver == "border":        # the missing pixels' representatives and coefficients, shared by the tasks
+                self._blocks.upload_border()
         self.iterations = iterations
         self.learning_rate = learning_rate
         self.lscales = []
@@ -193,7 +186,7 @@ class vreconstructor:
         if np.isnan(y).any() or np.isnan(X).any() or X.shape[1:] != y.shape[:-1]:
             return None
         try:
-            axes, _ = reconstructor._grid_axes(X)
+            axes, _ = gprutils.grid_axes(X)
             return gprutils.reflection_blocks_multi(X, y, axes)
         except (NotImplementedError, ValueError):
             return None
@@ -247,20 +240,12 @@ class vreconstructor:
     def _engine(self, fn, *args):
         """fn(h, m, vg, X, Y, N, *args) on the handle; in reflection mode (set around this call only) X is the fundamental
         domain and Y the projected targets; the 'border' solver sets the missing pixels as well."""
-        lib, h = self._handle.lib, self._handle.h
-        call = lambda: fn(h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd), _lib.ptr(self._Yd),
+        call = lambda: fn(self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct), _lib.ptr(self._Xd), _lib.ptr(self._Yd),
                           self._Xd.shape[0], *args)
-        S = self._refl
-        if S is None:
+        if self._blocks is None:
             return call()
-        _lib.check(lib.gpimhip_set_reflection(h, S["mask"], self._twoc, _lib.ptr(self._wts_d), S["n_total"], 0))
-        try:
-            if self._border:
-                _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(self._q_d.data_ptr()),
-                                                  _lib.ptr(self._coef_d)))
+        with _lib.reflection(self._handle, self._blocks, border=self._blocks.border):
             return call()
-        finally:      # (also switches a border off)
-            _lib.check(lib.gpimhip_set_reflection(h, 0, None, None, 0, 0))
 
     # ------------------------------------------------------------------ parameters
     def _params(self):
@@ -290,76 +275,38 @@ class vreconstructor:
         _lib.check(self._engine(self._handle.lib.gpimhip_vgp_nll_grad, _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
         return float(loss.item()), grad.cpu().numpy()
 
-    # ------------------------------------------------------------------ training
-    def train(self, **kwargs):
-        """Adam on the negative log marginal likelihood (vgpr.py:141-182); a fresh optimiser state per call."""
-        if kwargs.get("learning_rate") is not None:
-            self.learning_rate = kwargs.get("learning_rate")
-        if kwargs.get("iterations") is not None:
-            self.iterations = kwargs.get("iterations")
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        T = int(self.iterations)
-        if self.verbose:
-            print('Model training...')
-        start_time = time.time()
-        hist = torch.empty((max(T, 1), self._n_ls), dtype=_F64, device=self._dev)
-        loss = torch.empty((max(T, 1),), dtype=_F64, device=self._dev)
-        rc = self._engine(self._handle.lib.gpimhip_fit_vgp, _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist),
-                          _lib.ptr(loss))
-        failed = rc == _lib.E_NOT_PD
-        if failed:
-            T = int(self._handle.lib.gpimhip_fit_completed(self._handle.h))
-        else:
-            _lib.check(rc)
-        hist_h, loss_h = hist[:T].cpu().numpy(), loss[:T].cpu().numpy()
-        dt = time.time() - start_time
-        for i in range(T):
-            self.lscales.append(hist_h[i].tolist())
-            self.loss_all.append(float(loss_h[i]))
-            if self.verbose == 2 and (i % 10 == 0 or i == T - 1):
-                print('iter: {} ...'.format(i),
-                      'loss: {} ...'.format(np.around(loss_h[i], 4)),
-                      'length: {} ...'.format(np.around(self.lscales[-1], 4)))
-        if failed:
-            _lib.check(rc)
-        if self.verbose:
-            if T > 10:
-                print('average time per iteration: {} s'.format(np.round(dt / T, 6)))
-            print('training completed in {} s'.format(np.round(dt, 2)))
-            if T > 0:
-                print('Final parameter values:\n',
-                      'lengthscale: {}'.format(np.around(self.lscales[-1], 4)))
-        return
+    # ------------------------------------------------------------------ training (HostDriver.train)
+    def _hist_width(self):
+        return self._n_ls
+
+    def _fit(self, T, hist, loss):
+        return self._engine(self._handle.lib.gpimhip_fit_vgp, _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist),
+                            _lib.ptr(loss))
+
+    def _record(self, i, row, loss_i, show):
+        self.lscales.append(row.tolist())
+        self.loss_all.append(float(loss_i))
+        if show:
+            return ('length: {} ...'.format(np.around(self.lscales[-1], 4)),)
+
+    def _print_final(self, T):
+        if T > 0:
+            print('Final parameter values:\n',
+                  'lengthscale: {}'.format(np.around(self.lscales[-1], 4)))
 
     # ------------------------------------------------------------------ prediction
-    def predict(self, Xtest=None, **kwargs):
-        """Exact predictive mean and standard deviation at Xtest, shape ``Xtest.shape[1:] + (T,)`` each."""
-        if Xtest is None and self.Xtest is None:
-            warnings.warn("No test data provided. Using training data for prediction", UserWarning)
-            self.Xtest = self.X
-            self.fulldims = (self.X.shape[0], self.num_tasks)
-        elif Xtest is not None:
-            self.Xtest = gprutils.prepare_test_data(Xtest)
-            self.fulldims = Xtest.shape[1:] + (self.num_tasks,)
-        if kwargs.get("verbose") is not None:
-            self.verbose = kwargs.get("verbose")
-        if self.verbose:
-            print('Calculating predictive mean and uncertainty...')
+    def _new_test_grid(self, Xtest):
+        self.fulldims = ((self.X.shape[0],) if Xtest is None else Xtest.shape[1:]) + (self.num_tasks,)
+
+    def _posterior(self):
         Xs = self.Xtest.to(self._dev, _F64).contiguous()
         M = Xs.shape[0]
         mean = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
         var = torch.empty((M, self.num_tasks), dtype=_F64, device=self._dev)
         _lib.check(self._engine(self._handle.lib.gpimhip_predict_vgp, _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean),
                                 _lib.ptr(var)))
-        sd = torch.sqrt(var)
-        mean, sd = mean.cpu().numpy().reshape(self.fulldims), sd.cpu().numpy().reshape(self.fulldims)
-        if self.verbose:
-            print("Done")
-        return mean, sd
+        return mean, var
 
-    def run(self):
-        """train() then predict(); returns mean, sd, hyperparams (vgpr.py:258-270)."""
-        self.train()
-        mean, sd = self.predict()
-        return mean, sd, self.hyperparams
+    def predict(self, Xtest=None, **kwargs):
+        """Exact predictive mean and standard deviation at Xtest, shape ``Xtest.shape[1:] + (T,)`` each."""
+        return self._predict_host(Xtest, kwargs, self._posterior)[:2]

@@ -165,3 +165,28 @@ def test_rank_without_a_block_runs_the_replicated_step(gpim):
     ch.kinv(Xl, out=ch.local)                                             # K^-1 over the dead factor ...
     with pytest.raises(RuntimeError):
         ch.logdet()                                                       # ... which is gone
+
+
+@pytest.mark.parametrize("structured", [False, True])
+def test_dropping_the_reconstructor_frees_the_handle_without_the_collector(gpim, structured):
+    """No reference cycle through the reconstructor (see ``reconstructor.model``): with the cyclic collector off, dropping
+    the last reference must free the library handle -- and its N x N workspaces -- at once, for the dense solver and for
+    the reflection solver after it has uploaded its blocks."""
+    import gc
+    import weakref
+    R = _image((12, 10), 3)
+    X = gpim.utils.get_full_grid(R)
+    gc.collect()
+    gc.disable()
+    try:
+        rec = gpim.reconstructor(X, R, X, kernel="Matern52", lengthscale=[[1., 1.], [6., 6.]], structured=structured,
+                                 learning_rate=0.1, iterations=2, verbose=0)
+        assert rec.do_symm == structured
+        rec.run()
+        rec.model.kernel.lengthscale
+        rec.loss_and_grad()
+        handle = weakref.ref(rec._handle)
+        del rec
+        assert handle() is None
+    finally:
+        gc.enable()

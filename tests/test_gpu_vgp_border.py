@@ -192,7 +192,7 @@ def _nll_grad_raw(rec, S, wts_d, border=None):
     lib, h = rec._handle.lib, rec._handle.h
     u = rec._u.clone()
     out = torch.zeros(u.numel() + 1, dtype=torch.float64, device=u.device)
-    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rec._twoc, _lib.ptr(wts_d), S["n_total"], 0))
+    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rec._blocks.twoc, _lib.ptr(wts_d), S["n_total"], 0))
     try:
         if border is not None:
             M, q_d, coef_d = border
@@ -214,9 +214,9 @@ def test_border_on_sharded_handle_is_rejected():
     S = rb._refl
     u = rb._u.clone()
     out = torch.empty(u.numel() + 1, dtype=torch.float64, device=u.device)
-    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rb._twoc, _lib.ptr(rb._wts_d), S["n_total"], 0))
+    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rb._blocks.twoc, _lib.ptr(rb._blocks.wts), S["n_total"], 0))
     try:
-        _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(rb._q_d.data_ptr()), _lib.ptr(rb._coef_d)))
+        _lib.check(lib.gpimhip_set_border(h, len(S["miss"]), ctypes.c_void_p(rb._blocks.q.data_ptr()), _lib.ptr(rb._blocks.coef)))
         _lib.check(lib.gpimhip_set_reflection_shard(h, 0, 2, S["B"], 0))
         rc = lib.gpimhip_vgp_nll_grad(h, ctypes.byref(rb._mstruct), ctypes.byref(rb._vstruct), _lib.ptr(rb._Xd),
                                       _lib.ptr(rb._Yd), rb._Xd.shape[0], _lib.ptr(u), _lib.ptr(out), _lib.ptr(out[1:]))
@@ -232,8 +232,8 @@ def test_empty_border_gives_the_bits_of_the_complete_grid():
     X, Y = grid_stack((15, 14), 3, seed=8)
     rr = gpim_amd.vreconstructor(X, Y, kernel="Matern52", lengthscale=[0.5, 2.5], verbose=0)
     assert rr.solver == "reflection"
-    rc0, l0, g0 = _nll_grad_raw(rr, rr._refl, rr._wts_d)
-    rc1, l1, g1 = _nll_grad_raw(rr, rr._refl, rr._wts_d, border=(0, None, None))
+    rc0, l0, g0 = _nll_grad_raw(rr, rr._refl, rr._blocks.wts)
+    rc1, l1, g1 = _nll_grad_raw(rr, rr._refl, rr._blocks.wts, border=(0, None, None))
     assert rc0 == 0 and rc1 == 0
     assert np.array_equal(l0, l1) and np.array_equal(g0, g1)
     # ... also after the handle has carried a real border
@@ -241,7 +241,7 @@ def test_empty_border_gives_the_bits_of_the_complete_grid():
     rb, _ = pair(Xn, Yn, "Matern52", False, [0.5, 2.5])
     assert np.isfinite(rb.nll_grad()[0])
     rb._Yd = rr._Yd.to(rb._dev)          # (the completed grid's domain and weights are rr's own)
-    rc2, l2, g2 = _nll_grad_raw(rb, rr._refl, rr._wts_d.to(rb._dev), border=(0, None, None))
+    rc2, l2, g2 = _nll_grad_raw(rb, rr._refl, rr._blocks.wts.to(rb._dev), border=(0, None, None))
     assert rc2 == 0 and np.array_equal(l0, l2) and np.array_equal(g0, g2)
 
 

@@ -179,7 +179,7 @@ def test_reflection_mode_rejects_sharded_handle():
     S = rr._refl
     u = rr._u.clone()
     out = torch.empty(u.numel() + 1, dtype=torch.float64, device=u.device)
-    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rr._twoc, None, S["n_total"], 0))
+    _lib.check(lib.gpimhip_set_reflection(h, S["mask"], rr._blocks.twoc, None, S["n_total"], 0))
     try:
         _lib.check(lib.gpimhip_set_reflection_shard(h, 0, 2, S["B"], 0))
         rc = lib.gpimhip_vgp_nll_grad(h, ctypes.byref(rr._mstruct), ctypes.byref(rr._vstruct), _lib.ptr(rr._Xd),
