@@ -78,9 +78,8 @@ class HostDriver:
         mean, sd = self.predict()
         return mean, sd, self.hyperparams
 
-    def _predict_host(self, Xtest, kwargs, posterior):
-        """Resolves the test grid, calls ``posterior() -> (mean, var)`` device tensors, and returns (mean, sd) as numpy arrays
-        of shape ``fulldims`` plus the device pair (mean, sd)."""
+    def _resolve_test_grid(self, Xtest):
+        """The test grid of predict() / sample(): a new one when given, else the stored one, else the training points."""
         if Xtest is None and self.Xtest is None:
             warnings.warn("No test data provided. Using training data for prediction", UserWarning)
             self.Xtest = self.X
@@ -88,6 +87,11 @@ class HostDriver:
         elif Xtest is not None:
             self.Xtest = gprutils.prepare_test_data(Xtest, precision=self.precision)
             self._new_test_grid(Xtest)
+
+    def _predict_host(self, Xtest, kwargs, posterior):
+        """Resolves the test grid, calls ``posterior() -> (mean, var)`` device tensors, and returns (mean, sd) as numpy arrays
+        of shape ``fulldims`` plus the device pair (mean, sd)."""
+        self._resolve_test_grid(Xtest)
         if kwargs.get("verbose") is not None:
             self.verbose = kwargs.get("verbose")
         if self.verbose:
@@ -155,6 +159,13 @@ class Dense:
 
     def nll_grad(self, o, out):
         return o._handle.lib.gpimhip_nll_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), *_loss_grad(out))
+
+    def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
+        """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:
+        reconstructor._sample_supported refuses the other paths before a solver is asked."""
+        return o._handle.lib.gpimhip_sample_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                                  Xs.shape[0], ptr(z), z.shape[0], int(bool(noiseless)), float(jitter),
+                                                  ptr(mean), ptr(var), ptr(out))
 
 
 class Sparse(Dense):

@@ -143,3 +143,33 @@ def probability_of_improvement(gpmodel, X_full, X_sparse, **kwargs):
     acq, acq_d = _sweep(handle, "poi", md, sdd, best, xi, mean.shape)
     gpmodel._last_acq = acq_d if hasattr(gpmodel, "_last_pred") else None
     return acq, (mean, sd)
+
+
+def thompson_on_device(gpmodel, Xf_d, generator=None, z=None):
+    """One noiseless joint draw over the device rows ``Xf_d`` plus the posterior (mean, sd) from the same library call:
+    device tensors (draw, mean, sd).  ``z``: the (1, M) standard normals, else drawn from ``generator`` (None: the global
+    device generator) by the rule documented at ``reconstructor.sample``."""
+    if z is None:
+        z = gpmodel._draw_z(1, Xf_d.shape[0], generator=generator)
+    draws, mean_d, var_d = gpmodel._sample_device(Xf_d, z, noiseless=True)
+    return draws[0], mean_d, var_d.sqrt()
+
+
+def thompson_sampling(gpmodel, X_full, **kwargs):
+    """Thompson sampling: the acquisition map is ONE joint draw from the noiseless posterior over the grid, so its
+    maximiser is distributed like the maximiser of the unknown function.  kwargs: ``seed`` (int), ``generator`` (a device
+    torch.Generator) or ``z`` ((1, M) standard normals); none of them: the global device generator.  ``gpmodel`` is a dense
+    double-precision ``gpim_amd.reconstructor``."""
+    if not hasattr(gpmodel, "_sample_device"):
+        raise NotImplementedError("thompson_sampling needs a gpim_amd.reconstructor (joint posterior draws)")
+    Xf = gpmodel._to_device(_rows(X_full, gpmodel.precision))
+    gen, z = kwargs.get("generator"), kwargs.get("z")
+    if gen is None and z is None and kwargs.get("seed") is not None:
+        gen = torch.Generator(gpmodel._dev).manual_seed(int(kwargs.get("seed")))
+    if z is not None:
+        z = gpmodel._to_device(z if torch.is_tensor(z) else np.asarray(z)).reshape(1, -1)
+    acq_d, mean_d, sd_d = thompson_on_device(gpmodel, Xf, generator=gen, z=z)
+    shape = tuple(np.shape(X_full)[1:])
+    gpmodel._last_acq = acq_d
+    host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(gpmodel._np_out, copy=False)
+    return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))

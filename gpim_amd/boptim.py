@@ -69,7 +69,9 @@ class boptimizer:
     isotropic, precision, alpha, beta, xi, dscale, batch_dscale, batch_out_max, gamma, memory,
     exit_strategy, mask, extent, simulate_measurement, y_true, save_checkpoints, filename.
 
-    gpim_amd extension: ``shard_candidates=True`` (with torch.distributed initialised, one process
+    gpim_amd extension: ``acquisition_function='ts'`` is Thompson sampling -- one noiseless joint draw of the
+    posterior over the grid per step (reconstructor.sample), from a generator seeded with ``seed``; dense
+    double-precision surrogates only.  ``shard_candidates=True`` (with torch.distributed initialised, one process
     per GPU) makes every rank sweep only its contiguous block of the test grid; an all-gather of
     each rank's top-``batch_size`` (value, index) pairs gives all ranks the same global ranking
     (SURVEY 8(e)).  Training stays replicated -- it is deterministic, so all ranks hold the same
@@ -117,6 +119,14 @@ class boptimizer:
         self.save_checkpoints = kwargs.get("save_checkpoints", False)
         self.filename = kwargs.get("filename", "./boptim_results")
         self.shard_candidates = kwargs.get("shard_candidates", False)
+        self._ts_generator = None
+        if acquisition_function == 'ts':
+            if self.shard_candidates:
+                raise NotImplementedError("acquisition_function='ts' with shard_candidates=True: a joint draw does not "
+                                          "split over candidate blocks")
+            self.surrogate_model._sample_supported()
+            # the draws of all exploration steps come from this generator: a run is reproducible from `seed`
+            self._ts_generator = torch.Generator(self.surrogate_model._dev).manual_seed(seed)
         self.indices_all, self.vals_all = [], []
         self.target_func_vals, self.gp_predictions = [y_seed.copy()], _LazyMaps()
         self._mask_d = None
@@ -254,6 +264,16 @@ class boptimizer:
             mean_d, sd_d = self._retain_maps(mean_d, sd_d)
             self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
             vals_list, indices_list = self._rank_device(acq_d, grid_shape, masked=True)
+        elif af == 'ts':
+            # Thompson sampling: one noiseless joint draw over the grid per step, mean and sd from the same call; the
+            # draw stays on the device and is ranked like the built-in maps
+            if self._Xfull_d is None:
+                self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
+            acq_d, mean_d, sd_d = acqfunc.thompson_on_device(sm, self._Xfull_d, generator=self._ts_generator)
+            grid_shape = tuple(np.shape(self.X_full)[1:])
+            mean_d, sd_d = self._retain_maps(mean_d, sd_d)
+            self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
+            vals_list, indices_list = self._rank_device(acq_d, grid_shape)
         elif isinstance(af, types.FunctionType):
             acq, pred = af(sm, self.X_full, self.X_sparse)
             sm._last_acq = None
@@ -261,7 +281,7 @@ class boptimizer:
             vals_list, indices_list = self._rank(np.asarray(acq))
         else:
             raise NotImplementedError(
-                "Choose between 'cb', 'ei', and 'poi' acquisition functions or define your own")
+                "Choose between 'cb', 'ei', 'poi' and 'ts' acquisition functions or define your own")
         if not self.batch_update:
             return vals_list, indices_list
         radius = self.batch_dscale

@@ -12,6 +12,7 @@
 #include "border.hpp"
 #include "vgp.hpp"
 #include "sm.hpp"
+#include "sample.hpp"
 
 static thread_local std::string g_err;
 void gpim_set_error(const std::string& s) { g_err = s; }
@@ -755,6 +756,8 @@ int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<
 
 static void vgp_release(gpimhip_ctx* h);
 static void sm_release(gpimhip_ctx* h);
+static void sample_release(gpimhip_ctx* h);
+static int64_t sample_bytes(const gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -804,6 +807,7 @@ int gpimhip_set_precision(gpimhip_handle h, int32_t bits) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     ws_release_matrix(h);               // sized by the element type
     ws_release_predict(h);
+    sample_release(h);
     h->fp32 = want;
     return GPIMHIP_OK;
 }
@@ -817,6 +821,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     vgp_release(h);
     sm_release(h);
     border_release(h);
+    sample_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
     dev_free(h, &h->keys, h->keys_cap);
@@ -837,11 +842,11 @@ int gpimhip_destroy(gpimhip_handle h) {
     return GPIMHIP_OK;
 }
 
-// (with a border: the handle of S is part of the model's workspace)
+// (with a border: the handle of S is part of the model's workspace; so is the factorisation context of the draws)
 int64_t gpimhip_workspace_bytes(gpimhip_handle h) {
     if (!h) return 0;
     const BorderWs* w = bws(h);
-    return h->bytes + (w && w->sub ? w->sub->bytes : 0);
+    return h->bytes + (w && w->sub ? w->sub->bytes : 0) + sample_bytes(h);
 }
 
 int gpimhip_timing_enable(gpimhip_handle h, int enable) {
@@ -2040,6 +2045,114 @@ int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X
         GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
     return finish_and_check(h);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// joint posterior draws of the exact GP (sample.hip): one factorisation of the joint covariance of
+// [X; Xs].  The matrix belongs to this path: a Bayesian-optimisation step alternates training at order N with a draw at
+// order N + M, and sending the draw through ws_ensure would free and re-allocate A, B and Tm twice per step (two of the
+// three unused here).  `sub` is a handle of its own on the model handle's stream, as the border's: its workspace holds
+// what the step schedule needs (diagonal-block inverses, plans, status word, theta, O(order) vectors), no matrices.
+// J, the stacked coordinates and the vectors grow only when a larger order arrives.
+// ------------------------------------------------------------------------------------------
+struct SampleWs {
+    gpimhip_ctx* sub = nullptr;
+    double* J = nullptr; int64_t j_cap = 0;         // padded (N + M)^2 joint covariance -> its factor
+    double* XX = nullptr; int64_t xx_cap = 0;       // [X; Xs]
+    double* vec = nullptr; int64_t vec_cap = 0;     // t (order) | piece (512) | mean (M): forward substitution, draws
+};
+static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
+static int64_t sample_bytes(const gpimhip_ctx* h) {
+    const SampleWs* w = sws(h);
+    return w && w->sub ? w->sub->bytes : 0;
+}
+static void sample_release(gpimhip_ctx* h) {
+    SampleWs* w = sws(h);
+    if (!w) return;
+    dev_free(h, &w->J, w->j_cap);
+    dev_free(h, &w->XX, w->xx_cap);
+    dev_free(h, &w->vec, w->vec_cap);
+    if (w->sub) gpimhip_destroy(w->sub);
+    delete w;
+    h->sample = nullptr;
+}
+
+// sub->z = L11^-1 y from the factor L of the joint matrix: block forward substitution over the block rows that hold
+// training points, a panel of four blocks at a time against the inverted diagonal blocks the step schedule left in dinv
+// (distops.hip).  The last of these block rows may hold test points too: their entries of z are never read.
+// t (order of the matrix): the running products L(rows, panels so far) z; piece: 512.
+static int sample_forward(gpimhip_ctx* sub, const double* L, int64_t ld, const double* y, int64_t N, double* t, double* piece) {
+    const int nbn = (int)((N + NB - 1) / NB);
+    GP_TRY(launch_pad_copy(sub, y, N, sub->ypad, sub->np));
+    HIP_TRY(hipMemsetAsync(t, 0, (size_t)sub->np * sizeof(double), sub->stream));
+    for (int g0 = 0; g0 < nbn; g0 += OUTER_W) {
+        const int nblk = std::min(OUTER_W, nbn - g0), wd = nblk * NB;
+        const int64_t r0 = (int64_t)g0 * NB;
+        const double* P = L + r0 * ld + r0;
+        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, sub->ypad + r0, t + r0, piece));
+        HIP_TRY(hipMemcpyAsync(sub->z + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
+        GP_TRY(launch_dist_rows_acc(sub, P + (int64_t)wd * ld, ld, (int64_t)nbn * NB - r0 - wd, wd, piece, t + r0 + wd));
+    }
+    return GPIMHIP_OK;
+}
+
+static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                       const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
+                       double* var_out, double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sample) h->sample = new SampleWs();
+    SampleWs* w = sws(h);
+    if (!w->sub) GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
+    gpimhip_ctx* sub = w->sub;
+    sub->stream = h->stream;
+    sub->nbatch = 1;
+    const int64_t NM = N + M, d = m->dim;
+    GP_TRY(ws_ensure_b(sub, NM, 1, 1, false));
+    const int64_t np = sub->np, ld = sub->ld;
+    GP_TRY(dev_grow(h, &w->J, &w->j_cap, np * ld));
+    GP_TRY(dev_grow(h, &w->XX, &w->xx_cap, np * GPIMHIP_MAX_DIM));
+    GP_TRY(dev_grow(h, &w->vec, &w->vec_cap, 2 * np + 4 * NB));
+    double *t = w->vec, *piece = t + np, *mean_ws = piece + 4 * NB;
+    HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemcpyAsync(w->XX, X, (size_t)(N * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(w->XX + N * d, Xs, (size_t)(M * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    // J (lower tiles; identity padding at the end), the two diagonal terms, L
+    // (stage timers of the model handle: 4 covariance build, 0 factorisation, 1 forward substitution, 5 each sweep of the draws)
+    GP_TRY(launch_theta(sub, m, u));
+    {
+        StageTimer tm(h, 4);
+        GP_TRY(launch_kmat(sub, m, w->XX, NM, nullptr, NM, sub->theta, 0.0, 0, w->J, ld, np, np, 1, 1, 0, 0, 0));
+        GP_TRY(launch_sample_diag(sub, w->J, ld, N, M, sub->theta, noiseless, jitter_s));
+    }
+    { StageTimer tm(h, 0); GP_TRY(launch_potrf(sub, w->J, np, ld, sub->info)); }
+    {
+        StageTimer tm(h, 1);
+        GP_TRY(sample_forward(sub, w->J, ld, y, N, t, piece));
+    }
+    for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
+        StageTimer tm(h, 5);
+        GP_TRY(launch_sample_draws(sub, w->J, ld, N, M, sub->z, Z, S, s0, sub->theta, noiseless, jitter_s, mean_ws, mean_out,
+                                   var_out, samples_out));
+    }
+    return finish_and_check(sub);
+}
+
+extern "C" {
+
+int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                         const double* u, const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless,
+                         double jitter, double* mean_out, double* var_out, double* samples_out) {
+    FP64_ONLY(h);
+    if (!h || !X || !y || !u || !Xs || !Z || !samples_out || N < 1 || M < 1 || S < 1 || !(jitter >= 0.0))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_sample_exact: not available in reflection mode (the dense double-precision engine only)");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_impl(h, m, X, y, N, u, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
 }
 
 }  // extern "C"

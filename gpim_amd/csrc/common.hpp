@@ -208,6 +208,8 @@ struct gpimhip_ctx {
     void* sm = nullptr;
     // border of the reflection blocks (missing points of an incomplete grid), owned by api.hip (BorderWs); border_release()
     void* border = nullptr;
+    // joint posterior draws: the (N + M)^2 matrix and its factorisation context, owned by api.hip (SampleWs); sample_release()
+    void* sample = nullptr;
     double* refine = nullptr; int64_t refine_cap = 0;    // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
 };

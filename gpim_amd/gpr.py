@@ -308,6 +308,84 @@ class reconstructor(_solvers.HostDriver):
         mean, var = self._posterior(self._solver.predict, Xrows_d)
         return mean, var.sqrt()
 
+    # ------------------------------------------------------------------ joint posterior draws
+    _SAMPLE_ENGINE = "joint posterior draws are built for the dense double-precision engine only (%s)"
+
+    def _sample_supported(self):
+        if self.do_sparse:
+            raise NotImplementedError(self._SAMPLE_ENGINE % "sparse=True")
+        if self.do_structured or self.do_symm:
+            raise NotImplementedError(self._SAMPLE_ENGINE % "structured=True")
+        if self.precision == "single":
+            raise NotImplementedError(self._SAMPLE_ENGINE % "precision='single'")
+
+    def _require_finite(self, Xrows_d):
+        """ValueError unless the test rows are finite; one device-to-host look per tensor (boptimizer draws on the same
+        grid at every step)."""
+        if getattr(self, "_finite_rows", None) is Xrows_d:
+            return
+        if not bool(torch.isfinite(Xrows_d).all()):
+            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+        self._finite_rows = Xrows_d
+
+    def _sample_device(self, Xrows_d, z_d, noiseless=False, jitter=None):
+        """(samples (S, M), mean (M), var (M)) device tensors of joint draws at the (M, d) device rows `Xrows_d` with the
+        standard normals `z_d` (S, M): samples[s] = mean + chol(Sigma) z_d[s].  One library call; mean and var are the
+        posterior of predict() (noise included)."""
+        self._sample_supported()
+        self._check_data()
+        S, M = z_d.shape
+        N = self._Xd.shape[0]
+        if Xrows_d.shape[0] != M:
+            raise ValueError("z must have shape (n_samples, %d); got %s" % (Xrows_d.shape[0], tuple(z_d.shape)))
+        self._require_finite(Xrows_d)
+        jitter = self._spec.jitter if jitter is None else float(jitter)
+        # the one large allocation of the call: the padded (N + M)^2 joint covariance (kept by the handle, grow-only)
+        order = -(-(N + M) // 128) * 128
+        need = order * (order + (16 if order >= 1024 else 0)) * 8
+        if need > getattr(self, "_sample_bytes", 0):
+            free = torch.cuda.mem_get_info(self._dev)[0]
+            if need > free:
+                raise MemoryError("sample: the joint covariance of %d training and %d test points needs %.2f GiB of device "
+                                  "memory, %.2f GiB are free" % (N, M, need / 2.0 ** 30, free / 2.0 ** 30))
+        out = torch.empty((S, M), dtype=_F64, device=self._dev)
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        var = torch.empty((M,), dtype=_F64, device=self._dev)
+        _lib.check(self._solver.sample(self, Xrows_d, z_d, noiseless, jitter, mean, var, out))
+        self._sample_bytes = max(need, getattr(self, "_sample_bytes", 0))
+        return out, mean, var
+
+    def _draw_z(self, n_samples, M, seed=None, generator=None):
+        if generator is None and seed is not None:
+            generator = torch.Generator(self._dev).manual_seed(int(seed))
+        return torch.randn((n_samples, M), dtype=_F64, device=self._dev, generator=generator)
+
+    def sample(self, n_samples=1, Xtest=None, noiseless=False, seed=None, z=None, jitter=None):
+        """Joint draws from the posterior on the test grid: ndarray of shape ``(n_samples, *fulldims)``, each slice one
+        plausible reconstruction ``mean + chol(Sigma) z_s`` with ``Sigma`` the full posterior covariance of the grid plus
+        ``((0 if noiseless else noise) + jitter) I``.  ``Xtest`` as in ``predict``; ``jitter`` defaults to the model's.
+        ``z``: optional ``(n_samples, M)`` array or device tensor of standard normals, used as is (the result is then a
+        pure function of the model).  When absent it is drawn as
+        ``torch.randn((n_samples, M), dtype=torch.float64, device=dev, generator=g)`` with ``g = torch.Generator(dev).manual_seed(seed)``
+        (``seed is None``: the global device generator).  Dense double-precision models only; the test grid must be
+        finite."""
+        self._sample_supported()
+        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+            # (refused before it replaces the stored test grid)
+            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+        self._resolve_test_grid(Xtest)
+        Xs = self._Xtest_d
+        M = Xs.shape[0]
+        if z is None:
+            z_d = self._draw_z(int(n_samples), M, seed)
+        else:
+            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
+            if z_d.dim() != 2 or z_d.shape != (int(n_samples), M):
+                raise ValueError("z must have shape (n_samples, %d) = (%d, %d); got %s"
+                                 % (M, int(n_samples), M, tuple(z_d.shape)))
+        out, _, _ = self._sample_device(Xs, z_d, noiseless, jitter)
+        return out.cpu().numpy().reshape((z_d.shape[0],) + tuple(self.fulldims)).astype(self._np_out, copy=False)
+
     def run(self, **kwargs):
         """train + predict; returns (mean, sd, hyperparams) (gpr.py:257-283)."""
         if kwargs.get("learning_rate") is not None:

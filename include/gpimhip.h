@@ -146,6 +146,26 @@ int gpimhip_predict_exact(gpimhip_handle h, const gpimhip_model_t* m,
                           const double* u, const double* Xs, int64_t M,
                           double* mean_out, double* var_out);
 
+/* S joint draws from the posterior at Xs (M x d, finite), with the posterior mean and variance from the same pass.
+ * The reference draws through pyro / gpytorch rsample (its multi-output predictor, gpim/gpreg/vgpr.py:213-221); its
+ * exact GP exposes full_cov only.  draw s = mean + chol(Sigma) Z[s],  Sigma = K** - K*^T (K + (s_n^2 + jitter) I)^-1 K* + d I,
+ * d = (noiseless ? 0 : s_n^2) + jitter (the argument below; the model's own jitter stays on the training block).
+ * One Cholesky of the joint covariance of [X; Xs] (order N + M) on a matrix that belongs to this entry point
+ * (grow-only, counted by gpimhip_workspace_bytes, released by gpimhip_destroy / gpimhip_set_precision): the workspace
+ * of fit / predict is not touched.  DESIGN.md section 15.
+ *   Z            S x M standard normals (device), draw s contiguous
+ *   mean_out, var_out   M doubles each or NULL; var as gpimhip_predict_exact (noise included, jitter excluded)
+ *   samples_out  S x M
+ * Double-precision handles outside reflection mode only; NULL arguments, S < 1, M < 1 or jitter < 0 -> GPIMHIP_E_BADARG.
+ * Synchronises at the end (to report NOT_PD). */
+int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m,
+                         const double* X, const double* y, int64_t N, const double* u,
+                         const double* Xs, int64_t M,
+                         const double* Z, int32_t S,
+                         int32_t noiseless, double jitter,
+                         double* mean_out, double* var_out,
+                         double* samples_out);
+
 /* Batched forms: B independent problems with the SAME N (and the same model description), advanced in
  * lock-step by every launch (grid.y = problem index) -- B spectral slices of a cube share each
  * latency-bound step of the blocked factorisation instead of paying for it B times.
@@ -524,6 +544,8 @@ int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64
  *        3 = predictive-variance product L^-1 K(X,X*) (one launch per test-point slab),
  *        4 = spectral-mixture covariance build K(X, X) (gpimhip_sm_*: one launch per evaluation),
  *        5 = spectral-mixture gradient contraction (its tile launch and the record sum).
+ * gpimhip_sample_exact: 4 = build of the joint covariance, 0 = its factorisation, 1 = the forward substitution z = L11^-1 y,
+ *        5 = the draws kernel (one interval per sweep of the trapezoid).
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
