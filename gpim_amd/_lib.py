@@ -152,6 +152,9 @@ _PROTOS = {
                                         c_dp]),
     "gpimhip_step_plan_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "gpimhip_step_plan_host_f32": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                                  ctypes.POINTER(ctypes.c_int32)]),
     "gpimhip_vgp_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
                                             c_dp, ctypes.c_int64, c_dp, c_dp, c_dp]),
     "gpimhip_fit_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp, c_dp,

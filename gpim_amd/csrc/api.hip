@@ -571,7 +571,10 @@ static int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double*
     GP_TRY(launch_gemv_t_tri(h, h->A, ld, np, h->z, h->gemv_part, defer_alpha && !h->fp32 ? nullptr : h->alpha));
     if (!h->fp32) return GPIMHIP_OK;
     const int B = h->nbatch, nb = (int)(np / NB);
-    const int S = std::max(1, std::min(8, 512 / std::max(1, nb * B)));        // >= ~512 workgroups per launch
+    // >= ~512 workgroups per launch of ONE problem.  S sets the order in which the residual's partial sums are added, so it
+    // must not depend on the batch: a problem of a lock-step batch keeps the bits of its stand-alone run (it used to be
+    // 512 / (nb * B): from 17 block columns a batch of four summed in another order than the same problem alone).
+    const int S = std::max(1, std::min(8, 512 / std::max(1, nb)));
     double *res = h->refine, *delta = res + (int64_t)B * np, *scratch = delta + (int64_t)B * np;
     for (int pass = 0; pass < refine_passes(); ++pass) {
         GP_TRY(launch_kres(h, m, X, x_bs, N, scratch, S, res));

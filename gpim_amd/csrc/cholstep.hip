@@ -685,6 +685,55 @@ static bool plan_inverse(int nb, std::vector<std::vector<TileDesc>>& fill, std::
     return true;
 }
 
+// ---- what the launches of a SINGLE-PRECISION factorisation apply of the trailing update (policy above) ------------------
+// fill[j]: hosted by the step launch of block column j; rest[p]: the tile-engine launch before the first step of outer
+// panel p (what of the panel's bulk update exceeds the cap); ndiag[j]: the diagonal tiles j+1 .. j+ndiag[j] that D_j
+// (diag_update_kernel_f32) updates with column j -- every diagonal tile of the window, eagerly.  Host data only:
+// step_plan_build uploads it, gpimhip_step_plan_host_f32 hands it to the test that replays it.
+static void plan_updates_f32(int nb, std::vector<std::vector<TileDesc>>& fill, std::vector<std::vector<TileDesc>>& rest,
+                             std::vector<int>& ndiag) {
+    const int W = STEP_W;
+    const int npanel = (nb + W - 1) / W;
+    fill.assign(nb, {});
+    rest.assign(npanel, {});
+    ndiag.assign(nb, 0);
+    for (int p = 0; p < npanel; ++p) {
+        const int p0 = p * W, p1 = std::min(p0 + W, nb), ncol = p1 - p0;
+        // bulk(p-1): columns >= p0 + W, k-blocks = the columns of panel p-1.
+        // Pair mode (large matrices): panels are applied two at a time to everything at least two panels to their
+        // right -- k-depth 1024, half the passes over the trailing matrix -- and an even panel alone only to the
+        // one destination panel that needs it before its partner is factored:
+        //   start of an odd panel p  (p-1 even): panel p-1 -> destination panel p+1 only           (k-depth 512)
+        //   start of an even panel p (p-1 odd) : panels p-2, p-1 -> every column >= p0 + W          (k-depth 1024)
+        std::vector<TileDesc> bulk;
+        if (p > 0 && p0 + W < nb) {
+            if (!pair_mode32(nb)) {
+                lower_patches(bulk, p0 + W, nb, p0 - W, p0);
+            } else if ((p - 1) % 2 == 0) {
+                const int c0 = p0 + W, c1 = std::min(p0 + 2 * W, nb);
+                for (int ig = c0 / 8; ig <= (nb - 1) / 8; ++ig)
+                    for (int i = std::max(c0, ig * 8); i < std::min(nb, ig * 8 + 8); ++i)
+                        for (int j = c0; j < std::min(c1, i + 1); ++j) bulk.push_back({i, j, p0 - W, p0});
+            } else {
+                lower_patches(bulk, p0 + W, nb, p0 - 2 * W, p0);
+            }
+        }
+        const size_t per = std::min<size_t>((size_t)fill_cap32(nb), (bulk.size() + ncol - 1) / ncol);
+        size_t taken = 0;
+        for (int j = p0; j < p1; ++j) {
+            const int kb0 = std::max(0, p0 - W);
+            if (j > kb0)
+                for (int i = j + 1; i < nb; ++i) fill[j].push_back({i, j, kb0, j});
+            for (size_t q = 0; q < per && taken < bulk.size(); ++q) fill[j].push_back(bulk[taken++]);
+        }
+        while (taken < bulk.size()) rest[p].push_back(bulk[taken++]);
+    }
+    for (int j = 0; j < nb; ++j) {
+        const int p1 = std::min((j / W) * W + W, nb);
+        ndiag[j] = std::max(0, std::min(nb, p1 + W) - (j + 1));
+    }
+}
+
 static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_inverse) {
     const bool fp32 = h->fp32 != 0;
     if (P.nb == nb && P.fp32 == (int)fp32) return GPIMHIP_OK;
@@ -692,41 +741,9 @@ static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_invers
     const int W = STEP_W;
     const int npanel = (nb + W - 1) / W;
     std::vector<std::vector<TileDesc>> fill(nb), post, rest(npanel);
-    if (!fp32) {
-        plan_updates(nb, fill);
-    } else {
-        for (int p = 0; p < npanel; ++p) {
-            const int p0 = p * W, p1 = std::min(p0 + W, nb), ncol = p1 - p0;
-            // bulk(p-1): columns >= p0 + W, k-blocks = the columns of panel p-1.
-            // Pair mode (large matrices): panels are applied two at a time to everything at least two panels to their
-            // right -- k-depth 1024, half the passes over the trailing matrix -- and an even panel alone only to the
-            // one destination panel that needs it before its partner is factored:
-            //   start of an odd panel p  (p-1 even): panel p-1 -> destination panel p+1 only           (k-depth 512)
-            //   start of an even panel p (p-1 odd) : panels p-2, p-1 -> every column >= p0 + W          (k-depth 1024)
-            std::vector<TileDesc> bulk;
-            if (p > 0 && p0 + W < nb) {
-                if (!pair_mode32(nb)) {
-                    lower_patches(bulk, p0 + W, nb, p0 - W, p0);
-                } else if ((p - 1) % 2 == 0) {
-                    const int c0 = p0 + W, c1 = std::min(p0 + 2 * W, nb);
-                    for (int ig = c0 / 8; ig <= (nb - 1) / 8; ++ig)
-                        for (int i = std::max(c0, ig * 8); i < std::min(nb, ig * 8 + 8); ++i)
-                            for (int j = c0; j < std::min(c1, i + 1); ++j) bulk.push_back({i, j, p0 - W, p0});
-                } else {
-                    lower_patches(bulk, p0 + W, nb, p0 - 2 * W, p0);
-                }
-            }
-            const size_t per = std::min<size_t>((size_t)fill_cap32(nb), (bulk.size() + ncol - 1) / ncol);
-            size_t taken = 0;
-            for (int j = p0; j < p1; ++j) {
-                const int kb0 = std::max(0, p0 - W);
-                if (j > kb0)
-                    for (int i = j + 1; i < nb; ++i) fill[j].push_back({i, j, kb0, j});
-                for (size_t q = 0; q < per && taken < bulk.size(); ++q) fill[j].push_back(bulk[taken++]);
-            }
-            while (taken < bulk.size()) rest[p].push_back(bulk[taken++]);
-        }
-    }
+    std::vector<int> ndiag32;
+    if (!fp32) plan_updates(nb, fill);
+    else plan_updates_f32(nb, fill, rest, ndiag32);
     P.n_update.assign(nb, 0);
     for (int j = 0; j < nb; ++j)
         for (auto& t : fill[j]) P.n_update[j] += t.kb1 - t.kb0;
@@ -764,10 +781,9 @@ static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_invers
             for (TileDesc& t : fill[j])
                 if ((t.kb1 >> 16) == TK_UPDATE && t.ci == j + 1 && t.cj == j) { t.kb1 |= TILE_COPY; P.copy[j] = 1; }
         P.fill[j] = put(fill[j]);
-        const int p1 = std::min((j / W) * W + W, nb);
         // diagonal tiles D_j updates (count): double precision the next one only (the others receive column j through
         // the hosted window update of their own step, plan_updates); float handles every tile of the window, eagerly
-        P.diag[j] = PlanRange{0, fp32 ? std::max(0, std::min(nb, p1 + W) - (j + 1)) : (j + 1 < nb ? 1 : 0)};
+        P.diag[j] = PlanRange{0, fp32 ? ndiag32[j] : (j + 1 < nb ? 1 : 0)};
     }
     for (int p = 0; p < npanel; ++p) P.bulk_rest[p] = put(rest[p]);
     for (auto& v : post) P.post.push_back(put(v));
@@ -782,6 +798,17 @@ static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_invers
     return GPIMHIP_OK;
 }
 
+static int64_t emit_plan_records(int launch, const std::vector<TileDesc>& v, int32_t* out, int64_t cap, int64_t n) {
+    for (const TileDesc& t : v) {
+        if (out && n < cap) {
+            int32_t* r = out + 6 * n;
+            r[0] = launch; r[1] = t.ci; r[2] = t.cj; r[3] = t.kb0; r[4] = t.kb1 & 0xffff; r[5] = t.kb1 >> 16;
+        }
+        ++n;
+    }
+    return n;
+}
+
 // The double-precision plan as host data, for tests (no GPU involved): records of six int32 -- launch index (< nb: the
 // step launch of that block column; >= nb: the launches after the last step), ci, cj, kb0, kb1, kind.
 extern "C" int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out) {
@@ -791,17 +818,30 @@ extern "C" int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t*
     std::vector<uint8_t> pair(nb, 0);
     if (with_inverse && !plan_inverse(nb, fill, post, pair)) return GPIMHIP_E_BADARG;
     int64_t n = 0;
-    auto emit = [&](int launch, const std::vector<TileDesc>& v) {
-        for (const TileDesc& t : v) {
-            if (out && n < cap) {
-                int32_t* r = out + 6 * n;
-                r[0] = launch; r[1] = t.ci; r[2] = t.cj; r[3] = t.kb0; r[4] = t.kb1 & 0xffff; r[5] = t.kb1 >> 16;
-            }
-            ++n;
-        }
-    };
-    for (int j = 0; j < nb; ++j) emit(j, fill[j]);
-    for (size_t q = 0; q < post.size(); ++q) emit(nb + (int)q, post[q]);
+    for (int j = 0; j < nb; ++j) n = emit_plan_records(j, fill[j], out, cap, n);
+    for (size_t q = 0; q < post.size(); ++q) n = emit_plan_records(nb + (int)q, post[q], out, cap, n);
+    *n_out = n;
+    return GPIMHIP_OK;
+}
+
+// The single-precision plan (plan_updates_f32, with plan_inverse on top of it when with_inverse != 0 -- what
+// step_plan_build builds for a float handle), same records in the order of the uploaded tile list.  What the float
+// schedule adds: launch index -(p + 1) = the launch before the first step of outer panel p (bulk_rest), and
+// diag_out[j] (nb int32, may be NULL) = the diagonal tiles D_j updates.
+extern "C" int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out,
+                                          int32_t* diag_out) {
+    if (nb < 1 || nb > 4096 || !n_out) return GPIMHIP_E_BADARG;
+    std::vector<std::vector<TileDesc>> fill, rest, post;
+    std::vector<int> ndiag;
+    plan_updates_f32(nb, fill, rest, ndiag);
+    std::vector<uint8_t> pair(nb, 0);
+    if (with_inverse && !plan_inverse(nb, fill, post, pair)) return GPIMHIP_E_BADARG;
+    int64_t n = 0;
+    for (int j = 0; j < nb; ++j) n = emit_plan_records(j, fill[j], out, cap, n);
+    for (size_t p = 0; p < rest.size(); ++p) n = emit_plan_records(-((int)p + 1), rest[p], out, cap, n);
+    for (size_t q = 0; q < post.size(); ++q) n = emit_plan_records(nb + (int)q, post[q], out, cap, n);
+    if (diag_out)
+        for (int j = 0; j < nb; ++j) diag_out[j] = ndiag[j];
     *n_out = n;
     return GPIMHIP_OK;
 }

@@ -359,7 +359,10 @@ static int mid_tiles() {
 template <typename R, bool A_KM, bool B_KM, int EPI>
 static int launch_one(gpimhip_ctx* h, const GemmArgs& g) {
     if (g.ntiles <= 0) return GPIMHIP_OK;
-    const int64_t total = (int64_t)g.ntiles * h->nbatch;
+    // The column-sum epilogue adds its partial sums across the waves of the workgroup, in an order that follows the wave
+    // layout: its shape is chosen from the problem's own tiles, so that a problem of a lock-step batch gets the bits of its
+    // stand-alone prediction (N = 2300, M = 500: 72 tiles -- 8 waves alone, 4 waves in a batch of four otherwise).
+    const int64_t total = (int64_t)g.ntiles * (EPI == EPI_COLSUMSQ ? 1 : h->nbatch);
     const bool small = total <= 256;
     if (EPI == EPI_STORE && small && !g.inplace)
         // few tiles: spread each over four CUs (64x64 quadrants)

@@ -537,6 +537,14 @@ int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat
  * -sum_k A[ci,k] Tm[k,cj]; k over block columns [kb0, kb1)).  *n_out = number of records of the plan. */
 int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out);
 
+/* The same for a single-precision handle (cholstep32.hip: hosted fill capped from 88 block columns, pair mode from 160),
+ * records in the order of the tile list the handle uploads.  What the float schedule adds: launch index -(p + 1) = the
+ * tile-engine launch before the first step of outer panel p (four block columns; the part of the panel's bulk update
+ * that exceeds the cap), and diag_out (nb int32, may be NULL): diag_out[j] = how many diagonal tiles, (j+1, j+1)
+ * onwards, the launch after the panel solve of block column j updates with column j. */
+int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out,
+                               int32_t* diag_out);
+
 /* Stage timing for bench.py (HIP events on the handle's stream, recorded only while enabled).
  * stage: 0 = Cholesky (all launches of one factorisation, including the tile operations of the triangular inverse
  *            they host), 1 = what is left of the triangular inverse after the last step,

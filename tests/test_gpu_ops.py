@@ -354,7 +354,7 @@ def test_nanmax_and_topk(eng):
 
 
 def _fit_once(_lib, H, N, T, seed):
-    """T Adam iterations on a seeded problem through one handle; returns (history, final u)."""
+    """T Adam iterations on a seeded problem through one handle, in the handle's precision; returns (history, final u)."""
     from gpim_amd.kernels import KernelSpec
     X, y = scattered(N, 2, seed=seed, grid=64 if N <= 3000 else 128)
     spec = KernelSpec("RBF", 2, [[1., 1.], [20., 20.]], jitter=1e-5)
@@ -367,23 +367,32 @@ def _fit_once(_lib, H, N, T, seed):
     return hist.cpu().numpy(), u.cpu().numpy()
 
 
-def test_handle_reuse_across_sizes_and_regimes(eng):
+@pytest.mark.parametrize("precision", ["double", "single"])
+def test_handle_reuse_across_sizes_and_regimes(eng, precision):
     """One handle walks through the three regimes (fused small-N trainer, graph-replayed blocked path, plain in-order
     launches at large N) in growing and shrinking order -- workspace, tile plans and the captured graph are re-used or
-    rebuilt -- and every result is bit-identical to the one of a fresh handle."""
+    rebuilt -- and every result is bit-identical to the one of a fresh handle.  On a single-precision handle too: float
+    matrices in the same workspace, the float plan, and the double fused trainer at N <= 128 in between."""
     _lib, H = eng
+    if precision == "single":
+        H = _lib.Handle(precision="single")
     # (1207 / 449 / 448: a ragged last block -- at most 64 valid rows, whose padding the tile engine skips -- between
     # sizes of the same padded order that fill it: what a skipped region holds from the previous fit must never be read)
     sizes = [(100, 12), (700, 10), (1500, 4), (300, 10), (6200, 2), (60, 12), (1500, 4), (6200, 2),
              (1207, 4), (1250, 4), (1207, 4), (1216, 4), (1217, 4), (449, 6), (512, 6), (448, 6)]
-    for N, T in sizes:
-        got = _fit_once(_lib, H, N, T, seed=N)
-        fresh = _lib.Handle()
-        try:
-            want = _fit_once(_lib, fresh, N, T, seed=N)
-        finally:
-            fresh.close()
-        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), N
+    try:
+        for N, T in sizes:
+            got = _fit_once(_lib, H, N, T, seed=N)
+            fresh = _lib.Handle(precision=precision)
+            try:
+                want = _fit_once(_lib, fresh, N, T, seed=N)
+            finally:
+                fresh.close()
+            assert np.isfinite(got[0]).all()
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), N
+    finally:
+        if precision == "single":
+            H.close()
 
 
 def test_two_handles_interleaved(eng):

@@ -359,6 +359,52 @@ def test_not_pd_freezes_at_failing_iteration(gpim, npts, small, monkeypatch):
     assert np.isfinite(mean).all() and np.isfinite(sd).all()
 
 
+def test_not_pd_freezes_at_failing_iteration_single_precision(gpim, monkeypatch):
+    """The same run (300 points, every point twice) with precision='single'.  The oracle is fp64, so the failing
+    iteration cannot be the oracle's: a float32 trailing update loses the pivot of a matrix that is singular without
+    its noise term at noise ~ N eps32 |K|, a double one at ~ N eps64 |K|, and with lr = 1 Adam lowers the noise by a
+    factor e per iteration -- the float engine freezes ln(eps32 / eps64) = 29 ln 2 = 20.1 iterations before the oracle,
+    give or take the same 8 iterations for borderline pivots.  Up to 5 iterations before the freeze (noise e^5 above
+    the failing level) the history follows the oracle's at the float bar of test_reconstructor_single_precision
+    (2e-2).  The device loop freezes as in double: same exception class, one history row per completed iteration,
+    finite parameters; and with a jitter above N eps32 |K| = 600 x 6e-8 x 10 = 3.6e-4 (1e-3) the frozen parameters
+    give a finite posterior."""
+    monkeypatch.setenv("GPIMHIP_NO_SMALLN", "1")
+    side = int(np.ceil(np.sqrt(300)))
+    R = np.sin(np.arange(side)[:, None] / 3.0) * np.cos(np.arange(side)[None, :] / 4.0)
+    Xg = gpim.utils.get_full_grid(R).astype(np.float64)
+    Xd = np.concatenate([Xg, Xg], axis=2)
+    Rd = np.concatenate([R, R], axis=1)
+    kw = dict(kernel="RBF", lengthscale=[[1., 1.], [10., 10.]], learning_rate=1.0, iterations=400, verbose=0,
+              jitter=0.0)
+    rec = gpim.reconstructor(Xd, Rd, Xd, precision="single", **kw)
+    assert rec._handle.precision == "single"
+    orc = O.reconstructor(Xd, Rd, Xd, **kw)
+    # same start: precision='single' draws its initial hyper-parameters in float32, other numbers from the same seed
+    rec._u.copy_(torch.cat([p.detach().reshape(-1) for p in orc.model.kernel.parameters()]).to(rec._u.device))
+    u_before = rec._u.clone()
+    with pytest.raises(torch.linalg.LinAlgError):
+        rec.train()
+    n_done = len(rec.hyperparams["noise"])
+    assert 0 < n_done < 400
+    assert torch.isfinite(rec._u).all() and not torch.equal(rec._u.cpu(), u_before.cpu())
+    with pytest.raises(torch.linalg.LinAlgError):
+        orc.train()
+    n_ref = len(orc.hyperparams["noise"])
+    k = n_done - 5
+    print("float engine froze after %d iterations, the oracle after %d; noise history rel. diff over %d rows %.2e" % (
+        n_done, n_ref, k, np.abs(np.asarray(rec.hyperparams["noise"][:k], dtype=np.float64)
+                                 / np.asarray(orc.hyperparams["noise"][:k]) - 1).max() if k > 0 else -1))
+    assert abs((n_ref - n_done) - 29 * np.log(2.0)) <= 8, (n_done, n_ref)
+    assert k >= 1
+    assert_allclose(np.asarray(rec.hyperparams["noise"][:k], dtype=np.float64), orc.hyperparams["noise"][:k], rtol=2e-2)
+    assert_allclose(np.asarray(rec.hyperparams["lengthscale"][:k], dtype=np.float64), orc.hyperparams["lengthscale"][:k],
+                    rtol=2e-2)
+    rec._mstruct.jitter = 1e-3
+    mean, sd = rec.predict()
+    assert np.isfinite(mean).all() and np.isfinite(sd).all()
+
+
 def _large_fit(gpim, N, T, precision, seed=0):
     """T Adam iterations of gpimhip_fit_exact in the large-N regime on a fresh handle; (history, losses, final u)."""
     from gpim_amd import _lib
@@ -397,14 +443,16 @@ def test_large_n_eager_regime_reproducible(gpim, precision):
         assert np.array_equal(x, y_)
 
 
-def test_graph_replay_equals_eager_launches(gpim, monkeypatch):
+@pytest.mark.parametrize("precision", ["double", "single"])
+def test_graph_replay_equals_eager_launches(gpim, monkeypatch, precision):
     """Mid-size N: one captured iteration replayed T times (default) against the same launches enqueued iteration by
     iteration (GPIMHIP_NO_GRAPH=1, what the profiling tools use) -- the same bits, exact GP at N = 700 (6 block columns:
-    the triangular inverse rides in the factorisation's launches in both)."""
+    the triangular inverse rides in the factorisation's launches in both; a single-precision handle inverts level by
+    level after its own step schedule)."""
     monkeypatch.delenv("GPIMHIP_NO_GRAPH", raising=False)
-    a = _large_fit(gpim, 700, 12, "double")
+    a = _large_fit(gpim, 700, 12, precision)
     monkeypatch.setenv("GPIMHIP_NO_GRAPH", "1")
-    b = _large_fit(gpim, 700, 12, "double")
+    b = _large_fit(gpim, 700, 12, precision)
     assert np.isfinite(a[0]).all() and np.isfinite(a[1]).all()
     for x, y_ in zip(a, b):
         assert np.array_equal(x, y_)

@@ -127,6 +127,25 @@ def test_precision_switch_and_guards(ensure_built):
     again = run_engine(_lib, Hb, X, y, spec, u, Xs)
     assert again[0] == ref[0] and np.array_equal(again[1], ref[1]) and np.array_equal(again[2], ref[2])
     assert Hb.lib.gpimhip_set_precision(Hb.h, 16) == _lib.E_BADARG
+    # a USED handle: a double fit at N = 1207 (ragged last block), then float -- the bits of a fresh float handle --
+    # then double again -- the bits of a fresh double handle
+    X, y, kp, spec, u, Xs = problem(1207, 2, "Matern52", seed=3)
+    Xd, yd, ud = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (X, y, u.numpy()))
+    m = spec.struct()
+    hist = torch.empty(3, spec.n_params, dtype=torch.float64, device="cuda")
+    Hc, Hs, Hd = _lib.Handle(), _lib.Handle(precision="single"), _lib.Handle()
+    _lib.check(Hc.lib.gpimhip_fit_exact(Hc.h, ctypes.byref(m), _lib.ptr(Xd), _lib.ptr(yd), len(X), _lib.ptr(ud), 0.1, 3,
+                                        _lib.ptr(hist), None))
+    assert torch.isfinite(hist).all()
+    for bits, fresh in ((32, Hs), (64, Hd)):
+        _lib.check(Hc.lib.gpimhip_set_precision(Hc.h, bits))
+        got = run_engine(_lib, Hc, X, y, spec, u, Xs)
+        want = run_engine(_lib, fresh, X, y, spec, u, Xs)
+        assert np.isfinite(got[0]) and np.isfinite(got[2]).all()
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w), bits
+    for H in (Ha, Hb, Hc, Hs, Hd):
+        H.close()
 
 
 def test_reconstructor_single_precision(ensure_built):
@@ -209,9 +228,28 @@ def test_slices_and_bo_in_single_precision(ensure_built, tmp_path):
     cube, _ = hyperspectral_cube(size=24, nspec=3, keep=0.4, seed=1)
     kw = dict(kernel="RBF", lengthscale=[[1., 1.], [12., 12.]], learning_rate=0.1, iterations=30)
     md, sd_ = gdist.reconstruct_slices(cube, axis=-1, batch=3, **kw)
-    ms, ss = gdist.reconstruct_slices(cube.astype(np.float32), axis=-1, batch=3, precision="single", **kw)
+    ms, ss, hyp = gdist.reconstruct_slices(cube.astype(np.float32), axis=-1, batch=3, precision="single",
+                                           return_hyperparams=True, **kw)
     assert np.isfinite(ms).all() and np.isfinite(ss).all()
-    # float32 initial draws differ from the float64 ones (as in the reference): same model family, nearby optimum
+    # every slice of the float lock-step batch is the stand-alone float reconstructor started from the same u (the batch
+    # draws its initial u in float64, the stand-alone precision='single' run in float32: same seed, other numbers), bit
+    # for bit: the posterior in the float32 the stand-alone run returns, the hyper-parameter history in double
+    cube32 = cube.astype(np.float32)
+    for k in range(cube.shape[-1]):
+        Rk = cube32[..., k]
+        rs = gpim.reconstructor(gpim.utils.get_sparse_grid(Rk), Rk, gpim.utils.get_full_grid(Rk), precision="single",
+                                verbose=0, **kw)
+        rs._u.copy_(rs._spec.draw_initial_u(torch.Generator().manual_seed(0)))
+        m1, s1, h1 = rs.run()
+        assert rs._handle.precision == "single" and m1.dtype == np.float32
+        hk = np.asarray(hyp[k], dtype=np.float64)                      # (T, [variance, l_0, l_1, noise])
+        np.testing.assert_array_equal(hk[:, 0], np.asarray(h1["variance"], dtype=np.float64))
+        np.testing.assert_array_equal(hk[:, 1:3], np.asarray(h1["lengthscale"], dtype=np.float64))
+        np.testing.assert_array_equal(hk[:, 3], np.asarray(h1["noise"], dtype=np.float64))
+        np.testing.assert_array_equal(ms[..., k].astype(np.float32), m1)
+        np.testing.assert_array_equal(ss[..., k].astype(np.float32), s1)
+    # on top of that: float32 initial draws differ from the float64 ones (as in the reference): same model family,
+    # nearby optimum
     assert np.abs(ms - md).max() < 0.2 and np.abs(ss - sd_).max() < 0.2
     func, Z = bo_test_problem()
     bo = gpim.boptimizer(gpim.utils.get_sparse_grid(Z), Z, gpim.utils.get_full_grid(Z), func, acquisition_function="ei",

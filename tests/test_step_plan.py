@@ -4,7 +4,12 @@ the HOST with small blocks: the plan is expressed in block indices, so an interp
 exactly the dependency structure the GPU launches have.  Launch semantics: every tile operation of a launch reads the
 state the launch started from (hosted workgroups run concurrently with each other and with the factorisation of the
 diagonal block), so a schedule that hands an operation to a launch too early, lets two operations of one launch write
-the same tile, or reads a tile another operation of the same launch writes, fails here.  No GPU involved."""
+the same tile, or reads a tile another operation of the same launch writes, fails here.  No GPU involved.
+
+The plan of single-precision handles (plan_updates_f32; executed by cholstep32.hip) is replayed the same way further
+down: it has a launch of its own before the first step of a panel (what of the panel's bulk update exceeds the cap on
+hosted tiles, from 88 block columns), applies panels two at a time from 160 block columns, and its launch after the
+panel solve updates every diagonal tile of the window."""
 import ctypes
 
 import numpy as np
@@ -133,3 +138,127 @@ def test_lists_are_dispatched_deepest_first(ensure_built, nb):
         r = rec[rec[:, 0] == launch]
         depth = r[:, 4] - r[:, 3]
         assert (np.diff(depth) <= 0).all(), int(launch)
+
+
+# ---- the plan of single-precision handles ------------------------------------------------------------------------------
+def plan_f32(nb, with_inverse):
+    """records (launch, ci, cj, kb0, kb1, kind) and the diagonal tiles per step; launch -(p + 1) = before panel p"""
+    from gpim_amd import _lib
+    lib = _lib.load()
+    ip = ctypes.POINTER(ctypes.c_int32)
+    n = ctypes.c_int64()
+    assert lib.gpimhip_step_plan_host_f32(nb, with_inverse, None, 0, ctypes.byref(n), None) == 0
+    buf = np.zeros((max(n.value, 1), 6), dtype=np.int32)
+    diag = np.full(nb, -1, dtype=np.int32)
+    assert lib.gpimhip_step_plan_host_f32(nb, with_inverse, buf.ctypes.data_as(ip), n.value, ctypes.byref(n),
+                                          diag.ctypes.data_as(ip)) == 0
+    return buf[:n.value], diag
+
+
+def launch_f32(ops, A, Tm, bs):
+    """One launch: every operation reads the state the launch started from; one matrix product over the whole k-range
+    per operation (at 1x1 blocks the dot product of two row slices)."""
+    nb = A.shape[0] // bs
+    A0, T0 = A.copy(), Tm.copy()
+    wrA, wrT = np.zeros((nb, nb), bool), np.zeros((nb, nb), bool)
+    rdA, rdT = np.zeros((nb, nb), bool), np.zeros((nb, nb), bool)
+    for ci, cj, k0, k1, kind in ops:
+        assert 0 <= k0 < k1 <= nb and 0 <= cj <= ci < nb and 0 <= kind <= 4
+        r, c, k = slice(ci * bs, (ci + 1) * bs), slice(cj * bs, (cj + 1) * bs), slice(k0 * bs, k1 * bs)
+        wr = wrT if kind in (1, 2) else wrA
+        assert not wr[ci, cj], "two operations of one launch write tile (%d, %d)" % (ci, cj)
+        wr[ci, cj] = True
+        rdA[ci, k0:k1] = True
+        if kind == 0:
+            rdA[cj, k0:k1] = True
+            A[r, c] = A0[r, c] - A0[r, k] @ A0[c, k].T
+        elif kind in (1, 2):
+            rdA[k0:k1, cj] = True
+            acc = A0[r, k] @ A0[k, c]
+            Tm[r, c] = acc if kind == 1 else T0[r, c] + acc
+        else:
+            rdT[k0:k1, cj] = True
+            acc = A0[r, k] @ T0[k, c]
+            A[r, c] = -acc if kind == 3 else A0[r, c] - acc
+    assert not (wrA & rdA).any() and not (wrT & rdT).any(), "an operation reads what another of the same launch writes"
+    return wrA
+
+
+def replay_f32(nb, bs, with_inverse, seed=0):
+    rng = np.random.default_rng(seed)
+    n = nb * bs
+    G = rng.standard_normal((n, n))
+    K = G @ G.T / n + 2.0 * np.eye(n)
+    A = np.tril(K).copy()
+    Tm = np.full((n, n), np.nan)
+    rec, diag = plan_f32(nb, with_inverse)
+    by_launch = {}
+    for r in rec.tolist():
+        by_launch.setdefault(r[0], []).append(tuple(r[1:]))
+    blk = lambda M, i, j: M[i * bs:(i + 1) * bs, j * bs:(j + 1) * bs]
+    W = 4
+    for j in range(nb):
+        if j % W == 0:
+            # the launch before the panel's first step: trailing updates with the columns of finished panels
+            ops = by_launch.get(-(j // W + 1), [])
+            for o in ops:
+                assert o[4] == 0 and o[3] <= j and o[1] >= j + W, o
+            launch_f32(ops, A, Tm, bs)
+        ops = by_launch.get(j, [])
+        for o in ops:
+            assert o[3] <= j or o[4] != 0, "a trailing update uses a block column that is not final"
+        written = launch_f32(ops, A, Tm, bs)
+        assert not written[j, j]
+        # the factorisation role of the same launch touches block (j, j) only
+        d = np.tril(blk(A, j, j))
+        Lj = np.linalg.cholesky(d + np.tril(d, -1).T)
+        Dinv = np.linalg.inv(Lj)
+        blk(A, j, j)[...] = Dinv if with_inverse else Lj
+        # F_j: the panel solve of column j
+        A[(j + 1) * bs:, j * bs:(j + 1) * bs] = A[(j + 1) * bs:, j * bs:(j + 1) * bs] @ Dinv.T
+        # D_j: the next diag[j] diagonal tiles receive column j
+        assert 0 <= diag[j] <= nb - 1 - j
+        for jj in range(j + 1, j + 1 + diag[j]):
+            blk(A, jj, jj)[...] -= blk(A, jj, j) @ blk(A, jj, j).T
+    assert min(by_launch, default=0) >= -((nb + W - 1) // W)          # launch -(p + 1): before panel p
+    for l in sorted(k for k in by_launch if k >= nb):
+        assert with_inverse
+        launch_f32(by_launch[l], A, Tm, bs)
+    Lref = np.linalg.cholesky(K)
+    want = np.linalg.inv(Lref) if with_inverse else Lref
+    got = np.tril(A)
+    scale = np.abs(want).max()
+    assert np.abs(got - want).max() < 1e-10 * scale, np.abs(got - want).max()
+    return rec, diag
+
+
+F32_CAP = {False: 128, True: 64}          # hosted bulk tiles per launch from 88 block columns / in pair mode (from 160)
+
+
+@pytest.mark.parametrize("with_inverse", [0, 1])
+@pytest.mark.parametrize("nb", [1, 2, 4, 5, 8, 9, 13, 33, 87, 88, 96, 159, 160, 161, 168])
+def test_float_plan_replay(ensure_built, nb, with_inverse):
+    """Block-column counts on both sides of every policy change of the float plan: everything hosted (< 88), capped fill
+    and a launch before the panel's first step (88 .. 159), panels applied two at a time (>= 160)."""
+    rec, diag = replay_f32(nb, 2 if nb <= 13 else 1, with_inverse, seed=nb)
+    W = 4
+    upd = rec[rec[:, 5] == 0]
+    before = rec[rec[:, 0] < 0]
+    # bulk tiles of a step launch: trailing updates of columns right of the window (the column update is column `launch`)
+    step_upd = upd[upd[:, 0] >= 0]
+    bulk = step_upd[step_upd[:, 2] != step_upd[:, 0]]
+    assert (bulk[:, 2] >= (bulk[:, 0] // W) * W + W).all()
+    per_launch = np.bincount(bulk[:, 0], minlength=nb) if len(bulk) else np.zeros(nb, int)
+    # the window's diagonal tiles, eagerly: everything up to the end of the next panel
+    for j in range(nb):
+        assert diag[j] == max(0, min(nb, min((j // W) * W + W, nb) + W) - (j + 1))
+    if nb < 88:
+        assert len(before) == 0
+    else:
+        assert per_launch.max() <= F32_CAP[nb >= 160]
+        assert len(before) > 0
+    depth = np.append(upd[:, 4] - upd[:, 3], 0)
+    if nb >= 160:
+        assert depth.max() == 2 * W                      # a deferred tile comes back 8 block columns deep
+    else:
+        assert depth.max() <= 2 * W - 1                  # (the column update's window of two panels)
