@@ -167,6 +167,19 @@ class Dense:
                                                   Xs.shape[0], ptr(z), z.shape[0], int(bool(noiseless)), float(jitter),
                                                   ptr(mean), ptr(var), ptr(out))
 
+    def sample_pathwise(self, o, Xs, P, idx, z, noiseless, jitter, mean, out):
+        """Pathwise posterior draws on the complete grid whose rows are Xs (csrc/sample.hip):
+        out[s] = mean + g_s - (K_GX + d P)(K + s I)^-1 (g_s[idx] + sqrt(s - d) z_e), g_s a prior draw through the grid's
+        reflection blocks.  P: the dict of gprutils.pathwise_grid, idx: its flat training indices on the device, z:
+        (S, M + N [+ M]).  The dense model only, as ``sample``."""
+        d = o._spec.dim
+        shape = (ctypes.c_int32 * d)(*[int(n) for n in P["shape"]])
+        twoc = (ctypes.c_double * 4)(*P["twoc"])
+        return o._handle.lib.gpimhip_sample_pathwise(*_head(o), ptr(Xs), shape, int(P["mask"]), twoc,
+                                                     ctypes.c_void_p(idx.data_ptr()), ptr(o._yd), o._Xd.shape[0], ptr(o._u),
+                                                     ptr(z), z.shape[0], int(bool(noiseless)), float(jitter), ptr(mean),
+                                                     ptr(out))
+
 
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""

@@ -145,20 +145,32 @@ def probability_of_improvement(gpmodel, X_full, X_sparse, **kwargs):
     return acq, (mean, sd)
 
 
-def thompson_on_device(gpmodel, Xf_d, generator=None, z=None):
-    """One noiseless joint draw over the device rows ``Xf_d`` plus the posterior (mean, sd) from the same library call:
-    device tensors (draw, mean, sd).  ``z``: the (1, M) standard normals, else drawn from ``generator`` (None: the global
-    device generator) by the rule documented at ``reconstructor.sample``."""
-    if z is None:
-        z = gpmodel._draw_z(1, Xf_d.shape[0], generator=generator)
-    draws, mean_d, var_d = gpmodel._sample_device(Xf_d, z, noiseless=True)
-    return draws[0], mean_d, var_d.sqrt()
+def thompson_on_device(gpmodel, Xf_d, generator=None, z=None, method='joint', grid_shape=None, n_draws=1):
+    """Noiseless joint draws over the device rows ``Xf_d`` plus the posterior (mean, sd): device tensors (draw, mean, sd),
+    ``draw`` of shape (M,) for one draw and (n_draws, M) for more.  ``z``: the standard normals, else drawn from
+    ``generator`` (None: the global device generator) by the rule documented at ``reconstructor.sample``.
+    ``method='joint'``: one library call gives all three.  ``method='pathwise'`` (``grid_shape``: the shape of the product
+    grid the rows fill): the draws by Matheron's rule, (mean, sd) from the ordinary prediction."""
+    if method == 'pathwise':
+        if z is None:
+            z = gpmodel._draw_z(n_draws, Xf_d.shape[0] + gpmodel._Xd.shape[0], generator=generator)
+        draws, _ = gpmodel._sample_pathwise_device(Xf_d, grid_shape, z, noiseless=True)
+        mean_d, sd_d = gpmodel._predict_device(Xf_d)
+    elif method == 'joint':
+        if z is None:
+            z = gpmodel._draw_z(n_draws, Xf_d.shape[0], generator=generator)
+        draws, mean_d, var_d = gpmodel._sample_device(Xf_d, z, noiseless=True)
+        sd_d = var_d.sqrt()
+    else:
+        raise ValueError("method must be 'joint' or 'pathwise'; got %r" % (method,))
+    return (draws[0] if draws.shape[0] == 1 else draws), mean_d, sd_d
 
 
 def thompson_sampling(gpmodel, X_full, **kwargs):
     """Thompson sampling: the acquisition map is ONE joint draw from the noiseless posterior over the grid, so its
     maximiser is distributed like the maximiser of the unknown function.  kwargs: ``seed`` (int), ``generator`` (a device
-    torch.Generator) or ``z`` ((1, M) standard normals); none of them: the global device generator.  ``gpmodel`` is a dense
+    torch.Generator) or ``z`` ((1, M) standard normals; (1, M + N) for the pathwise method); none of them: the global
+    device generator.  ``method``: 'joint' (default) or 'pathwise' (reconstructor.sample).  ``gpmodel`` is a dense
     double-precision ``gpim_amd.reconstructor``."""
     if not hasattr(gpmodel, "_sample_device"):
         raise NotImplementedError("thompson_sampling needs a gpim_amd.reconstructor (joint posterior draws)")
@@ -168,8 +180,9 @@ def thompson_sampling(gpmodel, X_full, **kwargs):
         gen = torch.Generator(gpmodel._dev).manual_seed(int(kwargs.get("seed")))
     if z is not None:
         z = gpmodel._to_device(z if torch.is_tensor(z) else np.asarray(z)).reshape(1, -1)
-    acq_d, mean_d, sd_d = thompson_on_device(gpmodel, Xf, generator=gen, z=z)
     shape = tuple(np.shape(X_full)[1:])
+    acq_d, mean_d, sd_d = thompson_on_device(gpmodel, Xf, generator=gen, z=z, method=kwargs.get("method", "joint"),
+                                             grid_shape=shape)
     gpmodel._last_acq = acq_d
     host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(gpmodel._np_out, copy=False)
     return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))

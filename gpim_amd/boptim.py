@@ -71,7 +71,12 @@ class boptimizer:
 
     gpim_amd extension: ``acquisition_function='ts'`` is Thompson sampling -- one noiseless joint draw of the
     posterior over the grid per step (reconstructor.sample), from a generator seeded with ``seed``; dense
-    double-precision surrogates only.  ``shard_candidates=True`` (with torch.distributed initialised, one process
+    double-precision surrogates only.  ``ts_method='pathwise'`` takes the draw by Matheron's rule instead
+    (reconstructor.sample(method='pathwise'): the grid must be a complete product grid with a symmetric axis that holds
+    every observation), with (mean, sd) from the ordinary prediction.  With ``batch_update=True``, ``ts_batch='draws'``
+    takes ``batch_size`` draws in one call and sends their maximisers -- a draw whose maximiser an earlier draw has taken
+    contributes its best remaining point -- through ``update_points``; the default ``ts_batch='topk'`` keeps the top
+    ``batch_size`` of a single draw.  ``shard_candidates=True`` (with torch.distributed initialised, one process
     per GPU) makes every rank sweep only its contiguous block of the test grid; an all-gather of
     each rank's top-``batch_size`` (value, index) pairs gives all ranks the same global ranking
     (SURVEY 8(e)).  Training stays replicated -- it is deterministic, so all ranks hold the same
@@ -120,7 +125,14 @@ class boptimizer:
         self.filename = kwargs.get("filename", "./boptim_results")
         self.shard_candidates = kwargs.get("shard_candidates", False)
         self._ts_generator = None
+        self.ts_method = kwargs.get("ts_method", "joint")
+        self.ts_batch = kwargs.get("ts_batch", "topk")
         if acquisition_function == 'ts':
+            # (ts_method and ts_batch belong to 'ts' alone: the other acquisition functions never read them)
+            if self.ts_method not in ("joint", "pathwise"):
+                raise ValueError("ts_method must be 'joint' or 'pathwise'; got %r" % (self.ts_method,))
+            if self.ts_batch not in ("topk", "draws"):
+                raise ValueError("ts_batch must be 'topk' or 'draws'; got %r" % (self.ts_batch,))
             if self.shard_candidates:
                 raise NotImplementedError("acquisition_function='ts' with shard_candidates=True: a joint draw does not "
                                           "split over candidate blocks")
@@ -235,6 +247,28 @@ class boptimizer:
         indices_list = np.stack(np.unravel_index(flat, tuple(grid_shape)), axis=-1).tolist()
         return vals_list, indices_list
 
+    def _rank_draws(self, draws_d, grid_shape):
+        """One point per draw of a (S, M) batch of Thompson draws: the draw's maximiser, or its best point that no earlier
+        draw has taken; S distinct points, ranked by their values (descending).  The mask multiplies every draw and NaNs
+        are treated as in ``_rank_device``: without a mask they rank first, with one they are dropped."""
+        S, M = draws_d.shape
+        A = draws_d if self.mask is None else self._device_mask(M)[None, :] * draws_d
+        nan_rank = float("inf") if self.mask is None else float("-inf")
+        R = torch.where(torch.isnan(A), torch.full_like(A, nan_rank), A)
+        k = int(min(S, M))                                  # the first k of a draw hold a point the k - 1 others left
+        order = torch.topk(R, k, dim=1)[1]
+        vals, order = torch.gather(A, 1, order).cpu().numpy(), order.cpu().numpy()
+        taken, picked = set(), []
+        for s in range(S):
+            for v, i in zip(vals[s], order[s]):
+                if int(i) not in taken and not (self.mask is not None and np.isnan(v)):
+                    taken.add(int(i))
+                    picked.append((float(v), int(i)))
+                    break
+        picked.sort(key=lambda t: (0, 0.0) if np.isnan(t[0]) else (1, -t[0]))
+        flat = np.array([i for _, i in picked], dtype=np.int64)
+        return [v for v, _ in picked], np.stack(np.unravel_index(flat, tuple(grid_shape)), axis=-1).tolist()
+
     def next_point(self):
         """Acquisition sweep + ranking (+ batch thinning) -- boptim.py:278-324."""
         if self.verbose:
@@ -269,11 +303,17 @@ class boptimizer:
             # draw stays on the device and is ranked like the built-in maps
             if self._Xfull_d is None:
                 self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
-            acq_d, mean_d, sd_d = acqfunc.thompson_on_device(sm, self._Xfull_d, generator=self._ts_generator)
             grid_shape = tuple(np.shape(self.X_full)[1:])
+            by_draws = self.batch_update and self.ts_batch == 'draws'
+            acq_d, mean_d, sd_d = acqfunc.thompson_on_device(sm, self._Xfull_d, generator=self._ts_generator,
+                                                             method=self.ts_method, grid_shape=grid_shape,
+                                                             n_draws=int(self.batch_size) if by_draws else 1)
             mean_d, sd_d = self._retain_maps(mean_d, sd_d)
             self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
-            vals_list, indices_list = self._rank_device(acq_d, grid_shape)
+            if by_draws:
+                vals_list, indices_list = self._rank_draws(acq_d.reshape(int(self.batch_size), -1), grid_shape)
+            else:
+                vals_list, indices_list = self._rank_device(acq_d, grid_shape)
         elif isinstance(af, types.FunctionType):
             acq, pred = af(sm, self.X_full, self.X_sparse)
             sm._last_acq = None

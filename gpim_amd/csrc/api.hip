@@ -2065,11 +2065,19 @@ struct SampleWs {
     double* J = nullptr; int64_t j_cap = 0;         // padded (N + M)^2 joint covariance -> its factor
     double* XX = nullptr; int64_t xx_cap = 0;       // [X; Xs]
     double* vec = nullptr; int64_t vec_cap = 0;     // t (order) | piece (512) | mean (M): forward substitution, draws
+    // pathwise draws (sample_pathwise_impl): a context per matrix order (a call factors at both, and a context that changes
+    // its order rebuilds its launch plan), one block of the prior, the training matrix, the vectors
+    gpimhip_ctx* subp = nullptr;                    // order M / 2^r: the reflection blocks of the grid, one after the other
+    gpimhip_ctx* subt = nullptr;                    // order N: K + (noise + jitter) I
+    double* Pb = nullptr; int64_t pb_cap = 0;
+    double* Kt = nullptr; int64_t kt_cap = 0;
+    double* pw = nullptr; int64_t pw_cap = 0;
 };
 static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
 static int64_t sample_bytes(const gpimhip_ctx* h) {
     const SampleWs* w = sws(h);
-    return w && w->sub ? w->sub->bytes : 0;
+    if (!w) return 0;
+    return (w->sub ? w->sub->bytes : 0) + (w->subp ? w->subp->bytes : 0) + (w->subt ? w->subt->bytes : 0);
 }
 static void sample_release(gpimhip_ctx* h) {
     SampleWs* w = sws(h);
@@ -2077,7 +2085,12 @@ static void sample_release(gpimhip_ctx* h) {
     dev_free(h, &w->J, w->j_cap);
     dev_free(h, &w->XX, w->xx_cap);
     dev_free(h, &w->vec, w->vec_cap);
+    dev_free(h, &w->Pb, w->pb_cap);
+    dev_free(h, &w->Kt, w->kt_cap);
+    dev_free(h, &w->pw, w->pw_cap);
     if (w->sub) gpimhip_destroy(w->sub);
+    if (w->subp) gpimhip_destroy(w->subp);
+    if (w->subt) gpimhip_destroy(w->subt);
     delete w;
     h->sample = nullptr;
 }
@@ -2142,7 +2155,159 @@ static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X
     return finish_and_check(sub);
 }
 
+// ------------------------------------------------------------------------------------------
+// pathwise draws: f_s = mean + g - (K_GX + d P)(K + s I)^-1 (g[idx] + sqrt(s - d) z_e), g a prior
+// draw on the complete grid G through its 2^r reflection blocks.  The prior factor is shared by the S draws of a call.
+// ------------------------------------------------------------------------------------------
+// a = (L L^T)^-1 r for one padded vector r (np): the panel-wise substitutions of the distributed model (distops.hip) against
+// the inverted diagonal blocks the step schedule left in sub->dinv.  zf, t: np; piece, work: 512.
+static int pathwise_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const double* r, double* a, double* zf, double* t,
+                          double* piece, double* work) {
+    const int64_t np = sub->np;
+    const int nb = (int)(np / NB);
+    HIP_TRY(hipMemsetAsync(t, 0, (size_t)np * sizeof(double), sub->stream));
+    for (int g0 = 0; g0 < nb; g0 += OUTER_W) {
+        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
+        const int64_t r0 = (int64_t)g0 * NB;
+        const double* P = L + r0 * ld + r0;
+        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, r + r0, t + r0, piece));
+        HIP_TRY(hipMemcpyAsync(zf + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
+        GP_TRY(launch_dist_rows_acc(sub, P + (int64_t)wd * ld, ld, np - r0 - wd, wd, piece, t + r0 + wd));
+    }
+    for (int g0 = ((nb - 1) / OUTER_W) * OUTER_W; g0 >= 0; g0 -= OUTER_W) {
+        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
+        const int64_t r0 = (int64_t)g0 * NB, below = np - r0 - wd;
+        const double* P = L + r0 * ld + r0;
+        if (below > 0) GP_TRY(launch_gemv_t(sub, P + (int64_t)wd * ld, ld, below, wd, a + r0 + wd, work, 0, 0, 0, 0));
+        else HIP_TRY(hipMemsetAsync(work, 0, (size_t)wd * sizeof(double), sub->stream));
+        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 1, zf + r0, work, piece));
+        HIP_TRY(hipMemcpyAsync(a + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
+    }
+    return GPIMHIP_OK;
+}
+
+static int pathwise_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order) {
+    if (!*sub) GP_TRY(gpimhip_create(sub, h->device, h->stream));
+    (*sub)->stream = h->stream;
+    (*sub)->nbatch = 1;
+    return ws_ensure_b(*sub, order, 1, 1, false);
+}
+
+// (stage timers of the model handle: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p, 2 gathers and the
+// basis change U^T, 1 the vector solves, 3 cross_apply_kernel with its epilogue)
+static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
+                                int64_t M, const int64_t* idx, const double* y, int64_t N, const double* u, const double* Z,
+                                int S, int noiseless, double jitter_s, double* mean_out, double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sample) h->sample = new SampleWs();
+    SampleWs* w = sws(h);
+    int64_t Nq = 1;
+    for (int k = 0; k < gd.d; ++k) Nq *= gd.f[k];
+    const int B = 1 << __builtin_popcount(gd.mask);
+    GP_TRY(pathwise_sub(h, &w->subp, Nq));
+    GP_TRY(pathwise_sub(h, &w->subt, N));
+    gpimhip_ctx *sp = w->subp, *st = w->subt;
+    const int64_t npq = sp->np, ldq = sp->ld, npt = st->np, ldt = st->ld;
+    const int64_t zw = M + N + (noiseless ? 0 : M), SB = (int64_t)S * B;
+    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
+    GP_TRY(dev_grow(h, &w->Kt, &w->kt_cap, npt * ldt));
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
+                  o_g = o_c + even(SB * Nq), o_xt = o_g + even((int64_t)S * M), o_r = o_xt + npt * GPIMHIP_MAX_DIM,
+                  o_al = o_r + (S + 1) * npt, o_zf = o_al + (S + 1) * npt, o_t = o_zf + npt, o_piece = o_t + npt,
+                  o_work = o_piece + 4 * NB, o_mws = o_work + 4 * NB, o_end = o_mws + npq;
+    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *Xt = w->pw + o_xt,
+           *R = w->pw + o_r, *Al = w->pw + o_al, *zf = w->pw + o_zf, *t = w->pw + o_t, *piece = w->pw + o_piece,
+           *work = w->pw + o_work, *mean_ws = w->pw + o_mws;
+    // one status word for both factorisations: the training context's
+    HIP_TRY(hipMemsetAsync(st->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(launch_theta(sp, m, u));
+    GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
+    GP_TRY(launch_theta(st, m, u));
+    {
+        StageTimer tm(h, 2);
+        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, idx, N, Xt));
+        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
+    }
+    // ---- the prior draw: block b of the grid's covariance, its factor, L_b z_b for every draw
+    sp->refl.mask = gd.mask;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
+    sp->refl.n_total = M;
+    sp->refl.var_count = 0;
+    sp->refl.pb_stride = 1;
+    sp->refl.nblocks_total = B;
+    sp->refl.raw = 0;
+    for (int b = 0; b < B; ++b) {
+        sp->refl.pb_off = b;
+        sp->refl.wts = wts + (int64_t)b * Nq;
+        {
+            StageTimer tm(h, 4);
+            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+        }
+        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, st->info)); }
+        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
+            StageTimer tm(h, 5);
+            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
+                                       nullptr, nullptr, C + (int64_t)b * S * Nq));
+        }
+    }
+    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, C, S, Nq, B, M, g)); }
+    // ---- the training side: K + (noise + jitter) I, its factor, alpha for the S draws and for y
+    {
+        StageTimer tm(h, 4);
+        GP_TRY(launch_kmat(st, m, Xt, N, nullptr, N, st->theta, 0.0, 1, w->Kt, ldt, npt, npt, 1, 1, 0, 0, 0));
+    }
+    { StageTimer tm(h, 0); GP_TRY(launch_potrf(st, w->Kt, npt, ldt, st->info)); }
+    {
+        StageTimer tm(h, 1);
+        GP_TRY(launch_pw_rhs(st, g, M, idx, N, Z, zw, S, y, st->theta, jitter_s, R, npt));
+        for (int v = 0; v <= S; ++v)
+            GP_TRY(pathwise_solve(st, w->Kt, ldt, R + (int64_t)v * npt, Al + (int64_t)v * npt, zf, t, piece, work));
+    }
+    {
+        StageTimer tm(h, 3);
+        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0))
+            GP_TRY(launch_pw_cross_apply(st, m, G, M, Xt, N, st->theta, Al, npt, S, s0, g, Z, zw, M + N, noiseless, mean_out,
+                                         samples_out));
+        GP_TRY(launch_pw_scatter(st, idx, N, M, Al, npt, S, jitter_s, samples_out));
+    }
+    return finish_and_check(st);
+}
+
 extern "C" {
+
+int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,
+                            const double* twoc, const int64_t* idx, const double* y, int64_t N, const double* u,
+                            const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
+                            double* samples_out) {
+    FP64_ONLY(h);
+    if (!h || !G || !shape || !twoc || !idx || !y || !u || !Z || !samples_out || N < 1 || S < 1 || S > 65535 || !(jitter > 0.0))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_sample_pathwise: not available in reflection mode (the dense double-precision engine only)");
+        return GPIMHIP_E_BADARG;
+    }
+    PwGrid gd;
+    gd.d = m->dim;
+    gd.mask = mask;
+    int64_t M = 1;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+        gd.n[k] = k < m->dim ? shape[k] : 1;
+        if (gd.n[k] < 1) return GPIMHIP_E_BADARG;
+        const bool refl = (mask >> k) & 1;
+        if (refl && (k >= m->dim || gd.n[k] < 2)) return GPIMHIP_E_BADARG;
+        gd.f[k] = refl ? (gd.n[k] + 1) / 2 : gd.n[k];
+        M *= gd.n[k];
+        if (M > ((int64_t)1 << 31)) return GPIMHIP_E_BADARG;
+    }
+    if (!mask || (mask >> m->dim)) {
+        gpim_set_error("gpimhip_sample_pathwise: needs at least one reflected axis of the grid");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_pathwise_impl(h, m, gd, twoc, G, M, idx, y, N, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+}
 
 int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
                          const double* u, const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless,

@@ -7,6 +7,8 @@
 //   mean_i = L[N+i, :N] z        var_i = sum_k L22[i,k]^2 - d + noise        f_s,i = mean_i + L22[i, :i+1] z_s[:i+1]
 // sample_draws_kernel reads the trapezoid once per group of up to eight draws and produces all three.
 #include "sample.hpp"
+#include "kfun.hpp"
+#include "refl.hpp"
 
 __global__ void sample_diag_kernel(double* __restrict__ J, int64_t ld, int64_t n_train, int64_t n_test,
                                    const ThetaDev* __restrict__ th, int noiseless, double jitter_s) {
@@ -180,6 +182,272 @@ int launch_sample_draws(gpimhip_ctx* h, const double* L, int64_t ld, int64_t N, 
     else if (rem == 2) SD_LAUNCH(2);
     else SD_LAUNCH(1);
 #undef SD_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ==========================================================================================
+// Pathwise draws (gpimhip_sample_pathwise): a prior draw on the complete grid G through its
+// reflection blocks, then one mean-type update against the training factor.  api.hip: sample_pathwise_impl.
+// ==========================================================================================
+// multi-index of a row-major linear index over the extents ext[0 .. d)
+__device__ __forceinline__ void pw_unravel(int64_t p, const int* ext, int d, int* ix) {
+#pragma unroll
+    for (int k = GPIMHIP_MAX_DIM - 1; k >= 0; --k) {
+        if (k < d) {
+            ix[k] = (int)(p % ext[k]);
+            p /= ext[k];
+        } else {
+            ix[k] = 0;
+        }
+    }
+}
+__device__ __forceinline__ int64_t pw_ravel(const int* ix, const int* ext, int d) {
+    int64_t p = 0;
+#pragma unroll
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k)
+        if (k < d) p = p * ext[k] + ix[k];
+    return p;
+}
+// the reflected axes (bit k) on whose mirror plane the point of the fundamental domain lies (axes of odd length)
+__device__ __forceinline__ int pw_planes(const PwGrid& gd, const int* ix) {
+    int pl = 0;
+#pragma unroll
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k)
+        if (k < gd.d && ((gd.mask >> k) & 1) && (gd.n[k] & 1) && ix[k] == gd.n[k] / 2) pl |= 1 << k;
+    return pl;
+}
+
+__global__ __launch_bounds__(256) void pw_setup_kernel(PwGrid gd, const double* __restrict__ G, int64_t M, int64_t Nq, int B,
+                                                       double* __restrict__ Xq, double* __restrict__ wts,
+                                                       const int64_t* __restrict__ idx, int64_t N, double* __restrict__ Xt) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < Nq) {
+        int ix[GPIMHIP_MAX_DIM];
+        pw_unravel(p, gd.f, gd.d, ix);
+        const int64_t flat = pw_ravel(ix, gd.n, gd.d);
+        for (int k = 0; k < gd.d; ++k) Xq[p * gd.d + k] = G[flat * gd.d + k];
+        const int pl = pw_planes(gd, ix), cnt = __popc(pl);
+        const double w = ldexp((cnt & 1) ? 0.70710678118654752440 : 1.0, -(cnt >> 1));
+        for (int b = 0; b < B; ++b) wts[(int64_t)b * Nq + p] = (refl_sign_dims(gd.mask, b) & pl) ? 0.0 : w;
+    }
+    if (p < N) {
+        int64_t ii = idx[p];
+        ii = ii < 0 ? 0 : (ii >= M ? M - 1 : ii);
+        for (int k = 0; k < gd.d; ++k) Xt[p * gd.d + k] = G[ii * gd.d + k];
+    }
+}
+int launch_pw_setup(gpimhip_ctx* h, PwGrid gd, const double* G, int64_t M, int64_t Nq, int B, double* Xq, double* wts,
+                    const int64_t* idx, int64_t N, double* Xt) {
+    const int64_t n = Nq > N ? Nq : N;
+    hipLaunchKernelGGL(pw_setup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, gd, G, M, Nq, B, Xq, wts, idx,
+                       N, Xt);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+__global__ __launch_bounds__(256) void pw_gather_z_kernel(PwGrid gd, const double* __restrict__ Z, int64_t zw, int S, int64_t Nq,
+                                                          double* __restrict__ Zg) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y, b = blockIdx.z;
+    if (p >= Nq) return;
+    int ix[GPIMHIP_MAX_DIM];
+    pw_unravel(p, gd.f, gd.d, ix);
+    const int sg = refl_sign_dims(gd.mask, b);
+    double v = 0.0;
+    if (!(sg & pw_planes(gd, ix))) {
+#pragma unroll
+        for (int k = 0; k < GPIMHIP_MAX_DIM; ++k)
+            if ((sg >> k) & 1) ix[k] = gd.n[k] - 1 - ix[k];
+        v = Z[(int64_t)s * zw + pw_ravel(ix, gd.n, gd.d)];
+    }
+    Zg[((int64_t)b * S + s) * Nq + p] = v;
+}
+int launch_pw_gather_z(gpimhip_ctx* h, PwGrid gd, const double* Z, int64_t zw, int S, int64_t Nq, int B, double* Zg) {
+    hipLaunchKernelGGL(pw_gather_z_kernel, dim3((unsigned)((Nq + 255) / 256), S, B), dim3(256), 0, h->stream, gd, Z, zw, S, Nq, Zg);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+__global__ __launch_bounds__(256) void pw_basis_t_kernel(PwGrid gd, const double* __restrict__ C, int S, int64_t Nq, int B,
+                                                         int64_t M, double rsqrt_b, double* __restrict__ g) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (i >= M) return;
+    int ix[GPIMHIP_MAX_DIM];
+    pw_unravel(i, gd.n, gd.d, ix);
+    int gam = 0;                                            // the reflection that takes the representative to the point
+#pragma unroll
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k)
+        if (k < gd.d && ((gd.mask >> k) & 1) && ix[k] > (gd.n[k] - 1) / 2) {
+            gam |= 1 << k;
+            ix[k] = gd.n[k] - 1 - ix[k];
+        }
+    const int pl = pw_planes(gd, ix), cnt = __popc(pl);
+    const int64_t p = pw_ravel(ix, gd.f, gd.d);
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const int sg = refl_sign_dims(gd.mask, b);
+        if (sg & pl) continue;
+        const double c = C[((int64_t)b * S + s) * Nq + p];
+        acc += (__popc(sg & gam) & 1) ? -c : c;
+    }
+    g[(int64_t)s * M + i] = acc * (ldexp((cnt & 1) ? 1.41421356237309504880 : 1.0, cnt >> 1) * rsqrt_b);
+}
+int launch_pw_basis_t(gpimhip_ctx* h, PwGrid gd, const double* C, int S, int64_t Nq, int B, int64_t M, double* g) {
+    hipLaunchKernelGGL(pw_basis_t_kernel, dim3((unsigned)((M + 255) / 256), S), dim3(256), 0, h->stream, gd, C, S, Nq, B, M,
+                       1.0 / sqrt((double)B), g);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+__global__ __launch_bounds__(256) void pw_rhs_kernel(const double* __restrict__ g, int64_t M, const int64_t* __restrict__ idx,
+                                                     int64_t N, const double* __restrict__ Z, int64_t zw, int S,
+                                                     const double* __restrict__ y, const ThetaDev* __restrict__ th,
+                                                     double jitter_s, double* __restrict__ R, int64_t npt) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (j >= npt) return;
+    double v = 0.0;
+    if (j < N) {
+        if (s < S) {
+            const int64_t ii = idx[j];
+            const double e = th->diag_add - jitter_s;
+            v = ((ii >= 0 && ii < M) ? g[(int64_t)s * M + ii] : 0.0) + sqrt(e > 0.0 ? e : 0.0) * Z[(int64_t)s * zw + M + j];
+        } else {
+            v = y[j];
+        }
+    }
+    R[(int64_t)s * npt + j] = v;
+}
+int launch_pw_rhs(gpimhip_ctx* h, const double* g, int64_t M, const int64_t* idx, int64_t N, const double* Z, int64_t zw, int S,
+                  const double* y, const ThetaDev* theta, double jitter_s, double* R, int64_t npt) {
+    hipLaunchKernelGGL(pw_rhs_kernel, dim3((unsigned)((npt + 255) / 256), S + 1), dim3(256), 0, h->stream, g, M, idx, N, Z, zw, S,
+                       y, theta, jitter_s, R, npt);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+__global__ void pw_set_diag_kernel(ThetaDev* th, double v) { th->diag_add = v; }
+int launch_pw_set_diag(gpimhip_ctx* h, ThetaDev* theta, double v) {
+    hipLaunchKernelGGL(pw_set_diag_kernel, dim3(1), dim3(1), 0, h->stream, theta, v);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// cross_apply_kernel: K(G, X) applied to the solved right-hand sides without ever being written.  ALU-bound on the fp64
+// vector pipe (M N covariance evaluations of kfun.hpp, SG + 1 FMAs each).  One grid point per lane; the workgroup stages
+// CA_TJ training rows (scaled by the lengthscales) and the matching SG + 1 entries of Al in LDS once and every lane reads
+// them at the same address (a broadcast).  Each accumulator runs over j = 0 .. N-1 in order, by itself: a draw's bits do
+// not depend on S, on the group it falls into or on the other draws.  The last column is alpha_y: the posterior mean.
+// ------------------------------------------------------------------------------------------
+#define CA_TJ 128
+
+template <int KIND, int SG>
+__global__ __launch_bounds__(256) void cross_apply_kernel(const double* __restrict__ G, int64_t M, const double* __restrict__ Xt,
+                                                          int64_t N, int d, const ThetaDev* __restrict__ th,
+                                                          const double* __restrict__ Al, int64_t npt, int S, int s0,
+                                                          const double* __restrict__ g, const double* __restrict__ Z, int64_t zw,
+                                                          int64_t zn_off, int noiseless, double* __restrict__ mean_out,
+                                                          double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double xs[CA_TJ][GPIMHIP_MAX_DIM];
+    __shared__ __attribute__((aligned(16))) double as[CA_TJ][SG + 1];
+    const int tid = threadIdx.x;
+    // (the few fields needed, not a private copy of the struct: that would live in scratch memory)
+    const double t_var = th->var, t_alpha = th->alpha, t_noise = th->noise;
+    const double ls0 = th->ls[0], ls1 = th->ls[1], ls2 = th->ls[2], ls3 = th->ls[3];
+    const double ls[GPIMHIP_MAX_DIM] = {ls0, ls1, ls2, ls3};
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    double a[GPIMHIP_MAX_DIM];
+#pragma unroll
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) a[k] = (k < d && i < M) ? G[i * d + k] / ls[k] : 0.0;
+    double acc[SG + 1];
+#pragma unroll
+    for (int c = 0; c <= SG; ++c) acc[c] = 0.0;
+    for (int64_t j0 = 0; j0 < N; j0 += CA_TJ) {
+        __syncthreads();                                    // the previous tile has been read
+        {
+            const int r = tid & (CA_TJ - 1), hf = tid >> 7;
+            const int64_t j = j0 + r;
+#pragma unroll
+            for (int k = hf * 2; k < hf * 2 + 2; ++k) xs[r][k] = (k < d && j < N) ? Xt[j * d + k] / ls[k] : 0.0;
+#pragma unroll
+            for (int c = 0; c <= SG; ++c) {
+                if ((c & 1) != hf) continue;                // the two halves of the workgroup take alternate columns
+                const int64_t row = c == SG ? S : s0 + c;
+                as[r][c] = (j < N && (c == SG || s0 + c < S)) ? Al[row * npt + j] : 0.0;
+            }
+        }
+        __syncthreads();
+        const int jn = (int)(N - j0 < CA_TJ ? N - j0 : CA_TJ);
+        for (int r = 0; r < jn; ++r) {
+            double r2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+                const double df = a[k] - xs[r][k];
+                r2 = fma(df, df, r2);
+            }
+            const double kv = kfun_value<KIND>(r2, t_alpha);
+#pragma unroll
+            for (int c = 0; c <= SG; ++c) acc[c] = fma(kv, as[r][c], acc[c]);
+        }
+    }
+    if (i >= M) return;
+    const double mu = t_var * acc[SG];
+    if (s0 == 0 && mean_out) mean_out[i] = mu;
+    const double sn = noiseless ? 0.0 : sqrt(t_noise);
+#pragma unroll
+    for (int c = 0; c < SG; ++c) {
+        if (s0 + c >= S) continue;
+        const int64_t o = (int64_t)(s0 + c) * M + i;
+        double v = mu + (g[o] - t_var * acc[c]);
+        if (!noiseless) v = fma(sn, Z[(int64_t)(s0 + c) * zw + zn_off + i], v);
+        out[o] = v;
+    }
+}
+
+int launch_pw_cross_apply(gpimhip_ctx* h, const gpimhip_model_t* m, const double* G, int64_t M, const double* Xt, int64_t N,
+                          const ThetaDev* theta, const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z,
+                          int64_t zw, int64_t zn_off, int noiseless, double* mean_out, double* out) {
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    const int rem = S - s0;
+#define CA_LAUNCH(KIND, SG)                                                                                              \
+    hipLaunchKernelGGL((cross_apply_kernel<KIND, SG>), grid, block, 0, h->stream, G, M, Xt, N, m->dim, theta, Al, npt, S, s0, g, \
+                       Z, zw, zn_off, noiseless, mean_out, out)
+#define CA_KIND(KIND)                    \
+    do {                                 \
+        if (rem >= 5) CA_LAUNCH(KIND, 8); \
+        else if (rem >= 3) CA_LAUNCH(KIND, 4); \
+        else if (rem == 2) CA_LAUNCH(KIND, 2); \
+        else CA_LAUNCH(KIND, 1);         \
+    } while (0)
+    switch (m->kernel) {
+        case GPIMHIP_KERNEL_RBF: CA_KIND(GPIMHIP_KERNEL_RBF); break;
+        case GPIMHIP_KERNEL_MATERN52: CA_KIND(GPIMHIP_KERNEL_MATERN52); break;
+        case GPIMHIP_KERNEL_RQ: CA_KIND(GPIMHIP_KERNEL_RQ); break;
+        default: gpim_set_error("unknown kernel kind"); return GPIMHIP_E_BADARG;
+    }
+#undef CA_KIND
+#undef CA_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+__global__ __launch_bounds__(256) void pw_scatter_kernel(const int64_t* __restrict__ idx, int64_t N, int64_t M,
+                                                         const double* __restrict__ Al, int64_t npt, double jitter_s,
+                                                         double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (j >= N) return;
+    const int64_t ii = idx[j];
+    if (ii < 0 || ii >= M) return;
+    out[(int64_t)s * M + ii] -= jitter_s * Al[(int64_t)s * npt + j];
+}
+int launch_pw_scatter(gpimhip_ctx* h, const int64_t* idx, int64_t N, int64_t M, const double* Al, int64_t npt, int S,
+                      double jitter_s, double* out) {
+    hipLaunchKernelGGL(pw_scatter_kernel, dim3((unsigned)((N + 255) / 256), S), dim3(256), 0, h->stream, idx, N, M, Al, npt,
+                       jitter_s, out);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

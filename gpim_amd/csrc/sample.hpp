@@ -12,3 +12,30 @@ int launch_sample_draws(gpimhip_ctx* h, const double* L, int64_t ld, int64_t N, 
                         int S, int s0, const ThetaDev* theta, int noiseless, double jitter_s, double* mean_ws,
                         double* mean_out, double* var_out, double* out);
 int sample_draw_group(int S);
+
+// ---- pathwise draws (gpimhip_sample_pathwise) ----
+// The complete product grid G of the draw: n[k] points along axis k (row-major, last axis fastest), mask = the reflected
+// axes, f[k] = the extent of the fundamental domain ((n[k] + 1) / 2 on a reflected axis, else n[k]).
+struct PwGrid { int d, mask; int n[GPIMHIP_MAX_DIM], f[GPIMHIP_MAX_DIM]; };
+// Xq (Nq x d): the fundamental domain's coordinates out of G; wts (B x Nq): 1 / sqrt(|stabiliser|), 0 where the point does
+// not exist in the block (ReflArgs::wts); Xt (N x d): the training rows G[idx]
+int launch_pw_setup(gpimhip_ctx* h, PwGrid gd, const double* G, int64_t M, int64_t Nq, int B, double* Xq, double* wts,
+                    const int64_t* idx, int64_t N, double* Xt);
+// Zg[b][s][p] = Z[s][flat(gamma_b p)] where p exists in block b (gamma_b: the reflection of the axes whose sign is -1 in
+// b -- a bijection of the present (b, p) onto G), else 0
+int launch_pw_gather_z(gpimhip_ctx* h, PwGrid gd, const double* Z, int64_t zw, int S, int64_t Nq, int B, double* Zg);
+// g = U^T c: g[s][gamma p] = B^-1/2 sqrt(|Stab_p|) sum_b chi_b(gamma) c[b][s][p], b ascending over the blocks that hold p
+int launch_pw_basis_t(gpimhip_ctx* h, PwGrid gd, const double* C, int S, int64_t Nq, int B, int64_t M, double* g);
+// R (S + 1 rows of npt): row s = g[s][idx] + sqrt(diag_add - jitter_s) Z[s][M + .], row S = y; zero padding
+int launch_pw_rhs(gpimhip_ctx* h, const double* g, int64_t M, const int64_t* idx, int64_t N, const double* Z, int64_t zw, int S,
+                  const double* y, const ThetaDev* theta, double jitter_s, double* R, int64_t npt);
+// theta->diag_add = v (the prior blocks carry the draw's jitter where training carries noise + jitter)
+int launch_pw_set_diag(gpimhip_ctx* h, ThetaDev* theta, double v);
+// One sweep of K(G, X) for the draws s0 .. s0 + group - 1 and the mean column (row S of Al):
+//   out[s][i] = mean_i + g[s][i] - sum_j k(G_i, X_j) Al[s][j]  (+ sqrt(noise) Z[s][zn_off + i] unless noiseless)
+int launch_pw_cross_apply(gpimhip_ctx* h, const gpimhip_model_t* m, const double* G, int64_t M, const double* Xt, int64_t N,
+                          const ThetaDev* theta, const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z,
+                          int64_t zw, int64_t zn_off, int noiseless, double* mean_out, double* out);
+// out[s][idx[j]] -= jitter_s Al[s][j]  (idx distinct)
+int launch_pw_scatter(gpimhip_ctx* h, const int64_t* idx, int64_t N, int64_t M, const double* Al, int64_t npt, int S,
+                      double jitter_s, double* out);

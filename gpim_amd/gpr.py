@@ -355,12 +355,62 @@ class reconstructor(_solvers.HostDriver):
         self._sample_bytes = max(need, getattr(self, "_sample_bytes", 0))
         return out, mean, var
 
+    def _pathwise_grid(self, Xrows_d, grid_shape):
+        """(dict of gprutils.pathwise_grid, its idx on the device) for the grid rows `Xrows_d` and the current training
+        rows; kept while both tensors stay the same objects."""
+        c = getattr(self, "_pw_cache", None)
+        if c is not None and c[0] is Xrows_d and c[1] is self._Xd and c[2] == tuple(grid_shape):
+            return c[3], c[4]
+        d = self._spec.dim
+        if len(grid_shape) != d or int(np.prod(grid_shape)) != Xrows_d.shape[0]:
+            raise NotImplementedError("pathwise draws need a product grid: %d test rows do not fill a grid of shape %s in "
+                                      "%d dimensions" % (Xrows_d.shape[0], tuple(grid_shape), d))
+        Xg = Xrows_d.cpu().numpy().T.reshape((d,) + tuple(grid_shape))
+        P = gprutils.pathwise_grid(Xg, self._Xd.cpu().numpy())
+        idx_d = torch.from_numpy(P["idx"]).to(self._dev)
+        self._pw_cache = (Xrows_d, self._Xd, tuple(grid_shape), P, idx_d)
+        return P, idx_d
+
+    def _sample_pathwise_device(self, Xrows_d, grid_shape, z_d, noiseless=False, jitter=None):
+        """(samples (S, M), mean (M)) device tensors of pathwise draws (Matheron's rule) on the
+        complete product grid of shape `grid_shape` whose (M, d) device rows are `Xrows_d`, with the standard normals
+        `z_d` (S, M + N) when noiseless, else (S, 2 M + N), split [z_p | z_e | z_n].  One library call: a prior draw through
+        the grid's reflection blocks plus one mean-type update against the factor of the training covariance."""
+        self._sample_supported()
+        self._check_data()
+        self._require_finite(Xrows_d)
+        M, N = Xrows_d.shape[0], self._Xd.shape[0]
+        W = M + N + (0 if noiseless else M)
+        if z_d.dim() != 2 or z_d.shape[1] != W:
+            raise ValueError("z must have shape (n_samples, %d) for method='pathwise' (M = %d grid points, N = %d "
+                             "observations%s); got %s" % (W, M, N, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
+        jitter = self._spec.jitter if jitter is None else float(jitter)
+        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
+        if not (0.0 < jitter <= s):
+            raise ValueError("pathwise draws need 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
+        P, idx_d = self._pathwise_grid(Xrows_d, grid_shape)
+        # the large allocations of the call: one (M / 2^r)^2 block of the prior and the N^2 training covariance
+        nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
+        need = 0
+        for order in (-(-nq // 128) * 128, -(-N // 128) * 128):
+            need += order * (order + (16 if order >= 1024 else 0)) * 8
+        if need > getattr(self, "_pathwise_bytes", 0):
+            free = torch.cuda.mem_get_info(self._dev)[0]
+            if need > free:
+                raise MemoryError("sample: a prior block of %d points and the covariance of %d training points need %.2f GiB "
+                                  "of device memory, %.2f GiB are free" % (nq, N, need / 2.0 ** 30, free / 2.0 ** 30))
+        out = torch.empty((z_d.shape[0], M), dtype=_F64, device=self._dev)
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        _lib.check(self._solver.sample_pathwise(self, Xrows_d, P, idx_d, z_d, noiseless, jitter, mean, out))
+        self._pathwise_bytes = max(need, getattr(self, "_pathwise_bytes", 0))
+        return out, mean
+
     def _draw_z(self, n_samples, M, seed=None, generator=None):
         if generator is None and seed is not None:
             generator = torch.Generator(self._dev).manual_seed(int(seed))
         return torch.randn((n_samples, M), dtype=_F64, device=self._dev, generator=generator)
 
-    def sample(self, n_samples=1, Xtest=None, noiseless=False, seed=None, z=None, jitter=None):
+    def sample(self, n_samples=1, Xtest=None, noiseless=False, seed=None, z=None, jitter=None, method='joint'):
         """Joint draws from the posterior on the test grid: ndarray of shape ``(n_samples, *fulldims)``, each slice one
         plausible reconstruction ``mean + chol(Sigma) z_s`` with ``Sigma`` the full posterior covariance of the grid plus
         ``((0 if noiseless else noise) + jitter) I``.  ``Xtest`` as in ``predict``; ``jitter`` defaults to the model's.
@@ -368,14 +418,37 @@ class reconstructor(_solvers.HostDriver):
         pure function of the model).  When absent it is drawn as
         ``torch.randn((n_samples, M), dtype=torch.float64, device=dev, generator=g)`` with ``g = torch.Generator(dev).manual_seed(seed)``
         (``seed is None``: the global device generator).  Dense double-precision models only; the test grid must be
-        finite."""
+        finite.
+
+        ``method='pathwise'`` (Matheron's rule) draws ``mean + g - (K_GX + d P)(K + s I)^-1 (g[idx] + sqrt(s - d) z_e)`` with
+        ``g`` a prior draw on the grid: two factorisations of order M / 2^r and N instead of one of order N + M, for a test
+        grid that is a complete product grid with a symmetric axis and holds every training row.  The same distribution up
+        to terms of the size of ``jitter`` (0 < jitter <= noise + the model's jitter); ``z`` then has shape
+        ``(n_samples, M + N)`` if noiseless, else ``(n_samples, 2 M + N)``, split ``[z_p | z_e | z_n]``, and is drawn by
+        the rule above at that width."""
+        if method not in ("joint", "pathwise"):
+            raise ValueError("method must be 'joint' or 'pathwise'; got %r" % (method,))
         self._sample_supported()
         if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
             # (refused before it replaces the stored test grid)
             raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+        if method == "pathwise" and Xtest is not None:
+            # a grid the method cannot take (not a product grid, no symmetric axis, a training row off it), like any other
+            # refused argument, leaves the stored test grid as it was (the dense solver keeps no grid state of its own)
+            kept = (self.Xtest, self._Xtest_d, self.fulldims)
+            try:
+                return self._sample_host(n_samples, Xtest, noiseless, seed, z, jitter, method)
+            except Exception:
+                self.Xtest, self._Xtest_d, self.fulldims = kept
+                raise
+        return self._sample_host(n_samples, Xtest, noiseless, seed, z, jitter, method)
+
+    def _sample_host(self, n_samples, Xtest, noiseless, seed, z, jitter, method):
         self._resolve_test_grid(Xtest)
         Xs = self._Xtest_d
         M = Xs.shape[0]
+        if method == "pathwise":
+            M = M + self._Xd.shape[0] + (0 if noiseless else M)       # the width of z; the draws are (n_samples, grid)
         if z is None:
             z_d = self._draw_z(int(n_samples), M, seed)
         else:
@@ -383,7 +456,10 @@ class reconstructor(_solvers.HostDriver):
             if z_d.dim() != 2 or z_d.shape != (int(n_samples), M):
                 raise ValueError("z must have shape (n_samples, %d) = (%d, %d); got %s"
                                  % (M, int(n_samples), M, tuple(z_d.shape)))
-        out, _, _ = self._sample_device(Xs, z_d, noiseless, jitter)
+        if method == "pathwise":
+            out, _ = self._sample_pathwise_device(Xs, tuple(self.fulldims), z_d, noiseless, jitter)
+        else:
+            out, _, _ = self._sample_device(Xs, z_d, noiseless, jitter)
         return out.cpu().numpy().reshape((z_d.shape[0],) + tuple(self.fulldims)).astype(self._np_out, copy=False)
 
     def run(self, **kwargs):

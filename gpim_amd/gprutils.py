@@ -296,3 +296,58 @@ def border_flops(N, M, r):
     (DESIGN.md section 11): (F_border, F_dense) = (N^3 / 4^r + N^2 M / 2^r + N M^2 + M^3, (N - M)^3)."""
     N, M = float(N), float(M)
     return N ** 3 / 4.0 ** r + N * N * M / 2.0 ** r + N * M * M + M ** 3, (N - M) ** 3
+
+
+def pathwise_grid(Xgrid, Xrows):
+    """What a pathwise posterior draw needs from its test grid and its training rows (gpim_amd extension: reconstructor.
+    sample(method='pathwise')).
+
+    Xgrid (d, n_1, ..., n_d): the test grid, a complete product grid (what ``get_full_grid`` returns) with at least one axis
+    whose coordinates are symmetric about their centre; Xrows (N, d): the training rows, each of which must coincide exactly
+    with a grid point.  Returns a dict: axes (the d coordinate vectors), shape (n_1, ..., n_d), mask (bit k: axis k is
+    reflected), twoc (first + last coordinate per axis, 4 entries), dims (the reflected axes), idx (int64, N): the flat
+    (row-major) grid index of every training row.
+    Raises NotImplementedError, naming the reason, when the grid is not a product grid, when it has no symmetric axis, when
+    a training row is not on it or when two training rows are the same grid point."""
+    Xgrid = np.asarray(Xgrid, dtype=np.float64)
+    Xrows = np.asarray(Xrows, dtype=np.float64)
+    d = Xgrid.shape[0]
+    if Xgrid.ndim != d + 1:
+        raise NotImplementedError("pathwise draws need a product grid: coordinates of shape (d, n_1, ..., n_d), got %s"
+                                  % (Xgrid.shape,))
+    axes = []
+    for i in range(d):
+        c = np.moveaxis(Xgrid[i], i, 0).reshape(Xgrid.shape[1 + i], -1)[:, 0].copy()
+        shape = [1] * d
+        shape[i] = -1
+        if not np.array_equal(Xgrid[i], np.broadcast_to(c.reshape(shape), Xgrid.shape[1:])):
+            raise NotImplementedError("pathwise draws need a product grid: coordinate %d does not vary along axis %d only"
+                                      % (i, i))
+        if len(np.unique(c)) != len(c):
+            raise NotImplementedError("pathwise draws need a product grid: axis %d repeats a coordinate" % i)
+        axes.append(c)
+    mask, twoc, dims = 0, [0.0] * 4, []
+    for k, c in enumerate(axes):         # the rule of reflection_blocks
+        if len(c) >= 2 and np.allclose(c + c[::-1], c[0] + c[-1], rtol=0, atol=1e-12 * max(1.0, abs(c[-1]), abs(c[0]))):
+            mask |= 1 << k
+            twoc[k] = float(c[0] + c[-1])
+            dims.append(k)
+    if not dims:
+        raise NotImplementedError("pathwise draws need a grid with at least one axis that is symmetric about its centre "
+                                  "(no symmetric axis: the prior has no reflection blocks)")
+    if Xrows.ndim != 2 or Xrows.shape[1] != d:
+        raise NotImplementedError("pathwise draws need training rows of shape (N, %d), got %s" % (d, Xrows.shape))
+    sub = []
+    for k, c in enumerate(axes):
+        order = np.argsort(c, kind="stable")
+        pos = np.clip(np.searchsorted(c[order], Xrows[:, k]), 0, len(c) - 1)
+        hit = order[pos]
+        off = np.flatnonzero(c[hit] != Xrows[:, k])
+        if len(off):
+            raise NotImplementedError("pathwise draws need every training row on the test grid: row %d is not on it "
+                                      "(coordinate %d = %r)" % (off[0], k, Xrows[off[0], k]))
+        sub.append(hit)
+    idx = np.ravel_multi_index(tuple(sub), Xgrid.shape[1:]).astype(np.int64)
+    if len(np.unique(idx)) != len(idx):
+        raise NotImplementedError("pathwise draws need distinct training rows: two of them are the same grid point")
+    return {"axes": axes, "shape": tuple(Xgrid.shape[1:]), "mask": mask, "twoc": twoc, "dims": dims, "idx": idx}

@@ -166,6 +166,32 @@ int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m,
                          double* mean_out, double* var_out,
                          double* samples_out);
 
+/* S pathwise draws from the posterior on a complete product grid G (Matheron's rule):
+ *   g = U^T blockdiag_b(chol(K_b + d I)) z_p        a prior draw on G through its 2^r reflection blocks, ~ N(0, K_GG + d I)
+ *   r = g[idx] + sqrt(s - d) z_e                    s = s_n^2 + the model's jitter, d = `jitter` below, 0 < d <= s
+ *   draw = mean + g - (K_GX + d P)(K + s I)^-1 r  (+ s_n z_n unless noiseless),   mean = K_GX (K + s I)^-1 y
+ * Two factorisations, of order M / 2^r (2^r times, through one buffer) and of order N, instead of one of order N + M.
+ *   G        M x d coordinates of the grid, row-major over `shape` (device)
+ *   shape    d grid extents (host), their product M <= 2^31
+ *   mask     bit k: axis k is symmetric about its centre and reflected (at least one); twoc: 4 doubles (host), first + last
+ *            coordinate of each reflected axis
+ *   idx      N DISTINCT flat indices into G, each IN RANGE [0, M) (device, int64): the training rows are G[idx].  Neither
+ *            property is checked on the device: an index out of range is clamped where the training rows are gathered and
+ *            skipped elsewhere, a repeated one races in the scatter -- the result is then meaningless, no error is reported
+ *   Z        S x (M + N [+ M]) standard normals (device), row s = [z_p | z_e | z_n]; z_n only unless noiseless.  z_p is
+ *            indexed by the grid point: row p of block b takes z_p[flat(gamma_b p)], gamma_b the reflection of the axes
+ *            whose sign is -1 in b
+ *   mean_out M doubles or NULL (the posterior mean of gpimhip_predict_exact);  samples_out  S x M
+ * Matrices and vectors belong to this entry point (grow-only, counted by gpimhip_workspace_bytes).  Double-precision handles
+ * outside reflection mode only; NULL arguments, S < 1, S > 65535 or jitter <= 0 -> GPIMHIP_E_BADARG (d <= s is the caller's
+ * to check: s lives on the device).  Synchronises once, at the end (to report NOT_PD of a prior block or of K + s I). */
+int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m,
+                            const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                            const int64_t* idx, const double* y, int64_t N, const double* u,
+                            const double* Z, int32_t S,
+                            int32_t noiseless, double jitter,
+                            double* mean_out, double* samples_out);
+
 /* Batched forms: B independent problems with the SAME N (and the same model description), advanced in
  * lock-step by every launch (grid.y = problem index) -- B spectral slices of a cube share each
  * latency-bound step of the blocked factorisation instead of paying for it B times.
@@ -554,6 +580,8 @@ int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, i
  *        5 = spectral-mixture gradient contraction (its tile launch and the record sum).
  * gpimhip_sample_exact: 4 = build of the joint covariance, 0 = its factorisation, 1 = the forward substitution z = L11^-1 y,
  *        5 = the draws kernel (one interval per sweep of the trapezoid).
+ * gpimhip_sample_pathwise: 4 = covariance builds (2^r prior blocks, K), 0 = their factorisations, 5 = the sweeps L_b z_p,
+ *        2 = gathers and the basis change U^T, 1 = the vector solves, 3 = cross_apply_kernel and its epilogue.
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
