@@ -180,6 +180,21 @@ class Dense:
                                                      ptr(z), z.shape[0], int(bool(noiseless)), float(jitter), ptr(mean),
                                                      ptr(out))
 
+    def sample_blocks(self, o, Xs, P, z, noiseless, jitter, mean, out):
+        """Pathwise draws for observations on every point of the complete grid whose rows are Xs, block by block in the
+        grid's reflection basis (csrc/sample.hip).  P: the dict of gprutils.pathwise_grid plus idx_d,
+        the flat grid index of every training row on the device (None: the rows are in grid order); z: (S, 2 M [+ M]).
+        The entry needs the grid, y and u only, so ``Kron`` and ``Reflection`` models on a complete grid inherit it."""
+        d = o._spec.dim
+        shape = (ctypes.c_int32 * d)(*[int(n) for n in P["shape"]])
+        twoc = (ctypes.c_double * 4)(*P["twoc"])
+        y = o._yd
+        if P["idx_d"] is not None:
+            y = torch.empty_like(o._yd)
+            y[P["idx_d"]] = o._yd
+        return o._handle.lib.gpimhip_sample_blocks(*_head(o), ptr(Xs), shape, int(P["mask"]), twoc, ptr(y), ptr(o._u), ptr(z),
+                                                   z.shape[0], int(bool(noiseless)), float(jitter), ptr(mean), ptr(out))
+
 
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""

@@ -2275,7 +2275,163 @@ static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid
     return finish_and_check(st);
 }
 
+// ------------------------------------------------------------------------------------------
+// draws on a fully observed grid: every step of the recipe above in the reflection basis, block by
+// block -- no product with K_GX and no matrix of order N.  Pb holds chol(K_b + d I) until the prior draws c_b exist, then
+// K_b + s I and its factor.
+// ------------------------------------------------------------------------------------------
+// A = (L L^T)^-1 R for ncols (1 .. 8) padded columns, column c at + c * cs: pathwise_solve for a group, the panel and the
+// rows below it read once (distops.hip).  Zf: the forward results (columns of cs); t: ncols x np running products;
+// part: gemv_t_multi_chunks(np) x 8 x 512.
+static int blocks_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const double* R, double* A, double* Zf, int64_t cs,
+                        int ncols, double* t, double* part) {
+    const int64_t np = sub->np;
+    const int nb = (int)(np / NB);
+    const int64_t pcs = 4 * NB, pchs = (int64_t)multi_group_width(ncols) * pcs;
+    HIP_TRY(hipMemsetAsync(t, 0, (size_t)(ncols * np) * sizeof(double), sub->stream));
+    for (int g0 = 0; g0 < nb; g0 += OUTER_W) {
+        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
+        const int64_t r0 = (int64_t)g0 * NB;
+        const double* P = L + r0 * ld + r0;
+        GP_TRY(launch_dist_trsv_multi(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, R + r0, cs, t + r0, np, 0, 1, ncols,
+                                      Zf + r0, cs));
+        GP_TRY(launch_dist_rows_acc_multi(sub, P + (int64_t)wd * ld, ld, np - r0 - wd, wd, Zf + r0, cs, ncols, t + r0 + wd, np));
+    }
+    for (int g0 = ((nb - 1) / OUTER_W) * OUTER_W; g0 >= 0; g0 -= OUTER_W) {
+        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
+        const int64_t r0 = (int64_t)g0 * NB, below = np - r0 - wd;
+        const double* P = L + r0 * ld + r0;
+        GP_TRY(launch_gemv_t_multi(sub, P + (int64_t)wd * ld, ld, below, wd, A + r0 + wd, cs, ncols, part));
+        GP_TRY(launch_dist_trsv_multi(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 1, Zf + r0, cs, part, pcs, pchs,
+                                      below > 0 ? gemv_t_multi_chunks(below) : 0, ncols, A + r0, cs));
+    }
+    return GPIMHIP_OK;
+}
+
+// (stage timers of the model handle, as sample_pathwise_impl: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p,
+// 2 gathers and both basis changes, 1 the multi-column solves, 3 right-hand sides, combination and epilogue)
+static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
+                              int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
+                              double jitter_s, double* mean_out, double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sample) h->sample = new SampleWs();
+    SampleWs* w = sws(h);
+    int64_t Nq = 1;
+    for (int k = 0; k < gd.d; ++k) Nq *= gd.f[k];
+    const int B = 1 << __builtin_popcount(gd.mask);
+    GP_TRY(pathwise_sub(h, &w->subp, Nq));
+    gpimhip_ctx* sp = w->subp;
+    const int64_t npq = sp->np, ldq = sp->ld;
+    const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
+    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
+                  o_e = o_c + even(SB * Nq), o_cc = o_e + B * S1 * npq, o_g = o_cc + even(B * S1 * Nq), o_r = o_g + even(S1 * M),
+                  o_zf = o_r + S1 * npq, o_al = o_zf + S1 * npq, o_t = o_al + S1 * npq,
+                  o_part = o_t + 8 * npq, o_mws = o_part + (int64_t)gemv_t_multi_chunks(npq) * 8 * 4 * NB, o_end = o_mws + npq;
+    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *E = w->pw + o_e, *Cc = w->pw + o_cc,
+           *g = w->pw + o_g, *R = w->pw + o_r, *Zf = w->pw + o_zf, *Al = w->pw + o_al, *t = w->pw + o_t, *part = w->pw + o_part,
+           *mean_ws = w->pw + o_mws;
+    // one status word for the 2 B factorisations
+    HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(launch_theta(sp, m, u));
+    {
+        StageTimer tm(h, 2);
+        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
+        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
+        GP_TRY(launch_pw_basis_fwd(sp, gd, Z, zw, M, y, S, Nq, npq, B, E));
+    }
+    sp->refl.mask = gd.mask;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
+    sp->refl.n_total = M;
+    sp->refl.var_count = 0;
+    sp->refl.pb_stride = 1;
+    sp->refl.nblocks_total = B;
+    sp->refl.raw = 0;
+    for (int b = 0; b < B; ++b) {
+        sp->refl.pb_off = b;
+        sp->refl.wts = wts + (int64_t)b * Nq;
+        double *Cb = C + (int64_t)b * S * Nq, *Eb = E + (int64_t)b * S1 * npq;
+        // ---- the prior draw c_b = chol(K_b + d I) z_b
+        GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
+        {
+            StageTimer tm(h, 4);
+            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+        }
+        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
+        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
+            StageTimer tm(h, 5);
+            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
+                                       nullptr, nullptr, Cb));
+        }
+        // ---- T_b = K_b + s I in the same buffer, its factor, [alpha_b | alpha_y,b] for the S draws and y
+        GP_TRY(launch_pw_reset_diag(sp, sp->theta, m->jitter));
+        {
+            StageTimer tm(h, 4);
+            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+        }
+        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
+        { StageTimer tm(h, 3); GP_TRY(launch_pw_blocks_rhs(sp, Cb, Eb, S, Nq, npq, sp->theta, jitter_s, R)); }
+        {
+            StageTimer tm(h, 1);
+            for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
+                const int64_t off = (int64_t)c0 * npq;
+                GP_TRY(blocks_solve(sp, w->Pb, ldq, R + off, Al + off, Zf + off, npq, sample_draw_group(S + 1 - c0), t, part));
+            }
+        }
+        {
+            StageTimer tm(h, 3);
+            GP_TRY(launch_pw_blocks_combine(sp, Al, Eb, S, Nq, npq, sp->theta, jitter_s, Cc + (int64_t)b * S1 * Nq));
+        }
+    }
+    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, Cc, S + 1, Nq, B, M, g)); }
+    {
+        StageTimer tm(h, 3);
+        GP_TRY(launch_pw_blocks_out(sp, g, M, S, Z, zw, 2 * M, noiseless, sp->theta, mean_out, samples_out));
+    }
+    return finish_and_check(sp);
+}
+
+// the grid of a pathwise or block draw from its shape and reflected axes; M = its points (0: a bad argument)
+static int64_t pw_grid(const gpimhip_model_t* m, const int32_t* shape, int32_t mask, PwGrid* gd) {
+    gd->d = m->dim;
+    gd->mask = mask;
+    int64_t M = 1;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+        gd->n[k] = k < m->dim ? shape[k] : 1;
+        if (gd->n[k] < 1) return 0;
+        const bool refl = (mask >> k) & 1;
+        if (refl && (k >= m->dim || gd->n[k] < 2)) return 0;
+        gd->f[k] = refl ? (gd->n[k] + 1) / 2 : gd->n[k];
+        M *= gd->n[k];
+        if (M > ((int64_t)1 << 31)) return 0;
+    }
+    return M;
+}
+
 extern "C" {
+
+int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,
+                          const double* twoc, const double* y, const double* u, const double* Z, int32_t S, int32_t noiseless,
+                          double jitter, double* mean_out, double* samples_out) {
+    FP64_ONLY(h);
+    if (!h || !G || !shape || !twoc || !y || !u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_sample_blocks: not available in reflection mode (the dense double-precision engine only)");
+        return GPIMHIP_E_BADARG;
+    }
+    PwGrid gd;
+    const int64_t M = pw_grid(m, shape, mask, &gd);
+    if (M < 1) return GPIMHIP_E_BADARG;
+    if (!mask || (mask >> m->dim)) {
+        gpim_set_error("gpimhip_sample_blocks: needs at least one reflected axis of the grid");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_blocks_impl(h, m, gd, twoc, G, M, y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+}
 
 int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,
                             const double* twoc, const int64_t* idx, const double* y, int64_t N, const double* u,
@@ -2290,18 +2446,8 @@ int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const do
         return GPIMHIP_E_BADARG;
     }
     PwGrid gd;
-    gd.d = m->dim;
-    gd.mask = mask;
-    int64_t M = 1;
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
-        gd.n[k] = k < m->dim ? shape[k] : 1;
-        if (gd.n[k] < 1) return GPIMHIP_E_BADARG;
-        const bool refl = (mask >> k) & 1;
-        if (refl && (k >= m->dim || gd.n[k] < 2)) return GPIMHIP_E_BADARG;
-        gd.f[k] = refl ? (gd.n[k] + 1) / 2 : gd.n[k];
-        M *= gd.n[k];
-        if (M > ((int64_t)1 << 31)) return GPIMHIP_E_BADARG;
-    }
+    const int64_t M = pw_grid(m, shape, mask, &gd);
+    if (M < 1) return GPIMHIP_E_BADARG;
     if (!mask || (mask >> m->dim)) {
         gpim_set_error("gpimhip_sample_pathwise: needs at least one reflected axis of the grid");
         return GPIMHIP_E_BADARG;

@@ -296,6 +296,19 @@ int launch_colsumsq_acc(gpimhip_ctx* h, const double* W, int64_t ldw, int rows, 
 int launch_dist_trsv(gpimhip_ctx* h, const double* P, int64_t ld, const double* D, int nblk, int backward, const double* r0,
                      const double* r1, double* out);
 int launch_dist_rows_acc(gpimhip_ctx* h, const double* A, int64_t ld, int64_t rows, int w, const double* x, double* acc);
+// the same for a group of ncols (1 .. 8) columns per sweep, column c at its pointer + c * (its column stride): api.hip
+// blocks_solve.  r1: nch chunks (stride r1_chs) of partial sums, added in their order and taken off r0; part of
+// launch_gemv_t_multi: gemv_t_multi_chunks(nrows) x multi_group_width(ncols) x 512 doubles.
+#define GEMV_T_MULTI_RC 1024
+static inline int gemv_t_multi_chunks(int64_t nrows) { return (int)((nrows + GEMV_T_MULTI_RC - 1) / GEMV_T_MULTI_RC); }
+int multi_group_width(int ncols);
+int launch_dist_trsv_multi(gpimhip_ctx* h, const double* P, int64_t ld, const double* D, int nblk, int backward, const double* r0,
+                           int64_t r0_cs, const double* r1, int64_t r1_cs, int64_t r1_chs, int nch, int ncols, double* out,
+                           int64_t out_cs);
+int launch_dist_rows_acc_multi(gpimhip_ctx* h, const double* A, int64_t ld, int64_t rows, int w, const double* x, int64_t x_cs,
+                               int ncols, double* acc, int64_t acc_cs);
+int launch_gemv_t_multi(gpimhip_ctx* h, const double* A, int64_t ld, int64_t nrows, int w, const double* x, int64_t x_cs,
+                        int ncols, double* part);
 // engine.hip
 int launch_theta_raw(gpimhip_ctx* h, const gpimhip_model_t* m, const double* raw);
 int launch_kmat(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Z,

@@ -451,3 +451,128 @@ int launch_pw_scatter(gpimhip_ctx* h, const int64_t* idx, int64_t N, int64_t M, 
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
+
+// ==========================================================================================
+// Draws on a fully observed grid through its reflection blocks alone (gpimhip_sample_blocks): with
+// observations on every grid point the whole recipe above is block diagonal in the basis U.  api.hip: sample_blocks_impl.
+// ==========================================================================================
+// E[b][s][p] = (U v_s)_{b,p}: v_s = Z[s][ze_off + .] for s < S, y for s == S -- the transpose of pw_basis_t_kernel.  The
+// distinct mirror images of p are added in the order of the reflections; rows of points absent from block b and the padding
+// p >= Nq (rows of npq) are zero.
+__global__ __launch_bounds__(256) void pw_basis_fwd_kernel(PwGrid gd, const double* __restrict__ Z, int64_t zw, int64_t ze_off,
+                                                           const double* __restrict__ y, int S, int64_t Nq, int64_t npq, int B,
+                                                           double rsqrt_b, double* __restrict__ E) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y, b = blockIdx.z;
+    if (p >= npq) return;
+    double v = 0.0;
+    if (p < Nq) {
+        int ix[GPIMHIP_MAX_DIM];
+        pw_unravel(p, gd.f, gd.d, ix);
+        const int pl = pw_planes(gd, ix), cnt = __popc(pl), sb = refl_sign_dims(gd.mask, b);
+        if (!(sb & pl)) {
+            const double* src = s < S ? Z + (int64_t)s * zw + ze_off : y;
+            double acc = 0.0;
+            for (int g = 0; g < B; ++g) {
+                const int sg = refl_sign_dims(gd.mask, g);
+                if (sg & pl) continue;                      // the image of a point on the mirror plane is the point itself
+                int jx[GPIMHIP_MAX_DIM];
+#pragma unroll
+                for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) jx[k] = ((sg >> k) & 1) ? gd.n[k] - 1 - ix[k] : ix[k];
+                const double c = src[pw_ravel(jx, gd.n, gd.d)];
+                acc += (__popc(sb & sg) & 1) ? -c : c;
+            }
+            v = acc * (ldexp((cnt & 1) ? 1.41421356237309504880 : 1.0, cnt >> 1) * rsqrt_b);
+        }
+    }
+    E[((int64_t)b * (S + 1) + s) * npq + p] = v;
+}
+int launch_pw_basis_fwd(gpimhip_ctx* h, PwGrid gd, const double* Z, int64_t zw, int64_t ze_off, const double* y, int S,
+                        int64_t Nq, int64_t npq, int B, double* E) {
+    hipLaunchKernelGGL(pw_basis_fwd_kernel, dim3((unsigned)((npq + 255) / 256), S + 1, B), dim3(256), 0, h->stream, gd, Z, zw,
+                       ze_off, y, S, Nq, npq, B, 1.0 / sqrt((double)B), E);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// theta->diag_add = jitter_m + noise: what launch_theta left there before launch_pw_set_diag (theta.hpp: theta_from_u)
+__global__ void pw_reset_diag_kernel(ThetaDev* th, double jitter_m) { th->diag_add = jitter_m + th->noise; }
+int launch_pw_reset_diag(gpimhip_ctx* h, ThetaDev* theta, double jitter_m) {
+    hipLaunchKernelGGL(pw_reset_diag_kernel, dim3(1), dim3(1), 0, h->stream, theta, jitter_m);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// one block's right-hand sides R (S + 1 rows of npq): row s = c[s] + sqrt(diag_add - jitter_s) e[s], row S = ys (Eb: the
+// block's S + 1 rows of pw_basis_fwd_kernel; Cb: its S rows of Nq prior draws); theta->diag_add = s
+__global__ __launch_bounds__(256) void pw_blocks_rhs_kernel(const double* __restrict__ Cb, const double* __restrict__ Eb, int S,
+                                                            int64_t Nq, int64_t npq, const ThetaDev* __restrict__ th,
+                                                            double jitter_s, double* __restrict__ R) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (p >= npq) return;
+    double v = Eb[(int64_t)s * npq + p];
+    if (s < S) {
+        const double e = th->diag_add - jitter_s;
+        v = (p < Nq ? Cb[(int64_t)s * Nq + p] : 0.0) + sqrt(e > 0.0 ? e : 0.0) * v;
+    }
+    R[(int64_t)s * npq + p] = v;
+}
+int launch_pw_blocks_rhs(gpimhip_ctx* h, const double* Cb, const double* Eb, int S, int64_t Nq, int64_t npq,
+                         const ThetaDev* theta, double jitter_s, double* R) {
+    hipLaunchKernelGGL(pw_blocks_rhs_kernel, dim3((unsigned)((npq + 255) / 256), S + 1), dim3(256), 0, h->stream, Cb, Eb, S, Nq,
+                       npq, theta, jitter_s, R);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// one block's rows of the result in the basis U (S + 1 rows of Nq): with mean = ys - s alpha_y,
+// row v < S = mean + ((s - d) alpha_v - sqrt(s - d) e_v), row S = mean
+__global__ __launch_bounds__(256) void pw_blocks_combine_kernel(const double* __restrict__ Al, const double* __restrict__ Eb,
+                                                                int S, int64_t Nq, int64_t npq,
+                                                                const ThetaDev* __restrict__ th, double jitter_s,
+                                                                double* __restrict__ Cc) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int v = blockIdx.y;
+    if (p >= Nq) return;
+    const double sd = th->diag_add;
+    const double mean = Eb[(int64_t)S * npq + p] - sd * Al[(int64_t)S * npq + p];
+    double o = mean;
+    if (v < S) {
+        double e = sd - jitter_s;
+        e = e > 0.0 ? e : 0.0;
+        o = mean + (e * Al[(int64_t)v * npq + p] - sqrt(e) * Eb[(int64_t)v * npq + p]);
+    }
+    Cc[(int64_t)v * Nq + p] = o;
+}
+int launch_pw_blocks_combine(gpimhip_ctx* h, const double* Al, const double* Eb, int S, int64_t Nq, int64_t npq,
+                             const ThetaDev* theta, double jitter_s, double* Cc) {
+    hipLaunchKernelGGL(pw_blocks_combine_kernel, dim3((unsigned)((Nq + 255) / 256), S + 1), dim3(256), 0, h->stream, Al, Eb, S,
+                       Nq, npq, theta, jitter_s, Cc);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// out[s] = g[s] (+ sqrt(noise) Z[s][zn_off + .] unless noiseless) for s < S; mean_out = g[S]
+__global__ __launch_bounds__(256) void pw_blocks_out_kernel(const double* __restrict__ g, int64_t M, int S,
+                                                            const double* __restrict__ Z, int64_t zw, int64_t zn_off,
+                                                            int noiseless, const ThetaDev* __restrict__ th,
+                                                            double* __restrict__ mean_out, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (i >= M) return;
+    double v = g[(int64_t)s * M + i];
+    if (s == S) {
+        if (mean_out) mean_out[i] = v;
+        return;
+    }
+    if (!noiseless) v = fma(sqrt(th->noise), Z[(int64_t)s * zw + zn_off + i], v);
+    out[(int64_t)s * M + i] = v;
+}
+int launch_pw_blocks_out(gpimhip_ctx* h, const double* g, int64_t M, int S, const double* Z, int64_t zw, int64_t zn_off,
+                         int noiseless, const ThetaDev* theta, double* mean_out, double* out) {
+    hipLaunchKernelGGL(pw_blocks_out_kernel, dim3((unsigned)((M + 255) / 256), S + 1), dim3(256), 0, h->stream, g, M, S, Z, zw,
+                       zn_off, noiseless, theta, mean_out, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}

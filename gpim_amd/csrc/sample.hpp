@@ -39,3 +39,21 @@ int launch_pw_cross_apply(gpimhip_ctx* h, const gpimhip_model_t* m, const double
 // out[s][idx[j]] -= jitter_s Al[s][j]  (idx distinct)
 int launch_pw_scatter(gpimhip_ctx* h, const int64_t* idx, int64_t N, int64_t M, const double* Al, int64_t npt, int S,
                       double jitter_s, double* out);
+
+// ---- draws on a fully observed grid through the reflection blocks (gpimhip_sample_blocks) ----
+// E[b][s][p] (S + 1 rows of npq per block) = (U v_s)_{b,p}, v_s = Z[s][ze_off + .] (s < S) or y (s == S); zero in the rows of
+// points absent from block b and in the padding
+int launch_pw_basis_fwd(gpimhip_ctx* h, PwGrid gd, const double* Z, int64_t zw, int64_t ze_off, const double* y, int S,
+                        int64_t Nq, int64_t npq, int B, double* E);
+// theta->diag_add = jitter_m + noise(theta) again, after launch_pw_set_diag
+int launch_pw_reset_diag(gpimhip_ctx* h, ThetaDev* theta, double jitter_m);
+// R (S + 1 rows of npq) of one block: row s = Cb[s] + sqrt(diag_add - jitter_s) Eb[s], row S = Eb[S]
+int launch_pw_blocks_rhs(gpimhip_ctx* h, const double* Cb, const double* Eb, int S, int64_t Nq, int64_t npq,
+                         const ThetaDev* theta, double jitter_s, double* R);
+// Cc (S + 1 rows of Nq) of one block from its solutions Al (rows of npq): mean = Eb[S] - diag_add Al[S];
+// row v < S = mean + ((diag_add - jitter_s) Al[v] - sqrt(diag_add - jitter_s) Eb[v]), row S = mean
+int launch_pw_blocks_combine(gpimhip_ctx* h, const double* Al, const double* Eb, int S, int64_t Nq, int64_t npq,
+                             const ThetaDev* theta, double jitter_s, double* Cc);
+// out[s] = g[s] (+ sqrt(noise) Z[s][zn_off + .] unless noiseless), mean_out (optional) = g[S]
+int launch_pw_blocks_out(gpimhip_ctx* h, const double* g, int64_t M, int S, const double* Z, int64_t zw, int64_t zn_off,
+                         int noiseless, const ThetaDev* theta, double* mean_out, double* out);

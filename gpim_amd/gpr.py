@@ -405,6 +405,66 @@ class reconstructor(_solvers.HostDriver):
         self._pathwise_bytes = max(need, getattr(self, "_pathwise_bytes", 0))
         return out, mean
 
+    _BLOCKS_ENGINE = "method='blocks' draws on a fully observed grid in double precision (%s)"
+
+    def _sample_blocks_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
+        """sample(method='blocks'): every argument is checked before anything is stored, so a refused call leaves the model
+        and its stored test grid as they were."""
+        if self.do_sparse:
+            raise NotImplementedError(self._BLOCKS_ENGINE % "sparse=True")
+        if self.precision == "single":
+            raise NotImplementedError(self._BLOCKS_ENGINE % "precision='single'")
+        if self.do_border:
+            raise NotImplementedError(self._BLOCKS_ENGINE % "the image has missing points: method='blocks' needs a fully "
+                                      "observed grid")
+        self._check_data()
+        if Xtest is not None:
+            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+            Xs, shape = self._to_device(gprutils.prepare_test_data(Xtest, precision=self.precision)), tuple(Xtest.shape[1:])
+        elif self._Xtest_d is not None:
+            Xs, shape = self._Xtest_d, tuple(self.fulldims)
+        else:
+            Xs, shape = self._Xd, tuple(self.fulldims)
+        self._require_finite(Xs)
+        P, idx_d = self._pathwise_grid(Xs, shape)
+        M, N = Xs.shape[0], self._Xd.shape[0]
+        if N != M:          # (distinct rows, each on the grid: fewer of them than grid points)
+            first = int(np.setdiff1d(np.arange(M), P["idx"])[0])
+            raise NotImplementedError("method='blocks' needs an observation on every point of the test grid (the test grid "
+                                      "must be the training grid): grid point %s has none (%d observations, %d grid points)"
+                                      % (tuple(int(v) for v in np.unravel_index(first, shape)), N, M))
+        W = 2 * M + (0 if noiseless else M)
+        S = int(n_samples)
+        if z is None:
+            z_d = self._draw_z(S, W, seed)
+        else:
+            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
+            if z_d.dim() != 2 or z_d.shape != (S, W):
+                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='blocks' (M = %d grid points%s); got %s"
+                                 % (W, S, W, M, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
+        jitter = self._spec.jitter if jitter is None else float(jitter)
+        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
+        if not (0.0 < jitter <= s):
+            raise ValueError("method='blocks' needs 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
+        # the large allocation of the call: one (M / 2^r)^2 reflection block, reused by all 2 x 2^r factorisations
+        nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
+        order = -(-nq // 128) * 128
+        need = order * (order + (16 if order >= 1024 else 0)) * 8
+        if need > getattr(self, "_blocks_bytes", 0):
+            free = torch.cuda.mem_get_info(self._dev)[0]
+            if need > free:
+                raise MemoryError("sample: a reflection block of %d points needs %.2f GiB of device memory, %.2f GiB are free"
+                                  % (nq, need / 2.0 ** 30, free / 2.0 ** 30))
+        if Xtest is not None:
+            self._resolve_test_grid(Xtest)
+        out = torch.empty((S, M), dtype=_F64, device=self._dev)
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        Pd = dict(P, idx_d=None if np.array_equal(P["idx"], np.arange(M)) else idx_d)
+        _lib.check(self._solver.sample_blocks(self, Xs, Pd, z_d, noiseless, jitter, mean, out))
+        self._blocks_bytes = max(need, getattr(self, "_blocks_bytes", 0))
+        return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
+
     def _draw_z(self, n_samples, M, seed=None, generator=None):
         if generator is None and seed is not None:
             generator = torch.Generator(self._dev).manual_seed(int(seed))
@@ -425,9 +485,18 @@ class reconstructor(_solvers.HostDriver):
         grid that is a complete product grid with a symmetric axis and holds every training row.  The same distribution up
         to terms of the size of ``jitter`` (0 < jitter <= noise + the model's jitter); ``z`` then has shape
         ``(n_samples, M + N)`` if noiseless, else ``(n_samples, 2 M + N)``, split ``[z_p | z_e | z_n]``, and is drawn by
-        the rule above at that width."""
-        if method not in ("joint", "pathwise"):
-            raise ValueError("method must be 'joint' or 'pathwise'; got %r" % (method,))
+        the rule above at that width.
+
+        ``method='blocks'``: the pathwise draw for a model whose observations fill its grid -- ``reconstructor(...,
+        structured=True)``, ``skreconstructor`` on a complete image or cube, or a dense double-precision model with an
+        observation on every grid point -- computed in the grid's reflection basis alone: 2 x 2^r factorisations of order
+        M / 2^r, no matrix of order M.  The test grid must be the training grid (``Xtest`` None, the
+        stored grid, or equal to it) with a symmetric axis; ``z`` has shape ``(n_samples, 2 M)`` if noiseless, else
+        ``(n_samples, 3 M)``, the layout of ``'pathwise'`` with N = M; 0 < jitter <= noise + the model's jitter."""
+        if method not in ("joint", "pathwise", "blocks"):
+            raise ValueError("method must be 'joint', 'pathwise' or 'blocks'; got %r" % (method,))
+        if method == "blocks":
+            return self._sample_blocks_host(n_samples, Xtest, noiseless, seed, z, jitter)
         self._sample_supported()
         if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
             # (refused before it replaces the stored test grid)

@@ -192,6 +192,28 @@ int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m,
                             int32_t noiseless, double jitter,
                             double* mean_out, double* samples_out);
 
+/* S pathwise draws on a FULLY OBSERVED product grid G -- an observation y on every grid point -- computed in the grid's
+ * reflection basis alone.  Per reflection block b, with e_b = (U z_e)_b and ys_b = (U y)_b:
+ *   c_b = chol(K_b + d I) z_b                          the prior draw of gpimhip_sample_pathwise
+ *   [alpha_b | alpha_y,b] = (K_b + s I)^-1 [c_b + sqrt(s - d) e_b | ys_b]
+ *   draw = U^T [ys_b - s alpha_y,b + (s - d) alpha_b - sqrt(s - d) e_b]  (+ s_n z_n unless noiseless)
+ * the draws of gpimhip_sample_pathwise with idx = 0 .. M-1 up to rounding, at 2 x 2^r factorisations of order M / 2^r through
+ * one buffer: no matrix of order M and no product with K_GX.
+ *   G, shape, mask, twoc, u, noiseless, jitter, mean_out, samples_out   as for gpimhip_sample_pathwise
+ *   y        M observations in the row-major order of the grid (device)
+ *   Z        S x (2 M [+ M]) standard normals (device), row s = [z_p | z_e | z_n] -- the layout of gpimhip_sample_pathwise
+ *            with N = M
+ * Matrices and vectors are those of gpimhip_sample_pathwise (grow-only, counted by gpimhip_workspace_bytes).
+ * Double-precision handles outside reflection mode only; NULL arguments, S < 1, S > 65534 or jitter <= 0 ->
+ * GPIMHIP_E_BADARG.  Synchronises once, at the end (to report NOT_PD of any of the 2 x 2^r factorisations, through one status
+ * word; the handle stays usable). */
+int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m,
+                          const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                          const double* y, const double* u,
+                          const double* Z, int32_t S,
+                          int32_t noiseless, double jitter,
+                          double* mean_out, double* samples_out);
+
 /* Batched forms: B independent problems with the SAME N (and the same model description), advanced in
  * lock-step by every launch (grid.y = problem index) -- B spectral slices of a cube share each
  * latency-bound step of the blocked factorisation instead of paying for it B times.
@@ -582,6 +604,8 @@ int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, i
  *        5 = the draws kernel (one interval per sweep of the trapezoid).
  * gpimhip_sample_pathwise: 4 = covariance builds (2^r prior blocks, K), 0 = their factorisations, 5 = the sweeps L_b z_p,
  *        2 = gathers and the basis change U^T, 1 = the vector solves, 3 = cross_apply_kernel and its epilogue.
+ * gpimhip_sample_blocks: 4 = covariance builds (2 x 2^r), 0 = their factorisations, 5 = the sweeps L_b z_p, 2 = gathers and the
+ *        basis changes U and U^T, 1 = the multi-column solves, 3 = right-hand sides, combination and epilogue.
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
