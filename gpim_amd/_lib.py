@@ -80,6 +80,10 @@ _PROTOS = {
                                              ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_double), c_dp, c_dp, c_dp,
                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
+    "gpimhip_sample_border": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, c_dp,
+                                             ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.c_int32, ctypes.POINTER(ctypes.c_double), c_dp, c_dp, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
     "gpimhip_fit_exact_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64,
                                                  c_dp, ctypes.c_int64, ctypes.c_int32, c_dp, ctypes.c_double,
                                                  ctypes.c_int32, c_dp, c_dp]),

@@ -195,6 +195,11 @@ class Dense:
         return o._handle.lib.gpimhip_sample_blocks(*_head(o), ptr(Xs), shape, int(P["mask"]), twoc, ptr(y), ptr(o._u), ptr(z),
                                                    z.shape[0], int(bool(noiseless)), float(jitter), ptr(mean), ptr(out))
 
+    def sample_border(self, o, *args):
+        """Draws through the bordered reflection blocks belong to the border solver (``Reflection(border=True)``)."""
+        raise NotImplementedError("method='border' draws through the bordered reflection blocks of an image with missing "
+                                  "points (the %s solver has none)" % type(self).__name__)
+
 
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""
@@ -302,6 +307,20 @@ class Reflection(Dense):
         mean[self.perm_d] = mean_p
         torch.index_select(var_p[:nq], 0, self.rep_d, out=var)
         return rc
+
+    def sample_border(self, o, Xs, P, miss_d, z, noiseless, jitter, mean, out):
+        """Pathwise draws on the completed grid whose rows are Xs for a model with missing points, through the state a
+        prediction of the bordered blocks leaves (csrc/sample.hip).  P: shape, mask and twoc of the
+        completed grid; miss_d: the flat grid indices of the missing points on the device (int64, the border's order);
+        z: (S, 2 M [+ M]), every part indexed by the grid point."""
+        if not self.border:
+            return Dense.sample_border(self, o)
+        d = o._spec.dim
+        shape = (ctypes.c_int32 * d)(*[int(n) for n in P["shape"]])
+        twoc = (ctypes.c_double * 4)(*P["twoc"])
+        return self._call(o, o._handle.lib.gpimhip_sample_border, ptr(Xs), shape, int(P["mask"]), twoc,
+                          ctypes.c_void_p(miss_d.data_ptr()), ptr(z), z.shape[0], int(bool(noiseless)), float(jitter), ptr(mean),
+                          ptr(out))
 
     def nll_grad(self, o, out):
         if not self.border:         # the dense model of the same data

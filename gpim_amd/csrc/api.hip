@@ -859,7 +859,7 @@ int gpimhip_timing_enable(gpimhip_handle h, int enable) {
 }
 
 int gpimhip_timing_read(gpimhip_handle h, int stage, double* total_ms, int64_t* count) {
-    if (!h || stage < 0 || stage > 5 || !total_ms || !count) return GPIMHIP_E_BADARG;
+    if (!h || stage < 0 || stage > 6 || !total_ms || !count) return GPIMHIP_E_BADARG;
     HIP_TRY(hipStreamSynchronize(h->stream));
     double tot = 0.0;
     for (auto& pr : h->ev[stage]) {
@@ -1032,9 +1032,10 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
     return GPIMHIP_OK;
 }
 
-static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
-                        int64_t N, int B, const double* u, const double* Xs, int64_t M, double* mean_out,
-                        double* var_out) {
+// The model's state at u, what a prediction and a draw through the border start from: theta, L^-1 (h->A), alpha and, with a
+// border, the blocks' inverses (h->B), S, L_S^-1, C_b, Y_b and the corrected alpha
+static int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
+                            int B, const double* u) {
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = B;
     GP_TRY(ws_ensure_padded(h, N));
@@ -1047,6 +1048,13 @@ static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
         GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np)));
         GP_TRY(border_iter(h, N, false));
     }
+    return GPIMHIP_OK;
+}
+
+static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
+                        int64_t N, int B, const double* u, const double* Xs, int64_t M, double* mean_out,
+                        double* var_out) {
+    GP_TRY(model_state_at_u(h, m, X, x_bs, y, N, B, u));
     GP_TRY(predict_cols(h, m, X, x_bs, N, B, Xs, M, mean_out, var_out));
     return finish_and_check(h);
 }
@@ -2393,6 +2401,128 @@ static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid g
     return finish_and_check(sp);
 }
 
+// ------------------------------------------------------------------------------------------
+// draws on a grid with missing points: the recipe of section 17 with the bordered blocks of the model
+// in place of a second factorisation per block.  With A = K_GG + s I on the completed grid, V = A^-1 P_m, S = P_m^T V:
+//   beta = A^-1 [r~ | y~],  w = S^-1 beta_m,  alpha~ = beta - V w      ((K_oo + s I)^-1 embedded: zero at the missing points)
+//   p = (s - d) alpha~ - sqrt(s - d) z_e at the observed points, g + w at the missing ones;  mean = y - s alpha~_y, -w_y
+// Everything A^-1, S^-1 and V need is what a prediction leaves: L_b^-1 in h->A, L_S^-1 in the border's sub->A, Y_b = C_b L_S^-T.
+// Beyond that state: one np x ld block (SampleWs::Pb, the prior factors one after the other) and vectors.
+// (stage timers of the model handle: 4 the prior's covariance builds, 0 factorisations with the inverses their launches
+// host, 5 the sweeps L_b z_p, 2 gathers and the basis changes, 1 the multi-column sweeps through L_b^-1 and what is left of
+// the triangular inverses, 6 those sweeps alone (intervals inside stage 1's), 3 right-hand sides, the border's vectors,
+// combination and epilogue; the model's covariance build, its K^-1 product and the products of border_iter are not timed,
+// as in a prediction)
+// ------------------------------------------------------------------------------------------
+static int sample_border_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* ys,
+                              int64_t Nq, int B, const double* u, PwGrid gd, const double* twoc, const double* G, int64_t M,
+                              const int64_t* miss, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
+                              double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sample) h->sample = new SampleWs();
+    SampleWs* w = sws(h);
+    GP_TRY(pathwise_sub(h, &w->subp, Nq));
+    gpimhip_ctx* sp = w->subp;
+    const int64_t npq = sp->np, ldq = sp->ld;
+    const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
+    const int Mm = bws(h)->M;
+    const int64_t mp = pad_to(Mm, NB);
+    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int pg = sample_draw_group(S + 1);           // the first group of columns is the largest
+    const int64_t n_part = std::max((int64_t)B * tri_bwd_chunks(npq) * pg * npq, (int64_t)tri_bwd_chunks(mp) * pg * mp);
+    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
+                  o_g = o_c + even(SB * Nq), o_mws = o_g + even((int64_t)S * M), o_r = o_mws + npq, o_zf = o_r + B * S1 * npq,
+                  o_cc = o_zf + B * S1 * npq, o_g2 = o_cc + even(B * S1 * Nq), o_tv = o_g2 + even(S1 * M), o_part = o_tv + 3 * S1 * mp,
+                  o_mi = o_part + n_part, o_end = o_mi + even(M) / 2;
+    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *mean_ws = w->pw + o_mws,
+           *R = w->pw + o_r, *Zf = w->pw + o_zf, *Cc = w->pw + o_cc, *g2 = w->pw + o_g2, *tv = w->pw + o_tv, *vv = tv + S1 * mp,
+           *wv = vv + S1 * mp, *part = w->pw + o_part;
+    int32_t* mi = (int32_t*)(w->pw + o_mi);
+    // ---- the prior draws c_b = chol(K_b + d I) z_b block by block through Pb (sample_blocks_impl), g = U^T c
+    HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(launch_theta(sp, m, u));
+    GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
+    {
+        StageTimer tm(h, 2);
+        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
+        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
+        GP_TRY(launch_bs_mark(sp, miss, Mm, M, mi));
+    }
+    sp->refl.mask = gd.mask;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
+    sp->refl.n_total = M;
+    sp->refl.var_count = 0;
+    sp->refl.pb_stride = 1;
+    sp->refl.nblocks_total = B;
+    sp->refl.raw = 0;
+    for (int b = 0; b < B; ++b) {
+        sp->refl.pb_off = b;
+        sp->refl.wts = wts + (int64_t)b * Nq;
+        {
+            StageTimer tm(h, 4);
+            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+        }
+        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
+        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
+            StageTimer tm(h, 5);
+            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
+                                       nullptr, nullptr, C + (int64_t)b * S * Nq));
+        }
+    }
+    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, C, S, Nq, B, M, g)); }
+    // ---- the model's state: L_b^-1, B_b^-1, S, L_S^-1, Y_b (every factorisation reports through h->info)
+    GP_TRY(model_state_at_u(h, m, X, x_bs, ys, Nq, B, u));
+    GP_TRY(launch_bs_merge_info(h, sp->info, h->info));
+    BorderWs* bw = bws(h);
+    const int64_t np = h->np, ld = h->ld;
+    if (np != npq || sp->stream != h->stream) {         // the vectors above are sized by the prior's context and indexed by the model's
+        gpim_set_error("gpimhip_sample_border: the prior's context and the model's workspace disagree on the padded block order "
+                       "or on the stream");
+        return GPIMHIP_E_BADARG;
+    }
+    const double *Ls = bw->sub->A;
+    const int64_t lds = bw->sub->ld;
+    // ---- right-hand sides in the blocks: [U r~ | ys]; what the sweeps leave untouched (padding rows) is zero
+    HIP_TRY(hipMemsetAsync(Zf, 0, (size_t)(B * S1 * np) * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(tv, 0, (size_t)(3 * S1 * mp) * sizeof(double), h->stream));
+    {
+        StageTimer tm(h, 3);
+        GP_TRY(launch_bs_rhs_fwd(h, gd, g, Z, zw, M, mi, ys, h->theta, jitter_s, S, Nq, np, B, R));
+    }
+    // ---- beta_b = L_b^-T (L_b^-1 R_b), a group of columns per pass over the triangles (beta overwrites R)
+    {
+        StageTimer tm(h, 1);
+        for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
+            const int nc = sample_draw_group(S + 1 - c0);
+            const int64_t off = (int64_t)c0 * np;
+            StageTimer ts(h, 6);                        // (the two sweeps alone: stage 1 also holds the rest of the inverses)
+            GP_TRY(launch_tri_fwd_multi(h, h->A, ld, np * ld, Nq, B, R + off, Zf + off, np, S1 * np, nc));
+            GP_TRY(launch_tri_bwd_multi(h, h->A, ld, np * ld, Nq, np, B, Zf + off, R + off, np, S1 * np, nc, part, pg));
+        }
+    }
+    // ---- the border: t = beta_m, v = L_S^-1 t, w = L_S^-T v, alpha~_b = beta_b - Y_b v
+    {
+        StageTimer tm(h, 3);
+        GP_TRY(launch_bs_t(h, R, np, B, (int)S1, bw->q, bw->coef, Mm, mp, tv));
+        for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
+            const int nc = sample_draw_group(S + 1 - c0);
+            const int64_t off = (int64_t)c0 * mp;
+            GP_TRY(launch_tri_fwd_multi(h, Ls, lds, 0, Mm, 1, tv + off, vv + off, mp, 0, nc));
+            GP_TRY(launch_tri_bwd_multi(h, Ls, lds, 0, Mm, mp, 1, vv + off, wv + off, mp, 0, nc, part, pg));
+            GP_TRY(launch_bs_yv(h, bw->Y, mp, np, Nq, B, (int)S1, vv, c0, nc, R));
+        }
+        GP_TRY(launch_bs_combine(h, R, ys, S, Nq, np, B, h->theta, jitter_s, Cc));
+    }
+    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(h, gd, Cc, S + 1, Nq, B, M, g2)); }
+    {
+        StageTimer tm(h, 3);
+        GP_TRY(launch_bs_out(h, g2, g, wv, mp, mi, M, S, Z, zw, noiseless, h->theta, jitter_s, mean_out, samples_out));
+    }
+    return finish_and_check(h);
+}
+
 // the grid of a pathwise or block draw from its shape and reflected axes; M = its points (0: a bad argument)
 static int64_t pw_grid(const gpimhip_model_t* m, const int32_t* shape, int32_t mask, PwGrid* gd) {
     gd->d = m->dim;
@@ -2431,6 +2561,44 @@ int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m, const doub
         return GPIMHIP_E_BADARG;
     }
     return sample_blocks_impl(h, m, gd, twoc, G, M, y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+}
+
+int gpimhip_sample_border(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
+                          int64_t N, int32_t B, const double* u, const double* G, const int32_t* shape, int32_t mask,
+                          const double* twoc, const int64_t* miss, const double* Z, int32_t S, int32_t noiseless, double jitter,
+                          double* mean_out, double* samples_out) {
+    FP64_ONLY(h);
+    if (!h || !X || !y || !u || !G || !shape || !twoc || !miss || !Z || !samples_out || N < 1 || B < 1 ||
+        B > (1 << GPIMHIP_MAX_DIM) || S < 1 || S > 65534 || !(jitter > 0.0))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (!h->refl.mask) {
+        gpim_set_error("gpimhip_sample_border: needs reflection mode (gpimhip_set_reflection) with a border (gpimhip_set_border)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (!border_on(h)) {
+        gpim_set_error("gpimhip_sample_border: no border is set (no missing points: gpimhip_sample_blocks draws on a fully "
+                       "observed grid)");
+        return GPIMHIP_E_BADARG;
+    }
+    // (BorderWs::T > 1 can only come from a batch of T 2^r problems: this entry sets one border up, whatever ran before)
+    if (mask > 0 && mask < (1 << GPIMHIP_MAX_DIM) && B > (1 << __builtin_popcount(mask)) && B % (1 << __builtin_popcount(mask)) == 0) {
+        gpim_set_error("gpimhip_sample_border: a multi-output border (B = T 2^r problems, one border per task) is not built: the "
+                       "entry takes the 2^r blocks of one model");
+        return GPIMHIP_E_BADARG;
+    }
+    PwGrid gd;
+    const int64_t M = pw_grid(m, shape, mask, &gd);
+    int64_t Nq = M < 1 ? 0 : 1;
+    for (int k = 0; k < GPIMHIP_MAX_DIM && M >= 1; ++k) Nq *= gd.f[k];
+    if (M < 1 || mask != h->refl.mask || (mask >> m->dim) || B != (1 << __builtin_popcount(mask)) || Nq != N ||
+        bws(h)->M >= M || h->refl.pb_stride != 1 || h->refl.raw) {
+        gpim_set_error("gpimhip_sample_border: the grid (shape, mask) does not describe the handle's reflection blocks (mask, "
+                       "B = 2^r, N = the points of the fundamental domain, fewer missing points than grid points, unsharded)");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_border_impl(h, m, X, x_stride, y, N, B, u, gd, twoc, G, M, miss, Z, S, noiseless ? 1 : 0, jitter, mean_out,
+                              samples_out);
 }
 
 int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,

@@ -183,7 +183,7 @@ struct gpimhip_ctx {
     DistPlan dplan;
     // optional stage timing (bench.py): HIP event pairs on the handle's stream
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[7];
     // Adam bias-correction table for the fused small-N trainer
     double* bc = nullptr;
     int64_t bc_cap = 0;

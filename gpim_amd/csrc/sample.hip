@@ -576,3 +576,431 @@ int launch_pw_blocks_out(gpimhip_ctx* h, const double* g, int64_t M, int S, cons
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
+
+// ==========================================================================================
+// Draws on a grid with MISSING points through the bordered reflection blocks (gpimhip_sample_border).
+// The model's prediction state is all there is to solve against: the explicit inverse factors L_b^-1 of the completed grid's
+// blocks, and S, L_S^-1, Y_b of the border.  api.hip: sample_border_impl.  Vectors are stored block-major, S + 1 columns of
+// np per block (column S: y); every reduction below has a fixed order and every column accumulates by itself.
+// ==========================================================================================
+__device__ __forceinline__ double bs_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// mi[miss[j]] = j (mi preset to -1): the grid point's place among the missing ones
+__global__ __launch_bounds__(256) void bs_mark_kernel(const int64_t* __restrict__ miss, int Mm, int64_t M, int32_t* __restrict__ mi) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= Mm) return;
+    const int64_t ii = miss[j];
+    if (ii >= 0 && ii < M) mi[ii] = j;
+}
+int launch_bs_mark(gpimhip_ctx* h, const int64_t* miss, int Mm, int64_t M, int32_t* mi) {
+    HIP_TRY(hipMemsetAsync(mi, 0xff, (size_t)M * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(bs_mark_kernel, dim3((unsigned)((Mm + 255) / 256)), dim3(256), 0, h->stream, miss, Mm, M, mi);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+__global__ void bs_merge_info_kernel(int32_t* __restrict__ from, int32_t* __restrict__ into) {
+    const int32_t s = *from;
+    if (s != 0 && *into == 0) *into = s;
+    *from = 0;
+}
+int launch_bs_merge_info(gpimhip_ctx* h, int32_t* from, int32_t* into) {
+    hipLaunchKernelGGL(bs_merge_info_kernel, dim3(1), dim3(1), 0, h->stream, from, into);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// R[b][s][p] = (U r~_s)_{b,p} for s < S, r~_s = g_s + sqrt(diag_add - jitter_s) Z[s][M + .] at the observed points and 0 at
+// the missing ones; R[b][S] = ys[b] (y~ comes in the adapted basis).  pw_basis_fwd_kernel with the right-hand side formed on
+// the way: the same order over the mirror images, zero rows for absent points and for the padding p >= Nq.
+__global__ __launch_bounds__(256) void bs_rhs_fwd_kernel(PwGrid gd, const double* __restrict__ g, const double* __restrict__ Z,
+                                                         int64_t zw, int64_t M, const int32_t* __restrict__ mi,
+                                                         const double* __restrict__ ys, const ThetaDev* __restrict__ th,
+                                                         double jitter_s, int S, int64_t Nq, int64_t np, int B, double rsqrt_b,
+                                                         double* __restrict__ R) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y, b = blockIdx.z;
+    if (p >= np) return;
+    double v = 0.0;
+    if (p < Nq) {
+        if (s == S) {
+            v = ys[(int64_t)b * Nq + p];
+        } else {
+            int ix[GPIMHIP_MAX_DIM];
+            pw_unravel(p, gd.f, gd.d, ix);
+            const int pl = pw_planes(gd, ix), cnt = __popc(pl), sb = refl_sign_dims(gd.mask, b);
+            if (!(sb & pl)) {
+                const double e = th->diag_add - jitter_s, sq = sqrt(e > 0.0 ? e : 0.0);
+                double acc = 0.0;
+                for (int gm = 0; gm < B; ++gm) {
+                    const int sg = refl_sign_dims(gd.mask, gm);
+                    if (sg & pl) continue;
+                    int jx[GPIMHIP_MAX_DIM];
+#pragma unroll
+                    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) jx[k] = ((sg >> k) & 1) ? gd.n[k] - 1 - ix[k] : ix[k];
+                    const int64_t i = pw_ravel(jx, gd.n, gd.d);
+                    const double c = mi[i] >= 0 ? 0.0 : fma(sq, Z[(int64_t)s * zw + M + i], g[(int64_t)s * M + i]);
+                    acc += (__popc(sb & sg) & 1) ? -c : c;
+                }
+                v = acc * (ldexp((cnt & 1) ? 1.41421356237309504880 : 1.0, cnt >> 1) * rsqrt_b);
+            }
+        }
+    }
+    R[((int64_t)b * (S + 1) + s) * np + p] = v;
+}
+int launch_bs_rhs_fwd(gpimhip_ctx* h, PwGrid gd, const double* g, const double* Z, int64_t zw, int64_t M, const int32_t* mi,
+                      const double* ys, const ThetaDev* theta, double jitter_s, int S, int64_t Nq, int64_t np, int B, double* R) {
+    hipLaunchKernelGGL(bs_rhs_fwd_kernel, dim3((unsigned)((np + 255) / 256), S + 1, B), dim3(256), 0, h->stream, gd, g, Z, zw, M, mi,
+                       ys, theta, jitter_s, S, Nq, np, B, 1.0 / sqrt((double)B), R);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// The two triangular sweeps with an EXPLICIT lower-triangular inverse factor T (L_b^-1 of the blocks, batched over
+// blockIdx.y; L_S^-1 with one block): HBM-bound, the triangle is read once per group of SG columns, 16 bytes per lane along
+// the rows.  Only entries T[i][j], j <= i < n are used (what lies above the diagonal or in the padding is never relied on).
+//
+// tri_fwd_multi_kernel: Y[c][i] = sum_{j <= i} T[i][j] X[c][j].  sample_draws_kernel without its mean / variance half: a
+// workgroup owns TF_ROWS rows, two per wave; the columns go by in chunks of TF_CW whose slice of the SG vectors is staged in
+// LDS once for the eight rows.  A lane adds its entries in increasing j, the wave's sum is the xor butterfly: the order of a
+// column's sum depends on nothing but i.
+// ------------------------------------------------------------------------------------------
+#define TF_ROWS 8
+#define TF_CW 256
+
+template <int SG>
+__global__ __launch_bounds__(256) void tri_fwd_multi_kernel(const double* __restrict__ T, int64_t ld, int64_t t_bs, int64_t n,
+                                                            const double* __restrict__ X, double* __restrict__ Y, int64_t cs,
+                                                            int64_t v_bs, int ncols) {
+    __shared__ __attribute__((aligned(16))) double Xs[SG][TF_CW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    T += (int64_t)blockIdx.y * t_bs;
+    X += (int64_t)blockIdx.y * v_bs;
+    Y += (int64_t)blockIdx.y * v_bs;
+    const int64_t i0 = (int64_t)blockIdx.x * TF_ROWS, iw = i0 + 2 * wave;
+    const double* row[2];
+    int64_t lim[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const bool rv = iw + r < n;
+        row[r] = T + (rv ? iw + r : 0) * ld;
+        lim[r] = rv ? iw + r : -1;
+    }
+    double acc[2][SG];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int s = 0; s < SG; ++s) acc[r][s] = 0.0;
+    const int64_t cend = i0 + TF_ROWS < n ? i0 + TF_ROWS : n;          // one past the workgroup's last column
+    const bool rows_full = i0 + TF_ROWS <= n;
+    for (int64_t c0 = 0; c0 < cend; c0 += TF_CW) {
+        __syncthreads();                                    // the previous chunk has been read
+        {
+            const int64_t c = c0 + tid;
+#pragma unroll
+            for (int s = 0; s < SG; ++s) Xs[s][tid] = (c < n && s < ncols) ? X[(int64_t)s * cs + c] : 0.0;
+        }
+        __syncthreads();
+        const bool interior = rows_full && c0 + TF_CW - 1 <= i0;
+        auto body = [&](auto INTERIOR) {
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int e = hh * 128 + lane * 2;
+                const int64_t c = c0 + e;
+                double2 xv[SG];
+#pragma unroll
+                for (int s = 0; s < SG; ++s) xv[s] = *reinterpret_cast<const double2*>(&Xs[s][e]);
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    double2 l;
+                    if (decltype(INTERIOR)::value) {
+                        l = *reinterpret_cast<const double2*>(row[r] + c);
+                    } else {
+                        l.x = l.y = 0.0;
+                        if (c + 1 <= lim[r]) l = *reinterpret_cast<const double2*>(row[r] + c);
+                        else if (c <= lim[r]) l.x = row[r][c];
+                    }
+#pragma unroll
+                    for (int s = 0; s < SG; ++s) {
+                        acc[r][s] = fma(l.x, xv[s].x, acc[r][s]);
+                        acc[r][s] = fma(l.y, xv[s].y, acc[r][s]);
+                    }
+                }
+            }
+        };
+        if (interior) body(std::true_type{});
+        else body(std::false_type{});
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int s = 0; s < SG; ++s) acc[r][s] = bs_wave_sum(acc[r][s]);
+    if (lane != 0) return;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (lim[r] < 0) continue;
+#pragma unroll
+        for (int s = 0; s < SG; ++s)
+            if (s < ncols) Y[(int64_t)s * cs + iw + r] = acc[r][s];
+    }
+}
+// X, Y: the group's first column (column c at + c cs, block b at + b v_bs); ncols = sample_draw_group(columns left)
+int launch_tri_fwd_multi(gpimhip_ctx* h, const double* T, int64_t ld, int64_t t_bs, int64_t n, int B, const double* X, double* Y,
+                         int64_t cs, int64_t v_bs, int ncols) {
+    if (n < 1) return GPIMHIP_OK;
+    const dim3 grid((unsigned)((n + TF_ROWS - 1) / TF_ROWS), B), block(256);
+#define TF_LAUNCH(SG) hipLaunchKernelGGL(tri_fwd_multi_kernel<SG>, grid, block, 0, h->stream, T, ld, t_bs, n, X, Y, cs, v_bs, ncols)
+    if (ncols >= 5) TF_LAUNCH(8);
+    else if (ncols >= 3) TF_LAUNCH(4);
+    else if (ncols == 2) TF_LAUNCH(2);
+    else TF_LAUNCH(1);
+#undef TF_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// tri_bwd_multi_kernel: Y[c][j] = sum_{i >= j} T[i][j] X[c][i], the transposed sweep.  gemv_t_tri_kernel for SG columns: the
+// ROWS are cut into chunks of rc (tri_bwd_rc: a function of the padded order alone), workgroup (64-column strip, chunk)
+// handles what lies at or below the strip's first row and writes 64 partial sums per column to part[chunk][column][j] (pg columns per chunk: the call's largest group); a
+// wave reads two rows x 512 bytes per load (lane: row parity, column pair), four loads in flight, the chunk's slice of the
+// SG vectors staged in LDS 256 rows at a time.  Y[c][j] = the chunks' partial sums from the first chunk that holds a row
+// >= 64 (j / 64) on, in increasing order (tri_bwd_sum_kernel).
+// ------------------------------------------------------------------------------------------
+#define TB_XR 256
+
+template <int SG>
+__global__ __launch_bounds__(256) void tri_bwd_multi_kernel(const double* __restrict__ T, int64_t ld, int64_t t_bs, int64_t n,
+                                                            const double* __restrict__ X, int64_t cs, int64_t v_bs, int ncols,
+                                                            double* __restrict__ part, int64_t np, int rc, int nR, int pg) {
+    __shared__ __attribute__((aligned(16))) double xs[TB_XR][SG];
+    __shared__ double2 red[4][SG][32];
+    const int cb = blockIdx.x / nR, r = blockIdx.x % nR;
+    const int64_t strip0 = (int64_t)cb * 64;
+    int64_t i0 = (int64_t)r * rc, i1 = i0 + rc < n ? i0 + rc : n;
+    if (i1 <= strip0) return;                               // above the strip: never read by the sum
+    if (i0 < strip0) i0 = strip0;
+    T += (int64_t)blockIdx.y * t_bs;
+    X += (int64_t)blockIdx.y * v_bs;
+    part += (((int64_t)blockIdx.y * nR + r) * pg) * np;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cp = lane & 31, rp = lane >> 5;
+    const int64_t j0 = strip0 + 2 * cp;
+    const double* col = T + j0;
+    double2 acc[SG];
+#pragma unroll
+    for (int s = 0; s < SG; ++s) acc[s].x = acc[s].y = 0.0;
+    for (int64_t b0 = i0; b0 < i1; b0 += TB_XR) {
+        __syncthreads();                                    // the previous slice has been read
+        {
+            const int64_t i = b0 + tid;
+#pragma unroll
+            for (int s = 0; s < SG; ++s) xs[tid][s] = (i < i1 && s < ncols) ? X[(int64_t)s * cs + i] : 0.0;
+        }
+        __syncthreads();
+        const int cnt = (int)(i1 - b0 < TB_XR ? i1 - b0 : TB_XR);
+        auto row_step = [&](int il, double2 a) {
+            const int64_t i = b0 + il;
+            a.x = i >= j0 ? a.x : 0.0;                      // (the strict upper triangle is not relied on)
+            a.y = i >= j0 + 1 ? a.y : 0.0;
+#pragma unroll
+            for (int s = 0; s < SG; ++s) {
+                const double x = xs[il][s];
+                acc[s].x = fma(a.x, x, acc[s].x);
+                acc[s].y = fma(a.y, x, acc[s].y);
+            }
+        };
+        int il = 2 * wave + rp;                             // rows il, il + 8, ... (8 = 4 waves x 2 rows)
+        for (; il + 24 < cnt; il += 32) {
+            const double2 a0 = *reinterpret_cast<const double2*>(col + (b0 + il) * ld);
+            const double2 a1 = *reinterpret_cast<const double2*>(col + (b0 + il + 8) * ld);
+            const double2 a2 = *reinterpret_cast<const double2*>(col + (b0 + il + 16) * ld);
+            const double2 a3 = *reinterpret_cast<const double2*>(col + (b0 + il + 24) * ld);
+            row_step(il, a0);
+            row_step(il + 8, a1);
+            row_step(il + 16, a2);
+            row_step(il + 24, a3);
+        }
+        for (; il < cnt; il += 8) row_step(il, *reinterpret_cast<const double2*>(col + (b0 + il) * ld));
+    }
+#pragma unroll
+    for (int s = 0; s < SG; ++s) {
+        acc[s].x += __shfl_xor(acc[s].x, 32);               // the two row parities
+        acc[s].y += __shfl_xor(acc[s].y, 32);
+        if (rp == 0) red[wave][s][cp] = acc[s];
+    }
+    __syncthreads();
+    if (tid < 32) {
+#pragma unroll
+        for (int s = 0; s < SG; ++s) {
+            if (s >= ncols) continue;
+            double2 t = red[0][s][cp];
+            t.x = ((t.x + red[1][s][cp].x) + red[2][s][cp].x) + red[3][s][cp].x;
+            t.y = ((t.y + red[1][s][cp].y) + red[2][s][cp].y) + red[3][s][cp].y;
+            *reinterpret_cast<double2*>(part + (int64_t)s * np + j0) = t;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void tri_bwd_sum_kernel(const double* __restrict__ part, int64_t np, int64_t n, int rc, int nR,
+                                                          int pg, double* __restrict__ Y, int64_t cs, int64_t v_bs) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y, b = blockIdx.z;
+    if (j >= n) return;
+    const int rl = (int)((n + rc - 1) / rc);                // chunks that hold a row < n
+    double t = 0.0;
+    for (int r = (int)(((j / 64) * 64) / rc); r < rl; ++r) t += part[((((int64_t)b * nR + r) * pg) + s) * np + j];
+    Y[(int64_t)b * v_bs + (int64_t)s * cs + j] = t;
+}
+// part: B x tri_bwd_chunks(np) x pg x np, pg >= ncols (the largest group of the call)
+int launch_tri_bwd_multi(gpimhip_ctx* h, const double* T, int64_t ld, int64_t t_bs, int64_t n, int64_t np, int B, const double* X,
+                         double* Y, int64_t cs, int64_t v_bs, int ncols, double* part, int pg) {
+    if (n < 1) return GPIMHIP_OK;
+    if (pg < ncols) return GPIMHIP_E_BADARG;
+    const int rc = tri_bwd_rc(np), nR = tri_bwd_chunks(np);
+    const dim3 grid((unsigned)(((n + 63) / 64) * nR), B), block(256);
+#define TB_LAUNCH(SG) \
+    hipLaunchKernelGGL(tri_bwd_multi_kernel<SG>, grid, block, 0, h->stream, T, ld, t_bs, n, X, cs, v_bs, ncols, part, np, rc, nR, pg)
+    if (ncols >= 5) TB_LAUNCH(8);
+    else if (ncols >= 3) TB_LAUNCH(4);
+    else if (ncols == 2) TB_LAUNCH(2);
+    else TB_LAUNCH(1);
+#undef TB_LAUNCH
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tri_bwd_sum_kernel, dim3((unsigned)((n + 255) / 256), ncols, B), dim3(256), 0, h->stream,
+                       (const double*)part, np, n, rc, nR, pg, Y, cs, v_bs);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// t[c][j] = sum_b coef_b(j) beta_b[c][q(j)] for the S1 columns (border_t_kernel's sum, b ascending); 0 on the padding j >= Mm
+__global__ __launch_bounds__(256) void bs_t_kernel(const double* __restrict__ beta, int64_t np, int B, int S1,
+                                                   const int32_t* __restrict__ q, const double* __restrict__ coef, int Mm,
+                                                   int64_t mp, double* __restrict__ t) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (j >= mp) return;
+    double v = 0.0;
+    if (j < Mm)
+        for (int b = 0; b < B; ++b) v = fma(coef[(int64_t)b * Mm + j], beta[((int64_t)b * S1 + c) * np + q[j]], v);
+    t[(int64_t)c * mp + j] = v;
+}
+int launch_bs_t(gpimhip_ctx* h, const double* beta, int64_t np, int B, int S1, const int32_t* q, const double* coef, int Mm,
+                int64_t mp, double* t) {
+    hipLaunchKernelGGL(bs_t_kernel, dim3((unsigned)((mp + 255) / 256), S1), dim3(256), 0, h->stream, beta, np, B, S1, q, coef, Mm,
+                       mp, t);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// alpha~_b[c] = beta_b[c] - Y_b v[c] in place, for the rows p < Nq of every block: the skinny product over the stacked
+// (B np) x mp matrix Y, read once per group of SG columns.  Two rows per wave share the loads of v; a lane adds its entries
+// in increasing k, the wave's sum is the butterfly.  v is zero on its padding (and so are Y's padding columns).
+template <int SG>
+__global__ __launch_bounds__(256) void bs_yv_kernel(const double* __restrict__ Yb, int64_t mp, int64_t np, int64_t Nq, int S1,
+                                                    const double* __restrict__ v, int c0, int ncols, double* __restrict__ Al) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * 8 + 2 * wave;
+    if (p0 >= Nq) return;
+    const bool two = p0 + 1 < Nq;
+    const double* y0 = Yb + ((int64_t)b * np + p0) * mp;
+    const double* y1 = y0 + (two ? mp : 0);
+    double acc[2][SG];
+#pragma unroll
+    for (int s = 0; s < SG; ++s) acc[0][s] = acc[1][s] = 0.0;
+    for (int64_t k = lane * 2; k < mp; k += 128) {
+        const double2 a0 = *reinterpret_cast<const double2*>(y0 + k), a1 = *reinterpret_cast<const double2*>(y1 + k);
+#pragma unroll
+        for (int s = 0; s < SG; ++s) {
+            double2 x;
+            x.x = x.y = 0.0;
+            if (s < ncols) x = *reinterpret_cast<const double2*>(v + (int64_t)(c0 + s) * mp + k);
+            acc[0][s] = fma(a0.x, x.x, acc[0][s]);
+            acc[0][s] = fma(a0.y, x.y, acc[0][s]);
+            acc[1][s] = fma(a1.x, x.x, acc[1][s]);
+            acc[1][s] = fma(a1.y, x.y, acc[1][s]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < SG; ++s) {
+        acc[0][s] = bs_wave_sum(acc[0][s]);
+        acc[1][s] = bs_wave_sum(acc[1][s]);
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int s = 0; s < SG; ++s) {
+        if (s >= ncols) continue;
+        double* a = Al + ((int64_t)b * S1 + c0 + s) * np + p0;
+        a[0] -= acc[0][s];
+        if (two) a[1] -= acc[1][s];
+    }
+}
+int launch_bs_yv(gpimhip_ctx* h, const double* Yb, int64_t mp, int64_t np, int64_t Nq, int B, int S1, const double* v, int c0,
+                 int ncols, double* Al) {
+    const dim3 grid((unsigned)((Nq + 7) / 8), B), block(256);
+#define YV_LAUNCH(SG) hipLaunchKernelGGL(bs_yv_kernel<SG>, grid, block, 0, h->stream, Yb, mp, np, Nq, S1, v, c0, ncols, Al)
+    if (ncols >= 5) YV_LAUNCH(8);
+    else if (ncols >= 3) YV_LAUNCH(4);
+    else if (ncols == 2) YV_LAUNCH(2);
+    else YV_LAUNCH(1);
+#undef YV_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// Cc[b][c][p] (rows of Nq, the layout of pw_basis_t_kernel): c < S: (s - d) alpha~_b[c];  c == S: ys_b - s alpha~_y,b
+__global__ __launch_bounds__(256) void bs_combine_kernel(const double* __restrict__ Al, const double* __restrict__ ys, int S,
+                                                         int64_t Nq, int64_t np, const ThetaDev* __restrict__ th,
+                                                         double jitter_s, double* __restrict__ Cc) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y, b = blockIdx.z;
+    if (p >= Nq) return;
+    const double sd = th->diag_add, a = Al[((int64_t)b * (S + 1) + c) * np + p];
+    double e = sd - jitter_s;
+    e = e > 0.0 ? e : 0.0;
+    Cc[((int64_t)b * (S + 1) + c) * Nq + p] = c < S ? e * a : ys[(int64_t)b * Nq + p] - sd * a;
+}
+int launch_bs_combine(gpimhip_ctx* h, const double* Al, const double* ys, int S, int64_t Nq, int64_t np, int B,
+                      const ThetaDev* theta, double jitter_s, double* Cc) {
+    hipLaunchKernelGGL(bs_combine_kernel, dim3((unsigned)((Nq + 255) / 256), S + 1, B), dim3(256), 0, h->stream, Al, ys, S, Nq, np,
+                       theta, jitter_s, Cc);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// g2 = U^T Cc (S + 1 rows of M).  Observed point i: mean = g2[S][i], draw c = mean + (g2[c][i] - sqrt(s - d) Z[c][M + i]);
+// missing point j at i: mean = -w[S][j], draw c = mean + (g[c][i] + w[c][j]).  (+ sqrt(noise) Z[c][2 M + i] unless noiseless)
+__global__ __launch_bounds__(256) void bs_out_kernel(const double* __restrict__ g2, const double* __restrict__ g,
+                                                     const double* __restrict__ wv, int64_t mp, const int32_t* __restrict__ mi,
+                                                     int64_t M, int S, const double* __restrict__ Z, int64_t zw, int noiseless,
+                                                     const ThetaDev* __restrict__ th, double jitter_s,
+                                                     double* __restrict__ mean_out, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= M) return;
+    const int j = mi[i];
+    const double mean = j >= 0 ? -wv[(int64_t)S * mp + j] : g2[(int64_t)S * M + i];
+    if (c == S) {
+        if (mean_out) mean_out[i] = mean;
+        return;
+    }
+    double v;
+    if (j >= 0) {
+        v = mean + (g[(int64_t)c * M + i] + wv[(int64_t)c * mp + j]);
+    } else {
+        const double e = th->diag_add - jitter_s;
+        v = mean + (g2[(int64_t)c * M + i] - sqrt(e > 0.0 ? e : 0.0) * Z[(int64_t)c * zw + M + i]);
+    }
+    if (!noiseless) v = fma(sqrt(th->noise), Z[(int64_t)c * zw + 2 * M + i], v);
+    out[(int64_t)c * M + i] = v;
+}
+int launch_bs_out(gpimhip_ctx* h, const double* g2, const double* g, const double* wv, int64_t mp, const int32_t* mi, int64_t M,
+                  int S, const double* Z, int64_t zw, int noiseless, const ThetaDev* theta, double jitter_s, double* mean_out,
+                  double* out) {
+    hipLaunchKernelGGL(bs_out_kernel, dim3((unsigned)((M + 255) / 256), S + 1), dim3(256), 0, h->stream, g2, g, wv, mp, mi, M, S, Z,
+                       zw, noiseless, theta, jitter_s, mean_out, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}

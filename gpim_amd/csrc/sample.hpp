@@ -57,3 +57,38 @@ int launch_pw_blocks_combine(gpimhip_ctx* h, const double* Al, const double* Eb,
 // out[s] = g[s] (+ sqrt(noise) Z[s][zn_off + .] unless noiseless), mean_out (optional) = g[S]
 int launch_pw_blocks_out(gpimhip_ctx* h, const double* g, int64_t M, int S, const double* Z, int64_t zw, int64_t zn_off,
                          int noiseless, const ThetaDev* theta, double* mean_out, double* out);
+
+// ---- draws on a grid with missing points through the bordered reflection blocks (gpimhip_sample_border) ----
+// Vectors are block-major: block b at + b v_bs, column c at + c cs (cs = the padded block order).
+// mi (M int32) = -1, then mi[miss[j]] = j
+int launch_bs_mark(gpimhip_ctx* h, const int64_t* miss, int Mm, int64_t M, int32_t* mi);
+// *into = *from if *into == 0; *from = 0  (two status words, one report)
+int launch_bs_merge_info(gpimhip_ctx* h, int32_t* from, int32_t* into);
+// R[b][s] = (U (1_o (g_s + sqrt(diag_add - jitter_s) Z[s][M + .])))_b for s < S, R[b][S] = ys[b]; zero padding rows p >= Nq
+int launch_bs_rhs_fwd(gpimhip_ctx* h, PwGrid gd, const double* g, const double* Z, int64_t zw, int64_t M, const int32_t* mi,
+                      const double* ys, const ThetaDev* theta, double jitter_s, int S, int64_t Nq, int64_t np, int B, double* R);
+// Y[c][i] = sum_{j <= i} T[i][j] X[c][j], i < n, for ncols (1 .. 8) columns and B lower-triangular matrices T (t_bs apart)
+int launch_tri_fwd_multi(gpimhip_ctx* h, const double* T, int64_t ld, int64_t t_bs, int64_t n, int B, const double* X, double* Y,
+                         int64_t cs, int64_t v_bs, int ncols);
+// row chunks of the transposed sweep: ~np / 8 rows, a multiple of 256 -- a function of the padded order alone
+static inline int tri_bwd_rc(int64_t np) {
+    const int64_t rc = ((np / 8 + 255) / 256) * 256;
+    return (int)(rc < 256 ? 256 : rc);
+}
+static inline int tri_bwd_chunks(int64_t np) { return (int)((np + tri_bwd_rc(np) - 1) / tri_bwd_rc(np)); }
+// Y[c][j] = sum_{i >= j} T[i][j] X[c][i], j < n (X and Y may not alias); part: B x tri_bwd_chunks(np) x pg x np, pg >= ncols
+int launch_tri_bwd_multi(gpimhip_ctx* h, const double* T, int64_t ld, int64_t t_bs, int64_t n, int64_t np, int B, const double* X,
+                         double* Y, int64_t cs, int64_t v_bs, int ncols, double* part, int pg);
+// t[c][j] = sum_b coef_b(j) beta_b[c][q(j)] (S1 columns of mp, zero padding)
+int launch_bs_t(gpimhip_ctx* h, const double* beta, int64_t np, int B, int S1, const int32_t* q, const double* coef, int Mm,
+                int64_t mp, double* t);
+// Al_b[c] -= Y_b v[c] for the columns c0 .. c0 + ncols - 1, rows p < Nq
+int launch_bs_yv(gpimhip_ctx* h, const double* Yb, int64_t mp, int64_t np, int64_t Nq, int B, int S1, const double* v, int c0,
+                 int ncols, double* Al);
+// Cc[b][c] (rows of Nq): (diag_add - jitter_s) Al_b[c] for c < S, ys_b - diag_add Al_b[S] for c == S
+int launch_bs_combine(gpimhip_ctx* h, const double* Al, const double* ys, int S, int64_t Nq, int64_t np, int B,
+                      const ThetaDev* theta, double jitter_s, double* Cc);
+// the two cases of the combination, chosen by mi, and the z_n epilogue (sample.hip: bs_out_kernel)
+int launch_bs_out(gpimhip_ctx* h, const double* g2, const double* g, const double* wv, int64_t mp, const int32_t* mi, int64_t M,
+                  int S, const double* Z, int64_t zw, int noiseless, const ThetaDev* theta, double jitter_s, double* mean_out,
+                  double* out);

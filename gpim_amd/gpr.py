@@ -465,6 +465,78 @@ class reconstructor(_solvers.HostDriver):
         self._blocks_bytes = max(need, getattr(self, "_blocks_bytes", 0))
         return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
 
+    _BORDER_ENGINE = "method='border' draws on an image with missing points through its bordered reflection blocks, in " \
+                     "double precision (%s)"
+
+    def _sample_border_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
+        """sample(method='border'): every argument is checked before anything is stored, so a refused call leaves the model
+        and its stored test grid as they were."""
+        if self.do_sparse:
+            raise NotImplementedError(self._BORDER_ENGINE % "sparse=True")
+        if self.precision == "single":
+            raise NotImplementedError(self._BORDER_ENGINE % "precision='single'")
+        if not self.do_border:
+            if self.do_symm or self.do_structured:
+                raise NotImplementedError(self._BORDER_ENGINE % "the grid is fully observed: use method='blocks'")
+            raise NotImplementedError(self._BORDER_ENGINE % "a dense model: use method='pathwise', or skreconstructor for an "
+                                      "image or cube with missing pixels")
+        self._check_data()
+        B = self._solver.S
+        gshape = tuple(len(c) for c in B["axes"])
+        if Xtest is not None:
+            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+            Xs, shape = self._to_device(gprutils.prepare_test_data(Xtest, precision=self.precision)), tuple(Xtest.shape[1:])
+        elif self._Xtest_d is not None:
+            Xs, shape = self._Xtest_d, tuple(self.fulldims)
+        else:
+            Xs, shape = None, gshape
+        c = getattr(self, "_border_grid", None)
+        if c is None:
+            G = np.array(np.meshgrid(*B["axes"], indexing="ij")).reshape(len(gshape), -1).T
+            c = self._border_grid = [self._to_device(np.ascontiguousarray(G)),
+                                     torch.from_numpy(B["miss"].astype(np.int64)).to(self._dev), None]
+        G_d, miss_d = c[0], c[1]
+        if Xs is not None and c[2] is not Xs:
+            self._require_finite(Xs)
+            if shape != gshape or Xs.shape != G_d.shape or not bool(torch.equal(Xs, G_d)):
+                raise NotImplementedError("method='border' needs the completed training grid as its test grid (Xtest None, the "
+                                          "stored grid, or a grid equal to it: shape %s); got a grid of shape %s that is not it"
+                                          % (gshape, shape))
+            if Xtest is None:
+                c[2] = Xs                   # the stored grid: compared once
+        M = G_d.shape[0]
+        W = 2 * M + (0 if noiseless else M)
+        S = int(n_samples)
+        if z is None:
+            z_d = self._draw_z(S, W, seed)
+        else:
+            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
+            if z_d.dim() != 2 or z_d.shape != (S, W):
+                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='border' (M = %d grid points%s); got %s"
+                                 % (W, S, W, M, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
+        jitter = self._spec.jitter if jitter is None else float(jitter)
+        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
+        if not (0.0 < jitter <= s):
+            raise ValueError("method='border' needs 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
+        # the large allocation beyond a prediction of the model: one (M / 2^r)^2 block for the prior factors
+        nq = B["Xq"].shape[0]
+        order = -(-nq // 128) * 128
+        need = order * (order + (16 if order >= 1024 else 0)) * 8
+        if need > getattr(self, "_border_bytes", 0):
+            free, total = torch.cuda.mem_get_info(self._dev)
+            if need > free:
+                raise MemoryError("sample: a reflection block of %d points needs %.2f GiB of device memory, %.2f of %.2f GiB are "
+                                  "free" % (nq, need / 2.0 ** 30, free / 2.0 ** 30, total / 2.0 ** 30))
+        if Xtest is not None:
+            self._resolve_test_grid(Xtest)
+        out = torch.empty((S, M), dtype=_F64, device=self._dev)
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        P = {"shape": gshape, "mask": B["mask"], "twoc": B["twoc"]}
+        _lib.check(self._solver.sample_border(self, G_d, P, miss_d, z_d, noiseless, jitter, mean, out))
+        self._border_bytes = max(need, getattr(self, "_border_bytes", 0))
+        return out.cpu().numpy().reshape((S,) + gshape).astype(self._np_out, copy=False)
+
     def _draw_z(self, n_samples, M, seed=None, generator=None):
         if generator is None and seed is not None:
             generator = torch.Generator(self._dev).manual_seed(int(seed))
@@ -492,11 +564,20 @@ class reconstructor(_solvers.HostDriver):
         observation on every grid point -- computed in the grid's reflection basis alone: 2 x 2^r factorisations of order
         M / 2^r, no matrix of order M.  The test grid must be the training grid (``Xtest`` None, the
         stored grid, or equal to it) with a symmetric axis; ``z`` has shape ``(n_samples, 2 M)`` if noiseless, else
-        ``(n_samples, 3 M)``, the layout of ``'pathwise'`` with N = M; 0 < jitter <= noise + the model's jitter."""
-        if method not in ("joint", "pathwise", "blocks"):
-            raise ValueError("method must be 'joint', 'pathwise' or 'blocks'; got %r" % (method,))
+        ``(n_samples, 3 M)``, the layout of ``'pathwise'`` with N = M; 0 < jitter <= noise + the model's jitter.
+
+        ``method='border'``: the pathwise draw for an image or cube with missing pixels -- ``skreconstructor`` whose
+        ``solver`` is ``'border'`` -- through the bordered reflection blocks of the completed grid: the factorisations of a
+        prediction plus 2^r prior factors of order M / 2^r, no matrix of the order of the image.  A
+        draw fills the holes with one plausible reconstruction.  The test grid must be the completed training grid
+        (``Xtest`` None, the stored grid, or equal to it); ``z`` has the layout of ``'blocks'``, every part indexed by the
+        grid point (entries of ``z_e`` at missing pixels are ignored); 0 < jitter <= noise + the model's jitter."""
+        if method not in ("joint", "pathwise", "blocks", "border"):
+            raise ValueError("method must be 'joint', 'pathwise', 'blocks' or 'border'; got %r" % (method,))
         if method == "blocks":
             return self._sample_blocks_host(n_samples, Xtest, noiseless, seed, z, jitter)
+        if method == "border":
+            return self._sample_border_host(n_samples, Xtest, noiseless, seed, z, jitter)
         self._sample_supported()
         if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
             # (refused before it replaces the stored test grid)

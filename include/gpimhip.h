@@ -214,6 +214,36 @@ int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m,
                           int32_t noiseless, double jitter,
                           double* mean_out, double* samples_out);
 
+/* S pathwise draws on a product grid G with MISSING points, through the bordered reflection blocks of the model (DESIGN.md
+ * section 18): the handle is in reflection mode with a border (gpimhip_set_reflection, gpimhip_set_border), and X, x_stride,
+ * y, N, B, u are those of gpimhip_predict_exact_batched for that model -- the fundamental domain, y with 0 at the missing
+ * points in the adapted basis (gpim_amd.gprutils.border_blocks), B = 2^r copies of the parameter vector.
+ * With A = K_GG + s I on the completed grid, V = A^-1 P_m, S = P_m^T V and g the prior draw of gpimhip_sample_pathwise:
+ *   r~ = 1_o (g + sqrt(s - d) z_e),   beta = A^-1 [r~ | y~],   w = S^-1 beta_m,   alpha~ = beta - V w
+ *   draw = y - s alpha~_y + (s - d) alpha~ - sqrt(s - d) z_e   at the observed points
+ *        = -w_y + g + w                                        at the missing points      (+ s_n z_n unless noiseless)
+ * the draws of gpimhip_sample_pathwise with idx = the observed points up to rounding.  A^-1, S^-1 and V are applied through
+ * what a prediction of the model leaves (the explicit factors L_b^-1, L_S^-1 and Y_b): no matrix of the order of the grid,
+ * no product with K_GX.
+ *   G, shape, mask, twoc   the completed grid as for gpimhip_sample_pathwise; mask and B must be the handle's
+ *   miss     the flat (row-major) grid indices of the M_m missing points of gpimhip_set_border, in its order (device int64)
+ *   Z        S x (2 M [+ M]) standard normals (device), row s = [z_p | z_e | z_n], each indexed by the grid point; entries
+ *            of z_e at missing points are ignored
+ *   mean_out (M, may be NULL), samples_out (S x M)
+ * Beyond the prediction state of the model: one block of the prior (shared with gpimhip_sample_blocks) and vectors, grow-only,
+ * counted by gpimhip_workspace_bytes.  Double-precision handles only; no reflection mode, no border, a multi-output batch
+ * (B = T 2^r problems with T > 1: one border per task is not built; what the handle ran before does not matter, the entry
+ * sets its one border up itself), a grid that does not match the handle's blocks, NULL arguments, S < 1, S > 65534 or
+ * jitter <= 0 -> GPIMHIP_E_BADARG.  Synchronises once, at the end (NOT_PD of any factorisation -- prior blocks, model blocks, S -- through the
+ * model's status word; the handle stays usable). */
+int gpimhip_sample_border(gpimhip_handle h, const gpimhip_model_t* m,
+                          const double* X, int64_t x_stride, const double* y, int64_t N, int32_t B, const double* u,
+                          const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                          const int64_t* miss,
+                          const double* Z, int32_t S,
+                          int32_t noiseless, double jitter,
+                          double* mean_out, double* samples_out);
+
 /* Batched forms: B independent problems with the SAME N (and the same model description), advanced in
  * lock-step by every launch (grid.y = problem index) -- B spectral slices of a cube share each
  * latency-bound step of the blocked factorisation instead of paying for it B times.
@@ -606,6 +636,11 @@ int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, i
  *        2 = gathers and the basis change U^T, 1 = the vector solves, 3 = cross_apply_kernel and its epilogue.
  * gpimhip_sample_blocks: 4 = covariance builds (2 x 2^r), 0 = their factorisations, 5 = the sweeps L_b z_p, 2 = gathers and the
  *        basis changes U and U^T, 1 = the multi-column solves, 3 = right-hand sides, combination and epilogue.
+ * gpimhip_sample_border: 4 = covariance builds of the 2^r prior blocks, 0 = factorisations (prior blocks, model blocks, S,
+ *        with the inverses the launches host), 5 = the sweeps L_b z_p, 2 = gathers and basis changes, 1 = the multi-column
+ *        sweeps through L_b^-1 (and the rest of the triangular inverses), 6 = those two sweeps alone (one interval per group
+ *        of columns, inside stage 1's; no other entry point records stage 6), 3 = right-hand sides, the border's vectors,
+ *        combination and epilogue; the model's covariance build, K^-1 product and border products are not timed.
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
