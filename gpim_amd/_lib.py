@@ -173,6 +173,13 @@ _PROTOS = {
                                        ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
     "gpimhip_predict_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
                                            c_dp, ctypes.c_int64, c_dp, c_dp, ctypes.c_int64, c_dp, c_dp]),
+    "gpimhip_sample_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp, c_dp,
+                                          ctypes.c_int64, c_dp, c_dp, ctypes.c_int64, c_dp, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_double, c_dp, c_dp, c_dp]),
+    "gpimhip_sample_vgp_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
+                                                 ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                                 ctypes.POINTER(ctypes.c_double), c_dp, c_dp, c_dp, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
     "gpimhip_sm_kmat": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, ctypes.c_int64, c_dp, ctypes.c_int64,
                                        c_dp, c_dp, ctypes.c_int64]),
     "gpimhip_sm_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,

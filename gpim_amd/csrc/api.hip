@@ -2080,6 +2080,13 @@ struct SampleWs {
     double* Pb = nullptr; int64_t pb_cap = 0;
     double* Kt = nullptr; int64_t kt_cap = 0;
     double* pw = nullptr; int64_t pw_cap = 0;
+    // multi-output draws (sample_vgp_impl / sample_vgp_blocks_impl): the state of the reduction, the T
+    // latent blocks' thetas, their targets z_t (T x N), draws H (T x S x M) and moments (2 x T x M: mean, variance)
+    VgpDev* vst = nullptr;
+    ThetaDev* vth = nullptr;
+    double* vz = nullptr; int64_t vz_cap = 0;
+    double* vH = nullptr; int64_t vh_cap = 0;
+    double* vmom = nullptr; int64_t vmom_cap = 0;
 };
 static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
 static int64_t sample_bytes(const gpimhip_ctx* h) {
@@ -2096,6 +2103,11 @@ static void sample_release(gpimhip_ctx* h) {
     dev_free(h, &w->Pb, w->pb_cap);
     dev_free(h, &w->Kt, w->kt_cap);
     dev_free(h, &w->pw, w->pw_cap);
+    dev_free(h, &w->vst, 1);
+    dev_free(h, &w->vth, VGP_MAXT);
+    dev_free(h, &w->vz, w->vz_cap);
+    dev_free(h, &w->vH, w->vh_cap);
+    dev_free(h, &w->vmom, w->vmom_cap);
     if (w->sub) gpimhip_destroy(w->sub);
     if (w->subp) gpimhip_destroy(w->subp);
     if (w->subt) gpimhip_destroy(w->subt);
@@ -2122,9 +2134,13 @@ static int sample_forward(gpimhip_ctx* sub, const double* L, int64_t ld, const d
     return GPIMHIP_OK;
 }
 
-static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
-                       const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
-                       double* var_out, double* samples_out) {
+// Everything of one draw call but the closing synchronisation.  theta_src (optional, device): the hyper-parameters, copied
+// into the context's theta in place of launch_theta(sub, m, u) -- a latent block of the multi-output model (variance
+// lambda_t, noise 1, diag_add 1: sample_vgp_impl); u is not read then.  reset_info: clear the context's status word first
+// (a call of several blocks clears it once: the word keeps the first failure).
+static int sample_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                          const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
+                          double* var_out, double* samples_out, const ThetaDev* theta_src, bool reset_info) {
     HIP_TRY(hipSetDevice(h->device));
     if (!h->sample) h->sample = new SampleWs();
     SampleWs* w = sws(h);
@@ -2139,12 +2155,13 @@ static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X
     GP_TRY(dev_grow(h, &w->XX, &w->xx_cap, np * GPIMHIP_MAX_DIM));
     GP_TRY(dev_grow(h, &w->vec, &w->vec_cap, 2 * np + 4 * NB));
     double *t = w->vec, *piece = t + np, *mean_ws = piece + 4 * NB;
-    HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
+    if (reset_info) HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
     HIP_TRY(hipMemcpyAsync(w->XX, X, (size_t)(N * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(w->XX + N * d, Xs, (size_t)(M * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     // J (lower tiles; identity padding at the end), the two diagonal terms, L
     // (stage timers of the model handle: 4 covariance build, 0 factorisation, 1 forward substitution, 5 each sweep of the draws)
-    GP_TRY(launch_theta(sub, m, u));
+    if (theta_src) HIP_TRY(hipMemcpyAsync(sub->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
+    else GP_TRY(launch_theta(sub, m, u));
     {
         StageTimer tm(h, 4);
         GP_TRY(launch_kmat(sub, m, w->XX, NM, nullptr, NM, sub->theta, 0.0, 0, w->J, ld, np, np, 1, 1, 0, 0, 0));
@@ -2160,7 +2177,13 @@ static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X
         GP_TRY(launch_sample_draws(sub, w->J, ld, N, M, sub->z, Z, S, s0, sub->theta, noiseless, jitter_s, mean_ws, mean_out,
                                    var_out, samples_out));
     }
-    return finish_and_check(sub);
+    return GPIMHIP_OK;
+}
+static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                       const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
+                       double* var_out, double* samples_out) {
+    GP_TRY(sample_enqueue(h, m, X, y, N, u, Xs, M, Z, S, noiseless, jitter_s, mean_out, var_out, samples_out, nullptr, true));
+    return finish_and_check(sws(h)->sub);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2318,9 +2341,12 @@ static int blocks_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const dou
 
 // (stage timers of the model handle, as sample_pathwise_impl: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p,
 // 2 gathers and both basis changes, 1 the multi-column solves, 3 right-hand sides, combination and epilogue)
-static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
-                              int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
-                              double jitter_s, double* mean_out, double* samples_out) {
+// Everything of one call but the closing synchronisation.  theta_src / reset_info: as sample_enqueue; jitter_m: the model's
+// own jitter of the diagonal K_b + (noise + jitter_m) I (m->jitter; 0 for a latent block of the multi-output model).
+static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
+                                 int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
+                                 double jitter_s, double* mean_out, double* samples_out, const ThetaDev* theta_src,
+                                 double jitter_m, bool reset_info) {
     HIP_TRY(hipSetDevice(h->device));
     if (!h->sample) h->sample = new SampleWs();
     SampleWs* w = sws(h);
@@ -2342,8 +2368,9 @@ static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid g
            *g = w->pw + o_g, *R = w->pw + o_r, *Zf = w->pw + o_zf, *Al = w->pw + o_al, *t = w->pw + o_t, *part = w->pw + o_part,
            *mean_ws = w->pw + o_mws;
     // one status word for the 2 B factorisations
-    HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(launch_theta(sp, m, u));
+    if (reset_info) HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
+    if (theta_src) HIP_TRY(hipMemcpyAsync(sp->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
+    else GP_TRY(launch_theta(sp, m, u));
     {
         StageTimer tm(h, 2);
         GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
@@ -2374,7 +2401,7 @@ static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid g
                                        nullptr, nullptr, Cb));
         }
         // ---- T_b = K_b + s I in the same buffer, its factor, [alpha_b | alpha_y,b] for the S draws and y
-        GP_TRY(launch_pw_reset_diag(sp, sp->theta, m->jitter));
+        GP_TRY(launch_pw_reset_diag(sp, sp->theta, jitter_m));
         {
             StageTimer tm(h, 4);
             GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
@@ -2398,7 +2425,81 @@ static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid g
         StageTimer tm(h, 3);
         GP_TRY(launch_pw_blocks_out(sp, g, M, S, Z, zw, 2 * M, noiseless, sp->theta, mean_out, samples_out));
     }
-    return finish_and_check(sp);
+    return GPIMHIP_OK;
+}
+static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
+                              int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
+                              double jitter_s, double* mean_out, double* samples_out) {
+    GP_TRY(sample_blocks_enqueue(h, m, gd, twoc, G, M, y, u, Z, S, noiseless, jitter_s, mean_out, samples_out, nullptr, m->jitter,
+                                 true));
+    return finish_and_check(sws(h)->subp);
+}
+
+// ------------------------------------------------------------------------------------------
+// joint draws of the multi-output GP.  The reduction of section 9 diagonalises the posterior too: the
+// whitened, rotated latent functions h_t = sum_a Q_at s_a^-1/2 f_a are independent GPs with kernel lambda_t K, observed with
+// unit noise through z_t, so a joint draw of the T outputs is one single-output draw per latent block, mixed back:
+//   f_a = mu_a + s_a^1/2 sum_t Q_at h_t          (vgp.hip: vgp_sample_mix_kernel)
+// The blocks run one after the other through the single-output drivers above and the one matrix those own (J, or Pb): the
+// large allocation is that of a single-output call at the same sizes.  One status word, one synchronisation.
+// (stage timers of the model handle: those of the single-output driver, summed over the T blocks, and 6 = the mix kernel;
+// the joint route also records 2 = setup and projection, 3 = the mix of mean and variance)
+// ------------------------------------------------------------------------------------------
+static int sample_vgp_ws(gpimhip_ctx* h, int T, int64_t N, int64_t M, int S, SampleWs** out) {
+    if (!h->sample) h->sample = new SampleWs();
+    SampleWs* w = sws(h);
+    if (!w->vst) GP_TRY(dev_alloc(h, &w->vst, 1));
+    if (!w->vth) GP_TRY(dev_alloc(h, &w->vth, VGP_MAXT));
+    GP_TRY(dev_grow(h, &w->vz, &w->vz_cap, (int64_t)T * N));
+    GP_TRY(dev_grow(h, &w->vH, &w->vh_cap, (int64_t)T * S * M));
+    GP_TRY(dev_grow(h, &w->vmom, &w->vmom_cap, 2 * (int64_t)T * M));
+    *out = w;
+    return GPIMHIP_OK;
+}
+
+static int sample_vgp_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
+                           int64_t N, const double* u, const double* Xs, int64_t M, const double* Z, int S, int noiseless,
+                           double jitter_s, double* mean_out, double* var_out, double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int T = vg->tasks;
+    SampleWs* w = nullptr;
+    GP_TRY(sample_vgp_ws(h, T, N, M, S, &w));
+    double *mblk = w->vmom, *vblk = w->vmom + (int64_t)T * M;
+    {
+        StageTimer tm(h, 2);
+        GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
+        GP_TRY(launch_vgp_project_to(h, Y, N, T, w->vst, w->vz));
+    }
+    for (int t = 0; t < T; ++t)
+        GP_TRY(sample_enqueue(h, m, X, w->vz + (int64_t)t * N, N, nullptr, Xs, M, Z + (int64_t)t * S * M, S, noiseless, jitter_s,
+                              mean_out ? mblk + (int64_t)t * M : nullptr, var_out ? vblk + (int64_t)t * M : nullptr,
+                              w->vH + (int64_t)t * S * M, w->vth + t, t == 0));
+    { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
+    if (mean_out || var_out) {
+        StageTimer tm(h, 3);
+        GP_TRY(launch_vgp_combine(h, T, M, w->vst, mblk, vblk, mean_out, var_out));
+    }
+    return finish_and_check(w->sub);
+}
+
+static int sample_vgp_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, PwGrid gd,
+                                  const double* twoc, const double* G, int64_t M, const double* Y, const double* u,
+                                  const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
+                                  double* samples_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int T = vg->tasks;
+    SampleWs* w = nullptr;
+    GP_TRY(sample_vgp_ws(h, T, M, M, S, &w));
+    const int64_t zw = 2 * M + (noiseless ? 0 : M);
+    GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
+    GP_TRY(launch_vgp_project_to(h, Y, M, T, w->vst, w->vz));
+    for (int t = 0; t < T; ++t)
+        GP_TRY(sample_blocks_enqueue(h, m, gd, twoc, G, M, w->vz + (int64_t)t * M, nullptr, Z + (int64_t)t * S * zw, S, noiseless,
+                                     jitter_s, mean_out ? w->vmom + (int64_t)t * M : nullptr, w->vH + (int64_t)t * S * M,
+                                     w->vth + t, 0.0, t == 0));
+    { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
+    if (mean_out) GP_TRY(launch_vgp_combine(h, T, M, w->vst, w->vmom, nullptr, mean_out, nullptr));
+    return finish_and_check(w->subp);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2561,6 +2662,45 @@ int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m, const doub
         return GPIMHIP_E_BADARG;
     }
     return sample_blocks_impl(h, m, gd, twoc, G, M, y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+}
+
+int gpimhip_sample_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
+                       int64_t N, const double* u, const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless,
+                       double jitter, double* mean_out, double* var_out, double* samples_out) {
+    GP_TRY(vgp_check(h, m, vg, X, Y, N));
+    if (!u || !Xs || !Z || !samples_out || M < 1 || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_sample_vgp: not available in reflection mode (the observed rows X, Y of the dense model; "
+                       "gpimhip_set_reflection(h, 0, ...))");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_vgp_impl(h, m, vg, X, Y, N, u, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
+}
+
+int gpimhip_sample_vgp_blocks(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* G,
+                              const int32_t* shape, int32_t mask, const double* twoc, const double* Y, const double* u,
+                              const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
+                              double* samples_out) {
+    if (!shape || !twoc) return GPIMHIP_E_BADARG;
+    GP_TRY(vgp_check(h, m, vg, G, Y, 1));
+    if (!u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
+    if (jitter > 1.0) {
+        gpim_set_error("gpimhip_sample_vgp_blocks: needs 0 < jitter <= 1 (block units: the latent blocks have unit noise)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_sample_vgp_blocks: not available in reflection mode (the grid G and the rows Y of the dense "
+                       "model; gpimhip_set_reflection(h, 0, ...))");
+        return GPIMHIP_E_BADARG;
+    }
+    PwGrid gd;
+    const int64_t M = pw_grid(m, shape, mask, &gd);
+    if (M < 1) return GPIMHIP_E_BADARG;
+    if (!mask || (mask >> m->dim)) {
+        gpim_set_error("gpimhip_sample_vgp_blocks: needs at least one reflected axis of the grid");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_vgp_blocks_impl(h, m, vg, gd, twoc, G, M, Y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
 }
 
 int gpimhip_sample_border(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,

@@ -9,6 +9,7 @@
 //   vgp_kbeta_kernel     (K beta_t)_i for all t (K regenerated, variance 1): the bilinear forms beta_t^T K beta_t'
 //   vgp_finalize_kernel  loss, gradient (no eigenvector derivatives), chain rule to u, Adam step, history row
 //   vgp_combine_kernel   the T x T mix of the blocks' posterior mean / variance
+//   vgp_sample_mix_kernel  the same mix for joint draws: the T latent blocks' draws into S x M x T
 // Reflection mode (gpimhip_set_reflection): on a complete grid each block A_t splits further into the
 // 2^r reflection blocks A_{t,b} = lambda_t K_b + I of engine.hip's symmetry-reduced model; problem t 2^r + b of the batch is
 // task t with sign pattern b, and each task's sums run over its 2^r consecutive problems:
@@ -599,8 +600,8 @@ __global__ __launch_bounds__(256) void vgp_combine_kernel(int T, int64_t M, cons
     double mb[VGP_MAXT], vb[VGP_MAXT];
 #pragma unroll
     for (int t = 0; t < VGP_MAXT; ++t) {
-        mb[t] = t < T ? mblk[(int64_t)t * M + j] : 0.0;
-        vb[t] = t < T ? vblk[(int64_t)t * M + j] : 0.0;
+        mb[t] = (t < T && mean_out) ? mblk[(int64_t)t * M + j] : 0.0;
+        vb[t] = (t < T && var_out) ? vblk[(int64_t)t * M + j] : 0.0;
     }
     for (int a = 0; a < T; ++a) {
         double mu = 0.0, v = 0.0;
@@ -611,9 +612,48 @@ __global__ __launch_bounds__(256) void vgp_combine_kernel(int T, int64_t M, cons
                 mu = fma(q, mb[t], mu);
                 v = fma(q * q, vb[t], v);
             }
-        mean_out[j * T + a] = st->mu[a] + st->sqs[a] * mu;
-        var_out[j * T + a] = st->s[a] * v;
+        if (mean_out) mean_out[j * T + a] = st->mu[a] + st->sqs[a] * mu;
+        if (var_out) var_out[j * T + a] = st->s[a] * v;
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// vgp_sample_mix_kernel: out[s][i][a] = mu_a + s_a^1/2 sum_t Q_at H[t][s][i].  HBM-bound: every entry
+// of H is read once and every entry of out written once, 16 T S M bytes.  One workgroup = VM_PTS consecutive points of one
+// draw: lane i reads its T latent values along i (coalesced, 512 bytes per wave and block), forms the T outputs with t
+// ascending (the bits depend on the inputs alone) and parks them in LDS as tile[a][i]; the workgroup then writes its
+// VM_PTS * T contiguous doubles of `out` lane by lane -- without the LDS pass a lane would store T doubles of its own, T * 8
+// bytes apart from its neighbour's.  Row stride VM_PTS + 1 doubles: the transposed read walks a * (VM_PTS + 1) + i with a
+// fastest, two banks apart per lane.
+// ------------------------------------------------------------------------------------------
+#define VM_PTS 256
+__global__ __launch_bounds__(256) void vgp_sample_mix_kernel(int T, int S, int64_t M, const VgpDev* __restrict__ st,
+                                                             const double* __restrict__ H, double* __restrict__ out) {
+    __shared__ double tile[VGP_MAXT][VM_PTS + 1];
+    __shared__ double qs[VGP_MAXT][VGP_MAXT], mus[VGP_MAXT], sq[VGP_MAXT];
+    const int tid = threadIdx.x, s = blockIdx.y;
+    const int64_t i0 = (int64_t)blockIdx.x * VM_PTS, i = i0 + tid;
+    if (tid < T * T) qs[tid / T][tid % T] = st->Q[(tid / T) * VGP_MAXT + tid % T];
+    if (tid < T) {
+        mus[tid] = st->mu[tid];
+        sq[tid] = st->sqs[tid];
+    }
+    double hv[VGP_MAXT];
+#pragma unroll
+    for (int t = 0; t < VGP_MAXT; ++t) hv[t] = (t < T && i < M) ? H[((int64_t)t * S + s) * M + i] : 0.0;
+    __syncthreads();
+    for (int a = 0; a < T; ++a) {
+        double acc = 0.0;
+#pragma unroll
+        for (int t = 0; t < VGP_MAXT; ++t)
+            if (t < T) acc = fma(qs[a][t], hv[t], acc);
+        tile[a][tid] = mus[a] + sq[a] * acc;
+    }
+    __syncthreads();
+    const int64_t left = M - i0;
+    const int cnt = (int)(left < VM_PTS ? left : VM_PTS) * T;
+    double* dst = out + ((int64_t)s * M + i0) * T;
+    for (int e = tid; e < cnt; e += 256) dst[e] = tile[e % T][e / T];
 }
 
 // reflection mode, one chunk of test points: the blocks' posterior summed per task (mean_t = sum_b k*_{t,b}^T beta_{t,b},
@@ -664,6 +704,23 @@ __global__ __launch_bounds__(256) void vgp_group_combine_kernel(int T, int nrep,
 // ------------------------------------------------------------------------------------------
 int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep) {
     hipLaunchKernelGGL(vgp_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, *vg, u, st, h->theta, nrep);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_setup_to(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st,
+                        ThetaDev* theta) {
+    hipLaunchKernelGGL(vgp_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, *vg, u, st, theta, 1);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_project_to(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st, double* z) {
+    hipLaunchKernelGGL(vgp_project_kernel, dim3((unsigned)((N + 255) / 256), T), dim3(256), 0, h->stream, Y, N, N, T, st, z);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_vgp_sample_mix(gpimhip_ctx* h, int T, int S, int64_t M, const VgpDev* st, const double* H, double* out) {
+    hipLaunchKernelGGL(vgp_sample_mix_kernel, dim3((unsigned)((M + VM_PTS - 1) / VM_PTS), S), dim3(256), 0, h->stream, T, S, M, st,
+                       H, out);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

@@ -45,6 +45,11 @@ struct VgpDev {
 // pattern b); launch_vgp_finalize takes 0 for the dense model
 int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep);
 int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st);
+// the same two launches with caller-owned results (the multi-output draws, api.hip: sample_vgp_impl): the T blocks' theta
+// into `theta` (T entries) instead of h->theta, and z as plain T x N rows (no padding) instead of h->ypad
+int launch_vgp_setup_to(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st,
+                        ThetaDev* theta);
+int launch_vgp_project_to(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st, double* z);
 // uo / border_scal / radd: non-null with a border (BorderWs::uo, scal, rsq)
 int launch_vgp_project_refl(gpimhip_ctx* h, const double* Y, int64_t N, int T, int nrep, const double* uo, const VgpDev* st);
 int launch_vgp_kbeta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, int T, double* kb);
@@ -52,7 +57,11 @@ int launch_vgp_kbeta_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double
 int launch_vgp_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, int64_t N, const double* kb,
                         const VgpDev* st, double* u, double* adam_m, double* adam_v, int do_adam, AdamStep ast,
                         double* loss_out, double* grad_out, FinalizeIter fi, int nrep, const double* border_scal = nullptr);
+// (mean_out or var_out may be null: that half is neither read nor written)
 int launch_vgp_combine(gpimhip_ctx* h, int T, int64_t M, const VgpDev* st, const double* mblk, const double* vblk,
                        double* mean_out, double* var_out);
+// out[s][i][a] = mu_a + s_a^1/2 sum_t Q_at H[t][s][i]: the latent blocks' draws H (T x S x M) mixed into joint draws of the
+// T outputs (S x M x T, task fastest); DESIGN.md section 19
+int launch_vgp_sample_mix(gpimhip_ctx* h, int T, int S, int64_t M, const VgpDev* st, const double* H, double* out);
 int launch_vgp_group_combine(gpimhip_ctx* h, int T, int nrep, int nb, int64_t ldp, int64_t m0, int64_t mcount, const VgpDev* st,
                              double* mean_out, double* var_out, const double* radd = nullptr, int64_t ldr = 0);

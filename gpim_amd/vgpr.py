@@ -310,3 +310,118 @@ class vreconstructor(HostDriver):
     def predict(self, Xtest=None, **kwargs):
         """Exact predictive mean and standard deviation at Xtest, shape ``Xtest.shape[1:] + (T,)`` each."""
         return self._predict_host(Xtest, kwargs, self._posterior)[:2]
+
+    # ------------------------------------------------------------------ joint posterior draws
+    _SAMPLE_BUILT = ("vreconstructor.sample: method=%r is not built for the multi-output model; built are 'joint' (any test "
+                     "points) and 'blocks' (a fully observed grid with a symmetric axis)")
+
+    def _observed(self):
+        """(X (N, d), Y (T, N) task-major) device tensors of the observed rows -- all the posterior depends on besides u.
+        The dense solver holds them already; the others upload them at the first draw and keep them."""
+        if self._blocks is None:
+            return self._Xd, self._Yd
+        c = getattr(self, "_obs_d", None)
+        if c is None:
+            c = self._obs_d = (self.X.to(self._dev, _F64).contiguous(), self.y.to(self._dev, _F64).t().contiguous())
+        return c
+
+    def sample(self, n_samples=1, Xtest=None, noiseless=False, seed=None, z=None, jitter=None, method='joint'):
+        """Joint draws of all T outputs from the posterior on the test grid: ndarray of shape ``(n_samples,) + grid shape +
+        (T,)``, each slice one plausible stack of outputs that vary together as the posterior says.  The block reduction
+        makes the posterior of the T whitened, rotated latent functions independent, so a draw is T single-output draws
+        mixed back; every ``rec.solver`` draws from the same posterior of the observed rows.
+        ``Xtest`` as in ``predict``; the test grid must be finite.  ``noiseless=False`` includes each task's noise.
+
+        ``jitter`` (default 1e-5, > 0) is RELATIVE TO EACH TASK'S NOISE: the covariance of task a's draws carries
+        ``noise[a] * jitter`` on its diagonal (the latent blocks have unit noise, and the jitter is theirs).
+
+        ``z``: optional standard normals of shape ``(T, n_samples, W)``, array or device tensor, used as is (the result is
+        then a pure function of the model); block t's slice is what the single-output draw of latent block t takes.  When
+        absent it is drawn as ``torch.randn((T, n_samples, W), dtype=torch.float64, device=dev, generator=g)`` with
+        ``g = torch.Generator(dev).manual_seed(seed)`` (``seed is None``: the global device generator).
+
+        ``method='joint'``: one factorisation of order N + M per latent block, any test points; W = M.
+        ``method='blocks'``: for data that fill a product grid (no NaN) with at least one symmetric axis, drawn on that
+        grid (``Xtest`` None, the stored grid, or equal to it) through its reflection blocks: 2 x 2^r factorisations of
+        order M / 2^r per latent block; W = 2 M if noiseless, else 3 M; jitter <= 1.
+        ``'pathwise'`` and ``'border'`` are not built for this model (NotImplementedError)."""
+        if method in ("pathwise", "border"):
+            raise NotImplementedError(self._SAMPLE_BUILT % (method,))
+        if method not in ("joint", "blocks"):
+            raise ValueError("method must be 'joint' or 'blocks' ('pathwise' and 'border' are not built for the multi-output "
+                             "model); got %r" % (method,))
+        S, T = int(n_samples), self.num_tasks
+        if S < 1:
+            raise ValueError("n_samples must be at least 1; got %r" % (n_samples,))
+        jitter = 1e-5 if jitter is None else float(jitter)
+        if not (jitter > 0.0) or (method == "blocks" and jitter > 1.0):
+            raise ValueError("sample: jitter is relative to each task's noise and must be > 0%s; got %g"
+                             % (" and <= 1 for method='blocks'" if method == "blocks" else "", jitter))
+        # the test grid, resolved without storing it: a refused call leaves the model as it was
+        if Xtest is not None:
+            Xs_h, shape = gprutils.prepare_test_data(Xtest), tuple(Xtest.shape[1:])
+        elif self.Xtest is not None:
+            Xs_h, shape = self.Xtest, tuple(self.fulldims[:-1])
+        else:
+            Xs_h, shape = self.X, (self.X.shape[0],)
+        if not bool(torch.isfinite(Xs_h).all()):
+            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+        M, N, d = Xs_h.shape[0], self.X.shape[0], self.X.shape[1]
+        P = None
+        if method == "blocks":
+            if len(shape) != d or int(np.prod(shape)) != M:
+                raise NotImplementedError("method='blocks' needs a product grid as its test grid: %d test rows do not fill a "
+                                          "grid of shape %s in %d dimensions" % (M, shape, d))
+            P = gprutils.pathwise_grid(Xs_h.numpy().T.reshape((d,) + shape), self.X.numpy())     # NotImplementedError, with the reason
+            if N != M:
+                first = int(np.setdiff1d(np.arange(M), P["idx"])[0])
+                raise NotImplementedError("method='blocks' needs an observation of all outputs on every point of the test grid "
+                                          "(a complete stack, and the test grid must be the training grid): grid point %s has "
+                                          "none (%d observed rows, %d grid points)"
+                                          % (tuple(int(v) for v in np.unravel_index(first, shape)), N, M))
+            W = 2 * M + (0 if noiseless else M)
+        else:
+            W = M
+        if z is None:
+            g = None if seed is None else torch.Generator(self._dev).manual_seed(int(seed))
+            z_d = torch.randn((T, S, W), dtype=_F64, device=self._dev, generator=g)
+        else:
+            z_d = (z if torch.is_tensor(z) else torch.from_numpy(np.asarray(z))).to(self._dev, _F64).contiguous()
+            if tuple(z_d.shape) != (T, S, W):
+                raise ValueError("z must have shape (T, n_samples, W) = (%d, %d, %d) for method=%r (M = %d test points); got %s"
+                                 % (T, S, W, method, M, tuple(z_d.shape)))
+        # the one large allocation of the call (kept by the handle, grow-only): a single-output call's at the same sizes
+        if method == "joint":
+            order = -(-(N + M) // 128) * 128
+            what = "the joint covariance of %d observed rows and %d test points" % (N, M)
+        else:
+            nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
+            order = -(-nq // 128) * 128
+            what = "a reflection block of %d points" % nq
+        need = order * (order + (16 if order >= 1024 else 0)) * 8
+        key = "_sample_bytes_" + method
+        if need > getattr(self, key, 0):
+            free = torch.cuda.mem_get_info(self._dev)[0]
+            if need > free:
+                raise MemoryError("sample: %s needs %.2f GiB of device memory, %.2f GiB are free"
+                                  % (what, need / 2.0 ** 30, free / 2.0 ** 30))
+        self._resolve_test_grid(Xtest)
+        Xo, Yo = self._observed()
+        Xs = Xs_h.to(self._dev, _F64).contiguous()
+        out = torch.empty((S, M, T), dtype=_F64, device=self._dev)
+        lib, head = self._handle.lib, (self._handle.h, ctypes.byref(self._mstruct), ctypes.byref(self._vstruct))
+        if method == "joint":
+            rc = lib.gpimhip_sample_vgp(*head, _lib.ptr(Xo), _lib.ptr(Yo), N, _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(z_d), S,
+                                        int(bool(noiseless)), jitter, None, None, _lib.ptr(out))
+        else:
+            Yg = Yo
+            if not np.array_equal(P["idx"], np.arange(M)):      # the observed rows in grid order
+                Yg = torch.empty_like(Yo)
+                Yg[:, torch.from_numpy(P["idx"]).to(self._dev)] = Yo
+            cshape = (ctypes.c_int32 * d)(*[int(n) for n in P["shape"]])
+            twoc = (ctypes.c_double * 4)(*P["twoc"])
+            rc = lib.gpimhip_sample_vgp_blocks(*head, _lib.ptr(Xs), cshape, int(P["mask"]), twoc, _lib.ptr(Yg), _lib.ptr(self._u),
+                                               _lib.ptr(z_d), S, int(bool(noiseless)), jitter, None, _lib.ptr(out))
+        _lib.check(rc)
+        setattr(self, key, max(need, getattr(self, key, 0)))
+        return out.cpu().numpy().reshape((S,) + shape + (T,))

@@ -311,6 +311,41 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
                         const double* Y, int64_t N, const double* u, const double* Xs, int64_t M, double* mean_out,
                         double* var_out);
 
+/* Joint posterior draws of the T outputs (gpim_amd extension: vreconstructor.sample; the reference's only use of draws is
+ * the Monte-Carlo estimate of vgpr.py:218-224).  The block reduction diagonalises the posterior as well: the latent
+ * functions h_t = sum_a Q_at s_a^-1/2 f_a are independent GPs with kernel lambda_t K, unit noise and targets z_t, so the
+ * call is T single-output draws -- gpimhip_sample_exact, or gpimhip_sample_blocks on a fully observed grid -- run one after
+ * the other through the one matrix of those entries, and one mix f_a = mu_a + s_a^1/2 sum_t Q_at h_t.  DESIGN.md section 19.
+ *   X (N x d), Y (T x N, task-major), u      the observed rows and the raw vector, as gpimhip_predict_vgp on the dense model
+ *   Z            block-major standard normals (device): (T, S, M) for gpimhip_sample_vgp, (T, S, 2 M [+ M unless noiseless])
+ *                for gpimhip_sample_vgp_blocks; block t's slice means what the single-output entry gives it
+ *   jitter       > 0, in block units, i.e. relative to each task's noise: task a's draws carry s_a * jitter on the diagonal
+ *                of their covariance; gpimhip_sample_vgp_blocks also needs jitter <= 1 (section 17's d <= s with s = 1)
+ *   noiseless    0: the draws include the observation noise s_a of each task (the blocks' unit noise, mixed)
+ *   mean_out, var_out   M x T each (task fastest) or NULL: the posterior of gpimhip_predict_vgp (noise included, jitter
+ *                excluded); gpimhip_sample_vgp_blocks has no var_out
+ *   samples_out  S x M x T (task fastest)
+ *   G, shape, mask, twoc   the fully observed grid as for gpimhip_sample_blocks; Y (T x M) in grid order
+ * The training workspace of the handle is not touched; the state of the reduction, the blocks' draws (T S M doubles) and
+ * moments are grow-only and counted by gpimhip_workspace_bytes.  Double-precision handles outside reflection mode only; NULL
+ * arguments, S < 1, S > 65534, jitter <= 0, more than GPIMHIP_VGP_MAX_TASKS tasks -> GPIMHIP_E_BADARG.  Synchronises once,
+ * at the end (NOT_PD of any block's factorisation through one status word; the handle stays usable).
+ * Stage timers: those of the single-output entry summed over the T blocks, and 6 = the mix kernel; gpimhip_sample_vgp also
+ * records 2 = setup and projection, 3 = the mix of mean and variance. */
+int gpimhip_sample_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg,
+                       const double* X, const double* Y, int64_t N, const double* u,
+                       const double* Xs, int64_t M,
+                       const double* Z, int32_t S,
+                       int32_t noiseless, double jitter,
+                       double* mean_out, double* var_out,
+                       double* samples_out);
+int gpimhip_sample_vgp_blocks(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg,
+                              const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                              const double* Y, const double* u,
+                              const double* Z, int32_t S,
+                              int32_t noiseless, double jitter,
+                              double* mean_out, double* samples_out);
+
 /* ---- exact GP with the spectral-mixture kernel ---------------------------------------------
  * Replaces GPyTorch's ExactGP with a SpectralMixtureKernel, a ConstantMean and a GaussianLikelihood as the reference's
  * skreconstructor(kernel='Spectral') builds it (gpim/gpreg/skgpr.py:122-123: no SKI; gpim/kernels/gpytorch_kernels.py:65-70).
