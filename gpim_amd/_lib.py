@@ -188,6 +188,12 @@ _PROTOS = {
                                       ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
     "gpimhip_predict_sm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
                                           ctypes.c_int64, c_dp, c_dp]),
+    "gpimhip_sm_nll_grad_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, c_dp, ctypes.c_int64,
+                                                   ctypes.c_int32, c_dp, c_dp, c_dp]),
+    "gpimhip_fit_sm_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, c_dp, ctypes.c_int64,
+                                              ctypes.c_int32, c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
+    "gpimhip_predict_sm_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, c_dp, ctypes.c_int64,
+                                                  ctypes.c_int32, c_dp, c_dp, ctypes.c_int64, c_dp, c_dp]),
 }
 EXPORTS = tuple(_PROTOS)
 

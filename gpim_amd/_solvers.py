@@ -7,11 +7,13 @@ _solvers.py -- the host layer between the reconstructors and the C ABI (include/
     ``_lib.reflection``.
   * ``Dense`` / ``Sparse`` / ``Kron`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
     fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out), each returning the
-    library's status.  ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
+    library's status.  ``SpectralBlocks``: the reflection / border path of ``smreconstructor`` (one shared parameter vector).
+    ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
     through the library handle) and reads ``o._Xd`` / ``o._yd`` / ``o._u`` as they are at the time of the call
     (boptimizer swaps the training data between trainings).  A new path is one more class here and one more arm where
     ``reconstructor.__init__`` builds ``self._solver``.
 """
+import contextlib
 import ctypes
 import time
 import warnings
@@ -117,6 +119,7 @@ class DeviceBlocks:
         wts = S["wts"] if tasks is None or S["wts"] is None else np.tile(S["wts"], (tasks, 1))
         self.wts = None if wts is None else self._up(wts)
         self.border = None
+        self.ones = None                                # (B, Nq) basis change of the constant mean, uploaded by SpectralBlocks
 
     def _up(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, _F64).contiguous()
@@ -264,16 +267,23 @@ class Reflection(Dense):
     def __init__(self, S, border=False):
         self.S, self.border, self.blocks, self.perm_d = S, border, None, None
 
-    def _call(self, o, fn, *args, var_count=0):
-        """fn(h, model, Xq, 0, ys, Nq, B, u_b, *args) with the handle in reflection mode; the B parameter slots hold one
-        vector, and the first comes back into ``o._u``.  The blocks go to the device on first use."""
+    @contextlib.contextmanager
+    def _mode(self, o, var_count=0):
+        """The handle in reflection mode (with the border when there is one) for the body of the ``with``; yields the device
+        side of the blocks, which go to the device on first use."""
         if self.blocks is None:
             self.blocks = DeviceBlocks(self.S, o._dev)
         D = self.blocks
-        u_b = o._u.repeat(D.B).contiguous()
         if self.border and D.border is None:
             D.upload_border()
         with _lib.reflection(o._handle, D, var_count, D.border):
+            yield D
+
+    def _call(self, o, fn, *args, var_count=0):
+        """fn(h, model, Xq, 0, ys, Nq, B, u_b, *args) with the handle in reflection mode; the B parameter slots hold one
+        vector, and the first comes back into ``o._u``."""
+        with self._mode(o, var_count) as D:
+            u_b = o._u.repeat(D.B).contiguous()
             rc = fn(*_head(o), ptr(D.Xq), 0, ptr(D.ys), D.Xq.shape[0], D.B, ptr(u_b), *args)
         o._u.copy_(u_b[:o._u.numel()])
         return rc
@@ -327,3 +337,27 @@ class Reflection(Dense):
             return Dense.nll_grad(self, o, out)
         # the coupled blocks with the border: one evaluation of what a training iteration computes
         return self._call(o, o._handle.lib.gpimhip_nll_grad_batched, *_loss_grad(out))
+
+
+class SpectralBlocks(Reflection):
+    """The spectral-mixture GP of ``smreconstructor`` on the reflection blocks of a complete grid, or of a completed one with
+    a border (csrc/sm.hip: sm_kmat_refl_kernel, sm_grad_refl_kernel).  The blocks share ONE parameter
+    vector ``o._u``; S["ones"] = U 1 (U 1_o with a border) carries the constant mean into the blocks.  ``predict_grid`` is
+    Reflection's: on the training grid of a complete model the variance is computed on the fundamental domain."""
+
+    def _call(self, o, fn, *args, var_count=0):
+        """fn(h, sm, Xq, ys, ones, Nq, B, *args) with the handle in reflection mode."""
+        with self._mode(o, var_count) as D:
+            if D.ones is None:
+                D.ones = D._up(self.S["ones"])
+            return fn(o._handle.h, ctypes.byref(o._sstruct), ptr(D.Xq), ptr(D.ys), ptr(D.ones), D.Xq.shape[0], D.B, *args)
+
+    def fit(self, o, lr, T, hist, loss):
+        return self._call(o, o._handle.lib.gpimhip_fit_sm_batched, ptr(o._u), lr, T, ptr(hist), ptr(loss))
+
+    def predict(self, o, Xs, mean, var, var_count=0):
+        return self._call(o, o._handle.lib.gpimhip_predict_sm_batched, ptr(o._u), ptr(Xs), Xs.shape[0], ptr(mean), ptr(var),
+                          var_count=var_count)
+
+    def nll_grad(self, o, u, loss, grad):
+        return self._call(o, o._handle.lib.gpimhip_sm_nll_grad_batched, ptr(u), ptr(loss), ptr(grad))

@@ -1930,15 +1930,23 @@ static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t m
     *out = w;
     return GPIMHIP_OK;
 }
-static int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N) {
+// B = 0: a dense entry point (no reflection mode); B > 0: the blocks of a handle in reflection mode
+static int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B = 0) {
     if (!h || !sm || !X || N < 1) return GPIMHIP_E_BADARG;
     FP64_ONLY(h);
     if (sm->dim < 1 || sm->dim > GPIMHIP_MAX_DIM || sm->mixtures < 1 || sm->mixtures > GPIMHIP_SM_MAX_MIXTURES) {
         gpim_set_error("the spectral-mixture kernel takes 1 .. 4 dimensions and 1 .. 16 mixtures");
         return GPIMHIP_E_BADARG;
     }
-    if (h->refl.mask) {
-        gpim_set_error("the spectral-mixture kernel needs a handle without reflection blocks (gpimhip_set_reflection(h, 0, ...))");
+    if (h->refl.mask && B == 0) {
+        gpim_set_error("the spectral-mixture kernel on a handle in reflection mode runs through gpimhip_sm_nll_grad_batched / "
+                       "gpimhip_fit_sm_batched / gpimhip_predict_sm_batched (the dense entry points need gpimhip_set_reflection(h, 0, ...))");
+        return GPIMHIP_E_BADARG;
+    }
+    if (B > 0 && (!h->refl.mask || (h->refl.mask >> sm->dim) || B != (1 << __builtin_popcount(h->refl.mask)) ||
+                  h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw || h->refl.n_total < 1)) {
+        gpim_set_error("the spectral-mixture blocks need a handle in reflection mode (gpimhip_set_reflection) with all B = 2^r "
+                       "blocks of the reflected axes on it (unsharded), the axes within the kernel's dimensions");
         return GPIMHIP_E_BADARG;
     }
     return GPIMHIP_OK;
@@ -1971,15 +1979,127 @@ static int sm_iter(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double
     return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi);
 }
 
+// ---- the reflection blocks of a grid: the handle is in reflection mode, the batch is its B = 2^r
+// blocks on the N points X of the fundamental domain, ys / ones (B x N) the targets and U 1 (U 1_o with a border) in the
+// adapted basis, ONE parameter vector.  The engine's batched factor + inverse, solves and K^-1 product; with a border
+// (gpimhip_set_border) the kernel-agnostic border stage of border.hip between the inverse and the contraction.
+static int sm_begin_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, int B, SmWs** w) {
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = B;
+    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(ws_ensure_padded(h, N));
+    if (border_on(h)) GP_TRY(border_ensure(h));
+    const int64_t nb = h->np / NB;
+    return sm_ws(h, sm, h->np, 0, B * nb * (nb + 1) / 2, w);
+}
+static int sm_factor_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* ys, const double* ones,
+                          int64_t N, const double* u) {
+    const int64_t np = h->np, ld = h->ld;
+    GP_TRY(launch_sm_setup_refl(h, sm, u, X, N, np, w->csx, ys, ones, h->ypad, w->st, h->theta));
+    { StageTimer t(h, 4); GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, np, nullptr, N, nullptr, np, w->st, h->A, ld, np * ld, np, np, 1, 1, 1.0)); }
+    GP_TRY(launch_potrf_inv(h, h->A, h->Tm, np, ld, h->info, rag_of(N, np)));
+    return solve_vectors(h, nullptr, X, 0, N, false);
+}
+static int sm_iter_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* ys, const double* ones,
+                        int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
+    const int64_t np = h->np;
+    GP_TRY(sm_factor_refl(h, sm, w, X, ys, ones, N, u));
+    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
+    const bool bd = border_on(h);
+    if (bd) GP_TRY(border_iter(h, N, true));
+    { StageTimer t(h, 5); GP_TRY(launch_sm_grad_refl(h, sm, h->B, h->ld, X, N, w->csx, np, h->alpha, w->st, w->part, w->sums)); }
+    const AdamStep st = adam_step_init();
+    return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi, ones,
+                              h->refl.n_total, bd ? bws(h)->scal : nullptr);
+}
+// posterior of the blocks at M test points (predict_cols with the blocks' cross-covariance): mean = c + sum_b K*_b^T alpha_b,
+// var = sum w + noise - sum_b |L_b^-1 K*_b|^2 (+ |sum_b Y_b^T k*_b|^2 with a border)
+static int sm_predict_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, int64_t N, int B, const double* u,
+                           const double* Xs, int64_t M, double* mean_out, double* var_out) {
+    const int64_t np = h->np;
+    const int nb = (int)(np / NB);
+    int64_t mc = pad_to(M, NB);
+    mc = std::min(mc, std::max<int64_t>(NB, ((int64_t)1 << 27) / np / B / NB * NB));
+    GP_TRY(ws_ensure_predict(h, np, mc));
+    GP_TRY(sm_ws(h, sm, np, mc, (int64_t)B * nb * (nb + 1) / 2, &w));
+    const int64_t mcap = h->ks_cols, kld = mcap + 16;
+    const bool bd = border_on(h);
+    if (bd) GP_TRY(border_ensure_r(h, mcap));
+    for (int64_t m0 = 0; m0 < M; m0 += mc) {
+        const int64_t cnt = std::min(mc, M - m0);
+        const int64_t cpad = pad_to(cnt, NB);
+        const double* Zc = Xs + m0 * sm->dim;
+        GP_TRY(launch_sm_setup_refl(h, sm, u, Zc, cnt, cpad, w->csz, nullptr, nullptr, nullptr, nullptr, nullptr));
+        GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, np, Zc, cnt, w->csz, cpad, w->st, h->Ks, kld, np * kld, np, cpad, 0, 0,
+                                   1.0 / sqrt((double)B)));
+        GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
+        // (complete grids: the variance is invariant under the reflections -- ReflArgs::var_count, as predict_cols)
+        const int64_t nvar = (h->refl.var_count > 0 && !bd) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
+        const double* radd = nullptr;
+        if (nvar > 0) {
+            GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
+            if (nvar < cnt) g.cj_max = (int)((nvar + NB - 1) / NB);
+            g.sB = np * kld;
+            g.colpart = h->colpart;
+            g.ld_colpart = mcap;
+            g.sColpart = (int64_t)nb * mcap;
+            g.ntiles = (int)h->pred_ntiles;
+            g.chunk = deal_chunk(g.ntiles);
+            g.rag = rag_of(N, np);
+            { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
+            if (bd) {       // R = sum_b Y_b^T K*_b over the stacked blocks (predict_cols)
+                BorderWs* bw = bws(h);
+                bw->sub->stream = h->stream;
+                const int64_t brows = (int64_t)B * np;
+                GemmArgs gr = gemm_args(bw->Y, bw->mp, h->Ks, kld, bw->R, bw->r_cols, 1.0, 0.0, nullptr, 0, 0);
+                gr.sA = brows * bw->mp;
+                gr.sB = brows * kld;
+                gr.sC = bw->mp * bw->r_cols;
+                gr.rect_rows = (int)(bw->mp / NB);
+                gr.rect_cols = (int)(cpad / NB);
+                gr.ntiles = gr.rect_rows * gr.rect_cols;
+                gr.kfix0 = 0;
+                gr.kfix1 = (int)(brows / NB);
+                gr.chunk = deal_chunk(gr.ntiles);
+                GP_TRY(launch_gemm(bw->sub, true, true, EPI_STORE, gr));
+                GP_TRY(launch_border_colsumsq(h, bw, cnt));
+                radd = bw->rsq;
+            }
+        }
+        GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
+        GP_TRY(launch_sm_addc(h, mean_out + m0, cnt, w->st));
+    }
+    return GPIMHIP_OK;
+}
+
 extern "C" {
 
 int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* Z, int64_t M,
                     const double* u, double* out, int64_t ld) {
-    GP_TRY(sm_check(h, sm, X, N));
+    const int B = (h && h->refl.mask) ? 1 << __builtin_popcount(h->refl.mask) : 0;
+    GP_TRY(sm_check(h, sm, X, N, B));
     const bool sym = (Z == nullptr);
     const int64_t Mv = sym ? N : M;
     if (!u || !out || Mv < 1 || ld < Mv) return GPIMHIP_E_BADARG;
     HIP_TRY(hipSetDevice(h->device));
+    if (B) {       // reflection mode: the B blocks K_s (or K_s(X, Z) / sqrt(B)) stacked, B N rows
+        h->nbatch = B;
+        const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
+        SmWs* w = nullptr;
+        GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
+        GP_TRY(ws_ensure_predict(h, rp, cp));
+        const int64_t kld = h->ks_cols + 16;
+        GP_TRY(launch_sm_setup_refl(h, sm, u, X, N, rp, w->csx, nullptr, nullptr, nullptr, w->st, nullptr));
+        if (!sym) GP_TRY(launch_sm_setup_refl(h, sm, u, Z, M, cp, w->csz, nullptr, nullptr, nullptr, nullptr, nullptr));
+        GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, rp, Z, Mv, w->csz, cp, w->st, h->Ks, kld, rp * kld, rp, cp, sym ? 1 : 0, 0,
+                                   sym ? 1.0 : 1.0 / sqrt((double)B)));
+        for (int b = 0; b < B; ++b)
+            HIP_TRY(hipMemcpy2DAsync(out + (int64_t)b * N * ld, (size_t)ld * sizeof(double), h->Ks + (int64_t)b * rp * kld,
+                                     (size_t)kld * sizeof(double), (size_t)Mv * sizeof(double), (size_t)N,
+                                     hipMemcpyDeviceToDevice, h->stream));
+        h->nbatch = 1;
+        return GPIMHIP_OK;
+    }
     h->nbatch = 1;
     const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
     SmWs* w = nullptr;
@@ -2019,6 +2139,53 @@ int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, co
     HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
     return run_fit_iterations(h, T, FIT_LOOP_DENSE, [&] { return sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi); });
+}
+
+int gpimhip_sm_nll_grad_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                                int64_t N, int32_t B, const double* u, double* loss_out, double* grad_out) {
+    if (B < 1) return GPIMHIP_E_BADARG;
+    GP_TRY(sm_check(h, sm, X, N, B));
+    if (!ys || !ones || !u) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
+    GP_TRY(sm_iter_refl(h, sm, w, X, ys, ones, N, const_cast<double*>(u), 0, loss_out, grad_out,
+                        FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
+    return finish_and_check(h);
+}
+
+int gpimhip_fit_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                           int64_t N, int32_t B, double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out) {
+    if (B < 1) return GPIMHIP_E_BADARG;
+    GP_TRY(sm_check(h, sm, X, N, B));
+    if (!ys || !ones || !u_inout || T < 0) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
+    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
+    h->fit_completed = T;
+    if (T == 0) return finish_and_check(h);
+    GP_TRY(upload_bc_table(h, lr, T));
+    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * SM_MAXP * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
+    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
+    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
+                              [&] { return sm_iter_refl(h, sm, w, X, ys, ones, N, u_inout, 1, nullptr, nullptr, fi); });
+}
+
+int gpimhip_predict_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                               int64_t N, int32_t B, const double* u, const double* Xs, int64_t M, double* mean_out,
+                               double* var_out) {
+    if (B < 1) return GPIMHIP_E_BADARG;
+    GP_TRY(sm_check(h, sm, X, N, B));
+    if (!ys || !ones || !u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
+    SmWs* w = nullptr;
+    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
+    GP_TRY(sm_factor_refl(h, sm, w, X, ys, ones, N, u));
+    if (border_on(h)) {       // the state a prediction through the border starts from (model_state_at_u)
+        GP_TRY(launch_lauum(h, h->A, h->B, h->np, h->ld, rag_of(N, h->np)));
+        GP_TRY(border_iter(h, N, false));
+    }
+    GP_TRY(sm_predict_refl(h, sm, w, X, N, B, u, Xs, M, mean_out, var_out));
+    return finish_and_check(h);
 }
 
 int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,

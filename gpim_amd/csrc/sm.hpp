@@ -38,5 +38,17 @@ int launch_sm_grad(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, i
                    const double* csx, int64_t ldx, const double* alpha, const SmDev* st, double* part, double* sums);
 int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const double* sums, const SmDev* st, double* u,
                        double* adam_m, double* adam_v, int do_adam, AdamStep ast, double* loss_out, double* grad_out,
-                       FinalizeIter fi);
+                       FinalizeIter fi, const double* ones = nullptr, int64_t n_total = 0, const double* border_scal = nullptr);
 int launch_sm_mean(gpimhip_ctx* h, const double* mtmp, int64_t n, const SmDev* st, double* mean_out);
+
+// reflection blocks (handle in reflection mode, h->nbatch = 2^r blocks on the fundamental domain):
+// phases of the centred coordinates, r_b = ys_b - c ones_b (ys, ones: B x n; ypad: B x ldc), the blocks K_s (out_bs apart)
+// or K_s(Xq, Z) * scale, the contraction with one record per (block, lower tile), and mean += c
+int launch_sm_setup_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, const double* P, int64_t n, int64_t ldc,
+                         double* cs, const double* ys, const double* ones, double* ypad, SmDev* st, ThetaDev* theta);
+int launch_sm_kmat_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* csx, int64_t ldx,
+                        const double* Z, int64_t M, const double* csz, int64_t ldz, const SmDev* st, double* out, int64_t ld,
+                        int64_t out_bs, int64_t rows_pad, int64_t cols_pad, int sym, int lower_only, double scale);
+int launch_sm_grad_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* Kinv, int64_t ld, const double* X, int64_t N,
+                        const double* csx, int64_t ldx, const double* alpha, const SmDev* st, double* part, double* sums);
+int launch_sm_addc(gpimhip_ctx* h, double* mean, int64_t n, const SmDev* st);

@@ -13,7 +13,8 @@ gprutils.reflection_blocks + csrc/engine.hip: kmat_refl_kernel) -- with the mode
 ``gpim_amd.reconstructor`` (zero mean, Uniform priors on variance and lengthscales).  Same constructor shape and return values as the reference class;
 numbers are those of ``reconstructor(..., structured=True)``, i.e. of the exact GP -- not bit-comparable
 with an SKI run.  ``kernel='Spectral'`` (GPyTorch's spectral-mixture kernel, for which the reference turns SKI off) returns
-the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse images included.  Incomplete grids (NaN in y)
+the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse images included; complete and nearly complete
+grids run there as reflection blocks too (``rec.solver``).  Incomplete grids (NaN in y)
 with the other kernels: the exact GP on the observed points, either as the reflection blocks of the completed grid with a
 border for the missing points (csrc/border.hip) or on the dense engine, whichever the flop model says is cheaper
 (``rec.solver``: 'border' or 'dense').

@@ -24,6 +24,11 @@ Readings and deliberate differences, in one place:
     the predictive variance.  This engine is exact in both.
   * ``num_batches``, ``max_root`` / ``maxroot``, ``grid_points_ratio``, ``ski`` and ``sparse`` are accepted and ignored;
     ``precision='single'`` raises NotImplementedError.
+  * Solver (``rec.solver``; ``solver='dense' | 'reflection' | 'border'`` forces one): the kernel is stationary and even in
+    every coordinate difference, so on a complete product grid with a symmetric axis the model runs as the 2^r reflection
+    blocks of N / 2^r points ('reflection'), and on a grid with few missing pixels as the same blocks plus a border
+    ('border', chosen by the flop model of gprutils.border_flops against skgpr.BORDER_FACTOR) -- the same model to
+    rounding.  Everything else is the dense exact GP on the observed points ('dense').
 """
 import ctypes
 
@@ -32,7 +37,7 @@ import torch
 
 from . import _lib
 from . import gprutils
-from ._solvers import HostDriver
+from ._solvers import HostDriver, SpectralBlocks
 
 _F64 = torch.float64
 
@@ -90,7 +95,8 @@ def initial_raw(X, y, Q=4, isotropic=False, seed=0):
 class smreconstructor(HostDriver):
     """``skreconstructor(X, y, Xtest, kernel='Spectral', ...)`` -- argument order and defaults of gpim/gpreg/skgpr.py:79-91.
     X: (c, *dims) grid coordinates (NaN rows dropped together with the NaN entries of y: sparse images are fine);
-    ``n_mixtures`` (default 4) and ``isotropic`` as in the reference.  ``lengthscale`` is not used by this kernel."""
+    ``n_mixtures`` (default 4) and ``isotropic`` as in the reference.  ``lengthscale`` is not used by this kernel.
+    ``solver=None | 'dense' | 'reflection' | 'border'`` forces a solver (module docstring); ``rec.solver`` reports it."""
 
     def __init__(self, X, y, Xtest=None, kernel='Spectral', lengthscale=None, ski=True, learning_rate=.1,
                  iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
@@ -118,6 +124,8 @@ class smreconstructor(HostDriver):
         self._sstruct = sm
         u = initial_raw(Xt.numpy(), yt.numpy(), self.num_mixtures, self.isotropic, seed)
         self._u = torch.from_numpy(u).to(self._dev)
+        S, self.solver = self._choose_solver(X, y, kwargs.get("solver"))
+        self._solver = None if S is None else SpectralBlocks(S, border=self.solver == "border")
         self._Xd = self.X.to(self._dev, _F64).contiguous()
         self._yd = self.y.to(self._dev, _F64).contiguous()
         self.iterations = iterations
@@ -128,6 +136,74 @@ class smreconstructor(HostDriver):
                             "noise": self.noise_all, "maxdim": max(self.fulldims)}
         self.verbose = verbose
 
+    # ------------------------------------------------------------------ solver choice (host only)
+    @staticmethod
+    def _reflection_blocks(X, y):
+        """The blocks dict of a complete product grid with a symmetric axis (gprutils.reflection_blocks_multi with one task:
+        ys (B, Nq) and ones = U 1), else None."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if np.isnan(y).any() or np.isnan(X).any() or X.shape[1:] != y.shape:
+            return None
+        try:
+            axes, _ = gprutils.grid_axes(X)
+            S = gprutils.reflection_blocks_multi(X, y[..., None], axes)
+        except (NotImplementedError, ValueError):
+            return None
+        S["ys"] = S["ys"][0]
+        return S
+
+    @staticmethod
+    def _border_blocks(X, y):
+        """The blocks dict of an incomplete grid that can be completed and has a symmetric axis (gprutils.border_blocks_multi
+        with one task: ys with 0 at the missing points, ones = U 1_o, n_total = the observations), else None."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if not np.isnan(y).any():
+            return None
+        try:
+            S = gprutils.border_blocks_multi(X, y[..., None])
+        except (NotImplementedError, ValueError):
+            return None
+        S["ys"] = S["ys"][0]
+        S["n_total"] = S["n_obs"]           # the loss is that of the observed points
+        return S
+
+    @classmethod
+    def _choose_solver(cls, X, y, forced=None):
+        """(blocks dict or None, 'dense' | 'reflection' | 'border'): 'reflection' on a complete product grid with at least one
+        symmetric axis; 'border' when the grid can be completed and the border's flop model is below skgpr.BORDER_FACTOR of
+        the dense model's; else 'dense' (scattered points, no symmetric axis, too many holes).  ``forced`` names a solver and
+        raises NotImplementedError when the data do not allow it."""
+        from .skgpr import BORDER_FACTOR
+        if forced not in (None, "dense", "reflection", "border"):
+            raise ValueError("skreconstructor(kernel='Spectral'): solver must be None, 'dense', 'reflection' or 'border' "
+                             "(got %r)" % (forced,))
+        if forced == "dense":
+            return None, "dense"
+        if forced == "reflection":
+            S = cls._reflection_blocks(X, y)
+            if S is None:
+                raise NotImplementedError("skreconstructor(kernel='Spectral'): solver='reflection' needs a complete product "
+                                          "grid (no NaN) with at least one symmetric axis")
+            return S, "reflection"
+        if forced == "border":
+            S = cls._border_blocks(X, y)
+            if S is None:
+                raise NotImplementedError("skreconstructor(kernel='Spectral'): solver='border' needs a product grid with "
+                                          "missing pixels (NaN in y and in the coordinates), an observation at every index of "
+                                          "every axis, and at least one symmetric axis")
+            return S, "border"
+        S = cls._reflection_blocks(X, y)
+        if S is not None:
+            return S, "reflection"
+        S = cls._border_blocks(X, y)
+        if S is not None:
+            f_border, f_dense = gprutils.border_flops(S["n_obs"] + len(S["miss"]), len(S["miss"]), len(S["dims"]))
+            if f_border < BORDER_FACTOR * f_dense:
+                return S, "border"
+        return None, "dense"
+
     # ------------------------------------------------------------------ parameters
     def _params(self):
         return constrained(self._u.cpu().numpy(), self.num_mixtures, self._D)
@@ -137,9 +213,12 @@ class smreconstructor(HostDriver):
         u = self._u if u is None else torch.as_tensor(np.asarray(u, dtype=np.float64)).to(self._dev).contiguous()
         loss = torch.empty(1, dtype=_F64, device=self._dev)
         grad = torch.empty(u.numel(), dtype=_F64, device=self._dev)
-        _lib.check(self._handle.lib.gpimhip_sm_nll_grad(
-            self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
-            _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
+        if self._solver is not None:
+            _lib.check(self._solver.nll_grad(self, u, loss, grad))
+        else:
+            _lib.check(self._handle.lib.gpimhip_sm_nll_grad(
+                self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
+                _lib.ptr(u), _lib.ptr(loss), _lib.ptr(grad)))
         return float(loss.item()), grad.cpu().numpy()
 
     # ------------------------------------------------------------------ training (HostDriver.train)
@@ -147,6 +226,8 @@ class smreconstructor(HostDriver):
         return raw_layout(self.num_mixtures, self._D)[1]
 
     def _fit(self, T, hist, loss):
+        if self._solver is not None:
+            return self._solver.fit(self, float(self.learning_rate), T, hist, loss)
         return self._handle.lib.gpimhip_fit_sm(
             self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
             _lib.ptr(self._u), float(self.learning_rate), T, _lib.ptr(hist), _lib.ptr(loss))
@@ -176,6 +257,10 @@ class smreconstructor(HostDriver):
         M = Xs.shape[0]
         mean = torch.empty(M, dtype=_F64, device=self._dev)
         var = torch.empty(M, dtype=_F64, device=self._dev)
+        if self._solver is not None:
+            self._Xtest_d = Xs          # (Reflection.predict_grid: the training grid itself takes the mirrored-variance path)
+            _lib.check(self._solver.predict_grid(self, mean, var))
+            return mean, var
         _lib.check(self._handle.lib.gpimhip_predict_sm(
             self._handle.h, ctypes.byref(self._sstruct), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
             _lib.ptr(self._u), _lib.ptr(Xs), M, _lib.ptr(mean), _lib.ptr(var)))

@@ -354,8 +354,8 @@ int gpimhip_sample_vgp_blocks(gpimhip_handle h, const gpimhip_model_t* m, const 
  *   w = softplus(r_w), m = softplus(r_m), s = softplus(r_s), noise = 1e-4 + softplus(r_n), mean: a constant c
  * Parameter vector (unconstrained, what Adam updates), P = 2 + Q (2 D + 1) doubles:
  *   u = [c | r_w (Q) | r_m (Q x D, row-major) | r_s (Q x D) | r_n]
- * loss = -log N(y | c 1, K) / N  (gpytorch ExactMarginalLogLikelihood).  Double-precision handles only; the handle must
- * not have reflection blocks.  Q > GPIMHIP_SM_MAX_MIXTURES or dim outside 1 .. GPIMHIP_MAX_DIM -> GPIMHIP_E_BADARG.
+ * loss = -log N(y | c 1, K) / N  (gpytorch ExactMarginalLogLikelihood).  Double-precision handles only; a handle in
+ * reflection mode runs the _batched entries below.  Q > GPIMHIP_SM_MAX_MIXTURES or dim outside 1 .. GPIMHIP_MAX_DIM -> GPIMHIP_E_BADARG.
  *   gpimhip_sm_kmat      K(X, Z) (N x M) at u into out (leading dimension ld); Z == NULL: K(X, X) + noise I (N x N)
  *   gpimhip_sm_nll_grad  loss (1 double) and d loss / du (P doubles) at u
  *   gpimhip_fit_sm       T Adam iterations on u (skgpr.py:196-220), no host synchronisation inside the loop: fresh Adam
@@ -378,6 +378,23 @@ int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, co
                    double lr, int32_t T, double* hist_out, double* loss_out);
 int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
                        const double* u, const double* Xs, int64_t M, double* mean_out, double* var_out);
+/* The same model on the reflection blocks of a grid: the handle is in reflection mode (gpimhip_set_reflection; with
+ * gpimhip_set_border for an incomplete grid), X the N points of the fundamental domain, B = 2^r the blocks of the r reflected
+ * axes, ys (B x N) the targets and ones (B x N) the constant 1 (with a border: the indicator of the observed points) in the
+ * adapted basis, u ONE parameter vector of P doubles shared by the blocks.  The kernel is even in every coordinate difference:
+ *   K_s[p, p'] = w_p w_p' sum_q w_q prod_d ( f_qd(a_d - b_d) + sigma_d f_qd(a_d + b_d - 2 c_d) ),
+ *   f_qd(t) = exp(-2 pi^2 t^2 s_qd^2) cos(2 pi t m_qd),  sigma_d = +-1 the block's sign on a reflected axis (else no mirror term)
+ * loss, gradient, history and posterior are those of the dense model on the n_total points up to rounding.  Outputs as the
+ * dense entries (hist_out T x P, loss_out T); predictions honour var_count of gpimhip_set_reflection.
+ * gpimhip_sm_kmat on a handle in reflection mode returns the B blocks stacked (B N rows): K_s with the noise on the
+ * diagonal of the present points and identity rows for absent ones, or K_s(X, Z) / sqrt(B). */
+int gpimhip_sm_nll_grad_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                                int64_t N, int32_t B, const double* u, double* loss_out, double* grad_out);
+int gpimhip_fit_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                           int64_t N, int32_t B, double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out);
+int gpimhip_predict_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
+                               int64_t N, int32_t B, const double* u, const double* Xs, int64_t M, double* mean_out,
+                               double* var_out);
 
 /* ---- sparse (inducing-point) GP, variational free energy ---------------------------------
  * Replaces pyro.contrib.gp.models.SparseGPRegression(approx="VFE") as constructed by
