@@ -46,6 +46,27 @@ class SmStruct(ctypes.Structure):
 
 SM_MAX_MIXTURES = 16
 
+
+class GemmTestStruct(ctypes.Structure):
+    """gpimhip_gemm_test_t (diagnostic: one launch of the tile engine, gpimhip_gemm_tiles)"""
+    _fields_ = [("A", c_dp), ("lda", ctypes.c_int64), ("a_roff", ctypes.c_int32), ("a_coff", ctypes.c_int32),
+                ("B", c_dp), ("ldb", ctypes.c_int64), ("b_roff", ctypes.c_int32), ("b_coff", ctypes.c_int32),
+                ("C", c_dp), ("ldc", ctypes.c_int64), ("c_roff", ctypes.c_int32), ("c_coff", ctypes.c_int32),
+                ("colpart", c_dp), ("ld_colpart", ctypes.c_int64),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("tiles", ctypes.POINTER(ctypes.c_int32)), ("ntiles", ctypes.c_int32),
+                ("a_km", ctypes.c_int32), ("b_km", ctypes.c_int32), ("epi", ctypes.c_int32),
+                ("krev", ctypes.c_int32), ("chunk", ctypes.c_int32), ("kfix0", ctypes.c_int32), ("kfix1", ctypes.c_int32),
+                ("rect_rows", ctypes.c_int32), ("rect_cols", ctypes.c_int32), ("cj_max", ctypes.c_int32),
+                ("cmap", ctypes.c_int32), ("rag", ctypes.c_int32), ("inplace", ctypes.c_int32),
+                ("bshift", ctypes.c_int32), ("shape_div", ctypes.c_int32),
+                ("sA", ctypes.c_int64), ("sB", ctypes.c_int64), ("sC", ctypes.c_int64), ("sColpart", ctypes.c_int64),
+                ("batch", ctypes.c_int32)]
+
+
+GEMM_SHAPES = {"quad": 0, "rowhalf": 1, "8w_lds": 2, "8w": 3, "4w": 4}      # GPIMHIP_GEMM_SHAPE_*
+EPI_STORE, EPI_COLSUMSQ = 0, 1
+
 _lib = None
 
 _PROTOS = {
@@ -167,6 +188,14 @@ _PROTOS = {
     "gpimhip_step_plan_host_f32": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                   ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                                   ctypes.POINTER(ctypes.c_int32)]),
+    "gpimhip_gemm_tiles": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GemmTestStruct)]),
+    "gpimhip_gemm_shape_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "gpimhip_gemm_tile_pos_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.POINTER(ctypes.c_int32)]),
+    "gpimhip_gemm_rect_tile_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "gpimhip_vgp_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
                                             c_dp, ctypes.c_int64, c_dp, c_dp, c_dp]),
     "gpimhip_fit_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp, c_dp,

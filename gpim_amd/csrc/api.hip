@@ -806,6 +806,10 @@ int gpimhip_set_precision(gpimhip_handle h, int32_t bits) {
     if (!h || (bits != 32 && bits != 64)) return GPIMHIP_E_BADARG;
     const int want = bits == 32 ? 1 : 0;
     if (want == h->fp32) return GPIMHIP_OK;
+    if (want && h->refl.mask) {     // (the other order is refused by gpimhip_set_reflection)
+        gpim_set_error("the symmetry-reduced model computes in double precision: leave reflection mode (gpimhip_set_reflection(h, 0, ...)) first");
+        return GPIMHIP_E_BADARG;
+    }
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     ws_release_matrix(h);               // sized by the element type

@@ -422,3 +422,56 @@ struct GemmArgs {
 };
 int launch_gemm(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);
 int launch_gemm_f32(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);   // gemm32.hip
+
+// The workgroup shape of a tile-engine launch (NW waves on a TSM x TSN part of each 128 x 128 tile; gemm_body.hpp), chosen
+// from the launch's tile count by gemm_shape_f64 (gemm.hip) / gemm_shape_f32 (gemm_kernel.hpp, gemm32.hip); the values are
+// the GPIMHIP_GEMM_SHAPE_* of gpimhip.h.  -1: nothing to launch (no tiles) or an operand layout the engine does not have.
+enum GemmShape {
+    GEMM_SHAPE_QUAD = GPIMHIP_GEMM_SHAPE_QUAD,          // (4,  64,  64)
+    GEMM_SHAPE_ROWHALF = GPIMHIP_GEMM_SHAPE_ROWHALF,    // (8,  64, 128)
+    GEMM_SHAPE_8W_LDS = GPIMHIP_GEMM_SHAPE_8W_LDS,      // (8, 128, 128) + 24 KB of dynamic LDS: one tile per CU
+    GEMM_SHAPE_8W = GPIMHIP_GEMM_SHAPE_8W,              // (8, 128, 128)
+    GEMM_SHAPE_4W = GPIMHIP_GEMM_SHAPE_4W               // (4, 128, 128)
+};
+static inline bool gemm_layout_ok(bool a_km, bool b_km, int epi) {
+    if (epi == EPI_STORE) return !a_km || b_km;         // NT, NN, TN
+    return epi == EPI_COLSUMSQ && !a_km && b_km;        // NN
+}
+int gemm_shape_f64(bool a_km, bool b_km, int epi, int64_t ntiles, int64_t batch, int shape_div, int inplace);   // gemm.hip
+int gemm_shape_f32(bool a_km, bool b_km, int epi, int64_t ntiles, int64_t batch, int shape_div, int inplace);   // gemm32.hip
+int gemm_tile_pos_f32(int n, int chunk, int quads, int bx, int& quad);      // gemm32.hip: the float engine's copy of gemm_tile_pos
+
+// XCD-aware bijective remap of a launch's workgroup index to a position of its tile list (block b runs on XCD
+// b % 8, in order b / 8 on that XCD).
+//  chunk == 0: every XCD gets one contiguous slice of the tile list -- best L2 reuse when all
+//              tiles cost the same (SYRK-shaped trailing updates).
+//  chunk  > 0: the list is dealt to the XCDs in chunks of that many tiles (one 8x8 patch), back
+//              and forth, so lists sorted by decreasing k-range stay balanced across XCDs.
+// Host-callable for the tests of the map itself (gpimhip_gemm_tile_pos_host).  The float engine keeps a copy of its own
+// (gemm_kernel.hpp: GEMM_TILE_POS_T).
+template <int TSM, int TSN>
+__host__ __device__ __forceinline__ int gemm_tile_pos(int n, int chunk, int bx, int& quad) {
+    constexpr int QUADS = (128 / TSM) * (128 / TSN);    // workgroups per 128x128 tile
+    const int b = bx / QUADS;
+    quad = bx % QUADS;
+    if (QUADS > 1) return b;
+    if (chunk == 0) {
+        const int q = n >> 3, r = n & 7, x = b & 7, yy = b >> 3;
+        return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + yy;
+    }
+    const int C = chunk, full = (n / (8 * C)) * (8 * C);
+    if (b < full) {
+        // serpentine: odd rounds deal in reverse, so that on a list sorted by cost no XCD always
+        // gets the most expensive chunk of the round (16 % spread between XCD 0 and 7 otherwise)
+        const int x = b & 7, y = b >> 3, round = y / C;
+        return (round * 8 + ((round & 1) ? 7 - x : x)) * C + (y % C);
+    }
+    return b;
+}
+// Position p of a rectangle launch (GemmArgs::rect_rows / rect_cols) -> its tile: strips of eight rows, column by column
+// inside a strip (the last strip may be lower).
+__host__ __device__ __forceinline__ void gemm_rect_tile(int rect_rows, int rect_cols, int p, int& ci, int& cj) {
+    const int per = 8 * rect_cols, s = p / per, q = p - s * per, left = rect_rows - 8 * s, rows_here = left < 8 ? left : 8;
+    ci = 8 * s + q % rows_here;
+    cj = q / rows_here;
+}

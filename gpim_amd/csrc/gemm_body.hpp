@@ -147,31 +147,8 @@ __host__ __device__ constexpr int gemm_smem_doubles() {
     constexpr int TSX = TSM > TSN ? TSM : TSN;
     return 2 * NSTG * ((TSX * LD_MK > GEMM_BK * (TSX + 16)) ? TSX * LD_MK : GEMM_BK * (TSX + 16));
 }
-// XCD-aware bijective remap of a launch's workgroup index to a position of its tile list (block b runs on XCD
-// b % 8, in order b / 8 on that XCD).
-//  chunk == 0: every XCD gets one contiguous slice of the tile list -- best L2 reuse when all
-//              tiles cost the same (SYRK-shaped trailing updates).
-//  chunk  > 0: the list is dealt to the XCDs in chunks of that many tiles (one 8x8 patch), back
-//              and forth, so lists sorted by decreasing k-range stay balanced across XCDs.
-template <int TSM, int TSN>
-__device__ __forceinline__ int gemm_tile_pos(int n, int chunk, int bx, int& quad) {
-    constexpr int QUADS = (128 / TSM) * (128 / TSN);    // workgroups per 128x128 tile
-    const int b = bx / QUADS;
-    quad = bx % QUADS;
-    if (QUADS > 1) return b;
-    if (chunk == 0) {
-        const int q = n >> 3, r = n & 7, x = b & 7, yy = b >> 3;
-        return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + yy;
-    }
-    const int C = chunk, full = (n / (8 * C)) * (8 * C);
-    if (b < full) {
-        // serpentine: odd rounds deal in reverse, so that on a list sorted by cost no XCD always
-        // gets the most expensive chunk of the round (16 % spread between XCD 0 and 7 otherwise)
-        const int x = b & 7, y = b >> 3, round = y / C;
-        return (round * 8 + ((round & 1) ? 7 - x : x)) * C + (y % C);
-    }
-    return b;
-}
+// (the XCD-aware remap of the workgroup index to a position of the tile list, gemm_tile_pos, and the rectangle map,
+// gemm_rect_tile, are host-callable and live in common.hpp)
 
 // RAG: the launch has a ragged last block (GemmArgs::rag != 0).  A template parameter so that the k-loop of every other
 // launch keeps its schedule (as a run-time test inside the loop it cost the K^-1 product at N = 16384 0.4 %).
@@ -184,9 +161,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bx, const i
     const int p = gemm_tile_pos<TSM, TSN>(g.ntiles, g.chunk, bx, quad);
     TileDesc t;
     if (g.rect_cols > 0) {
-        const int per = 8 * g.rect_cols, s = p / per, q = p - s * per, rows_here = min(8, g.rect_rows - 8 * s);
-        t.ci = 8 * s + q % rows_here;
-        t.cj = q / rows_here;
+        gemm_rect_tile(g.rect_rows, g.rect_cols, p, t.ci, t.cj);
         t.kb0 = g.kfix0;
         t.kb1 = g.kfix1;
     } else {

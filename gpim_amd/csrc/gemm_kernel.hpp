@@ -150,6 +150,42 @@ constexpr int gemm_smem_elems_t() {
     return 4 * ((TSX * LD_MK_OF(R) > BK * (TSX + 16)) ? TSX * LD_MK_OF(R) : BK * (TSX + 16));
 }
 
+// XCD-aware bijective remap (block b runs on XCD b%8, in order b/8 on that XCD).
+//  chunk == 0: every XCD gets one contiguous slice of the tile list -- best L2 reuse when all
+//              tiles cost the same (SYRK-shaped trailing updates).
+//  chunk  > 0: the list is dealt to the XCDs in chunks of that many tiles (one 8x8 patch), back
+//              and forth, so lists sorted by decreasing k-range stay balanced across XCDs.
+// The same map as gemm_tile_pos of common.hpp.  It stays this engine's own text, expanded in place: calling the shared
+// function (or any function) instead changes the register allocation and instruction schedule of the float kernels.  A
+// macro so that the host test of the map (gemm_tile_pos_t below; gpimhip_gemm_tile_pos_host with fp32 = 1) runs the
+// very statements the kernels compile.  Declares n, b, quad and p; needs QUADS = workgroups per 128x128 tile.
+#define GEMM_TILE_POS_T(ntiles_, chunk_, bx_)                                                                \
+    const int n = ntiles_, b = bx_ / QUADS, quad = bx_ % QUADS;                                              \
+    int p;                                                                                                   \
+    if (QUADS > 1) {                                                                                         \
+        p = b;                                                                                               \
+    } else if (chunk_ == 0) {                                                                                \
+        const int q = n >> 3, r = n & 7, x = b & 7, yy = b >> 3;                                             \
+        p = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + yy;                                          \
+    } else {                                                                                                 \
+        const int C = chunk_, full = (n / (8 * C)) * (8 * C);                                                \
+        if (b < full) {                                                                                      \
+            /* serpentine: odd rounds deal in reverse, so that on a list sorted by cost no XCD always */    \
+            /* gets the most expensive chunk of the round (16 % spread between XCD 0 and 7 otherwise) */    \
+            const int x = b & 7, y = b >> 3, round = y / C;                                                  \
+            p = (round * 8 + ((round & 1) ? 7 - x : x)) * C + (y % C);                                       \
+        } else {                                                                                             \
+            p = b;                                                                                           \
+        }                                                                                                    \
+    }
+template <int TSM, int TSN>
+static inline int gemm_tile_pos_t(int ntiles, int chunk, int bx, int& quad_out) {
+    constexpr int QUADS = (128 / TSM) * (128 / TSN);
+    GEMM_TILE_POS_T(ntiles, chunk, bx)
+    quad_out = quad;
+    return p;
+}
+
 // One workgroup's share of a tile launch as a device function: bx / by = the workgroup's position in the launch
 // (the block index of gemm_tiles_kernel_t; the step kernel of cholstep32.hip hosts tiles next to a factorisation
 // role), smem = gemm_smem_elems_t<R, TSM, TSN>() elements of LDS.
@@ -176,31 +212,9 @@ __device__ __forceinline__ void gemm_tile_body_t(GemmArgs g, const int bx, const
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-aware bijective remap (block b runs on XCD b%8, in order b/8 on that XCD).
-    //  chunk == 0: every XCD gets one contiguous slice of the tile list -- best L2 reuse when all
-    //              tiles cost the same (SYRK-shaped trailing updates).
-    //  chunk  > 0: the list is dealt to the XCDs in chunks of that many tiles (one 8x8 patch), back
-    //              and forth, so lists sorted by decreasing k-range stay balanced across XCDs.
     constexpr int QN = 128 / TSN;                       // workgroups per tile along n
     constexpr int QUADS = (128 / TSM) * QN;             // workgroups per 128x128 tile
-    const int n = g.ntiles, b = bx / QUADS, quad = bx % QUADS;
-    int p;
-    if (QUADS > 1) {
-        p = b;
-    } else if (g.chunk == 0) {
-        const int q = n >> 3, r = n & 7, x = b & 7, yy = b >> 3;
-        p = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + yy;
-    } else {
-        const int C = g.chunk, full = (n / (8 * C)) * (8 * C);
-        if (b < full) {
-            // serpentine: odd rounds deal in reverse, so that on a list sorted by cost no XCD always
-            // gets the most expensive chunk of the round (16 % spread between XCD 0 and 7 otherwise)
-            const int x = b & 7, y = b >> 3, round = y / C;
-            p = (round * 8 + ((round & 1) ? 7 - x : x)) * C + (y % C);
-        } else {
-            p = b;
-        }
-    }
+    GEMM_TILE_POS_T(g.ntiles, g.chunk, bx)
     TileDesc t = g.tiles[p];
     if (g.kfix1 > g.kfix0) { t.kb0 = g.kfix0; t.kb1 = g.kfix1; }
     const int nsteps = (t.kb1 - t.kb0) * (NB / BK);
@@ -356,42 +370,71 @@ static int mid_tiles() {
     return v;
 }
 
-template <typename R, bool A_KM, bool B_KM, int EPI>
-static int launch_one(gpimhip_ctx* h, const GemmArgs& g) {
-    if (g.ntiles <= 0) return GPIMHIP_OK;
+// The launch shape of this engine (GemmShape) for ntiles tiles per problem and `batch` problems; GemmArgs::shape_div is
+// not implemented here (launch_gemm_t refuses it).
+static int gemm_shape_generic(bool a_km, bool b_km, int epi, int64_t ntiles, int64_t batch, int inplace) {
+    if (ntiles <= 0 || batch <= 0 || !gemm_layout_ok(a_km, b_km, epi)) return -1;
     // The column-sum epilogue adds its partial sums across the waves of the workgroup, in an order that follows the wave
     // layout: its shape is chosen from the problem's own tiles, so that a problem of a lock-step batch gets the bits of its
     // stand-alone prediction (N = 2300, M = 500: 72 tiles -- 8 waves alone, 4 waves in a batch of four otherwise).
-    const int64_t total = (int64_t)g.ntiles * (EPI == EPI_COLSUMSQ ? 1 : h->nbatch);
+    const int64_t total = ntiles * (epi == EPI_COLSUMSQ ? 1 : batch);
     const bool small = total <= 256;
-    if (EPI == EPI_STORE && small && !g.inplace)
-        // few tiles: spread each over four CUs (64x64 quadrants)
+    // few tiles: spread each over four CUs (64x64 quadrants)
+    if (epi == EPI_STORE && small && !inplace) return GEMM_SHAPE_QUAD;
+    // in-place panel solve: row halves (the workgroup owns the rows it overwrites), 8 waves
+    if (epi == EPI_STORE && small) return GEMM_SHAPE_ROWHALF;
+    // one tile per CU (see mid_tiles()).  Not for the column-sum epilogue: its cross-wave summation order
+    // follows the wave layout, and batched and stand-alone predictions must stay bit-identical.
+    if (epi == EPI_STORE && total > 256 && total <= mid_tiles()) return GEMM_SHAPE_8W_LDS;
+    // (also every SYRK-shaped update of the Cholesky: measured 8 % faster factorisation at N = 16384,
+    // the 512-thread workgroups interleave better with the concurrent panel chain)
+    // at most one tile per CU: 8-wave workgroup so every SIMD still holds two MFMA waves
+    if (total <= 256 || (!a_km && !b_km)) return GEMM_SHAPE_8W;
+    return GEMM_SHAPE_4W;
+}
+
+template <typename R, bool A_KM, bool B_KM, int EPI>
+static int launch_one(gpimhip_ctx* h, const GemmArgs& g) {
+    if (g.ntiles <= 0) return GPIMHIP_OK;
+    switch (gemm_shape_generic(A_KM, B_KM, EPI, g.ntiles, h->nbatch, g.inplace)) {
+    case GEMM_SHAPE_QUAD:
         hipLaunchKernelGGL((gemm_tiles_kernel_t<R, A_KM, B_KM, EPI_STORE, 4, 64, 64>), dim3(g.ntiles * 4, h->nbatch),
                            dim3(256), 0, h->stream, g);
-    else if (EPI == EPI_STORE && small)
-        // in-place panel solve: row halves (the workgroup owns the rows it overwrites), 8 waves
+        break;
+    case GEMM_SHAPE_ROWHALF:
         hipLaunchKernelGGL((gemm_tiles_kernel_t<R, A_KM, B_KM, EPI_STORE, 8, 64, 128>), dim3(g.ntiles * 2, h->nbatch),
                            dim3(512), 0, h->stream, g);
-    else if (EPI == EPI_STORE && total > 256 && total <= mid_tiles())
-        // one tile per CU (see mid_tiles()).  Not for the column-sum epilogue: its cross-wave summation order
-        // follows the wave layout, and batched and stand-alone predictions must stay bit-identical.
+        break;
+    case GEMM_SHAPE_8W_LDS:
         hipLaunchKernelGGL((gemm_tiles_kernel_t<R, A_KM, B_KM, EPI, 8, 128, 128>), dim3(g.ntiles, h->nbatch), dim3(512),
                            24 * 1024, h->stream, g);
-    else if (total <= 256 || (!A_KM && !B_KM))
-        // (also every SYRK-shaped update of the Cholesky: measured 8 % faster factorisation at N = 16384,
-        // the 512-thread workgroups interleave better with the concurrent panel chain)
-        // at most one tile per CU: 8-wave workgroup so every SIMD still holds two MFMA waves
+        break;
+    case GEMM_SHAPE_8W:
         hipLaunchKernelGGL((gemm_tiles_kernel_t<R, A_KM, B_KM, EPI, 8, 128, 128>), dim3(g.ntiles, h->nbatch), dim3(512), 0,
                            h->stream, g);
-    else
+        break;
+    case GEMM_SHAPE_4W:
         hipLaunchKernelGGL((gemm_tiles_kernel_t<R, A_KM, B_KM, EPI, 4, 128, 128>), dim3(g.ntiles, h->nbatch), dim3(256), 0,
                            h->stream, g);
+        break;
+    default:
+        gpim_set_error("launch_gemm: no launch shape for this batch");
+        return GPIMHIP_E_BADARG;
+    }
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
 
 template <typename R>
 static int launch_gemm_t(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g) {
+    // switches of GemmArgs that gemm_tile_body_t does not implement (the double engine of gemm_body.hpp does): refused, not
+    // ignored -- no caller that can run on a single-precision handle sets one
+    const char* missing = g.rect_cols > 0 ? "rect_cols" : g.cj_max > 0 ? "cj_max" : g.cmap ? "cmap" : g.rag ? "rag"
+                          : g.C2 ? "C2" : g.shape_div > 1 ? "shape_div" : nullptr;
+    if (missing) {
+        gpim_set_error(std::string("launch_gemm: the single-precision tile engine does not implement GemmArgs::") + missing);
+        return GPIMHIP_E_BADARG;
+    }
     if (epi == EPI_STORE) {
         if (!a_km && !b_km) return launch_one<R, false, false, EPI_STORE>(h, g);   // NT
         if (!a_km && b_km) return launch_one<R, false, true, EPI_STORE>(h, g);     // NN

@@ -675,6 +675,60 @@ int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64
 int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out,
                                int32_t* diag_out);
 
+/* DIAGNOSTIC: the MFMA tile engine behind every O(N^3) stage, by itself (tests/test_gemm_host.py, tests/test_gpu_gemm.py).
+ * Nothing in the product path calls these four.
+ *
+ * A launch covers a list of 128 x 128 output tiles, for `batch` problems in lock-step:
+ *   C[ci + c_roff, cj + c_coff] = alpha * sum_{kb in [kb0, kb1)} A-block(ci, kb) * B-block(kb, cj) + beta * C[...]
+ * on row-major matrices in blocks of 128.  A-block(ci, kb) is block (ci + a_roff, kb + a_coff) of A when a_km = 0 (rows
+ * of A are rows of the product, k contiguous) and the transpose of block (kb + a_roff, ci + a_coff) when a_km = 1;
+ * B-block(kb, cj) is the transpose of block (cj + b_roff, kb + b_coff) of B when b_km = 0 and block (kb + b_roff,
+ * cj + b_coff) when b_km = 1.  Layout pairs: NT (0, 0), NN (0, 1), TN (1, 1).  epi = 1 (NN only) stores, instead of C,
+ * the column sums of squares of each product tile: colpart[ci * ld_colpart + (cj + c_coff) * 128 + col], in double for
+ * either precision.  Problem p of the batch reads A + p * sA, B + (p >> bshift) * sB and writes C + p * sC (colpart +
+ * p * sColpart), strides in elements.  Switches, as GemmArgs (csrc/common.hpp) documents them: krev (walk each k-range
+ * from its end), chunk (dealing of the list to the XCDs), kfix0 < kfix1 (one k-range for every tile), rect_rows x
+ * rect_cols (no list: the tiles of a rectangle, ntiles = their product; needs kfix), cj_max (> 0: tiles with cj >= cj_max
+ * are skipped), cmap (the output block column is the tile's kb0; needs kfix), rag (> 0: rows >= 64 of block row rag - 1
+ * are not computed and the last 64 k of a range ending at block rag are not read), inplace (row-half workgroups),
+ * shape_div (the shape is chosen for ntiles * batch / shape_div tiles).  A single-precision handle
+ * (gpimhip_set_precision) reads A, B, C as float and refuses rect_cols, cj_max, cmap, rag and shape_div, which its
+ * engine does not implement.
+ *   gpimhip_gemm_tiles          copies the HOST list `tiles` (ntiles quadruples ci, cj, kb0, kb1; NULL with rect_cols > 0)
+ *                               to the device, runs the production dispatch (launch_gemm) once and synchronises.
+ *                               A, B, C, colpart: device.  The caller answers for the extents: every block a tile names
+ *                               must lie inside the matrices.
+ *   gpimhip_gemm_shape_host     the workgroup shape the dispatch chooses (GPIMHIP_GEMM_SHAPE_*), or -1 when there is
+ *                               nothing to launch or the engine has no such layout / switch.  No device involved.
+ *   gpimhip_gemm_tile_pos_host  the map workgroup index -> (position in the tile list, part of the tile) of a launch of
+ *                               n tiles in `quads` (1, 2, 4) workgroups per tile, for bx = bx0 .. bx0 + count - 1; fp32 != 0:
+ *                               the copy of the map that the single-precision kernels compile.
+ *   gpimhip_gemm_rect_tile_host the map position -> (ci, cj) of a rectangle launch, for p = p0 .. p0 + count - 1. */
+#define GPIMHIP_GEMM_SHAPE_QUAD 0     /* 4 waves on a 64 x 64 quadrant */
+#define GPIMHIP_GEMM_SHAPE_ROWHALF 1  /* 8 waves on a 64 x 128 row half */
+#define GPIMHIP_GEMM_SHAPE_8W_LDS 2   /* 8 waves on a tile, one workgroup per CU (24 KB of dynamic LDS) */
+#define GPIMHIP_GEMM_SHAPE_8W 3       /* 8 waves on a tile */
+#define GPIMHIP_GEMM_SHAPE_4W 4       /* 4 waves on a tile */
+typedef struct {
+    const void* A; int64_t lda; int32_t a_roff, a_coff;
+    const void* B; int64_t ldb; int32_t b_roff, b_coff;
+    void* C; int64_t ldc; int32_t c_roff, c_coff;
+    double* colpart; int64_t ld_colpart;
+    double alpha, beta;
+    const int32_t* tiles; int32_t ntiles;
+    int32_t a_km, b_km, epi;
+    int32_t krev, chunk, kfix0, kfix1, rect_rows, rect_cols, cj_max, cmap, rag, inplace, bshift, shape_div;
+    int64_t sA, sB, sC, sColpart;
+    int32_t batch;
+} gpimhip_gemm_test_t;
+int gpimhip_gemm_tiles(gpimhip_handle h, const gpimhip_gemm_test_t* d);
+int gpimhip_gemm_shape_host(int32_t fp32, int32_t a_km, int32_t b_km, int32_t epi, int64_t ntiles, int64_t batch,
+                            int32_t shape_div, int32_t inplace);
+int gpimhip_gemm_tile_pos_host(int32_t fp32, int32_t n, int32_t chunk, int32_t quads, int32_t bx0, int32_t count,
+                               int32_t* p_out, int32_t* quad_out);
+int gpimhip_gemm_rect_tile_host(int32_t rect_rows, int32_t rect_cols, int32_t p0, int32_t count, int32_t* ci_out,
+                                int32_t* cj_out);
+
 /* Stage timing for bench.py (HIP events on the handle's stream, recorded only while enabled).
  * stage: 0 = Cholesky (all launches of one factorisation, including the tile operations of the triangular inverse
  *            they host), 1 = what is left of the triangular inverse after the last step,
