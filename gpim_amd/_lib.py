@@ -131,6 +131,12 @@ _PROTOS = {
     "gpimhip_predict_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp,
                                             ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp]),
+    "gpimhip_sample_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp,
+                                           ctypes.POINTER(ctypes.c_int32), c_dp,
+                                           ctypes.POINTER(ctypes.c_int32), c_dp,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                           c_dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
     "gpimhip_acq": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_dp, c_dp, ctypes.c_int64, ctypes.c_double,
                                    ctypes.c_double, c_dp, c_dp]),
     "gpimhip_nanmax": (ctypes.c_int, [ctypes.c_void_p, c_dp, ctypes.c_int64, c_dp]),

@@ -203,6 +203,11 @@ class Dense:
         raise NotImplementedError("method='border' draws through the bordered reflection blocks of an image with missing "
                                   "points (the %s solver has none)" % type(self).__name__)
 
+    def sample_kron(self, o, *args):
+        """Draws through the Kronecker factors belong to the Kronecker model (``Kron``)."""
+        raise NotImplementedError("method='kron' draws through the Kronecker eigenbasis of the structured RBF model on a "
+                                  "complete grid (the %s solver has none)" % type(self).__name__)
+
 
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""
@@ -256,6 +261,20 @@ class Kron(Dense):
 
     def nll_grad(self, o, out):
         return o._handle.lib.gpimhip_kron_nll_grad(*self._grid(o), *_loss_grad(out))
+
+    def sample_kron(self, o, taxes, union, z, noiseless, jitter, mean, out):
+        """Joint posterior draws on the product grid of the axes ``taxes`` by Matheron's rule in Kronecker form (csrc/kron.hip:
+        gpimhip_sample_kron).  union: what gprutils.union_axes returns for the training and the test
+        axes; z: (S, prod U_i + N + M) device tensor [zeta | z_e | z_n]; mean (M), out (S, M)."""
+        au, ic, it = union
+        i32 = lambda v: (ctypes.c_int32 * len(v))(*[int(k) for k in v])
+        # (both device tensors stay referenced until the call returns: a temporary's block would be handed to the next one)
+        taxes_d, au_d = o._to_device(np.concatenate(taxes)), o._to_device(np.concatenate(au))
+        return o._handle.lib.gpimhip_sample_kron(*self._grid(o), i32([len(t) for t in taxes]),
+                                                 ptr(taxes_d), i32([len(a) for a in au]),
+                                                 ptr(au_d), i32(np.concatenate(ic)),
+                                                 i32(np.concatenate(it)), ptr(z), z.shape[0], int(bool(noiseless)),
+                                                 float(jitter), ptr(mean), ptr(out))
 
 
 class Reflection(Dense):

@@ -23,7 +23,11 @@
 //   kron_modeprod_kernel out[p,a,q] = sum_b M[a,b] in[p,b,q]   (tensor-times-matrix along one mode)
 //   kron_dvec_kernel     D, alpha~ = y~ / D, first reduction pass;  kron_quad_kernel second pass
 //   kron_finalize_kernel sums -> finalize_step;  kron_cross_kernel / kron_var_kernel for the posterior
+//   posterior draws on any product test grid (gpimhip_sample_kron), all S draws per launch:
+//   kron_root_rows_kernel rows of the prior root of a union axis;  kron_zeta_kernel zeta out of z;  kron_resid_kernel the
+//   residual;  kron_dscale_kernel the 1 / D scaling;  kron_draw_kernel the epilogue
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 #include <algorithm>
 #include "common.hpp"
@@ -51,13 +55,26 @@ struct KronDev {
     int plam[2 * KMAXD];                                    // offset of its eigenvalues / Qt rows inside the axis
 };
 
-struct KronWs {
+// One set of grid axes with everything that belongs to an axis alone: coordinates, K_i, the eigen-problem plan and the
+// eigen-decomposition (KronDev).  The training grid has one; gpimhip_sample_kron keeps a second one for the union of the
+// training and the test axes, without the gradient matrices (E, Mm, mdiag) and without any N-sized vector.
+struct KronAxes {
     int d = 0;
     int n[KMAXD] = {0, 0, 0, 0};
-    int64_t N = 0, sum_n = 0, sum_n2 = 0;
+    int64_t sum_n = 0, sum_n2 = 0;
+    bool grad = false;
     double* arena = nullptr;
     int64_t arena_count = 0;
     KronDev dev;
+};
+
+struct KronWs {
+    int d = 0;
+    int n[KMAXD] = {0, 0, 0, 0};
+    int64_t N = 0;
+    KronAxes tr;                 // the training grid's axes
+    double* arena = nullptr;     // the N-sized vectors
+    int64_t arena_count = 0;
     double *yt = nullptr, *at = nullptr, *t1 = nullptr, *t2 = nullptr, *Z = nullptr, *part = nullptr;
     int nblk = 0;
     // prediction
@@ -67,15 +84,74 @@ struct KronWs {
     int64_t parena_count = 0;
     double *Ks = nullptr, *Bs = nullptr, *p1 = nullptr, *p2 = nullptr, *tcoords = nullptr;
     int64_t koff[KMAXD] = {0, 0, 0, 0};
+    // posterior draws (gpimhip_sample_kron)
+    KronAxes un;                 // the union axes, when they differ from the training axes
+    double* sarena = nullptr;
+    int64_t sarena_count = 0;
+    int64_t s_key[3 + 3 * KMAXD] = {0};      // S, d, buffer size, n_union, n, n_test the workspace was carved for
+    double *RG = nullptr, *RT = nullptr, *Zc = nullptr, *sa = nullptr, *sb = nullptr;
+    int32_t *ic = nullptr, *it = nullptr;
+    int64_t rgoff[KMAXD] = {0, 0, 0, 0}, rtoff[KMAXD] = {0, 0, 0, 0};
 };
+
+static void kron_free(gpimhip_ctx* h, double*& p, int64_t& count) {
+    if (p) { (void)hipFree(p); h->bytes -= count * (int64_t)sizeof(double); }
+    p = nullptr; count = 0;
+}
 
 void kron_release(gpimhip_ctx* h) {
     KronWs* w = static_cast<KronWs*>(h->kron);
     if (!w) return;
-    if (w->arena) { (void)hipFree(w->arena); h->bytes -= w->arena_count * (int64_t)sizeof(double); }
-    if (w->parena) { (void)hipFree(w->parena); h->bytes -= w->parena_count * (int64_t)sizeof(double); }
+    kron_free(h, w->arena, w->arena_count);
+    kron_free(h, w->tr.arena, w->tr.arena_count);
+    kron_free(h, w->un.arena, w->un.arena_count);
+    kron_free(h, w->parena, w->parena_count);
+    kron_free(h, w->sarena, w->sarena_count);
     delete w;
     h->kron = nullptr;
+}
+
+static int kron_alloc(gpimhip_ctx* h, int64_t count, const char* what, double*& p, int64_t& kept) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)count * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        gpim_set_error(what);
+        return GPIMHIP_E_NOMEM;
+    }
+    p = (double*)q;
+    kept = count;
+    h->bytes += count * (int64_t)sizeof(double);
+    return GPIMHIP_OK;
+}
+
+// the per-axis state for axes of the orders n[]; grad: with E, Mm and mdiag (training)
+static int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool grad) {
+    bool same = a.d == d && a.arena && a.grad == grad;
+    for (int i = 0; i < d && same; ++i) same = a.n[i] == n[i];
+    if (same) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    kron_free(h, a.arena, a.arena_count);
+    a.d = d; a.grad = grad;
+    a.sum_n = 0; a.sum_n2 = 0;
+    int64_t N = 1;
+    for (int i = 0; i < KMAXD; ++i) a.n[i] = i < d ? n[i] : 1;
+    for (int i = 0; i < d; ++i) { N *= n[i]; a.sum_n += n[i]; a.sum_n2 += (int64_t)n[i] * n[i]; }
+    const int64_t count = (grad ? 3 : 2) * a.sum_n + (grad ? 7 : 5) * a.sum_n2 + 32;
+    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP axis workspace)", a.arena, a.arena_count));
+    double* p = a.arena;
+    auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
+    KronDev& dv = a.dev;
+    memset(&dv, 0, sizeof(dv));
+    dv.d = d; dv.N = N;
+    int off = 0; int64_t moff = 0;
+    for (int i = 0; i < KMAXD; ++i) {
+        dv.n[i] = a.n[i]; dv.off[i] = off; dv.moff[i] = moff;
+        if (i < d) { off += n[i]; moff += (int64_t)n[i] * n[i]; }
+    }
+    dv.coords = take(a.sum_n); dv.lam = take(a.sum_n);
+    dv.K = take(a.sum_n2); dv.W = take(a.sum_n2); dv.Qt = take(a.sum_n2); dv.Tt = take(a.sum_n2); dv.Vr = take(a.sum_n2);
+    if (grad) { dv.mdiag = take(a.sum_n); dv.E = take(a.sum_n2); dv.Mm = take(a.sum_n2); }
+    return GPIMHIP_OK;
 }
 
 static int kron_ensure(gpimhip_ctx* h, int d, const int32_t* n, KronWs** out) {
@@ -84,36 +160,19 @@ static int kron_ensure(gpimhip_ctx* h, int d, const int32_t* n, KronWs** out) {
     *out = &w;
     bool same = w.d == d && w.arena;
     for (int i = 0; i < d && same; ++i) same = w.n[i] == n[i];
+    GP_TRY(kron_axes_ensure(h, w.tr, d, n, true));
     if (same) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (w.arena) { (void)hipFree(w.arena); h->bytes -= w.arena_count * (int64_t)sizeof(double); w.arena = nullptr; }
+    kron_free(h, w.arena, w.arena_count);
     w.d = d;
-    w.N = 1; w.sum_n = 0; w.sum_n2 = 0;
+    w.N = 1;
     for (int i = 0; i < KMAXD; ++i) w.n[i] = i < d ? n[i] : 1;
-    for (int i = 0; i < d; ++i) { w.N *= n[i]; w.sum_n += n[i]; w.sum_n2 += (int64_t)n[i] * n[i]; }
+    for (int i = 0; i < d; ++i) w.N *= n[i];
     w.nblk = (int)std::min<int64_t>(1024, (w.N + 255) / 256);
-    const int64_t count = 3 * w.sum_n + 7 * w.sum_n2 + (4 + d) * w.N + (int64_t)w.nblk * 16 + 64;
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)count * sizeof(double)) != hipSuccess) {
-        gpim_set_error("hipMalloc failed (structured-GP workspace)");
-        return GPIMHIP_E_NOMEM;
-    }
-    w.arena = (double*)q;
-    w.arena_count = count;
-    h->bytes += count * (int64_t)sizeof(double);
+    const int64_t count = (4 + d) * w.N + (int64_t)w.nblk * 16 + 32;
+    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP workspace)", w.arena, w.arena_count));
     double* p = w.arena;
     auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
-    KronDev& dv = w.dev;
-    memset(&dv, 0, sizeof(dv));
-    dv.d = d; dv.N = w.N;
-    int off = 0; int64_t moff = 0;
-    for (int i = 0; i < KMAXD; ++i) {
-        dv.n[i] = w.n[i]; dv.off[i] = off; dv.moff[i] = moff;
-        if (i < d) { off += n[i]; moff += (int64_t)n[i] * n[i]; }
-    }
-    dv.coords = take(w.sum_n); dv.lam = take(w.sum_n); dv.mdiag = take(w.sum_n);
-    dv.K = take(w.sum_n2); dv.E = take(w.sum_n2); dv.W = take(w.sum_n2);
-    dv.Qt = take(w.sum_n2); dv.Mm = take(w.sum_n2); dv.Tt = take(w.sum_n2); dv.Vr = take(w.sum_n2);
     w.yt = take(w.N); w.at = take(w.N); w.t1 = take(w.N); w.t2 = take(w.N);
     w.Z = take((int64_t)d * w.N);
     w.part = take((int64_t)w.nblk * 16);
@@ -136,7 +195,7 @@ __global__ void kron_axis_kernel(KronDev dv, const ThetaDev* __restrict__ th) {
     const double k = exp(-0.5 * r2);
     const int64_t o = dv.moff[ax] + e;
     dv.K[o] = k;
-    dv.E[o] = k * r2;
+    if (dv.E) dv.E[o] = k * r2;      // (an axis set without the gradient matrices: the union axes of the draws)
 }
 
 // Vr <- I for every eigen-problem (cold start of the rotations)
@@ -421,16 +480,18 @@ static int modeprod(gpimhip_ctx* h, const double* in, double* out, const double*
 }
 
 // applies, for every axis i, the matrix mats[i] (ma[i] x nb[i]) along mode i of `src` (shape nb[]);
-// ping-pongs between bufa/bufb and returns the buffer that holds the result (shape ma[])
+// ping-pongs between bufa/bufb and returns the buffer that holds the result (shape ma[]).  batch > 1: src is `batch`
+// contiguous tensors (batch, nb[]) -- the batch index folds into `pre`, so a mode is still one launch.  src may be bufb
+// (it is read by the first mode only, which writes bufa), never bufa.
 static int tensor_apply(gpimhip_ctx* h, int d, const int* nbv, const int* mav, const double* const* mats,
                         const int* ldm, int trans, int sq, const double* src, double* bufa, double* bufb,
-                        double** result) {
+                        double** result, int64_t batch = 1) {
     const double* cur = src;
     double* dst = bufa;
     int shape[KMAXD];
     for (int i = 0; i < d; ++i) shape[i] = nbv[i];
     for (int i = 0; i < d; ++i) {
-        int64_t pre = 1, post = 1;
+        int64_t pre = batch, post = 1;
         for (int k = 0; k < i; ++k) pre *= shape[k];
         for (int k = i + 1; k < d; ++k) post *= shape[k];
         GP_TRY(modeprod(h, cur, dst, mats[i], mav[i], nbv[i], ldm[i], trans, sq, pre, post));
@@ -595,28 +656,86 @@ __global__ void kron_post_kernel(const double* mean_raw, const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------
+// posterior draws (gpimhip_sample_kron); every kernel handles all S draws in one launch
+// ------------------------------------------------------------------------------------------
+// rows of the prior root R_i = Q_i diag(sqrt(max(lam_i, 0))) of axis ax:  out[r, j] = Q_i[idx[r], j] sqrt(max(lam_i[j], 0))
+// (Qt holds Q_i^T; idx was checked against the axis by the host side of the entry point)
+__global__ void kron_root_rows_kernel(KronDev dv, int ax, const int32_t* __restrict__ idx, int rows,
+                                      double* __restrict__ out) {
+    const int n = dv.n[ax];
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)rows * n) return;
+    const int r = (int)(e / n), j = (int)(e % n);
+    const double lam = dv.lam[dv.off[ax] + j];
+    out[e] = dv.Qt[dv.moff[ax] + (int64_t)j * n + idx[r]] * sqrt(lam > 0.0 ? lam : 0.0);
+}
+// zeta of every draw, the first PU entries of its row of z, as one contiguous (S, PU) tensor
+__global__ void kron_zeta_kernel(const double* __restrict__ z, int64_t zw, int64_t PU, int64_t total,
+                                 double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    out[e] = z[(e / PU) * zw + e % PU];
+}
+// g[s, j] <- y[j] - sqrt(s2) g[s, j] - sqrt(sigma) z_e[s, j]     (ze: the z_e part of draw 0; rows zw apart)
+__global__ void kron_resid_kernel(const double* __restrict__ y, const double* __restrict__ ze, int64_t zw, int64_t N,
+                                  int64_t total, const ThetaDev* __restrict__ th, double* __restrict__ g) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const int64_t s = e / N, j = e % N;
+    g[e] = y[j] - sqrt(th->var) * g[e] - sqrt(th->diag_add) * ze[s * zw + j];
+}
+// v[s, j] <- v[s, j] / D[j] in the eigenbasis of the training grid (the D of kron_dvec_kernel, none of its sums);
+// blockIdx.y strides the draws
+__global__ void kron_dscale_kernel(KronDev dv, const ThetaDev* __restrict__ th, int64_t S, double* __restrict__ v) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= dv.N) return;
+    int idx[KMAXD];
+    int64_t r = j;
+    for (int i = dv.d - 1; i >= 0; --i) { idx[i] = (int)(r % dv.n[i]); r /= dv.n[i]; }
+    double lam = th->var;           // the product in kron_dvec_kernel's order: a draw at z = 0 is the mean, bit for bit
+    for (int i = 0; i < dv.d; ++i) lam *= dv.lam[dv.off[i] + idx[i]];
+    const double D = lam + th->diag_add;
+    for (int64_t s = blockIdx.y; s < S; s += gridDim.y) v[s * dv.N + j] = v[s * dv.N + j] / D;
+}
+// out[s, j] <- sqrt(s2) g*[s, j] + s2 out[s, j] + sqrt(c) z_n[s, j],  c = (0 if noiseless else noise) + jitter;
+// mean[j] <- s2 mean[j] (the arithmetic of kron_post_kernel), by the threads of draw 0
+__global__ void kron_draw_kernel(const double* __restrict__ gs, const double* __restrict__ zn, int64_t zw, int64_t M,
+                                 int64_t total, const ThetaDev* __restrict__ th, int noiseless, double jitter,
+                                 double* __restrict__ mean, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const int64_t s = e / M, j = e % M;
+    const double s2 = th->var;
+    const double c = (noiseless ? 0.0 : th->noise) + jitter;
+    double v = fma(sqrt(s2), gs[e], s2 * out[e]);
+    if (c > 0.0) v = fma(sqrt(c), zn[s * zw + j], v);
+    out[e] = v;
+    if (s == 0) mean[j] = s2 * mean[j];
+}
+
+// ------------------------------------------------------------------------------------------
 // drivers
 // ------------------------------------------------------------------------------------------
-static int kron_cold_start(gpimhip_ctx* h, KronWs& w) {
+static int kron_cold_start(gpimhip_ctx* h, const KronDev& dv) {
     int nmax = 1;
-    for (int pr = 0; pr < w.dev.nprob; ++pr) nmax = std::max(nmax, w.dev.pn[pr]);
-    hipLaunchKernelGGL(kron_eye_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), w.dev.nprob), dim3(256), 0,
-                       h->stream, w.dev);
+    for (int pr = 0; pr < dv.nprob; ++pr) nmax = std::max(nmax, dv.pn[pr]);
+    hipLaunchKernelGGL(kron_eye_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), dv.nprob), dim3(256), 0,
+                       h->stream, dv);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
 
 // Splits every axis whose coordinates are centro-symmetric (c_a + c_{n-1-a} constant: any uniform grid) into a
 // symmetric and a skew-symmetric eigen-problem.  Needs the coordinates on the host: one small copy + sync per call.
-static int kron_plan_problems(gpimhip_ctx* h, KronWs& w) {
-    std::vector<double> c((size_t)w.sum_n);
-    HIP_TRY(hipMemcpyAsync(c.data(), w.dev.coords, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+static int kron_plan_problems(gpimhip_ctx* h, KronAxes& ax) {
+    std::vector<double> c((size_t)ax.sum_n);
+    HIP_TRY(hipMemcpyAsync(c.data(), ax.dev.coords, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    KronDev& dv = w.dev;
+    KronDev& dv = ax.dev;
     dv.nprob = 0;
     const bool allow = true;
-    for (int i = 0; i < w.d; ++i) {
-        const int n = w.n[i];
+    for (int i = 0; i < ax.d; ++i) {
+        const int n = ax.n[i];
         const double* ci = c.data() + dv.off[i];
         bool sym = allow && n >= 8;
         double scale = 1.0;
@@ -638,14 +757,14 @@ static int kron_plan_problems(gpimhip_ctx* h, KronWs& w) {
     return GPIMHIP_OK;
 }
 
-// K_i(u), its eigen-decomposition continued from the rotations in Vr (kron_cold_start() resets them), y~
-static int kron_decompose(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, const double* u, const double* y) {
-    const KronDev& dv = w.dev;
-    GP_TRY(launch_theta(h, m, u));
+// K_i at the lengthscales in h->theta and its eigen-decomposition (Qt, lam), continued from the rotations in Vr
+// (kron_cold_start() resets them), for every axis of the set
+static int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax) {
+    const KronDev& dv = ax.dev;
     int nmax = 1, pmax = 1;
-    for (int i = 0; i < w.d; ++i) nmax = std::max(nmax, w.n[i]);
+    for (int i = 0; i < ax.d; ++i) nmax = std::max(nmax, ax.n[i]);
     for (int pr = 0; pr < dv.nprob; ++pr) pmax = std::max(pmax, dv.pn[pr]);
-    hipLaunchKernelGGL(kron_axis_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), w.d), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(kron_axis_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), ax.d), dim3(256), 0, h->stream,
                        dv, h->theta);
     hipLaunchKernelGGL(kron_reduce_kernel, dim3((unsigned)(((int64_t)pmax * pmax + 255) / 256), dv.nprob), dim3(256), 0,
                        h->stream, dv);
@@ -662,6 +781,14 @@ static int kron_decompose(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, c
     hipLaunchKernelGGL(kron_assemble_kernel, dim3((unsigned)(((int64_t)pmax * nmax + 255) / 256), dv.nprob), dim3(256), 0,
                        h->stream, dv);
     HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// theta(u), the eigen-decomposition of the training axes, y~
+static int kron_decompose(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, const double* u, const double* y) {
+    const KronDev& dv = w.tr.dev;
+    GP_TRY(launch_theta(h, m, u));
+    GP_TRY(kron_eig_axes(h, w.tr));
     // y~ = (Q_1^T (x) ... (x) Q_d^T) y
     const double* mats[KMAXD]; int ld[KMAXD];
     for (int i = 0; i < w.d; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = w.n[i]; }
@@ -673,7 +800,7 @@ static int kron_decompose(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, c
 
 static int kron_loss_grad(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, const double* y, double* u, int do_adam,
                           double* loss_out, double* grad_out, const FinalizeIter* it) {
-    const KronDev& dv = w.dev;
+    const KronDev& dv = w.tr.dev;
     GP_TRY(kron_decompose(h, w, m, u, y));
     // M_i = Q_i^T E_i Q_i  (two mode products on the n_i x n_i "tensor") and its diagonal
     int nmax = 1;
@@ -714,11 +841,99 @@ static int kron_prepare(gpimhip_ctx* h, const gpimhip_model_t* m, int32_t d, con
     h->nbatch = 1;
     GP_TRY(ws_ensure(h, 1));                   // theta, Adam state, iteration counter
     GP_TRY(kron_ensure(h, d, n, w));
-    HIP_TRY(hipMemcpyAsync(const_cast<double*>((*w)->dev.coords), axes, (size_t)(*w)->sum_n * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>((*w)->tr.dev.coords), axes, (size_t)(*w)->tr.sum_n * sizeof(double),
                            hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(kron_plan_problems(h, **w));
-    return kron_cold_start(h, **w);
+    GP_TRY(kron_plan_problems(h, (*w)->tr));
+    return kron_cold_start(h, (*w)->tr.dev);
+}
+
+// the prediction workspace for the test grid of the orders n_test[] and its coordinates
+static int kron_predict_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* n_test, const double* axes_test) {
+    int64_t M = 1, sum_m = 0, sum_mn = 0, pmax = w.N;
+    {
+        int64_t cur = w.N;
+        for (int i = 0; i < d; ++i) {
+            if (n_test[i] < 1) return GPIMHIP_E_BADARG;
+            M *= n_test[i]; sum_m += n_test[i]; sum_mn += (int64_t)n_test[i] * w.n[i];
+            cur = cur / w.n[i] * n_test[i];
+            pmax = std::max(pmax, cur);
+        }
+    }
+    bool same = w.parena && w.M == M && w.pmax == pmax;
+    for (int i = 0; i < d && same; ++i) same = w.m[i] == n_test[i];
+    if (!same) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        kron_free(h, w.parena, w.parena_count);
+        const int64_t count = sum_m + 2 * sum_mn + 2 * pmax + 64;
+        GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP prediction workspace)", w.parena, w.parena_count));
+        double* p = w.parena;
+        auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
+        w.tcoords = take(sum_m); w.Ks = take(sum_mn); w.Bs = take(sum_mn); w.p1 = take(pmax); w.p2 = take(pmax);
+        int64_t ko = 0;
+        for (int i = 0; i < KMAXD; ++i) {
+            w.m[i] = i < d ? n_test[i] : 1;
+            w.koff[i] = ko;
+            if (i < d) ko += (int64_t)n_test[i] * w.n[i];
+        }
+        w.M = M; w.pmax = pmax;
+    }
+    HIP_TRY(hipMemcpyAsync(w.tcoords, axes_test, (size_t)sum_m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return GPIMHIP_OK;
+}
+
+// cross-covariances per axis and B_i = Ks_i Q_i
+static int kron_cross_factors(gpimhip_ctx* h, KronWs& w) {
+    const KronDev& dv = w.tr.dev;
+    int toff = 0;
+    for (int i = 0; i < w.d; ++i) {
+        const int64_t cnt = (int64_t)w.m[i] * w.n[i];
+        hipLaunchKernelGGL(kron_cross_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, dv, h->theta,
+                           w.tcoords, toff, w.m[i], i, w.Ks + w.koff[i]);
+        GP_TRY(modeprod(h, w.Ks + w.koff[i], w.Bs + w.koff[i], dv.Qt + dv.moff[i], w.n[i], w.n[i], w.n[i], 0, 0, w.m[i], 1));
+        toff += w.m[i];
+    }
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// the workspace of gpimhip_sample_kron: the gathered root rows, the index maps, zeta of every draw and two buffers of
+// S * smax doubles for the mode products (smax: the largest tensor any of the four chains U -> n, n -> n, n -> m, U -> m
+// passes through)
+static int kron_sample_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* nu, int64_t S, int64_t* PU_out) {
+    const int32_t* lo[2] = {w.n, w.m};
+    int64_t PU = 1, smax = std::max(w.N, w.M), sum_gu = 0, sum_tu = 0;
+    for (int i = 0; i < d; ++i) { PU *= nu[i]; sum_gu += (int64_t)w.n[i] * nu[i]; sum_tu += (int64_t)w.m[i] * nu[i]; }
+    for (int c = 0; c < 2; ++c) {
+        int64_t cur = PU;
+        for (int i = 0; i < d; ++i) { cur = cur / nu[i] * lo[c][i]; smax = std::max(smax, cur); }
+    }
+    {
+        int64_t cur = w.N;
+        for (int i = 0; i < d; ++i) { cur = cur / w.n[i] * w.m[i]; smax = std::max(smax, cur); }
+    }
+    *PU_out = PU;
+    int64_t key[3 + 3 * KMAXD] = {S, d, smax};
+    for (int i = 0; i < d; ++i) { key[3 + i] = nu[i]; key[3 + KMAXD + i] = w.n[i]; key[3 + 2 * KMAXD + i] = w.m[i]; }
+    if (w.sarena && memcmp(key, w.s_key, sizeof(key)) == 0) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    kron_free(h, w.sarena, w.sarena_count);
+    int64_t sum_n = 0, sum_m = 0;
+    for (int i = 0; i < d; ++i) { sum_n += w.n[i]; sum_m += w.m[i]; }
+    const int64_t count = sum_gu + sum_tu + (sum_n + sum_m + 4) / 2 + S * PU + 2 * S * smax + 32;
+    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP posterior-draw workspace)", w.sarena, w.sarena_count));
+    double* p = w.sarena;
+    auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
+    w.RG = take(sum_gu); w.RT = take(sum_tu);
+    w.ic = (int32_t*)take((sum_n + 1) / 2); w.it = (int32_t*)take((sum_m + 1) / 2);
+    w.Zc = take(S * PU); w.sa = take(S * smax); w.sb = take(S * smax);
+    int64_t go = 0, to = 0;
+    for (int i = 0; i < KMAXD; ++i) {
+        w.rgoff[i] = go; w.rtoff[i] = to;
+        if (i < d) { go += (int64_t)w.n[i] * nu[i]; to += (int64_t)w.m[i] * nu[i]; }
+    }
+    memcpy(w.s_key, key, sizeof(key));
+    return GPIMHIP_OK;
 }
 
 extern "C" {
@@ -757,54 +972,12 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
     KronWs* wp;
     GP_TRY(kron_prepare(h, m, d, n, axes, &wp));
     KronWs& w = *wp;
-    const KronDev& dv = w.dev;
-    // prediction workspace
-    int64_t M = 1, sum_m = 0, sum_mn = 0, pmax = w.N;
-    {
-        int64_t cur = w.N;
-        for (int i = 0; i < d; ++i) {
-            if (n_test[i] < 1) return GPIMHIP_E_BADARG;
-            M *= n_test[i]; sum_m += n_test[i]; sum_mn += (int64_t)n_test[i] * w.n[i];
-            cur = cur / w.n[i] * n_test[i];
-            pmax = std::max(pmax, cur);
-        }
-    }
-    bool same = w.parena && w.M == M && w.pmax == pmax;
-    for (int i = 0; i < d && same; ++i) same = w.m[i] == n_test[i];
-    if (!same) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (w.parena) { (void)hipFree(w.parena); h->bytes -= w.parena_count * (int64_t)sizeof(double); w.parena = nullptr; }
-        const int64_t count = sum_m + 2 * sum_mn + 2 * pmax + 64;
-        void* q = nullptr;
-        if (hipMalloc(&q, (size_t)count * sizeof(double)) != hipSuccess) {
-            gpim_set_error("hipMalloc failed (structured-GP prediction workspace)");
-            return GPIMHIP_E_NOMEM;
-        }
-        w.parena = (double*)q; w.parena_count = count; h->bytes += count * (int64_t)sizeof(double);
-        double* p = w.parena;
-        auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
-        w.tcoords = take(sum_m); w.Ks = take(sum_mn); w.Bs = take(sum_mn); w.p1 = take(pmax); w.p2 = take(pmax);
-        int64_t ko = 0;
-        for (int i = 0; i < KMAXD; ++i) {
-            w.m[i] = i < d ? n_test[i] : 1;
-            w.koff[i] = ko;
-            if (i < d) ko += (int64_t)n_test[i] * w.n[i];
-        }
-        w.M = M; w.pmax = pmax;
-    }
-    HIP_TRY(hipMemcpyAsync(w.tcoords, axes_test, (size_t)sum_m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    const KronDev& dv = w.tr.dev;
+    GP_TRY(kron_predict_ws(h, w, d, n_test, axes_test));
+    const int64_t M = w.M;
     GP_TRY(kron_decompose(h, w, m, u, y));
     hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
-    // cross-covariances per axis and B_i = Ks_i Q_i
-    int toff = 0;
-    for (int i = 0; i < d; ++i) {
-        const int64_t cnt = (int64_t)w.m[i] * w.n[i];
-        hipLaunchKernelGGL(kron_cross_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, dv, h->theta,
-                           w.tcoords, toff, w.m[i], i, w.Ks + w.koff[i]);
-        GP_TRY(modeprod(h, w.Ks + w.koff[i], w.Bs + w.koff[i], dv.Qt + dv.moff[i], w.n[i], w.n[i], w.n[i], 0, 0, w.m[i], 1));
-        toff += w.m[i];
-    }
-    HIP_TRY(hipGetLastError());
+    GP_TRY(kron_cross_factors(h, w));
     // mean = s2 * ((x) B_i) alpha~        (B_i = Ks_i Q_i maps eigen-coordinates straight to test points)
     const double* mats[KMAXD]; int ld[KMAXD];
     for (int i = 0; i < d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
@@ -817,6 +990,142 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
     hipLaunchKernelGGL(kron_post_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, mean_out, res, M,
                        h->theta, mean_out, var_out);
     HIP_TRY(hipGetLastError());
+    return finish_and_check(h);
+}
+
+// Joint posterior draws on the product test grid by Matheron's rule with every factor a Kronecker product (DESIGN.md
+// section 21).  Stage timers: 0 the union axes' eigen-decomposition, 1 the training axes' (with y~), 2 the prior's root
+// rows and mode products, 3 the update's factors and mode products (the mean's among them), 5 the epilogue.
+int gpimhip_sample_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
+                        const double* y, const double* u, const int32_t* n_test, const double* axes_test,
+                        const int32_t* n_union, const double* axes_union, const int32_t* idx_train, const int32_t* idx_test,
+                        const double* z, int32_t S, int32_t noiseless, double jitter, double* mean_out, double* out) {
+    if (!h || !m || !y || !u || !n || !n_test || !axes_test || !n_union || !axes_union || !idx_train || !idx_test || !z ||
+        !mean_out || !out) {
+        gpim_set_error("gpimhip_sample_kron: a null argument (every pointer of the entry point is required)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (S < 1 || !(jitter >= 0.0) || !(jitter < HUGE_VAL)) {
+        gpim_set_error("gpimhip_sample_kron: needs S >= 1 and a finite jitter >= 0");
+        return GPIMHIP_E_BADARG;
+    }
+    if (d < 1 || d > KMAXD) {
+        gpim_set_error("gpimhip_sample_kron: d must be between 1 and 4");
+        return GPIMHIP_E_BADARG;
+    }
+    // the union axes and the index maps (host arrays): every index inside its union axis, which is no longer than the two
+    // axes together and no shorter than either; shared: the union axes ARE the training axes (the test grid is the training
+    // grid or a crop of it), the training decomposition serves as the union one
+    bool shared = true;
+    int64_t sum_n = 0, sum_m = 0, sum_u = 0;
+    for (int i = 0, oc = 0, ot = 0; i < d; ++i) {
+        if (n[i] < 1 || n_test[i] < 1) {
+            gpim_set_error("gpimhip_sample_kron: every axis of the training and of the test grid needs at least one coordinate");
+            return GPIMHIP_E_BADARG;
+        }
+        if (n_union[i] > 4096) {
+            char msg[200];
+            snprintf(msg, sizeof(msg), "gpimhip_sample_kron: the union of the training and the test coordinates of axis %d has "
+                     "%d entries; the eigen-solver takes at most 4096", i, (int)n_union[i]);
+            gpim_set_error(msg);
+            return GPIMHIP_E_BADARG;
+        }
+        if (n_union[i] < n[i] || (int64_t)n_union[i] > (int64_t)n[i] + n_test[i]) {
+            gpim_set_error("gpimhip_sample_kron: n_union[i] must lie between n[i] and n[i] + n_test[i]");
+            return GPIMHIP_E_BADARG;
+        }
+        for (int a = 0; a < n[i]; ++a) {
+            const int32_t v = idx_train[oc + a];
+            if (v < 0 || v >= n_union[i]) { gpim_set_error("gpimhip_sample_kron: idx_train outside its union axis"); return GPIMHIP_E_BADARG; }
+            shared = shared && v == a;
+        }
+        for (int a = 0; a < n_test[i]; ++a) {
+            const int32_t v = idx_test[ot + a];
+            if (v < 0 || v >= n_union[i]) { gpim_set_error("gpimhip_sample_kron: idx_test outside its union axis"); return GPIMHIP_E_BADARG; }
+        }
+        shared = shared && n_union[i] == n[i];
+        oc += n[i]; ot += n_test[i];
+        sum_n += n[i]; sum_m += n_test[i]; sum_u += n_union[i];
+    }
+    KronWs* wp;
+    GP_TRY(kron_prepare(h, m, d, n, axes, &wp));
+    KronWs& w = *wp;
+    const KronDev& dv = w.tr.dev;
+    GP_TRY(kron_predict_ws(h, w, d, n_test, axes_test));
+    if (!shared) {
+        GP_TRY(kron_axes_ensure(h, w.un, d, n_union, false));
+        HIP_TRY(hipMemcpyAsync(const_cast<double*>(w.un.dev.coords), axes_union, (size_t)sum_u * sizeof(double),
+                               hipMemcpyDeviceToDevice, h->stream));
+        GP_TRY(kron_plan_problems(h, w.un));
+        GP_TRY(kron_cold_start(h, w.un.dev));
+    }
+    const KronAxes& ua = shared ? w.tr : w.un;
+    const KronDev& du = ua.dev;
+    int64_t PU = 0;
+    GP_TRY(kron_sample_ws(h, w, d, n_union, S, &PU));
+    HIP_TRY(hipMemcpyAsync(w.ic, idx_train, (size_t)sum_n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(w.it, idx_test, (size_t)sum_m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // the host arrays are the caller's
+    const int64_t N = w.N, M = w.M, zw = PU + N + M;
+    const double* mats[KMAXD]; int ld[KMAXD];
+    double* res;
+    {
+        StageTimer t(h, 1);
+        GP_TRY(kron_decompose(h, w, m, u, y));
+        hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
+    }
+    if (!shared) {
+        StageTimer t(h, 0);
+        GP_TRY(kron_eig_axes(h, w.un));
+    }
+    double* gG;
+    {   // the prior on the training grid: g_G / sqrt(s2) = ((x) R_i[ic_i, :]) zeta
+        StageTimer t(h, 2);
+        for (int i = 0, oc = 0, ot = 0; i < d; ++i) {
+            const int U = ua.n[i];
+            hipLaunchKernelGGL(kron_root_rows_kernel, dim3((unsigned)(((int64_t)w.n[i] * U + 255) / 256)), dim3(256), 0, h->stream,
+                               du, i, w.ic + oc, w.n[i], w.RG + w.rgoff[i]);
+            hipLaunchKernelGGL(kron_root_rows_kernel, dim3((unsigned)(((int64_t)w.m[i] * U + 255) / 256)), dim3(256), 0, h->stream,
+                               du, i, w.it + ot, w.m[i], w.RT + w.rtoff[i]);
+            oc += w.n[i]; ot += w.m[i];
+        }
+        hipLaunchKernelGGL(kron_zeta_kernel, dim3((unsigned)((S * PU + 255) / 256)), dim3(256), 0, h->stream, z, zw, PU,
+                           (int64_t)S * PU, w.Zc);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < d; ++i) { mats[i] = w.RG + w.rgoff[i]; ld[i] = ua.n[i]; }
+        GP_TRY(tensor_apply(h, d, ua.n, w.n, mats, ld, 0, 0, w.Zc, w.sa, w.sb, &gG, S));
+    }
+    {   // the update: out <- ((x) Ks_i Q_i) D^-1 ((x) Q_i^T) (y - sqrt(s2) g_G - sqrt(sigma) z_e), and the mean's
+        StageTimer t(h, 3);
+        GP_TRY(kron_cross_factors(h, w));
+        hipLaunchKernelGGL(kron_resid_kernel, dim3((unsigned)((S * N + 255) / 256)), dim3(256), 0, h->stream, y, z + PU, zw, N,
+                           (int64_t)S * N, h->theta, gG);
+        double* other = gG == w.sa ? w.sb : w.sa;
+        for (int i = 0; i < d; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = w.n[i]; }
+        GP_TRY(tensor_apply(h, d, w.n, w.n, mats, ld, 0, 0, gG, other, gG, &res, S));
+        hipLaunchKernelGGL(kron_dscale_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)std::min<int64_t>(S, 64)), dim3(256), 0,
+                           h->stream, dv, h->theta, S, res);
+        HIP_TRY(hipGetLastError());
+        other = res == w.sa ? w.sb : w.sa;
+        for (int i = 0; i < d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
+        double* upd;
+        GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 0, res, other, res, &upd, S));
+        HIP_TRY(hipMemcpyAsync(out, upd, (size_t)S * M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 0, w.at, w.p1, w.p2, &res));     // the launches of predict's mean
+        HIP_TRY(hipMemcpyAsync(mean_out, res, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    double* gs;
+    {   // the prior on the test grid, from the same zeta
+        StageTimer t(h, 2);
+        for (int i = 0; i < d; ++i) { mats[i] = w.RT + w.rtoff[i]; ld[i] = ua.n[i]; }
+        GP_TRY(tensor_apply(h, d, ua.n, w.m, mats, ld, 0, 0, w.Zc, w.sa, w.sb, &gs, S));
+    }
+    {
+        StageTimer t(h, 5);
+        hipLaunchKernelGGL(kron_draw_kernel, dim3((unsigned)((S * M + 255) / 256)), dim3(256), 0, h->stream, gs, z + PU + N, zw,
+                           M, (int64_t)S * M, h->theta, noiseless, jitter, mean_out, out);
+        HIP_TRY(hipGetLastError());
+    }
     return finish_and_check(h);
 }
 

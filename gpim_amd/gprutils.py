@@ -121,6 +121,41 @@ def grid_axes(X):
     return axes, (ctypes.c_int32 * d)(*[len(c) for c in axes])
 
 
+def union_axes(axes_train, axes_test):
+    """Per grid axis, the sorted union of the training and the test coordinates with the position of every coordinate in
+    it (gpim_amd extension: reconstructor.sample(method='kron')).
+
+    axes_train, axes_test: d coordinate vectors each.  Coordinates within ``1e-12 * max(1, max|coordinate|)`` of their
+    neighbour in sorted order merge (the tolerance of the structured solver's symmetry test); a merged coordinate is
+    represented by a training coordinate when it holds one, so axes that bring nothing new leave the training axis as it
+    is.  Returns (axes_union, idx_train, idx_test): d float64 vectors and two lists of d int32 index vectors with
+    ``axes_union[i][idx_train[i]] ~ axes_train[i]`` and ``axes_union[i][idx_test[i]] ~ axes_test[i]``."""
+    if len(axes_train) != len(axes_test):
+        raise ValueError("union_axes needs as many test axes as training axes; got %d and %d"
+                         % (len(axes_train), len(axes_test)))
+    au, ic, it = [], [], []
+    for c, t in zip(axes_train, axes_test):
+        c = np.asarray(c, dtype=np.float64).ravel()
+        t = np.asarray(t, dtype=np.float64).ravel()
+        both = np.concatenate([c, t])
+        if not np.isfinite(both).all():
+            raise ValueError("union_axes needs finite coordinates")
+        tol = 1e-12 * max(1.0, float(np.abs(both).max()))
+        order = np.argsort(both, kind="stable")
+        sv = both[order]
+        first = np.concatenate([[True], np.diff(sv) > tol])
+        group = np.cumsum(first) - 1
+        u = sv[first].copy()
+        from_train = order < len(c)
+        u[group[from_train][::-1]] = sv[from_train][::-1]       # the first training coordinate of a group stands for it
+        idx = np.empty(len(both), dtype=np.int32)
+        idx[order] = group
+        au.append(u)
+        ic.append(idx[:len(c)].copy())
+        it.append(idx[len(c):].copy())
+    return au, ic, it
+
+
 def reflection_blocks(X, y, axes):
     """Symmetry reduction of an exact GP on a COMPLETE grid (gpim_amd extension; role of the reference's structured class
     gpim/gpreg/skgpr.py:399-448 for kernels that do not factorise over the axes -- csrc/engine.hip: kmat_refl_kernel).
