@@ -131,6 +131,17 @@ _PROTOS = {
     "gpimhip_predict_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp,
                                             ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp]),
+    # (h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, u, ...)
+    "gpimhip_pkron_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                              c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "gpimhip_fit_pkron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                         c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
+    "gpimhip_predict_pkron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                             c_dp, c_dp, c_dp, c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), c_dp,
+                                             c_dp, c_dp]),
     "gpimhip_sample_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp,
                                            ctypes.POINTER(ctypes.c_int32), c_dp,

@@ -5,7 +5,7 @@ _solvers.py -- the host layer between the reconstructors and the C ABI (include/
     smreconstructor; a class supplies its fit call, what it records per history row and its messages.
   * ``DeviceBlocks``: the device side of a blocks dict (gprutils.reflection_blocks* / border_blocks*), entered with
     ``_lib.reflection``.
-  * ``Dense`` / ``Sparse`` / ``Kron`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
+  * ``Dense`` / ``Sparse`` / ``Kron`` / ``Columns`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
     fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out), each returning the
     library's status.  ``SpectralBlocks``: the reflection / border path of ``smreconstructor`` (one shared parameter vector).
     ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
@@ -275,6 +275,121 @@ class Kron(Dense):
                                                  ptr(au_d), i32(np.concatenate(ic)),
                                                  i32(np.concatenate(it)), ptr(z), z.shape[0], int(bool(noiseless)),
                                                  float(jitter), ptr(mean), ptr(out))
+
+
+class Columns(Dense):
+    """Exact RBF GP on a grid whose missing points are whole columns (a cube measured at a sparse set of pixels, an image
+    with whole rows missing): J dense blocks of the N_s observed ragged points, one per eigen-direction of the complete axes,
+    in one lock-step batch (gprutils.column_blocks; csrc/pkron.hip).  ``o._u``, the loss, the history
+    and the posterior are those of ``Dense`` on the same observations."""
+    structured = True
+    _NO_DRAWS = "posterior draws are not built for solver='columns'"
+
+    def __init__(self, C):
+        self.C = C
+        self.taxes = None                               # the test grid's d coordinate vectors; None: the training points
+
+    def attach(self, o):
+        C = self.C
+        i32 = lambda v: (ctypes.c_int32 * len(v))(*[int(k) for k in v])
+        self.Xs_d, self.Y_d = o._to_device(C["Xs"]), o._to_device(C["Y"])
+        self.axes_d = o._to_device(np.concatenate(C["axes_c"]))
+        self.n_c, self.perm = i32([len(c) for c in C["axes_c"]]), i32(C["perm"])
+        self._train_order = None
+
+    def new_test_grid(self, Xtest):
+        self.taxes = gprutils.grid_axes(Xtest)[0]
+
+    def _model(self, o):
+        C = self.C
+        return (*_head(o), ptr(self.Xs_d), self.Xs_d.shape[0], len(C["ragged"]), len(C["complete"]), self.n_c, self.perm,
+                ptr(self.axes_d), ptr(self.Y_d))
+
+    def fit(self, o, lr, T, hist, loss):
+        return o._handle.lib.gpimhip_fit_pkron(*self._model(o), ptr(o._u), lr, T, ptr(hist), ptr(loss))
+
+    def nll_grad(self, o, out):
+        return o._handle.lib.gpimhip_pkron_nll_grad(*self._model(o), ptr(o._u), *_loss_grad(out))
+
+    def _predict_product(self, o, rows_d, caxes, mean, var):
+        """The posterior on (the ragged rows rows_d (M_s, p)) x (the product of the complete axes' vectors caxes), M_s x M_c."""
+        i32 = lambda v: (ctypes.c_int32 * len(v))(*[int(k) for k in v])
+        caxes_d = o._to_device(np.concatenate(caxes))       # (referenced until the call returns)
+        return o._handle.lib.gpimhip_predict_pkron(*self._model(o), ptr(o._u), ptr(rows_d), rows_d.shape[0],
+                                                   i32([len(c) for c in caxes]), ptr(caxes_d), ptr(mean), ptr(var))
+
+    def _predict_axes(self, o, taxes, mean, var):
+        """The posterior on the product grid of the d coordinate vectors taxes, in the grid's own (C) order."""
+        C = self.C
+        shape = [len(t) for t in taxes]
+        if int(np.prod(shape, dtype=np.int64)) != mean.shape[0]:
+            raise NotImplementedError("solver='columns' predicts on product grids: %d test rows do not fill a grid of shape %s"
+                                      % (mean.shape[0], tuple(shape)))
+        rows = np.array(np.meshgrid(*[taxes[i] for i in C["ragged"]], indexing="ij")).reshape(len(C["ragged"]), -1).T
+        mp, vp = torch.empty_like(mean), torch.empty_like(var)
+        rc = self._predict_product(o, o._to_device(np.ascontiguousarray(rows)), [taxes[i] for i in C["complete"]], mp, vp)
+        pshape = [shape[i] for i in C["perm"]]
+        mean.copy_(mp.reshape(pshape).permute(C["inv"]).reshape(-1))
+        var.copy_(vp.reshape(pshape).permute(C["inv"]).reshape(-1))
+        return rc
+
+    def predict_grid(self, o, mean, var):
+        if self.taxes is not None:
+            return self._predict_axes(o, self.taxes, mean, var)
+        # no test grid: the training points, (observed ragged points) x (complete axes), back in their row-major order
+        C = self.C
+        if self._train_order is None:
+            Ns, J = C["Y"].shape
+            rshape = [C["shape"][i] for i in C["ragged"]]
+            P = np.full((int(np.prod(rshape)), J), -1, dtype=np.int64)
+            P[C["obs"]] = np.arange(Ns * J).reshape(Ns, J)
+            P = P.reshape([C["shape"][i] for i in C["perm"]]).transpose(C["inv"]).ravel()
+            self._train_order = torch.from_numpy(P[P >= 0]).to(o._dev)
+        mp, vp = torch.empty_like(mean), torch.empty_like(var)
+        rc = self._predict_product(o, self.Xs_d, C["axes_c"], mp, vp)
+        torch.index_select(mp, 0, self._train_order, out=mean)
+        torch.index_select(vp, 0, self._train_order, out=var)
+        return rc
+
+    def predict(self, o, Xs, mean, var):
+        """Arbitrary rows, in any order, are served when they are (a set of ragged points) x (a product of coordinate vectors
+        for the complete axes): every block then shares the complete axes' cross-covariances.  Rows with a NaN give NaN."""
+        C = self.C
+        X = Xs.cpu().numpy()[:, C["perm"]]
+        p = len(C["ragged"])
+        fin = np.isfinite(X).all(axis=1)
+        Xf = X[fin]
+        rows, ridx = np.unique(Xf[:, :p], axis=0, return_inverse=True)
+        caxes, cidx = [], np.zeros(len(Xf), dtype=np.int64)
+        for k in range(p, X.shape[1]):
+            vals, inv = np.unique(Xf[:, k], return_inverse=True)
+            caxes.append(vals)
+            cidx = cidx * len(vals) + inv
+        Mc = int(np.prod([len(c) for c in caxes], dtype=np.int64))
+        flat = ridx.reshape(-1) * Mc + cidx
+        if len(Xf) == 0 or len(rows) * Mc != len(Xf) or len(np.unique(flat)) != len(Xf):
+            raise NotImplementedError("solver='columns' predicts on product test grids: the %d test rows are not (a set of "
+                                      "points of the ragged axes %s) x (a product of coordinate vectors for the complete axes "
+                                      "%s)" % (len(Xf), C["ragged"], C["complete"]))
+        mp = torch.empty(len(Xf), dtype=_F64, device=o._dev)
+        vp = torch.empty_like(mp)
+        rc = self._predict_product(o, o._to_device(np.ascontiguousarray(rows)), caxes, mp, vp)
+        flat_d = torch.from_numpy(flat).to(o._dev)
+        if fin.all():
+            torch.index_select(mp, 0, flat_d, out=mean)
+            torch.index_select(vp, 0, flat_d, out=var)
+        else:
+            fin_d = torch.from_numpy(fin).to(o._dev)
+            mean.fill_(float("nan"))
+            var.fill_(float("nan"))
+            mean[fin_d] = mp[flat_d]
+            var[fin_d] = vp[flat_d]
+        return rc
+
+    def sample(self, o, *args):
+        raise NotImplementedError(self._NO_DRAWS)
+
+    sample_pathwise = sample_blocks = sample_border = sample_kron = sample
 
 
 class Reflection(Dense):

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "border.hpp"
 #include "vgp.hpp"
+#include "pkron.hpp"
 #include "sm.hpp"
 #include "sample.hpp"
 
@@ -758,6 +759,7 @@ int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<
 }
 
 static void vgp_release(gpimhip_ctx* h);
+static void pkron_release(gpimhip_ctx* h);
 static void sm_release(gpimhip_ctx* h);
 static void sample_release(gpimhip_ctx* h);
 static int64_t sample_bytes(const gpimhip_ctx* h);
@@ -826,6 +828,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     vfe_release(h);
     kron_release(h);
     vgp_release(h);
+    pkron_release(h);
     sm_release(h);
     border_release(h);
     sample_release(h);
@@ -1880,6 +1883,308 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
     double* vblk = w->pred + (int64_t)T * M;
     GP_TRY(predict_cols(h, m, X, 0, N, T, Xs, M, mblk, vblk));
     GP_TRY(launch_vgp_combine(h, T, M, w->st, mblk, vblk, mean_out, var_out));
+    return finish_and_check(h);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// dense-by-Kronecker blocks (gpimhip_pkron_nll_grad / gpimhip_fit_pkron / gpimhip_predict_pkron; pkron.hip, DESIGN.md section
+// 22): a grid whose missing points are whole columns.  J = prod n_i blocks s2 lambda_j K_s + sigma I of the N_s observed ragged
+// points run in lock-step through the batched engine (B = J, shared X_s); the complete axes are a KronAxes set of kron.hip.
+// ------------------------------------------------------------------------------------------
+struct PkronWs {
+    KronAxes ax;                                        // the complete axes: K_i, E_i, Q_i, lambda_i, Mm_i, mdiag_i
+    ThetaDev* th3 = nullptr;                            // PK_TH_MODEL, PK_TH_AXES, PK_TH_UNIT
+    double* lamj = nullptr; int64_t lamj_cap = 0;       // J: lambda_j
+    double* yt = nullptr; int64_t yt_cap = 0;           // 2 x N_s J: the mode products of the projection
+    double* Ks = nullptr; int64_t ks_cap = 0;           // np x ld: K_s at variance 1
+    double* Bp = nullptr; int64_t bp_cap = 0;           // Jp x np: beta, zero on the padding (Jp = J padded to 128)
+    double* W = nullptr; int64_t w_cap = 0;             // Jp x np: K_s B
+    double* Z = nullptr; int64_t z_cap = 0;             // dc x J x np: W x_i Mm_i
+    double* bsum = nullptr; int64_t bsum_cap = 0;       // J x PK_SUMS
+    // prediction (chunks of mc ragged test rows)
+    double* colpart = nullptr; int64_t colpart_cap = 0; // J x nb x mc
+    double* G = nullptr; int64_t g_cap = 0;             // Jp x mc: K*_s B
+    double* Q = nullptr; int64_t q_cap = 0;             // J x mc: k*^T M_j k*
+    double* pp = nullptr; int64_t pp_cap = 0;           // 4 x pmax x mc: the mode products of mean and variance
+    double* cross = nullptr; int64_t cross_cap = 0;     // 2 x sum m_i n_i: K*_i and K*_i Q_i
+};
+static void pkron_release(gpimhip_ctx* h) {
+    PkronWs* w = (PkronWs*)h->pkron;
+    if (!w) return;
+    kron_axes_free(h, w->ax);
+    dev_free(h, &w->th3, 3);
+    dev_free(h, &w->lamj, w->lamj_cap);
+    dev_free(h, &w->yt, w->yt_cap);
+    dev_free(h, &w->Ks, w->ks_cap);
+    dev_free(h, &w->Bp, w->bp_cap);
+    dev_free(h, &w->W, w->w_cap);
+    dev_free(h, &w->Z, w->z_cap);
+    dev_free(h, &w->bsum, w->bsum_cap);
+    dev_free(h, &w->colpart, w->colpart_cap);
+    dev_free(h, &w->G, w->g_cap);
+    dev_free(h, &w->Q, w->q_cap);
+    dev_free(h, &w->pp, w->pp_cap);
+    dev_free(h, &w->cross, w->cross_cap);
+    delete w;
+    h->pkron = nullptr;
+}
+static int pkron_bad(const char* what) {
+    gpim_set_error(std::string("dense-by-Kronecker blocks: ") + what);
+    return GPIMHIP_E_BADARG;
+}
+static int pkron_check(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                       const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, PkronMap* mp) {
+    if (!h || !m || !Xs || !n_c || !axes_c || !Y || Ns < 1) return GPIMHIP_E_BADARG;
+    FP64_ONLY(h);
+    GP_TRY(check_model(m));
+    if (m->kernel != GPIMHIP_KERNEL_RBF) return pkron_bad("only the RBF kernel factorises over the complete axes");
+    if (h->refl.mask) return pkron_bad("the handle is in reflection mode (gpimhip_set_reflection(h, 0, ...) first)");
+    if (p < 1 || dc < 1 || p + dc != m->dim) return pkron_bad("needs p >= 1 ragged and dc >= 1 complete axes with p + dc = dim");
+    memset(mp, 0, sizeof(*mp));
+    mp->p = p; mp->dc = dc;
+    int64_t J = 1;
+    int seen = 0;
+    for (int k = 0; k < m->dim; ++k) {
+        const int a = perm ? perm[k] : k;
+        if (a < 0 || a >= m->dim || (seen >> a & 1)) return pkron_bad("perm is not a permutation of the model's axes");
+        seen |= 1 << a;
+        mp->perm[k] = a;
+    }
+    for (int i = 0; i < dc; ++i) {
+        if (n_c[i] < 1 || n_c[i] > 4096) return pkron_bad("a complete axis takes 1 .. 4096 points (the eigen-solver's limit)");
+        mp->nc[i] = n_c[i];
+        J *= n_c[i];
+        if (J > 65535) return pkron_bad("more than 65535 blocks (the batched engine's cap)");
+    }
+    mp->J = (int)J;
+    return GPIMHIP_OK;
+}
+static int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, const double* axes_c, int64_t Ns, PkronWs** out) {
+    HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = mp.J;
+    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
+    GP_TRY(ws_ensure_padded(h, Ns));
+    PkronWs* w = (PkronWs*)h->pkron;
+    if (!w) {
+        w = new PkronWs();
+        h->pkron = w;
+        GP_TRY(dev_alloc(h, &w->th3, 3));
+    }
+    const int64_t np = h->np, J = mp.J, Jp = pad_to(J, NB);
+    GP_TRY(dev_grow(h, &w->lamj, &w->lamj_cap, J));
+    GP_TRY(dev_grow(h, &w->yt, &w->yt_cap, 2 * Ns * J));
+    GP_TRY(dev_grow(h, &w->Ks, &w->ks_cap, np * h->ld));
+    GP_TRY(dev_grow(h, &w->Bp, &w->bp_cap, Jp * np));
+    GP_TRY(dev_grow(h, &w->W, &w->w_cap, Jp * np));
+    GP_TRY(dev_grow(h, &w->Z, &w->z_cap, (int64_t)mp.dc * J * np));
+    GP_TRY(dev_grow(h, &w->bsum, &w->bsum_cap, J * PK_SUMS));
+    // the rows of the padding of B (a buffer that served a larger J may hold an earlier beta there)
+    if (Jp > J) HIP_TRY(hipMemsetAsync(w->Bp + J * np, 0, (size_t)((Jp - J) * np) * sizeof(double), h->stream));
+    GP_TRY(kron_axes_ensure(h, w->ax, mp.dc, n_c, true));
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(w->ax.dev.coords), axes_c, (size_t)w->ax.sum_n * sizeof(double),
+                           hipMemcpyDeviceToDevice, h->stream));
+    GP_TRY(kron_plan_problems(h, w->ax));
+    GP_TRY(kron_cold_start(h, w->ax.dev));
+    *out = w;
+    return GPIMHIP_OK;
+}
+// the blocks' sub-model: the p ragged columns of X_s (the blocks' theta carry their lengthscales)
+static gpimhip_model_t pkron_submodel(const gpimhip_model_t* m, int p) {
+    gpimhip_model_t ms = *m;
+    ms.dim = p;
+    ms.n_ls = p;
+    return ms;
+}
+// C (Jp x cols) = B (Jp x np: beta, one block per row) x R (np x cols, row stride ldr): one rectangle launch of the tile
+// engine on a single problem
+static int pkron_times_b(gpimhip_ctx* h, const PkronWs* w, int J, const double* R, int64_t ldr, int64_t cols, double* C,
+                         int64_t ldc) {
+    const int64_t np = h->np;
+    GemmArgs g = gemm_args(w->Bp, np, R, ldr, C, ldc, 1.0, 0.0, nullptr, 0, 0);
+    g.rect_rows = (int)(pad_to(J, NB) / NB);
+    g.rect_cols = (int)(cols / NB);
+    g.ntiles = g.rect_rows * g.rect_cols;
+    g.kfix0 = 0;
+    g.kfix1 = (int)(np / NB);
+    g.chunk = deal_chunk(g.ntiles);
+    const int nbatch = h->nbatch;
+    h->nbatch = 1;
+    const int rc = launch_gemm(h, false, true, EPI_STORE, g);
+    h->nbatch = nbatch;
+    return rc;
+}
+// theta, the complete axes' decomposition, the blocks' theta, y~ = Y Q in the padded right-hand sides, and the blocks'
+// K, L, L^-1, z, beta (steps 1 - 4 of an iteration without the inverse)
+static int pkron_factor(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_model_t* ms, const PkronMap& mp, PkronWs* w,
+                        const double* Xs, const double* Y, int64_t Ns, const double* u, bool grad) {
+    const KronDev& dv = w->ax.dev;
+    GP_TRY(launch_pkron_setup(h, m, mp, u, w->th3));
+    GP_TRY(kron_eig_axes(h, w->ax, w->th3 + PK_TH_AXES));
+    if (grad) GP_TRY(kron_grad_matrices(h, w->ax));
+    GP_TRY(launch_pkron_blocks_theta(h, mp, dv, w->th3, w->lamj));
+    const double* mats[KMAXD]; int ld[KMAXD];
+    for (int i = 0; i < mp.dc; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = mp.nc[i]; }
+    double* res;
+    GP_TRY(tensor_apply(h, mp.dc, mp.nc, mp.nc, mats, ld, 0, 0, Y, w->yt, w->yt + Ns * mp.J, &res, Ns));
+    GP_TRY(launch_pkron_scatter(h, res, Ns, mp.J, h->ypad));
+    return factor_at_u(h, ms, Xs, 0, Ns, u, true, false);
+}
+// Loss and gradient at u (and, fit mode, one Adam step).  Every launch reads its iteration-dependent values from the device.
+static int pkron_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, PkronWs* w, const double* Xs,
+                      const double* Y, int64_t Ns, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
+    const int64_t np = h->np;
+    const int J = mp.J;
+    const KronDev& dv = w->ax.dev;
+    const gpimhip_model_t ms = pkron_submodel(m, mp.p);
+    GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, true));
+    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(Ns, np))); }
+    GP_TRY(launch_grad_reduce(h, &ms, h->B, h->ld, Xs, Ns, (int)(np / NB), h->alpha, 0));
+    // W = K_s B: K_s once at variance 1, then one product on the tile engine (rows of W: the blocks)
+    h->nbatch = 1;
+    int rc = launch_kmat(h, &ms, Xs, Ns, nullptr, Ns, w->th3 + PK_TH_UNIT, 0.0, 0, w->Ks, h->ld, np, np, 1, 0, 0, 0, 0);
+    h->nbatch = J;
+    GP_TRY(rc);
+    GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
+    GP_TRY(pkron_times_b(h, w, J, w->Ks, h->ld, np, w->W, np));
+    // Z_i = W x_i Mm_i: the mode product along complete axis i of the (n_1, ..., n_dc, np) tensor W
+    for (int i = 0; i < mp.dc; ++i) {
+        int64_t pre = 1, post = np;
+        for (int k = 0; k < i; ++k) pre *= mp.nc[k];
+        for (int k = i + 1; k < mp.dc; ++k) post *= mp.nc[k];
+        GP_TRY(modeprod(h, w->W, w->Z + (int64_t)i * J * np, dv.Mm + dv.moff[i], mp.nc[i], mp.nc[i], mp.nc[i], 0, 0, pre,
+                             post));
+    }
+    GP_TRY(launch_pkron_block_sums(h, mp, Ns, w->W, w->Z, w->bsum));
+    return launch_pkron_finalize(h, m, mp, dv, Ns * (int64_t)J, w->bsum, w->th3, u, do_adam, loss_out, grad_out, fi);
+}
+
+extern "C" {
+
+int gpimhip_pkron_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                           const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
+                           double* loss_out, double* grad_out) {
+    PkronMap mp;
+    GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
+    if (!u) return GPIMHIP_E_BADARG;
+    PkronWs* w = nullptr;
+    GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
+    GP_TRY(pkron_iter(h, m, mp, w, Xs, Y, Ns, const_cast<double*>(u), 0, loss_out, grad_out,
+                      FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
+    return finish_and_check(h);
+}
+
+int gpimhip_fit_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                      const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, double* u_inout, double lr,
+                      int32_t T, double* hist_out, double* loss_out) {
+    PkronMap mp;
+    GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
+    if (!u_inout || T < 0) return GPIMHIP_E_BADARG;
+    PkronWs* w = nullptr;
+    GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
+    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
+    h->fit_completed = T;
+    if (T == 0) return finish_and_check(h);
+    GP_TRY(upload_bc_table(h, lr, T));
+    HIP_TRY(hipMemsetAsync(h->adam_m, 0, MAXP * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(h->adam_v, 0, MAXP * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(h->iter, 0, sizeof(int32_t), h->stream));
+    const FinalizeIter fi{h->iter, h->bc, T, hist_out, loss_out};
+    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
+                              [&] { return pkron_iter(h, m, mp, w, Xs, Y, Ns, u_inout, 1, nullptr, nullptr, fi); });
+}
+
+int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                          const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
+                          const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
+                          double* mean_out, double* var_out) {
+    PkronMap mp;
+    GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
+    if (!u || !Xs_test || Ms < 1 || !n_test_c || !axes_test_c || !mean_out || !var_out) return GPIMHIP_E_BADARG;
+    int64_t Mc = 1, sum_mn = 0, pmax = 1;
+    {
+        int64_t cur = mp.J;
+        for (int i = 0; i < dc; ++i) {
+            if (n_test_c[i] < 1) return GPIMHIP_E_BADARG;
+            Mc *= n_test_c[i];
+            sum_mn += (int64_t)n_test_c[i] * n_c[i];
+            cur = cur / n_c[i] * n_test_c[i];
+            pmax = std::max(pmax, cur);
+        }
+    }
+    PkronWs* w = nullptr;
+    GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
+    const int64_t np = h->np;
+    const int J = mp.J, nb = (int)(np / NB);
+    const int64_t Jp = pad_to(J, NB);
+    const KronDev& dv = w->ax.dev;
+    const gpimhip_model_t ms = pkron_submodel(m, p);
+    // chunks of ragged test rows: the blocks' partial column sums (J x nb x mc doubles) stay <= ~0.5 GiB
+    const int64_t mc = std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
+    h->nbatch = 1;              // ONE K* slab, shared by the J blocks
+    int rc = ws_ensure_predict(h, np, mc);
+    h->nbatch = J;
+    GP_TRY(rc);
+    const int64_t kld = h->ks_cols + 16;
+    GP_TRY(dev_grow(h, &w->colpart, &w->colpart_cap, (int64_t)J * nb * mc));
+    GP_TRY(dev_grow(h, &w->G, &w->g_cap, Jp * mc));
+    GP_TRY(dev_grow(h, &w->Q, &w->q_cap, (int64_t)J * mc));
+    GP_TRY(dev_grow(h, &w->pp, &w->pp_cap, 4 * pmax * mc));
+    GP_TRY(dev_grow(h, &w->cross, &w->cross_cap, 2 * sum_mn));
+    GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, false));
+    GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
+    // per complete axis: K*_i and b_i = K*_i Q_i (eigen-coordinates straight to test points)
+    const double* bmat[KMAXD];
+    {
+        int toff = 0;
+        int64_t ko = 0;
+        for (int i = 0; i < dc; ++i) {
+            double* Kc = w->cross + ko;
+            double* Bc = w->cross + sum_mn + ko;
+            GP_TRY(kron_cross(h, dv, w->th3 + PK_TH_AXES, axes_test_c, toff, n_test_c[i], i, Kc));
+            GP_TRY(modeprod(h, Kc, Bc, dv.Qt + dv.moff[i], n_c[i], n_c[i], n_c[i], 0, 0, n_test_c[i], 1));
+            bmat[i] = Bc;
+            toff += n_test_c[i];
+            ko += (int64_t)n_test_c[i] * n_c[i];
+        }
+    }
+    for (int64_t m0 = 0; m0 < Ms; m0 += mc) {
+        const int64_t cnt = std::min(mc, Ms - m0), cpad = pad_to(cnt, NB);
+        h->nbatch = 1;
+        rc = launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0);
+        h->nbatch = J;
+        GP_TRY(rc);
+        // G = B K*_s (Jp x cpad): the blocks' means before the mix
+        GP_TRY(pkron_times_b(h, w, J, h->Ks, kld, cpad, w->G, mc));
+        // q_j = |L_j^-1 k*|^2 from the raw column sums of the batched variance product (K* at variance 1, shared: stride 0)
+        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
+        g.sB = 0;
+        g.colpart = w->colpart;
+        g.ld_colpart = mc;
+        g.sColpart = (int64_t)nb * mc;
+        g.ntiles = (int)h->pred_ntiles;
+        g.chunk = deal_chunk(g.ntiles);
+        g.rag = rag_of(Ns, np);
+        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
+        GP_TRY(launch_pkron_qsum(h, J, nb, mc, cnt, w->colpart, w->Q));
+        // mean = s2 G b^T, var = clamp(s2 - s2^2 Q (b o b)^T, 0) + noise: mode products over the (n_1, ..., n_dc, mc) tensors
+        const double* cur[2] = {w->G, w->Q};
+        for (int v = 0; v < 2; ++v) {
+            double* bufa = w->pp + (int64_t)(2 * v) * pmax * mc;
+            double* bufb = bufa + pmax * mc;
+            double* dst = bufa;
+            for (int i = 0; i < dc; ++i) {
+                int64_t pre = 1, post = mc;
+                for (int k = 0; k < i; ++k) pre *= n_test_c[k];
+                for (int k = i + 1; k < dc; ++k) post *= n_c[k];
+                GP_TRY(modeprod(h, cur[v], dst, bmat[i], n_test_c[i], n_c[i], n_c[i], 0, v, pre, post));
+                cur[v] = dst;
+                dst = (dst == bufa) ? bufb : bufa;
+            }
+        }
+        GP_TRY(launch_pkron_post(h, w->th3, Mc, mc, m0, cnt, cur[0], cur[1], mean_out, var_out));
+    }
     return finish_and_check(h);
 }
 

@@ -204,6 +204,8 @@ struct gpimhip_ctx {
     void* kron = nullptr;
     // multi-output GP workspace, owned by api.hip (VgpWs); released by vgp_release()
     void* vgp = nullptr;
+    // dense-by-Kronecker blocks (a grid whose missing points are whole columns), owned by api.hip (PkronWs); pkron_release()
+    void* pkron = nullptr;
     // spectral-mixture workspace, owned by api.hip (SmWs); released by sm_release()
     void* sm = nullptr;
     // border of the reflection blocks (missing points of an incomplete grid), owned by api.hip (BorderWs); border_release()

@@ -35,38 +35,7 @@
 #include "theta.hpp"
 #include "blocklds.hpp"      // wave_sum: DPP / readlane reduction (no LDS crossbar round trips)
 
-#define KMAXD GPIMHIP_MAX_DIM
-
-struct KronDev {
-    int d;
-    int n[KMAXD];            // training grid
-    int off[KMAXD];          // offset of axis i in the per-axis vectors (coords, lam, mdiag)
-    int64_t moff[KMAXD];     // offset of axis i's n_i x n_i matrices
-    int64_t N;
-    const double* coords;    // [sum n_i]
-    double *K, *E, *W, *Qt, *Mm, *Tt, *Vr;   // [sum n_i^2] each
-    double *lam, *mdiag;     // [sum n_i]
-    // eigen-problems: one per axis, or two (symmetric / skew-symmetric half) when the axis' coordinates
-    // are centro-symmetric (any uniform grid): K_i then commutes with the exchange matrix and splits into
-    // two problems of half the size -- an eighth of the Jacobi work each, half the round-robin steps
-    int nprob;
-    int pax[2 * KMAXD], ppart[2 * KMAXD], pn[2 * KMAXD];   // axis, part (0 whole, 1 symmetric, 2 skew), order
-    int64_t poff[2 * KMAXD];                                // offset inside the axis' n_i^2 region (W, Vr, Tt)
-    int plam[2 * KMAXD];                                    // offset of its eigenvalues / Qt rows inside the axis
-};
-
-// One set of grid axes with everything that belongs to an axis alone: coordinates, K_i, the eigen-problem plan and the
-// eigen-decomposition (KronDev).  The training grid has one; gpimhip_sample_kron keeps a second one for the union of the
-// training and the test axes, without the gradient matrices (E, Mm, mdiag) and without any N-sized vector.
-struct KronAxes {
-    int d = 0;
-    int n[KMAXD] = {0, 0, 0, 0};
-    int64_t sum_n = 0, sum_n2 = 0;
-    bool grad = false;
-    double* arena = nullptr;
-    int64_t arena_count = 0;
-    KronDev dev;
-};
+#include "kron.hpp"      // KronDev, KronAxes and the per-axis drivers shared with the dense-by-Kronecker blocks
 
 struct KronWs {
     int d = 0;
@@ -125,7 +94,7 @@ static int kron_alloc(gpimhip_ctx* h, int64_t count, const char* what, double*& 
 }
 
 // the per-axis state for axes of the orders n[]; grad: with E, Mm and mdiag (training)
-static int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool grad) {
+int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool grad) {
     bool same = a.d == d && a.arena && a.grad == grad;
     for (int i = 0; i < d && same; ++i) same = a.n[i] == n[i];
     if (same) return GPIMHIP_OK;
@@ -470,8 +439,8 @@ __global__ void kron_modeprod_kernel(const double* __restrict__ in, double* __re
     out[idx] = s;
 }
 
-static int modeprod(gpimhip_ctx* h, const double* in, double* out, const double* M, int ma, int nbk, int ldm,
-                    int trans, int sq, int64_t pre, int64_t post) {
+int modeprod(gpimhip_ctx* h, const double* in, double* out, const double* M, int ma, int nbk, int ldm,
+             int trans, int sq, int64_t pre, int64_t post) {
     const int64_t total = pre * ma * post;
     hipLaunchKernelGGL(kron_modeprod_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, in, out, M,
                        ma, nbk, ldm, trans, sq, pre, post);
@@ -483,9 +452,9 @@ static int modeprod(gpimhip_ctx* h, const double* in, double* out, const double*
 // ping-pongs between bufa/bufb and returns the buffer that holds the result (shape ma[]).  batch > 1: src is `batch`
 // contiguous tensors (batch, nb[]) -- the batch index folds into `pre`, so a mode is still one launch.  src may be bufb
 // (it is read by the first mode only, which writes bufa), never bufa.
-static int tensor_apply(gpimhip_ctx* h, int d, const int* nbv, const int* mav, const double* const* mats,
-                        const int* ldm, int trans, int sq, const double* src, double* bufa, double* bufb,
-                        double** result, int64_t batch = 1) {
+int tensor_apply(gpimhip_ctx* h, int d, const int* nbv, const int* mav, const double* const* mats,
+                 const int* ldm, int trans, int sq, const double* src, double* bufa, double* bufb,
+                 double** result, int64_t batch) {
     const double* cur = src;
     double* dst = bufa;
     int shape[KMAXD];
@@ -716,7 +685,7 @@ __global__ void kron_draw_kernel(const double* __restrict__ gs, const double* __
 // ------------------------------------------------------------------------------------------
 // drivers
 // ------------------------------------------------------------------------------------------
-static int kron_cold_start(gpimhip_ctx* h, const KronDev& dv) {
+int kron_cold_start(gpimhip_ctx* h, const KronDev& dv) {
     int nmax = 1;
     for (int pr = 0; pr < dv.nprob; ++pr) nmax = std::max(nmax, dv.pn[pr]);
     hipLaunchKernelGGL(kron_eye_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), dv.nprob), dim3(256), 0,
@@ -727,7 +696,7 @@ static int kron_cold_start(gpimhip_ctx* h, const KronDev& dv) {
 
 // Splits every axis whose coordinates are centro-symmetric (c_a + c_{n-1-a} constant: any uniform grid) into a
 // symmetric and a skew-symmetric eigen-problem.  Needs the coordinates on the host: one small copy + sync per call.
-static int kron_plan_problems(gpimhip_ctx* h, KronAxes& ax) {
+int kron_plan_problems(gpimhip_ctx* h, KronAxes& ax) {
     std::vector<double> c((size_t)ax.sum_n);
     HIP_TRY(hipMemcpyAsync(c.data(), ax.dev.coords, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -759,13 +728,14 @@ static int kron_plan_problems(gpimhip_ctx* h, KronAxes& ax) {
 
 // K_i at the lengthscales in h->theta and its eigen-decomposition (Qt, lam), continued from the rotations in Vr
 // (kron_cold_start() resets them), for every axis of the set
-static int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax) {
+int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax, const ThetaDev* th) {
     const KronDev& dv = ax.dev;
+    if (!th) th = h->theta;
     int nmax = 1, pmax = 1;
     for (int i = 0; i < ax.d; ++i) nmax = std::max(nmax, ax.n[i]);
     for (int pr = 0; pr < dv.nprob; ++pr) pmax = std::max(pmax, dv.pn[pr]);
     hipLaunchKernelGGL(kron_axis_kernel, dim3((unsigned)(((int64_t)nmax * nmax + 255) / 256), ax.d), dim3(256), 0, h->stream,
-                       dv, h->theta);
+                       dv, th);
     hipLaunchKernelGGL(kron_reduce_kernel, dim3((unsigned)(((int64_t)pmax * pmax + 255) / 256), dv.nprob), dim3(256), 0,
                        h->stream, dv);
     for (int pr = 0; pr < dv.nprob; ++pr) {      // W = V * (matrix of the problem)
@@ -780,6 +750,33 @@ static int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax) {
     else hipLaunchKernelGGL((kron_eigh_kernel<0, 1>), dim3(dv.nprob), dim3(EIGH_WAVES * 64), 0, h->stream, dv);
     hipLaunchKernelGGL(kron_assemble_kernel, dim3((unsigned)(((int64_t)pmax * nmax + 255) / 256), dv.nprob), dim3(256), 0,
                        h->stream, dv);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// M_i = Q_i^T E_i Q_i  (two mode products on the n_i x n_i "tensor") and its diagonal
+int kron_grad_matrices(gpimhip_ctx* h, const KronAxes& ax) {
+    const KronDev& dv = ax.dev;
+    int nmax = 1;
+    for (int i = 0; i < ax.d; ++i) {
+        const int n = ax.n[i];
+        nmax = std::max(nmax, n);
+        GP_TRY(modeprod(h, dv.E + dv.moff[i], dv.Tt + dv.moff[i], dv.Qt + dv.moff[i], n, n, n, 0, 0, 1, n));
+        GP_TRY(modeprod(h, dv.Tt + dv.moff[i], dv.Mm + dv.moff[i], dv.Qt + dv.moff[i], n, n, n, 0, 0, n, 1));
+    }
+    hipLaunchKernelGGL(kron_mdiag_kernel, dim3((nmax + 63) / 64, ax.d), dim3(64), 0, h->stream, dv);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+void kron_axes_free(gpimhip_ctx* h, KronAxes& a) {
+    kron_free(h, a.arena, a.arena_count);
+    a.d = 0;
+}
+int kron_cross(gpimhip_ctx* h, const KronDev& dv, const ThetaDev* th, const double* tcoords, int toff, int mi, int ax, double* Ks) {
+    const int64_t cnt = (int64_t)mi * dv.n[ax];
+    hipLaunchKernelGGL(kron_cross_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, dv, th, tcoords, toff, mi, ax,
+                       Ks);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -802,15 +799,7 @@ static int kron_loss_grad(gpimhip_ctx* h, KronWs& w, const gpimhip_model_t* m, c
                           double* loss_out, double* grad_out, const FinalizeIter* it) {
     const KronDev& dv = w.tr.dev;
     GP_TRY(kron_decompose(h, w, m, u, y));
-    // M_i = Q_i^T E_i Q_i  (two mode products on the n_i x n_i "tensor") and its diagonal
-    int nmax = 1;
-    for (int i = 0; i < w.d; ++i) {
-        const int n = w.n[i];
-        nmax = std::max(nmax, n);
-        GP_TRY(modeprod(h, dv.E + dv.moff[i], dv.Tt + dv.moff[i], dv.Qt + dv.moff[i], n, n, n, 0, 0, 1, n));
-        GP_TRY(modeprod(h, dv.Tt + dv.moff[i], dv.Mm + dv.moff[i], dv.Qt + dv.moff[i], n, n, n, 0, 0, n, 1));
-    }
-    hipLaunchKernelGGL(kron_mdiag_kernel, dim3((nmax + 63) / 64, w.d), dim3(64), 0, h->stream, dv);
+    GP_TRY(kron_grad_matrices(h, w.tr));
     hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
     for (int i = 0; i < w.d; ++i) {
         int64_t pre = 1, post = 1;

@@ -1,0 +1,58 @@
+// kron.hpp -- the per-axis part of the Kronecker solver (kron.hip) that other translation units build on: one set of grid
+// axes with K_i, its eigen-decomposition and the gradient matrices, and the mode products.  Used by the dense-by-Kronecker
+// blocks (pkron.hip, api.hip), whose complete axes are exactly such a set.
+#pragma once
+#include "common.hpp"
+
+#define KMAXD GPIMHIP_MAX_DIM
+
+struct KronDev {
+    int d;
+    int n[KMAXD];            // training grid
+    int off[KMAXD];          // offset of axis i in the per-axis vectors (coords, lam, mdiag)
+    int64_t moff[KMAXD];     // offset of axis i's n_i x n_i matrices
+    int64_t N;
+    const double* coords;    // [sum n_i]
+    double *K, *E, *W, *Qt, *Mm, *Tt, *Vr;   // [sum n_i^2] each
+    double *lam, *mdiag;     // [sum n_i]
+    // eigen-problems: one per axis, or two (symmetric / skew-symmetric half) when the axis' coordinates
+    // are centro-symmetric (any uniform grid): K_i then commutes with the exchange matrix and splits into
+    // two problems of half the size -- an eighth of the Jacobi work each, half the round-robin steps
+    int nprob;
+    int pax[2 * KMAXD], ppart[2 * KMAXD], pn[2 * KMAXD];   // axis, part (0 whole, 1 symmetric, 2 skew), order
+    int64_t poff[2 * KMAXD];                                // offset inside the axis' n_i^2 region (W, Vr, Tt)
+    int plam[2 * KMAXD];                                    // offset of its eigenvalues / Qt rows inside the axis
+};
+
+// One set of grid axes with everything that belongs to an axis alone: coordinates, K_i, the eigen-problem plan and the
+// eigen-decomposition (KronDev).  The training grid has one; gpimhip_sample_kron keeps a second one for the union of the
+// training and the test axes, without the gradient matrices (E, Mm, mdiag) and without any N-sized vector.
+struct KronAxes {
+    int d = 0;
+    int n[KMAXD] = {0, 0, 0, 0};
+    int64_t sum_n = 0, sum_n2 = 0;
+    bool grad = false;
+    double* arena = nullptr;
+    int64_t arena_count = 0;
+    KronDev dev;
+};
+
+// the per-axis state for axes of the orders n[] (grow / re-carve; synchronises when it re-allocates); grad: with E, Mm, mdiag
+int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool grad);
+void kron_axes_free(gpimhip_ctx* h, KronAxes& a);
+// the eigen-problem plan from the coordinates in a.dev.coords (one small copy to the host and a synchronisation)
+int kron_plan_problems(gpimhip_ctx* h, KronAxes& ax);
+// Vr <- I: the next kron_eig_axes starts its rotations cold
+int kron_cold_start(gpimhip_ctx* h, const KronDev& dv);
+// K_i (and E_i) at the lengthscales th->ls[i] (th null: h->theta) and the eigen-decomposition (Qt, lam), warm-started from Vr
+int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax, const ThetaDev* th = nullptr);
+// Mm_i = Q_i^T E_i Q_i and its diagonal mdiag_i, for every axis of a set with the gradient matrices
+int kron_grad_matrices(gpimhip_ctx* h, const KronAxes& ax);
+// Ks[t, a] = exp(-((tcoords[toff + t] - c_ax[a]) / th->ls[ax])^2 / 2): the cross-covariance of axis ax, mi x n_ax
+int kron_cross(gpimhip_ctx* h, const KronDev& dv, const ThetaDev* th, const double* tcoords, int toff, int mi, int ax, double* Ks);
+// out[p, a, q] = sum_b Mx(a, b) in[p, b, q]; Mx(a, b) = M[a * ldm + b] (trans == 0) or M[b * ldm + a]; sq != 0 squares Mx
+int modeprod(gpimhip_ctx* h, const double* in, double* out, const double* M, int ma, int nbk, int ldm, int trans, int sq,
+             int64_t pre, int64_t post);
+// mats[i] (ma[i] x nb[i]) along mode i of `src` (shape nb[], `batch` contiguous tensors), ping-pong between bufa / bufb
+int tensor_apply(gpimhip_ctx* h, int d, const int* nbv, const int* mav, const double* const* mats, const int* ldm, int trans,
+                 int sq, const double* src, double* bufa, double* bufb, double** result, int64_t batch = 1);

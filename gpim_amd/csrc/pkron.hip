@@ -1,0 +1,280 @@
+// pkron.hip -- exact GP on a grid whose missing points are whole columns (a hyperspectral cube measured at a sparse set of
+// pixels, an image with whole rows missing): dense-by-Kronecker blocks.
+//
+// The observed set is (the N_s observed points X_s of the p "ragged" axes) x (the complete product of the other axes), so
+// for the RBF kernel
+//     K = s2 K_s(X_s, X_s) (x) K_c,     K_c = (x) K_i = Q Lam Q^T   (Q = (x) Q_i, lambda_j = prod_i lambda_i[j_i])
+//     K + sigma I = (I (x) Q) blockdiag_j( s2 lambda_j K_s + sigma I ) (I (x) Q^T),     sigma = noise + jitter
+// i.e. J = prod n_i ordinary exact-GP blocks A_j of order N_s that share X_s: block j has kernel variance s2 max(lambda_j, 0)
+// and targets y~_j = column j of Y Q.  The blocks run in lock-step through the batched engine (api.hip: pkron_iter) the way
+// the multi-output GP's do (vgp.hip); the complete axes are a KronAxes set of kron.hip.  Here:
+//   pkron_setup_kernel        u -> the model's theta, the complete axes' lengthscales, the ragged ones at variance 1
+//   pkron_blocks_theta_kernel lambda_j (each factor clamped at 0) and the J blocks' theta
+//   pkron_scatter_kernel      y~ (N_s x J, from the mode products) into the padded per-problem right-hand sides
+//   pkron_block_sums_kernel   per block: the gradient contraction's sums, |L_j^-1 y~_j|^2, sum log diag L_j, beta_j . (K_s beta_j)
+//                             and, per complete axis i, beta_j . Z_i,j with Z_i = W x_i Mm_i (W = K_s B on the tile engine)
+//   pkron_finalize_kernel     the sums over the blocks in a fixed order -> the reduced sums S[] of the model on all N = N_s J
+//                             observations -> the shared finalize_step (chain rule, Adam, history row)
+//   pkron_qsum_kernel / pkron_post_kernel   prediction: the blocks' raw quadratic forms, the epilogue
+// With F_i = Mm_i at axis i and diag(lambda_k) on the other complete axes (Mm_i = Q_i^T E_i Q_i, E_i = l_i dK_i / dl_i):
+//   d/d s2            1/2 sum_j lambda_j S_j[0]                         (S_j[]: grad_reduce_kernel's sums of block j)
+//   l_k d/d l_k       1/2 s2 sum_j lambda_j S_j[1 + k]                  ragged column k
+//   d/d noise         1/2 sum_j S_j[5]
+//   l_i d/d l_i       1/2 s2 [ sum_j mdiag_i[j_i] prod_{k != i} lambda_k[j_k] tr(M_j K_s) - <B, W F_i^T> ]   complete axis i
+// with tr(M_j K_s) = S_j[0] + beta_j^T K_s beta_j.  No eigenvector derivative appears: repeated lambda are harmless.
+// Every reduction has a fixed shape: results are bit-reproducible run to run.
+#include "kfun.hpp"
+#include "theta.hpp"
+#include "pkron.hpp"
+
+// NQ sums over the 256 threads of a workgroup at once (fixed tree); arr: NQ x 256 doubles of LDS; results in out[0 .. NQ)
+template <int NQ>
+__device__ __forceinline__ void pk_sum_multi(const double* v, double* arr, double* out) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) arr[q * 256 + tid] = v[q];
+    __syncthreads();
+    if (tid < 64) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const double* p = arr + q * 256;
+            double x = (p[tid] + p[tid + 128]) + (p[tid + 64] + p[tid + 192]);
+            x += __shfl_down(x, 32);
+            x += __shfl_down(x, 16);
+            x += __shfl_down(x, 8);
+            x += __shfl_down(x, 4);
+            x += __shfl_down(x, 2);
+            x += __shfl_down(x, 1);
+            if (tid == 0) out[q] = x;
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void pkron_setup_kernel(gpimhip_model_t m, PkronMap mp, const double* __restrict__ u,
+                                                         ThetaDev* __restrict__ th3) {
+    if (threadIdx.x != 0) return;
+    ThetaDev t;
+    theta_from_u(m, u, t);
+    th3[PK_TH_MODEL] = t;
+    ThetaDev a = t, r = t;
+    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
+        a.ls[k] = (k < mp.dc) ? t.ls[mp.perm[mp.p + k]] : 1.0;
+        r.ls[k] = (k < mp.p) ? t.ls[mp.perm[k]] : 1.0;
+        a.inv_ls[k] = 1.0 / a.ls[k];
+        r.inv_ls[k] = 1.0 / r.ls[k];
+        a.dls_du[k] = r.dls_du[k] = 0.0;
+    }
+    r.var = 1.0;
+    r.diag_add = 0.0;
+    r.dvar_du = r.dnoise_du = r.dalpha_du = 0.0;
+    a.dvar_du = a.dnoise_du = a.dalpha_du = 0.0;
+    th3[PK_TH_AXES] = a;
+    th3[PK_TH_UNIT] = r;
+}
+
+// the factor of lambda_j that belongs to axis i, clamped at 0 (K_i is positive semi-definite: a negative value is rounding)
+__device__ __forceinline__ double pk_lam(const KronDev& dv, int i, int ji) {
+    const double l = dv.lam[dv.off[i] + ji];
+    return l > 0.0 ? l : 0.0;
+}
+
+__global__ __launch_bounds__(256) void pkron_blocks_theta_kernel(PkronMap mp, KronDev dv, const ThetaDev* __restrict__ th3,
+                                                                 ThetaDev* __restrict__ theta, double* __restrict__ lamj) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= mp.J) return;
+    int r = j;
+    int idx[GPIMHIP_MAX_DIM];
+    for (int i = mp.dc - 1; i >= 0; --i) { idx[i] = r % mp.nc[i]; r /= mp.nc[i]; }
+    double lam = 1.0;
+    for (int i = 0; i < mp.dc; ++i) lam *= pk_lam(dv, i, idx[i]);
+    lamj[j] = lam;
+    ThetaDev t = th3[PK_TH_UNIT];
+    const ThetaDev tm = th3[PK_TH_MODEL];
+    t.var = tm.var * lam;
+    t.noise = tm.noise;
+    t.alpha = 1.0;
+    t.diag_add = tm.diag_add;
+    theta[j] = t;
+}
+
+__global__ __launch_bounds__(256) void pkron_scatter_kernel(const double* __restrict__ yt, int64_t Ns, int J, int64_t np,
+                                                            double* __restrict__ ypad) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int j = blockIdx.y;
+    if (n >= np) return;
+    ypad[(int64_t)j * np + n] = (n < Ns) ? yt[n * J + j] : 0.0;
+}
+
+// B[j * np + n] = beta_j[n] for n < Ns, 0 on the padding rows: the A operand of the two products with B (rows j >= J of the
+// buffer stay zero from its allocation)
+__global__ __launch_bounds__(256) void pkron_beta_kernel(const double* __restrict__ beta, int64_t Ns, int64_t np,
+                                                         double* __restrict__ B) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = blockIdx.y;
+    if (n >= np) return;
+    B[j * np + n] = (n < Ns) ? beta[j * np + n] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void pkron_block_sums_kernel(PkronMap mp, int64_t Ns, int64_t np, int nb, int ntile,
+                                                               const double* __restrict__ grad_part, const double* __restrict__ z,
+                                                               const double* __restrict__ logdet_part,
+                                                               const double* __restrict__ beta, const double* __restrict__ W,
+                                                               const double* __restrict__ Z, double* __restrict__ bsum) {
+    __shared__ double arr[13 * 256];
+    __shared__ double out[13];
+    const int tid = threadIdx.x;
+    const int64_t j = blockIdx.x;
+    double v[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const double* gp = grad_part + j * ntile * 8;
+    for (int q = tid; q < ntile; q += 256)
+        for (int k = 0; k < 7; ++k) v[k] += gp[(int64_t)q * 8 + k];
+    const double* zj = z + j * np;
+    for (int64_t i = tid; i < np; i += 256) v[7] = fma(zj[i], zj[i], v[7]);
+    for (int k = tid; k < nb; k += 256) v[8] += logdet_part[j * nb + k];
+    const double* bj = beta + j * np;
+    const double* wj = W + j * np;
+    for (int64_t i = tid; i < Ns; i += 256) {
+        const double b = bj[i];
+        v[9] = fma(b, wj[i], v[9]);
+        for (int a = 0; a < mp.dc; ++a) v[10 + a] = fma(b, Z[((int64_t)a * mp.J + j) * np + i], v[10 + a]);
+    }
+    pk_sum_multi<13>(v, arr, out);
+    if (tid < PK_SUMS) bsum[j * PK_SUMS + tid] = tid < 13 ? out[tid] : 0.0;
+}
+
+// E[0] = sum_j lambda_j S_j[0], E[1 + k] = sum_j lambda_j S_j[1 + k] (ragged column k), E[5] = sum_j S_j[5],
+// E[6] = sum |z|^2, E[7] = sum log diag L, E[8 + i] = sum_j po_i(j) [mdiag_i[j_i] (S_j[0] + beta_j . W_j) - beta_j . Z_i,j]
+__global__ __launch_bounds__(256) void pkron_finalize_kernel(gpimhip_model_t m, PkronMap mp, KronDev dv, int64_t Ntot,
+                                                             const double* __restrict__ bsum, const ThetaDev* __restrict__ th3,
+                                                             double* __restrict__ u, double* __restrict__ adam_m,
+                                                             double* __restrict__ adam_v, int do_adam, double* loss_out,
+                                                             double* grad_out, FinalizeIter fi, int32_t* __restrict__ info) {
+    __shared__ double arr[11 * 256];
+    __shared__ double E[11];
+    const int tid = threadIdx.x;
+    double v[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = tid; j < mp.J; j += 256) {
+        const double* b = bsum + (int64_t)j * PK_SUMS;
+        int r = j;
+        int idx[GPIMHIP_MAX_DIM];
+        double l[GPIMHIP_MAX_DIM];
+        for (int i = mp.dc - 1; i >= 0; --i) { idx[i] = r % mp.nc[i]; r /= mp.nc[i]; }
+        double lam = 1.0;
+        for (int i = 0; i < mp.dc; ++i) { l[i] = pk_lam(dv, i, idx[i]); lam *= l[i]; }
+        v[0] = fma(lam, b[0], v[0]);
+        for (int k = 0; k < mp.p; ++k) v[1 + k] = fma(lam, b[1 + k], v[1 + k]);
+        v[5] += b[5];
+        v[6] += b[7];
+        v[7] += b[8];
+        const double trmk = b[0] + b[9];
+        for (int i = 0; i < mp.dc; ++i) {
+            double po = 1.0;
+            for (int k = 0; k < mp.dc; ++k)
+                if (k != i) po *= l[k];
+            v[8 + i] = fma(po, dv.mdiag[dv.off[i] + idx[i]] * trmk - b[10 + i], v[8 + i]);
+        }
+    }
+    pk_sum_multi<11>(v, arr, E);
+    if (tid != 0) return;
+    const ThetaDev t = th3[PK_TH_MODEL];
+    double S[7] = {0, 0, 0, 0, 0, 0, 0};
+    S[0] = E[0];
+    for (int k = 0; k < mp.p; ++k) S[1 + mp.perm[k]] = E[1 + k];
+    for (int i = 0; i < mp.dc; ++i) S[1 + mp.perm[mp.p + i]] = E[8 + i];
+    S[5] = E[5];
+    // NaN sums (NaN inputs, a garbage spectrum) count as a failed factorisation
+    if (!(E[7] == E[7]) && *info == 0) *info = 1;
+    AdamStep st;
+    st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
+    double* hist_row = nullptr;
+    if (fi.iter) {
+        const int it = *fi.iter;
+        // a factorisation of this training loop failed: u, the Adam state and the history stay as the previous iteration
+        // left them (the reference raises inside torch.linalg.cholesky there)
+        if (*info != 0) { atomicMin(info + 1, it); return; }
+        const int P = 2 + m.n_ls;
+        st.lr_over_bc1 = fi.bc[it];
+        st.bc2_sqrt = fi.bc[fi.T + it];
+        loss_out = fi.loss_base ? fi.loss_base + it : nullptr;
+        hist_row = fi.hist_base ? fi.hist_base + (int64_t)it * P : nullptr;
+        *fi.iter = it + 1;
+    }
+    finalize_step(m, Ntot, S, E[6], E[7], t, u, adam_m, adam_v, do_adam, st, loss_out, grad_out, hist_row, prior_constant(m));
+}
+
+__global__ __launch_bounds__(256) void pkron_qsum_kernel(int nb, int64_t ldq, int64_t cnt, const double* __restrict__ colpart,
+                                                         double* __restrict__ q) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = blockIdx.y;
+    if (t >= cnt) return;
+    double s = 0.0;
+    for (int ci = 0; ci < nb; ++ci) s += colpart[(j * nb + ci) * ldq + t];
+    q[j * ldq + t] = s;
+}
+
+__global__ __launch_bounds__(256) void pkron_post_kernel(const ThetaDev* __restrict__ th3, int64_t Mc, int64_t ldq, int64_t m0,
+                                                         int64_t cnt, const double* __restrict__ mraw,
+                                                         const double* __restrict__ vraw, double* __restrict__ mean_out,
+                                                         double* __restrict__ var_out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cnt * Mc) return;
+    const int64_t t = e / Mc, c = e % Mc;
+    const double s2 = th3[PK_TH_MODEL].var, noise = th3[PK_TH_MODEL].noise;
+    mean_out[(m0 + t) * Mc + c] = s2 * mraw[c * ldq + t];
+    var_out[(m0 + t) * Mc + c] = clamp0_nan(s2 - s2 * s2 * vraw[c * ldq + t]) + noise;
+}
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+int launch_pkron_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const double* u, ThetaDev* th3) {
+    hipLaunchKernelGGL(pkron_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, mp, u, th3);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_blocks_theta(gpimhip_ctx* h, const PkronMap& mp, const KronDev& dv, const ThetaDev* th3, double* lamj) {
+    hipLaunchKernelGGL(pkron_blocks_theta_kernel, dim3((unsigned)((mp.J + 255) / 256)), dim3(256), 0, h->stream, mp, dv, th3,
+                       h->theta, lamj);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_scatter(gpimhip_ctx* h, const double* yt, int64_t Ns, int J, double* ypad) {
+    hipLaunchKernelGGL(pkron_scatter_kernel, dim3((unsigned)((h->np + 255) / 256), J), dim3(256), 0, h->stream, yt, Ns, J, h->np,
+                       ypad);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_beta(gpimhip_ctx* h, int64_t Ns, int J, double* B) {
+    hipLaunchKernelGGL(pkron_beta_kernel, dim3((unsigned)((h->np + 255) / 256), J), dim3(256), 0, h->stream, h->alpha, Ns, h->np, B);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_block_sums(gpimhip_ctx* h, const PkronMap& mp, int64_t Ns, const double* W, const double* Z, double* bsum) {
+    const int nb = (int)(h->np / NB);
+    hipLaunchKernelGGL(pkron_block_sums_kernel, dim3(mp.J), dim3(256), 0, h->stream, mp, Ns, h->np, nb, nb * (nb + 1) / 2,
+                       h->grad_part, h->z, h->logdet_part, h->alpha, W, Z, bsum);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const KronDev& dv, int64_t Ntot,
+                          const double* bsum, const ThetaDev* th3, double* u, int do_adam, double* loss_out, double* grad_out,
+                          FinalizeIter fi) {
+    hipLaunchKernelGGL(pkron_finalize_kernel, dim3(1), dim3(256), 0, h->stream, *m, mp, dv, Ntot, bsum, th3, u, h->adam_m,
+                       h->adam_v, do_adam, loss_out, grad_out, fi, h->info);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_qsum(gpimhip_ctx* h, int J, int nb, int64_t ldq, int64_t cnt, const double* colpart, double* q) {
+    hipLaunchKernelGGL(pkron_qsum_kernel, dim3((unsigned)((cnt + 255) / 256), J), dim3(256), 0, h->stream, nb, ldq, cnt, colpart, q);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_post(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, const double* mraw,
+                      const double* vraw, double* mean_out, double* var_out) {
+    hipLaunchKernelGGL(pkron_post_kernel, dim3((unsigned)((cnt * Mc + 255) / 256)), dim3(256), 0, h->stream, th3, Mc, ldq, m0, cnt,
+                       mraw, vraw, mean_out, var_out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}

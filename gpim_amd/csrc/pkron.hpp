@@ -1,0 +1,39 @@
+// pkron.hpp -- shared declarations of the dense-by-Kronecker blocks (pkron.hip kernels, api.hip drivers).
+#pragma once
+#include "common.hpp"
+#include "kron.hpp"
+
+#define PK_SUMS 16          // doubles per block in PkronWs::bsum (pkron_block_sums_kernel)
+
+// the split of the model's axes: ragged columns of Xs first, then the complete axes.  perm[k] = the model's axis (the
+// index of its lengthscale) behind ragged column k (k < p) or complete axis k - p.  Passed to the kernels by value.
+struct PkronMap {
+    int p, dc, J;
+    int perm[GPIMHIP_MAX_DIM];
+    int nc[GPIMHIP_MAX_DIM];        // orders of the complete axes
+};
+
+// theta of one evaluation (device): [0] the model's (original axis order: the chain rule of finalize_step), [1] the
+// complete axes' lengthscales in ls[0 .. dc) (kron_eig_axes, kron_cross), [2] the ragged columns' at variance 1 (K_s, K*_s)
+#define PK_TH_MODEL 0
+#define PK_TH_AXES 1
+#define PK_TH_UNIT 2
+
+int launch_pkron_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const double* u, ThetaDev* th3);
+// lambda_j = prod_i max(lam_i[j_i], 0) into lamj and the J blocks' theta (variance s2 lambda_j, the ragged lengthscales,
+// noise, noise + jitter on the diagonal) into h->theta
+int launch_pkron_blocks_theta(gpimhip_ctx* h, const PkronMap& mp, const KronDev& dv, const ThetaDev* th3, double* lamj);
+// ypad[j * np + n] = yt[n * J + j] (n < Ns), 0 on the padding rows
+int launch_pkron_scatter(gpimhip_ctx* h, const double* yt, int64_t Ns, int J, double* ypad);
+// B[j * np + n] = beta_j[n] (h->alpha) with zeros on the padding rows n >= Ns
+int launch_pkron_beta(gpimhip_ctx* h, int64_t Ns, int J, double* B);
+// per block j: the seven gradient sums, |z_j|^2, sum log diag L_j, beta_j . W_j and beta_j . Z_i,j (i < dc) into bsum[j]
+int launch_pkron_block_sums(gpimhip_ctx* h, const PkronMap& mp, int64_t Ns, const double* W, const double* Z, double* bsum);
+int launch_pkron_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const KronDev& dv, int64_t Ntot,
+                          const double* bsum, const ThetaDev* th3, double* u, int do_adam, double* loss_out, double* grad_out,
+                          FinalizeIter fi);
+// q[j * ldq + t] = sum_ci colpart[(j * nb + ci) * ldq + t]: the raw |L_j^-1 k*_s(x_t)|^2 of the batched variance product
+int launch_pkron_qsum(gpimhip_ctx* h, int J, int nb, int64_t ldq, int64_t cnt, const double* colpart, double* q);
+// mean_out[(m0 + t) * Mc + c] = s2 mraw[c * ldq + t];  var_out = clamp(s2 - s2^2 vraw[c * ldq + t], 0) + noise
+int launch_pkron_post(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, const double* mraw,
+                      const double* vraw, double* mean_out, double* var_out);

@@ -154,7 +154,13 @@ class reconstructor(_solvers.HostDriver):
         self._kernel_name = kernel
         structured = bool(kwargs.get("structured", False))
         border = kwargs.get("_border")       # set by skreconstructor on an incomplete grid (gprutils.border_blocks)
-        if structured and border is not None:
+        columns = kwargs.get("_columns")     # set by skreconstructor when whole columns are missing (gprutils.column_blocks)
+        if structured and columns is not None:
+            # J dense blocks of the observed ragged points, one per eigen-direction of the complete axes (csrc/pkron.hip)
+            if kernel != "RBF":
+                raise NotImplementedError("column blocks: only the RBF kernel factorises over the complete axes")
+            self._solver = _solvers.Columns(columns)
+        elif structured and border is not None:
             # the reflection blocks of the completed grid with a border for its missing points (csrc/border.hip)
             border["n_total"] = border["n_obs"]          # the loss is that of the observed points
             self._solver = _solvers.Reflection(border, border=True)
@@ -665,6 +671,8 @@ class reconstructor(_solvers.HostDriver):
         for one ``z`` are not comparable with another implementation of the rule -- their distribution is."""
         if method not in ("joint", "pathwise", "blocks", "border", "kron"):
             raise ValueError("method must be 'joint', 'pathwise', 'blocks', 'border' or 'kron'; got %r" % (method,))
+        if isinstance(self._solver, _solvers.Columns):
+            raise NotImplementedError(self._solver._NO_DRAWS + " (method=%r)" % (method,))
         if method == "kron":
             return self._sample_kron_host(n_samples, Xtest, noiseless, seed, z, jitter)
         if method == "blocks":

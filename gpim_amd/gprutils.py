@@ -333,6 +333,80 @@ def border_flops(N, M, r):
     return N ** 3 / 4.0 ** r + N * N * M / 2.0 ** r + N * M * M + M ** 3, (N - M) ** 3
 
 
+def column_blocks(X, y):
+    """The dense-by-Kronecker form of a grid whose missing points are whole columns (gpim_amd extension; DESIGN.md section
+    22): a hyperspectral cube in which a pixel is either measured with its whole spectrum or missing with it, an image
+    with whole rows missing.  The NaN mask of y is constant along the "complete" axes C and depends on the other, "ragged",
+    axes only, so the observations are (observed ragged points) x (product of the complete axes) and the RBF covariance
+    is K_s (x) K_c: J = prod n_i (i in C) exact-GP blocks of the N_s observed ragged points.
+
+    X (d, n_1, ..., n_d): grid coordinates with NaN at the missing points, y (n_1, ..., n_d) with NaN at the same points.
+    Returns a dict: ragged, complete (the axes, ascending), perm (ragged then complete) and inv (its inverse: an array in
+    permuted axis order goes back with ``a.transpose(inv)``), shape, Xs (N_s, p: the observed ragged points, row-major in
+    ragged-grid order), obs (their flat indices in the ragged grid), axes_c (the coordinate vectors of the complete axes),
+    Y (N_s, J: complete axes fastest, C order), n_obs = N_s J.
+    Raises NotImplementedError, naming the reason, when no axis is complete, when every axis is (nothing is missing: the
+    Kronecker solver's case), when the observed coordinates do not form a product grid, when a complete axis is longer than
+    4096 or J exceeds 65535."""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    d = X.shape[0]
+    if X.ndim != d + 1 or X.shape[1:] != y.shape or d < 2 or d > 4:
+        raise NotImplementedError("column blocks need coordinates of shape (d, n_1, ..., n_d) and y of shape (n_1, ..., n_d), "
+                                  "d = 2 .. 4")
+    missing = np.isnan(y)
+    if not np.array_equal(np.isnan(X).any(axis=0), missing):
+        raise NotImplementedError("column blocks need the same NaN pattern in X and y")
+    if not missing.any():
+        raise NotImplementedError("column blocks: nothing is missing (every axis is complete: the Kronecker solver's case)")
+    complete = [i for i in range(d) if (missing == np.take(missing, [0], axis=i)).all()]
+    ragged = [i for i in range(d) if i not in complete]
+    if not complete:
+        raise NotImplementedError("column blocks: the NaN mask is constant along no axis (scattered missing points)")
+    perm = ragged + complete
+    p = len(ragged)
+    mask_r = np.transpose(missing, perm)[(Ellipsis,) + (0,) * len(complete)]         # the mask over the ragged grid
+    obs = np.flatnonzero(~mask_r.ravel())
+    if obs.size == 0:
+        raise NotImplementedError("column blocks: no observed point")
+    rshape = tuple(y.shape[i] for i in ragged)
+    cshape = tuple(y.shape[i] for i in complete)
+    J = int(np.prod(cshape, dtype=np.int64))
+    if max(cshape) > 4096:
+        raise NotImplementedError("column blocks: a complete axis of %d points (the eigen-solver takes at most 4096)" % max(cshape))
+    if J > 65535:
+        raise NotImplementedError("column blocks: %d blocks (the batched engine takes at most 65535)" % J)
+    Xp = np.transpose(X, [0] + [1 + i for i in perm]).reshape(d, -1, J)[:, obs, :]  # (d, N_s, J), observed points only
+    for i in ragged:
+        if not (Xp[i] == Xp[i][:, :1]).all():
+            raise NotImplementedError("column blocks need a product grid (coordinate %d must not vary along a complete axis)" % i)
+    axes_c = []
+    for k, i in enumerate(complete):
+        if not (Xp[i] == Xp[i][:1, :]).all():
+            raise NotImplementedError("column blocks need a product grid (coordinate %d varying along axis %d only)" % (i, i))
+        c = np.moveaxis(Xp[i][0].reshape(cshape), k, 0).reshape(cshape[k], -1)
+        if not (c == c[:, :1]).all():
+            raise NotImplementedError("column blocks need a product grid (coordinate %d varying along axis %d only)" % (i, i))
+        axes_c.append(c[:, 0].copy())
+    Xs = np.ascontiguousarray(Xp[ragged, :, 0].T)
+    # ragged coordinate k must vary along ragged axis k only, where observed (as complete_grid checks)
+    ridx = np.unravel_index(obs, rshape)
+    for k, i in enumerate(ragged):
+        ref = np.full(rshape[k], np.nan)
+        ref[ridx[k]] = Xs[:, k]
+        if not (ref[ridx[k]] == Xs[:, k]).all():
+            raise NotImplementedError("column blocks need a product grid (coordinate %d varying along axis %d only)" % (i, i))
+    Y = np.ascontiguousarray(np.transpose(y, perm).reshape(-1, J)[obs])
+    return {"ragged": ragged, "complete": complete, "perm": perm, "inv": [int(k) for k in np.argsort(perm)],
+            "shape": tuple(y.shape), "Xs": Xs, "obs": obs, "axes_c": axes_c, "Y": Y, "n_obs": int(obs.size) * J}
+
+
+def column_flops(Ns, J):
+    """Per-iteration flop model of the dense-by-Kronecker blocks, in the units of ``border_flops``:
+    J N_s^3 against the dense exact GP's (J N_s)^3."""
+    return float(J) * float(Ns) ** 3
+
+
 def pathwise_grid(Xgrid, Xrows):
     """What a pathwise posterior draw needs from its test grid and its training rows (gpim_amd extension: reconstructor.
     sample(method='pathwise')).

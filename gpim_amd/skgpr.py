@@ -17,7 +17,10 @@ the exact GP of gpim_amd/smgpr.py on the observed points of any grid, sparse ima
 grids run there as reflection blocks too (``rec.solver``).  Incomplete grids (NaN in y)
 with the other kernels: the exact GP on the observed points, either as the reflection blocks of the completed grid with a
 border for the missing points (csrc/border.hip) or on the dense engine, whichever the flop model says is cheaper
-(``rec.solver``: 'border' or 'dense').
+(``rec.solver``: 'border' or 'dense').  With the RBF kernel, a grid whose missing points are whole columns -- a
+hyperspectral cube measured at a sparse set of pixels, an image with whole rows missing -- is an exact Kronecker product of
+the observed pixels and the complete axes: J dense blocks of the N_s observed pixels (gprutils.column_blocks, csrc/pkron.hip;
+``rec.solver``: 'columns') instead of one of J N_s points.
 """
 import numpy as np
 
@@ -44,27 +47,41 @@ class skreconstructor(reconstructor):
 
     def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, ski=True, learning_rate=.1,
                  iterations=50, use_gpu=1, verbose=1, seed=0, **kwargs):
-        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures", "sparse", "_border"):
+        for k in ("grid_points_ratio", "max_root", "maxroot", "num_batches", "n_mixtures", "sparse", "_border",
+                  "_columns"):
             kwargs.pop(k, None)
-        solver, border = self._choose_solver(X, y, kernel)
+        solver, blocks = self._choose_solver(X, y, kernel)
         super().__init__(X, y, Xtest, kernel=kernel, lengthscale=lengthscale, sparse=False, indpoints=None,
                          learning_rate=learning_rate, iterations=iterations, use_gpu=use_gpu, verbose=verbose,
-                         seed=seed, structured=solver != "dense", _border=border, **kwargs)
+                         seed=seed, structured=solver != "dense", _border=blocks if solver == "border" else None,
+                         _columns=blocks if solver == "columns" else None, **kwargs)
         self.solver = solver
 
     @staticmethod
     def _choose_solver(X, y, kernel):
         """('kronecker' | 'reflection', None) on a complete grid; on an incomplete one ('border', border_blocks(X, y)) when
         the grid can be completed, has a symmetric axis and the border's flop model is below BORDER_FACTOR of the dense
-        exact GP's on the observed points, else ('dense', None)."""
+        exact GP's on the observed points, else ('dense', None).  RBF on a grid whose missing points are whole columns:
+        ('columns', column_blocks(X, y)) when the blocks' flop model is below that of the choice above."""
         yv = np.asarray(y, dtype=np.float64)
         if not np.isnan(yv).any():
             return ("kronecker" if kernel == "RBF" else "reflection"), None
         if kernel not in ("RBF", "Matern52", "RationalQuadratic"):
             return "dense", None
+        n_obs = int(np.count_nonzero(~np.isnan(yv)))
+        choice, f_choice = ("dense", None), float(n_obs) ** 3
         try:
             S = gprutils.border_blocks(X, yv)
+            f_border, f_dense = gprutils.border_flops(yv.size, len(S["miss"]), len(S["dims"]))
+            if f_border < BORDER_FACTOR * f_dense:
+                choice, f_choice = ("border", S), f_border
         except (NotImplementedError, ValueError):
-            return "dense", None
-        f_border, f_dense = gprutils.border_flops(yv.size, len(S["miss"]), len(S["dims"]))
-        return ("border", S) if f_border < BORDER_FACTOR * f_dense else ("dense", None)
+            pass
+        if kernel == "RBF":
+            try:
+                C = gprutils.column_blocks(X, yv)
+            except NotImplementedError:
+                return choice
+            if gprutils.column_flops(C["Xs"].shape[0], C["Y"].shape[1]) < f_choice:
+                return "columns", C
+        return choice

@@ -483,6 +483,41 @@ int gpimhip_sample_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, c
                         const double* z, int32_t S, int32_t noiseless, double jitter,
                         double* mean_out, double* out);
 
+/* ---- exact GP on a grid whose missing points are whole columns (dense-by-Kronecker blocks) ----------
+ * The reference's hyperspectral use case (gpim/gpreg/gpr.py:30-43): a cube measured at a sparse set of pixels, each with
+ * its whole spectrum -- or an image with whole rows missing.  The observations are (the N_s observed points X_s of the p
+ * "ragged" axes) x (the complete product grid of the other dc axes), so the RBF covariance is s2 K_s (x) K_c and, with the
+ * eigen-decompositions K_i = Q_i diag(lambda_i) Q_i^T of the complete axes, K + sigma I splits exactly into J = prod n_i
+ * ordinary exact-GP blocks s2 lambda_j K_s + sigma I of order N_s.  They share X_s and run in lock-step through the batched
+ * engine: J N_s^3 work and J N_s^2 memory instead of (J N_s)^3 and (J N_s)^2.  The SAME model,
+ * parameterisation, u, loss, gradient, history rows and posterior as gpimhip_nll_grad / gpimhip_fit_exact /
+ * gpimhip_predict_exact on the N = N_s J observations, up to rounding.
+ *   m          the model of all dim = p + dc axes (RBF; ARD or isotropic); lengthscales in the model's own axis order
+ *   Xs         device, N_s x p: the observed ragged points (column k = model axis perm[k])
+ *   n_c        HOST, dc ints: the orders of the complete axes (each <= 4096, J = prod n_c <= 65535)
+ *   perm       HOST, dim ints, or NULL for the identity: the model's axis behind ragged column k (k < p) and behind
+ *              complete axis k - p (k >= p)
+ *   axes_c     device, sum n_c doubles: the coordinate vectors of the complete axes, concatenated
+ *   Y          device, N_s x J: row n = the observations at ragged point n over the complete grid in C order
+ *   Xs_test    device, M_s x p ragged test rows (NaN rows give NaN); n_test_c (HOST) / axes_test_c (device): the test
+ *              coordinates of the complete axes; mean_out / var_out: M_s x prod n_test_c (ragged row major), var with
+ *              the noise as gpimhip_predict_exact
+ * Double-precision handles outside reflection mode; another kernel, p < 1, dc < 1, p + dc != dim, an axis longer than
+ * 4096, J > 65535 or an invalid perm -> GPIMHIP_E_BADARG.  The workspace is grow-only and counted by
+ * gpimhip_workspace_bytes.  A block that is not positive definite ends training like any failed factorisation
+ * (GPIMHIP_E_NOT_PD, gpimhip_fit_completed).  Stage timers: 0 / 1 the blocks' factorisation and inverse, 2 their K^-1
+ * products, 3 the variance product. */
+int gpimhip_pkron_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                           const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
+                           double* loss_out, double* grad_out);
+int gpimhip_fit_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                      const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, double* u_inout,
+                      double lr, int32_t T, double* hist_out, double* loss_out);
+int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                          const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
+                          const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
+                          double* mean_out, double* var_out);
+
 /* Acquisition sweep over the dense grid (gpim/gpbayes/acqfunc.py:11-92):
  *   CB : p0*mean + p1*sd                                  (alpha, beta)
  *   EI : imp*Phi(imp/sd) + sd*phi(imp/sd), imp = mean - p0 - p1     (best, xi)
