@@ -142,6 +142,14 @@ _PROTOS = {
                                              ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                              c_dp, c_dp, c_dp, c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), c_dp,
                                              c_dp, c_dp]),
+    # (.. predict_pkron's up to axes_test_c, P, Us, irow_train, irow_test, n_union, axes_union, idx_train, idx_test, z, S, ..)
+    "gpimhip_sample_pkron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                            c_dp, c_dp, c_dp, c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), c_dp,
+                                            c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32), c_dp, ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32), c_dp, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_double, c_dp, c_dp]),
     "gpimhip_sample_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp,
                                            ctypes.POINTER(ctypes.c_int32), c_dp,

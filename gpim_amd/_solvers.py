@@ -208,6 +208,11 @@ class Dense:
         raise NotImplementedError("method='kron' draws through the Kronecker eigenbasis of the structured RBF model on a "
                                   "complete grid (the %s solver has none)" % type(self).__name__)
 
+    def sample_columns(self, o, *args):
+        """Draws through the dense-by-Kronecker blocks belong to the column-blocks model (``Columns``)."""
+        raise NotImplementedError("method='columns' draws through the dense-by-Kronecker blocks of a grid whose missing points "
+                                  "are whole columns, solver='columns' (the %s solver has none)" % type(self).__name__)
+
 
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""
@@ -283,7 +288,7 @@ class Columns(Dense):
     in one lock-step batch (gprutils.column_blocks; csrc/pkron.hip).  ``o._u``, the loss, the history
     and the posterior are those of ``Dense`` on the same observations."""
     structured = True
-    _NO_DRAWS = "posterior draws are not built for solver='columns'"
+    _NO_DRAWS = "solver='columns' draws with method='columns' only"
 
     def __init__(self, C):
         self.C = C
@@ -390,6 +395,43 @@ class Columns(Dense):
         raise NotImplementedError(self._NO_DRAWS)
 
     sample_pathwise = sample_blocks = sample_border = sample_kron = sample
+
+    def sample_geometry(self, taxes):
+        """What a draw on the product grid of the d coordinate vectors taxes needs beside z: the ragged test rows (as
+        ``_predict_axes`` builds them), the complete test axes, the union of the ragged rows and of the complete axes."""
+        C = self.C
+        rows = np.array(np.meshgrid(*[taxes[i] for i in C["ragged"]], indexing="ij")).reshape(len(C["ragged"]), -1).T
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        caxes = [np.asarray(taxes[i], dtype=np.float64) for i in C["complete"]]
+        return rows, caxes, gprutils.union_rows(C["Xs"], rows), gprutils.union_axes(C["axes_c"], caxes)
+
+    def sample_columns(self, o, taxes, z, noiseless, jitter, mean, out, geometry=None):
+        """Joint posterior draws on the product grid of the axes ``taxes`` by Matheron's rule through the dense-by-Kronecker
+        blocks (csrc/api.hip: gpimhip_sample_pkron).  z: (S, U_s prod U_i + N + M) device tensor
+        [zeta | z_e | z_n], z_e in the training points' row order and z_n in the test grid's own (C) order; mean (M) and out
+        (S, M) come back in the test grid's order."""
+        C = self.C
+        rows, caxes, (P, iX, iT), (au, ic, it) = geometry or self.sample_geometry(taxes)
+        shape = [len(t) for t in taxes]
+        N, M, S = C["n_obs"], int(np.prod(shape, dtype=np.int64)), z.shape[0]
+        PU = z.shape[1] - N - M
+        e_idx, n_idx, o_idx = (torch.from_numpy(a).to(o._dev) for a in gprutils.column_sample_maps(C, shape))
+        zl = torch.empty_like(z)
+        zl[:, :PU] = z[:, :PU]
+        zl[:, PU:PU + N] = z[:, PU:PU + N].index_select(1, e_idx)
+        zl[:, PU + N:] = z[:, PU + N:].index_select(1, n_idx)
+        i32 = lambda v: (ctypes.c_int32 * len(v))(*[int(k) for k in v])
+        # (every device tensor stays referenced until the call returns)
+        rows_d, caxes_d, P_d, au_d = (o._to_device(a) for a in (rows, np.concatenate(caxes), P, np.concatenate(au)))
+        mp, op = torch.empty_like(mean), torch.empty_like(out)
+        rc = o._handle.lib.gpimhip_sample_pkron(*self._model(o), ptr(o._u), ptr(rows_d), rows_d.shape[0],
+                                                i32([len(c) for c in caxes]), ptr(caxes_d), ptr(P_d), P_d.shape[0], i32(iX),
+                                                i32(iT), i32([len(a) for a in au]), ptr(au_d), i32(np.concatenate(ic)),
+                                                i32(np.concatenate(it)), ptr(zl), S, int(bool(noiseless)), float(jitter),
+                                                ptr(mp), ptr(op))
+        mean.copy_(mp.index_select(0, o_idx))
+        out.copy_(op.index_select(1, o_idx))
+        return rc
 
 
 class Reflection(Dense):

@@ -769,6 +769,13 @@ int kron_grad_matrices(gpimhip_ctx* h, const KronAxes& ax) {
     return GPIMHIP_OK;
 }
 
+int kron_root_rows(gpimhip_ctx* h, const KronDev& dv, int ax, const int32_t* idx, int rows, double* out) {
+    hipLaunchKernelGGL(kron_root_rows_kernel, dim3((unsigned)(((int64_t)rows * dv.n[ax] + 255) / 256)), dim3(256), 0, h->stream, dv,
+                       ax, idx, rows, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
 void kron_axes_free(gpimhip_ctx* h, KronAxes& a) {
     kron_free(h, a.arena, a.arena_count);
     a.d = 0;

@@ -50,6 +50,8 @@ int kron_eig_axes(gpimhip_ctx* h, const KronAxes& ax, const ThetaDev* th = nullp
 int kron_grad_matrices(gpimhip_ctx* h, const KronAxes& ax);
 // Ks[t, a] = exp(-((tcoords[toff + t] - c_ax[a]) / th->ls[ax])^2 / 2): the cross-covariance of axis ax, mi x n_ax
 int kron_cross(gpimhip_ctx* h, const KronDev& dv, const ThetaDev* th, const double* tcoords, int toff, int mi, int ax, double* Ks);
+// out[r, j] = Q_ax[idx[r], j] sqrt(max(lam_ax[j], 0)): `rows` rows of the prior root of axis ax (idx: device, inside the axis)
+int kron_root_rows(gpimhip_ctx* h, const KronDev& dv, int ax, const int32_t* idx, int rows, double* out);
 // out[p, a, q] = sum_b Mx(a, b) in[p, b, q]; Mx(a, b) = M[a * ldm + b] (trans == 0) or M[b * ldm + a]; sq != 0 squares Mx
 int modeprod(gpimhip_ctx* h, const double* in, double* out, const double* M, int ma, int nbk, int ldm, int trans, int sq,
              int64_t pre, int64_t post);

@@ -16,6 +16,9 @@
 //   pkron_finalize_kernel     the sums over the blocks in a fixed order -> the reduced sums S[] of the model on all N = N_s J
 //                             observations -> the shared finalize_step (chain rule, Adam, history row)
 //   pkron_qsum_kernel / pkron_post_kernel   prediction: the blocks' raw quadratic forms, the epilogue
+//   posterior draws (gpimhip_sample_pkron), all draws of a group per launch: pkron_prior_theta_kernel,
+//   pkron_tril_kernel (the prior factor), pkron_zeta_kernel, pkron_gather_kernel (the prior draws), pkron_resid_kernel,
+//   pkron_scatter_multi_kernel, pkron_beta_stack_kernel (the update), pkron_mean_kernel, pkron_draw_kernel (the epilogue)
 // With F_i = Mm_i at axis i and diag(lambda_k) on the other complete axes (Mm_i = Q_i^T E_i Q_i, E_i = l_i dK_i / dl_i):
 //   d/d s2            1/2 sum_j lambda_j S_j[0]                         (S_j[]: grad_reduce_kernel's sums of block j)
 //   l_k d/d l_k       1/2 s2 sum_j lambda_j S_j[1 + k]                  ragged column k
@@ -227,8 +230,150 @@ __global__ __launch_bounds__(256) void pkron_post_kernel(const ThetaDev* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// posterior draws (gpimhip_sample_pkron); every kernel handles all draws of a group in one launch, one
+// thread per output element, no reduction
+// ------------------------------------------------------------------------------------------
+// theta of the prior factor of the ragged part: the ragged lengthscales (PK_TH_UNIT) at the model's variance
+__global__ __launch_bounds__(64) void pkron_prior_theta_kernel(const ThetaDev* __restrict__ th3, ThetaDev* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    ThetaDev t = th3[PK_TH_UNIT];
+    t.var = th3[PK_TH_MODEL].var;
+    *out = t;
+}
+// the strict upper triangle of the nb diagonal blocks of a factor <- 0 (the factorisation leaves what the covariance build
+// wrote there, and a product on the tile engine reads diagonal tiles whole)
+__global__ __launch_bounds__(256) void pkron_tril_kernel(double* __restrict__ L, int64_t ld) {
+    double* D = L + (int64_t)blockIdx.x * NB * (ld + 1);
+    for (int e = threadIdx.x; e < NB * NB; e += 256) {
+        const int r = e / NB, c = e % NB;
+        if (c > r) D[(int64_t)r * ld + c] = 0.0;
+    }
+}
+// zeta of the draws s0 .. s0 + Sg as the right-hand operand of H = L_P zeta: out[r, s * U + c] = zeta_{s0 + s}[r, c] for
+// r < Us, zero on the padding rows and columns (out: rows x cols, both multiples of 128)
+__global__ __launch_bounds__(256) void pkron_zeta_kernel(const double* __restrict__ z, int64_t zw, int64_t Us, int64_t U, int s0,
+                                                         int Sg, int64_t rows, int64_t cols, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * cols) return;
+    const int64_t r = e / cols, q = e % cols;
+    double v = 0.0;
+    if (r < Us && q < Sg * U) v = z[(s0 + q / U) * zw + r * U + q % U];
+    out[e] = v;
+}
+// out[s, n, c] = H[idx[n], s * U + c]: the rows of the prior draw at the training (or the test) ragged rows
+__global__ __launch_bounds__(256) void pkron_gather_kernel(const double* __restrict__ H, int64_t ldh, const int32_t* __restrict__ idx,
+                                                           int64_t rows, int64_t U, int Sg, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Sg * rows * U) return;
+    const int64_t c = e % U, n = (e / U) % rows, s = e / (U * rows);
+    out[e] = H[(int64_t)idx[n] * ldh + s * U + c];
+}
+// g[s, e] <- -g[s, e] - sqrt(sigma) z_e[s0 + s, e] over the NJ = N_s J observations: what the draw adds to the targets
+// (Y's own share of the update is the mean)
+__global__ __launch_bounds__(256) void pkron_resid_kernel(const double* __restrict__ ze, int64_t zw, int s0, int64_t NJ, int Sg,
+                                                          const ThetaDev* __restrict__ th3, double* __restrict__ g) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Sg * NJ) return;
+    const int64_t s = e / NJ, k = e % NJ;
+    g[e] = -g[e] - sqrt(th3[PK_TH_MODEL].diag_add) * ze[(s0 + s) * zw + k];
+}
+// the projected targets of the group (Sg, N_s, J) as the J blocks' right-hand sides: out[j, n, s] = yt[s, n, j], zero on the
+// padding rows n >= Ns and columns s >= Sg (out: J x np x Sp)
+__global__ __launch_bounds__(256) void pkron_scatter_multi_kernel(const double* __restrict__ yt, int64_t Ns, int64_t J, int64_t np,
+                                                                  int Sg, int64_t Sp, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= J * np * Sp) return;
+    const int64_t s = e % Sp, n = (e / Sp) % np, j = e / (Sp * np);
+    out[e] = (n < Ns && s < Sg) ? yt[(s * Ns + n) * J + j] : 0.0;
+}
+// the blocks' solutions (J x np x Sp) as the rows of one left operand: out[s * J + j, n] = beta[j, n, s], zero on the padding
+// rows of the operand (>= Sg J) and of the blocks (n >= Ns)
+__global__ __launch_bounds__(256) void pkron_beta_stack_kernel(const double* __restrict__ beta, int64_t Ns, int64_t J, int64_t np,
+                                                               int Sg, int64_t Sp, int64_t rows, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * np) return;
+    const int64_t n = e % np, r = e / np;
+    out[e] = (r < Sg * J && n < Ns) ? beta[((r % J) * np + n) * Sp + r / J] : 0.0;
+}
+// mean_out[(m0 + t) Mc + c] = s2 mraw[c ldq + t]: the arithmetic of pkron_post_kernel's mean
+__global__ __launch_bounds__(256) void pkron_mean_kernel(const ThetaDev* __restrict__ th3, int64_t Mc, int64_t ldq, int64_t m0,
+                                                         int64_t cnt, const double* __restrict__ mraw, double* __restrict__ mean_out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cnt * Mc) return;
+    const int64_t t = e / Mc, c = e % Mc;
+    mean_out[(m0 + t) * Mc + c] = th3[PK_TH_MODEL].var * mraw[c * ldq + t];
+}
+// out[s0 + s, m0 + t, c] = mean[m0 + t, c] + (g*[s, m0 + t, c] + s2 upd[s, c, t]) + sqrt(c_n) z_n[s0 + s, m0 + t, c]; at
+// z = 0 the bracket is 0 and the draw is the mean, bit for bit.  z_n is not read when c_n = 0.
+__global__ __launch_bounds__(256) void pkron_draw_kernel(const ThetaDev* __restrict__ th3, int64_t Mc, int64_t ldq, int64_t m0,
+                                                         int64_t cnt, int64_t Ms, int s0, int Sg, const double* __restrict__ gs,
+                                                         const double* __restrict__ upd, const double* __restrict__ mean,
+                                                         const double* __restrict__ zn, int64_t zw, int noiseless,
+                                                         double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Sg * cnt * Mc) return;
+    const int64_t c = e % Mc, t = (e / Mc) % cnt, s = e / (Mc * cnt);
+    const int64_t pos = (m0 + t) * Mc + c;
+    const double cn = noiseless ? 0.0 : th3[PK_TH_MODEL].noise;
+    double v = fma(th3[PK_TH_MODEL].var, upd[(s * Mc + c) * ldq + t], gs[s * Ms * Mc + pos]);
+    if (cn > 0.0) v = fma(sqrt(cn), zn[(s0 + s) * zw + pos], v);
+    out[(s0 + s) * Ms * Mc + pos] = mean[pos] + v;
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+#define PK_GRID(total) dim3((unsigned)(((total) + 255) / 256))
+int launch_pkron_prior_theta(gpimhip_ctx* h, const ThetaDev* th3, ThetaDev* out) {
+    hipLaunchKernelGGL(pkron_prior_theta_kernel, dim3(1), dim3(64), 0, h->stream, th3, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_tril(gpimhip_ctx* h, double* L, int64_t ld, int nb) {
+    hipLaunchKernelGGL(pkron_tril_kernel, dim3(nb), dim3(256), 0, h->stream, L, ld);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_zeta(gpimhip_ctx* h, const double* z, int64_t zw, int64_t Us, int64_t U, int s0, int Sg, int64_t rows, int64_t cols,
+                      double* out) {
+    hipLaunchKernelGGL(pkron_zeta_kernel, PK_GRID(rows * cols), dim3(256), 0, h->stream, z, zw, Us, U, s0, Sg, rows, cols, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_gather(gpimhip_ctx* h, const double* H, int64_t ldh, const int32_t* idx, int64_t rows, int64_t U, int Sg, double* out) {
+    hipLaunchKernelGGL(pkron_gather_kernel, PK_GRID(Sg * rows * U), dim3(256), 0, h->stream, H, ldh, idx, rows, U, Sg, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_resid(gpimhip_ctx* h, const double* ze, int64_t zw, int s0, int64_t NJ, int Sg, const ThetaDev* th3, double* g) {
+    hipLaunchKernelGGL(pkron_resid_kernel, PK_GRID(Sg * NJ), dim3(256), 0, h->stream, ze, zw, s0, NJ, Sg, th3, g);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_scatter_multi(gpimhip_ctx* h, const double* yt, int64_t Ns, int64_t J, int Sg, int64_t Sp, double* out) {
+    hipLaunchKernelGGL(pkron_scatter_multi_kernel, PK_GRID(J * h->np * Sp), dim3(256), 0, h->stream, yt, Ns, J, h->np, Sg, Sp, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_beta_stack(gpimhip_ctx* h, const double* beta, int64_t Ns, int64_t J, int Sg, int64_t Sp, int64_t rows, double* out) {
+    hipLaunchKernelGGL(pkron_beta_stack_kernel, PK_GRID(rows * h->np), dim3(256), 0, h->stream, beta, Ns, J, h->np, Sg, Sp, rows, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_mean(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, const double* mraw,
+                      double* mean_out) {
+    hipLaunchKernelGGL(pkron_mean_kernel, PK_GRID(cnt * Mc), dim3(256), 0, h->stream, th3, Mc, ldq, m0, cnt, mraw, mean_out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_pkron_draw(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, int64_t Ms, int s0, int Sg,
+                      const double* gs, const double* upd, const double* mean, const double* zn, int64_t zw, int noiseless,
+                      double* out) {
+    hipLaunchKernelGGL(pkron_draw_kernel, PK_GRID(Sg * cnt * Mc), dim3(256), 0, h->stream, th3, Mc, ldq, m0, cnt, Ms, s0, Sg, gs, upd,
+                       mean, zn, zw, noiseless, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
 int launch_pkron_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const double* u, ThetaDev* th3) {
     hipLaunchKernelGGL(pkron_setup_kernel, dim3(1), dim3(64), 0, h->stream, *m, mp, u, th3);
     HIP_TRY(hipGetLastError());

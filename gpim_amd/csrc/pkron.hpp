@@ -37,3 +37,27 @@ int launch_pkron_qsum(gpimhip_ctx* h, int J, int nb, int64_t ldq, int64_t cnt, c
 // mean_out[(m0 + t) * Mc + c] = s2 mraw[c * ldq + t];  var_out = clamp(s2 - s2^2 vraw[c * ldq + t], 0) + noise
 int launch_pkron_post(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, const double* mraw,
                       const double* vraw, double* mean_out, double* var_out);
+
+// ---- posterior draws (gpimhip_sample_pkron): Sg draws s0 .. s0 + Sg of the call per launch ----
+// *out = the ragged lengthscales at the model's variance: theta of the prior factor chol(s2 K_s(P, P) + d I)
+int launch_pkron_prior_theta(gpimhip_ctx* h, const ThetaDev* th3, ThetaDev* out);
+// the strict upper triangle of the nb diagonal blocks of the factor L <- 0
+int launch_pkron_tril(gpimhip_ctx* h, double* L, int64_t ld, int nb);
+// out (rows x cols, zero padded)[r, s U + c] = zeta_{s0 + s}[r, c]; z: rows of zw doubles, zeta first (Us x U)
+int launch_pkron_zeta(gpimhip_ctx* h, const double* z, int64_t zw, int64_t Us, int64_t U, int s0, int Sg, int64_t rows, int64_t cols,
+                      double* out);
+// out[s, n, c] = H[idx[n], s U + c] (n < rows, c < U)
+int launch_pkron_gather(gpimhip_ctx* h, const double* H, int64_t ldh, const int32_t* idx, int64_t rows, int64_t U, int Sg, double* out);
+// g[s, e] <- -g[s, e] - sqrt(noise + jitter) ze[(s0 + s) zw + e], e < NJ
+int launch_pkron_resid(gpimhip_ctx* h, const double* ze, int64_t zw, int s0, int64_t NJ, int Sg, const ThetaDev* th3, double* g);
+// out (J x np x Sp)[j, n, s] = yt[s, n, j], zero for n >= Ns or s >= Sg
+int launch_pkron_scatter_multi(gpimhip_ctx* h, const double* yt, int64_t Ns, int64_t J, int Sg, int64_t Sp, double* out);
+// out (rows x np)[s J + j, n] = beta (J x np x Sp)[j, n, s], zero for rows >= Sg J or n >= Ns
+int launch_pkron_beta_stack(gpimhip_ctx* h, const double* beta, int64_t Ns, int64_t J, int Sg, int64_t Sp, int64_t rows, double* out);
+// mean_out[(m0 + t) Mc + c] = s2 mraw[c ldq + t]
+int launch_pkron_mean(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, const double* mraw,
+                      double* mean_out);
+// out[s0 + s, m0 + t, c] = mean[m0 + t, c] + g*[s, m0 + t, c] + s2 upd[(s Mc + c) ldq + t] + sqrt(c_n) zn[(s0 + s) zw + ...]
+int launch_pkron_draw(gpimhip_ctx* h, const ThetaDev* th3, int64_t Mc, int64_t ldq, int64_t m0, int64_t cnt, int64_t Ms, int s0, int Sg,
+                      const double* gs, const double* upd, const double* mean, const double* zn, int64_t zw, int noiseless,
+                      double* out);

@@ -622,6 +622,99 @@ class reconstructor(_solvers.HostDriver):
         self._kron_bytes = max(need, getattr(self, "_kron_bytes", 0))
         return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
 
+    _COLUMNS_ENGINE = "method='columns' draws through the dense-by-Kronecker blocks: skreconstructor(..., 'RBF') whose solver " \
+                      "is 'columns' (whole columns of the grid missing), in double precision (%s)"
+
+    def _sample_columns_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
+        """sample(method='columns'): every argument is checked before anything is stored, so a refused call leaves the model,
+        its stored test grid and the solver's test axes as they were."""
+        sol = self._solver
+        if not isinstance(sol, _solvers.Columns):
+            what = ("sparse=True" if self.do_sparse else "the missing points are scattered: use method='border'" if self.do_border
+                    else "the Kronecker model of a complete grid: use method='kron'" if isinstance(sol, _solvers.Kron)
+                    else "a reflection-block model: use method='blocks'" if self.do_symm
+                    else "a dense model: use method='joint' or 'pathwise'")
+            raise NotImplementedError(self._COLUMNS_ENGINE % what)
+        if self.precision == "single":
+            raise NotImplementedError(self._COLUMNS_ENGINE % "precision='single'")
+        self._check_data()
+        if Xtest is not None:
+            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+            try:
+                taxes = gprutils.grid_axes(Xtest)[0]
+            except NotImplementedError as e:
+                raise NotImplementedError("method='columns' needs a product test grid: %s" % e)
+            shape = tuple(np.shape(Xtest)[1:])
+        else:
+            taxes, shape = sol.taxes, tuple(self.fulldims)
+            if taxes is None:
+                raise NotImplementedError("method='columns' needs a product test grid: the model holds none (pass Xtest)")
+            if not all(np.isfinite(t).all() for t in taxes):
+                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be at least 1; got %r" % (n_samples,))
+        jitter = self._spec.jitter if jitter is None else float(jitter)
+        if not (0.0 < jitter < np.inf):
+            raise ValueError("method='columns' needs a finite jitter > 0 (the prior factor of the ragged rows); got %g" % jitter)
+        geometry = sol.sample_geometry(taxes)
+        rows, caxes, (P, _, _), (au, ic, _) = geometry
+        for i, a in enumerate(au):
+            if len(a) > 4096:
+                raise NotImplementedError("method='columns': the union of the training and the test coordinates of axis %d has "
+                                          "%d entries, the eigen-solver takes at most 4096" % (sol.C["complete"][i], len(a)))
+        Us, U = len(P), int(np.prod([len(a) for a in au], dtype=np.int64))
+        N, M = self._Xd.shape[0], int(np.prod(shape, dtype=np.int64))
+        W = Us * U + N + M
+        parts = "[zeta | z_e | z_n] = %d x %d union rows x union-axes points + %d observations + %d test points" % (Us, U, N, M)
+        if z is not None:
+            zt = z if torch.is_tensor(z) else np.asarray(z)
+            if zt.ndim != 2 or tuple(zt.shape) != (S, W):
+                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='columns' (%s); got %s"
+                                 % (W, S, W, parts, tuple(zt.shape)))
+        # what the call allocates: z (as given and in the library's layout), the draws twice and the mean here; in the library
+        # (csrc/api.hip: gpimhip_sample_pkron) the prior factor, zeta and H, the mode products' and the blocks' buffers
+        Ns, J = sol.C["Y"].shape
+        need = 8 * (S * ((1 if torch.is_tensor(z) and z.is_cuda and z.dtype == _F64 else 2) * W + 2 * M) + 2 * M
+                    + self._columns_library_doubles(S, Ns, len(rows), Us, J, [len(a) for a in au],
+                                                    [len(c) for c in sol.C["axes_c"]], [len(c) for c in caxes]))
+        if need > getattr(self, "_columns_bytes", 0):
+            free = torch.cuda.mem_get_info(self._dev)[0]
+            if need > free:
+                raise MemoryError("sample: %d draws on %d test points through %d x %d union points need %.2f GiB of device "
+                                  "memory, %.2f GiB are free" % (S, M, Us, U, need / 2.0 ** 30, free / 2.0 ** 30))
+        z_d = self._draw_z(S, W, seed) if z is None else self._to_device(z if torch.is_tensor(z) else np.asarray(z))
+        if Xtest is not None:
+            self._resolve_test_grid(Xtest)
+        out = torch.empty((S, M), dtype=_F64, device=self._dev)
+        mean = torch.empty((M,), dtype=_F64, device=self._dev)
+        _lib.check(sol.sample_columns(self, taxes, z_d, noiseless, jitter, mean, out, geometry))
+        self._columns_bytes = max(need, getattr(self, "_columns_bytes", 0))
+        return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
+
+    @staticmethod
+    def _columns_library_doubles(S, Ns, Ms, Us, J, nu, nn, nm):
+        """The doubles gpimhip_sample_pkron's own buffers take (its arena and the prediction slab), by the library's formulas."""
+        pad = lambda n: -(-int(n) // 128) * 128
+        np_, npU = pad(Ns), pad(Us)
+        nb = np_ // 128
+        mc = min(pad(Ms), max(128, (1 << 26) // (J * nb) // 128 * 128))
+        U = int(np.prod(nu, dtype=np.int64))
+        pmax, cur, cx, ct, maxX, maxT = 1, J, U, U, U, U
+        for a, b, c in zip(nu, nn, nm):
+            cur, cx, ct = cur // b * c, cx // a * b, ct // a * c
+            pmax, maxX, maxT = max(pmax, cur), max(maxX, cx), max(maxT, ct)
+        big = max(Ns * maxX, Ms * maxT)
+        per_draw = 2 * npU * U + 3 * big + 2 * pmax * mc + J * (3 * np_ + mc)
+        sg = max(1, min(S, (1 << 25) // per_draw))
+        groups = -(-S // sg)
+        sg = -(-S // groups)
+        cols, Sp, rowsP = pad(sg * U), pad(sg), pad(sg * J)
+        arena = npU * (npU + 16) + 2 * npU * cols + 3 * sg * big + 2 * J * np_ * Sp + rowsP * (np_ + mc) + 2 * sg * pmax * mc
+        slab = np_ * (mc + 16) + nb * mc + pad(J) * mc + 4 * pmax * mc
+        return arena + slab
+
     def _draw_z(self, n_samples, M, seed=None, generator=None):
         if generator is None and seed is not None:
             generator = torch.Generator(self._dev).manual_seed(int(seed))
@@ -668,11 +761,28 @@ class reconstructor(_solvers.HostDriver):
         ``(n_samples, prod U_i + N + M)`` whether noiseless or not, split ``[zeta | z_e | z_n]``: ``zeta`` row-major over
         the union axes (of orders ``U_i``), ``z_e`` in training-grid order, ``z_n`` in test-grid order.  A draw is a pure
         function of ``z`` on this engine; the prior root is fixed only up to an orthogonal change of ``zeta``, so draws
-        for one ``z`` are not comparable with another implementation of the rule -- their distribution is."""
-        if method not in ("joint", "pathwise", "blocks", "border", "kron"):
-            raise ValueError("method must be 'joint', 'pathwise', 'blocks', 'border' or 'kron'; got %r" % (method,))
+        for one ``z`` are not comparable with another implementation of the rule -- their distribution is.
+
+        ``method='columns'``: Matheron's rule for a cube measured at a sparse set of pixels -- ``skreconstructor(..., 'RBF')``
+        whose ``solver`` is ``'columns'`` -- on ANY finite product test grid.  A draw fills the
+        unmeasured pixels with whole plausible spectra.  The prior goes through ``L_P = chol(s2 K_s(P, P) + jitter I)`` of
+        the union ``P`` of the ragged (pixel) training and test rows (``gprutils.union_rows``, ``U_s`` rows) and the
+        eigen-roots of the union of the complete (spectral) axes (``gprutils.union_axes``, orders ``U_i``), the update
+        through the model's J blocks.  ``0 < jitter < inf`` (default: the model's).  The draws are exactly
+        ``N(mean, Sigma_post + (0 if noiseless else noise) I + jitter T (I (x) K_c(u, u)) T^T)`` with
+        ``T = S_* - K_*X (K_XX + (noise + model jitter) I)^-1 S_X`` (``S_X``, ``S_*`` select the training and the test points
+        out of the union product grid, ``K_c(u, u)`` is the covariance of the union of the complete axes): the last term is
+        positive semi-definite and of the size of ``jitter``, the price of factoring ``K_s(P, P)``, which is numerically
+        singular on a pixel grid.  ``z`` has shape ``(n_samples, U_s prod U_i + N + M)`` whether noiseless or not, split
+        ``[zeta | z_e | z_n]``: ``zeta`` row-major over ``(U_s, U_1, ...)``, ``z_e`` in the training points' row order,
+        ``z_n`` in test-grid order.  ``z = 0`` gives ``predict``'s mean bit for bit.  The other five methods refuse this
+        model, and ``'columns'`` refuses every other model, naming the method it has."""
+        if method not in ("joint", "pathwise", "blocks", "border", "kron", "columns"):
+            raise ValueError("method must be 'joint', 'pathwise', 'blocks', 'border', 'kron' or 'columns'; got %r" % (method,))
+        if method == "columns":
+            return self._sample_columns_host(n_samples, Xtest, noiseless, seed, z, jitter)
         if isinstance(self._solver, _solvers.Columns):
-            raise NotImplementedError(self._solver._NO_DRAWS + " (method=%r)" % (method,))
+            raise NotImplementedError(self._solver._NO_DRAWS + " (got method=%r)" % (method,))
         if method == "kron":
             return self._sample_kron_host(n_samples, Xtest, noiseless, seed, z, jitter)
         if method == "blocks":

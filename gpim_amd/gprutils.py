@@ -156,6 +156,51 @@ def union_axes(axes_train, axes_test):
     return au, ic, it
 
 
+def union_rows(Xs, Xt):
+    """The sorted (lexicographic) union P of the ragged training rows Xs (N_s, p) and the ragged test rows Xt (M_s, p) with
+    the position of every row in it (gpim_amd extension: reconstructor.sample(method='columns')).
+
+    Two rows merge when every coordinate agrees within ``1e-12 * max(1, max|coordinate|)`` (per coordinate column: the
+    tolerance of ``union_axes``, applied to neighbours in sorted order); a merged row is represented by the training one when
+    it holds one.  Returns (P (U_s, p) float64, i_train (N_s,) int32, i_test (M_s,) int32) with ``P[i_train] ~ Xs`` and
+    ``P[i_test] ~ Xt``."""
+    Xs = np.asarray(Xs, dtype=np.float64)
+    Xt = np.asarray(Xt, dtype=np.float64)
+    if Xs.ndim != 2 or Xt.ndim != 2 or Xs.shape[1] != Xt.shape[1]:
+        raise ValueError("union_rows needs training rows (N_s, p) and test rows (M_s, p); got %s and %s"
+                         % (Xs.shape, Xt.shape))
+    both = np.concatenate([Xs, Xt])
+    if not np.isfinite(both).all():
+        raise ValueError("union_rows needs finite coordinates")
+    ids = np.empty(both.shape, dtype=np.int64)
+    for k in range(both.shape[1]):
+        tol = 1e-12 * max(1.0, float(np.abs(both[:, k]).max()))
+        order = np.argsort(both[:, k], kind="stable")
+        ids[order, k] = np.cumsum(np.concatenate([[True], np.diff(both[order, k]) > tol])) - 1
+    # rows of equal ids are one row; np.unique sorts them lexicographically (ids grow with the coordinate) and names the
+    # first row of every group in `both`, a training row whenever the group holds one
+    _, first, inv = np.unique(ids, axis=0, return_index=True, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1).astype(np.int32)
+    return both[first].copy(), inv[:len(Xs)].copy(), inv[len(Xs):].copy()
+
+
+def column_sample_maps(C, tshape):
+    """Index vectors between the caller's layouts and the library's for draws of a ``column_blocks`` model C on a test grid
+    of shape tshape: (e_idx, n_idx, o_idx) with ``z_e_lib = z_e[:, e_idx]`` (the training points'
+    row order -> (N_s, J)), ``z_n_lib = z_n[:, n_idx]`` (the test grid's C order -> (M_s, M_c), ragged axes first) and
+    ``out = out_lib[:, o_idx]`` (back).  All three go through ``C["perm"]``."""
+    Ns, J = C["Y"].shape
+    rshape = [C["shape"][i] for i in C["ragged"]]
+    T = np.full((int(np.prod(rshape)), J), -1, dtype=np.int64)
+    T[C["obs"]] = np.arange(Ns * J).reshape(Ns, J)
+    T = T.reshape([C["shape"][i] for i in C["perm"]]).transpose(C["inv"]).ravel()
+    T = T[T >= 0]                                        # training row t (grid order, NaN dropped) sits at T[t] of (N_s, J)
+    M = int(np.prod(tshape, dtype=np.int64))
+    n_idx = np.arange(M).reshape(tshape).transpose(C["perm"]).ravel()
+    o_idx = np.arange(M).reshape([tshape[i] for i in C["perm"]]).transpose(C["inv"]).ravel()
+    return np.argsort(T), n_idx, o_idx
+
+
 def reflection_blocks(X, y, axes):
     """Symmetry reduction of an exact GP on a COMPLETE grid (gpim_amd extension; role of the reference's structured class
     gpim/gpreg/skgpr.py:399-448 for kernels that do not factorise over the axes -- csrc/engine.hip: kmat_refl_kernel).

@@ -518,6 +518,35 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
                           const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
                           double* mean_out, double* var_out);
 
+/* Joint posterior draws of the dense-by-Kronecker blocks on (M_s ragged test rows) x (any product of test coordinates for
+ * the complete axes), by Matheron's rule.  With P the union of the ragged training and test rows
+ * (U_s rows), L_P = chol(s2 K_s(P, P) + jitter I), u_i / R_i the union axes and root rows of gpimhip_sample_kron for the
+ * complete axes (U = prod U_i), sigma = noise + m->jitter and c_n = noiseless ? 0 : noise:
+ *   H = L_P zeta,   g_X = H[irow_train, :] x_i R_i[idx_train_i, :],   g_* = H[irow_test, :] x_i R_i[idx_test_i, :]
+ *   out[s]   = mean + g_* - K_*X (K_XX + sigma I)^-1 (g_X + sqrt(sigma) z_e) + sqrt(c_n) z_n
+ *   mean_out = the mean of gpimhip_predict_pkron, by its launches (same bits); a draw at z = 0 is mean_out bit for bit
+ * The draws are exactly N(mean, Sigma_post + c_n I + jitter T (I (x) K_c(u, u)) T^T), T = S_* - K_*X (K_XX + sigma I)^-1 S_X
+ * (S_X, S_* select the training / test points out of P x u): the last term, positive semi-definite and of the size of
+ * jitter, is the price of factoring K_s(P, P), which is numerically singular on a pixel grid.
+ *   Xs .. axes_test_c   as for gpimhip_predict_pkron (test rows must be finite)
+ *   P            device, U_s x p: the union rows, 1 <= U_s <= N_s + M_s
+ *   irow_train, irow_test   HOST, N_s and M_s int32: the position of every training / test ragged row in P
+ *   n_union, axes_union, idx_train, idx_test   as for gpimhip_sample_kron, for the dc complete axes (U_i <= 4096)
+ *   z            device, S x (U_s U + N_s J + M_s M_c) doubles, each row [zeta | z_e | z_n]: zeta row-major over
+ *                (U_s, U_1, .., U_dc), z_e in the layout of Y, z_n in the layout of the output (read only when c_n > 0)
+ *   S >= 1, jitter > 0 (finite);  mean_out: M_s x M_c, samples_out: S x M_s x M_c doubles (device)
+ * Every limit is checked before anything is allocated or launched (GPIMHIP_E_BADARG with a message; the handle stays
+ * usable); a prior factor that is not positive definite -> GPIMHIP_E_NOT_PD at the closing check.  The draws are taken in
+ * groups whose buffers stay within 0.25 GiB; the result does not depend on the grouping, and two calls with the same z give
+ * the same bits (no atomics, fixed reduction shapes).  Workspace: grow-only, counted by gpimhip_workspace_bytes.
+ * Stage timers: see gpimhip_timing_enable. */
+int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                         const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
+                         const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
+                         const double* P, int64_t Us, const int32_t* irow_train, const int32_t* irow_test,
+                         const int32_t* n_union, const double* axes_union, const int32_t* idx_train, const int32_t* idx_test,
+                         const double* z, int32_t S, int32_t noiseless, double jitter, double* mean_out, double* samples_out);
+
 /* Acquisition sweep over the dense grid (gpim/gpbayes/acqfunc.py:11-92):
  *   CB : p0*mean + p1*sd                                  (alpha, beta)
  *   EI : imp*Phi(imp/sd) + sd*phi(imp/sd), imp = mean - p0 - p1     (best, xi)
@@ -813,6 +842,12 @@ int gpimhip_gemm_rect_tile_host(int32_t rect_rows, int32_t rect_cols, int32_t p0
  * gpimhip_sample_kron: 0 = eigen-decomposition of the union axes (absent when the training one serves), 1 = that of the
  *        training axes with y~ and alpha~, 2 = the prior: root rows, zeta, both chains of mode products, 3 = the update:
  *        cross factors, residual, its three chains of mode products (the mean's among them), 5 = the epilogue.
+ * gpimhip_sample_pkron: 6 = the blocks as a whole (theta, eigen-decomposition of the complete axes, factorisation with the
+ *        inverse, the mean's beta; inside it the intervals 0 / 1 of the blocks' factorisation and inverse), 4 = the prior
+ *        factor (covariance build of the union rows and its factorisation), 2 = the prior draws (the union axes'
+ *        eigen-decomposition and root rows, zeta, H = L_P zeta on the tile engine, gathers, mode products), 3 = the update
+ *        (cross factors, residual, projection, the blocks' two solve launches, K*_s products and mode products, the mean's
+ *        among them), 5 = the epilogue.
  * gpimhip_timing_read synchronises, returns the summed milliseconds and the number of timed
  * intervals since the last read, and clears them. */
 int gpimhip_timing_enable(gpimhip_handle h, int enable);
