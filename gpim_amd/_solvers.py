@@ -165,7 +165,7 @@ class Dense:
 
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:
-        reconstructor._sample_supported refuses the other paths before a solver is asked."""
+        the gate of _sampling.Joint refuses the other paths before a solver is asked."""
         return o._handle.lib.gpimhip_sample_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
                                                   Xs.shape[0], ptr(z), z.shape[0], int(bool(noiseless)), float(jitter),
                                                   ptr(mean), ptr(var), ptr(out))
@@ -390,11 +390,6 @@ class Columns(Dense):
             mean[fin_d] = mp[flat_d]
             var[fin_d] = vp[flat_d]
         return rc
-
-    def sample(self, o, *args):
-        raise NotImplementedError(self._NO_DRAWS)
-
-    sample_pathwise = sample_blocks = sample_border = sample_kron = sample
 
     def sample_geometry(self, taxes):
         """What a draw on the product grid of the d coordinate vectors taxes needs beside z: the ragged test rows (as

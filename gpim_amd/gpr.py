@@ -33,7 +33,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, _solvers, gprutils
+from . import _lib, _sampling, _solvers, gprutils
 from .kernels import get_kernel
 
 _F64 = torch.float64
@@ -224,6 +224,7 @@ class reconstructor(_solvers.HostDriver):
             "inducing_points": self.indpoints_all
         }
         self._last_pred = None       # (mean, sd) device tensors of the latest predict()
+        self._draw_bytes = {}        # method -> the largest sample() call that has run (_sampling.reserve)
 
     @property
     def model(self):
@@ -314,406 +315,22 @@ class reconstructor(_solvers.HostDriver):
         mean, var = self._posterior(self._solver.predict, Xrows_d)
         return mean, var.sqrt()
 
-    # ------------------------------------------------------------------ joint posterior draws
-    _SAMPLE_ENGINE = "joint posterior draws are built for the dense double-precision engine only (%s)"
-
+    # ------------------------------------------------------------------ joint posterior draws (_sampling.py)
     def _sample_supported(self):
-        if self.do_sparse:
-            raise NotImplementedError(self._SAMPLE_ENGINE % "sparse=True")
-        if self.do_structured or self.do_symm:
-            raise NotImplementedError(self._SAMPLE_ENGINE % "structured=True")
-        if self.precision == "single":
-            raise NotImplementedError(self._SAMPLE_ENGINE % "precision='single'")
-
-    def _require_finite(self, Xrows_d):
-        """ValueError unless the test rows are finite; one device-to-host look per tensor (boptimizer draws on the same
-        grid at every step)."""
-        if getattr(self, "_finite_rows", None) is Xrows_d:
-            return
-        if not bool(torch.isfinite(Xrows_d).all()):
-            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-        self._finite_rows = Xrows_d
+        _sampling.METHODS["joint"].gate(self)
 
     def _sample_device(self, Xrows_d, z_d, noiseless=False, jitter=None):
         """(samples (S, M), mean (M), var (M)) device tensors of joint draws at the (M, d) device rows `Xrows_d` with the
         standard normals `z_d` (S, M): samples[s] = mean + chol(Sigma) z_d[s].  One library call; mean and var are the
         posterior of predict() (noise included)."""
-        self._sample_supported()
-        self._check_data()
-        S, M = z_d.shape
-        N = self._Xd.shape[0]
-        if Xrows_d.shape[0] != M:
-            raise ValueError("z must have shape (n_samples, %d); got %s" % (Xrows_d.shape[0], tuple(z_d.shape)))
-        self._require_finite(Xrows_d)
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        # the one large allocation of the call: the padded (N + M)^2 joint covariance (kept by the handle, grow-only)
-        order = -(-(N + M) // 128) * 128
-        need = order * (order + (16 if order >= 1024 else 0)) * 8
-        if need > getattr(self, "_sample_bytes", 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: the joint covariance of %d training and %d test points needs %.2f GiB of device "
-                                  "memory, %.2f GiB are free" % (N, M, need / 2.0 ** 30, free / 2.0 ** 30))
-        out = torch.empty((S, M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        var = torch.empty((M,), dtype=_F64, device=self._dev)
-        _lib.check(self._solver.sample(self, Xrows_d, z_d, noiseless, jitter, mean, var, out))
-        self._sample_bytes = max(need, getattr(self, "_sample_bytes", 0))
-        return out, mean, var
-
-    def _pathwise_grid(self, Xrows_d, grid_shape):
-        """(dict of gprutils.pathwise_grid, its idx on the device) for the grid rows `Xrows_d` and the current training
-        rows; kept while both tensors stay the same objects."""
-        c = getattr(self, "_pw_cache", None)
-        if c is not None and c[0] is Xrows_d and c[1] is self._Xd and c[2] == tuple(grid_shape):
-            return c[3], c[4]
-        d = self._spec.dim
-        if len(grid_shape) != d or int(np.prod(grid_shape)) != Xrows_d.shape[0]:
-            raise NotImplementedError("pathwise draws need a product grid: %d test rows do not fill a grid of shape %s in "
-                                      "%d dimensions" % (Xrows_d.shape[0], tuple(grid_shape), d))
-        Xg = Xrows_d.cpu().numpy().T.reshape((d,) + tuple(grid_shape))
-        P = gprutils.pathwise_grid(Xg, self._Xd.cpu().numpy())
-        idx_d = torch.from_numpy(P["idx"]).to(self._dev)
-        self._pw_cache = (Xrows_d, self._Xd, tuple(grid_shape), P, idx_d)
-        return P, idx_d
+        return _sampling.draw_device(self, "joint", Xrows_d, None, z_d, noiseless, jitter)
 
     def _sample_pathwise_device(self, Xrows_d, grid_shape, z_d, noiseless=False, jitter=None):
         """(samples (S, M), mean (M)) device tensors of pathwise draws (Matheron's rule) on the
         complete product grid of shape `grid_shape` whose (M, d) device rows are `Xrows_d`, with the standard normals
         `z_d` (S, M + N) when noiseless, else (S, 2 M + N), split [z_p | z_e | z_n].  One library call: a prior draw through
         the grid's reflection blocks plus one mean-type update against the factor of the training covariance."""
-        self._sample_supported()
-        self._check_data()
-        self._require_finite(Xrows_d)
-        M, N = Xrows_d.shape[0], self._Xd.shape[0]
-        W = M + N + (0 if noiseless else M)
-        if z_d.dim() != 2 or z_d.shape[1] != W:
-            raise ValueError("z must have shape (n_samples, %d) for method='pathwise' (M = %d grid points, N = %d "
-                             "observations%s); got %s" % (W, M, N, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
-        if not (0.0 < jitter <= s):
-            raise ValueError("pathwise draws need 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
-        P, idx_d = self._pathwise_grid(Xrows_d, grid_shape)
-        # the large allocations of the call: one (M / 2^r)^2 block of the prior and the N^2 training covariance
-        nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
-        need = 0
-        for order in (-(-nq // 128) * 128, -(-N // 128) * 128):
-            need += order * (order + (16 if order >= 1024 else 0)) * 8
-        if need > getattr(self, "_pathwise_bytes", 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: a prior block of %d points and the covariance of %d training points need %.2f GiB "
-                                  "of device memory, %.2f GiB are free" % (nq, N, need / 2.0 ** 30, free / 2.0 ** 30))
-        out = torch.empty((z_d.shape[0], M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        _lib.check(self._solver.sample_pathwise(self, Xrows_d, P, idx_d, z_d, noiseless, jitter, mean, out))
-        self._pathwise_bytes = max(need, getattr(self, "_pathwise_bytes", 0))
-        return out, mean
-
-    _BLOCKS_ENGINE = "method='blocks' draws on a fully observed grid in double precision (%s)"
-
-    def _sample_blocks_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
-        """sample(method='blocks'): every argument is checked before anything is stored, so a refused call leaves the model
-        and its stored test grid as they were."""
-        if self.do_sparse:
-            raise NotImplementedError(self._BLOCKS_ENGINE % "sparse=True")
-        if self.precision == "single":
-            raise NotImplementedError(self._BLOCKS_ENGINE % "precision='single'")
-        if self.do_border:
-            raise NotImplementedError(self._BLOCKS_ENGINE % "the image has missing points: method='blocks' needs a fully "
-                                      "observed grid")
-        self._check_data()
-        if Xtest is not None:
-            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-            Xs, shape = self._to_device(gprutils.prepare_test_data(Xtest, precision=self.precision)), tuple(Xtest.shape[1:])
-        elif self._Xtest_d is not None:
-            Xs, shape = self._Xtest_d, tuple(self.fulldims)
-        else:
-            Xs, shape = self._Xd, tuple(self.fulldims)
-        self._require_finite(Xs)
-        P, idx_d = self._pathwise_grid(Xs, shape)
-        M, N = Xs.shape[0], self._Xd.shape[0]
-        if N != M:          # (distinct rows, each on the grid: fewer of them than grid points)
-            first = int(np.setdiff1d(np.arange(M), P["idx"])[0])
-            raise NotImplementedError("method='blocks' needs an observation on every point of the test grid (the test grid "
-                                      "must be the training grid): grid point %s has none (%d observations, %d grid points)"
-                                      % (tuple(int(v) for v in np.unravel_index(first, shape)), N, M))
-        W = 2 * M + (0 if noiseless else M)
-        S = int(n_samples)
-        if z is None:
-            z_d = self._draw_z(S, W, seed)
-        else:
-            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
-            if z_d.dim() != 2 or z_d.shape != (S, W):
-                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='blocks' (M = %d grid points%s); got %s"
-                                 % (W, S, W, M, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
-        if not (0.0 < jitter <= s):
-            raise ValueError("method='blocks' needs 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
-        # the large allocation of the call: one (M / 2^r)^2 reflection block, reused by all 2 x 2^r factorisations
-        nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
-        order = -(-nq // 128) * 128
-        need = order * (order + (16 if order >= 1024 else 0)) * 8
-        if need > getattr(self, "_blocks_bytes", 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: a reflection block of %d points needs %.2f GiB of device memory, %.2f GiB are free"
-                                  % (nq, need / 2.0 ** 30, free / 2.0 ** 30))
-        if Xtest is not None:
-            self._resolve_test_grid(Xtest)
-        out = torch.empty((S, M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        Pd = dict(P, idx_d=None if np.array_equal(P["idx"], np.arange(M)) else idx_d)
-        _lib.check(self._solver.sample_blocks(self, Xs, Pd, z_d, noiseless, jitter, mean, out))
-        self._blocks_bytes = max(need, getattr(self, "_blocks_bytes", 0))
-        return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
-
-    _BORDER_ENGINE = "method='border' draws on an image with missing points through its bordered reflection blocks, in " \
-                     "double precision (%s)"
-
-    def _sample_border_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
-        """sample(method='border'): every argument is checked before anything is stored, so a refused call leaves the model
-        and its stored test grid as they were."""
-        if self.do_sparse:
-            raise NotImplementedError(self._BORDER_ENGINE % "sparse=True")
-        if self.precision == "single":
-            raise NotImplementedError(self._BORDER_ENGINE % "precision='single'")
-        if not self.do_border:
-            if self.do_symm or self.do_structured:
-                raise NotImplementedError(self._BORDER_ENGINE % "the grid is fully observed: use method='blocks'")
-            raise NotImplementedError(self._BORDER_ENGINE % "a dense model: use method='pathwise', or skreconstructor for an "
-                                      "image or cube with missing pixels")
-        self._check_data()
-        B = self._solver.S
-        gshape = tuple(len(c) for c in B["axes"])
-        if Xtest is not None:
-            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-            Xs, shape = self._to_device(gprutils.prepare_test_data(Xtest, precision=self.precision)), tuple(Xtest.shape[1:])
-        elif self._Xtest_d is not None:
-            Xs, shape = self._Xtest_d, tuple(self.fulldims)
-        else:
-            Xs, shape = None, gshape
-        c = getattr(self, "_border_grid", None)
-        if c is None:
-            G = np.array(np.meshgrid(*B["axes"], indexing="ij")).reshape(len(gshape), -1).T
-            c = self._border_grid = [self._to_device(np.ascontiguousarray(G)),
-                                     torch.from_numpy(B["miss"].astype(np.int64)).to(self._dev), None]
-        G_d, miss_d = c[0], c[1]
-        if Xs is not None and c[2] is not Xs:
-            self._require_finite(Xs)
-            if shape != gshape or Xs.shape != G_d.shape or not bool(torch.equal(Xs, G_d)):
-                raise NotImplementedError("method='border' needs the completed training grid as its test grid (Xtest None, the "
-                                          "stored grid, or a grid equal to it: shape %s); got a grid of shape %s that is not it"
-                                          % (gshape, shape))
-            if Xtest is None:
-                c[2] = Xs                   # the stored grid: compared once
-        M = G_d.shape[0]
-        W = 2 * M + (0 if noiseless else M)
-        S = int(n_samples)
-        if z is None:
-            z_d = self._draw_z(S, W, seed)
-        else:
-            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
-            if z_d.dim() != 2 or z_d.shape != (S, W):
-                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='border' (M = %d grid points%s); got %s"
-                                 % (W, S, W, M, "" if noiseless else ", noise on the grid", tuple(z_d.shape)))
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        s = float(self._spec.constrained(self._u)[2]) + self._spec.jitter
-        if not (0.0 < jitter <= s):
-            raise ValueError("method='border' needs 0 < jitter <= noise + the model's jitter = %g; got %g" % (s, jitter))
-        # the large allocation beyond a prediction of the model: one (M / 2^r)^2 block for the prior factors
-        nq = B["Xq"].shape[0]
-        order = -(-nq // 128) * 128
-        need = order * (order + (16 if order >= 1024 else 0)) * 8
-        if need > getattr(self, "_border_bytes", 0):
-            free, total = torch.cuda.mem_get_info(self._dev)
-            if need > free:
-                raise MemoryError("sample: a reflection block of %d points needs %.2f GiB of device memory, %.2f of %.2f GiB are "
-                                  "free" % (nq, need / 2.0 ** 30, free / 2.0 ** 30, total / 2.0 ** 30))
-        if Xtest is not None:
-            self._resolve_test_grid(Xtest)
-        out = torch.empty((S, M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        P = {"shape": gshape, "mask": B["mask"], "twoc": B["twoc"]}
-        _lib.check(self._solver.sample_border(self, G_d, P, miss_d, z_d, noiseless, jitter, mean, out))
-        self._border_bytes = max(need, getattr(self, "_border_bytes", 0))
-        return out.cpu().numpy().reshape((S,) + gshape).astype(self._np_out, copy=False)
-
-    _KRON_ENGINE = "method='kron' draws through the Kronecker eigenbasis: reconstructor(..., kernel='RBF', structured=True) " \
-                   "or skreconstructor(..., 'RBF') on a fully observed grid, in double precision (%s)"
-
-    def _sample_kron_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
-        """sample(method='kron'): every argument is checked before anything is stored, so a refused call leaves the model,
-        its stored test grid and the solver's test axes as they were."""
-        sol = self._solver
-        if not isinstance(sol, _solvers.Kron):
-            what = ("sparse=True" if self.do_sparse else "the image has missing points: use method='border'" if self.do_border
-                    else "a reflection-block model: use method='blocks'" if self.do_symm
-                    else "a dense model: use method='joint' or 'pathwise'")
-            raise NotImplementedError(self._KRON_ENGINE % what)
-        if self.precision == "single":
-            raise NotImplementedError(self._KRON_ENGINE % "precision='single'")
-        self._check_data()
-        if Xtest is not None:
-            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-            try:
-                taxes = gprutils.grid_axes(Xtest)[0]
-            except NotImplementedError as e:
-                raise NotImplementedError("method='kron' needs a product test grid: %s" % e)
-            shape = tuple(np.shape(Xtest)[1:])
-        else:
-            taxes, shape = sol.taxes[0], tuple(self.fulldims)
-            if not all(np.isfinite(t).all() for t in taxes):
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-        union = gprutils.union_axes(sol.axes, taxes)
-        for i, a in enumerate(union[0]):
-            if len(a) > 4096:
-                raise NotImplementedError("method='kron': the union of the training and the test coordinates of axis %d has "
-                                          "%d entries, the eigen-solver takes at most 4096" % (i, len(a)))
-        PU = int(np.prod([len(a) for a in union[0]], dtype=np.int64))
-        N, M = self._Xd.shape[0], int(np.prod(shape, dtype=np.int64))
-        W = PU + N + M
-        S = int(n_samples)
-        if S < 1:
-            raise ValueError("n_samples must be at least 1; got %r" % (n_samples,))
-        parts = "[zeta | z_e | z_n] = %d union-grid points + %d observations + %d test points" % (PU, N, M)
-        if z is not None:
-            zt = z if torch.is_tensor(z) else np.asarray(z)
-            if zt.ndim != 2 or tuple(zt.shape) != (S, W):
-                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='kron' (%s); got %s"
-                                 % (W, S, W, parts, tuple(zt.shape)))
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        if not (0.0 <= jitter < np.inf):
-            raise ValueError("method='kron' needs a finite jitter >= 0; got %g" % jitter)
-        # what the call allocates: z, the draws and the mean here; in the library (csrc/kron.hip) zeta and the two buffers of
-        # the mode products (S x the largest tensor a chain of mode products passes through), the gathered root rows, the
-        # union axes' matrices when the training decomposition does not serve, and the prediction workspace
-        nu, nn, nm = [len(a) for a in union[0]], [len(c) for c in sol.axes], [len(t) for t in taxes]
-        smax, pmax = max(N, M), N
-        for src, dst in ((nu, nn), (nu, nm), (nn, nm)):
-            cur = int(np.prod(src, dtype=np.int64))
-            for a, b in zip(src, dst):
-                cur = cur // a * b
-                smax = max(smax, cur)
-                if src is nn:
-                    pmax = max(pmax, cur)
-        shared = nu == nn and all(np.array_equal(i, np.arange(len(i))) for i in union[1])
-        lib_axes = 0 if shared else 2 * sum(nu) + 5 * sum(a * a for a in nu)
-        lib_rows = sum((a + b) * c for a, b, c in zip(nn, nm, nu))
-        lib_pred = sum(nm) + 2 * sum(a * b for a, b in zip(nn, nm)) + 2 * pmax
-        z_on_device = torch.is_tensor(z) and z.is_cuda and z.dtype == _F64
-        need = 8 * (S * ((0 if z_on_device else W) + M + PU + 2 * smax) + M + lib_axes + lib_rows + lib_pred)
-        if need > getattr(self, "_kron_bytes", 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: %d draws on %d test points through %d union-grid points need %.2f GiB of device "
-                                  "memory, %.2f GiB are free" % (S, M, PU, need / 2.0 ** 30, free / 2.0 ** 30))
-        z_d = self._draw_z(S, W, seed) if z is None else self._to_device(z if torch.is_tensor(z) else np.asarray(z))
-        if Xtest is not None:
-            self._resolve_test_grid(Xtest)
-        out = torch.empty((S, M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        _lib.check(sol.sample_kron(self, taxes, union, z_d, noiseless, jitter, mean, out))
-        self._kron_bytes = max(need, getattr(self, "_kron_bytes", 0))
-        return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
-
-    _COLUMNS_ENGINE = "method='columns' draws through the dense-by-Kronecker blocks: skreconstructor(..., 'RBF') whose solver " \
-                      "is 'columns' (whole columns of the grid missing), in double precision (%s)"
-
-    def _sample_columns_host(self, n_samples, Xtest, noiseless, seed, z, jitter):
-        """sample(method='columns'): every argument is checked before anything is stored, so a refused call leaves the model,
-        its stored test grid and the solver's test axes as they were."""
-        sol = self._solver
-        if not isinstance(sol, _solvers.Columns):
-            what = ("sparse=True" if self.do_sparse else "the missing points are scattered: use method='border'" if self.do_border
-                    else "the Kronecker model of a complete grid: use method='kron'" if isinstance(sol, _solvers.Kron)
-                    else "a reflection-block model: use method='blocks'" if self.do_symm
-                    else "a dense model: use method='joint' or 'pathwise'")
-            raise NotImplementedError(self._COLUMNS_ENGINE % what)
-        if self.precision == "single":
-            raise NotImplementedError(self._COLUMNS_ENGINE % "precision='single'")
-        self._check_data()
-        if Xtest is not None:
-            if not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-            try:
-                taxes = gprutils.grid_axes(Xtest)[0]
-            except NotImplementedError as e:
-                raise NotImplementedError("method='columns' needs a product test grid: %s" % e)
-            shape = tuple(np.shape(Xtest)[1:])
-        else:
-            taxes, shape = sol.taxes, tuple(self.fulldims)
-            if taxes is None:
-                raise NotImplementedError("method='columns' needs a product test grid: the model holds none (pass Xtest)")
-            if not all(np.isfinite(t).all() for t in taxes):
-                raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-        S = int(n_samples)
-        if S < 1:
-            raise ValueError("n_samples must be at least 1; got %r" % (n_samples,))
-        jitter = self._spec.jitter if jitter is None else float(jitter)
-        if not (0.0 < jitter < np.inf):
-            raise ValueError("method='columns' needs a finite jitter > 0 (the prior factor of the ragged rows); got %g" % jitter)
-        geometry = sol.sample_geometry(taxes)
-        rows, caxes, (P, _, _), (au, ic, _) = geometry
-        for i, a in enumerate(au):
-            if len(a) > 4096:
-                raise NotImplementedError("method='columns': the union of the training and the test coordinates of axis %d has "
-                                          "%d entries, the eigen-solver takes at most 4096" % (sol.C["complete"][i], len(a)))
-        Us, U = len(P), int(np.prod([len(a) for a in au], dtype=np.int64))
-        N, M = self._Xd.shape[0], int(np.prod(shape, dtype=np.int64))
-        W = Us * U + N + M
-        parts = "[zeta | z_e | z_n] = %d x %d union rows x union-axes points + %d observations + %d test points" % (Us, U, N, M)
-        if z is not None:
-            zt = z if torch.is_tensor(z) else np.asarray(z)
-            if zt.ndim != 2 or tuple(zt.shape) != (S, W):
-                raise ValueError("z must have shape (n_samples, %d) = (%d, %d) for method='columns' (%s); got %s"
-                                 % (W, S, W, parts, tuple(zt.shape)))
-        # what the call allocates: z (as given and in the library's layout), the draws twice and the mean here; in the library
-        # (csrc/api.hip: gpimhip_sample_pkron) the prior factor, zeta and H, the mode products' and the blocks' buffers
-        Ns, J = sol.C["Y"].shape
-        need = 8 * (S * ((1 if torch.is_tensor(z) and z.is_cuda and z.dtype == _F64 else 2) * W + 2 * M) + 2 * M
-                    + self._columns_library_doubles(S, Ns, len(rows), Us, J, [len(a) for a in au],
-                                                    [len(c) for c in sol.C["axes_c"]], [len(c) for c in caxes]))
-        if need > getattr(self, "_columns_bytes", 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: %d draws on %d test points through %d x %d union points need %.2f GiB of device "
-                                  "memory, %.2f GiB are free" % (S, M, Us, U, need / 2.0 ** 30, free / 2.0 ** 30))
-        z_d = self._draw_z(S, W, seed) if z is None else self._to_device(z if torch.is_tensor(z) else np.asarray(z))
-        if Xtest is not None:
-            self._resolve_test_grid(Xtest)
-        out = torch.empty((S, M), dtype=_F64, device=self._dev)
-        mean = torch.empty((M,), dtype=_F64, device=self._dev)
-        _lib.check(sol.sample_columns(self, taxes, z_d, noiseless, jitter, mean, out, geometry))
-        self._columns_bytes = max(need, getattr(self, "_columns_bytes", 0))
-        return out.cpu().numpy().reshape((S,) + shape).astype(self._np_out, copy=False)
-
-    @staticmethod
-    def _columns_library_doubles(S, Ns, Ms, Us, J, nu, nn, nm):
-        """The doubles gpimhip_sample_pkron's own buffers take (its arena and the prediction slab), by the library's formulas."""
-        pad = lambda n: -(-int(n) // 128) * 128
-        np_, npU = pad(Ns), pad(Us)
-        nb = np_ // 128
-        mc = min(pad(Ms), max(128, (1 << 26) // (J * nb) // 128 * 128))
-        U = int(np.prod(nu, dtype=np.int64))
-        pmax, cur, cx, ct, maxX, maxT = 1, J, U, U, U, U
-        for a, b, c in zip(nu, nn, nm):
-            cur, cx, ct = cur // b * c, cx // a * b, ct // a * c
-            pmax, maxX, maxT = max(pmax, cur), max(maxX, cx), max(maxT, ct)
-        big = max(Ns * maxX, Ms * maxT)
-        per_draw = 2 * npU * U + 3 * big + 2 * pmax * mc + J * (3 * np_ + mc)
-        sg = max(1, min(S, (1 << 25) // per_draw))
-        groups = -(-S // sg)
-        sg = -(-S // groups)
-        cols, Sp, rowsP = pad(sg * U), pad(sg), pad(sg * J)
-        arena = npU * (npU + 16) + 2 * npU * cols + 3 * sg * big + 2 * J * np_ * Sp + rowsP * (np_ + mc) + 2 * sg * pmax * mc
-        slab = np_ * (mc + 16) + nb * mc + pad(J) * mc + 4 * pmax * mc
-        return arena + slab
+        return _sampling.draw_device(self, "pathwise", Xrows_d, grid_shape, z_d, noiseless, jitter)[:2]
 
     def _draw_z(self, n_samples, M, seed=None, generator=None):
         if generator is None and seed is not None:
@@ -777,51 +394,9 @@ class reconstructor(_solvers.HostDriver):
         ``[zeta | z_e | z_n]``: ``zeta`` row-major over ``(U_s, U_1, ...)``, ``z_e`` in the training points' row order,
         ``z_n`` in test-grid order.  ``z = 0`` gives ``predict``'s mean bit for bit.  The other five methods refuse this
         model, and ``'columns'`` refuses every other model, naming the method it has."""
-        if method not in ("joint", "pathwise", "blocks", "border", "kron", "columns"):
+        if method not in _sampling.METHODS:
             raise ValueError("method must be 'joint', 'pathwise', 'blocks', 'border', 'kron' or 'columns'; got %r" % (method,))
-        if method == "columns":
-            return self._sample_columns_host(n_samples, Xtest, noiseless, seed, z, jitter)
-        if isinstance(self._solver, _solvers.Columns):
-            raise NotImplementedError(self._solver._NO_DRAWS + " (got method=%r)" % (method,))
-        if method == "kron":
-            return self._sample_kron_host(n_samples, Xtest, noiseless, seed, z, jitter)
-        if method == "blocks":
-            return self._sample_blocks_host(n_samples, Xtest, noiseless, seed, z, jitter)
-        if method == "border":
-            return self._sample_border_host(n_samples, Xtest, noiseless, seed, z, jitter)
-        self._sample_supported()
-        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-            # (refused before it replaces the stored test grid)
-            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
-        if method == "pathwise" and Xtest is not None:
-            # a grid the method cannot take (not a product grid, no symmetric axis, a training row off it), like any other
-            # refused argument, leaves the stored test grid as it was (the dense solver keeps no grid state of its own)
-            kept = (self.Xtest, self._Xtest_d, self.fulldims)
-            try:
-                return self._sample_host(n_samples, Xtest, noiseless, seed, z, jitter, method)
-            except Exception:
-                self.Xtest, self._Xtest_d, self.fulldims = kept
-                raise
-        return self._sample_host(n_samples, Xtest, noiseless, seed, z, jitter, method)
-
-    def _sample_host(self, n_samples, Xtest, noiseless, seed, z, jitter, method):
-        self._resolve_test_grid(Xtest)
-        Xs = self._Xtest_d
-        M = Xs.shape[0]
-        if method == "pathwise":
-            M = M + self._Xd.shape[0] + (0 if noiseless else M)       # the width of z; the draws are (n_samples, grid)
-        if z is None:
-            z_d = self._draw_z(int(n_samples), M, seed)
-        else:
-            z_d = self._to_device(np.asarray(z) if not torch.is_tensor(z) else z)
-            if z_d.dim() != 2 or z_d.shape != (int(n_samples), M):
-                raise ValueError("z must have shape (n_samples, %d) = (%d, %d); got %s"
-                                 % (M, int(n_samples), M, tuple(z_d.shape)))
-        if method == "pathwise":
-            out, _ = self._sample_pathwise_device(Xs, tuple(self.fulldims), z_d, noiseless, jitter)
-        else:
-            out, _, _ = self._sample_device(Xs, z_d, noiseless, jitter)
-        return out.cpu().numpy().reshape((z_d.shape[0],) + tuple(self.fulldims)).astype(self._np_out, copy=False)
+        return _sampling.draw(self, method, n_samples, Xtest, noiseless, seed, z, jitter)
 
     def run(self, **kwargs):
         """train + predict; returns (mean, sd, hyperparams) (gpr.py:257-283)."""

@@ -39,7 +39,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _sampling
 from . import gprutils
 from ._solvers import DeviceBlocks, HostDriver
 from .skgpr import BORDER_FACTOR
@@ -176,6 +176,7 @@ class vreconstructor(HostDriver):
         self.loss_all = []
         self.hyperparams = {"lengthscale": self.lscales}
         self.verbose = verbose
+        self._draw_bytes = {}           # method -> the largest sample() call that has run (_sampling.reserve)
 
     @staticmethod
     def _reflection_blocks(X, y):
@@ -358,14 +359,10 @@ class vreconstructor(HostDriver):
             raise ValueError("sample: jitter is relative to each task's noise and must be > 0%s; got %g"
                              % (" and <= 1 for method='blocks'" if method == "blocks" else "", jitter))
         # the test grid, resolved without storing it: a refused call leaves the model as it was
-        if Xtest is not None:
-            Xs_h, shape = gprutils.prepare_test_data(Xtest), tuple(Xtest.shape[1:])
-        elif self.Xtest is not None:
-            Xs_h, shape = self.Xtest, tuple(self.fulldims[:-1])
-        else:
-            Xs_h, shape = self.X, (self.X.shape[0],)
+        Xs_h, shape = _sampling.rows_grid(Xtest, gprutils.prepare_test_data, (self.Xtest, tuple(self.fulldims[:-1])),
+                                          (self.X, (self.X.shape[0],)))
         if not bool(torch.isfinite(Xs_h).all()):
-            raise ValueError("sample: the test grid must be finite (NaN rows have no joint distribution)")
+            raise ValueError(_sampling.FINITE)
         M, N, d = Xs_h.shape[0], self.X.shape[0], self.X.shape[1]
         P = None
         if method == "blocks":
@@ -392,19 +389,11 @@ class vreconstructor(HostDriver):
                                  % (T, S, W, method, M, tuple(z_d.shape)))
         # the one large allocation of the call (kept by the handle, grow-only): a single-output call's at the same sizes
         if method == "joint":
-            order = -(-(N + M) // 128) * 128
-            what = "the joint covariance of %d observed rows and %d test points" % (N, M)
+            need, what = _sampling.factor_bytes(N + M), "the joint covariance of %d observed rows and %d test points needs" % (N, M)
         else:
-            nq = int(np.prod([(n + 1) // 2 if k in P["dims"] else n for k, n in enumerate(P["shape"])]))
-            order = -(-nq // 128) * 128
-            what = "a reflection block of %d points" % nq
-        need = order * (order + (16 if order >= 1024 else 0)) * 8
-        key = "_sample_bytes_" + method
-        if need > getattr(self, key, 0):
-            free = torch.cuda.mem_get_info(self._dev)[0]
-            if need > free:
-                raise MemoryError("sample: %s needs %.2f GiB of device memory, %.2f GiB are free"
-                                  % (what, need / 2.0 ** 30, free / 2.0 ** 30))
+            nq = _sampling.block_points(P)
+            need, what = _sampling.factor_bytes(nq), "a reflection block of %d points needs" % nq
+        _sampling.reserve(self, method, need, what)
         self._resolve_test_grid(Xtest)
         Xo, Yo = self._observed()
         Xs = Xs_h.to(self._dev, _F64).contiguous()
@@ -423,5 +412,5 @@ class vreconstructor(HostDriver):
             rc = lib.gpimhip_sample_vgp_blocks(*head, _lib.ptr(Xs), cshape, int(P["mask"]), twoc, _lib.ptr(Yg), _lib.ptr(self._u),
                                                _lib.ptr(z_d), S, int(bool(noiseless)), jitter, None, _lib.ptr(out))
         _lib.check(rc)
-        setattr(self, key, max(need, getattr(self, key, 0)))
+        _sampling.record(self, method, need)
         return out.cpu().numpy().reshape((S,) + shape + (T,))

@@ -231,6 +231,61 @@ def test_sample_refused_off_the_dense_double_engine(fitted):
             model.sample()
 
 
+def model_of(gpim_amd, method):
+    """(the smallest model that reaches `method`, the Xtest of the call): 8 x 8 images, an 8 x 7 x 5 cube for 'columns'"""
+    from columns_oracle import cube
+    rng = np.random.default_rng(0)
+    ii, jj = np.meshgrid(np.arange(8.0), np.arange(8.0), indexing="ij")
+    full = np.cos(ii / 3.0) * np.sin(jj / 2.0 + 0.3) + 0.05 * rng.standard_normal((8, 8))
+    Xf = gpim_amd.utils.get_full_grid(full)
+    kw = dict(lengthscale=[[1., 1.], [6., 6.]], iterations=1, verbose=0)
+    if method in ("joint", "pathwise"):             # 40 scattered observations; off the grid for 'joint'
+        R = full.copy()
+        R.ravel()[rng.permutation(64)[:24]] = np.nan
+        Xs = gpim_amd.utils.get_sparse_grid(R)
+        if method == "joint":
+            Xs = Xs + np.where(np.isnan(Xs), 0.0, 0.3 * rng.random(Xs.shape))
+        return gpim_amd.reconstructor(Xs, R, Xf, kernel="RBF", **kw), None
+    if method == "blocks":
+        return gpim_amd.reconstructor(Xf, full, Xf, kernel="Matern52", structured=True, **kw), None
+    if method == "kron":                            # drawn on a grid twice as fine
+        return (gpim_amd.reconstructor(Xf, full, Xf, kernel="RBF", structured=True, **kw),
+                gpim_amd.utils.get_full_grid(full, dense_x=0.5))
+    if method == "border":                          # 5 scattered pixels missing
+        R = full.copy()
+        for p in ((1, 2), (3, 5), (4, 1), (6, 6), (2, 4)):
+            R[p] = np.nan
+        Xs = gpim_amd.utils.get_sparse_grid(R)
+        return gpim_amd.reconstructor(Xs, R, Xf, kernel="Matern52", structured=True,
+                                      _border=gpim_amd.utils.border_blocks(Xs, R), **kw), None
+    Xg, Xc, Rc = cube((8, 7, 5), (0, 1), 0.6, seed=0)       # 40 % of the pixels observed
+    rec = gpim_amd.skreconstructor(Xc, Rc, Xg, kernel="RBF", lengthscale=[[0.1] * 3, [100.0] * 3], verbose=0)
+    assert rec.solver == "columns"
+    return rec, None
+
+
+@pytest.mark.parametrize("method", ("joint", "pathwise", "blocks", "border", "kron", "columns"))
+def test_seeded_draw_is_the_documented_randn(ensure_built, method):
+    """sample(seed=k) is sample(z=torch.randn((S, W), dtype=float64, device=dev, generator=Generator(dev).manual_seed(k))),
+    bit for bit, with W the width the method's description plans: the position and the width of the implicit draw."""
+    import gpim_amd
+    from gpim_amd import _sampling
+    rec, Xtest = model_of(gpim_amd, method)
+    m = _sampling.METHODS[method]
+    S, k = 2, 3
+    for noiseless in (False, True):
+        W = m.plan(m.geometry(rec, *m.grid(rec, Xtest)), S, noiseless, True)[0]
+        z = torch.randn((S, W), dtype=torch.float64, device=rec._dev, generator=torch.Generator(rec._dev).manual_seed(k))
+        a = rec.sample(n_samples=S, Xtest=Xtest, seed=k, noiseless=noiseless, method=method)
+        b = rec.sample(n_samples=S, Xtest=Xtest, z=z, noiseless=noiseless, method=method)
+        assert a.shape == (S,) + tuple(rec.fulldims) and np.isfinite(a).all() and a.std() > 0
+        assert np.array_equal(a, b), (method, noiseless, W)
+        # a z one column wider or narrower is refused: W is the only width
+        for bad in (W - 1, W + 1):
+            with pytest.raises(ValueError, match="z must have shape"):
+                rec.sample(n_samples=S, Xtest=Xtest, z=np.zeros((S, bad)), noiseless=noiseless, method=method)
+
+
 def bo_problem():
     rng = np.random.default_rng(4)
     ii, jj = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
