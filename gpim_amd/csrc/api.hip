@@ -30,61 +30,13 @@ static int deal_chunk(int ntiles = 1 << 30) { return std::max(1, std::min(64, nt
 // ------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int dev_alloc(gpimhip_ctx* h, T** p, int64_t count) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, (size_t)count * sizeof(T));
-    if (e != hipSuccess) {
-        gpim_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-        return GPIMHIP_E_NOMEM;
-    }
-    *p = (T*)q;
-    h->bytes += count * (int64_t)sizeof(T);
-    return GPIMHIP_OK;
-}
-template <typename T>
-static void dev_free(gpimhip_ctx* h, T** p, int64_t count) {
-    if (*p) {
-        (void)hipFree(*p);
-        h->bytes -= count * (int64_t)sizeof(T);
-        *p = nullptr;
-    }
-}
-// grow-only buffer of *cap elements.  The stream is synchronised before the free: earlier launches may still read the buffer.
-template <typename T>
-static int dev_grow(gpimhip_ctx* h, T** p, int64_t* cap, int64_t want) {
-    if (*cap >= want) return GPIMHIP_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    dev_free(h, p, *cap);
-    *cap = 0;
-    GP_TRY(dev_alloc(h, p, want));
-    *cap = want;
-    return GPIMHIP_OK;
-}
 
 // the N x N matrices hold floats on a single-precision handle: same element counts, half the doubles
 static inline int64_t mat_doubles(const gpimhip_ctx* h, int64_t elements) { return h->fp32 ? (elements + 1) / 2 : elements; }
 
 static void ws_release_matrix(gpimhip_ctx* h) {
-    const int64_t np = h->np, nb = np / NB, B = h->ws_batch;
-    if (!np) return;
-    dev_free(h, &h->A, mat_doubles(h, B * np * h->ld));
-    dev_free(h, &h->B, mat_doubles(h, B * np * h->ld));
-    dev_free(h, &h->Tm, mat_doubles(h, B * np * h->ld));
-    dev_free(h, &h->dinv, mat_doubles(h, B * nb * NB * NB));
-    dev_free(h, &h->dinvB, B * nb * NB * NB);
-    dev_free(h, &h->pcopy, B * NB * NB);
-    dev_free(h, &h->ypad, B * np);
-    dev_free(h, &h->z, B * np);
-    dev_free(h, &h->alpha, B * np);
-    dev_free(h, &h->logdet_part, B * nb);
-    dev_free(h, &h->grad_part, B * nb * (nb + 1) / 2 * 8);
-    dev_free(h, &h->gemv_part, B * (int64_t)gemv_tri_chunks(np) * np);
-    dev_free(h, &h->fin_counter, (int64_t)B);
-    dev_free(h, &h->theta, B);
-    dev_free(h, &h->adam_m, B * MAXP);
-    dev_free(h, &h->adam_v, B * MAXP);
-    dev_free(h, &h->iter, B);
+    dev_release(h, h->A, h->B, h->Tm, h->dinv, h->dinvB, h->pcopy, h->ypad, h->z, h->alpha, h->logdet_part, h->grad_part,
+                h->gemv_part, h->fin_counter, h->theta, h->adam_m, h->adam_v, h->iter);
     h->np = 0;
     h->ws_batch = 0;
 }
@@ -104,23 +56,22 @@ static int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matric
     HIP_TRY(hipStreamSynchronize(h->stream));
     ws_release_matrix(h);
     const int64_t nb = np / NB;
-    // sizes first: if an allocation in the middle fails, ws_release_matrix() frees what exists (it
-    // frees by pointer, with these sizes for the byte accounting)
+    // (if an allocation in the middle fails, ws_release_matrix() frees what exists)
     h->np = np;
     h->ws_batch = B;
     h->ld = ld;
     int rc = GPIMHIP_OK;
-    if ((matrices && ((rc = dev_alloc(h, &h->A, mat_doubles(h, B * np * ld))) ||
-                      (rc = dev_alloc(h, &h->B, mat_doubles(h, B * np * ld))) ||
-                      (rc = dev_alloc(h, &h->Tm, mat_doubles(h, B * np * ld))))) ||
-        (rc = dev_alloc(h, &h->dinv, mat_doubles(h, B * nb * NB * NB))) ||
-        (rc = dev_alloc(h, &h->dinvB, B * nb * NB * NB)) ||
-        (rc = dev_alloc(h, &h->pcopy, (int64_t)B * NB * NB)) ||
-        (rc = dev_alloc(h, &h->ypad, B * np)) || (rc = dev_alloc(h, &h->z, B * np)) ||
-        (rc = dev_alloc(h, &h->alpha, B * np)) || (rc = dev_alloc(h, &h->logdet_part, B * nb)) ||
-        (rc = dev_alloc(h, &h->grad_part, B * nb * (nb + 1) / 2 * 8)) || (rc = dev_alloc(h, &h->gemv_part, B * (int64_t)gemv_tri_chunks(np) * np)) || (rc = dev_alloc(h, &h->fin_counter, (int64_t)B)) || (rc = dev_alloc(h, &h->theta, (int64_t)B)) ||
-        (rc = dev_alloc(h, &h->adam_m, (int64_t)B * MAXP)) || (rc = dev_alloc(h, &h->adam_v, (int64_t)B * MAXP)) ||
-        (rc = dev_alloc(h, &h->iter, (int64_t)B))) {
+    if ((matrices && ((rc = h->A.alloc(h, mat_doubles(h, B * np * ld))) ||
+                      (rc = h->B.alloc(h, mat_doubles(h, B * np * ld))) ||
+                      (rc = h->Tm.alloc(h, mat_doubles(h, B * np * ld))))) ||
+        (rc = h->dinv.alloc(h, mat_doubles(h, B * nb * NB * NB))) ||
+        (rc = h->dinvB.alloc(h, B * nb * NB * NB)) ||
+        (rc = h->pcopy.alloc(h, (int64_t)B * NB * NB)) ||
+        (rc = h->ypad.alloc(h, B * np)) || (rc = h->z.alloc(h, B * np)) ||
+        (rc = h->alpha.alloc(h, B * np)) || (rc = h->logdet_part.alloc(h, B * nb)) ||
+        (rc = h->grad_part.alloc(h, B * nb * (nb + 1) / 2 * 8)) || (rc = h->gemv_part.alloc(h, B * (int64_t)gemv_tri_chunks(np) * np)) || (rc = h->fin_counter.alloc(h, (int64_t)B)) || (rc = h->theta.alloc(h, (int64_t)B)) ||
+        (rc = h->adam_m.alloc(h, (int64_t)B * MAXP)) || (rc = h->adam_v.alloc(h, (int64_t)B * MAXP)) ||
+        (rc = h->iter.alloc(h, (int64_t)B))) {
         ws_release_matrix(h);
         return rc;
     }
@@ -130,14 +81,12 @@ static int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matric
         HIP_TRY(hipMemsetAsync(h->Tm, 0, (size_t)mat_doubles(h, B * np * ld) * sizeof(double), h->stream));
         HIP_TRY(hipMemsetAsync(h->B, 0, (size_t)mat_doubles(h, B * np * ld) * sizeof(double), h->stream));
     }
-    if (h->fp32 && h->refine_cap < 10 * (int64_t)B * np) {
-        dev_free(h, &h->refine, h->refine_cap);
-        h->refine_cap = 0;
-        if ((rc = dev_alloc(h, &h->refine, 10 * (int64_t)B * np))) {
+    if (h->fp32 && h->refine.cap < 10 * (int64_t)B * np) {
+        h->refine.release(h);           // (no launch still reads it: the stream was synchronised above)
+        if ((rc = h->refine.alloc(h, 10 * (int64_t)B * np))) {
             ws_release_matrix(h);       // the next call with this N must not take the early return without it
             return rc;
         }
-        h->refine_cap = 10 * (int64_t)B * np;
     }
     // launch plans of the single-GPU path (built here: building one synchronises the stream, which a graph
     // capture does not allow); the distributed factorisation has its own (gpimhip_dist_setup)
@@ -154,10 +103,8 @@ int ws_ensure(gpimhip_ctx* h, int64_t N) { return ws_ensure_b(h, N, h->nbatch, 0
 static int ws_ensure_padded(gpimhip_ctx* h, int64_t N) { return ws_ensure_b(h, N, h->nbatch, 1); }
 
 static void ws_release_predict(gpimhip_ctx* h) {
-    dev_free(h, &h->Ks, mat_doubles(h, h->ks_batch * h->ks_rows * (h->ks_cols + 16)));
-    dev_free(h, &h->colpart, h->ks_batch * (h->ks_rows / NB) * h->ks_cols);
-    dev_free(h, &h->mean_tmp, h->ks_batch * h->ks_cols);
-    for (auto& pl : h->pred_lists) dev_free(h, &pl.tiles, pl.n);
+    dev_release(h, h->Ks, h->colpart, h->mean_tmp);
+    for (auto& pl : h->pred_lists) pl.tiles.release(h);
     h->pred_lists.clear();
     h->pred_tiles = nullptr;
     h->pred_ntiles = 0;
@@ -176,12 +123,12 @@ int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         const int64_t cap = (h->ks_rows == np && h->ks_batch == B) ? std::max(mc, h->ks_cols) : mc;
         ws_release_predict(h);
-        h->ks_rows = np;                 // sizes first: a failed allocation is cleaned up by pointer
+        h->ks_rows = np;
         h->ks_cols = cap;
         h->ks_batch = B;
         int rc = GPIMHIP_OK;
-        if ((rc = dev_alloc(h, &h->Ks, mat_doubles(h, B * np * (cap + 16)))) || (rc = dev_alloc(h, &h->colpart, B * (np / NB) * cap)) ||
-            (rc = dev_alloc(h, &h->mean_tmp, B * cap))) {
+        if ((rc = h->Ks.alloc(h, mat_doubles(h, B * np * (cap + 16)))) || (rc = h->colpart.alloc(h, B * (np / NB) * cap)) ||
+            (rc = h->mean_tmp.alloc(h, B * cap))) {
             ws_release_predict(h);
             return rc;
         }
@@ -190,7 +137,7 @@ int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc) {
     for (auto& pl : h->pred_lists)
         if (pl.nc == nc) {
             h->pred_tiles = pl.tiles;
-            h->pred_ntiles = pl.n;
+            h->pred_ntiles = pl.tiles.cap;
             return GPIMHIP_OK;
         }
     // tile list of the variance product W = L^-1 K*: 8x8 patches, longest k-ranges first
@@ -200,15 +147,15 @@ int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc) {
         for (int jg = 0; jg <= (nc - 1) / 8; ++jg)
             for (int ci = std::min(nb - 1, ig * 8 + 7); ci >= ig * 8; --ci)
                 for (int cj = jg * 8; cj < std::min(nc, jg * 8 + 8); ++cj) tl.push_back({ci, cj, 0, ci + 1});
-    gpimhip_ctx::PredList pl{nc, nullptr, (int64_t)tl.size()};
-    GP_TRY(dev_alloc(h, &pl.tiles, pl.n));
+    gpimhip_ctx::PredList pl{nc, {}};
+    GP_TRY(pl.tiles.alloc(h, (int64_t)tl.size()));
     // (async + stream sync rather than hipMemcpy: the latter serialises against the legacy stream and is
     // illegal while another thread captures a graph)
     HIP_TRY(hipMemcpyAsync(pl.tiles, tl.data(), tl.size() * sizeof(TileDesc), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->pred_lists.push_back(pl);
     h->pred_tiles = pl.tiles;
-    h->pred_ntiles = pl.n;
+    h->pred_ntiles = pl.tiles.cap;
     return GPIMHIP_OK;
 }
 
@@ -435,16 +382,8 @@ static BorderWs* bws(const gpimhip_ctx* h) { return (BorderWs*)h->border; }
 static bool border_on(const gpimhip_ctx* h) { return h->refl.mask && h->border && bws(h)->M > 0; }
 
 static void border_free_bufs(gpimhip_ctx* h, BorderWs* w) {
-    dev_free(h, &w->C, (int64_t)w->B * w->np * w->mp);
-    dev_free(h, &w->Y, (int64_t)w->B * w->np * w->mp);
-    dev_free(h, &w->tv, 2 * w->mp * w->T);
-    dev_free(h, &w->scal, 2 * w->T);
-    dev_free(h, &w->uo, w->uo_n);
-    dev_free(h, &w->tiles_y, w->n_y);
-    dev_free(h, &w->tiles_upd, w->n_upd);
-    dev_free(h, &w->R, w->mp * w->r_cols * w->T);
-    dev_free(h, &w->rsq, w->r_cols * w->T);
-    w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0; w->uo_n = 0;
+    dev_release(h, w->C, w->Y, w->tv, w->scal, w->uo, w->tiles_y, w->tiles_upd, w->R, w->rsq);
+    w->np = 0; w->B = 0; w->n_y = w->n_upd = 0; w->r_cols = 0;
 }
 static void border_release(gpimhip_ctx* h) {
     BorderWs* w = bws(h);
@@ -476,9 +415,9 @@ static int border_ensure(gpimhip_ctx* h, int T = 1) {
     w->n_y = (int)ty.size();
     w->n_upd = (int)tu.size();
     int rc = GPIMHIP_OK;
-    if ((rc = dev_alloc(h, &w->C, (int64_t)w->B * w->np * mp)) || (rc = dev_alloc(h, &w->Y, (int64_t)w->B * w->np * mp)) ||
-        (rc = dev_alloc(h, &w->tv, 2 * mp * T)) || (rc = dev_alloc(h, &w->scal, 2 * T)) || (rc = dev_alloc(h, &w->tiles_y, w->n_y)) ||
-        (rc = dev_alloc(h, &w->tiles_upd, w->n_upd))) {
+    if ((rc = w->C.alloc(h, (int64_t)w->B * w->np * mp)) || (rc = w->Y.alloc(h, (int64_t)w->B * w->np * mp)) ||
+        (rc = w->tv.alloc(h, 2 * mp * T)) || (rc = w->scal.alloc(h, 2 * T)) || (rc = w->tiles_y.alloc(h, w->n_y)) ||
+        (rc = w->tiles_upd.alloc(h, w->n_upd))) {
         border_free_bufs(h, w);
         return rc;
     }
@@ -491,12 +430,11 @@ static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
     BorderWs* w = bws(h);
     if (w->r_cols >= cols && w->R) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    dev_free(h, &w->R, w->mp * w->r_cols * w->T);
-    dev_free(h, &w->rsq, w->r_cols * w->T);
+    dev_release(h, w->R, w->rsq);
     w->r_cols = 0;
     int rc = GPIMHIP_OK;
-    if ((rc = dev_alloc(h, &w->R, w->mp * cols * w->T)) || (rc = dev_alloc(h, &w->rsq, cols * w->T))) {
-        dev_free(h, &w->R, w->mp * cols * w->T);
+    if ((rc = w->R.alloc(h, w->mp * cols * w->T)) || (rc = w->rsq.alloc(h, cols * w->T))) {
+        w->R.release(h);
         return rc;
     }
     w->r_cols = cols;
@@ -650,7 +588,7 @@ static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double
 
 // Fill the device table of Adam bias corrections (same libm pow() values for every path).
 int upload_bc_table(gpimhip_ctx* h, double lr, int T) {
-    GP_TRY(dev_grow(h, &h->bc, &h->bc_cap, 2 * (int64_t)T));
+    GP_TRY(h->bc.grow(h, 2 * (int64_t)T));
     h->bc_host.resize(2 * (size_t)T);
     for (int t = 1; t <= T; ++t) {
         h->bc_host[t - 1] = lr / (1.0 - pow(0.9, (double)t));
@@ -658,6 +596,17 @@ int upload_bc_table(gpimhip_ctx* h, double lr, int T) {
     }
     HIP_TRY(hipMemcpyAsync(h->bc, h->bc_host.data(), 2 * (size_t)T * sizeof(double), hipMemcpyHostToDevice,
                            h->stream));
+    return GPIMHIP_OK;
+}
+
+int fit_prologue(gpimhip_ctx* h, double lr, int T, double* adam_m, double* adam_v, size_t adam_bytes, int32_t* iter) {
+    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
+    h->fit_completed = T;
+    if (T == 0) return GPIMHIP_OK;
+    GP_TRY(upload_bc_table(h, lr, T));
+    HIP_TRY(hipMemsetAsync(adam_m, 0, adam_bytes, h->stream));
+    if (adam_v) HIP_TRY(hipMemsetAsync(adam_v, 0, adam_bytes, h->stream));
+    HIP_TRY(hipMemsetAsync(iter, 0, sizeof(int32_t), h->stream));
     return GPIMHIP_OK;
 }
 
@@ -795,7 +744,7 @@ int gpimhip_create(gpimhip_handle* out, int device, void* hip_stream) {
     h->device = device;
     h->stream = (hipStream_t)hip_stream;     // NULL = the device's default (null) stream
     int rc = GPIMHIP_OK;
-    if ((rc = dev_alloc(h, &h->theta1, 1)) || (rc = dev_alloc(h, &h->info, 4))) {
+    if ((rc = h->theta1.alloc(h, 1)) || (rc = h->info.alloc(h, 4))) {
         delete h;
         return rc;
     }
@@ -834,13 +783,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     sample_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
-    dev_free(h, &h->keys, h->keys_cap);
-    if (h->sel_scratch) dev_free(h, &h->sel_scratch, (int64_t)sel_scratch_bytes());
-    dev_free(h, &h->acq_tmp, h->acq_tmp_cap);
-    dev_free(h, &h->refine, h->refine_cap);
-    dev_free(h, &h->bc, h->bc_cap);
-    dev_free(h, &h->theta1, 1);
-    dev_free(h, &h->info, 4);
+    dev_release(h, h->keys, h->sel_scratch, h->acq_tmp, h->refine, h->bc, h->theta1, h->info);
     if (h->plan.d_tiles) (void)hipFree(h->plan.d_tiles);
     step_plan_release(h);
     dist_plan_release(h);
@@ -1167,14 +1110,7 @@ int gpimhip_acquire_exact(gpimhip_handle h, const gpimhip_model_t* m, const doub
     const double* inc = nullptr;
     if (kind != GPIMHIP_ACQ_CB) {
         // incumbent = nanmax of the posterior at the observed rows (EI: means; POI: means and sds), on device
-        if (h->acq_tmp_cap < 2 * Mobs + 2) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            dev_free(h, &h->acq_tmp, h->acq_tmp_cap);
-
-            h->acq_tmp_cap = 0;
-            GP_TRY(dev_alloc(h, &h->acq_tmp, 2 * Mobs + 2));
-            h->acq_tmp_cap = 2 * Mobs + 2;
-        }
+        GP_TRY(h->acq_tmp.grow(h, 2 * Mobs + 2));
         double *mo = h->acq_tmp, *so = h->acq_tmp + Mobs, *best = h->acq_tmp + 2 * Mobs;
         if (fused) {
             GP_TRY(launch_predict_fused(h, m, X, 0, N, Xobs, Mobs, mo, nullptr, so, nullptr, -1, 0.0, nullptr, 0.0, nullptr));
@@ -1203,7 +1139,7 @@ int gpimhip_acquire_exact(gpimhip_handle h, const gpimhip_model_t* m, const doub
 
 static int sel_scratch_ensure(gpimhip_ctx* h) {
     if (h->sel_scratch) return GPIMHIP_OK;
-    return dev_alloc(h, &h->sel_scratch, (int64_t)sel_scratch_bytes());
+    return h->sel_scratch.alloc(h, (int64_t)sel_scratch_bytes());
 }
 
 int gpimhip_nanmax(gpimhip_handle h, const double* x, int64_t n, double* out) {
@@ -1218,13 +1154,7 @@ int gpimhip_topk(gpimhip_handle h, const double* acq, int64_t M, int32_t k, int3
                  int64_t* idx_out, int64_t* count_out) {
     if (!h || !acq || !vals_out || !idx_out || !count_out || M < 1 || k < 1) return GPIMHIP_E_BADARG;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->keys_cap < M) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        dev_free(h, &h->keys, h->keys_cap);
-        h->keys_cap = 0;
-        GP_TRY(dev_alloc(h, &h->keys, M));
-        h->keys_cap = M;
-    }
+    GP_TRY(h->keys.grow(h, M));
     // large grids: multi-block radix selection (15 launches, O(M) each); small ones: k arg-max passes of one
     // workgroup (2 launches)
     if (M > 2048 && k <= 1024 && M < ((int64_t)1 << 32) && !getenv("GPIMHIP_NO_RADIX_TOPK")) {
@@ -1728,20 +1658,16 @@ int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat
 // engine, x_stride 0, whose per-problem theta comes from vgp_setup_kernel (vgp.hip)
 // ------------------------------------------------------------------------------------------
 struct VgpWs {
-    VgpDev* st = nullptr;
-    double* adam = nullptr;         // 2 x VGP_MAXP: Adam m, v
-    int32_t* iter = nullptr;
-    double* kb = nullptr; int64_t kb_cap = 0;        // T x np: K beta_t (reflection mode: T 2^r x np, K_b beta_{t,b})
-    double* pred = nullptr; int64_t pred_cap = 0;    // 2 x T x M: the blocks' mean and variance
+    DevBuf<VgpDev> st;
+    DevBuf<double> adam;            // 2 x VGP_MAXP: Adam m, v
+    DevBuf<int32_t> iter;
+    DevBuf<double> kb;              // T x np: K beta_t (reflection mode: T 2^r x np, K_b beta_{t,b})
+    DevBuf<double> pred;            // 2 x T x M: the blocks' mean and variance
 };
 static void vgp_release(gpimhip_ctx* h) {
     VgpWs* w = (VgpWs*)h->vgp;
     if (!w) return;
-    dev_free(h, &w->st, 1);
-    dev_free(h, &w->adam, 2 * VGP_MAXP);
-    dev_free(h, &w->iter, 1);
-    dev_free(h, &w->kb, w->kb_cap);
-    dev_free(h, &w->pred, w->pred_cap);
+    dev_release(h, w->st, w->adam, w->iter, w->kb, w->pred);
     delete w;
     h->vgp = nullptr;
 }
@@ -1750,13 +1676,13 @@ static int vgp_ws(gpimhip_ctx* h, int nprob, int T, int64_t M, VgpWs** out) {
     if (!w) {
         w = new VgpWs();
         h->vgp = w;
-        GP_TRY(dev_alloc(h, &w->st, 1));
-        GP_TRY(dev_alloc(h, &w->adam, 2 * VGP_MAXP));
-        GP_TRY(dev_alloc(h, &w->iter, 1));
+        GP_TRY(w->st.alloc(h, 1));
+        GP_TRY(w->adam.alloc(h, 2 * VGP_MAXP));
+        GP_TRY(w->iter.alloc(h, 1));
     }
     const int64_t kb = (int64_t)nprob * h->np, pr = 2 * (int64_t)T * M;
-    GP_TRY(dev_grow(h, &w->kb, &w->kb_cap, kb));
-    GP_TRY(dev_grow(h, &w->pred, &w->pred_cap, pr));
+    GP_TRY(w->kb.grow(h, kb));
+    GP_TRY(w->pred.grow(h, pr));
     *out = w;
     return GPIMHIP_OK;
 }
@@ -1822,7 +1748,7 @@ static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t
     GP_TRY(border_ensure(h, vg->tasks));
     BorderWs* b = bws(h);
     const int nrep = vgp_nrep(h);
-    GP_TRY(dev_grow(h, &b->uo, &b->uo_n, (int64_t)nrep * N));
+    GP_TRY(b->uo.grow(h, (int64_t)nrep * N));
     return launch_border_ones(h, b, N, nrep, b->uo);
 }
 
@@ -1844,12 +1770,8 @@ int gpimhip_fit_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vg
     if (!u_inout || T < 0) return GPIMHIP_E_BADARG;
     VgpWs* w = nullptr;
     GP_TRY(vgp_begin(h, vg, N, 0, &w));
-    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
-    h->fit_completed = T;
+    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * VGP_MAXP * sizeof(double), w->iter));
     if (T == 0) return finish_and_check(h);
-    GP_TRY(upload_bc_table(h, lr, T));
-    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * VGP_MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
     return run_fit_iterations(h, T, FIT_LOOP_DENSE,
                               [&] { return vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi); });
@@ -1895,38 +1817,26 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
 // ------------------------------------------------------------------------------------------
 struct PkronWs {
     KronAxes ax;                                        // the complete axes: K_i, E_i, Q_i, lambda_i, Mm_i, mdiag_i
-    ThetaDev* th3 = nullptr;                            // PK_TH_MODEL, PK_TH_AXES, PK_TH_UNIT
-    double* lamj = nullptr; int64_t lamj_cap = 0;       // J: lambda_j
-    double* yt = nullptr; int64_t yt_cap = 0;           // 2 x N_s J: the mode products of the projection
-    double* Ks = nullptr; int64_t ks_cap = 0;           // np x ld: K_s at variance 1
-    double* Bp = nullptr; int64_t bp_cap = 0;           // Jp x np: beta, zero on the padding (Jp = J padded to 128)
-    double* W = nullptr; int64_t w_cap = 0;             // Jp x np: K_s B
-    double* Z = nullptr; int64_t z_cap = 0;             // dc x J x np: W x_i Mm_i
-    double* bsum = nullptr; int64_t bsum_cap = 0;       // J x PK_SUMS
+    DevBuf<ThetaDev> th3;           // PK_TH_MODEL, PK_TH_AXES, PK_TH_UNIT
+    DevBuf<double> lamj;            // J: lambda_j
+    DevBuf<double> yt;              // 2 x N_s J: the mode products of the projection
+    DevBuf<double> Ks;              // np x ld: K_s at variance 1
+    DevBuf<double> Bp;              // Jp x np: beta, zero on the padding (Jp = J padded to 128)
+    DevBuf<double> W;               // Jp x np: K_s B
+    DevBuf<double> Z;               // dc x J x np: W x_i Mm_i
+    DevBuf<double> bsum;            // J x PK_SUMS
     // prediction (chunks of mc ragged test rows)
-    double* colpart = nullptr; int64_t colpart_cap = 0; // J x nb x mc
-    double* G = nullptr; int64_t g_cap = 0;             // Jp x mc: K*_s B
-    double* Q = nullptr; int64_t q_cap = 0;             // J x mc: k*^T M_j k*
-    double* pp = nullptr; int64_t pp_cap = 0;           // 4 x pmax x mc: the mode products of mean and variance
-    double* cross = nullptr; int64_t cross_cap = 0;     // 2 x sum m_i n_i: K*_i and K*_i Q_i
+    DevBuf<double> colpart;         // J x nb x mc
+    DevBuf<double> G;               // Jp x mc: K*_s B
+    DevBuf<double> Q;               // J x mc: k*^T M_j k*
+    DevBuf<double> pp;              // 4 x pmax x mc: the mode products of mean and variance
+    DevBuf<double> cross;           // 2 x sum m_i n_i: K*_i and K*_i Q_i
 };
 static void pkron_release(gpimhip_ctx* h) {
     PkronWs* w = (PkronWs*)h->pkron;
     if (!w) return;
     kron_axes_free(h, w->ax);
-    dev_free(h, &w->th3, 3);
-    dev_free(h, &w->lamj, w->lamj_cap);
-    dev_free(h, &w->yt, w->yt_cap);
-    dev_free(h, &w->Ks, w->ks_cap);
-    dev_free(h, &w->Bp, w->bp_cap);
-    dev_free(h, &w->W, w->w_cap);
-    dev_free(h, &w->Z, w->z_cap);
-    dev_free(h, &w->bsum, w->bsum_cap);
-    dev_free(h, &w->colpart, w->colpart_cap);
-    dev_free(h, &w->G, w->g_cap);
-    dev_free(h, &w->Q, w->q_cap);
-    dev_free(h, &w->pp, w->pp_cap);
-    dev_free(h, &w->cross, w->cross_cap);
+    dev_release(h, w->th3, w->lamj, w->yt, w->Ks, w->Bp, w->W, w->Z, w->bsum, w->colpart, w->G, w->Q, w->pp, w->cross);
     delete w;
     h->pkron = nullptr;
 }
@@ -1970,16 +1880,16 @@ static int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, c
     if (!w) {
         w = new PkronWs();
         h->pkron = w;
-        GP_TRY(dev_alloc(h, &w->th3, 3));
+        GP_TRY(w->th3.alloc(h, 3));
     }
     const int64_t np = h->np, J = mp.J, Jp = pad_to(J, NB);
-    GP_TRY(dev_grow(h, &w->lamj, &w->lamj_cap, J));
-    GP_TRY(dev_grow(h, &w->yt, &w->yt_cap, 2 * Ns * J));
-    GP_TRY(dev_grow(h, &w->Ks, &w->ks_cap, np * h->ld));
-    GP_TRY(dev_grow(h, &w->Bp, &w->bp_cap, Jp * np));
-    GP_TRY(dev_grow(h, &w->W, &w->w_cap, Jp * np));
-    GP_TRY(dev_grow(h, &w->Z, &w->z_cap, (int64_t)mp.dc * J * np));
-    GP_TRY(dev_grow(h, &w->bsum, &w->bsum_cap, J * PK_SUMS));
+    GP_TRY(w->lamj.grow(h, J));
+    GP_TRY(w->yt.grow(h, 2 * Ns * J));
+    GP_TRY(w->Ks.grow(h, np * h->ld));
+    GP_TRY(w->Bp.grow(h, Jp * np));
+    GP_TRY(w->W.grow(h, Jp * np));
+    GP_TRY(w->Z.grow(h, (int64_t)mp.dc * J * np));
+    GP_TRY(w->bsum.grow(h, J * PK_SUMS));
     // the rows of the padding of B (a buffer that served a larger J may hold an earlier beta there)
     if (Jp > J) HIP_TRY(hipMemsetAsync(w->Bp + J * np, 0, (size_t)((Jp - J) * np) * sizeof(double), h->stream));
     GP_TRY(kron_axes_ensure(h, w->ax, mp.dc, n_c, true));
@@ -2017,11 +1927,8 @@ static int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, cons
     g.kfix0 = 0;
     g.kfix1 = (int)(np / NB);
     g.chunk = deal_chunk(g.ntiles);
-    const int nbatch = h->nbatch;
-    h->nbatch = 1;
-    const int rc = launch_gemm(h, false, true, EPI_STORE, g);
-    h->nbatch = nbatch;
-    return rc;
+    BatchScope one(h, 1);
+    return launch_gemm(h, false, true, EPI_STORE, g);
 }
 // theta, the complete axes' decomposition, the blocks' theta, y~ = Y Q in the padded right-hand sides, and the blocks'
 // K, L, L^-1, z, beta (steps 1 - 4 of an iteration without the inverse)
@@ -2050,10 +1957,10 @@ static int pkron_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& 
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(Ns, np))); }
     GP_TRY(launch_grad_reduce(h, &ms, h->B, h->ld, Xs, Ns, (int)(np / NB), h->alpha, 0));
     // W = K_s B: K_s once at variance 1, then one product on the tile engine (rows of W: the blocks)
-    h->nbatch = 1;
-    int rc = launch_kmat(h, &ms, Xs, Ns, nullptr, Ns, w->th3 + PK_TH_UNIT, 0.0, 0, w->Ks, h->ld, np, np, 1, 0, 0, 0, 0);
-    h->nbatch = J;
-    GP_TRY(rc);
+    {
+        BatchScope one(h, 1);
+        GP_TRY(launch_kmat(h, &ms, Xs, Ns, nullptr, Ns, w->th3 + PK_TH_UNIT, 0.0, 0, w->Ks, h->ld, np, np, 1, 0, 0, 0, 0));
+    }
     GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
     GP_TRY(pkron_times_b(h, w, J, w->Ks, h->ld, np, w->W, np));
     // Z_i = W x_i Mm_i: the mode product along complete axis i of the (n_1, ..., n_dc, np) tensor W
@@ -2091,13 +1998,8 @@ int gpimhip_fit_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* 
     if (!u_inout || T < 0) return GPIMHIP_E_BADARG;
     PkronWs* w = nullptr;
     GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
-    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
-    h->fit_completed = T;
+    GP_TRY(fit_prologue(h, lr, T, h->adam_m, h->adam_v, MAXP * sizeof(double), h->iter));
     if (T == 0) return finish_and_check(h);
-    GP_TRY(upload_bc_table(h, lr, T));
-    HIP_TRY(hipMemsetAsync(h->adam_m, 0, MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->adam_v, 0, MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter fi{h->iter, h->bc, T, hist_out, loss_out};
     return run_fit_iterations(h, T, FIT_LOOP_DENSE,
                               [&] { return pkron_iter(h, m, mp, w, Xs, Y, Ns, u_inout, 1, nullptr, nullptr, fi); });
@@ -2130,16 +2032,16 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
     const gpimhip_model_t ms = pkron_submodel(m, p);
     // chunks of ragged test rows: the blocks' partial column sums (J x nb x mc doubles) stay <= ~0.5 GiB
     const int64_t mc = std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
-    h->nbatch = 1;              // ONE K* slab, shared by the J blocks
-    int rc = ws_ensure_predict(h, np, mc);
-    h->nbatch = J;
-    GP_TRY(rc);
+    {
+        BatchScope one(h, 1);       // ONE K* slab, shared by the J blocks
+        GP_TRY(ws_ensure_predict(h, np, mc));
+    }
     const int64_t kld = h->ks_cols + 16;
-    GP_TRY(dev_grow(h, &w->colpart, &w->colpart_cap, (int64_t)J * nb * mc));
-    GP_TRY(dev_grow(h, &w->G, &w->g_cap, Jp * mc));
-    GP_TRY(dev_grow(h, &w->Q, &w->q_cap, (int64_t)J * mc));
-    GP_TRY(dev_grow(h, &w->pp, &w->pp_cap, 4 * pmax * mc));
-    GP_TRY(dev_grow(h, &w->cross, &w->cross_cap, 2 * sum_mn));
+    GP_TRY(w->colpart.grow(h, (int64_t)J * nb * mc));
+    GP_TRY(w->G.grow(h, Jp * mc));
+    GP_TRY(w->Q.grow(h, (int64_t)J * mc));
+    GP_TRY(w->pp.grow(h, 4 * pmax * mc));
+    GP_TRY(w->cross.grow(h, 2 * sum_mn));
     GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, false));
     GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
     // per complete axis: K*_i and b_i = K*_i Q_i (eigen-coordinates straight to test points)
@@ -2159,10 +2061,10 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
     }
     for (int64_t m0 = 0; m0 < Ms; m0 += mc) {
         const int64_t cnt = std::min(mc, Ms - m0), cpad = pad_to(cnt, NB);
-        h->nbatch = 1;
-        rc = launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0);
-        h->nbatch = J;
-        GP_TRY(rc);
+        {
+            BatchScope one(h, 1);
+            GP_TRY(launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0));
+        }
         // G = B K*_s (Jp x cpad): the blocks' means before the mix
         GP_TRY(pkron_times_b(h, w, J, h->Ks, kld, cpad, w->G, mc));
         // q_j = |L_j^-1 k*|^2 from the raw column sums of the batched variance product (K* at variance 1, shared: stride 0)
@@ -2204,24 +2106,18 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
 // the finalize step of sm.hip.  Parameters, Adam state and history live here: P = 2 + Q (2 D + 1) exceeds GPIMHIP_MAX_PARAMS.
 // ------------------------------------------------------------------------------------------
 struct SmWs {
-    SmDev* st = nullptr;
-    double* adam = nullptr;                            // 2 x SM_MAXP: Adam m, v
-    int32_t* iter = nullptr;
-    double* sums = nullptr;                            // SM_MAXP: the gradient records added up over the tiles
-    double* csx = nullptr; int64_t csx_cap = 0;        // 2 Q dim x np: phases of the training points
-    double* csz = nullptr; int64_t csz_cap = 0;        // 2 Q dim x (test chunk): phases of the test points
-    double* part = nullptr; int64_t part_cap = 0;      // records x lower tiles
+    DevBuf<SmDev> st;
+    DevBuf<double> adam;            // 2 x SM_MAXP: Adam m, v
+    DevBuf<int32_t> iter;
+    DevBuf<double> sums;            // SM_MAXP: the gradient records added up over the tiles
+    DevBuf<double> csx;             // 2 Q dim x np: phases of the training points
+    DevBuf<double> csz;             // 2 Q dim x (test chunk): phases of the test points
+    DevBuf<double> part;            // records x lower tiles
 };
 static void sm_release(gpimhip_ctx* h) {
     SmWs* w = (SmWs*)h->sm;
     if (!w) return;
-    dev_free(h, &w->st, 1);
-    dev_free(h, &w->adam, 2 * SM_MAXP);
-    dev_free(h, &w->iter, 1);
-    dev_free(h, &w->sums, SM_MAXP);
-    dev_free(h, &w->csx, w->csx_cap);
-    dev_free(h, &w->csz, w->csz_cap);
-    dev_free(h, &w->part, w->part_cap);
+    dev_release(h, w->st, w->adam, w->iter, w->sums, w->csx, w->csz, w->part);
     delete w;
     h->sm = nullptr;
 }
@@ -2230,10 +2126,10 @@ static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t m
     SmWs* w = (SmWs*)h->sm;
     if (!w) {       // the fixed buffers first; the workspace is published only once all of them exist
         w = new SmWs();
-        int rc = dev_alloc(h, &w->st, 1);
-        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->adam, 2 * SM_MAXP);
-        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->iter, 1);
-        if (rc == GPIMHIP_OK) rc = dev_alloc(h, &w->sums, SM_MAXP);
+        int rc = w->st.alloc(h, 1);
+        if (rc == GPIMHIP_OK) rc = w->adam.alloc(h, 2 * SM_MAXP);
+        if (rc == GPIMHIP_OK) rc = w->iter.alloc(h, 1);
+        if (rc == GPIMHIP_OK) rc = w->sums.alloc(h, SM_MAXP);
         h->sm = w;
         if (rc != GPIMHIP_OK) {
             sm_release(h);
@@ -2241,9 +2137,9 @@ static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t m
         }
     }
     const int64_t per = 2 * (int64_t)sm->mixtures * sm->dim;
-    GP_TRY(dev_grow(h, &w->csx, &w->csx_cap, per * np_x));
-    GP_TRY(dev_grow(h, &w->csz, &w->csz_cap, per * mz));
-    GP_TRY(dev_grow(h, &w->part, &w->part_cap, (int64_t)sm_layout(*sm).P * ntile));
+    GP_TRY(w->csx.grow(h, per * np_x));
+    GP_TRY(w->csz.grow(h, per * mz));
+    GP_TRY(w->part.grow(h, (int64_t)sm_layout(*sm).P * ntile));
     *out = w;
     return GPIMHIP_OK;
 }
@@ -2399,8 +2295,9 @@ int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, i
     const int64_t Mv = sym ? N : M;
     if (!u || !out || Mv < 1 || ld < Mv) return GPIMHIP_E_BADARG;
     HIP_TRY(hipSetDevice(h->device));
+    h->nbatch = 1;
     if (B) {       // reflection mode: the B blocks K_s (or K_s(X, Z) / sqrt(B)) stacked, B N rows
-        h->nbatch = B;
+        BatchScope batch(h, B);
         const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
         SmWs* w = nullptr;
         GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
@@ -2414,10 +2311,8 @@ int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, i
             HIP_TRY(hipMemcpy2DAsync(out + (int64_t)b * N * ld, (size_t)ld * sizeof(double), h->Ks + (int64_t)b * rp * kld,
                                      (size_t)kld * sizeof(double), (size_t)Mv * sizeof(double), (size_t)N,
                                      hipMemcpyDeviceToDevice, h->stream));
-        h->nbatch = 1;
         return GPIMHIP_OK;
     }
-    h->nbatch = 1;
     const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
     SmWs* w = nullptr;
     GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
@@ -2448,12 +2343,8 @@ int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, co
     if (!y || !u_inout || T < 0) return GPIMHIP_E_BADARG;
     SmWs* w = nullptr;
     GP_TRY(sm_begin(h, sm, N, &w));
-    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
-    h->fit_completed = T;
+    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * SM_MAXP * sizeof(double), w->iter));
     if (T == 0) return finish_and_check(h);
-    GP_TRY(upload_bc_table(h, lr, T));
-    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * SM_MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
     return run_fit_iterations(h, T, FIT_LOOP_DENSE, [&] { return sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi); });
 }
@@ -2477,12 +2368,8 @@ int gpimhip_fit_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const doubl
     if (!ys || !ones || !u_inout || T < 0) return GPIMHIP_E_BADARG;
     SmWs* w = nullptr;
     GP_TRY(sm_begin_refl(h, sm, N, B, &w));
-    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));   // "completed" = huge until a failure
-    h->fit_completed = T;
+    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * SM_MAXP * sizeof(double), w->iter));
     if (T == 0) return finish_and_check(h);
-    GP_TRY(upload_bc_table(h, lr, T));
-    HIP_TRY(hipMemsetAsync(w->adam, 0, 2 * SM_MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(w->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
     return run_fit_iterations(h, T, FIT_LOOP_DENSE,
                               [&] { return sm_iter_refl(h, sm, w, X, ys, ones, N, u_inout, 1, nullptr, nullptr, fi); });
@@ -2554,27 +2441,27 @@ int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X
 // ------------------------------------------------------------------------------------------
 struct SampleWs {
     gpimhip_ctx* sub = nullptr;
-    double* J = nullptr; int64_t j_cap = 0;         // padded (N + M)^2 joint covariance -> its factor
-    double* XX = nullptr; int64_t xx_cap = 0;       // [X; Xs]
-    double* vec = nullptr; int64_t vec_cap = 0;     // t (order) | piece (512) | mean (M): forward substitution, draws
+    DevBuf<double> J;               // padded (N + M)^2 joint covariance -> its factor
+    DevBuf<double> XX;              // [X; Xs]
+    DevBuf<double> vec;             // t (order) | piece (512) | mean (M): forward substitution, draws
     // pathwise draws (sample_pathwise_impl): a context per matrix order (a call factors at both, and a context that changes
     // its order rebuilds its launch plan), one block of the prior, the training matrix, the vectors
     gpimhip_ctx* subp = nullptr;                    // order M / 2^r: the reflection blocks of the grid, one after the other
     gpimhip_ctx* subt = nullptr;                    // order N: K + (noise + jitter) I
-    double* Pb = nullptr; int64_t pb_cap = 0;
-    double* Kt = nullptr; int64_t kt_cap = 0;
-    double* pw = nullptr; int64_t pw_cap = 0;
+    DevBuf<double> Pb;
+    DevBuf<double> Kt;
+    DevBuf<double> pw;
     // multi-output draws (sample_vgp_impl / sample_vgp_blocks_impl): the state of the reduction, the T
     // latent blocks' thetas, their targets z_t (T x N), draws H (T x S x M) and moments (2 x T x M: mean, variance)
-    VgpDev* vst = nullptr;
-    ThetaDev* vth = nullptr;
-    double* vz = nullptr; int64_t vz_cap = 0;
-    double* vH = nullptr; int64_t vh_cap = 0;
-    double* vmom = nullptr; int64_t vmom_cap = 0;
+    DevBuf<VgpDev> vst;
+    DevBuf<ThetaDev> vth;
+    DevBuf<double> vz;
+    DevBuf<double> vH;
+    DevBuf<double> vmom;
     // draws of the dense-by-Kronecker blocks (gpimhip_sample_pkron): one arena carved per call (the
     // prior factor, zeta and H, the mode products' buffers, the blocks' right-hand sides, the stacked solutions, root rows,
     // index maps, tile lists) and the union of the complete axes when the training axes do not serve; `sub` factors L_P
-    double* ck = nullptr; int64_t ck_cap = 0;
+    DevBuf<double> ck;
     KronAxes ck_un;
 };
 static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
@@ -2586,18 +2473,7 @@ static int64_t sample_bytes(const gpimhip_ctx* h) {
 static void sample_release(gpimhip_ctx* h) {
     SampleWs* w = sws(h);
     if (!w) return;
-    dev_free(h, &w->J, w->j_cap);
-    dev_free(h, &w->XX, w->xx_cap);
-    dev_free(h, &w->vec, w->vec_cap);
-    dev_free(h, &w->Pb, w->pb_cap);
-    dev_free(h, &w->Kt, w->kt_cap);
-    dev_free(h, &w->pw, w->pw_cap);
-    dev_free(h, &w->vst, 1);
-    dev_free(h, &w->vth, VGP_MAXT);
-    dev_free(h, &w->vz, w->vz_cap);
-    dev_free(h, &w->vH, w->vh_cap);
-    dev_free(h, &w->vmom, w->vmom_cap);
-    dev_free(h, &w->ck, w->ck_cap);
+    dev_release(h, w->J, w->XX, w->vec, w->Pb, w->Kt, w->pw, w->vst, w->vth, w->vz, w->vH, w->vmom, w->ck);
     kron_axes_free(h, w->ck_un);
     if (w->sub) gpimhip_destroy(w->sub);
     if (w->subp) gpimhip_destroy(w->subp);
@@ -2642,9 +2518,9 @@ static int sample_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, const double
     const int64_t NM = N + M, d = m->dim;
     GP_TRY(ws_ensure_b(sub, NM, 1, 1, false));
     const int64_t np = sub->np, ld = sub->ld;
-    GP_TRY(dev_grow(h, &w->J, &w->j_cap, np * ld));
-    GP_TRY(dev_grow(h, &w->XX, &w->xx_cap, np * GPIMHIP_MAX_DIM));
-    GP_TRY(dev_grow(h, &w->vec, &w->vec_cap, 2 * np + 4 * NB));
+    GP_TRY(w->J.grow(h, np * ld));
+    GP_TRY(w->XX.grow(h, np * GPIMHIP_MAX_DIM));
+    GP_TRY(w->vec.grow(h, 2 * np + 4 * NB));
     double *t = w->vec, *piece = t + np, *mean_ws = piece + 4 * NB;
     if (reset_info) HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
     HIP_TRY(hipMemcpyAsync(w->XX, X, (size_t)(N * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -2731,14 +2607,14 @@ static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid
     gpimhip_ctx *sp = w->subp, *st = w->subt;
     const int64_t npq = sp->np, ldq = sp->ld, npt = st->np, ldt = st->ld;
     const int64_t zw = M + N + (noiseless ? 0 : M), SB = (int64_t)S * B;
-    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
-    GP_TRY(dev_grow(h, &w->Kt, &w->kt_cap, npt * ldt));
+    GP_TRY(w->Pb.grow(h, npq * ldq));
+    GP_TRY(w->Kt.grow(h, npt * ldt));
     auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
     const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
                   o_g = o_c + even(SB * Nq), o_xt = o_g + even((int64_t)S * M), o_r = o_xt + npt * GPIMHIP_MAX_DIM,
                   o_al = o_r + (S + 1) * npt, o_zf = o_al + (S + 1) * npt, o_t = o_zf + npt, o_piece = o_t + npt,
                   o_work = o_piece + 4 * NB, o_mws = o_work + 4 * NB, o_end = o_mws + npq;
-    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    GP_TRY(w->pw.grow(h, o_end));
     double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *Xt = w->pw + o_xt,
            *R = w->pw + o_r, *Al = w->pw + o_al, *zf = w->pw + o_zf, *t = w->pw + o_t, *piece = w->pw + o_piece,
            *work = w->pw + o_work, *mean_ws = w->pw + o_mws;
@@ -2848,13 +2724,13 @@ static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGri
     gpimhip_ctx* sp = w->subp;
     const int64_t npq = sp->np, ldq = sp->ld;
     const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
-    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
+    GP_TRY(w->Pb.grow(h, npq * ldq));
     auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
     const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
                   o_e = o_c + even(SB * Nq), o_cc = o_e + B * S1 * npq, o_g = o_cc + even(B * S1 * Nq), o_r = o_g + even(S1 * M),
                   o_zf = o_r + S1 * npq, o_al = o_zf + S1 * npq, o_t = o_al + S1 * npq,
                   o_part = o_t + 8 * npq, o_mws = o_part + (int64_t)gemv_t_multi_chunks(npq) * 8 * 4 * NB, o_end = o_mws + npq;
-    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    GP_TRY(w->pw.grow(h, o_end));
     double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *E = w->pw + o_e, *Cc = w->pw + o_cc,
            *g = w->pw + o_g, *R = w->pw + o_r, *Zf = w->pw + o_zf, *Al = w->pw + o_al, *t = w->pw + o_t, *part = w->pw + o_part,
            *mean_ws = w->pw + o_mws;
@@ -2939,11 +2815,11 @@ static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid g
 static int sample_vgp_ws(gpimhip_ctx* h, int T, int64_t N, int64_t M, int S, SampleWs** out) {
     if (!h->sample) h->sample = new SampleWs();
     SampleWs* w = sws(h);
-    if (!w->vst) GP_TRY(dev_alloc(h, &w->vst, 1));
-    if (!w->vth) GP_TRY(dev_alloc(h, &w->vth, VGP_MAXT));
-    GP_TRY(dev_grow(h, &w->vz, &w->vz_cap, (int64_t)T * N));
-    GP_TRY(dev_grow(h, &w->vH, &w->vh_cap, (int64_t)T * S * M));
-    GP_TRY(dev_grow(h, &w->vmom, &w->vmom_cap, 2 * (int64_t)T * M));
+    if (!w->vst) GP_TRY(w->vst.alloc(h, 1));
+    if (!w->vth) GP_TRY(w->vth.alloc(h, VGP_MAXT));
+    GP_TRY(w->vz.grow(h, (int64_t)T * N));
+    GP_TRY(w->vH.grow(h, (int64_t)T * S * M));
+    GP_TRY(w->vmom.grow(h, 2 * (int64_t)T * M));
     *out = w;
     return GPIMHIP_OK;
 }
@@ -3019,7 +2895,7 @@ static int sample_border_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const do
     const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
     const int Mm = bws(h)->M;
     const int64_t mp = pad_to(Mm, NB);
-    GP_TRY(dev_grow(h, &w->Pb, &w->pb_cap, npq * ldq));
+    GP_TRY(w->Pb.grow(h, npq * ldq));
     auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
     const int pg = sample_draw_group(S + 1);           // the first group of columns is the largest
     const int64_t n_part = std::max((int64_t)B * tri_bwd_chunks(npq) * pg * npq, (int64_t)tri_bwd_chunks(mp) * pg * mp);
@@ -3027,7 +2903,7 @@ static int sample_border_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const do
                   o_g = o_c + even(SB * Nq), o_mws = o_g + even((int64_t)S * M), o_r = o_mws + npq, o_zf = o_r + B * S1 * npq,
                   o_cc = o_zf + B * S1 * npq, o_g2 = o_cc + even(B * S1 * Nq), o_tv = o_g2 + even(S1 * M), o_part = o_tv + 3 * S1 * mp,
                   o_mi = o_part + n_part, o_end = o_mi + even(M) / 2;
-    GP_TRY(dev_grow(h, &w->pw, &w->pw_cap, o_end));
+    GP_TRY(w->pw.grow(h, o_end));
     double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *mean_ws = w->pw + o_mws,
            *R = w->pw + o_r, *Zf = w->pw + o_zf, *Cc = w->pw + o_cc, *g2 = w->pw + o_g2, *tv = w->pw + o_tv, *vv = tv + S1 * mp,
            *wv = vv + S1 * mp, *part = w->pw + o_part;
@@ -3347,14 +3223,14 @@ int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doubl
     const int rag = rag_of(Ns, np);
     // the chunks of ragged test rows and the mean's buffers are gpimhip_predict_pkron's
     const int64_t mc = std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
-    h->nbatch = 1;
-    int rc = ws_ensure_predict(h, np, mc);
-    h->nbatch = J;
-    GP_TRY(rc);
+    {
+        BatchScope one(h, 1);
+        GP_TRY(ws_ensure_predict(h, np, mc));
+    }
     const int64_t kld = h->ks_cols + 16;
-    GP_TRY(dev_grow(h, &w->G, &w->g_cap, Jp * mc));
-    GP_TRY(dev_grow(h, &w->pp, &w->pp_cap, 4 * pmax * mc));
-    GP_TRY(dev_grow(h, &w->cross, &w->cross_cap, 2 * sum_mn));
+    GP_TRY(w->G.grow(h, Jp * mc));
+    GP_TRY(w->pp.grow(h, 4 * pmax * mc));
+    GP_TRY(w->cross.grow(h, 2 * sum_mn));
     if (!h->sample) h->sample = new SampleWs();
     SampleWs* sw = sws(h);
     GP_TRY(pathwise_sub(h, &sw->sub, Us));
@@ -3392,7 +3268,7 @@ int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doubl
     const int64_t th_d = (int64_t)((sizeof(ThetaDev) + 15) / 16 * 2);
     const int64_t total = th_d + npU * ldU + 2 * npU * cols + 3 * Sg0 * big + 2 * J * np * Sp + rowsP * np + rowsP * mc +
                           2 * Sg0 * pmax * mc + sum_nu + sum_mu + (Ns + Ms + sum_n + sum_m) / 2 + 2 * (int64_t)tl.size() + 64;
-    GP_TRY(dev_grow(h, &sw->ck, &sw->ck_cap, total));
+    GP_TRY(sw->ck.grow(h, total));
     double* ap = sw->ck;
     auto take = [&](int64_t c) { double* r = ap; ap += (c + 1) / 2 * 2; return r; };    // keeps 16-byte alignment
     ThetaDev* thp = (ThetaDev*)take(th_d);
@@ -3503,10 +3379,10 @@ int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doubl
             const double* upd;
             {
                 StageTimer t(h, 3);
-                h->nbatch = 1;
-                rc = launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0);
-                h->nbatch = J;
-                GP_TRY(rc);
+                {
+                    BatchScope one(h, 1);
+                    GP_TRY(launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0));
+                }
                 if (s0 == 0) {      // the mean: the launches of gpimhip_predict_pkron's
                     GP_TRY(pkron_times_b(h, w, J, h->Ks, kld, cpad, w->G, mc));
                     const double* cur = w->G;

@@ -13,18 +13,17 @@ struct BorderWs {
     int B = 0;                      // the batch: 2^r blocks, times T tasks for the multi-output GP (task-major)
     int T = 1;                      // borders handled in lock-step: one S_t per task of the multi-output GP (vgp.hip), else 1;
                                     // sub's batch.  Per-task buffers below are stacked, task t at t times their size
-    double* C = nullptr;            // B x np x mp   C_b[:, j] = c_b(j) B_b^-1[:, q(j)]
-    double* Y = nullptr;            // B x np x mp   Y_b = C_b L_S^-T
-    double* tv = nullptr;           // T x 2 x mp: t = (A^-1 y~)_m, v = L_S^-1 t
-    double* scal = nullptr;         // T x 2: |v|^2, sum log (L_S)_ii
-    double* uo = nullptr;           // 2^r x N (multi-output GP only): U 1_o, the observed points' indicator in the adapted basis
-    int64_t uo_n = 0;
-    TileDesc* tiles_y = nullptr;    // Y = C L_S^-T: (np / 128) x (mp / 128) tiles, k-range [0, cj]
+    DevBuf<double> C;               // B x np x mp   C_b[:, j] = c_b(j) B_b^-1[:, q(j)]
+    DevBuf<double> Y;               // B x np x mp   Y_b = C_b L_S^-T
+    DevBuf<double> tv;              // T x 2 x mp: t = (A^-1 y~)_m, v = L_S^-1 t
+    DevBuf<double> scal;            // T x 2: |v|^2, sum log (L_S)_ii
+    DevBuf<double> uo;              // 2^r x N (multi-output GP only): U 1_o, the observed points' indicator in the adapted basis
+    DevBuf<TileDesc> tiles_y;       // Y = C L_S^-T: (np / 128) x (mp / 128) tiles, k-range [0, cj]
     int n_y = 0;
-    TileDesc* tiles_upd = nullptr;  // B_b^-1 -= Y_b Y_b^T: the lower tiles of the block
+    DevBuf<TileDesc> tiles_upd;     // B_b^-1 -= Y_b Y_b^T: the lower tiles of the block
     int n_upd = 0;
-    double* R = nullptr;            // T x mp x r_cols: R = sum_b Y_b^T K*_b for one test chunk
-    double* rsq = nullptr;          // T x r_cols: column sums of squares of R
+    DevBuf<double> R;               // T x mp x r_cols: R = sum_b Y_b^T K*_b for one test chunk
+    DevBuf<double> rsq;             // T x r_cols: column sums of squares of R
     int64_t r_cols = 0;
 };
 

@@ -169,7 +169,7 @@ int launch_potrf_steps_f32(gpimhip_ctx* h, double* A_, int64_t np, int64_t ld, i
     GP_TRY(step_plan_ensure(h, nb));
     const StepPlan& P = h->splan;
     float* A = reinterpret_cast<float*>(A_);
-    float* const dinv = reinterpret_cast<float*>(h->dinv);
+    float* const dinv = reinterpret_cast<float*>(h->dinv.p);
     double* const Ad = reinterpret_cast<double*>(A);
     const int B = h->nbatch;
     const int quad_max = 128, half_max = 512, host_max_batch = 4;

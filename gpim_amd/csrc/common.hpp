@@ -29,6 +29,20 @@ void gpim_set_error(const std::string& s);
         if (_r != GPIMHIP_OK) return _r;  \
     } while (0)
 
+// A device buffer that knows its own size: cap elements, charged to h->bytes by alloc / grow and credited by release (the
+// members are defined below gpimhip_ctx).  Reads as a plain pointer wherever one is expected.
+struct gpimhip_ctx;
+template <typename T> struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;                          // elements allocated (what h->bytes was charged for)
+    // exactly count elements into an empty buffer; what: the error text of a failed hipMalloc (default: HIP's own)
+    int alloc(gpimhip_ctx* h, int64_t count, const char* what = nullptr);
+    // grow-only, to exactly want elements.  The stream is synchronised before the free: earlier launches may still read the buffer.
+    int grow(gpimhip_ctx* h, int64_t want);
+    void release(gpimhip_ctx* h);
+    operator T*() const { return p; }
+};
+
 // One output tile of a blocked GEMM-like launch: C[ci,cj] (op)= sum_{kb in [kb0,kb1)} A(ci,kb) B(kb,cj)
 struct TileDesc {
     int32_t ci, cj, kb0, kb1;
@@ -148,33 +162,33 @@ struct gpimhip_ctx {
     int64_t ld = 0;                 // leading dimension (doubles) of A, B, Tm: np, or np + 16 (see ws_ensure_b)
     int nbatch = 1;                 // problems processed in lock-step by the current call (grid.y)
     int ws_batch = 0;               // number of problems the workspace is sized for
-    double* A = nullptr;            // np x np : K -> L -> L^-1
-    double* B = nullptr;            // np x np : K^-1 (lower)
-    double* Tm = nullptr;           // np x np : trtri temporary
-    double* dinv = nullptr;         // nb x 128 x 128 inverses of diagonal blocks
-    double* dinvB = nullptr;        // the same in MFMA B-operand order (panel solve of cholstep.hip); fp64 handles
-    double* pcopy = nullptr;        // B x 128 x 128: A[j+1, j] as the step launch of column j left it (cholstep.hip: panel_solve_diag_kernel)
-    double* ypad = nullptr;         // np
-    double* z = nullptr;            // np  (L^-1 y)
-    double* alpha = nullptr;        // np  (K^-1 y)
-    double* logdet_part = nullptr;  // nb
-    double* grad_part = nullptr;    // ntiles_lower x 8
-    double* gemv_part = nullptr;    // gemv_tri_chunks(np) x np: row-chunk partial sums of alpha = L^-T z (engine.hip: gemv_t_tri_kernel)
-    uint32_t* fin_counter = nullptr;   // per problem: workgroups of grad_reduce_kernel that have finished (engine.hip: FinFused; the last
+    DevBuf<double> A;               // np x np : K -> L -> L^-1
+    DevBuf<double> B;               // np x np : K^-1 (lower)
+    DevBuf<double> Tm;              // np x np : trtri temporary
+    DevBuf<double> dinv;            // nb x 128 x 128 inverses of diagonal blocks
+    DevBuf<double> dinvB;           // the same in MFMA B-operand order (panel solve of cholstep.hip); fp64 handles
+    DevBuf<double> pcopy;           // B x 128 x 128: A[j+1, j] as the step launch of column j left it (cholstep.hip: panel_solve_diag_kernel)
+    DevBuf<double> ypad;            // np
+    DevBuf<double> z;               // np  (L^-1 y)
+    DevBuf<double> alpha;           // np  (K^-1 y)
+    DevBuf<double> logdet_part;     // nb
+    DevBuf<double> grad_part;       // ntiles_lower x 8
+    DevBuf<double> gemv_part;       // gemv_tri_chunks(np) x np: row-chunk partial sums of alpha = L^-T z (engine.hip: gemv_t_tri_kernel)
+    DevBuf<uint32_t> fin_counter;      // per problem: workgroups of grad_reduce_kernel that have finished (engine.hip: FinFused; the last
                                        // one runs the finalize step and resets it)
-    ThetaDev* theta = nullptr;      // [ws_batch]
-    ThetaDev* theta1 = nullptr;     // single struct for the operator-level gpimhip_kmat
-    int32_t* iter = nullptr;        // [ws_batch] device-side iteration counters
-    double* adam_m = nullptr;       // MAXP
-    double* adam_v = nullptr;       // MAXP
-    int32_t* info = nullptr;        // potrf status word
+    DevBuf<ThetaDev> theta;         // [ws_batch]
+    DevBuf<ThetaDev> theta1;        // single struct for the operator-level gpimhip_kmat
+    DevBuf<int32_t> iter;           // [ws_batch] device-side iteration counters
+    DevBuf<double> adam_m;          // MAXP
+    DevBuf<double> adam_v;          // MAXP
+    DevBuf<int32_t> info;           // potrf status word
     // prediction workspace
     int64_t ks_rows = 0, ks_cols = 0, ks_batch = 0;   // ks_cols = CAPACITY in test-point columns (grow-only)
-    struct PredList { int nc; TileDesc* tiles; int64_t n; };
+    struct PredList { int nc; DevBuf<TileDesc> tiles; };
     std::vector<PredList> pred_lists;                // variance-product tile lists by number of column blocks
-    double* Ks = nullptr;           // np x mc chunk of K(X, X*)
-    double* colpart = nullptr;      // nb x mc partial column sums of squares
-    double* mean_tmp = nullptr;     // mc
+    DevBuf<double> Ks;              // np x mc chunk of K(X, X*)
+    DevBuf<double> colpart;         // nb x mc partial column sums of squares
+    DevBuf<double> mean_tmp;        // mc
     TileDesc* pred_tiles = nullptr; // tile list of the variance product
     int64_t pred_ntiles = 0;
     int64_t bytes = 0;
@@ -185,14 +199,12 @@ struct gpimhip_ctx {
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[7];
     // Adam bias-correction table for the fused small-N trainer
-    double* bc = nullptr;
-    int64_t bc_cap = 0;
+    DevBuf<double> bc;
     std::vector<double> bc_host;
     // top-k scratch
-    unsigned long long* keys = nullptr;
-    int64_t keys_cap = 0;
-    double* acq_tmp = nullptr; int64_t acq_tmp_cap = 0;   // observed-rows posterior + incumbent (gpimhip_acquire_exact)
-    char* sel_scratch = nullptr;    // radix-select state, candidates, nanmax partials (select.hip)
+    DevBuf<unsigned long long> keys;
+    DevBuf<double> acq_tmp;         // observed-rows posterior + incumbent (gpimhip_acquire_exact)
+    DevBuf<char> sel_scratch;       // radix-select state, candidates, nanmax partials (select.hip)
     // training-loop bookkeeping: iterations completed by the last fit call, pinned copy of the status
     // word + events of the bounded run-ahead check (api.hip: RunAhead)
     int fit_completed = 0;
@@ -212,8 +224,44 @@ struct gpimhip_ctx {
     void* border = nullptr;
     // joint posterior draws: the (N + M)^2 matrix and its factorisation context, owned by api.hip (SampleWs); sample_release()
     void* sample = nullptr;
-    double* refine = nullptr; int64_t refine_cap = 0;    // residual, correction and partial sums of the refinement (fp32 handles)
+    DevBuf<double> refine;          // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
+};
+
+template <typename T> int DevBuf<T>::alloc(gpimhip_ctx* h, int64_t count, const char* what) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (size_t)count * sizeof(T));
+    if (e != hipSuccess) {
+        if (what) (void)hipGetLastError();
+        gpim_set_error(what ? std::string(what) : std::string("hipMalloc failed: ") + hipGetErrorString(e));
+        return GPIMHIP_E_NOMEM;
+    }
+    p = (T*)q;
+    cap = count;
+    h->bytes += cap * (int64_t)sizeof(T);
+    return GPIMHIP_OK;
+}
+template <typename T> void DevBuf<T>::release(gpimhip_ctx* h) {
+    if (p) {
+        (void)hipFree(p);
+        h->bytes -= cap * (int64_t)sizeof(T);
+    }
+    p = nullptr;
+    cap = 0;
+}
+template <typename T> int DevBuf<T>::grow(gpimhip_ctx* h, int64_t want) {
+    if (cap >= want) return GPIMHIP_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    release(h);
+    return alloc(h, want);
+}
+template <typename... Bufs> static inline void dev_release(gpimhip_ctx* h, Bufs&... bufs) { (bufs.release(h), ...); }
+
+// h->nbatch = nbatch until the end of the scope, then what it was before (a launch of ONE problem in a call on a batch)
+struct BatchScope {
+    gpimhip_ctx* h; int prev;
+    BatchScope(gpimhip_ctx* h_, int nbatch) : h(h_), prev(h_->nbatch) { h->nbatch = nbatch; }
+    ~BatchScope() { h->nbatch = prev; }
 };
 
 // entry points outside the exact-GP path keep their matrices in double
@@ -257,6 +305,10 @@ static inline int gemv_tri_chunks(int64_t np) { return (int)((np + gemv_tri_rc(n
 // api.hip
 int ws_ensure(gpimhip_ctx* h, int64_t N);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
+// The preamble of a fit call: info[1] = "completed" = huge until a failure, fit_completed = T and, for T > 0, the
+// bias-correction table, then the Adam state (adam_bytes at adam_m and, where the two halves are buffers of their own, at
+// adam_v) and the iteration counter zeroed.  What a fit of T == 0 returns is the caller's business.
+int fit_prologue(gpimhip_ctx* h, double lr, int T, double* adam_m, double* adam_v, size_t adam_bytes, int32_t* iter);
 int plan_ensure(gpimhip_ctx* h, int nb);
 int check_model(const gpimhip_model_t* m);
 int launch_potrf(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);

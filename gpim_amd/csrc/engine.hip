@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void diag_inv_copy_kernel(R* __restrict__ A, i
 int launch_diag_inv_copy(gpimhip_ctx* h, double* A, int64_t ld, int nb) {
     if (h->fp32)
         hipLaunchKernelGGL(diag_inv_copy_kernel<float>, dim3(nb, h->nbatch), dim3(256), 0, h->stream,
-                           reinterpret_cast<float*>(A), ld, reinterpret_cast<const float*>(h->dinv), (int64_t)nb * NB * ld,
+                           reinterpret_cast<float*>(A), ld, reinterpret_cast<const float*>(h->dinv.p), (int64_t)nb * NB * ld,
                            (int64_t)nb * NB * NB);
     else
         hipLaunchKernelGGL(diag_inv_copy_kernel<double>, dim3(nb, h->nbatch), dim3(256), 0, h->stream, A, ld, h->dinv,

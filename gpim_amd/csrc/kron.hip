@@ -42,55 +42,30 @@ struct KronWs {
     int n[KMAXD] = {0, 0, 0, 0};
     int64_t N = 0;
     KronAxes tr;                 // the training grid's axes
-    double* arena = nullptr;     // the N-sized vectors
-    int64_t arena_count = 0;
+    DevBuf<double> arena;        // the N-sized vectors
     double *yt = nullptr, *at = nullptr, *t1 = nullptr, *t2 = nullptr, *Z = nullptr, *part = nullptr;
     int nblk = 0;
     // prediction
     int m[KMAXD] = {0, 0, 0, 0};
     int64_t M = 0, pmax = 0;
-    double* parena = nullptr;
-    int64_t parena_count = 0;
+    DevBuf<double> parena;
     double *Ks = nullptr, *Bs = nullptr, *p1 = nullptr, *p2 = nullptr, *tcoords = nullptr;
     int64_t koff[KMAXD] = {0, 0, 0, 0};
     // posterior draws (gpimhip_sample_kron)
     KronAxes un;                 // the union axes, when they differ from the training axes
-    double* sarena = nullptr;
-    int64_t sarena_count = 0;
+    DevBuf<double> sarena;
     int64_t s_key[3 + 3 * KMAXD] = {0};      // S, d, buffer size, n_union, n, n_test the workspace was carved for
     double *RG = nullptr, *RT = nullptr, *Zc = nullptr, *sa = nullptr, *sb = nullptr;
     int32_t *ic = nullptr, *it = nullptr;
     int64_t rgoff[KMAXD] = {0, 0, 0, 0}, rtoff[KMAXD] = {0, 0, 0, 0};
 };
 
-static void kron_free(gpimhip_ctx* h, double*& p, int64_t& count) {
-    if (p) { (void)hipFree(p); h->bytes -= count * (int64_t)sizeof(double); }
-    p = nullptr; count = 0;
-}
-
 void kron_release(gpimhip_ctx* h) {
     KronWs* w = static_cast<KronWs*>(h->kron);
     if (!w) return;
-    kron_free(h, w->arena, w->arena_count);
-    kron_free(h, w->tr.arena, w->tr.arena_count);
-    kron_free(h, w->un.arena, w->un.arena_count);
-    kron_free(h, w->parena, w->parena_count);
-    kron_free(h, w->sarena, w->sarena_count);
+    dev_release(h, w->arena, w->tr.arena, w->un.arena, w->parena, w->sarena);
     delete w;
     h->kron = nullptr;
-}
-
-static int kron_alloc(gpimhip_ctx* h, int64_t count, const char* what, double*& p, int64_t& kept) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)count * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        gpim_set_error(what);
-        return GPIMHIP_E_NOMEM;
-    }
-    p = (double*)q;
-    kept = count;
-    h->bytes += count * (int64_t)sizeof(double);
-    return GPIMHIP_OK;
 }
 
 // the per-axis state for axes of the orders n[]; grad: with E, Mm and mdiag (training)
@@ -99,14 +74,14 @@ int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool 
     for (int i = 0; i < d && same; ++i) same = a.n[i] == n[i];
     if (same) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    kron_free(h, a.arena, a.arena_count);
+    a.arena.release(h);
     a.d = d; a.grad = grad;
     a.sum_n = 0; a.sum_n2 = 0;
     int64_t N = 1;
     for (int i = 0; i < KMAXD; ++i) a.n[i] = i < d ? n[i] : 1;
     for (int i = 0; i < d; ++i) { N *= n[i]; a.sum_n += n[i]; a.sum_n2 += (int64_t)n[i] * n[i]; }
     const int64_t count = (grad ? 3 : 2) * a.sum_n + (grad ? 7 : 5) * a.sum_n2 + 32;
-    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP axis workspace)", a.arena, a.arena_count));
+    GP_TRY(a.arena.alloc(h, count, "hipMalloc failed (structured-GP axis workspace)"));
     double* p = a.arena;
     auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
     KronDev& dv = a.dev;
@@ -132,14 +107,14 @@ static int kron_ensure(gpimhip_ctx* h, int d, const int32_t* n, KronWs** out) {
     GP_TRY(kron_axes_ensure(h, w.tr, d, n, true));
     if (same) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    kron_free(h, w.arena, w.arena_count);
+    w.arena.release(h);
     w.d = d;
     w.N = 1;
     for (int i = 0; i < KMAXD; ++i) w.n[i] = i < d ? n[i] : 1;
     for (int i = 0; i < d; ++i) w.N *= n[i];
     w.nblk = (int)std::min<int64_t>(1024, (w.N + 255) / 256);
     const int64_t count = (4 + d) * w.N + (int64_t)w.nblk * 16 + 32;
-    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP workspace)", w.arena, w.arena_count));
+    GP_TRY(w.arena.alloc(h, count, "hipMalloc failed (structured-GP workspace)"));
     double* p = w.arena;
     auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
     w.yt = take(w.N); w.at = take(w.N); w.t1 = take(w.N); w.t2 = take(w.N);
@@ -777,7 +752,7 @@ int kron_root_rows(gpimhip_ctx* h, const KronDev& dv, int ax, const int32_t* idx
 }
 
 void kron_axes_free(gpimhip_ctx* h, KronAxes& a) {
-    kron_free(h, a.arena, a.arena_count);
+    a.arena.release(h);
     a.d = 0;
 }
 int kron_cross(gpimhip_ctx* h, const KronDev& dv, const ThetaDev* th, const double* tcoords, int toff, int mi, int ax, double* Ks) {
@@ -860,9 +835,9 @@ static int kron_predict_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* n_te
     for (int i = 0; i < d && same; ++i) same = w.m[i] == n_test[i];
     if (!same) {
         HIP_TRY(hipStreamSynchronize(h->stream));
-        kron_free(h, w.parena, w.parena_count);
+        w.parena.release(h);
         const int64_t count = sum_m + 2 * sum_mn + 2 * pmax + 64;
-        GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP prediction workspace)", w.parena, w.parena_count));
+        GP_TRY(w.parena.alloc(h, count, "hipMalloc failed (structured-GP prediction workspace)"));
         double* p = w.parena;
         auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
         w.tcoords = take(sum_m); w.Ks = take(sum_mn); w.Bs = take(sum_mn); w.p1 = take(pmax); w.p2 = take(pmax);
@@ -913,11 +888,11 @@ static int kron_sample_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* nu, i
     for (int i = 0; i < d; ++i) { key[3 + i] = nu[i]; key[3 + KMAXD + i] = w.n[i]; key[3 + 2 * KMAXD + i] = w.m[i]; }
     if (w.sarena && memcmp(key, w.s_key, sizeof(key)) == 0) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    kron_free(h, w.sarena, w.sarena_count);
+    w.sarena.release(h);
     int64_t sum_n = 0, sum_m = 0;
     for (int i = 0; i < d; ++i) { sum_n += w.n[i]; sum_m += w.m[i]; }
     const int64_t count = sum_gu + sum_tu + (sum_n + sum_m + 4) / 2 + S * PU + 2 * S * smax + 32;
-    GP_TRY(kron_alloc(h, count, "hipMalloc failed (structured-GP posterior-draw workspace)", w.sarena, w.sarena_count));
+    GP_TRY(w.sarena.alloc(h, count, "hipMalloc failed (structured-GP posterior-draw workspace)"));
     double* p = w.sarena;
     auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
     w.RG = take(sum_gu); w.RT = take(sum_tu);
@@ -948,13 +923,8 @@ int gpimhip_fit_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, cons
     if (!h || !m || !y || !u_inout || T < 0) return GPIMHIP_E_BADARG;
     KronWs* w;
     GP_TRY(kron_prepare(h, m, d, n, axes, &w));
-    HIP_TRY(hipMemsetAsync(h->info + 1, 0x7f, sizeof(int32_t), h->stream));
-    h->fit_completed = T;
+    GP_TRY(fit_prologue(h, lr, T, h->adam_m, h->adam_v, MAXP * sizeof(double), h->iter));
     if (T == 0) return GPIMHIP_OK;
-    GP_TRY(upload_bc_table(h, lr, T));
-    HIP_TRY(hipMemsetAsync(h->adam_m, 0, MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->adam_v, 0, MAXP * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->iter, 0, sizeof(int32_t), h->stream));
     const FinalizeIter it{h->iter, h->bc, T, hist_out, loss_out};
     // every iteration is the same ~4d + 8 small launches
     return run_fit_iterations(h, T, FIT_LOOP_PLAIN,

@@ -1,6 +1,6 @@
 // kron.hpp -- the per-axis part of the Kronecker solver (kron.hip) that other translation units build on: one set of grid
 // axes with K_i, its eigen-decomposition and the gradient matrices, and the mode products.  Used by the dense-by-Kronecker
-// blocks (pkron.hip, api.hip), whose complete axes are exactly such a set.
+// blocks (pkron.hip), whose complete axes are exactly such a set.
 #pragma once
 #include "common.hpp"
 
@@ -32,8 +32,7 @@ struct KronAxes {
     int n[KMAXD] = {0, 0, 0, 0};
     int64_t sum_n = 0, sum_n2 = 0;
     bool grad = false;
-    double* arena = nullptr;
-    int64_t arena_count = 0;
+    DevBuf<double> arena;
     KronDev dev;
 };
 

@@ -190,8 +190,8 @@ __global__ __launch_bounds__(1024) void sel_sort_kernel(const double* __restrict
 
 int launch_topk_radix(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
                       int64_t* count) {
-    SelState* st = reinterpret_cast<SelState*>(h->sel_scratch);
-    SelCand* cand = reinterpret_cast<SelCand*>(h->sel_scratch + 4096);
+    SelState* st = reinterpret_cast<SelState*>(h->sel_scratch.p);
+    SelCand* cand = reinterpret_cast<SelCand*>(h->sel_scratch.p + 4096);
     const unsigned nblk = (unsigned)std::min<int64_t>(1024, (M + 255) / 256);
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(SelState), h->stream));
     hipLaunchKernelGGL(sel_keys_kernel, dim3(nblk), dim3(256), 0, h->stream, x, (long long)M, keep_nan, k, h->keys, st);
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(1024) void nanmax_final_kernel(const double* __rest
     if (threadIdx.x == 0) out[0] = (red[0] == -INFINITY) ? __builtin_nan("") : red[0];
 }
 int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* out) {
-    double* part = reinterpret_cast<double*>(h->sel_scratch + 4096 + SEL_MAXK * sizeof(SelCand));
+    double* part = reinterpret_cast<double*>(h->sel_scratch.p + 4096 + SEL_MAXK * sizeof(SelCand));
     const int nblk = (int)std::min<int64_t>(1024, (n + 255) / 256);
     hipLaunchKernelGGL(nanmax_partial_kernel, dim3(nblk), dim3(256), 0, h->stream, x, (long long)n, part);
     hipLaunchKernelGGL(nanmax_final_kernel, dim3(1), dim3(1024), 0, h->stream, part, nblk, out);
