@@ -242,6 +242,17 @@ _PROTOS = {
                                       ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
     "gpimhip_predict_sm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
                                           ctypes.c_int64, c_dp, c_dp]),
+    "gpimhip_sample_sm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
+                                         ctypes.c_int64, c_dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_dp, c_dp,
+                                         c_dp]),
+    "gpimhip_sample_sm_pathwise": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp,
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_double), c_dp, c_dp, ctypes.c_int64, c_dp, c_dp,
+                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
+    "gpimhip_sample_sm_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_double), c_dp, c_dp, c_dp,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_dp, c_dp]),
     "gpimhip_sm_nll_grad_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, c_dp, ctypes.c_int64,
                                                    ctypes.c_int32, c_dp, c_dp, c_dp]),
     "gpimhip_fit_sm_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SmStruct), c_dp, c_dp, c_dp, ctypes.c_int64,

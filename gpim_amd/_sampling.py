@@ -7,13 +7,16 @@ for), ``_check_data``, the test grid resolved WITHOUT storing it (finite, or Val
 grid, ``n_samples``, the shape of a given ``z``, the jitter rule, device memory -- and only then stores a new grid, draws
 ``z`` when none was given, allocates, calls the solver and remembers the size of the call.  So a refused call leaves the
 model, its stored test grid and the solver's test axes as they were, whatever the method.  ``draw_device`` is the same for
-device rows and a device ``z`` (Thompson sampling, acqfunc.thompson_on_device).
+device rows and a device ``z`` (Thompson sampling, acqfunc.thompson_on_device).  ``SPECTRAL_METHODS`` are the three methods of
+``skreconstructor(kernel='Spectral').sample``: the same objects with their gate, the source of the
+jitter rule's noise and their call replaced, through the same ``draw``.
 
 A method says what differs (``o`` is the reconstructor): ``gate(o)``; ``grid(o, Xtest) -> (X, shape)``, rows on the device
 or the coordinate vectors of a product grid; ``geometry(o, X, shape) -> g``, a dict of host sizes and of what the call
 takes; ``plan(g, S, noiseless, z_on_device) -> (W, layout, bytes, subject)``, the width of z, the words for its layout, the
 device memory of the call and the subject of its MemoryError, from ``g`` alone (no device); ``jitter``, a rule of
-``_check_jitter``; ``call(o, g, X, z, noiseless, jitter, mean, out) -> rc``.
+``_check_jitter``, with ``jitter_default(o)`` and ``jitter_bound(o)`` (the noise plus the model's own jitter, named by
+``BOUND``); ``call(o, g, X, z, noiseless, jitter, mean, out) -> rc``.
 """
 import numpy as np
 import torch
@@ -116,6 +119,13 @@ class Joint:
     name, jitter, checks_n_samples, memory_of_total = "joint", None, False, False
     stores_training_grid = True     # without any test grid the training points become the stored one, as in predict()
     ENGINE = "joint posterior draws are built for the dense double-precision engine only (%s)"
+    BOUND = "noise + the model's jitter"
+
+    def jitter_default(self, o):
+        return o._spec.jitter
+
+    def jitter_bound(self, o):
+        return float(o._spec.constrained(o._u)[2]) + o._spec.jitter
 
     def gate(self, o):
         _refuse(self.ENGINE, (o.do_sparse, "sparse=True"), (o.do_structured or o.do_symm, "structured=True"),
@@ -149,7 +159,7 @@ class Pathwise(Joint):
         the same tensors."""
         c = getattr(o, "_pw_cache", None)
         if c is None or c[0] is not X or c[1] is not o._Xd or c[2] != tuple(shape):
-            d = o._spec.dim
+            d = o._Xd.shape[1]
             if len(shape) != d or int(np.prod(shape)) != X.shape[0]:
                 raise NotImplementedError("pathwise draws need a product grid: %d test rows do not fill a grid of shape %s in "
                                           "%d dimensions" % (X.shape[0], tuple(shape), d))
@@ -244,6 +254,7 @@ class Kron:
     [zeta (prod U_i) | z_e (N) | z_n (M)] whether noiseless or not."""
     name, stores_training_grid, checks_n_samples, memory_of_total = "kron", False, True, False
     jitter = ("ge0", "method='kron' needs a finite jitter >= 0")
+    jitter_default = Joint.jitter_default
     ENGINE = "method='kron' draws through the Kronecker eigenbasis: reconstructor(..., kernel='RBF', structured=True) " \
              "or skreconstructor(..., 'RBF') on a fully observed grid, in double precision (%s)"
 
@@ -299,6 +310,7 @@ class Columns:
     (DESIGN.md section 23); z is [zeta (U_s prod U_i) | z_e (N) | z_n (M)] whether noiseless or not."""
     name, stores_training_grid, checks_n_samples, memory_of_total = "columns", False, True, False
     jitter = ("gt0", "method='columns' needs a finite jitter > 0 (the prior factor of the ragged rows)")
+    jitter_default = Joint.jitter_default
     ENGINE = "method='columns' draws through the dense-by-Kronecker blocks: skreconstructor(..., 'RBF') whose solver " \
              "is 'columns' (whole columns of the grid missing), in double precision (%s)"
 
@@ -365,15 +377,80 @@ def _columns_library_doubles(S, Ns, Ms, Us, J, nu, nn, nm):
 METHODS = {m.name: m() for m in (Joint, Pathwise, Blocks, Border, Kron, Columns)}
 
 
+class _Spectral:
+    """What differs for ``smreconstructor``.  A method is gated by the data, not by ``rec.solver``:
+    the posterior depends on the observed rows and u only, which every solver's model holds.  The model has no jitter of
+    its own, so the jitter rule's bound is the noise, and the draw's jitter defaults to 1e-5 (below the noise floor 1e-4)."""
+    BOUND = "noise (this model has no jitter of its own)"
+
+    def gate(self, o):
+        pass
+
+    def jitter_default(self, o):
+        return 1e-5
+
+    def jitter_bound(self, o):
+        return o._params()[4]
+
+    @staticmethod
+    def phase_bytes(o, *rows):
+        """The phase buffers of the library: 2 Q d doubles per row, the rows padded to 128 per buffer."""
+        return 16 * o.num_mixtures * o._Xd.shape[1] * sum(-(-int(n) // 128) * 128 for n in rows)
+
+
+class SpectralJoint(_Spectral, Joint):
+    jitter = ("ge0", "method='joint' needs a finite jitter >= 0")
+
+    def geometry(self, o, X, shape):
+        return dict(Joint.geometry(self, o, X, shape), phases=self.phase_bytes(o, o._Xd.shape[0] + X.shape[0]))
+
+    def plan(self, g, S, noiseless, z_on_device):
+        W, layout, need, subject = Joint.plan(self, g, S, noiseless, z_on_device)
+        return W, layout, need + g["phases"], subject
+
+    def call(self, o, g, X, z, noiseless, jitter, mean, out):
+        g["var"] = torch.empty_like(mean)
+        return o._draw_joint(X, z, noiseless, jitter, mean, g["var"], out)
+
+
+class SpectralPathwise(_Spectral, Pathwise):
+    def geometry(self, o, X, shape):
+        g = Pathwise.geometry(self, o, X, shape)
+        return dict(g, phases=self.phase_bytes(o, g["N"], g["nq"], g["M"]))
+
+    def plan(self, g, S, noiseless, z_on_device):
+        W, layout, need, subject = Pathwise.plan(self, g, S, noiseless, z_on_device)
+        return W, layout, need + g["phases"], subject
+
+    def call(self, o, g, X, z, noiseless, jitter, mean, out):
+        return o._draw_pathwise(X, g["P"], g["idx_d"], z, noiseless, jitter, mean, out)
+
+
+class SpectralBlocks(_Spectral, Blocks):
+    def geometry(self, o, X, shape):
+        g = Blocks.geometry(self, o, X, shape)
+        return dict(g, phases=self.phase_bytes(o, g["nq"]))
+
+    def plan(self, g, S, noiseless, z_on_device):
+        W, layout, need, subject = Blocks.plan(self, g, S, noiseless, z_on_device)
+        return W, layout, need + g["phases"], subject
+
+    def call(self, o, g, X, z, noiseless, jitter, mean, out):
+        return o._draw_blocks(X, g["P"], z, noiseless, jitter, mean, out)
+
+
+SPECTRAL_METHODS = {m.name: m() for m in (SpectralJoint, SpectralPathwise, SpectralBlocks)}
+
+
 def _check_jitter(o, m, jitter):
-    """The jitter of the call (default: the model's) under the method's rule: 'noise' 0 < jitter <= noise + the model's
-    jitter, 'ge0' 0 <= jitter < inf, 'gt0' 0 < jitter < inf; None: the library checks it."""
-    jitter = o._spec.jitter if jitter is None else float(jitter)
+    """The jitter of the call (default: the method's, i.e. the model's) under the method's rule: 'noise' 0 < jitter <= noise
+    + the model's jitter, 'ge0' 0 <= jitter < inf, 'gt0' 0 < jitter < inf; None: the library checks it."""
+    jitter = m.jitter_default(o) if jitter is None else float(jitter)
     rule, text = m.jitter or (None, None)
     if rule == "noise":
-        s = float(o._spec.constrained(o._u)[2]) + o._spec.jitter
+        s = m.jitter_bound(o)
         if not (0.0 < jitter <= s):
-            raise ValueError("%s 0 < jitter <= noise + the model's jitter = %g; got %g" % (text, s, jitter))
+            raise ValueError("%s 0 < jitter <= %s = %g; got %g" % (text, m.BOUND, s, jitter))
     elif rule and not ((0.0 <= jitter if rule == "ge0" else 0.0 < jitter) and jitter < np.inf):
         raise ValueError("%s; got %g" % (text, jitter))
     return jitter
@@ -412,9 +489,10 @@ def draw_device(o, name, X, shape, z_d, noiseless, jitter):
     return _draw(o, m, X, shape, None, z_d, noiseless, jitter)
 
 
-def draw(o, name, n_samples, Xtest, noiseless, seed, z, jitter):
-    """``reconstructor.sample``: ndarray (n_samples, *grid shape) of method `name`'s draws."""
-    m = METHODS[name]
+def draw(o, name, n_samples, Xtest, noiseless, seed, z, jitter, methods=METHODS):
+    """``reconstructor.sample`` (and ``smreconstructor.sample`` with ``methods=SPECTRAL_METHODS``): ndarray (n_samples, *grid
+    shape) of method `name`'s draws."""
+    m = methods[name]
     if name != "columns" and isinstance(o._solver, _solvers.Columns):
         raise NotImplementedError(_solvers.Columns._NO_DRAWS + " (got method=%r)" % (name,))
     m.gate(o)

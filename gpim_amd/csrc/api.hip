@@ -2463,6 +2463,13 @@ struct SampleWs {
     // index maps, tile lists) and the union of the complete axes when the training axes do not serve; `sub` factors L_P
     DevBuf<double> ck;
     KronAxes ck_un;
+    // draws of the spectral-mixture model (sm_family): the two parameter sets of launch_sm_params, the
+    // phases of the dense rows ([X; Xs], or the training rows), of the fundamental domain and of the grid G, and y - c
+    DevBuf<SmDev> smst;
+    DevBuf<double> phx;
+    DevBuf<double> phq;
+    DevBuf<double> phg;
+    DevBuf<double> smy;
 };
 static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
 static int64_t sample_bytes(const gpimhip_ctx* h) {
@@ -2473,13 +2480,122 @@ static int64_t sample_bytes(const gpimhip_ctx* h) {
 static void sample_release(gpimhip_ctx* h) {
     SampleWs* w = sws(h);
     if (!w) return;
-    dev_release(h, w->J, w->XX, w->vec, w->Pb, w->Kt, w->pw, w->vst, w->vth, w->vz, w->vH, w->vmom, w->ck);
+    dev_release(h, w->J, w->XX, w->vec, w->Pb, w->Kt, w->pw, w->vst, w->vth, w->vz, w->vH, w->vmom, w->ck, w->smst, w->phx, w->phq,
+                w->phg, w->smy);
     kron_axes_free(h, w->ck_un);
     if (w->sub) gpimhip_destroy(w->sub);
     if (w->subp) gpimhip_destroy(w->subp);
     if (w->subt) gpimhip_destroy(w->subt);
     delete w;
     h->sample = nullptr;
+}
+
+// ------------------------------------------------------------------------------------------
+// What the draw drivers below (sample_enqueue, sample_pathwise_impl, sample_blocks_enqueue) need of a kernel family.  The
+// vectors, the factorisations, the sweeps, the basis changes and the workspaces are shared; a family sets the parameters up,
+// builds a dense or a reflection-block covariance, and applies K(G, X) -- and, where its mean is a constant c, centres y and
+// shifts the results.  `ctx` is the context the launch runs on (its theta, its reflection state, its stream).
+//   params       ctx->theta at u (var, noise, diag_add = the model's diagonal term s); `other`: the call's second diagonal
+//                term (0 for the joint matrix, the draw's jitter d for the prior blocks), for a family that keeps it itself
+//   kmat         lower tiles of K(X, X) (+ s I if model_diag), identity padding up to np
+//   kmat_refl    block ctx->refl.pb_off of the grid's covariance on the fundamental domain, + s I if model_diag, else + the
+//                other term (the stationary kernels read either from ctx->theta->diag_add, which the drivers set)
+//   cross_apply  launch_pw_cross_apply (sample.hpp); Xt must be the rows of the latest kmat on ctx
+//   reserve      the family's own buffers for dense rows / a fundamental domain / a grid of these (padded) sizes and n_y targets
+//   centre       out = y - c;  shift: v += c   (null: a zero mean)
+// ------------------------------------------------------------------------------------------
+struct DrawFamily {
+    int dim = 0;
+    const gpimhip_model_t* m = nullptr;         // the stationary kernels of kfun.hpp
+    const gpimhip_sm_t* sm = nullptr;           // the spectral mixture
+    const double* u = nullptr;
+    int (*params)(const DrawFamily&, gpimhip_ctx* ctx, double other) = nullptr;
+    int (*kmat)(const DrawFamily&, gpimhip_ctx* ctx, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
+                int64_t np) = nullptr;
+    int (*kmat_refl)(const DrawFamily&, gpimhip_ctx* ctx, const double* Xq, int64_t Nq, bool model_diag, double* out, int64_t ld,
+                     int64_t np) = nullptr;
+    int (*cross_apply)(const DrawFamily&, gpimhip_ctx* ctx, const double* G, int64_t M, const double* Xt, int64_t N,
+                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
+                       int noiseless, double* mean_out, double* out) = nullptr;
+    int (*reserve)(const DrawFamily&, gpimhip_ctx* h, int64_t rows_x, int64_t rows_q, int64_t rows_g, int64_t n_y) = nullptr;
+    int (*centre)(const DrawFamily&, gpimhip_ctx* ctx, const double* y, int64_t n, double* out) = nullptr;
+    int (*shift)(const DrawFamily&, gpimhip_ctx* ctx, double* v, int64_t n) = nullptr;
+    SampleWs* w = nullptr;                      // where reserve's buffers live (the model handle's)
+};
+
+static DrawFamily stationary_family(const gpimhip_model_t* m, const double* u) {
+    DrawFamily F;
+    F.dim = m->dim;
+    F.m = m;
+    F.u = u;
+    F.params = [](const DrawFamily& F, gpimhip_ctx* c, double) { return launch_theta(c, F.m, F.u); };
+    F.kmat = [](const DrawFamily& F, gpimhip_ctx* c, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
+                int64_t np) {
+        return launch_kmat(c, F.m, X, N, nullptr, N, c->theta, 0.0, model_diag ? 1 : 0, out, ld, np, np, 1, 1, 0, 0, 0);
+    };
+    F.kmat_refl = [](const DrawFamily& F, gpimhip_ctx* c, const double* Xq, int64_t Nq, bool, double* out, int64_t ld,
+                     int64_t np) { return launch_kmat_refl(c, F.m, Xq, Nq, nullptr, Nq, c->theta, out, ld, np, np, 1, 0, 0, 0, 1.0); };
+    F.cross_apply = [](const DrawFamily& F, gpimhip_ctx* c, const double* G, int64_t M, const double* Xt, int64_t N,
+                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
+                       int noiseless, double* mean_out, double* out) {
+        return launch_pw_cross_apply(c, F.m, G, M, Xt, N, c->theta, Al, npt, S, s0, g, Z, zw, zn_off, noiseless, mean_out, out);
+    };
+    return F;
+}
+
+// The spectral mixture: the phases of a build's points are computed right before it (O(points Q d) next to the build's
+// O(points^2 Q d)); those of the dense rows stay in phx for cross_apply, which adds the phases of G once per call.
+static DrawFamily sm_family(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u) {
+    if (!h->sample) h->sample = new SampleWs();
+    DrawFamily F;
+    F.dim = sm->dim;
+    F.sm = sm;
+    F.u = u;
+    F.w = sws(h);
+    F.reserve = [](const DrawFamily& F, gpimhip_ctx* h, int64_t rows_x, int64_t rows_q, int64_t rows_g, int64_t n_y) {
+        const int64_t per = 2 * (int64_t)F.sm->mixtures * F.sm->dim;
+        if (!F.w->smst) GP_TRY(F.w->smst.alloc(h, 2));
+        GP_TRY(F.w->phx.grow(h, per * rows_x));
+        GP_TRY(F.w->phq.grow(h, per * rows_q));
+        GP_TRY(F.w->phg.grow(h, per * rows_g));
+        return F.w->smy.grow(h, n_y);
+    };
+    F.params = [](const DrawFamily& F, gpimhip_ctx* c, double other) {
+        return launch_sm_params(c, F.sm, F.u, F.w->smst, c->theta, other);
+    };
+    F.kmat = [](const DrawFamily& F, gpimhip_ctx* c, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
+                int64_t np) {
+        GP_TRY(launch_sm_setup(c, F.sm, F.u, X, N, np, F.w->phx, nullptr, nullptr, nullptr, nullptr));
+        return launch_sm_kmat(c, F.sm, X, N, F.w->phx, np, nullptr, N, nullptr, np, F.w->smst + (model_diag ? 0 : 1), out, ld, np,
+                              np, 1, 1);
+    };
+    F.kmat_refl = [](const DrawFamily& F, gpimhip_ctx* c, const double* Xq, int64_t Nq, bool model_diag, double* out, int64_t ld,
+                     int64_t np) {
+        GP_TRY(launch_sm_setup_refl(c, F.sm, F.u, Xq, Nq, np, F.w->phq, nullptr, nullptr, nullptr, nullptr, nullptr));
+        return launch_sm_kmat_refl(c, F.sm, Xq, Nq, F.w->phq, np, nullptr, Nq, nullptr, np, F.w->smst + (model_diag ? 0 : 1), out,
+                                   ld, 0, np, np, 1, 1, 1.0);
+    };
+    F.cross_apply = [](const DrawFamily& F, gpimhip_ctx* c, const double* G, int64_t M, const double* Xt, int64_t N,
+                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
+                       int noiseless, double* mean_out, double* out) {
+        const int64_t ldg = pad_to(M, NB);
+        if (s0 == 0) GP_TRY(launch_sm_setup(c, F.sm, F.u, G, M, ldg, F.w->phg, nullptr, nullptr, nullptr, nullptr));
+        return launch_sm_cross_apply(c, F.sm, G, M, F.w->phg, ldg, Xt, N, F.w->phx, npt, F.w->smst, c->theta, Al, npt, S, s0, g, Z,
+                                     zw, zn_off, noiseless, mean_out, out);
+    };
+    F.centre = [](const DrawFamily& F, gpimhip_ctx* c, const double* y, int64_t n, double* out) {
+        return launch_sm_centre(c, y, n, F.w->smst, out);
+    };
+    F.shift = [](const DrawFamily& F, gpimhip_ctx* c, double* v, int64_t n) { return launch_sm_addc(c, v, n, F.w->smst); };
+    return F;
+}
+// y - c in the family's buffer when its mean is a constant (reserve has sized it), else y itself
+static int centred(const DrawFamily& F, gpimhip_ctx* ctx, const double* y, int64_t n, const double** out) {
+    *out = y;
+    if (!F.centre) return GPIMHIP_OK;
+    GP_TRY(F.centre(F, ctx, y, n, F.w->smy));
+    *out = F.w->smy;
+    return GPIMHIP_OK;
 }
 
 // sub->z = L11^-1 y from the factor L of the joint matrix: block forward substitution over the block rows that hold
@@ -2502,10 +2618,10 @@ static int sample_forward(gpimhip_ctx* sub, const double* L, int64_t ld, const d
 }
 
 // Everything of one draw call but the closing synchronisation.  theta_src (optional, device): the hyper-parameters, copied
-// into the context's theta in place of launch_theta(sub, m, u) -- a latent block of the multi-output model (variance
-// lambda_t, noise 1, diag_add 1: sample_vgp_impl); u is not read then.  reset_info: clear the context's status word first
+// into the context's theta in place of the family's params -- a latent block of the multi-output model (variance
+// lambda_t, noise 1, diag_add 1: sample_vgp_impl); the family's u is not read then.  reset_info: clear the context's status word first
 // (a call of several blocks clears it once: the word keeps the first failure).
-static int sample_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+static int sample_enqueue(gpimhip_ctx* h, const DrawFamily& F, const double* X, const double* y, int64_t N,
                           const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
                           double* var_out, double* samples_out, const ThetaDev* theta_src, bool reset_info) {
     HIP_TRY(hipSetDevice(h->device));
@@ -2515,12 +2631,13 @@ static int sample_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, const double
     gpimhip_ctx* sub = w->sub;
     sub->stream = h->stream;
     sub->nbatch = 1;
-    const int64_t NM = N + M, d = m->dim;
+    const int64_t NM = N + M, d = F.dim;
     GP_TRY(ws_ensure_b(sub, NM, 1, 1, false));
     const int64_t np = sub->np, ld = sub->ld;
     GP_TRY(w->J.grow(h, np * ld));
     GP_TRY(w->XX.grow(h, np * GPIMHIP_MAX_DIM));
     GP_TRY(w->vec.grow(h, 2 * np + 4 * NB));
+    if (F.reserve) GP_TRY(F.reserve(F, h, np, 0, 0, N));
     double *t = w->vec, *piece = t + np, *mean_ws = piece + 4 * NB;
     if (reset_info) HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
     HIP_TRY(hipMemcpyAsync(w->XX, X, (size_t)(N * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -2528,28 +2645,35 @@ static int sample_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, const double
     // J (lower tiles; identity padding at the end), the two diagonal terms, L
     // (stage timers of the model handle: 4 covariance build, 0 factorisation, 1 forward substitution, 5 each sweep of the draws)
     if (theta_src) HIP_TRY(hipMemcpyAsync(sub->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
-    else GP_TRY(launch_theta(sub, m, u));
+    else GP_TRY(F.params(F, sub, 0.0));
     {
         StageTimer tm(h, 4);
-        GP_TRY(launch_kmat(sub, m, w->XX, NM, nullptr, NM, sub->theta, 0.0, 0, w->J, ld, np, np, 1, 1, 0, 0, 0));
+        GP_TRY(F.kmat(F, sub, w->XX, NM, false, w->J, ld, np));
         GP_TRY(launch_sample_diag(sub, w->J, ld, N, M, sub->theta, noiseless, jitter_s));
     }
     { StageTimer tm(h, 0); GP_TRY(launch_potrf(sub, w->J, np, ld, sub->info)); }
     {
         StageTimer tm(h, 1);
-        GP_TRY(sample_forward(sub, w->J, ld, y, N, t, piece));
+        const double* yc;
+        GP_TRY(centred(F, sub, y, N, &yc));
+        GP_TRY(sample_forward(sub, w->J, ld, yc, N, t, piece));
     }
     for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
         StageTimer tm(h, 5);
         GP_TRY(launch_sample_draws(sub, w->J, ld, N, M, sub->z, Z, S, s0, sub->theta, noiseless, jitter_s, mean_ws, mean_out,
                                    var_out, samples_out));
     }
+    if (F.shift) {
+        StageTimer tm(h, 5);
+        if (mean_out) GP_TRY(F.shift(F, sub, mean_out, M));
+        GP_TRY(F.shift(F, sub, samples_out, (int64_t)S * M));
+    }
     return GPIMHIP_OK;
 }
-static int sample_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+static int sample_impl(gpimhip_ctx* h, const DrawFamily& F, const double* X, const double* y, int64_t N,
                        const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
                        double* var_out, double* samples_out) {
-    GP_TRY(sample_enqueue(h, m, X, y, N, u, Xs, M, Z, S, noiseless, jitter_s, mean_out, var_out, samples_out, nullptr, true));
+    GP_TRY(sample_enqueue(h, F, X, y, N, Xs, M, Z, S, noiseless, jitter_s, mean_out, var_out, samples_out, nullptr, true));
     return finish_and_check(sws(h)->sub);
 }
 
@@ -2593,8 +2717,8 @@ static int pathwise_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order) {
 
 // (stage timers of the model handle: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p, 2 gathers and the
 // basis change U^T, 1 the vector solves, 3 cross_apply_kernel with its epilogue)
-static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
-                                int64_t M, const int64_t* idx, const double* y, int64_t N, const double* u, const double* Z,
+static int sample_pathwise_impl(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
+                                int64_t M, const int64_t* idx, const double* y, int64_t N, const double* Z,
                                 int S, int noiseless, double jitter_s, double* mean_out, double* samples_out) {
     HIP_TRY(hipSetDevice(h->device));
     if (!h->sample) h->sample = new SampleWs();
@@ -2615,14 +2739,15 @@ static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid
                   o_al = o_r + (S + 1) * npt, o_zf = o_al + (S + 1) * npt, o_t = o_zf + npt, o_piece = o_t + npt,
                   o_work = o_piece + 4 * NB, o_mws = o_work + 4 * NB, o_end = o_mws + npq;
     GP_TRY(w->pw.grow(h, o_end));
+    if (F.reserve) GP_TRY(F.reserve(F, h, npt, npq, pad_to(M, NB), N));
     double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *Xt = w->pw + o_xt,
            *R = w->pw + o_r, *Al = w->pw + o_al, *zf = w->pw + o_zf, *t = w->pw + o_t, *piece = w->pw + o_piece,
            *work = w->pw + o_work, *mean_ws = w->pw + o_mws;
     // one status word for both factorisations: the training context's
     HIP_TRY(hipMemsetAsync(st->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(launch_theta(sp, m, u));
+    GP_TRY(F.params(F, sp, jitter_s));
     GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
-    GP_TRY(launch_theta(st, m, u));
+    GP_TRY(F.params(F, st, jitter_s));
     {
         StageTimer tm(h, 2);
         GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, idx, N, Xt));
@@ -2641,7 +2766,7 @@ static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid
         sp->refl.wts = wts + (int64_t)b * Nq;
         {
             StageTimer tm(h, 4);
-            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, false, w->Pb, ldq, npq));
         }
         { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, st->info)); }
         for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
@@ -2654,20 +2779,21 @@ static int sample_pathwise_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid
     // ---- the training side: K + (noise + jitter) I, its factor, alpha for the S draws and for y
     {
         StageTimer tm(h, 4);
-        GP_TRY(launch_kmat(st, m, Xt, N, nullptr, N, st->theta, 0.0, 1, w->Kt, ldt, npt, npt, 1, 1, 0, 0, 0));
+        GP_TRY(F.kmat(F, st, Xt, N, true, w->Kt, ldt, npt));
     }
     { StageTimer tm(h, 0); GP_TRY(launch_potrf(st, w->Kt, npt, ldt, st->info)); }
     {
         StageTimer tm(h, 1);
-        GP_TRY(launch_pw_rhs(st, g, M, idx, N, Z, zw, S, y, st->theta, jitter_s, R, npt));
+        const double* yc;
+        GP_TRY(centred(F, st, y, N, &yc));
+        GP_TRY(launch_pw_rhs(st, g, M, idx, N, Z, zw, S, yc, st->theta, jitter_s, R, npt));
         for (int v = 0; v <= S; ++v)
             GP_TRY(pathwise_solve(st, w->Kt, ldt, R + (int64_t)v * npt, Al + (int64_t)v * npt, zf, t, piece, work));
     }
     {
         StageTimer tm(h, 3);
         for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0))
-            GP_TRY(launch_pw_cross_apply(st, m, G, M, Xt, N, st->theta, Al, npt, S, s0, g, Z, zw, M + N, noiseless, mean_out,
-                                         samples_out));
+            GP_TRY(F.cross_apply(F, st, G, M, Xt, N, Al, npt, S, s0, g, Z, zw, M + N, noiseless, mean_out, samples_out));
         GP_TRY(launch_pw_scatter(st, idx, N, M, Al, npt, S, jitter_s, samples_out));
     }
     return finish_and_check(st);
@@ -2709,9 +2835,10 @@ static int blocks_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const dou
 // (stage timers of the model handle, as sample_pathwise_impl: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p,
 // 2 gathers and both basis changes, 1 the multi-column solves, 3 right-hand sides, combination and epilogue)
 // Everything of one call but the closing synchronisation.  theta_src / reset_info: as sample_enqueue; jitter_m: the model's
-// own jitter of the diagonal K_b + (noise + jitter_m) I (m->jitter; 0 for a latent block of the multi-output model).
-static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
-                                 int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
+// own jitter of the diagonal K_b + (noise + jitter_m) I (m->jitter; 0 for a latent block of the multi-output model and for
+// the spectral mixture).
+static int sample_blocks_enqueue(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
+                                 int64_t M, const double* y, const double* Z, int S, int noiseless,
                                  double jitter_s, double* mean_out, double* samples_out, const ThetaDev* theta_src,
                                  double jitter_m, bool reset_info) {
     HIP_TRY(hipSetDevice(h->device));
@@ -2731,18 +2858,21 @@ static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGri
                   o_zf = o_r + S1 * npq, o_al = o_zf + S1 * npq, o_t = o_al + S1 * npq,
                   o_part = o_t + 8 * npq, o_mws = o_part + (int64_t)gemv_t_multi_chunks(npq) * 8 * 4 * NB, o_end = o_mws + npq;
     GP_TRY(w->pw.grow(h, o_end));
+    if (F.reserve) GP_TRY(F.reserve(F, h, 0, npq, 0, M));
     double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *E = w->pw + o_e, *Cc = w->pw + o_cc,
            *g = w->pw + o_g, *R = w->pw + o_r, *Zf = w->pw + o_zf, *Al = w->pw + o_al, *t = w->pw + o_t, *part = w->pw + o_part,
            *mean_ws = w->pw + o_mws;
     // one status word for the 2 B factorisations
     if (reset_info) HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
     if (theta_src) HIP_TRY(hipMemcpyAsync(sp->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
-    else GP_TRY(launch_theta(sp, m, u));
+    else GP_TRY(F.params(F, sp, jitter_s));
     {
         StageTimer tm(h, 2);
+        const double* yc;
+        GP_TRY(centred(F, sp, y, M, &yc));
         GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
         GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
-        GP_TRY(launch_pw_basis_fwd(sp, gd, Z, zw, M, y, S, Nq, npq, B, E));
+        GP_TRY(launch_pw_basis_fwd(sp, gd, Z, zw, M, yc, S, Nq, npq, B, E));
     }
     sp->refl.mask = gd.mask;
     for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
@@ -2759,7 +2889,7 @@ static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGri
         GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
         {
             StageTimer tm(h, 4);
-            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, false, w->Pb, ldq, npq));
         }
         { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
         for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
@@ -2771,7 +2901,7 @@ static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGri
         GP_TRY(launch_pw_reset_diag(sp, sp->theta, jitter_m));
         {
             StageTimer tm(h, 4);
-            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
+            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, true, w->Pb, ldq, npq));
         }
         { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
         { StageTimer tm(h, 3); GP_TRY(launch_pw_blocks_rhs(sp, Cb, Eb, S, Nq, npq, sp->theta, jitter_s, R)); }
@@ -2791,13 +2921,18 @@ static int sample_blocks_enqueue(gpimhip_ctx* h, const gpimhip_model_t* m, PwGri
     {
         StageTimer tm(h, 3);
         GP_TRY(launch_pw_blocks_out(sp, g, M, S, Z, zw, 2 * M, noiseless, sp->theta, mean_out, samples_out));
+        if (F.shift) {
+            if (mean_out) GP_TRY(F.shift(F, sp, mean_out, M));
+            GP_TRY(F.shift(F, sp, samples_out, (int64_t)S * M));
+        }
     }
     return GPIMHIP_OK;
 }
-static int sample_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, PwGrid gd, const double* twoc, const double* G,
-                              int64_t M, const double* y, const double* u, const double* Z, int S, int noiseless,
-                              double jitter_s, double* mean_out, double* samples_out) {
-    GP_TRY(sample_blocks_enqueue(h, m, gd, twoc, G, M, y, u, Z, S, noiseless, jitter_s, mean_out, samples_out, nullptr, m->jitter,
+// jitter_m: the model's own jitter (m->jitter; the spectral mixture has none)
+static int sample_blocks_impl(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
+                              int64_t M, const double* y, const double* Z, int S, int noiseless,
+                              double jitter_s, double jitter_m, double* mean_out, double* samples_out) {
+    GP_TRY(sample_blocks_enqueue(h, F, gd, twoc, G, M, y, Z, S, noiseless, jitter_s, mean_out, samples_out, nullptr, jitter_m,
                                  true));
     return finish_and_check(sws(h)->subp);
 }
@@ -2837,8 +2972,9 @@ static int sample_vgp_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimh
         GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
         GP_TRY(launch_vgp_project_to(h, Y, N, T, w->vst, w->vz));
     }
+    const DrawFamily F = stationary_family(m, nullptr);         // (every block's theta comes from vth)
     for (int t = 0; t < T; ++t)
-        GP_TRY(sample_enqueue(h, m, X, w->vz + (int64_t)t * N, N, nullptr, Xs, M, Z + (int64_t)t * S * M, S, noiseless, jitter_s,
+        GP_TRY(sample_enqueue(h, F, X, w->vz + (int64_t)t * N, N, Xs, M, Z + (int64_t)t * S * M, S, noiseless, jitter_s,
                               mean_out ? mblk + (int64_t)t * M : nullptr, var_out ? vblk + (int64_t)t * M : nullptr,
                               w->vH + (int64_t)t * S * M, w->vth + t, t == 0));
     { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
@@ -2860,8 +2996,9 @@ static int sample_vgp_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, cons
     const int64_t zw = 2 * M + (noiseless ? 0 : M);
     GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
     GP_TRY(launch_vgp_project_to(h, Y, M, T, w->vst, w->vz));
+    const DrawFamily F = stationary_family(m, nullptr);         // (every block's theta comes from vth)
     for (int t = 0; t < T; ++t)
-        GP_TRY(sample_blocks_enqueue(h, m, gd, twoc, G, M, w->vz + (int64_t)t * M, nullptr, Z + (int64_t)t * S * zw, S, noiseless,
+        GP_TRY(sample_blocks_enqueue(h, F, gd, twoc, G, M, w->vz + (int64_t)t * M, Z + (int64_t)t * S * zw, S, noiseless,
                                      jitter_s, mean_out ? w->vmom + (int64_t)t * M : nullptr, w->vH + (int64_t)t * S * M,
                                      w->vth + t, 0.0, t == 0));
     { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
@@ -2992,15 +3129,15 @@ static int sample_border_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const do
 }
 
 // the grid of a pathwise or block draw from its shape and reflected axes; M = its points (0: a bad argument)
-static int64_t pw_grid(const gpimhip_model_t* m, const int32_t* shape, int32_t mask, PwGrid* gd) {
-    gd->d = m->dim;
+static int64_t pw_grid(int dim, const int32_t* shape, int32_t mask, PwGrid* gd) {
+    gd->d = dim;
     gd->mask = mask;
     int64_t M = 1;
     for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
-        gd->n[k] = k < m->dim ? shape[k] : 1;
+        gd->n[k] = k < dim ? shape[k] : 1;
         if (gd->n[k] < 1) return 0;
         const bool refl = (mask >> k) & 1;
-        if (refl && (k >= m->dim || gd->n[k] < 2)) return 0;
+        if (refl && (k >= dim || gd->n[k] < 2)) return 0;
         gd->f[k] = refl ? (gd->n[k] + 1) / 2 : gd->n[k];
         M *= gd->n[k];
         if (M > ((int64_t)1 << 31)) return 0;
@@ -3022,13 +3159,14 @@ int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m, const doub
         return GPIMHIP_E_BADARG;
     }
     PwGrid gd;
-    const int64_t M = pw_grid(m, shape, mask, &gd);
+    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
     if (M < 1) return GPIMHIP_E_BADARG;
     if (!mask || (mask >> m->dim)) {
         gpim_set_error("gpimhip_sample_blocks: needs at least one reflected axis of the grid");
         return GPIMHIP_E_BADARG;
     }
-    return sample_blocks_impl(h, m, gd, twoc, G, M, y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+    return sample_blocks_impl(h, stationary_family(m, u), gd, twoc, G, M, y, Z, S, noiseless ? 1 : 0, jitter, m->jitter, mean_out,
+                              samples_out);
 }
 
 int gpimhip_sample_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
@@ -3061,7 +3199,7 @@ int gpimhip_sample_vgp_blocks(gpimhip_handle h, const gpimhip_model_t* m, const 
         return GPIMHIP_E_BADARG;
     }
     PwGrid gd;
-    const int64_t M = pw_grid(m, shape, mask, &gd);
+    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
     if (M < 1) return GPIMHIP_E_BADARG;
     if (!mask || (mask >> m->dim)) {
         gpim_set_error("gpimhip_sample_vgp_blocks: needs at least one reflected axis of the grid");
@@ -3095,7 +3233,7 @@ int gpimhip_sample_border(gpimhip_handle h, const gpimhip_model_t* m, const doub
         return GPIMHIP_E_BADARG;
     }
     PwGrid gd;
-    const int64_t M = pw_grid(m, shape, mask, &gd);
+    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
     int64_t Nq = M < 1 ? 0 : 1;
     for (int k = 0; k < GPIMHIP_MAX_DIM && M >= 1; ++k) Nq *= gd.f[k];
     if (M < 1 || mask != h->refl.mask || (mask >> m->dim) || B != (1 << __builtin_popcount(mask)) || Nq != N ||
@@ -3121,13 +3259,14 @@ int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const do
         return GPIMHIP_E_BADARG;
     }
     PwGrid gd;
-    const int64_t M = pw_grid(m, shape, mask, &gd);
+    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
     if (M < 1) return GPIMHIP_E_BADARG;
     if (!mask || (mask >> m->dim)) {
         gpim_set_error("gpimhip_sample_pathwise: needs at least one reflected axis of the grid");
         return GPIMHIP_E_BADARG;
     }
-    return sample_pathwise_impl(h, m, gd, twoc, G, M, idx, y, N, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
+    return sample_pathwise_impl(h, stationary_family(m, u), gd, twoc, G, M, idx, y, N, Z, S, noiseless ? 1 : 0, jitter, mean_out,
+                                samples_out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3432,7 +3571,49 @@ int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m, const doubl
         gpim_set_error("gpimhip_sample_exact: not available in reflection mode (the dense double-precision engine only)");
         return GPIMHIP_E_BADARG;
     }
-    return sample_impl(h, m, X, y, N, u, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
+    return sample_impl(h, stationary_family(m, u), X, y, N, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
+}
+
+// ---- the same three draws for the spectral-mixture model: the drivers above with sm_family.  sm_check
+// refuses a handle in reflection mode, as the entries above do.
+int gpimhip_sample_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N, const double* u,
+                      const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless, double jitter,
+                      double* mean_out, double* var_out, double* samples_out) {
+    GP_TRY(sm_check(h, sm, X, N));
+    if (!y || !u || !Xs || !Z || !samples_out || M < 1 || S < 1 || !(jitter >= 0.0)) return GPIMHIP_E_BADARG;
+    return sample_impl(h, sm_family(h, sm, u), X, y, N, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
+}
+
+int gpimhip_sample_sm_pathwise(gpimhip_handle h, const gpimhip_sm_t* sm, const double* G, const int32_t* shape, int32_t mask,
+                               const double* twoc, const int64_t* idx, const double* y, int64_t N, const double* u,
+                               const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
+                               double* samples_out) {
+    GP_TRY(sm_check(h, sm, G, N));
+    if (!shape || !twoc || !idx || !y || !u || !Z || !samples_out || S < 1 || S > 65535 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
+    PwGrid gd;
+    const int64_t M = pw_grid(sm->dim, shape, mask, &gd);
+    if (M < 1) return GPIMHIP_E_BADARG;
+    if (!mask || (mask >> sm->dim)) {
+        gpim_set_error("gpimhip_sample_sm_pathwise: needs at least one reflected axis of the grid");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_pathwise_impl(h, sm_family(h, sm, u), gd, twoc, G, M, idx, y, N, Z, S, noiseless ? 1 : 0, jitter, mean_out,
+                                samples_out);
+}
+
+int gpimhip_sample_sm_blocks(gpimhip_handle h, const gpimhip_sm_t* sm, const double* G, const int32_t* shape, int32_t mask,
+                             const double* twoc, const double* y, const double* u, const double* Z, int32_t S, int32_t noiseless,
+                             double jitter, double* mean_out, double* samples_out) {
+    GP_TRY(sm_check(h, sm, G, 1));
+    if (!shape || !twoc || !y || !u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
+    PwGrid gd;
+    const int64_t M = pw_grid(sm->dim, shape, mask, &gd);
+    if (M < 1) return GPIMHIP_E_BADARG;
+    if (!mask || (mask >> sm->dim)) {
+        gpim_set_error("gpimhip_sample_sm_blocks: needs at least one reflected axis of the grid");
+        return GPIMHIP_E_BADARG;
+    }
+    return sample_blocks_impl(h, sm_family(h, sm, u), gd, twoc, G, M, y, Z, S, noiseless ? 1 : 0, jitter, 0.0, mean_out, samples_out);
 }
 
 }  // extern "C"

@@ -781,8 +781,177 @@ __global__ void sm_addc_kernel(double* mean, int64_t n, const SmDev* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// posterior draws (api.hip: the spectral-mixture side of the draw drivers)
+// ------------------------------------------------------------------------------------------
+// the constrained parameters at u into st[0] and theta (one thread), and st[1] = st[0] with `other` as its diagonal term: the
+// covariance builders put st->noise on the diagonal, and a draw also builds K_b + d I (prior blocks) and the joint matrix
+// with no diagonal term (launch_sample_diag adds its two)
+__global__ void sm_params_kernel(gpimhip_sm_t sm, const double* __restrict__ u, SmDev* __restrict__ st,
+                                 ThetaDev* __restrict__ theta, double other) {
+    sm_setup_params(sm, sm_layout(sm), u, st, theta);
+    st[1] = st[0];
+    st[1].noise = other;
+}
+
+// out = y - c (the right-hand side of a model with a constant mean)
+__global__ void sm_centre_kernel(const double* __restrict__ y, int64_t n, const SmDev* __restrict__ st, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = y[j] - st->c;
+}
+
+// ------------------------------------------------------------------------------------------
+// sm_cross_apply_kernel: cross_apply_kernel (sample.hip) for this kernel -- K(G, X) applied to the solved right-hand sides
+// without ever being written:
+//   out[s][i] = c + mean_i + g[s][i] - sum_j k(G_i, X_j) Al[s][j]  (+ sqrt(noise) z_n unless noiseless),  mean_i = sum_j k Al[S][j]
+// ALU-bound on the fp64 vector pipe: M N Q exponentials.  One grid point per lane.  Neither a lane's registers nor the LDS
+// hold the phases of all Q <= 16 mixtures (128 doubles per point at d = 4), so the mixtures go by in chunks of SCA_QC: a lane
+// keeps its own phases of the chunk (2 d SCA_QC doubles), the workgroup stages SCA_TJ training rows with their phases of the
+// chunk and the SG + 1 entries of Al, and every lane reads them at the same address (a broadcast).  Per (chunk, row) the
+// chunk's share of the kernel value is completed in a register -- cosine of the difference from the phases as in
+// sm_kmat_kernel, no sincos here -- and then takes SG + 1 FMAs: with Q <= SCA_QC (the default Q = 4) that is the whole kernel
+// value, and SG + 1 FMAs per (mixture, row) would cost a quarter of an entry's ~35 instructions at SG = 8.  Each accumulator
+// runs over (chunk, j) in that order, by itself: a draw's bits do not depend on S, on s0, on the group it falls into or on
+// the other draws.
+// ------------------------------------------------------------------------------------------
+#define SCA_TJ 128
+
+template <int DIM, int SG>
+__global__ __launch_bounds__(256) void sm_cross_apply_kernel(const double* __restrict__ G, int64_t M, const double* __restrict__ csg,
+                                                             int64_t ldg, const double* __restrict__ Xt, int64_t N,
+                                                             const double* __restrict__ csx, int64_t ldx, int Q,
+                                                             const SmDev* __restrict__ st, const ThetaDev* __restrict__ th,
+                                                             const double* __restrict__ Al, int64_t npt, int S, int s0,
+                                                             const double* __restrict__ g, const double* __restrict__ Z,
+                                                             int64_t zw, int64_t zn_off, int noiseless,
+                                                             double* __restrict__ mean_out, double* __restrict__ out) {
+    constexpr int SCA_QC = DIM <= 2 ? 4 : 2;                    // mixtures per chunk: 2 d SCA_QC <= 16 phases in a lane's registers
+    __shared__ __attribute__((aligned(16))) double xs[SCA_TJ][DIM];
+    __shared__ __attribute__((aligned(16))) double as[SCA_TJ][SG + 1];
+    __shared__ __attribute__((aligned(16))) double ph[SCA_TJ][SCA_QC][2 * DIM];     // cos, sin per dimension
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    double a[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) a[d] = (i < M) ? G[i * DIM + d] : 0.0;
+    double acc[SG + 1];
+#pragma unroll
+    for (int c = 0; c <= SG; ++c) acc[c] = 0.0;
+    for (int q0 = 0; q0 < Q; q0 += SCA_QC) {
+        const int qn = Q - q0 < SCA_QC ? Q - q0 : SCA_QC;
+        double gp[SCA_QC][2 * DIM];
+#pragma unroll
+        for (int qq = 0; qq < SCA_QC; ++qq)
+#pragma unroll
+            for (int k = 0; k < 2 * DIM; ++k)
+                gp[qq][k] = (qq < qn && i < M) ? csg[((int64_t)(q0 + qq) * 2 * DIM + k) * ldg + i] : 0.0;
+        double wq[SCA_QC], kap[SCA_QC][DIM];                    // (wave-uniform: scalar registers)
+#pragma unroll
+        for (int qq = 0; qq < SCA_QC; ++qq) {
+            const int q = qq < qn ? q0 + qq : q0;
+            wq[qq] = st->w[q];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) kap[qq][d] = st->kap[q * GPIMHIP_MAX_DIM + d];
+        }
+        for (int64_t j0 = 0; j0 < N; j0 += SCA_TJ) {
+            __syncthreads();                                    // the previous tile has been read
+            {
+                const int r = tid & (SCA_TJ - 1), hf = tid >> 7;
+                const int64_t j = j0 + r;
+                if (hf == 0)
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) xs[r][d] = (j < N) ? Xt[j * DIM + d] : 0.0;
+#pragma unroll 1
+                for (int c = hf; c <= SG; c += 2) {             // the two halves of the workgroup take alternate columns
+                    const int64_t row = c == SG ? S : s0 + c;
+                    as[r][c] = (j < N && (c == SG || s0 + c < S)) ? Al[row * npt + j] : 0.0;
+                }
+#pragma unroll 1
+                for (int e = hf; e < SCA_QC * 2 * DIM; e += 2)  // and alternate phases of the chunk's mixtures
+                    (&ph[r][0][0])[e] = (e / (2 * DIM) < qn && j < N) ? csx[((int64_t)q0 * 2 * DIM + e) * ldx + j] : 0.0;
+            }
+            __syncthreads();
+            const int jn = (int)(N - j0 < SCA_TJ ? N - j0 : SCA_TJ);
+            for (int r = 0; r < jn; ++r) {
+                double t2[DIM];
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) {
+                    const double t = a[d] - xs[r][d];
+                    t2[d] = t * t;
+                }
+                double kv = 0.0;
+#pragma unroll
+                for (int qq = 0; qq < SCA_QC; ++qq) {
+                    if (qq >= qn) break;                        // (wave-uniform)
+                    double arg = 0.0, cp = 1.0;
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) {
+                        arg = fma(t2[d], kap[qq][d], arg);
+                        cp *= fma(gp[qq][2 * d], ph[r][qq][2 * d], gp[qq][2 * d + 1] * ph[r][qq][2 * d + 1]);
+                    }
+                    kv = fma(wq[qq], cp * kf_exp_neg(-arg), kv);
+                }
+#pragma unroll
+                for (int c = 0; c <= SG; ++c) acc[c] = fma(kv, as[r][c], acc[c]);
+            }
+        }
+    }
+    if (i >= M) return;
+    const double mu = st->c + acc[SG];
+    if (s0 == 0 && mean_out) mean_out[i] = mu;
+    const double sn = noiseless ? 0.0 : sqrt(th->noise);
+#pragma unroll
+    for (int c = 0; c < SG; ++c) {
+        if (s0 + c >= S) continue;
+        const int64_t o = (int64_t)(s0 + c) * M + i;
+        double v = mu + (g[o] - acc[c]);
+        if (!noiseless) v = fma(sn, Z[(int64_t)(s0 + c) * zw + zn_off + i], v);
+        out[o] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+int launch_sm_params(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, SmDev* st, ThetaDev* theta, double other) {
+    hipLaunchKernelGGL(sm_params_kernel, dim3(1), dim3(1), 0, h->stream, *sm, u, st, theta, other);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_centre(gpimhip_ctx* h, const double* y, int64_t n, const SmDev* st, double* out) {
+    hipLaunchKernelGGL(sm_centre_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, y, n, st, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+int launch_sm_cross_apply(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* G, int64_t M, const double* csg, int64_t ldg,
+                          const double* Xt, int64_t N, const double* csx, int64_t ldx, const SmDev* st, const ThetaDev* theta,
+                          const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw,
+                          int64_t zn_off, int noiseless, double* mean_out, double* out) {
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    const int rem = S - s0;
+#define SCA_LAUNCH(DIM, SG)                                                                                                 \
+    hipLaunchKernelGGL((sm_cross_apply_kernel<DIM, SG>), grid, block, 0, h->stream, G, M, csg, ldg, Xt, N, csx, ldx, sm->mixtures, \
+                       st, theta, Al, npt, S, s0, g, Z, zw, zn_off, noiseless, mean_out, out)
+#define SCA_DIM(DIM)                            \
+    do {                                        \
+        if (rem >= 5) SCA_LAUNCH(DIM, 8);       \
+        else if (rem >= 3) SCA_LAUNCH(DIM, 4);  \
+        else if (rem == 2) SCA_LAUNCH(DIM, 2);  \
+        else SCA_LAUNCH(DIM, 1);                \
+    } while (0)
+    switch (sm->dim) {
+        case 1: SCA_DIM(1); break;
+        case 2: SCA_DIM(2); break;
+        case 3: SCA_DIM(3); break;
+        default: SCA_DIM(4); break;
+    }
+#undef SCA_DIM
+#undef SCA_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
 int launch_sm_setup(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, const double* P, int64_t n, int64_t ldc,
                     double* cs, const double* y, double* ypad, SmDev* st, ThetaDev* theta) {
     hipLaunchKernelGGL(sm_setup_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, h->stream, *sm, u, P, n, ldc, cs, y,

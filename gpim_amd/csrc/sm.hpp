@@ -41,6 +41,18 @@ int launch_sm_finalize(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, const 
                        FinalizeIter fi, const double* ones = nullptr, int64_t n_total = 0, const double* border_scal = nullptr);
 int launch_sm_mean(gpimhip_ctx* h, const double* mtmp, int64_t n, const SmDev* st, double* mean_out);
 
+// posterior draws.  st: TWO SmDev -- st[0] the parameters at u (and theta: sum w, noise, diag_add =
+// noise), st[1] the same with `other` in place of the noise, for a build with another diagonal term (K_b + d I; none)
+int launch_sm_params(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u, SmDev* st, ThetaDev* theta, double other);
+// out = y - c
+int launch_sm_centre(gpimhip_ctx* h, const double* y, int64_t n, const SmDev* st, double* out);
+// launch_pw_cross_apply (sample.hpp) for this kernel; csg (leading dimension ldg >= M), csx (ldx >= N): the phases of G and of
+// the training rows Xt by launch_sm_setup; the constant mean is added to mean_out and to every draw
+int launch_sm_cross_apply(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* G, int64_t M, const double* csg, int64_t ldg,
+                          const double* Xt, int64_t N, const double* csx, int64_t ldx, const SmDev* st, const ThetaDev* theta,
+                          const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw,
+                          int64_t zn_off, int noiseless, double* mean_out, double* out);
+
 // reflection blocks (handle in reflection mode, h->nbatch = 2^r blocks on the fundamental domain):
 // phases of the centred coordinates, r_b = ys_b - c ones_b (ys, ones: B x n; ypad: B x ldc), the blocks K_s (out_bs apart)
 // or K_s(Xq, Z) * scale, the contraction with one record per (block, lower tile), and mean += c

@@ -24,6 +24,7 @@ Readings and deliberate differences, in one place:
     the predictive variance.  This engine is exact in both.
   * ``num_batches``, ``max_root`` / ``maxroot``, ``grid_points_ratio``, ``ski`` and ``sparse`` are accepted and ignored;
     ``precision='single'`` raises NotImplementedError.
+  * ``sample`` (joint posterior draws; the reference has none for this model) is this engine's: DESIGN.md section 24.
   * Solver (``rec.solver``; ``solver='dense' | 'reflection' | 'border'`` forces one): the kernel is stationary and even in
     every coordinate difference, so on a complete product grid with a symmetric axis the model runs as the 2^r reflection
     blocks of N / 2^r points ('reflection'), and on a grid with few missing pixels as the same blocks plus a border
@@ -36,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _sampling
 from . import gprutils
 from ._solvers import HostDriver, SpectralBlocks
 
@@ -126,8 +128,10 @@ class smreconstructor(HostDriver):
         self._u = torch.from_numpy(u).to(self._dev)
         S, self.solver = self._choose_solver(X, y, kwargs.get("solver"))
         self._solver = None if S is None else SpectralBlocks(S, border=self.solver == "border")
-        self._Xd = self.X.to(self._dev, _F64).contiguous()
-        self._yd = self.y.to(self._dev, _F64).contiguous()
+        self._Xd = self._to_device(self.X)
+        self._yd = self._to_device(self.y)
+        self._Xtest_d = self._to_device(self.Xtest) if self.Xtest is not None else None
+        self._draw_bytes = {}        # method -> the largest sample() call that has run (_sampling.reserve)
         self.iterations = iterations
         self.learning_rate = learning_rate
         self.scales, self.means, self.weights, self.noise_all = [], [], [], []
@@ -249,16 +253,21 @@ class smreconstructor(HostDriver):
                   'noise: {}'.format(np.around(self.noise_all[-1], 7)))
 
     # ------------------------------------------------------------------ prediction
+    def _to_device(self, t):
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(t)
+        return t.detach().to(self._dev, _F64).contiguous()
+
     def _new_test_grid(self, Xtest):
         self.fulldims = (self.X.shape[0],) if Xtest is None else Xtest.shape[1:]
+        self._Xtest_d = self._Xd if Xtest is None else self._to_device(self.Xtest)
 
     def _posterior(self):
-        Xs = self.Xtest.to(self._dev, _F64).contiguous()
+        Xs = self._Xtest_d              # (Reflection.predict_grid: the training grid itself takes the mirrored-variance path)
         M = Xs.shape[0]
         mean = torch.empty(M, dtype=_F64, device=self._dev)
         var = torch.empty(M, dtype=_F64, device=self._dev)
         if self._solver is not None:
-            self._Xtest_d = Xs          # (Reflection.predict_grid: the training grid itself takes the mirrored-variance path)
             _lib.check(self._solver.predict_grid(self, mean, var))
             return mean, var
         _lib.check(self._handle.lib.gpimhip_predict_sm(
@@ -269,3 +278,62 @@ class smreconstructor(HostDriver):
     def predict(self, Xtest=None, **kwargs):
         """Exact predictive mean and standard deviation of likelihood(model(Xtest)) (noise included), shape fulldims."""
         return self._predict_host(Xtest, kwargs, self._posterior)[:2]
+
+    # ------------------------------------------------------------------ joint posterior draws (_sampling.py)
+    _SAMPLE_BUILT = ("skreconstructor(kernel='Spectral').sample: method=%r is not built for the spectral-mixture model; built "
+                     "are 'joint' (any finite test rows), 'pathwise' (a complete product test grid with a symmetric axis "
+                     "that holds every training row) and 'blocks' (an observation on every point of that grid)")
+
+    def _draw_z(self, n_samples, W, seed=None):
+        g = None if seed is None else torch.Generator(self._dev).manual_seed(int(seed))
+        return torch.randn((n_samples, W), dtype=_F64, device=self._dev, generator=g)
+
+    def _draw_head(self):
+        """The leading arguments of the draw entries.  They run outside reflection mode: the block solvers hold that mode
+        only inside ``Reflection._mode``, and a draw depends on the observed rows and u alone."""
+        return self._handle.h, ctypes.byref(self._sstruct)
+
+    def _grid_args(self, P):
+        d = self._Xd.shape[1]
+        return (ctypes.c_int32 * d)(*[int(n) for n in P["shape"]]), int(P["mask"]), (ctypes.c_double * 4)(*P["twoc"])
+
+    def _draw_joint(self, Xs, z, noiseless, jitter, mean, var, out):
+        return self._handle.lib.gpimhip_sample_sm(*self._draw_head(), _lib.ptr(self._Xd), _lib.ptr(self._yd), self._Xd.shape[0],
+                                                  _lib.ptr(self._u), _lib.ptr(Xs), Xs.shape[0], _lib.ptr(z), z.shape[0],
+                                                  int(bool(noiseless)), float(jitter), _lib.ptr(mean), _lib.ptr(var),
+                                                  _lib.ptr(out))
+
+    def _draw_pathwise(self, Xs, P, idx, z, noiseless, jitter, mean, out):
+        return self._handle.lib.gpimhip_sample_sm_pathwise(*self._draw_head(), _lib.ptr(Xs), *self._grid_args(P),
+                                                           ctypes.c_void_p(idx.data_ptr()), _lib.ptr(self._yd),
+                                                           self._Xd.shape[0], _lib.ptr(self._u), _lib.ptr(z), z.shape[0],
+                                                           int(bool(noiseless)), float(jitter), _lib.ptr(mean), _lib.ptr(out))
+
+    def _draw_blocks(self, Xs, P, z, noiseless, jitter, mean, out):
+        y = self._yd
+        if P["idx_d"] is not None:      # the observations in grid order
+            y = torch.empty_like(self._yd)
+            y[P["idx_d"]] = self._yd
+        return self._handle.lib.gpimhip_sample_sm_blocks(*self._draw_head(), _lib.ptr(Xs), *self._grid_args(P), _lib.ptr(y),
+                                                         _lib.ptr(self._u), _lib.ptr(z), z.shape[0], int(bool(noiseless)),
+                                                         float(jitter), _lib.ptr(mean), _lib.ptr(out))
+
+    def sample(self, n_samples=1, Xtest=None, noiseless=False, seed=None, z=None, jitter=None, method='joint'):
+        """Joint draws from the posterior on the test grid: ndarray of shape ``(n_samples, *grid shape)``, each slice one
+        plausible reconstruction.  Meaning, the layout of ``z`` and the seeding are those of ``reconstructor.sample``; the
+        constant mean is part of every draw.  A method is open to every ``rec.solver`` (the posterior depends on the
+        observed rows and the parameters only) and gated by the data:
+
+        ``'joint'``: any finite test rows; one factorisation of order N + M; ``z`` is ``(n_samples, M)``; ``jitter >= 0``.
+        ``'pathwise'`` (Matheron's rule): a complete product test grid with a symmetric axis that holds every training row
+        -- the completed image of a model with missing pixels -- at two factorisations of order M / 2^r and N; ``z`` is
+        ``(n_samples, M + N)`` if noiseless, else ``(n_samples, 2 M + N)``, split ``[z_p | z_e | z_n]``.
+        ``'blocks'``: an observation on every point of that grid; 2 x 2^r factorisations of order M / 2^r; ``z`` is
+        ``(n_samples, 2 M)`` if noiseless, else ``(n_samples, 3 M)``.
+        ``jitter`` defaults to 1e-5; the model has no jitter of its own, so 0 < jitter <= noise for ``'pathwise'`` and
+        ``'blocks'``.  ``'border'``, ``'kron'`` and ``'columns'`` are not built for this model (NotImplementedError)."""
+        if method in ("border", "kron", "columns"):
+            raise NotImplementedError(self._SAMPLE_BUILT % (method,))
+        if method not in _sampling.SPECTRAL_METHODS:
+            raise ValueError("method must be 'joint', 'pathwise' or 'blocks'; got %r" % (method,))
+        return _sampling.draw(self, method, n_samples, Xtest, noiseless, seed, z, jitter, _sampling.SPECTRAL_METHODS)

@@ -378,6 +378,34 @@ int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, co
                    double lr, int32_t T, double* hist_out, double* loss_out);
 int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
                        const double* u, const double* Xs, int64_t M, double* mean_out, double* var_out);
+/* Posterior draws of this model: gpimhip_sample_exact, gpimhip_sample_pathwise and gpimhip_sample_blocks
+ * with the spectral-mixture covariance and its constant mean.  Arguments, the layout of Z, workspaces and error rules are
+ * those of the three entries above with `sm` in place of the model struct; what differs:
+ *   - the right-hand sides are y - c, and c is added to mean_out and to every draw;
+ *   - the training diagonal is the model's noise alone (it has no jitter of its own), so s = noise: jitter >= 0 for
+ *     gpimhip_sample_sm, 0 < jitter <= noise (the caller's to check: the noise lives on the device) for the other two;
+ *   - var_out of gpimhip_sample_sm is gpimhip_predict_sm's (noise included, jitter excluded).
+ * The entries depend on the observed rows and u only: they serve a model whose training ran on reflection blocks as well,
+ * called outside reflection mode (a handle in reflection mode -> GPIMHIP_E_BADARG). */
+int gpimhip_sample_sm(gpimhip_handle h, const gpimhip_sm_t* sm,
+                      const double* X, const double* y, int64_t N, const double* u,
+                      const double* Xs, int64_t M,
+                      const double* Z, int32_t S,
+                      int32_t noiseless, double jitter,
+                      double* mean_out, double* var_out,
+                      double* samples_out);
+int gpimhip_sample_sm_pathwise(gpimhip_handle h, const gpimhip_sm_t* sm,
+                               const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                               const int64_t* idx, const double* y, int64_t N, const double* u,
+                               const double* Z, int32_t S,
+                               int32_t noiseless, double jitter,
+                               double* mean_out, double* samples_out);
+int gpimhip_sample_sm_blocks(gpimhip_handle h, const gpimhip_sm_t* sm,
+                             const double* G, const int32_t* shape, int32_t mask, const double* twoc,
+                             const double* y, const double* u,
+                             const double* Z, int32_t S,
+                             int32_t noiseless, double jitter,
+                             double* mean_out, double* samples_out);
 /* The same model on the reflection blocks of a grid: the handle is in reflection mode (gpimhip_set_reflection; with
  * gpimhip_set_border for an incomplete grid), X the N points of the fundamental domain, B = 2^r the blocks of the r reflected
  * axes, ys (B x N) the targets and ones (B x N) the constant 1 (with a border: the indicator of the observed points) in the
@@ -834,6 +862,8 @@ int gpimhip_gemm_rect_tile_host(int32_t rect_rows, int32_t rect_cols, int32_t p0
  *        2 = gathers and the basis change U^T, 1 = the vector solves, 3 = cross_apply_kernel and its epilogue.
  * gpimhip_sample_blocks: 4 = covariance builds (2 x 2^r), 0 = their factorisations, 5 = the sweeps L_b z_p, 2 = gathers and the
  *        basis changes U and U^T, 1 = the multi-column solves, 3 = right-hand sides, combination and epilogue.
+ * gpimhip_sample_sm / _sm_pathwise / _sm_blocks: the stages of gpimhip_sample_exact / _pathwise / _blocks (the phases belong
+ *        to the covariance builds and to the cross apply, y - c and + c to the stage they sit in).
  * gpimhip_sample_border: 4 = covariance builds of the 2^r prior blocks, 0 = factorisations (prior blocks, model blocks, S,
  *        with the inverses the launches host), 5 = the sweeps L_b z_p, 2 = gathers and basis changes, 1 = the multi-column
  *        sweeps through L_b^-1 (and the rest of the triangular inverses), 6 = those two sweeps alone (one interval per group
