@@ -1,5 +1,6 @@
 // api.hip -- host side of libgpimhip: workspace, launch plans, blocked-algorithm drivers and the
-// extern "C" entry points declared in include/gpimhip.h.
+// extern "C" entry points declared in include/gpimhip.h.  The posterior draws (gpimhip_sample_*, but gpimhip_sample_kron of
+// kron.hip) have their drivers and entries in draws.hip.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -21,11 +22,10 @@ void gpim_set_error(const std::string& s) { g_err = s; }
 // XCD dealing chunk for lists sorted by decreasing cost: 64-tile chunks keep neighbouring tiles (shared operand
 // panels) on one XCD's L2, but a list of a few hundred tiles dealt 64 at a time puts all the longest tiles on
 // XCD 0 (N = 4206: K^-1 product 0.92 -> 0.72 ms with single-tile dealing); grow the chunk with the list.
-static int deal_chunk(int ntiles = 1 << 30) { return std::max(1, std::min(64, ntiles / 512)); }
+int deal_chunk(int ntiles) { return std::max(1, std::min(64, ntiles / 512)); }
 // "large N": from 12 outer panels (6144 unknowns) on an iteration is enqueued launch by launch on the caller's stream
 // (below: one captured iteration is replayed; its ~100 launches are then one host call)
 #define EAGER_MIN_PANELS 12
-#define OUTER_W 4    // outer Cholesky panel = 4 x 128 columns
 
 // ------------------------------------------------------------------------------------------
 // workspace
@@ -49,7 +49,7 @@ static void ws_release_matrix(gpimhip_ctx* h) {
 // matrices == false: only what the diagonal-block kernels and the launch plan need (dinv, log-det partials,
 // theta, Adam state) -- the distributed factorisation keeps its share of the matrix in caller-owned storage
 // and never needs the three np x np buffers (3 x 32 GiB at N = 65536).
-static int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices = true) {
+int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices) {
     const int64_t np = pad_to(std::max<int64_t>(N, 1), NB);
     const int64_t ld = np + ((padded && np >= 1024) ? (h->fp32 ? 32 : 16) : 0);      // one extra 128-byte line per row
     if (np == h->np && B == h->ws_batch && ld == h->ld && (h->A != nullptr || !matrices)) return GPIMHIP_OK;
@@ -271,8 +271,8 @@ int plan_ensure(gpimhip_ctx* h, int nb) {
 // ------------------------------------------------------------------------------------------
 // blocked drivers
 // ------------------------------------------------------------------------------------------
-static GemmArgs gemm_args(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
-                          double alpha, double beta, const TileDesc* tiles, int n, int64_t rows) {
+GemmArgs gemm_args(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                   double alpha, double beta, const TileDesc* tiles, int n, int64_t rows) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
@@ -378,8 +378,8 @@ int launch_lauum(gpimhip_ctx* h, const double* A, double* B, int64_t np, int64_t
 // section 11).  S = (A^-1)_mm has a handle of its own (`sub`: mp x mp workspace, factorisation plans, status word) that
 // enqueues on the model handle's stream, so the factorisation of S is the engine's own and rides in the captured iteration.
 // ------------------------------------------------------------------------------------------
-static BorderWs* bws(const gpimhip_ctx* h) { return (BorderWs*)h->border; }
-static bool border_on(const gpimhip_ctx* h) { return h->refl.mask && h->border && bws(h)->M > 0; }
+BorderWs* bws(const gpimhip_ctx* h) { return (BorderWs*)h->border; }
+bool border_on(const gpimhip_ctx* h) { return h->refl.mask && h->border && bws(h)->M > 0; }
 
 static void border_free_bufs(gpimhip_ctx* h, BorderWs* w) {
     dev_release(h, w->C, w->Y, w->tv, w->scal, w->uo, w->tiles_y, w->tiles_upd, w->R, w->rsq);
@@ -710,8 +710,6 @@ int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<
 static void vgp_release(gpimhip_ctx* h);
 static void pkron_release(gpimhip_ctx* h);
 static void sm_release(gpimhip_ctx* h);
-static void sample_release(gpimhip_ctx* h);
-static int64_t sample_bytes(const gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -984,8 +982,9 @@ static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
 
 // The model's state at u, what a prediction and a draw through the border start from: theta, L^-1 (h->A), alpha and, with a
 // border, the blocks' inverses (h->B), S, L_S^-1, C_b, Y_b and the corrected alpha
-static int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
-                            int B, const double* u) {
+// (C++ linkage: declared in common.hpp for draws.hip; not part of the C ABI this block defines)
+extern "C++" int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
+                                  int64_t N, int B, const double* u) {
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = B;
     GP_TRY(ws_ensure_padded(h, N));
@@ -1688,8 +1687,7 @@ static int vgp_ws(gpimhip_ctx* h, int nprob, int T, int64_t M, VgpWs** out) {
 }
 // the problems per task: 2^r in reflection mode (r = the reflected axes), else 1
 static int vgp_nrep(const gpimhip_ctx* h) { return h->refl.mask ? 1 << __builtin_popcount(h->refl.mask) : 1; }
-static int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
-                     int64_t N) {
+int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y, int64_t N) {
     if (!h || !m || !vg || !X || !Y || N < 1) return GPIMHIP_E_BADARG;
     FP64_ONLY(h);
     GP_TRY(check_model(m));
@@ -1815,23 +1813,6 @@ int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhi
 // 22): a grid whose missing points are whole columns.  J = prod n_i blocks s2 lambda_j K_s + sigma I of the N_s observed ragged
 // points run in lock-step through the batched engine (B = J, shared X_s); the complete axes are a KronAxes set of kron.hip.
 // ------------------------------------------------------------------------------------------
-struct PkronWs {
-    KronAxes ax;                                        // the complete axes: K_i, E_i, Q_i, lambda_i, Mm_i, mdiag_i
-    DevBuf<ThetaDev> th3;           // PK_TH_MODEL, PK_TH_AXES, PK_TH_UNIT
-    DevBuf<double> lamj;            // J: lambda_j
-    DevBuf<double> yt;              // 2 x N_s J: the mode products of the projection
-    DevBuf<double> Ks;              // np x ld: K_s at variance 1
-    DevBuf<double> Bp;              // Jp x np: beta, zero on the padding (Jp = J padded to 128)
-    DevBuf<double> W;               // Jp x np: K_s B
-    DevBuf<double> Z;               // dc x J x np: W x_i Mm_i
-    DevBuf<double> bsum;            // J x PK_SUMS
-    // prediction (chunks of mc ragged test rows)
-    DevBuf<double> colpart;         // J x nb x mc
-    DevBuf<double> G;               // Jp x mc: K*_s B
-    DevBuf<double> Q;               // J x mc: k*^T M_j k*
-    DevBuf<double> pp;              // 4 x pmax x mc: the mode products of mean and variance
-    DevBuf<double> cross;           // 2 x sum m_i n_i: K*_i and K*_i Q_i
-};
 static void pkron_release(gpimhip_ctx* h) {
     PkronWs* w = (PkronWs*)h->pkron;
     if (!w) return;
@@ -1844,8 +1825,8 @@ static int pkron_bad(const char* what) {
     gpim_set_error(std::string("dense-by-Kronecker blocks: ") + what);
     return GPIMHIP_E_BADARG;
 }
-static int pkron_check(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
-                       const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, PkronMap* mp) {
+int pkron_check(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
+                const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, PkronMap* mp) {
     if (!h || !m || !Xs || !n_c || !axes_c || !Y || Ns < 1) return GPIMHIP_E_BADARG;
     FP64_ONLY(h);
     GP_TRY(check_model(m));
@@ -1871,7 +1852,7 @@ static int pkron_check(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X
     mp->J = (int)J;
     return GPIMHIP_OK;
 }
-static int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, const double* axes_c, int64_t Ns, PkronWs** out) {
+int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, const double* axes_c, int64_t Ns, PkronWs** out) {
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = mp.J;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
@@ -1901,7 +1882,7 @@ static int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, c
     return GPIMHIP_OK;
 }
 // the blocks' sub-model: the p ragged columns of X_s (the blocks' theta carry their lengthscales)
-static gpimhip_model_t pkron_submodel(const gpimhip_model_t* m, int p) {
+gpimhip_model_t pkron_submodel(const gpimhip_model_t* m, int p) {
     gpimhip_model_t ms = *m;
     ms.dim = p;
     ms.n_ls = p;
@@ -1909,16 +1890,13 @@ static gpimhip_model_t pkron_submodel(const gpimhip_model_t* m, int p) {
 }
 // C (Jp x cols) = B (Jp x np: beta, one block per row) x R (np x cols, row stride ldr): one rectangle launch of the tile
 // engine on a single problem
-static int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, const double* R, int64_t ldr, int64_t cols, double* C,
-                            int64_t ldc);
-static int pkron_times_b(gpimhip_ctx* h, const PkronWs* w, int J, const double* R, int64_t ldr, int64_t cols, double* C,
-                         int64_t ldc) {
+int pkron_times_b(gpimhip_ctx* h, const PkronWs* w, int J, const double* R, int64_t ldr, int64_t cols, double* C, int64_t ldc) {
     return pkron_rows_times(h, w->Bp, pad_to(J, NB), R, ldr, cols, C, ldc);
 }
 // the same for any left operand Bm of `rows` rows (a multiple of 128) of np entries each: the draws' solutions stacked
 // (gpimhip_sample_pkron)
-static int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, const double* R, int64_t ldr, int64_t cols, double* C,
-                            int64_t ldc) {
+int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, const double* R, int64_t ldr, int64_t cols, double* C,
+                     int64_t ldc) {
     const int64_t np = h->np;
     GemmArgs g = gemm_args(Bm, np, R, ldr, C, ldc, 1.0, 0.0, nullptr, 0, 0);
     g.rect_rows = (int)(rows / NB);
@@ -1932,8 +1910,8 @@ static int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, cons
 }
 // theta, the complete axes' decomposition, the blocks' theta, y~ = Y Q in the padded right-hand sides, and the blocks'
 // K, L, L^-1, z, beta (steps 1 - 4 of an iteration without the inverse)
-static int pkron_factor(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_model_t* ms, const PkronMap& mp, PkronWs* w,
-                        const double* Xs, const double* Y, int64_t Ns, const double* u, bool grad) {
+int pkron_factor(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_model_t* ms, const PkronMap& mp, PkronWs* w,
+                 const double* Xs, const double* Y, int64_t Ns, const double* u, bool grad) {
     const KronDev& dv = w->ax.dev;
     GP_TRY(launch_pkron_setup(h, m, mp, u, w->th3));
     GP_TRY(kron_eig_axes(h, w->ax, w->th3 + PK_TH_AXES));
@@ -1975,6 +1953,54 @@ static int pkron_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& 
     return launch_pkron_finalize(h, m, mp, dv, Ns * (int64_t)J, w->bsum, w->th3, u, do_adam, loss_out, grad_out, fi);
 }
 
+// ---- what a prediction and a draw (draws.hip: gpimhip_sample_pkron) share on the test side (pkron.hpp)
+bool pkron_test_grid(const PkronMap& mp, const int32_t* n_test_c, PkronTest* out) {
+    *out = PkronTest{1, 0, 1};
+    int64_t cur = mp.J;
+    for (int i = 0; i < mp.dc; ++i) {
+        if (n_test_c[i] < 1) return false;
+        out->Mc *= n_test_c[i];
+        out->sum_mn += (int64_t)n_test_c[i] * mp.nc[i];
+        cur = cur / mp.nc[i] * n_test_c[i];
+        out->pmax = std::max(out->pmax, cur);
+    }
+    return true;
+}
+int64_t pkron_chunk(int64_t Ms, int J, int nb) {
+    return std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
+}
+int pkron_cross_factors(gpimhip_ctx* h, PkronWs* w, const PkronMap& mp, const int32_t* n_test_c, const double* axes_test_c,
+                        int64_t sum_mn, const double** bmat) {
+    const KronDev& dv = w->ax.dev;
+    int toff = 0;
+    int64_t ko = 0;
+    for (int i = 0; i < mp.dc; ++i) {
+        double* Kc = w->cross + ko;
+        double* Bc = w->cross + sum_mn + ko;
+        GP_TRY(kron_cross(h, dv, w->th3 + PK_TH_AXES, axes_test_c, toff, n_test_c[i], i, Kc));
+        GP_TRY(modeprod(h, Kc, Bc, dv.Qt + dv.moff[i], mp.nc[i], mp.nc[i], mp.nc[i], 0, 0, n_test_c[i], 1));
+        bmat[i] = Bc;
+        toff += n_test_c[i];
+        ko += (int64_t)n_test_c[i] * mp.nc[i];
+    }
+    return GPIMHIP_OK;
+}
+int pkron_mode_chain(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_test_c, const double* const* bmat, const double* src,
+                     double* bufa, double* bufb, int64_t lead, int64_t mc, int square, const double** out) {
+    const double* cur = src;
+    double* dst = bufa;
+    for (int i = 0; i < mp.dc; ++i) {
+        int64_t pre = lead, post = mc;
+        for (int k = 0; k < i; ++k) pre *= n_test_c[k];
+        for (int k = i + 1; k < mp.dc; ++k) post *= mp.nc[k];
+        GP_TRY(modeprod(h, cur, dst, bmat[i], n_test_c[i], mp.nc[i], mp.nc[i], 0, square, pre, post));
+        cur = dst;
+        dst = (dst == bufa) ? bufb : bufa;
+    }
+    *out = cur;
+    return GPIMHIP_OK;
+}
+
 extern "C" {
 
 int gpimhip_pkron_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
@@ -2012,26 +2038,16 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
     PkronMap mp;
     GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
     if (!u || !Xs_test || Ms < 1 || !n_test_c || !axes_test_c || !mean_out || !var_out) return GPIMHIP_E_BADARG;
-    int64_t Mc = 1, sum_mn = 0, pmax = 1;
-    {
-        int64_t cur = mp.J;
-        for (int i = 0; i < dc; ++i) {
-            if (n_test_c[i] < 1) return GPIMHIP_E_BADARG;
-            Mc *= n_test_c[i];
-            sum_mn += (int64_t)n_test_c[i] * n_c[i];
-            cur = cur / n_c[i] * n_test_c[i];
-            pmax = std::max(pmax, cur);
-        }
-    }
+    PkronTest tg;
+    if (!pkron_test_grid(mp, n_test_c, &tg)) return GPIMHIP_E_BADARG;
+    const int64_t Mc = tg.Mc, sum_mn = tg.sum_mn, pmax = tg.pmax;
     PkronWs* w = nullptr;
     GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
     const int64_t np = h->np;
     const int J = mp.J, nb = (int)(np / NB);
     const int64_t Jp = pad_to(J, NB);
-    const KronDev& dv = w->ax.dev;
     const gpimhip_model_t ms = pkron_submodel(m, p);
-    // chunks of ragged test rows: the blocks' partial column sums (J x nb x mc doubles) stay <= ~0.5 GiB
-    const int64_t mc = std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
+    const int64_t mc = pkron_chunk(Ms, J, nb);
     {
         BatchScope one(h, 1);       // ONE K* slab, shared by the J blocks
         GP_TRY(ws_ensure_predict(h, np, mc));
@@ -2044,21 +2060,8 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
     GP_TRY(w->cross.grow(h, 2 * sum_mn));
     GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, false));
     GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
-    // per complete axis: K*_i and b_i = K*_i Q_i (eigen-coordinates straight to test points)
     const double* bmat[KMAXD];
-    {
-        int toff = 0;
-        int64_t ko = 0;
-        for (int i = 0; i < dc; ++i) {
-            double* Kc = w->cross + ko;
-            double* Bc = w->cross + sum_mn + ko;
-            GP_TRY(kron_cross(h, dv, w->th3 + PK_TH_AXES, axes_test_c, toff, n_test_c[i], i, Kc));
-            GP_TRY(modeprod(h, Kc, Bc, dv.Qt + dv.moff[i], n_c[i], n_c[i], n_c[i], 0, 0, n_test_c[i], 1));
-            bmat[i] = Bc;
-            toff += n_test_c[i];
-            ko += (int64_t)n_test_c[i] * n_c[i];
-        }
-    }
+    GP_TRY(pkron_cross_factors(h, w, mp, n_test_c, axes_test_c, sum_mn, bmat));
     for (int64_t m0 = 0; m0 < Ms; m0 += mc) {
         const int64_t cnt = std::min(mc, Ms - m0), cpad = pad_to(cnt, NB);
         {
@@ -2079,21 +2082,12 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
         { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
         GP_TRY(launch_pkron_qsum(h, J, nb, mc, cnt, w->colpart, w->Q));
         // mean = s2 G b^T, var = clamp(s2 - s2^2 Q (b o b)^T, 0) + noise: mode products over the (n_1, ..., n_dc, mc) tensors
-        const double* cur[2] = {w->G, w->Q};
+        const double* raw[2] = {w->G, w->Q};
         for (int v = 0; v < 2; ++v) {
             double* bufa = w->pp + (int64_t)(2 * v) * pmax * mc;
-            double* bufb = bufa + pmax * mc;
-            double* dst = bufa;
-            for (int i = 0; i < dc; ++i) {
-                int64_t pre = 1, post = mc;
-                for (int k = 0; k < i; ++k) pre *= n_test_c[k];
-                for (int k = i + 1; k < dc; ++k) post *= n_c[k];
-                GP_TRY(modeprod(h, cur[v], dst, bmat[i], n_test_c[i], n_c[i], n_c[i], 0, v, pre, post));
-                cur[v] = dst;
-                dst = (dst == bufa) ? bufb : bufa;
-            }
+            GP_TRY(pkron_mode_chain(h, mp, n_test_c, bmat, raw[v], bufa, bufa + pmax * mc, 1, mc, v, &raw[v]));
         }
-        GP_TRY(launch_pkron_post(h, w->th3, Mc, mc, m0, cnt, cur[0], cur[1], mean_out, var_out));
+        GP_TRY(launch_pkron_post(h, w->th3, Mc, mc, m0, cnt, raw[0], raw[1], mean_out, var_out));
     }
     return finish_and_check(h);
 }
@@ -2144,7 +2138,7 @@ static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t m
     return GPIMHIP_OK;
 }
 // B = 0: a dense entry point (no reflection mode); B > 0: the blocks of a handle in reflection mode
-static int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B = 0) {
+int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B) {
     if (!h || !sm || !X || N < 1) return GPIMHIP_E_BADARG;
     FP64_ONLY(h);
     if (sm->dim < 1 || sm->dim > GPIMHIP_MAX_DIM || sm->mixtures < 1 || sm->mixtures > GPIMHIP_SM_MAX_MIXTURES) {
@@ -2427,1193 +2421,6 @@ int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X
         GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
     return finish_and_check(h);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// joint posterior draws of the exact GP (sample.hip): one factorisation of the joint covariance of
-// [X; Xs].  The matrix belongs to this path: a Bayesian-optimisation step alternates training at order N with a draw at
-// order N + M, and sending the draw through ws_ensure would free and re-allocate A, B and Tm twice per step (two of the
-// three unused here).  `sub` is a handle of its own on the model handle's stream, as the border's: its workspace holds
-// what the step schedule needs (diagonal-block inverses, plans, status word, theta, O(order) vectors), no matrices.
-// J, the stacked coordinates and the vectors grow only when a larger order arrives.
-// ------------------------------------------------------------------------------------------
-struct SampleWs {
-    gpimhip_ctx* sub = nullptr;
-    DevBuf<double> J;               // padded (N + M)^2 joint covariance -> its factor
-    DevBuf<double> XX;              // [X; Xs]
-    DevBuf<double> vec;             // t (order) | piece (512) | mean (M): forward substitution, draws
-    // pathwise draws (sample_pathwise_impl): a context per matrix order (a call factors at both, and a context that changes
-    // its order rebuilds its launch plan), one block of the prior, the training matrix, the vectors
-    gpimhip_ctx* subp = nullptr;                    // order M / 2^r: the reflection blocks of the grid, one after the other
-    gpimhip_ctx* subt = nullptr;                    // order N: K + (noise + jitter) I
-    DevBuf<double> Pb;
-    DevBuf<double> Kt;
-    DevBuf<double> pw;
-    // multi-output draws (sample_vgp_impl / sample_vgp_blocks_impl): the state of the reduction, the T
-    // latent blocks' thetas, their targets z_t (T x N), draws H (T x S x M) and moments (2 x T x M: mean, variance)
-    DevBuf<VgpDev> vst;
-    DevBuf<ThetaDev> vth;
-    DevBuf<double> vz;
-    DevBuf<double> vH;
-    DevBuf<double> vmom;
-    // draws of the dense-by-Kronecker blocks (gpimhip_sample_pkron): one arena carved per call (the
-    // prior factor, zeta and H, the mode products' buffers, the blocks' right-hand sides, the stacked solutions, root rows,
-    // index maps, tile lists) and the union of the complete axes when the training axes do not serve; `sub` factors L_P
-    DevBuf<double> ck;
-    KronAxes ck_un;
-    // draws of the spectral-mixture model (sm_family): the two parameter sets of launch_sm_params, the
-    // phases of the dense rows ([X; Xs], or the training rows), of the fundamental domain and of the grid G, and y - c
-    DevBuf<SmDev> smst;
-    DevBuf<double> phx;
-    DevBuf<double> phq;
-    DevBuf<double> phg;
-    DevBuf<double> smy;
-};
-static SampleWs* sws(const gpimhip_ctx* h) { return (SampleWs*)h->sample; }
-static int64_t sample_bytes(const gpimhip_ctx* h) {
-    const SampleWs* w = sws(h);
-    if (!w) return 0;
-    return (w->sub ? w->sub->bytes : 0) + (w->subp ? w->subp->bytes : 0) + (w->subt ? w->subt->bytes : 0);
-}
-static void sample_release(gpimhip_ctx* h) {
-    SampleWs* w = sws(h);
-    if (!w) return;
-    dev_release(h, w->J, w->XX, w->vec, w->Pb, w->Kt, w->pw, w->vst, w->vth, w->vz, w->vH, w->vmom, w->ck, w->smst, w->phx, w->phq,
-                w->phg, w->smy);
-    kron_axes_free(h, w->ck_un);
-    if (w->sub) gpimhip_destroy(w->sub);
-    if (w->subp) gpimhip_destroy(w->subp);
-    if (w->subt) gpimhip_destroy(w->subt);
-    delete w;
-    h->sample = nullptr;
-}
-
-// ------------------------------------------------------------------------------------------
-// What the draw drivers below (sample_enqueue, sample_pathwise_impl, sample_blocks_enqueue) need of a kernel family.  The
-// vectors, the factorisations, the sweeps, the basis changes and the workspaces are shared; a family sets the parameters up,
-// builds a dense or a reflection-block covariance, and applies K(G, X) -- and, where its mean is a constant c, centres y and
-// shifts the results.  `ctx` is the context the launch runs on (its theta, its reflection state, its stream).
-//   params       ctx->theta at u (var, noise, diag_add = the model's diagonal term s); `other`: the call's second diagonal
-//                term (0 for the joint matrix, the draw's jitter d for the prior blocks), for a family that keeps it itself
-//   kmat         lower tiles of K(X, X) (+ s I if model_diag), identity padding up to np
-//   kmat_refl    block ctx->refl.pb_off of the grid's covariance on the fundamental domain, + s I if model_diag, else + the
-//                other term (the stationary kernels read either from ctx->theta->diag_add, which the drivers set)
-//   cross_apply  launch_pw_cross_apply (sample.hpp); Xt must be the rows of the latest kmat on ctx
-//   reserve      the family's own buffers for dense rows / a fundamental domain / a grid of these (padded) sizes and n_y targets
-//   centre       out = y - c;  shift: v += c   (null: a zero mean)
-// ------------------------------------------------------------------------------------------
-struct DrawFamily {
-    int dim = 0;
-    const gpimhip_model_t* m = nullptr;         // the stationary kernels of kfun.hpp
-    const gpimhip_sm_t* sm = nullptr;           // the spectral mixture
-    const double* u = nullptr;
-    int (*params)(const DrawFamily&, gpimhip_ctx* ctx, double other) = nullptr;
-    int (*kmat)(const DrawFamily&, gpimhip_ctx* ctx, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
-                int64_t np) = nullptr;
-    int (*kmat_refl)(const DrawFamily&, gpimhip_ctx* ctx, const double* Xq, int64_t Nq, bool model_diag, double* out, int64_t ld,
-                     int64_t np) = nullptr;
-    int (*cross_apply)(const DrawFamily&, gpimhip_ctx* ctx, const double* G, int64_t M, const double* Xt, int64_t N,
-                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
-                       int noiseless, double* mean_out, double* out) = nullptr;
-    int (*reserve)(const DrawFamily&, gpimhip_ctx* h, int64_t rows_x, int64_t rows_q, int64_t rows_g, int64_t n_y) = nullptr;
-    int (*centre)(const DrawFamily&, gpimhip_ctx* ctx, const double* y, int64_t n, double* out) = nullptr;
-    int (*shift)(const DrawFamily&, gpimhip_ctx* ctx, double* v, int64_t n) = nullptr;
-    SampleWs* w = nullptr;                      // where reserve's buffers live (the model handle's)
-};
-
-static DrawFamily stationary_family(const gpimhip_model_t* m, const double* u) {
-    DrawFamily F;
-    F.dim = m->dim;
-    F.m = m;
-    F.u = u;
-    F.params = [](const DrawFamily& F, gpimhip_ctx* c, double) { return launch_theta(c, F.m, F.u); };
-    F.kmat = [](const DrawFamily& F, gpimhip_ctx* c, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
-                int64_t np) {
-        return launch_kmat(c, F.m, X, N, nullptr, N, c->theta, 0.0, model_diag ? 1 : 0, out, ld, np, np, 1, 1, 0, 0, 0);
-    };
-    F.kmat_refl = [](const DrawFamily& F, gpimhip_ctx* c, const double* Xq, int64_t Nq, bool, double* out, int64_t ld,
-                     int64_t np) { return launch_kmat_refl(c, F.m, Xq, Nq, nullptr, Nq, c->theta, out, ld, np, np, 1, 0, 0, 0, 1.0); };
-    F.cross_apply = [](const DrawFamily& F, gpimhip_ctx* c, const double* G, int64_t M, const double* Xt, int64_t N,
-                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
-                       int noiseless, double* mean_out, double* out) {
-        return launch_pw_cross_apply(c, F.m, G, M, Xt, N, c->theta, Al, npt, S, s0, g, Z, zw, zn_off, noiseless, mean_out, out);
-    };
-    return F;
-}
-
-// The spectral mixture: the phases of a build's points are computed right before it (O(points Q d) next to the build's
-// O(points^2 Q d)); those of the dense rows stay in phx for cross_apply, which adds the phases of G once per call.
-static DrawFamily sm_family(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* u) {
-    if (!h->sample) h->sample = new SampleWs();
-    DrawFamily F;
-    F.dim = sm->dim;
-    F.sm = sm;
-    F.u = u;
-    F.w = sws(h);
-    F.reserve = [](const DrawFamily& F, gpimhip_ctx* h, int64_t rows_x, int64_t rows_q, int64_t rows_g, int64_t n_y) {
-        const int64_t per = 2 * (int64_t)F.sm->mixtures * F.sm->dim;
-        if (!F.w->smst) GP_TRY(F.w->smst.alloc(h, 2));
-        GP_TRY(F.w->phx.grow(h, per * rows_x));
-        GP_TRY(F.w->phq.grow(h, per * rows_q));
-        GP_TRY(F.w->phg.grow(h, per * rows_g));
-        return F.w->smy.grow(h, n_y);
-    };
-    F.params = [](const DrawFamily& F, gpimhip_ctx* c, double other) {
-        return launch_sm_params(c, F.sm, F.u, F.w->smst, c->theta, other);
-    };
-    F.kmat = [](const DrawFamily& F, gpimhip_ctx* c, const double* X, int64_t N, bool model_diag, double* out, int64_t ld,
-                int64_t np) {
-        GP_TRY(launch_sm_setup(c, F.sm, F.u, X, N, np, F.w->phx, nullptr, nullptr, nullptr, nullptr));
-        return launch_sm_kmat(c, F.sm, X, N, F.w->phx, np, nullptr, N, nullptr, np, F.w->smst + (model_diag ? 0 : 1), out, ld, np,
-                              np, 1, 1);
-    };
-    F.kmat_refl = [](const DrawFamily& F, gpimhip_ctx* c, const double* Xq, int64_t Nq, bool model_diag, double* out, int64_t ld,
-                     int64_t np) {
-        GP_TRY(launch_sm_setup_refl(c, F.sm, F.u, Xq, Nq, np, F.w->phq, nullptr, nullptr, nullptr, nullptr, nullptr));
-        return launch_sm_kmat_refl(c, F.sm, Xq, Nq, F.w->phq, np, nullptr, Nq, nullptr, np, F.w->smst + (model_diag ? 0 : 1), out,
-                                   ld, 0, np, np, 1, 1, 1.0);
-    };
-    F.cross_apply = [](const DrawFamily& F, gpimhip_ctx* c, const double* G, int64_t M, const double* Xt, int64_t N,
-                       const double* Al, int64_t npt, int S, int s0, const double* g, const double* Z, int64_t zw, int64_t zn_off,
-                       int noiseless, double* mean_out, double* out) {
-        const int64_t ldg = pad_to(M, NB);
-        if (s0 == 0) GP_TRY(launch_sm_setup(c, F.sm, F.u, G, M, ldg, F.w->phg, nullptr, nullptr, nullptr, nullptr));
-        return launch_sm_cross_apply(c, F.sm, G, M, F.w->phg, ldg, Xt, N, F.w->phx, npt, F.w->smst, c->theta, Al, npt, S, s0, g, Z,
-                                     zw, zn_off, noiseless, mean_out, out);
-    };
-    F.centre = [](const DrawFamily& F, gpimhip_ctx* c, const double* y, int64_t n, double* out) {
-        return launch_sm_centre(c, y, n, F.w->smst, out);
-    };
-    F.shift = [](const DrawFamily& F, gpimhip_ctx* c, double* v, int64_t n) { return launch_sm_addc(c, v, n, F.w->smst); };
-    return F;
-}
-// y - c in the family's buffer when its mean is a constant (reserve has sized it), else y itself
-static int centred(const DrawFamily& F, gpimhip_ctx* ctx, const double* y, int64_t n, const double** out) {
-    *out = y;
-    if (!F.centre) return GPIMHIP_OK;
-    GP_TRY(F.centre(F, ctx, y, n, F.w->smy));
-    *out = F.w->smy;
-    return GPIMHIP_OK;
-}
-
-// sub->z = L11^-1 y from the factor L of the joint matrix: block forward substitution over the block rows that hold
-// training points, a panel of four blocks at a time against the inverted diagonal blocks the step schedule left in dinv
-// (distops.hip).  The last of these block rows may hold test points too: their entries of z are never read.
-// t (order of the matrix): the running products L(rows, panels so far) z; piece: 512.
-static int sample_forward(gpimhip_ctx* sub, const double* L, int64_t ld, const double* y, int64_t N, double* t, double* piece) {
-    const int nbn = (int)((N + NB - 1) / NB);
-    GP_TRY(launch_pad_copy(sub, y, N, sub->ypad, sub->np));
-    HIP_TRY(hipMemsetAsync(t, 0, (size_t)sub->np * sizeof(double), sub->stream));
-    for (int g0 = 0; g0 < nbn; g0 += OUTER_W) {
-        const int nblk = std::min(OUTER_W, nbn - g0), wd = nblk * NB;
-        const int64_t r0 = (int64_t)g0 * NB;
-        const double* P = L + r0 * ld + r0;
-        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, sub->ypad + r0, t + r0, piece));
-        HIP_TRY(hipMemcpyAsync(sub->z + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
-        GP_TRY(launch_dist_rows_acc(sub, P + (int64_t)wd * ld, ld, (int64_t)nbn * NB - r0 - wd, wd, piece, t + r0 + wd));
-    }
-    return GPIMHIP_OK;
-}
-
-// Everything of one draw call but the closing synchronisation.  theta_src (optional, device): the hyper-parameters, copied
-// into the context's theta in place of the family's params -- a latent block of the multi-output model (variance
-// lambda_t, noise 1, diag_add 1: sample_vgp_impl); the family's u is not read then.  reset_info: clear the context's status word first
-// (a call of several blocks clears it once: the word keeps the first failure).
-static int sample_enqueue(gpimhip_ctx* h, const DrawFamily& F, const double* X, const double* y, int64_t N,
-                          const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
-                          double* var_out, double* samples_out, const ThetaDev* theta_src, bool reset_info) {
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* w = sws(h);
-    if (!w->sub) GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
-    gpimhip_ctx* sub = w->sub;
-    sub->stream = h->stream;
-    sub->nbatch = 1;
-    const int64_t NM = N + M, d = F.dim;
-    GP_TRY(ws_ensure_b(sub, NM, 1, 1, false));
-    const int64_t np = sub->np, ld = sub->ld;
-    GP_TRY(w->J.grow(h, np * ld));
-    GP_TRY(w->XX.grow(h, np * GPIMHIP_MAX_DIM));
-    GP_TRY(w->vec.grow(h, 2 * np + 4 * NB));
-    if (F.reserve) GP_TRY(F.reserve(F, h, np, 0, 0, N));
-    double *t = w->vec, *piece = t + np, *mean_ws = piece + 4 * NB;
-    if (reset_info) HIP_TRY(hipMemsetAsync(sub->info, 0, sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemcpyAsync(w->XX, X, (size_t)(N * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(w->XX + N * d, Xs, (size_t)(M * d) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    // J (lower tiles; identity padding at the end), the two diagonal terms, L
-    // (stage timers of the model handle: 4 covariance build, 0 factorisation, 1 forward substitution, 5 each sweep of the draws)
-    if (theta_src) HIP_TRY(hipMemcpyAsync(sub->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
-    else GP_TRY(F.params(F, sub, 0.0));
-    {
-        StageTimer tm(h, 4);
-        GP_TRY(F.kmat(F, sub, w->XX, NM, false, w->J, ld, np));
-        GP_TRY(launch_sample_diag(sub, w->J, ld, N, M, sub->theta, noiseless, jitter_s));
-    }
-    { StageTimer tm(h, 0); GP_TRY(launch_potrf(sub, w->J, np, ld, sub->info)); }
-    {
-        StageTimer tm(h, 1);
-        const double* yc;
-        GP_TRY(centred(F, sub, y, N, &yc));
-        GP_TRY(sample_forward(sub, w->J, ld, yc, N, t, piece));
-    }
-    for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
-        StageTimer tm(h, 5);
-        GP_TRY(launch_sample_draws(sub, w->J, ld, N, M, sub->z, Z, S, s0, sub->theta, noiseless, jitter_s, mean_ws, mean_out,
-                                   var_out, samples_out));
-    }
-    if (F.shift) {
-        StageTimer tm(h, 5);
-        if (mean_out) GP_TRY(F.shift(F, sub, mean_out, M));
-        GP_TRY(F.shift(F, sub, samples_out, (int64_t)S * M));
-    }
-    return GPIMHIP_OK;
-}
-static int sample_impl(gpimhip_ctx* h, const DrawFamily& F, const double* X, const double* y, int64_t N,
-                       const double* Xs, int64_t M, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
-                       double* var_out, double* samples_out) {
-    GP_TRY(sample_enqueue(h, F, X, y, N, Xs, M, Z, S, noiseless, jitter_s, mean_out, var_out, samples_out, nullptr, true));
-    return finish_and_check(sws(h)->sub);
-}
-
-// ------------------------------------------------------------------------------------------
-// pathwise draws: f_s = mean + g - (K_GX + d P)(K + s I)^-1 (g[idx] + sqrt(s - d) z_e), g a prior
-// draw on the complete grid G through its 2^r reflection blocks.  The prior factor is shared by the S draws of a call.
-// ------------------------------------------------------------------------------------------
-// a = (L L^T)^-1 r for one padded vector r (np): the panel-wise substitutions of the distributed model (distops.hip) against
-// the inverted diagonal blocks the step schedule left in sub->dinv.  zf, t: np; piece, work: 512.
-static int pathwise_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const double* r, double* a, double* zf, double* t,
-                          double* piece, double* work) {
-    const int64_t np = sub->np;
-    const int nb = (int)(np / NB);
-    HIP_TRY(hipMemsetAsync(t, 0, (size_t)np * sizeof(double), sub->stream));
-    for (int g0 = 0; g0 < nb; g0 += OUTER_W) {
-        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
-        const int64_t r0 = (int64_t)g0 * NB;
-        const double* P = L + r0 * ld + r0;
-        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, r + r0, t + r0, piece));
-        HIP_TRY(hipMemcpyAsync(zf + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
-        GP_TRY(launch_dist_rows_acc(sub, P + (int64_t)wd * ld, ld, np - r0 - wd, wd, piece, t + r0 + wd));
-    }
-    for (int g0 = ((nb - 1) / OUTER_W) * OUTER_W; g0 >= 0; g0 -= OUTER_W) {
-        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
-        const int64_t r0 = (int64_t)g0 * NB, below = np - r0 - wd;
-        const double* P = L + r0 * ld + r0;
-        if (below > 0) GP_TRY(launch_gemv_t(sub, P + (int64_t)wd * ld, ld, below, wd, a + r0 + wd, work, 0, 0, 0, 0));
-        else HIP_TRY(hipMemsetAsync(work, 0, (size_t)wd * sizeof(double), sub->stream));
-        GP_TRY(launch_dist_trsv(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 1, zf + r0, work, piece));
-        HIP_TRY(hipMemcpyAsync(a + r0, piece, (size_t)wd * sizeof(double), hipMemcpyDeviceToDevice, sub->stream));
-    }
-    return GPIMHIP_OK;
-}
-
-static int pathwise_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order) {
-    if (!*sub) GP_TRY(gpimhip_create(sub, h->device, h->stream));
-    (*sub)->stream = h->stream;
-    (*sub)->nbatch = 1;
-    return ws_ensure_b(*sub, order, 1, 1, false);
-}
-
-// (stage timers of the model handle: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p, 2 gathers and the
-// basis change U^T, 1 the vector solves, 3 cross_apply_kernel with its epilogue)
-static int sample_pathwise_impl(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
-                                int64_t M, const int64_t* idx, const double* y, int64_t N, const double* Z,
-                                int S, int noiseless, double jitter_s, double* mean_out, double* samples_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* w = sws(h);
-    int64_t Nq = 1;
-    for (int k = 0; k < gd.d; ++k) Nq *= gd.f[k];
-    const int B = 1 << __builtin_popcount(gd.mask);
-    GP_TRY(pathwise_sub(h, &w->subp, Nq));
-    GP_TRY(pathwise_sub(h, &w->subt, N));
-    gpimhip_ctx *sp = w->subp, *st = w->subt;
-    const int64_t npq = sp->np, ldq = sp->ld, npt = st->np, ldt = st->ld;
-    const int64_t zw = M + N + (noiseless ? 0 : M), SB = (int64_t)S * B;
-    GP_TRY(w->Pb.grow(h, npq * ldq));
-    GP_TRY(w->Kt.grow(h, npt * ldt));
-    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
-    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
-                  o_g = o_c + even(SB * Nq), o_xt = o_g + even((int64_t)S * M), o_r = o_xt + npt * GPIMHIP_MAX_DIM,
-                  o_al = o_r + (S + 1) * npt, o_zf = o_al + (S + 1) * npt, o_t = o_zf + npt, o_piece = o_t + npt,
-                  o_work = o_piece + 4 * NB, o_mws = o_work + 4 * NB, o_end = o_mws + npq;
-    GP_TRY(w->pw.grow(h, o_end));
-    if (F.reserve) GP_TRY(F.reserve(F, h, npt, npq, pad_to(M, NB), N));
-    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *Xt = w->pw + o_xt,
-           *R = w->pw + o_r, *Al = w->pw + o_al, *zf = w->pw + o_zf, *t = w->pw + o_t, *piece = w->pw + o_piece,
-           *work = w->pw + o_work, *mean_ws = w->pw + o_mws;
-    // one status word for both factorisations: the training context's
-    HIP_TRY(hipMemsetAsync(st->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(F.params(F, sp, jitter_s));
-    GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
-    GP_TRY(F.params(F, st, jitter_s));
-    {
-        StageTimer tm(h, 2);
-        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, idx, N, Xt));
-        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
-    }
-    // ---- the prior draw: block b of the grid's covariance, its factor, L_b z_b for every draw
-    sp->refl.mask = gd.mask;
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
-    sp->refl.n_total = M;
-    sp->refl.var_count = 0;
-    sp->refl.pb_stride = 1;
-    sp->refl.nblocks_total = B;
-    sp->refl.raw = 0;
-    for (int b = 0; b < B; ++b) {
-        sp->refl.pb_off = b;
-        sp->refl.wts = wts + (int64_t)b * Nq;
-        {
-            StageTimer tm(h, 4);
-            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, false, w->Pb, ldq, npq));
-        }
-        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, st->info)); }
-        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
-            StageTimer tm(h, 5);
-            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
-                                       nullptr, nullptr, C + (int64_t)b * S * Nq));
-        }
-    }
-    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, C, S, Nq, B, M, g)); }
-    // ---- the training side: K + (noise + jitter) I, its factor, alpha for the S draws and for y
-    {
-        StageTimer tm(h, 4);
-        GP_TRY(F.kmat(F, st, Xt, N, true, w->Kt, ldt, npt));
-    }
-    { StageTimer tm(h, 0); GP_TRY(launch_potrf(st, w->Kt, npt, ldt, st->info)); }
-    {
-        StageTimer tm(h, 1);
-        const double* yc;
-        GP_TRY(centred(F, st, y, N, &yc));
-        GP_TRY(launch_pw_rhs(st, g, M, idx, N, Z, zw, S, yc, st->theta, jitter_s, R, npt));
-        for (int v = 0; v <= S; ++v)
-            GP_TRY(pathwise_solve(st, w->Kt, ldt, R + (int64_t)v * npt, Al + (int64_t)v * npt, zf, t, piece, work));
-    }
-    {
-        StageTimer tm(h, 3);
-        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0))
-            GP_TRY(F.cross_apply(F, st, G, M, Xt, N, Al, npt, S, s0, g, Z, zw, M + N, noiseless, mean_out, samples_out));
-        GP_TRY(launch_pw_scatter(st, idx, N, M, Al, npt, S, jitter_s, samples_out));
-    }
-    return finish_and_check(st);
-}
-
-// ------------------------------------------------------------------------------------------
-// draws on a fully observed grid: every step of the recipe above in the reflection basis, block by
-// block -- no product with K_GX and no matrix of order N.  Pb holds chol(K_b + d I) until the prior draws c_b exist, then
-// K_b + s I and its factor.
-// ------------------------------------------------------------------------------------------
-// A = (L L^T)^-1 R for ncols (1 .. 8) padded columns, column c at + c * cs: pathwise_solve for a group, the panel and the
-// rows below it read once (distops.hip).  Zf: the forward results (columns of cs); t: ncols x np running products;
-// part: gemv_t_multi_chunks(np) x 8 x 512.
-static int blocks_solve(gpimhip_ctx* sub, const double* L, int64_t ld, const double* R, double* A, double* Zf, int64_t cs,
-                        int ncols, double* t, double* part) {
-    const int64_t np = sub->np;
-    const int nb = (int)(np / NB);
-    const int64_t pcs = 4 * NB, pchs = (int64_t)multi_group_width(ncols) * pcs;
-    HIP_TRY(hipMemsetAsync(t, 0, (size_t)(ncols * np) * sizeof(double), sub->stream));
-    for (int g0 = 0; g0 < nb; g0 += OUTER_W) {
-        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
-        const int64_t r0 = (int64_t)g0 * NB;
-        const double* P = L + r0 * ld + r0;
-        GP_TRY(launch_dist_trsv_multi(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 0, R + r0, cs, t + r0, np, 0, 1, ncols,
-                                      Zf + r0, cs));
-        GP_TRY(launch_dist_rows_acc_multi(sub, P + (int64_t)wd * ld, ld, np - r0 - wd, wd, Zf + r0, cs, ncols, t + r0 + wd, np));
-    }
-    for (int g0 = ((nb - 1) / OUTER_W) * OUTER_W; g0 >= 0; g0 -= OUTER_W) {
-        const int nblk = std::min(OUTER_W, nb - g0), wd = nblk * NB;
-        const int64_t r0 = (int64_t)g0 * NB, below = np - r0 - wd;
-        const double* P = L + r0 * ld + r0;
-        GP_TRY(launch_gemv_t_multi(sub, P + (int64_t)wd * ld, ld, below, wd, A + r0 + wd, cs, ncols, part));
-        GP_TRY(launch_dist_trsv_multi(sub, P, ld, sub->dinv + (int64_t)g0 * NB * NB, nblk, 1, Zf + r0, cs, part, pcs, pchs,
-                                      below > 0 ? gemv_t_multi_chunks(below) : 0, ncols, A + r0, cs));
-    }
-    return GPIMHIP_OK;
-}
-
-// (stage timers of the model handle, as sample_pathwise_impl: 4 covariance builds, 0 factorisations, 5 the sweeps L_b z_p,
-// 2 gathers and both basis changes, 1 the multi-column solves, 3 right-hand sides, combination and epilogue)
-// Everything of one call but the closing synchronisation.  theta_src / reset_info: as sample_enqueue; jitter_m: the model's
-// own jitter of the diagonal K_b + (noise + jitter_m) I (m->jitter; 0 for a latent block of the multi-output model and for
-// the spectral mixture).
-static int sample_blocks_enqueue(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
-                                 int64_t M, const double* y, const double* Z, int S, int noiseless,
-                                 double jitter_s, double* mean_out, double* samples_out, const ThetaDev* theta_src,
-                                 double jitter_m, bool reset_info) {
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* w = sws(h);
-    int64_t Nq = 1;
-    for (int k = 0; k < gd.d; ++k) Nq *= gd.f[k];
-    const int B = 1 << __builtin_popcount(gd.mask);
-    GP_TRY(pathwise_sub(h, &w->subp, Nq));
-    gpimhip_ctx* sp = w->subp;
-    const int64_t npq = sp->np, ldq = sp->ld;
-    const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
-    GP_TRY(w->Pb.grow(h, npq * ldq));
-    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
-    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
-                  o_e = o_c + even(SB * Nq), o_cc = o_e + B * S1 * npq, o_g = o_cc + even(B * S1 * Nq), o_r = o_g + even(S1 * M),
-                  o_zf = o_r + S1 * npq, o_al = o_zf + S1 * npq, o_t = o_al + S1 * npq,
-                  o_part = o_t + 8 * npq, o_mws = o_part + (int64_t)gemv_t_multi_chunks(npq) * 8 * 4 * NB, o_end = o_mws + npq;
-    GP_TRY(w->pw.grow(h, o_end));
-    if (F.reserve) GP_TRY(F.reserve(F, h, 0, npq, 0, M));
-    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *E = w->pw + o_e, *Cc = w->pw + o_cc,
-           *g = w->pw + o_g, *R = w->pw + o_r, *Zf = w->pw + o_zf, *Al = w->pw + o_al, *t = w->pw + o_t, *part = w->pw + o_part,
-           *mean_ws = w->pw + o_mws;
-    // one status word for the 2 B factorisations
-    if (reset_info) HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
-    if (theta_src) HIP_TRY(hipMemcpyAsync(sp->theta, theta_src, sizeof(ThetaDev), hipMemcpyDeviceToDevice, h->stream));
-    else GP_TRY(F.params(F, sp, jitter_s));
-    {
-        StageTimer tm(h, 2);
-        const double* yc;
-        GP_TRY(centred(F, sp, y, M, &yc));
-        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
-        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
-        GP_TRY(launch_pw_basis_fwd(sp, gd, Z, zw, M, yc, S, Nq, npq, B, E));
-    }
-    sp->refl.mask = gd.mask;
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
-    sp->refl.n_total = M;
-    sp->refl.var_count = 0;
-    sp->refl.pb_stride = 1;
-    sp->refl.nblocks_total = B;
-    sp->refl.raw = 0;
-    for (int b = 0; b < B; ++b) {
-        sp->refl.pb_off = b;
-        sp->refl.wts = wts + (int64_t)b * Nq;
-        double *Cb = C + (int64_t)b * S * Nq, *Eb = E + (int64_t)b * S1 * npq;
-        // ---- the prior draw c_b = chol(K_b + d I) z_b
-        GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
-        {
-            StageTimer tm(h, 4);
-            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, false, w->Pb, ldq, npq));
-        }
-        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
-        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
-            StageTimer tm(h, 5);
-            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
-                                       nullptr, nullptr, Cb));
-        }
-        // ---- T_b = K_b + s I in the same buffer, its factor, [alpha_b | alpha_y,b] for the S draws and y
-        GP_TRY(launch_pw_reset_diag(sp, sp->theta, jitter_m));
-        {
-            StageTimer tm(h, 4);
-            GP_TRY(F.kmat_refl(F, sp, Xq, Nq, true, w->Pb, ldq, npq));
-        }
-        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
-        { StageTimer tm(h, 3); GP_TRY(launch_pw_blocks_rhs(sp, Cb, Eb, S, Nq, npq, sp->theta, jitter_s, R)); }
-        {
-            StageTimer tm(h, 1);
-            for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
-                const int64_t off = (int64_t)c0 * npq;
-                GP_TRY(blocks_solve(sp, w->Pb, ldq, R + off, Al + off, Zf + off, npq, sample_draw_group(S + 1 - c0), t, part));
-            }
-        }
-        {
-            StageTimer tm(h, 3);
-            GP_TRY(launch_pw_blocks_combine(sp, Al, Eb, S, Nq, npq, sp->theta, jitter_s, Cc + (int64_t)b * S1 * Nq));
-        }
-    }
-    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, Cc, S + 1, Nq, B, M, g)); }
-    {
-        StageTimer tm(h, 3);
-        GP_TRY(launch_pw_blocks_out(sp, g, M, S, Z, zw, 2 * M, noiseless, sp->theta, mean_out, samples_out));
-        if (F.shift) {
-            if (mean_out) GP_TRY(F.shift(F, sp, mean_out, M));
-            GP_TRY(F.shift(F, sp, samples_out, (int64_t)S * M));
-        }
-    }
-    return GPIMHIP_OK;
-}
-// jitter_m: the model's own jitter (m->jitter; the spectral mixture has none)
-static int sample_blocks_impl(gpimhip_ctx* h, const DrawFamily& F, PwGrid gd, const double* twoc, const double* G,
-                              int64_t M, const double* y, const double* Z, int S, int noiseless,
-                              double jitter_s, double jitter_m, double* mean_out, double* samples_out) {
-    GP_TRY(sample_blocks_enqueue(h, F, gd, twoc, G, M, y, Z, S, noiseless, jitter_s, mean_out, samples_out, nullptr, jitter_m,
-                                 true));
-    return finish_and_check(sws(h)->subp);
-}
-
-// ------------------------------------------------------------------------------------------
-// joint draws of the multi-output GP.  The reduction of section 9 diagonalises the posterior too: the
-// whitened, rotated latent functions h_t = sum_a Q_at s_a^-1/2 f_a are independent GPs with kernel lambda_t K, observed with
-// unit noise through z_t, so a joint draw of the T outputs is one single-output draw per latent block, mixed back:
-//   f_a = mu_a + s_a^1/2 sum_t Q_at h_t          (vgp.hip: vgp_sample_mix_kernel)
-// The blocks run one after the other through the single-output drivers above and the one matrix those own (J, or Pb): the
-// large allocation is that of a single-output call at the same sizes.  One status word, one synchronisation.
-// (stage timers of the model handle: those of the single-output driver, summed over the T blocks, and 6 = the mix kernel;
-// the joint route also records 2 = setup and projection, 3 = the mix of mean and variance)
-// ------------------------------------------------------------------------------------------
-static int sample_vgp_ws(gpimhip_ctx* h, int T, int64_t N, int64_t M, int S, SampleWs** out) {
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* w = sws(h);
-    if (!w->vst) GP_TRY(w->vst.alloc(h, 1));
-    if (!w->vth) GP_TRY(w->vth.alloc(h, VGP_MAXT));
-    GP_TRY(w->vz.grow(h, (int64_t)T * N));
-    GP_TRY(w->vH.grow(h, (int64_t)T * S * M));
-    GP_TRY(w->vmom.grow(h, 2 * (int64_t)T * M));
-    *out = w;
-    return GPIMHIP_OK;
-}
-
-static int sample_vgp_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
-                           int64_t N, const double* u, const double* Xs, int64_t M, const double* Z, int S, int noiseless,
-                           double jitter_s, double* mean_out, double* var_out, double* samples_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    const int T = vg->tasks;
-    SampleWs* w = nullptr;
-    GP_TRY(sample_vgp_ws(h, T, N, M, S, &w));
-    double *mblk = w->vmom, *vblk = w->vmom + (int64_t)T * M;
-    {
-        StageTimer tm(h, 2);
-        GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
-        GP_TRY(launch_vgp_project_to(h, Y, N, T, w->vst, w->vz));
-    }
-    const DrawFamily F = stationary_family(m, nullptr);         // (every block's theta comes from vth)
-    for (int t = 0; t < T; ++t)
-        GP_TRY(sample_enqueue(h, F, X, w->vz + (int64_t)t * N, N, Xs, M, Z + (int64_t)t * S * M, S, noiseless, jitter_s,
-                              mean_out ? mblk + (int64_t)t * M : nullptr, var_out ? vblk + (int64_t)t * M : nullptr,
-                              w->vH + (int64_t)t * S * M, w->vth + t, t == 0));
-    { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
-    if (mean_out || var_out) {
-        StageTimer tm(h, 3);
-        GP_TRY(launch_vgp_combine(h, T, M, w->vst, mblk, vblk, mean_out, var_out));
-    }
-    return finish_and_check(w->sub);
-}
-
-static int sample_vgp_blocks_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, PwGrid gd,
-                                  const double* twoc, const double* G, int64_t M, const double* Y, const double* u,
-                                  const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
-                                  double* samples_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    const int T = vg->tasks;
-    SampleWs* w = nullptr;
-    GP_TRY(sample_vgp_ws(h, T, M, M, S, &w));
-    const int64_t zw = 2 * M + (noiseless ? 0 : M);
-    GP_TRY(launch_vgp_setup_to(h, m, vg, u, w->vst, w->vth));
-    GP_TRY(launch_vgp_project_to(h, Y, M, T, w->vst, w->vz));
-    const DrawFamily F = stationary_family(m, nullptr);         // (every block's theta comes from vth)
-    for (int t = 0; t < T; ++t)
-        GP_TRY(sample_blocks_enqueue(h, F, gd, twoc, G, M, w->vz + (int64_t)t * M, Z + (int64_t)t * S * zw, S, noiseless,
-                                     jitter_s, mean_out ? w->vmom + (int64_t)t * M : nullptr, w->vH + (int64_t)t * S * M,
-                                     w->vth + t, 0.0, t == 0));
-    { StageTimer tm(h, 6); GP_TRY(launch_vgp_sample_mix(h, T, S, M, w->vst, w->vH, samples_out)); }
-    if (mean_out) GP_TRY(launch_vgp_combine(h, T, M, w->vst, w->vmom, nullptr, mean_out, nullptr));
-    return finish_and_check(w->subp);
-}
-
-// ------------------------------------------------------------------------------------------
-// draws on a grid with missing points: the recipe of section 17 with the bordered blocks of the model
-// in place of a second factorisation per block.  With A = K_GG + s I on the completed grid, V = A^-1 P_m, S = P_m^T V:
-//   beta = A^-1 [r~ | y~],  w = S^-1 beta_m,  alpha~ = beta - V w      ((K_oo + s I)^-1 embedded: zero at the missing points)
-//   p = (s - d) alpha~ - sqrt(s - d) z_e at the observed points, g + w at the missing ones;  mean = y - s alpha~_y, -w_y
-// Everything A^-1, S^-1 and V need is what a prediction leaves: L_b^-1 in h->A, L_S^-1 in the border's sub->A, Y_b = C_b L_S^-T.
-// Beyond that state: one np x ld block (SampleWs::Pb, the prior factors one after the other) and vectors.
-// (stage timers of the model handle: 4 the prior's covariance builds, 0 factorisations with the inverses their launches
-// host, 5 the sweeps L_b z_p, 2 gathers and the basis changes, 1 the multi-column sweeps through L_b^-1 and what is left of
-// the triangular inverses, 6 those sweeps alone (intervals inside stage 1's), 3 right-hand sides, the border's vectors,
-// combination and epilogue; the model's covariance build, its K^-1 product and the products of border_iter are not timed,
-// as in a prediction)
-// ------------------------------------------------------------------------------------------
-static int sample_border_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* ys,
-                              int64_t Nq, int B, const double* u, PwGrid gd, const double* twoc, const double* G, int64_t M,
-                              const int64_t* miss, const double* Z, int S, int noiseless, double jitter_s, double* mean_out,
-                              double* samples_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* w = sws(h);
-    GP_TRY(pathwise_sub(h, &w->subp, Nq));
-    gpimhip_ctx* sp = w->subp;
-    const int64_t npq = sp->np, ldq = sp->ld;
-    const int64_t zw = 2 * M + (noiseless ? 0 : M), SB = (int64_t)S * B, S1 = S + 1;
-    const int Mm = bws(h)->M;
-    const int64_t mp = pad_to(Mm, NB);
-    GP_TRY(w->Pb.grow(h, npq * ldq));
-    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
-    const int pg = sample_draw_group(S + 1);           // the first group of columns is the largest
-    const int64_t n_part = std::max((int64_t)B * tri_bwd_chunks(npq) * pg * npq, (int64_t)tri_bwd_chunks(mp) * pg * mp);
-    const int64_t o_xq = 0, o_wts = o_xq + npq * GPIMHIP_MAX_DIM, o_zg = o_wts + even(B * Nq), o_c = o_zg + even(SB * Nq),
-                  o_g = o_c + even(SB * Nq), o_mws = o_g + even((int64_t)S * M), o_r = o_mws + npq, o_zf = o_r + B * S1 * npq,
-                  o_cc = o_zf + B * S1 * npq, o_g2 = o_cc + even(B * S1 * Nq), o_tv = o_g2 + even(S1 * M), o_part = o_tv + 3 * S1 * mp,
-                  o_mi = o_part + n_part, o_end = o_mi + even(M) / 2;
-    GP_TRY(w->pw.grow(h, o_end));
-    double *Xq = w->pw + o_xq, *wts = w->pw + o_wts, *Zg = w->pw + o_zg, *C = w->pw + o_c, *g = w->pw + o_g, *mean_ws = w->pw + o_mws,
-           *R = w->pw + o_r, *Zf = w->pw + o_zf, *Cc = w->pw + o_cc, *g2 = w->pw + o_g2, *tv = w->pw + o_tv, *vv = tv + S1 * mp,
-           *wv = vv + S1 * mp, *part = w->pw + o_part;
-    int32_t* mi = (int32_t*)(w->pw + o_mi);
-    // ---- the prior draws c_b = chol(K_b + d I) z_b block by block through Pb (sample_blocks_impl), g = U^T c
-    HIP_TRY(hipMemsetAsync(sp->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(launch_theta(sp, m, u));
-    GP_TRY(launch_pw_set_diag(sp, sp->theta, jitter_s));
-    {
-        StageTimer tm(h, 2);
-        GP_TRY(launch_pw_setup(sp, gd, G, M, Nq, B, Xq, wts, nullptr, 0, nullptr));
-        GP_TRY(launch_pw_gather_z(sp, gd, Z, zw, S, Nq, B, Zg));
-        GP_TRY(launch_bs_mark(sp, miss, Mm, M, mi));
-    }
-    sp->refl.mask = gd.mask;
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) sp->refl.twoc[k] = twoc[k];
-    sp->refl.n_total = M;
-    sp->refl.var_count = 0;
-    sp->refl.pb_stride = 1;
-    sp->refl.nblocks_total = B;
-    sp->refl.raw = 0;
-    for (int b = 0; b < B; ++b) {
-        sp->refl.pb_off = b;
-        sp->refl.wts = wts + (int64_t)b * Nq;
-        {
-            StageTimer tm(h, 4);
-            GP_TRY(launch_kmat_refl(sp, m, Xq, Nq, nullptr, Nq, sp->theta, w->Pb, ldq, npq, npq, 1, 0, 0, 0, 1.0));
-        }
-        { StageTimer tm(h, 0); GP_TRY(launch_potrf(sp, w->Pb, npq, ldq, sp->info)); }
-        for (int s0 = 0; s0 < S; s0 += sample_draw_group(S - s0)) {
-            StageTimer tm(h, 5);
-            GP_TRY(launch_sample_draws(sp, w->Pb, ldq, 0, Nq, nullptr, Zg + (int64_t)b * S * Nq, S, s0, sp->theta, 1, 0.0, mean_ws,
-                                       nullptr, nullptr, C + (int64_t)b * S * Nq));
-        }
-    }
-    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(sp, gd, C, S, Nq, B, M, g)); }
-    // ---- the model's state: L_b^-1, B_b^-1, S, L_S^-1, Y_b (every factorisation reports through h->info)
-    GP_TRY(model_state_at_u(h, m, X, x_bs, ys, Nq, B, u));
-    GP_TRY(launch_bs_merge_info(h, sp->info, h->info));
-    BorderWs* bw = bws(h);
-    const int64_t np = h->np, ld = h->ld;
-    if (np != npq || sp->stream != h->stream) {         // the vectors above are sized by the prior's context and indexed by the model's
-        gpim_set_error("gpimhip_sample_border: the prior's context and the model's workspace disagree on the padded block order "
-                       "or on the stream");
-        return GPIMHIP_E_BADARG;
-    }
-    const double *Ls = bw->sub->A;
-    const int64_t lds = bw->sub->ld;
-    // ---- right-hand sides in the blocks: [U r~ | ys]; what the sweeps leave untouched (padding rows) is zero
-    HIP_TRY(hipMemsetAsync(Zf, 0, (size_t)(B * S1 * np) * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(tv, 0, (size_t)(3 * S1 * mp) * sizeof(double), h->stream));
-    {
-        StageTimer tm(h, 3);
-        GP_TRY(launch_bs_rhs_fwd(h, gd, g, Z, zw, M, mi, ys, h->theta, jitter_s, S, Nq, np, B, R));
-    }
-    // ---- beta_b = L_b^-T (L_b^-1 R_b), a group of columns per pass over the triangles (beta overwrites R)
-    {
-        StageTimer tm(h, 1);
-        for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
-            const int nc = sample_draw_group(S + 1 - c0);
-            const int64_t off = (int64_t)c0 * np;
-            StageTimer ts(h, 6);                        // (the two sweeps alone: stage 1 also holds the rest of the inverses)
-            GP_TRY(launch_tri_fwd_multi(h, h->A, ld, np * ld, Nq, B, R + off, Zf + off, np, S1 * np, nc));
-            GP_TRY(launch_tri_bwd_multi(h, h->A, ld, np * ld, Nq, np, B, Zf + off, R + off, np, S1 * np, nc, part, pg));
-        }
-    }
-    // ---- the border: t = beta_m, v = L_S^-1 t, w = L_S^-T v, alpha~_b = beta_b - Y_b v
-    {
-        StageTimer tm(h, 3);
-        GP_TRY(launch_bs_t(h, R, np, B, (int)S1, bw->q, bw->coef, Mm, mp, tv));
-        for (int c0 = 0; c0 <= S; c0 += sample_draw_group(S + 1 - c0)) {
-            const int nc = sample_draw_group(S + 1 - c0);
-            const int64_t off = (int64_t)c0 * mp;
-            GP_TRY(launch_tri_fwd_multi(h, Ls, lds, 0, Mm, 1, tv + off, vv + off, mp, 0, nc));
-            GP_TRY(launch_tri_bwd_multi(h, Ls, lds, 0, Mm, mp, 1, vv + off, wv + off, mp, 0, nc, part, pg));
-            GP_TRY(launch_bs_yv(h, bw->Y, mp, np, Nq, B, (int)S1, vv, c0, nc, R));
-        }
-        GP_TRY(launch_bs_combine(h, R, ys, S, Nq, np, B, h->theta, jitter_s, Cc));
-    }
-    { StageTimer tm(h, 2); GP_TRY(launch_pw_basis_t(h, gd, Cc, S + 1, Nq, B, M, g2)); }
-    {
-        StageTimer tm(h, 3);
-        GP_TRY(launch_bs_out(h, g2, g, wv, mp, mi, M, S, Z, zw, noiseless, h->theta, jitter_s, mean_out, samples_out));
-    }
-    return finish_and_check(h);
-}
-
-// the grid of a pathwise or block draw from its shape and reflected axes; M = its points (0: a bad argument)
-static int64_t pw_grid(int dim, const int32_t* shape, int32_t mask, PwGrid* gd) {
-    gd->d = dim;
-    gd->mask = mask;
-    int64_t M = 1;
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) {
-        gd->n[k] = k < dim ? shape[k] : 1;
-        if (gd->n[k] < 1) return 0;
-        const bool refl = (mask >> k) & 1;
-        if (refl && (k >= dim || gd->n[k] < 2)) return 0;
-        gd->f[k] = refl ? (gd->n[k] + 1) / 2 : gd->n[k];
-        M *= gd->n[k];
-        if (M > ((int64_t)1 << 31)) return 0;
-    }
-    return M;
-}
-
-extern "C" {
-
-int gpimhip_sample_blocks(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,
-                          const double* twoc, const double* y, const double* u, const double* Z, int32_t S, int32_t noiseless,
-                          double jitter, double* mean_out, double* samples_out) {
-    FP64_ONLY(h);
-    if (!h || !G || !shape || !twoc || !y || !u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0))
-        return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
-    if (h->refl.mask) {
-        gpim_set_error("gpimhip_sample_blocks: not available in reflection mode (the dense double-precision engine only)");
-        return GPIMHIP_E_BADARG;
-    }
-    PwGrid gd;
-    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
-    if (M < 1) return GPIMHIP_E_BADARG;
-    if (!mask || (mask >> m->dim)) {
-        gpim_set_error("gpimhip_sample_blocks: needs at least one reflected axis of the grid");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_blocks_impl(h, stationary_family(m, u), gd, twoc, G, M, y, Z, S, noiseless ? 1 : 0, jitter, m->jitter, mean_out,
-                              samples_out);
-}
-
-int gpimhip_sample_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
-                       int64_t N, const double* u, const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless,
-                       double jitter, double* mean_out, double* var_out, double* samples_out) {
-    GP_TRY(vgp_check(h, m, vg, X, Y, N));
-    if (!u || !Xs || !Z || !samples_out || M < 1 || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
-    if (h->refl.mask) {
-        gpim_set_error("gpimhip_sample_vgp: not available in reflection mode (the observed rows X, Y of the dense model; "
-                       "gpimhip_set_reflection(h, 0, ...))");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_vgp_impl(h, m, vg, X, Y, N, u, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
-}
-
-int gpimhip_sample_vgp_blocks(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* G,
-                              const int32_t* shape, int32_t mask, const double* twoc, const double* Y, const double* u,
-                              const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
-                              double* samples_out) {
-    if (!shape || !twoc) return GPIMHIP_E_BADARG;
-    GP_TRY(vgp_check(h, m, vg, G, Y, 1));
-    if (!u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
-    if (jitter > 1.0) {
-        gpim_set_error("gpimhip_sample_vgp_blocks: needs 0 < jitter <= 1 (block units: the latent blocks have unit noise)");
-        return GPIMHIP_E_BADARG;
-    }
-    if (h->refl.mask) {
-        gpim_set_error("gpimhip_sample_vgp_blocks: not available in reflection mode (the grid G and the rows Y of the dense "
-                       "model; gpimhip_set_reflection(h, 0, ...))");
-        return GPIMHIP_E_BADARG;
-    }
-    PwGrid gd;
-    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
-    if (M < 1) return GPIMHIP_E_BADARG;
-    if (!mask || (mask >> m->dim)) {
-        gpim_set_error("gpimhip_sample_vgp_blocks: needs at least one reflected axis of the grid");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_vgp_blocks_impl(h, m, vg, gd, twoc, G, M, Y, u, Z, S, noiseless ? 1 : 0, jitter, mean_out, samples_out);
-}
-
-int gpimhip_sample_border(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
-                          int64_t N, int32_t B, const double* u, const double* G, const int32_t* shape, int32_t mask,
-                          const double* twoc, const int64_t* miss, const double* Z, int32_t S, int32_t noiseless, double jitter,
-                          double* mean_out, double* samples_out) {
-    FP64_ONLY(h);
-    if (!h || !X || !y || !u || !G || !shape || !twoc || !miss || !Z || !samples_out || N < 1 || B < 1 ||
-        B > (1 << GPIMHIP_MAX_DIM) || S < 1 || S > 65534 || !(jitter > 0.0))
-        return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
-    if (!h->refl.mask) {
-        gpim_set_error("gpimhip_sample_border: needs reflection mode (gpimhip_set_reflection) with a border (gpimhip_set_border)");
-        return GPIMHIP_E_BADARG;
-    }
-    if (!border_on(h)) {
-        gpim_set_error("gpimhip_sample_border: no border is set (no missing points: gpimhip_sample_blocks draws on a fully "
-                       "observed grid)");
-        return GPIMHIP_E_BADARG;
-    }
-    // (BorderWs::T > 1 can only come from a batch of T 2^r problems: this entry sets one border up, whatever ran before)
-    if (mask > 0 && mask < (1 << GPIMHIP_MAX_DIM) && B > (1 << __builtin_popcount(mask)) && B % (1 << __builtin_popcount(mask)) == 0) {
-        gpim_set_error("gpimhip_sample_border: a multi-output border (B = T 2^r problems, one border per task) is not built: the "
-                       "entry takes the 2^r blocks of one model");
-        return GPIMHIP_E_BADARG;
-    }
-    PwGrid gd;
-    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
-    int64_t Nq = M < 1 ? 0 : 1;
-    for (int k = 0; k < GPIMHIP_MAX_DIM && M >= 1; ++k) Nq *= gd.f[k];
-    if (M < 1 || mask != h->refl.mask || (mask >> m->dim) || B != (1 << __builtin_popcount(mask)) || Nq != N ||
-        bws(h)->M >= M || h->refl.pb_stride != 1 || h->refl.raw) {
-        gpim_set_error("gpimhip_sample_border: the grid (shape, mask) does not describe the handle's reflection blocks (mask, "
-                       "B = 2^r, N = the points of the fundamental domain, fewer missing points than grid points, unsharded)");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_border_impl(h, m, X, x_stride, y, N, B, u, gd, twoc, G, M, miss, Z, S, noiseless ? 1 : 0, jitter, mean_out,
-                              samples_out);
-}
-
-int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const double* G, const int32_t* shape, int32_t mask,
-                            const double* twoc, const int64_t* idx, const double* y, int64_t N, const double* u,
-                            const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
-                            double* samples_out) {
-    FP64_ONLY(h);
-    if (!h || !G || !shape || !twoc || !idx || !y || !u || !Z || !samples_out || N < 1 || S < 1 || S > 65535 || !(jitter > 0.0))
-        return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
-    if (h->refl.mask) {
-        gpim_set_error("gpimhip_sample_pathwise: not available in reflection mode (the dense double-precision engine only)");
-        return GPIMHIP_E_BADARG;
-    }
-    PwGrid gd;
-    const int64_t M = pw_grid(m->dim, shape, mask, &gd);
-    if (M < 1) return GPIMHIP_E_BADARG;
-    if (!mask || (mask >> m->dim)) {
-        gpim_set_error("gpimhip_sample_pathwise: needs at least one reflected axis of the grid");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_pathwise_impl(h, stationary_family(m, u), gd, twoc, G, M, idx, y, N, Z, S, noiseless ? 1 : 0, jitter, mean_out,
-                                samples_out);
-}
-
-// ------------------------------------------------------------------------------------------
-// posterior draws of the dense-by-Kronecker blocks: Matheron's rule with the prior drawn through
-// L_P = chol(s2 K_s(P, P) + d I) of the union P of the ragged training and test rows and the root rows of the union of the
-// complete axes (section 21), the update through the blocks' L_j^-1 for all draws of a group at once on the tile engine.
-// Stage timers: 6 the blocks as a whole (theta, eigen-decomposition, factorisation, the mean's beta; inside it the engine's
-// own intervals 0 / 1 of the blocks' factorisation and inverse), 4 the prior factor (covariance build, factorisation -- its
-// context records no intervals of its own), 2 the prior draws (the union axes' decomposition and root rows, zeta,
-// H = L_P zeta, gathers, mode products), 3 the update (cross factors, residual, projection, the blocks' solves, K*_s
-// products and mode products, the mean's among them), 5 the epilogue.
-// ------------------------------------------------------------------------------------------
-// doubles of the buffers that grow with the draws of one group (0.25 GiB): a call of more draws takes them group by group
-#define PKS_GROUP_BUDGET ((int64_t)1 << 25)
-static int pks_bad(const std::string& what) {
-    gpim_set_error("gpimhip_sample_pkron: " + what);
-    return GPIMHIP_E_BADARG;
-}
-
-int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
-                         const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
-                         const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
-                         const double* P, int64_t Us, const int32_t* irow_train, const int32_t* irow_test,
-                         const int32_t* n_union, const double* axes_union, const int32_t* idx_train, const int32_t* idx_test,
-                         const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out, double* samples_out) {
-    if (!h || !m || !Xs || !n_c || !axes_c || !Y || !u || !Xs_test || !n_test_c || !axes_test_c || !P || !irow_train ||
-        !irow_test || !n_union || !axes_union || !idx_train || !idx_test || !Z || !mean_out || !samples_out)
-        return pks_bad("a null argument (every pointer but perm is required)");
-    if (S < 1) return pks_bad("needs S >= 1");
-    if (!(jitter > 0.0) || !(jitter < HUGE_VAL))
-        return pks_bad("needs a finite jitter > 0 (the prior factor of the ragged rows is chol(s2 K_s(P, P) + jitter I))");
-    PkronMap mp;
-    GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
-    if (Ms < 1 || Us < 1 || Us > Ns + Ms) return pks_bad("needs Ms >= 1 and 1 <= Us <= Ns + Ms union rows");
-    // the union axes and the index maps (host arrays), as gpimhip_sample_kron checks them; shared: the union axes ARE the
-    // training axes and the training decomposition serves
-    bool shared = true;
-    int64_t sum_n = 0, sum_m = 0, sum_u = 0, sum_mn = 0, sum_nu = 0, sum_mu = 0, U = 1, Mc = 1, pmax = 1, maxX = 1, maxT = 1;
-    {
-        int64_t cur = mp.J;
-        for (int i = 0, oc = 0, ot = 0; i < dc; ++i) {
-            if (n_test_c[i] < 1) return pks_bad("every complete axis of the test grid needs at least one coordinate");
-            if (n_union[i] > 4096) {
-                char msg[200];
-                snprintf(msg, sizeof(msg), "the union of the training and the test coordinates of complete axis %d has %d entries; "
-                         "the eigen-solver takes at most 4096", i, (int)n_union[i]);
-                return pks_bad(msg);
-            }
-            if (n_union[i] < n_c[i] || (int64_t)n_union[i] > (int64_t)n_c[i] + n_test_c[i])
-                return pks_bad("n_union[i] must lie between n_c[i] and n_c[i] + n_test_c[i]");
-            for (int a = 0; a < n_c[i]; ++a) {
-                const int32_t v = idx_train[oc + a];
-                if (v < 0 || v >= n_union[i]) return pks_bad("idx_train outside its union axis");
-                shared = shared && v == a;
-            }
-            for (int a = 0; a < n_test_c[i]; ++a) {
-                const int32_t v = idx_test[ot + a];
-                if (v < 0 || v >= n_union[i]) return pks_bad("idx_test outside its union axis");
-            }
-            shared = shared && n_union[i] == n_c[i];
-            oc += n_c[i]; ot += n_test_c[i];
-            sum_n += n_c[i]; sum_m += n_test_c[i]; sum_u += n_union[i];
-            sum_mn += (int64_t)n_test_c[i] * n_c[i];
-            sum_nu += (int64_t)n_c[i] * n_union[i];
-            sum_mu += (int64_t)n_test_c[i] * n_union[i];
-            U *= n_union[i];
-            Mc *= n_test_c[i];
-            cur = cur / n_c[i] * n_test_c[i];
-            pmax = std::max(pmax, cur);
-        }
-        // the largest tensor (per ragged row) the two chains of root rows pass through: U -> J and U -> Mc
-        int64_t cx = U, ct = U;
-        maxX = maxT = U;
-        for (int i = 0; i < dc; ++i) {
-            cx = cx / n_union[i] * n_c[i];
-            ct = ct / n_union[i] * n_test_c[i];
-            maxX = std::max(maxX, cx);
-            maxT = std::max(maxT, ct);
-        }
-    }
-    for (int64_t a = 0; a < Ns; ++a)
-        if (irow_train[a] < 0 || irow_train[a] >= Us) return pks_bad("irow_train outside the union rows");
-    for (int64_t a = 0; a < Ms; ++a)
-        if (irow_test[a] < 0 || irow_test[a] >= Us) return pks_bad("irow_test outside the union rows");
-
-    PkronWs* w = nullptr;
-    GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
-    const int64_t np = h->np;
-    const int J = mp.J, nb = (int)(np / NB);
-    const int64_t Jp = pad_to(J, NB), NJ = Ns * J, M = Ms * Mc, zw = Us * U + NJ + M;
-    const KronDev& dv = w->ax.dev;
-    const gpimhip_model_t ms = pkron_submodel(m, p);
-    const int rag = rag_of(Ns, np);
-    // the chunks of ragged test rows and the mean's buffers are gpimhip_predict_pkron's
-    const int64_t mc = std::min(pad_to(Ms, NB), std::max<int64_t>(NB, ((int64_t)1 << 26) / ((int64_t)J * nb) / NB * NB));
-    {
-        BatchScope one(h, 1);
-        GP_TRY(ws_ensure_predict(h, np, mc));
-    }
-    const int64_t kld = h->ks_cols + 16;
-    GP_TRY(w->G.grow(h, Jp * mc));
-    GP_TRY(w->pp.grow(h, 4 * pmax * mc));
-    GP_TRY(w->cross.grow(h, 2 * sum_mn));
-    if (!h->sample) h->sample = new SampleWs();
-    SampleWs* sw = sws(h);
-    GP_TRY(pathwise_sub(h, &sw->sub, Us));
-    gpimhip_ctx* sub = sw->sub;
-    const int64_t npU = sub->np, ldU = sub->ld;
-    const int nbU = (int)(npU / NB);
-    if (!shared) {
-        GP_TRY(kron_axes_ensure(h, sw->ck_un, dc, n_union, false));
-        HIP_TRY(hipMemcpyAsync(const_cast<double*>(sw->ck_un.dev.coords), axes_union, (size_t)sum_u * sizeof(double),
-                               hipMemcpyDeviceToDevice, h->stream));
-        GP_TRY(kron_plan_problems(h, sw->ck_un));
-        GP_TRY(kron_cold_start(h, sw->ck_un.dev));
-    }
-    const KronDev& du = shared ? dv : sw->ck_un.dev;
-    // draw groups: the buffers below that grow with the draws stay within PKS_GROUP_BUDGET; every draw's arithmetic is its
-    // own (one thread per element in the new kernels, one k-loop per element in the tile engine and the mode products), so
-    // the grouping does not reach the result
-    const int64_t big = std::max(Ns * maxX, Ms * maxT);
-    const int64_t per_draw = 2 * npU * U + 3 * big + 2 * pmax * mc + (int64_t)J * (3 * np + mc);
-    const int Sg_max = (int)std::max<int64_t>(1, std::min<int64_t>(S, PKS_GROUP_BUDGET / per_draw));
-    const int ngroups = (S + Sg_max - 1) / Sg_max, Sg0 = (S + ngroups - 1) / ngroups;
-    const int64_t cols = pad_to(Sg0 * U, NB), Sp = pad_to(Sg0, NB), rowsP = pad_to((int64_t)Sg0 * J, NB);
-    const int nct = (int)(cols / NB), nst = (int)(Sp / NB);
-    if ((int64_t)nbU * nct > (1 << 28) || (int64_t)nb * nst > (1 << 28)) return pks_bad("too many tiles in one launch");
-    // tile lists, longest k-ranges first: H = L_P zeta and T = L_j^-1 R stop at the diagonal block, beta = L_j^-T T starts there
-    std::vector<TileDesc> tl;
-    tl.reserve((size_t)nbU * nct + 2 * (size_t)nb * nst);
-    for (int ci = nbU - 1; ci >= 0; --ci)
-        for (int cj = 0; cj < nct; ++cj) tl.push_back({ci, cj, 0, ci + 1});
-    for (int ci = nb - 1; ci >= 0; --ci)
-        for (int cj = 0; cj < nst; ++cj) tl.push_back({ci, cj, 0, ci + 1});
-    for (int ci = 0; ci < nb; ++ci)
-        for (int cj = 0; cj < nst; ++cj) tl.push_back({ci, cj, ci, nb});
-    const int n_prior = nbU * nct, n_solve = nb * nst;
-    const int64_t th_d = (int64_t)((sizeof(ThetaDev) + 15) / 16 * 2);
-    const int64_t total = th_d + npU * ldU + 2 * npU * cols + 3 * Sg0 * big + 2 * J * np * Sp + rowsP * np + rowsP * mc +
-                          2 * Sg0 * pmax * mc + sum_nu + sum_mu + (Ns + Ms + sum_n + sum_m) / 2 + 2 * (int64_t)tl.size() + 64;
-    GP_TRY(sw->ck.grow(h, total));
-    double* ap = sw->ck;
-    auto take = [&](int64_t c) { double* r = ap; ap += (c + 1) / 2 * 2; return r; };    // keeps 16-byte alignment
-    ThetaDev* thp = (ThetaDev*)take(th_d);
-    double* LP = take(npU * ldU);
-    double *Zg = take(npU * cols), *Hm = take(npU * cols);
-    double *g0 = take(Sg0 * big), *g1 = take(Sg0 * big), *g2 = take(Sg0 * big);
-    double *R0 = take((int64_t)J * np * Sp), *R1 = take((int64_t)J * np * Sp);
-    double *Bst = take(rowsP * np), *Gs = take(rowsP * mc);
-    double *pa = take(Sg0 * pmax * mc), *pb = take(Sg0 * pmax * mc);
-    double *RX = take(sum_nu), *RT = take(sum_mu);
-    int32_t* iX = (int32_t*)take((Ns + 1) / 2);
-    int32_t* iT = (int32_t*)take((Ms + 1) / 2);
-    int32_t* ic = (int32_t*)take((sum_n + 1) / 2);
-    int32_t* it = (int32_t*)take((sum_m + 1) / 2);
-    TileDesc* tiles = (TileDesc*)take(2 * (int64_t)tl.size());
-    HIP_TRY(hipMemcpyAsync(iX, irow_train, (size_t)Ns * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(iT, irow_test, (size_t)Ms * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(ic, idx_train, (size_t)sum_n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(it, idx_test, (size_t)sum_m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(tiles, tl.data(), tl.size() * sizeof(TileDesc), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // the host arrays are the caller's
-    const TileDesc *t_prior = tiles, *t_nn = tiles + n_prior, *t_tn = t_nn + n_solve;
-
-    {   // the blocks: theta, the complete axes, L_j^-1, and the mean's beta as gpimhip_predict_pkron computes it
-        StageTimer t(h, 6);
-        GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, false));
-        GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
-    }
-    const double* bmat[KMAXD];
-    {
-        StageTimer t(h, 3);
-        int toff = 0;
-        int64_t ko = 0;
-        for (int i = 0; i < dc; ++i) {
-            double* Kc = w->cross + ko;
-            double* Bc = w->cross + sum_mn + ko;
-            GP_TRY(kron_cross(h, dv, w->th3 + PK_TH_AXES, axes_test_c, toff, n_test_c[i], i, Kc));
-            GP_TRY(modeprod(h, Kc, Bc, dv.Qt + dv.moff[i], n_c[i], n_c[i], n_c[i], 0, 0, n_test_c[i], 1));
-            bmat[i] = Bc;
-            toff += n_test_c[i];
-            ko += (int64_t)n_test_c[i] * n_c[i];
-        }
-    }
-    const double *rxm[KMAXD], *rtm[KMAXD], *qtm[KMAXD];
-    int ldu[KMAXD], ldn[KMAXD];
-    {   // the union of the complete axes and the rows of its root at the training and at the test coordinates
-        StageTimer t(h, 2);
-        if (!shared) GP_TRY(kron_eig_axes(h, sw->ck_un, w->th3 + PK_TH_AXES));
-        int64_t xo = 0, to = 0;
-        for (int i = 0, oc = 0, ot = 0; i < dc; ++i) {
-            GP_TRY(kron_root_rows(h, du, i, ic + oc, n_c[i], RX + xo));
-            GP_TRY(kron_root_rows(h, du, i, it + ot, n_test_c[i], RT + to));
-            rxm[i] = RX + xo; rtm[i] = RT + to; qtm[i] = dv.Qt + dv.moff[i];
-            ldu[i] = n_union[i]; ldn[i] = n_c[i];
-            xo += (int64_t)n_c[i] * n_union[i]; to += (int64_t)n_test_c[i] * n_union[i];
-            oc += n_c[i]; ot += n_test_c[i];
-        }
-    }
-    {   // L_P = chol(s2 K_s(P, P) + d I); its status goes into the word of the call (NOT_PD at the closing check)
-        StageTimer t(h, 4);
-        GP_TRY(launch_pkron_prior_theta(h, w->th3, thp));
-        GP_TRY(launch_kmat(sub, &ms, P, Us, nullptr, Us, thp, jitter, 0, LP, ldU, npU, npU, 1, 1, 0, 0, 0));
-        GP_TRY(launch_potrf(sub, LP, npU, ldU, h->info));
-        // the factorisation leaves the strict upper triangle of the diagonal blocks as the covariance build wrote it
-        GP_TRY(launch_pkron_tril(h, LP, ldU, nbU));
-    }
-    const double* ze = Z + Us * U;
-    const double* zn = ze + NJ;
-    for (int s0 = 0; s0 < S; s0 += Sg0) {
-        const int Sg = std::min(Sg0, S - s0);
-        double *gX, *res, *gs;
-        {   // H = L_P zeta for the Sg U columns of the group, then g_X = H[i_X, :] x_i R_i[ic_i, :]
-            StageTimer t(h, 2);
-            GP_TRY(launch_pkron_zeta(h, Z, zw, Us, U, s0, Sg, npU, cols, Zg));
-            GemmArgs g = gemm_args(LP, ldU, Zg, cols, Hm, cols, 1.0, 0.0, t_prior, n_prior, 0);
-            g.chunk = deal_chunk(g.ntiles);
-            GP_TRY(launch_gemm(sub, false, true, EPI_STORE, g));
-            GP_TRY(launch_pkron_gather(h, Hm, cols, iX, Ns, U, Sg, g0));
-            GP_TRY(tensor_apply(h, dc, n_union, mp.nc, rxm, ldu, 0, 0, g0, g1, g2, &gX, (int64_t)Sg * Ns));
-        }
-        {   // r = -g_X - sqrt(sigma) z_e, r~ = r x_i Q_i^T, beta_j = L_j^-T (L_j^-1 r~_j) for the J blocks and all draws
-            StageTimer t(h, 3);
-            GP_TRY(launch_pkron_resid(h, ze, zw, s0, NJ, Sg, w->th3, gX));
-            double* other = gX == g1 ? g2 : g1;
-            GP_TRY(tensor_apply(h, dc, mp.nc, mp.nc, qtm, ldn, 0, 0, gX, other, gX, &res, (int64_t)Sg * Ns));
-            GP_TRY(launch_pkron_scatter_multi(h, res, Ns, J, Sg, Sp, R0));
-            // (a ragged launch stores no row of the padding of the last block: GemmArgs::rag)
-            if (rag) HIP_TRY(hipMemsetAsync(R1, 0, (size_t)((int64_t)J * np * Sp) * sizeof(double), h->stream));
-            GemmArgs g = gemm_args(h->A, h->ld, R0, Sp, R1, Sp, 1.0, 0.0, t_nn, n_solve, np);
-            g.chunk = deal_chunk(g.ntiles);
-            g.rag = rag;
-            GP_TRY(launch_gemm(h, false, true, EPI_STORE, g));
-            if (rag) HIP_TRY(hipMemsetAsync(R0, 0, (size_t)((int64_t)J * np * Sp) * sizeof(double), h->stream));
-            g = gemm_args(h->A, h->ld, R1, Sp, R0, Sp, 1.0, 0.0, t_tn, n_solve, np);
-            g.chunk = deal_chunk(g.ntiles);
-            g.krev = 1;
-            g.rag = rag;
-            GP_TRY(launch_gemm(h, true, true, EPI_STORE, g));
-            GP_TRY(launch_pkron_beta_stack(h, R0, Ns, J, Sg, Sp, rowsP, Bst));
-        }
-        {   // g_* = H[i_*, :] x_i R_i[it_i, :]
-            StageTimer t(h, 2);
-            GP_TRY(launch_pkron_gather(h, Hm, cols, iT, Ms, U, Sg, g0));
-            GP_TRY(tensor_apply(h, dc, n_union, n_test_c, rtm, ldu, 0, 0, g0, g1, g2, &gs, (int64_t)Sg * Ms));
-        }
-        for (int64_t m0 = 0; m0 < Ms; m0 += mc) {
-            const int64_t cnt = std::min(mc, Ms - m0), cpad = pad_to(cnt, NB);
-            const double* upd;
-            {
-                StageTimer t(h, 3);
-                {
-                    BatchScope one(h, 1);
-                    GP_TRY(launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0));
-                }
-                if (s0 == 0) {      // the mean: the launches of gpimhip_predict_pkron's
-                    GP_TRY(pkron_times_b(h, w, J, h->Ks, kld, cpad, w->G, mc));
-                    const double* cur = w->G;
-                    double* bufa = w->pp;
-                    double* bufb = bufa + pmax * mc;
-                    double* dst = bufa;
-                    for (int i = 0; i < dc; ++i) {
-                        int64_t pre = 1, post = mc;
-                        for (int k = 0; k < i; ++k) pre *= n_test_c[k];
-                        for (int k = i + 1; k < dc; ++k) post *= n_c[k];
-                        GP_TRY(modeprod(h, cur, dst, bmat[i], n_test_c[i], n_c[i], n_c[i], 0, 0, pre, post));
-                        cur = dst;
-                        dst = (dst == bufa) ? bufb : bufa;
-                    }
-                    GP_TRY(launch_pkron_mean(h, w->th3, Mc, mc, m0, cnt, cur, mean_out));
-                }
-                // G = B K*_s with the draws' solutions stacked as rows, then the mode products with b_i, batch Sg
-                GP_TRY(pkron_rows_times(h, Bst, rowsP, h->Ks, kld, cpad, Gs, mc));
-                const double* cur = Gs;
-                double* dst = pa;
-                for (int i = 0; i < dc; ++i) {
-                    int64_t pre = Sg, post = mc;
-                    for (int k = 0; k < i; ++k) pre *= n_test_c[k];
-                    for (int k = i + 1; k < dc; ++k) post *= n_c[k];
-                    GP_TRY(modeprod(h, cur, dst, bmat[i], n_test_c[i], n_c[i], n_c[i], 0, 0, pre, post));
-                    cur = dst;
-                    dst = (dst == pa) ? pb : pa;
-                }
-                upd = cur;
-            }
-            StageTimer t(h, 5);
-            GP_TRY(launch_pkron_draw(h, w->th3, Mc, mc, m0, cnt, Ms, s0, Sg, gs, upd, mean_out, zn, zw, noiseless ? 1 : 0,
-                                     samples_out));
-        }
-    }
-    return finish_and_check(h);
-}
-
-int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
-                         const double* u, const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless,
-                         double jitter, double* mean_out, double* var_out, double* samples_out) {
-    FP64_ONLY(h);
-    if (!h || !X || !y || !u || !Xs || !Z || !samples_out || N < 1 || M < 1 || S < 1 || !(jitter >= 0.0))
-        return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
-    if (h->refl.mask) {
-        gpim_set_error("gpimhip_sample_exact: not available in reflection mode (the dense double-precision engine only)");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_impl(h, stationary_family(m, u), X, y, N, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
-}
-
-// ---- the same three draws for the spectral-mixture model: the drivers above with sm_family.  sm_check
-// refuses a handle in reflection mode, as the entries above do.
-int gpimhip_sample_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N, const double* u,
-                      const double* Xs, int64_t M, const double* Z, int32_t S, int32_t noiseless, double jitter,
-                      double* mean_out, double* var_out, double* samples_out) {
-    GP_TRY(sm_check(h, sm, X, N));
-    if (!y || !u || !Xs || !Z || !samples_out || M < 1 || S < 1 || !(jitter >= 0.0)) return GPIMHIP_E_BADARG;
-    return sample_impl(h, sm_family(h, sm, u), X, y, N, Xs, M, Z, S, noiseless ? 1 : 0, jitter, mean_out, var_out, samples_out);
-}
-
-int gpimhip_sample_sm_pathwise(gpimhip_handle h, const gpimhip_sm_t* sm, const double* G, const int32_t* shape, int32_t mask,
-                               const double* twoc, const int64_t* idx, const double* y, int64_t N, const double* u,
-                               const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out,
-                               double* samples_out) {
-    GP_TRY(sm_check(h, sm, G, N));
-    if (!shape || !twoc || !idx || !y || !u || !Z || !samples_out || S < 1 || S > 65535 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
-    PwGrid gd;
-    const int64_t M = pw_grid(sm->dim, shape, mask, &gd);
-    if (M < 1) return GPIMHIP_E_BADARG;
-    if (!mask || (mask >> sm->dim)) {
-        gpim_set_error("gpimhip_sample_sm_pathwise: needs at least one reflected axis of the grid");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_pathwise_impl(h, sm_family(h, sm, u), gd, twoc, G, M, idx, y, N, Z, S, noiseless ? 1 : 0, jitter, mean_out,
-                                samples_out);
-}
-
-int gpimhip_sample_sm_blocks(gpimhip_handle h, const gpimhip_sm_t* sm, const double* G, const int32_t* shape, int32_t mask,
-                             const double* twoc, const double* y, const double* u, const double* Z, int32_t S, int32_t noiseless,
-                             double jitter, double* mean_out, double* samples_out) {
-    GP_TRY(sm_check(h, sm, G, 1));
-    if (!shape || !twoc || !y || !u || !Z || !samples_out || S < 1 || S > 65534 || !(jitter > 0.0)) return GPIMHIP_E_BADARG;
-    PwGrid gd;
-    const int64_t M = pw_grid(sm->dim, shape, mask, &gd);
-    if (M < 1) return GPIMHIP_E_BADARG;
-    if (!mask || (mask >> sm->dim)) {
-        gpim_set_error("gpimhip_sample_sm_blocks: needs at least one reflected axis of the grid");
-        return GPIMHIP_E_BADARG;
-    }
-    return sample_blocks_impl(h, sm_family(h, sm, u), gd, twoc, G, M, y, Z, S, noiseless ? 1 : 0, jitter, 0.0, mean_out, samples_out);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// border.hpp -- launches of the border form of the reflection blocks (border.hip; driven by api.hip: border_*).
+// border.hpp -- launches of the border form of the reflection blocks (border.hip; driven by api.hip: border_* and draws.hip: sample_border_impl).
 #pragma once
 #include "common.hpp"
 
@@ -26,6 +26,9 @@ struct BorderWs {
     DevBuf<double> rsq;             // T x r_cols: column sums of squares of R
     int64_t r_cols = 0;
 };
+// api.hip: the handle's border (null: none was ever set), and whether one is in force
+BorderWs* bws(const gpimhip_ctx* h);
+bool border_on(const gpimhip_ctx* h);
 
 int launch_border_gather_s(gpimhip_ctx* h, const BorderWs* w, const double* Binv, int64_t ld, double* S, int64_t lds);
 int launch_border_tidy(gpimhip_ctx* h, const BorderWs* w, double* Linv, int64_t lds);

@@ -222,7 +222,7 @@ struct gpimhip_ctx {
     void* sm = nullptr;
     // border of the reflection blocks (missing points of an incomplete grid), owned by api.hip (BorderWs); border_release()
     void* border = nullptr;
-    // joint posterior draws: the (N + M)^2 matrix and its factorisation context, owned by api.hip (SampleWs); sample_release()
+    // joint posterior draws: the (N + M)^2 matrix and its factorisation context, owned by draws.hip (SampleWs); sample_release()
     void* sample = nullptr;
     DevBuf<double> refine;          // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
@@ -274,6 +274,19 @@ struct BatchScope {
     } while (0)
 
 static inline int64_t pad_to(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
+// Carves pieces off one arena of doubles.  Every piece starts at an even offset (16-byte alignment), i.e. the piece before
+// it is rounded up to an even count; `used` is the total once the last piece is taken.  With base == nullptr take() only
+// counts -- the sizing pass, before the buffer exists; the same list of takes with the buffer then hands out the pointers.
+struct Carve {
+    double* base;
+    int64_t used = 0;
+    explicit Carve(double* b) : base(b) {}
+    template <typename T = double> T* take(int64_t doubles) {
+        const int64_t off = (used + 1) & ~(int64_t)1;
+        used = off + doubles;
+        return base ? (T*)(base + off) : nullptr;
+    }
+};
 // GemmArgs::rag for an exact-GP matrix of N valid rows padded to np with the identity
 static inline int rag_of(int64_t N, int64_t np) {
     const int64_t last = N - (np - NB);
@@ -303,8 +316,16 @@ static inline int gemv_tri_rc(int64_t np) {
 }
 static inline int gemv_tri_chunks(int64_t np) { return (int)((np + gemv_tri_rc(np) - 1) / gemv_tri_rc(np)); }
 // api.hip
+#define OUTER_W 4    // outer Cholesky panel = 4 x 128 columns
 int ws_ensure(gpimhip_ctx* h, int64_t N);
+int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices = true);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
+int deal_chunk(int ntiles = 1 << 30);
+int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
+                     int B, const double* u);
+// draws.hip
+void sample_release(gpimhip_ctx* h);
+int64_t sample_bytes(const gpimhip_ctx* h);
 // The preamble of a fit call: info[1] = "completed" = huge until a failure, fit_completed = T and, for T > 0, the
 // bias-correction table, then the Adam state (adam_bytes at adam_m and, where the two halves are buffers of their own, at
 // adam_v) and the iteration counter zeroed.  What a fit of T == 0 returns is the caller's business.
@@ -350,7 +371,7 @@ int launch_colsumsq_acc(gpimhip_ctx* h, const double* W, int64_t ldw, int rows, 
 int launch_dist_trsv(gpimhip_ctx* h, const double* P, int64_t ld, const double* D, int nblk, int backward, const double* r0,
                      const double* r1, double* out);
 int launch_dist_rows_acc(gpimhip_ctx* h, const double* A, int64_t ld, int64_t rows, int w, const double* x, double* acc);
-// the same for a group of ncols (1 .. 8) columns per sweep, column c at its pointer + c * (its column stride): api.hip
+// the same for a group of ncols (1 .. 8) columns per sweep, column c at its pointer + c * (its column stride): draws.hip
 // blocks_solve.  r1: nch chunks (stride r1_chs) of partial sums, added in their order and taken off r0; part of
 // launch_gemv_t_multi: gemv_t_multi_chunks(nrows) x multi_group_width(ncols) x 512 doubles.
 #define GEMV_T_MULTI_RC 1024
@@ -476,6 +497,8 @@ struct GemmArgs {
 };
 int launch_gemm(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);
 int launch_gemm_f32(gpimhip_ctx* h, bool a_km, bool b_km, int epi, const GemmArgs& g);   // gemm32.hip
+GemmArgs gemm_args(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, double alpha, double beta,
+                   const TileDesc* tiles, int n, int64_t rows);                           // api.hip
 
 // The workgroup shape of a tile-engine launch (NW waves on a TSM x TSN part of each 128 x 128 tile; gemm_body.hpp), chosen
 // from the launch's tile count by gemm_shape_f64 (gemm.hip) / gemm_shape_f32 (gemm_kernel.hpp, gemm32.hip); the values are

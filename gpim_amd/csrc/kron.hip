@@ -82,8 +82,7 @@ int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool 
     for (int i = 0; i < d; ++i) { N *= n[i]; a.sum_n += n[i]; a.sum_n2 += (int64_t)n[i] * n[i]; }
     const int64_t count = (grad ? 3 : 2) * a.sum_n + (grad ? 7 : 5) * a.sum_n2 + 32;
     GP_TRY(a.arena.alloc(h, count, "hipMalloc failed (structured-GP axis workspace)"));
-    double* p = a.arena;
-    auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
+    Carve c(a.arena);
     KronDev& dv = a.dev;
     memset(&dv, 0, sizeof(dv));
     dv.d = d; dv.N = N;
@@ -92,9 +91,9 @@ int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool 
         dv.n[i] = a.n[i]; dv.off[i] = off; dv.moff[i] = moff;
         if (i < d) { off += n[i]; moff += (int64_t)n[i] * n[i]; }
     }
-    dv.coords = take(a.sum_n); dv.lam = take(a.sum_n);
-    dv.K = take(a.sum_n2); dv.W = take(a.sum_n2); dv.Qt = take(a.sum_n2); dv.Tt = take(a.sum_n2); dv.Vr = take(a.sum_n2);
-    if (grad) { dv.mdiag = take(a.sum_n); dv.E = take(a.sum_n2); dv.Mm = take(a.sum_n2); }
+    dv.coords = c.take(a.sum_n); dv.lam = c.take(a.sum_n);
+    dv.K = c.take(a.sum_n2); dv.W = c.take(a.sum_n2); dv.Qt = c.take(a.sum_n2); dv.Tt = c.take(a.sum_n2); dv.Vr = c.take(a.sum_n2);
+    if (grad) { dv.mdiag = c.take(a.sum_n); dv.E = c.take(a.sum_n2); dv.Mm = c.take(a.sum_n2); }
     return GPIMHIP_OK;
 }
 
@@ -115,11 +114,10 @@ static int kron_ensure(gpimhip_ctx* h, int d, const int32_t* n, KronWs** out) {
     w.nblk = (int)std::min<int64_t>(1024, (w.N + 255) / 256);
     const int64_t count = (4 + d) * w.N + (int64_t)w.nblk * 16 + 32;
     GP_TRY(w.arena.alloc(h, count, "hipMalloc failed (structured-GP workspace)"));
-    double* p = w.arena;
-    auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };    // keep 16-byte alignment
-    w.yt = take(w.N); w.at = take(w.N); w.t1 = take(w.N); w.t2 = take(w.N);
-    w.Z = take((int64_t)d * w.N);
-    w.part = take((int64_t)w.nblk * 16);
+    Carve c(w.arena);
+    w.yt = c.take(w.N); w.at = c.take(w.N); w.t1 = c.take(w.N); w.t2 = c.take(w.N);
+    w.Z = c.take((int64_t)d * w.N);
+    w.part = c.take((int64_t)w.nblk * 16);
     return GPIMHIP_OK;
 }
 
@@ -838,9 +836,8 @@ static int kron_predict_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* n_te
         w.parena.release(h);
         const int64_t count = sum_m + 2 * sum_mn + 2 * pmax + 64;
         GP_TRY(w.parena.alloc(h, count, "hipMalloc failed (structured-GP prediction workspace)"));
-        double* p = w.parena;
-        auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
-        w.tcoords = take(sum_m); w.Ks = take(sum_mn); w.Bs = take(sum_mn); w.p1 = take(pmax); w.p2 = take(pmax);
+        Carve c(w.parena);
+        w.tcoords = c.take(sum_m); w.Ks = c.take(sum_mn); w.Bs = c.take(sum_mn); w.p1 = c.take(pmax); w.p2 = c.take(pmax);
         int64_t ko = 0;
         for (int i = 0; i < KMAXD; ++i) {
             w.m[i] = i < d ? n_test[i] : 1;
@@ -893,11 +890,10 @@ static int kron_sample_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* nu, i
     for (int i = 0; i < d; ++i) { sum_n += w.n[i]; sum_m += w.m[i]; }
     const int64_t count = sum_gu + sum_tu + (sum_n + sum_m + 4) / 2 + S * PU + 2 * S * smax + 32;
     GP_TRY(w.sarena.alloc(h, count, "hipMalloc failed (structured-GP posterior-draw workspace)"));
-    double* p = w.sarena;
-    auto take = [&](int64_t c) { double* r = p; p += (c + 1) / 2 * 2; return r; };
-    w.RG = take(sum_gu); w.RT = take(sum_tu);
-    w.ic = (int32_t*)take((sum_n + 1) / 2); w.it = (int32_t*)take((sum_m + 1) / 2);
-    w.Zc = take(S * PU); w.sa = take(S * smax); w.sb = take(S * smax);
+    Carve c(w.sarena);
+    w.RG = c.take(sum_gu); w.RT = c.take(sum_tu);
+    w.ic = c.take<int32_t>((sum_n + 1) / 2); w.it = c.take<int32_t>((sum_m + 1) / 2);
+    w.Zc = c.take(S * PU); w.sa = c.take(S * smax); w.sb = c.take(S * smax);
     int64_t go = 0, to = 0;
     for (int i = 0; i < KMAXD; ++i) {
         w.rgoff[i] = go; w.rtoff[i] = to;

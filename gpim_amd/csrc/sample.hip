@@ -1,6 +1,6 @@
 // sample.hip -- joint draws from the posterior of the exact GP (gpimhip_sample_exact).
 //
-// The joint covariance J of the stacked points [X; Xs] is factored once by the engine's Cholesky (api.hip:
+// The joint covariance J of the stacked points [X; Xs] is factored once by the engine's Cholesky (draws.hip:
 // sample_impl).  In chol(J) = [[L11, 0], [L21, L22]] the right-looking factorisation has formed the Schur complement on
 // its way: L21 = (L11^-1 K*)^T and L22 = chol(K** - K*^T K^-1 K* + d I), so with z = L11^-1 y and one row
 // [z; z_s] per draw everything the caller wants is a product with the trapezoid L[N:, :]:
@@ -188,7 +188,7 @@ int launch_sample_draws(gpimhip_ctx* h, const double* L, int64_t ld, int64_t N, 
 
 // ==========================================================================================
 // Pathwise draws (gpimhip_sample_pathwise): a prior draw on the complete grid G through its
-// reflection blocks, then one mean-type update against the training factor.  api.hip: sample_pathwise_impl.
+// reflection blocks, then one mean-type update against the training factor.  draws.hip: sample_pathwise_impl.
 // ==========================================================================================
 // multi-index of a row-major linear index over the extents ext[0 .. d)
 __device__ __forceinline__ void pw_unravel(int64_t p, const int* ext, int d, int* ix) {
@@ -454,7 +454,7 @@ int launch_pw_scatter(gpimhip_ctx* h, const int64_t* idx, int64_t N, int64_t M, 
 
 // ==========================================================================================
 // Draws on a fully observed grid through its reflection blocks alone (gpimhip_sample_blocks): with
-// observations on every grid point the whole recipe above is block diagonal in the basis U.  api.hip: sample_blocks_impl.
+// observations on every grid point the whole recipe above is block diagonal in the basis U.  draws.hip: sample_blocks_impl.
 // ==========================================================================================
 // E[b][s][p] = (U v_s)_{b,p}: v_s = Z[s][ze_off + .] for s < S, y for s == S -- the transpose of pw_basis_t_kernel.  The
 // distinct mirror images of p are added in the order of the reflections; rows of points absent from block b and the padding
@@ -580,7 +580,7 @@ int launch_pw_blocks_out(gpimhip_ctx* h, const double* g, int64_t M, int S, cons
 // ==========================================================================================
 // Draws on a grid with MISSING points through the bordered reflection blocks (gpimhip_sample_border).
 // The model's prediction state is all there is to solve against: the explicit inverse factors L_b^-1 of the completed grid's
-// blocks, and S, L_S^-1, Y_b of the border.  api.hip: sample_border_impl.  Vectors are stored block-major, S + 1 columns of
+// blocks, and S, L_S^-1, Y_b of the border.  draws.hip: sample_border_impl.  Vectors are stored block-major, S + 1 columns of
 // np per block (column S: y); every reduction below has a fixed order and every column accumulates by itself.
 // ==========================================================================================
 __device__ __forceinline__ double bs_wave_sum(double v) {

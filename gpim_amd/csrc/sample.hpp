@@ -1,4 +1,4 @@
-// sample.hpp -- shared declarations of the joint posterior draws (sample.hip kernels, api.hip driver).
+// sample.hpp -- shared declarations of the joint posterior draws (sample.hip kernels, draws.hip drivers).
 #pragma once
 #include "common.hpp"
 

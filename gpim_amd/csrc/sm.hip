@@ -781,7 +781,7 @@ __global__ void sm_addc_kernel(double* mean, int64_t n, const SmDev* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// posterior draws (api.hip: the spectral-mixture side of the draw drivers)
+// posterior draws (draws.hip: sm_family, the spectral-mixture side of the draw drivers)
 // ------------------------------------------------------------------------------------------
 // the constrained parameters at u into st[0] and theta (one thread), and st[1] = st[0] with `other` as its diagonal term: the
 // covariance builders put st->noise on the diagonal, and a draw also builds K_b + d I (prior blocks) and the joint matrix

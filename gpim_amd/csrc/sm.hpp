@@ -1,6 +1,10 @@
-// sm.hpp -- shared declarations of the spectral-mixture kernel (sm.hip kernels, api.hip drivers).
+// sm.hpp -- shared declarations of the spectral-mixture kernel (sm.hip kernels, api.hip drivers, draws.hip: sm_family).
 #pragma once
 #include "common.hpp"
+
+// api.hip: the argument check of every spectral-mixture entry.  B = 0: a dense entry point (no reflection mode); B > 0: the
+// blocks of a handle in reflection mode
+int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B = 0);
 
 #define SM_MAXQ GPIMHIP_SM_MAX_MIXTURES
 #define SM_MAXP (2 + SM_MAXQ * (2 * GPIMHIP_MAX_DIM + 1))

@@ -1,6 +1,9 @@
-// vgp.hpp -- shared declarations of the multi-output GP (vgp.hip kernels, api.hip drivers).
+// vgp.hpp -- shared declarations of the multi-output GP (vgp.hip kernels, api.hip drivers, draws.hip: sample_vgp_*).
 #pragma once
 #include "common.hpp"
+
+// api.hip: the argument check of every multi-output entry
+int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y, int64_t N);
 
 #define VGP_MAXT GPIMHIP_VGP_MAX_TASKS
 #define VGP_MAXR GPIMHIP_VGP_MAX_TASKS      // IndexKernel rank <= T
@@ -45,7 +48,7 @@ struct VgpDev {
 // pattern b); launch_vgp_finalize takes 0 for the dense model
 int launch_vgp_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st, int nrep);
 int launch_vgp_project(gpimhip_ctx* h, const double* Y, int64_t N, int T, const VgpDev* st);
-// the same two launches with caller-owned results (the multi-output draws, api.hip: sample_vgp_impl): the T blocks' theta
+// the same two launches with caller-owned results (the multi-output draws, draws.hip: sample_vgp_impl): the T blocks' theta
 // into `theta` (T entries) instead of h->theta, and z as plain T x N rows (no padding) instead of h->ypad
 int launch_vgp_setup_to(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* u, VgpDev* st,
                         ThetaDev* theta);

@@ -1,0 +1,135 @@
+"""Prints the SHA-256 of what the public sample() / predict() calls return on a fixed set of small cases, one line per case.
+
+    python tests/tools/draw_hashes.py
+
+For refactors of the draw and prediction drivers that must not change a bit: run it on the commit before and on the commit
+after, on the same machine, and diff the two printouts by hand.  It compares nothing and stores nothing.  The models are
+not trained (the hyper-parameters are the seeded initial ones); every draw takes S = 9 samples, two draw groups (8 + 1).
+The cases, each for a branch of csrc/draws.hip, the prediction of the dense-by-Kronecker blocks in csrc/api.hip or the
+workspaces of csrc/kron.hip:
+  joint      N = 300, M = 340 (the training rows end in block row 3 of 5) with an explicit z; N = 40, M = 20 (one block)
+  pathwise   48 x 48 grid, both axes reflected (576-point blocks: two panels), 600 observed pixels; with noise and noiseless
+  blocks     the same grid, fully observed;  border: the same grid with 5 missing pixels
+  vgp        T = 2 outputs on a 16 x 16 grid: joint and blocks
+  spectral   Q = 2 mixtures on a 16 x 16 grid: joint, pathwise and blocks
+  columns    a (48, 6, 5) cube, 37 of the 48 rows along the first axis observed, drawn and predicted at 11 new rows times the
+             training axes (the union axes are the training axes), and with new coordinates on one complete axis
+  kron       a fully observed 12 x 10 grid
+"""
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+import gpim_amd  # noqa: E402
+
+S = 9
+LS2 = [[1., 1.], [8., 8.]]
+
+
+def sha(*arrays):
+    return " ".join(hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest() for a in arrays)
+
+
+def image(shape, n_obs=None, seed=0):
+    """(y with NaN at the unobserved pixels, the full image)"""
+    rng = np.random.default_rng(seed)
+    ii, jj = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), indexing="ij")
+    full = np.sin(ii / 3.0) * np.cos(jj / 4.0) + 0.05 * rng.standard_normal(shape)
+    R = full.copy()
+    if n_obs is not None:
+        R.ravel()[rng.permutation(full.size)[n_obs:]] = np.nan
+    return R, full
+
+
+def grid(*axes):
+    return np.array(np.meshgrid(*axes, indexing="ij"))
+
+
+def sparse_and_full(R):
+    return gpim_amd.utils.get_sparse_grid(R), gpim_amd.utils.get_full_grid(R)
+
+
+def columns_cube():
+    """(X with NaN, y with NaN) of a (48, 6, 5) cube with 37 of the 48 rows along axis 0 observed"""
+    rng = np.random.default_rng(1)
+    Xg = grid(np.arange(48.0), np.arange(6.0), np.arange(5.0))
+    y = np.cos(Xg[0] / 7.0) * np.sin(Xg[1] / 2.0 + 0.3) + 0.4 * np.cos(Xg[2] / 2.5) + 0.05 * rng.standard_normal(Xg.shape[1:])
+    gone = rng.permutation(48)[37:]
+    X = Xg.copy()
+    X[:, gone] = np.nan
+    y[gone] = np.nan
+    return X, y
+
+
+def cases():
+    """(name, thunk returning the arrays to hash) in a fixed order"""
+    kw = dict(lengthscale=LS2, verbose=0)
+    # ---- joint
+    R, _ = image((20, 17), 300)
+    Xs, Xf = sparse_and_full(R)
+    r = gpim_amd.reconstructor(Xs, R, Xf, kernel="Matern52", **kw)
+    z = np.random.default_rng(5).standard_normal((S, 340))
+    yield "joint N=300 M=340", lambda: (r.sample(S, z=z),)
+    yield "joint N=300 M=340 noiseless", lambda: (r.sample(S, z=z, noiseless=True),)
+    yield "predict N=300 M=340", lambda: r.predict(verbose=0)
+    _, full = image((8, 5))
+    r1 = gpim_amd.reconstructor(gpim_amd.utils.get_full_grid(full), full, grid(np.arange(5) + 0.5, np.arange(4) + 0.25),
+                                kernel="RBF", **kw)
+    yield "joint N=40 M=20", lambda: (r1.sample(S, seed=3),)
+    # ---- pathwise, blocks, border on a 48 x 48 grid
+    R, full = image((48, 48), 600)
+    Xs, Xf = sparse_and_full(R)
+    rp = gpim_amd.reconstructor(Xs, R, Xf, kernel="Matern52", **kw)
+    yield "pathwise 48x48 N=600", lambda: (rp.sample(S, seed=1, method="pathwise"),)
+    yield "pathwise 48x48 N=600 noiseless", lambda: (rp.sample(S, seed=1, noiseless=True, method="pathwise"),)
+    rb = gpim_amd.skreconstructor(Xf, full, Xf, kernel="Matern52", **kw)
+    yield "blocks 48x48 (%s)" % rb.solver, lambda: (rb.sample(S, seed=2, method="blocks"),)
+    yield "blocks 48x48 noiseless", lambda: (rb.sample(S, seed=2, noiseless=True, method="blocks"),)
+    Rm = full.copy()
+    for hole in ((3, 4), (9, 2), (20, 31), (40, 7), (47, 47)):
+        Rm[hole] = np.nan
+    rm = gpim_amd.skreconstructor(gpim_amd.utils.get_sparse_grid(Rm), Rm, Xf, kernel="Matern52", **kw)
+    yield "border 48x48 5 missing (%s)" % rm.solver, lambda: (rm.sample(S, seed=3, method="border"),)
+    yield "predict border 48x48", lambda: rm.predict(verbose=0)
+    # ---- the multi-output model, T = 2
+    _, f16 = image((16, 16))
+    X16 = gpim_amd.utils.get_full_grid(f16)
+    Y = np.stack([f16, np.cos(f16) + 0.1 * image((16, 16), seed=4)[1]], -1)
+    for solver, method in (("dense", "joint"), ("reflection", "blocks")):
+        rv = gpim_amd.vreconstructor(X16.astype(np.float64), Y, X16, kernel="Matern52", solver=solver, **kw)
+        yield "vgp %s T=2 16x16 (%s)" % (method, rv.solver), lambda rv=rv, method=method: (rv.sample(S, seed=4, method=method),)
+    # ---- the spectral mixture, Q = 2
+    R16, _ = image((16, 16), 200)
+    Xs16 = gpim_amd.utils.get_sparse_grid(R16)
+    rs = gpim_amd.skreconstructor(Xs16, R16, X16, kernel="Spectral", n_mixtures=2, verbose=0)
+    yield "spectral joint Q=2 16x16 N=200", lambda: (rs.sample(S, seed=5, method="joint"),)
+    yield "spectral pathwise Q=2 16x16 N=200", lambda: (rs.sample(S, seed=5, method="pathwise"),)
+    rsf = gpim_amd.skreconstructor(X16, f16, X16, kernel="Spectral", n_mixtures=2, verbose=0)
+    yield "spectral blocks Q=2 16x16 (%s)" % rsf.solver, lambda: (rsf.sample(S, seed=5, method="blocks"),)
+    # ---- the dense-by-Kronecker blocks
+    Xc, yc = columns_cube()
+    rc = gpim_amd.skreconstructor(Xc, yc, None, kernel="RBF", lengthscale=[[0.5] * 3, [20.0] * 3], verbose=0)
+    rows = np.arange(11) * 4.0 + 0.5
+    for name, taxes in (("shared union", (rows, np.arange(6.0), np.arange(5.0))),
+                        ("own union", (rows, np.arange(6.0) + 0.25, np.arange(5.0)))):
+        Xt = grid(*taxes)
+        yield "columns sample, %s (%s)" % (name, rc.solver), lambda Xt=Xt: (rc.sample(S, seed=6, Xtest=Xt, method="columns"),)
+        yield "columns predict, %s" % name, lambda Xt=Xt: rc.predict(Xt, verbose=0)
+    # ---- the Kronecker model
+    _, fk = image((12, 10))
+    Xk = gpim_amd.utils.get_full_grid(fk)
+    rk = gpim_amd.reconstructor(Xk, fk, Xk, kernel="RBF", structured=True, **kw)
+    yield "kron sample 12x10", lambda: (rk.sample(S, seed=7, method="kron"),)
+    yield "kron predict 12x10", lambda: rk.predict(verbose=0)
+
+
+def main():
+    for name, run in cases():
+        print("%-44s %s" % (name, sha(*run())), flush=True)
+
+
+if __name__ == "__main__":
+    main()
