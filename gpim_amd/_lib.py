@@ -221,6 +221,11 @@ _PROTOS = {
                                                   ctypes.POINTER(ctypes.c_int32)]),
     "gpimhip_gemm_rect_tile_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    # (h, d, n, axes, ls, warm, lam_out, Qt_out, nprob_out, plan_out, rot_out, cap_out)
+    "gpimhip_kron_eigh": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), c_dp,
+                                         ctypes.POINTER(ctypes.c_double), ctypes.c_int32, c_dp, c_dp,
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]),
     "gpimhip_vgp_nll_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp,
                                             c_dp, ctypes.c_int64, c_dp, c_dp, c_dp]),
     "gpimhip_fit_vgp": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.POINTER(VgpStruct), c_dp, c_dp,

@@ -58,12 +58,15 @@ struct KronWs {
     double *RG = nullptr, *RT = nullptr, *Zc = nullptr, *sa = nullptr, *sb = nullptr;
     int32_t *ic = nullptr, *it = nullptr;
     int64_t rgoff[KMAXD] = {0, 0, 0, 0}, rtoff[KMAXD] = {0, 0, 0, 0};
+    // the axis set of the diagnostic gpimhip_kron_eigh (its own: the rotations it leaves in Vr are no fit's warm start)
+    KronAxes dg;
+    bool dg_ready = false;       // dg holds the rotations of a completed call (what warm = 1 continues from)
 };
 
 void kron_release(gpimhip_ctx* h) {
     KronWs* w = static_cast<KronWs*>(h->kron);
     if (!w) return;
-    dev_release(h, w->arena, w->tr.arena, w->un.arena, w->parena, w->sarena);
+    dev_release(h, w->arena, w->tr.arena, w->un.arena, w->dg.arena, w->parena, w->sarena);
     delete w;
     h->kron = nullptr;
 }
@@ -94,6 +97,7 @@ int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool 
     dv.coords = c.take(a.sum_n); dv.lam = c.take(a.sum_n);
     dv.K = c.take(a.sum_n2); dv.W = c.take(a.sum_n2); dv.Qt = c.take(a.sum_n2); dv.Tt = c.take(a.sum_n2); dv.Vr = c.take(a.sum_n2);
     if (grad) { dv.mdiag = c.take(a.sum_n); dv.E = c.take(a.sum_n2); dv.Mm = c.take(a.sum_n2); }
+    dv.stat = c.take(2 * 2 * KMAXD);      // out of the 32 spare entries (the ten pieces above round up by at most one each)
     return GPIMHIP_OK;
 }
 
@@ -360,8 +364,15 @@ __global__ __launch_bounds__(EIGH_WAVES * 64) void kron_eigh_kernel(KronDev dv) 
     // rotations continue from the V the caller left in Vr -- the identity, or the eigenvectors of the
     // previous Adam iteration, whose K differs by a small change of the lengthscale: W = V K then starts
     // almost orthogonal and two or three sweeps are enough instead of 8 ... 18.
+    // The cap: measured on the MI355X through gpimhip_kron_eigh (tests/test_gpu_kron_eigh.py), cold starts of order 64 ... 520
+    // end by the rule above in 11 ... 30 sweeps.  The two halves of a uniform 1300-point axis at lengthscale 3 (order 650
+    // each) run into the cap with rotations of |sin| 0.29 and 0.71 still being applied in sweep 40 -- and are converged all
+    // the same: eigenvalues within 0.8 n eps lmax of LAPACK's, orthogonality 1.1 n eps, as good as the problems that stop
+    // by themselves.  (Not traced, but consistent with it: what still rotates are rows inside the eps * lmax cluster, whose
+    // mutual rotations change nothing that is resolved.)  Nothing above order 650 has been measured.
     int nsweep = 0;
-    for (int sweep = 0; sweep < 40; ++sweep) {
+    double all = 0.0;
+    for (int sweep = 0; sweep < EIGH_MAX_SWEEPS; ++sweep) {
         ++nsweep;
         if (tid < EIGH_WAVES) s_max[tid] = 0.0;
         __syncthreads();
@@ -375,11 +386,12 @@ __global__ __launch_bounds__(EIGH_WAVES * 64) void kron_eigh_kernel(KronDev dv) 
         }
         if (lane == 0) s_max[wave] = big;
         __syncthreads();
-        double all = 0.0;
+        all = 0.0;
         for (int w = 0; w < EIGH_WAVES; ++w) all = fmax(all, s_max[w]);
         __syncthreads();
         if (all < 1e-8) break;
     }
+    if (tid == 0 && dv.stat) { dv.stat[2 * pr] = (double)nsweep; dv.stat[2 * pr + 1] = all; }
 #ifdef KRON_DEBUG
     if (tid == 0) printf("eigh axis %d part %d n %d: %d sweeps, lmax %.3f\n", ax, dv.ppart[pr], n, nsweep, lmax);
 #endif
@@ -1089,6 +1101,72 @@ int gpimhip_sample_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, c
         HIP_TRY(hipGetLastError());
     }
     return finish_and_check(h);
+}
+
+static int kron_eigh_bad(const char* what) {
+    gpim_set_error(std::string("gpimhip_kron_eigh: ") + what);
+    return GPIMHIP_E_BADARG;
+}
+
+// DIAGNOSTIC (tests/test_gpu_kron_eigh.py): the axis eigen-decomposition by the product's own chain -- kron_axes_ensure,
+// kron_plan_problems, kron_cold_start (unless warm), kron_eig_axes -- on an axis set of its own, and what the sweep loop of
+// every eigen-problem did.
+int gpimhip_kron_eigh(gpimhip_handle h, int32_t d, const int32_t* n, const double* axes, const double* ls, int32_t warm,
+                      double* lam_out, double* Qt_out, int32_t* nprob_out, int32_t* plan_out, double* rot_out,
+                      int32_t* cap_out) {
+    if (!h) return kron_eigh_bad("null handle");
+    FP64_ONLY(h);
+    if (!n || !axes || !ls || !lam_out || !Qt_out || !nprob_out || !plan_out || !rot_out) return kron_eigh_bad("null argument");
+    if (d < 1 || d > KMAXD) return kron_eigh_bad("d must be between 1 and 4");
+    ThetaDev th;
+    memset(&th, 0, sizeof(th));
+    th.var = 1.0;
+    for (int i = 0; i < KMAXD; ++i) th.ls[i] = th.inv_ls[i] = 1.0;
+    for (int i = 0; i < d; ++i) {
+        if (n[i] < 1 || n[i] > 4096) return kron_eigh_bad("every axis needs between 1 and 4096 points");
+        if (!(ls[i] > 0.0) || !(ls[i] < HUGE_VAL)) return kron_eigh_bad("lengthscales must be positive and finite");
+        th.ls[i] = ls[i]; th.inv_ls[i] = 1.0 / ls[i];
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    GP_TRY(ws_ensure(h, 1));                   // theta
+    if (!h->kron) h->kron = new KronWs();
+    KronWs& w = *static_cast<KronWs*>(h->kron);
+    KronAxes& ax = w.dg;
+    bool same = w.dg_ready && ax.arena && ax.d == d;
+    for (int i = 0; i < d && same; ++i) same = ax.n[i] == n[i];
+    if (warm && !same) return kron_eigh_bad("warm = 1 continues the previous call: it needs one, on axes of the same orders");
+    w.dg_ready = false;
+    KronDev prev;
+    memset(&prev, 0, sizeof(prev));
+    if (warm) prev = ax.dev;
+    GP_TRY(kron_axes_ensure(h, ax, d, n, false));
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(ax.dev.coords), axes, (size_t)ax.sum_n * sizeof(double), hipMemcpyDeviceToDevice,
+                           h->stream));
+    GP_TRY(kron_plan_problems(h, ax));
+    const KronDev& dv = ax.dev;
+    if (warm) {
+        bool plan_same = prev.nprob == dv.nprob;
+        for (int pr = 0; pr < dv.nprob && plan_same; ++pr) plan_same = prev.pn[pr] == dv.pn[pr] && prev.pax[pr] == dv.pax[pr];
+        if (!plan_same) return kron_eigh_bad("warm = 1 on coordinates that split into other eigen-problems than the previous call's");
+    } else {
+        GP_TRY(kron_cold_start(h, dv));
+    }
+    HIP_TRY(hipMemcpyAsync(h->theta.p, &th, sizeof(th), hipMemcpyHostToDevice, h->stream));
+    GP_TRY(kron_eig_axes(h, ax, h->theta));
+    double stat[2 * 2 * KMAXD];
+    HIP_TRY(hipMemcpyAsync(stat, dv.stat, sizeof(stat), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(lam_out, dv.lam, (size_t)ax.sum_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(Qt_out, dv.Qt, (size_t)ax.sum_n2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *nprob_out = dv.nprob;
+    for (int pr = 0; pr < dv.nprob; ++pr) {
+        plan_out[4 * pr] = dv.pax[pr]; plan_out[4 * pr + 1] = dv.ppart[pr]; plan_out[4 * pr + 2] = dv.pn[pr];
+        plan_out[4 * pr + 3] = (int32_t)stat[2 * pr];
+        rot_out[pr] = stat[2 * pr + 1];
+    }
+    if (cap_out) *cap_out = EIGH_MAX_SWEEPS;
+    w.dg_ready = true;
+    return GPIMHIP_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 #include "common.hpp"
 
 #define KMAXD GPIMHIP_MAX_DIM
+// the sweep loop of kron_eigh_kernel ends by its own rule (largest rotation of a sweep < 1e-8) or after this many sweeps
+#define EIGH_MAX_SWEEPS 40
 
 struct KronDev {
     int d;
@@ -22,6 +24,7 @@ struct KronDev {
     int pax[2 * KMAXD], ppart[2 * KMAXD], pn[2 * KMAXD];   // axis, part (0 whole, 1 symmetric, 2 skew), order
     int64_t poff[2 * KMAXD];                                // offset inside the axis' n_i^2 region (W, Vr, Tt)
     int plam[2 * KMAXD];                                    // offset of its eigenvalues / Qt rows inside the axis
+    double* stat;            // [2 * nprob] per eigen-problem: sweeps run, largest rotation of the last one (gpimhip_kron_eigh)
 };
 
 // One set of grid axes with everything that belongs to an axis alone: coordinates, K_i, the eigen-problem plan and the

@@ -849,6 +849,24 @@ int gpimhip_gemm_tile_pos_host(int32_t fp32, int32_t n, int32_t chunk, int32_t q
 int gpimhip_gemm_rect_tile_host(int32_t rect_rows, int32_t rect_cols, int32_t p0, int32_t count, int32_t* ci_out,
                                 int32_t* cj_out);
 
+/* DIAGNOSTIC: the eigen-solver under the structured (Kronecker) paths by itself (tests/test_gpu_kron_eigh.py).  Nothing in
+ * the product path calls it.  Runs the product's own chain -- the axis workspace, the eigen-problem plan (a centro-symmetric
+ * axis of n >= 8 points splits into a symmetric problem of order ceil(n/2) and a skew one of order floor(n/2)), the cold
+ * start of the rotations unless warm != 0, then K_i[a,b] = exp(-((c_a - c_b) / ls[i])^2 / 2) and its one-sided Jacobi
+ * eigen-decomposition -- on an axis set of its own, and synchronises.
+ *   d, n (HOST, d orders, each 1 .. 4096), axes (device, sum n_i coordinates), ls (HOST, d lengthscales > 0)
+ *   warm      != 0: the rotations continue from those the previous call on this handle left behind, as an Adam iteration's
+ *             do (needs such a call, on axes of the same orders that split the same way); 0: from the identity
+ *   lam_out   device, sum n_i: the eigenvalues, axis by axis, in the solver's own (unsorted) order
+ *   Qt_out    device, sum n_i^2: row j of axis i's n_i x n_i block is the eigenvector of lam_out[off_i + j]
+ *   nprob_out HOST: the number of eigen-problems (at most 2 d)
+ *   plan_out  HOST, 4 int32 per problem: axis, part (0 whole, 1 symmetric, 2 skew), order, sweeps run
+ *   rot_out   HOST, one double per problem: the largest |sin| of a rotation applied in the last sweep
+ *   cap_out   HOST (may be NULL): the cap of the sweep loop; a problem whose sweeps reach it did not end by its own rule */
+int gpimhip_kron_eigh(gpimhip_handle h, int32_t d, const int32_t* n, const double* axes, const double* ls, int32_t warm,
+                      double* lam_out, double* Qt_out, int32_t* nprob_out, int32_t* plan_out, double* rot_out,
+                      int32_t* cap_out);
+
 /* Stage timing for bench.py (HIP events on the handle's stream, recorded only while enabled).
  * stage: 0 = Cholesky (all launches of one factorisation, including the tile operations of the triangular inverse
  *            they host), 1 = what is left of the triangular inverse after the last step,
