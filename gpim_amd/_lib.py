@@ -210,6 +210,8 @@ _PROTOS = {
                                         c_dp]),
     "gpimhip_step_plan_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "gpimhip_step_plan_host_paired": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64,
+                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
     "gpimhip_step_plan_host_f32": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                   ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                                   ctypes.POINTER(ctypes.c_int32)]),

@@ -95,6 +95,7 @@ int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices) {
         // fit / predict invert the factor in the factorisation's launches (double precision); float matrices and
         // gpimhip_potrf use the plain plan, which is built on first use (never inside a capture)
         if (rc == GPIMHIP_OK) rc = h->fp32 ? step_plan_ensure(h, (int)nb) : step_plan_ensure_inv(h, (int)nb);
+        if (rc == GPIMHIP_OK && !h->fp32) rc = step_plan_ensure_pair(h, (int)nb);
         if (rc != GPIMHIP_OK) { ws_release_matrix(h); return rc; }     // (a later call must not find buffers without plans)
     }
     return GPIMHIP_OK;

@@ -21,6 +21,11 @@
 // H_j -> F_j -> D_j; nothing else is ever on it.  Every tile receives each k-block exactly once: columns of the
 // two most recent panels through the left-looking column updates (off-diagonal) or D (diagonal), older ones
 // through bulk() -- see build_step_plan().
+//
+// From 68 block columns on, with the fused inverse and at most four problems, the panels of the bulk regime (at least 64 block
+// columns right of them) advance TWO block columns per launch pair: HH_j = H_j whose role workgroup goes on with a bridge and
+// block j+1, FD2_j = the panel solve of both columns and the next diagonal super-block (plan_updates with `lead`,
+// chol_step_kernel<.., PAIR>, panel_solve2_kernel, diag_update2_kernel).
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -62,11 +67,14 @@ struct StepArgs {
 // where the chain of diagonal blocks bounds the launch, a hosted workgroup on the factorisation role's CU stretches
 // the role from 35 to 50 us (its serial fp64 chain shares the SIMD's fp64 pipe with the neighbour's MFMAs), and what
 // such a launch hosts for free is one quadrant per CU anyway.
-template <int FTM, int FTN, bool ALONE, bool RAG = false>
+// PAIR: the launch HH_j of the paired schedule (plan_updates) -- the role workgroup factors block kblk, runs the bridge
+// (pair_bridge: L[kblk+1,kblk] to A and, in B-operand order, to Pcopy; column kblk's term of A[kblk+1,kblk+1]) and factors
+// block kblk+1.  The hosted tiles read block columns < kblk only.
+template <int FTM, int FTN, bool ALONE, bool RAG = false, bool PAIR = false>
 __global__ __launch_bounds__(NTH, ALONE ? 2 : 4) void chol_step_kernel(StepArgs a) {
     constexpr int SM0 = POTF2_SMEM_DOUBLES > gemm_smem_doubles<FTM, FTN, 2>() ? POTF2_SMEM_DOUBLES : gemm_smem_doubles<FTM, FTN, 2>();
     static_assert(SM0 * 8 <= 80 * 1024, "two workgroups per CU");
-    constexpr int SM = ALONE ? 84 * 128 : SM0;
+    constexpr int SM = ALONE ? 84 * 128 : SM0 + (PAIR ? 2 : 0);      // (PAIR: the wave counter of pair_tid)
     __shared__ __attribute__((aligned(16))) double smem[SM];
     const int b = a.swap ? blockIdx.y : blockIdx.x;
     const int by = a.swap ? blockIdx.x : blockIdx.y;
@@ -99,8 +107,24 @@ __global__ __launch_bounds__(NTH, ALONE ? 2 : 4) void chol_step_kernel(StepArgs 
     // beside hosted neighbours on its CU the serial chain competes with their MFMA blocks (raised to priority 3 in the
     // tile engine): the role runs at that priority throughout (chain-bound launches: 1.93 -> 1.90 ms at N = 4212)
     if (!ALONE) __builtin_amdgcn_s_setprio(3);
+    int* wave_counter = reinterpret_cast<int*>(smem + POTF2_SMEM_DOUBLES);
+    if (PAIR && threadIdx.x == 0) *wave_counter = 0;           // (the role's first barrier comes before pair_tid reads it)
     potf2_body<double, ALONE && FI_LOOKAHEAD>(smem, by + a.pb_off, a.A, a.ld, a.kblk, a.dinv_all, a.dinvB_all, a.logdet, a.info, a.nb,
                                               a.col_off, a.Tm != nullptr);
+    if (PAIR) {
+        // The first role leaves no register free (the kernel is at the limit of both register files at two workgroups per CU):
+        // the bridge and the second role fetch the launch arguments again and number their threads afresh (pair_tid) instead
+        // of keeping either live across it.
+        const volatile __attribute__((address_space(4))) StepArgs* ka =
+            (const volatile __attribute__((address_space(4))) StepArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        const int tid2 = pair_tid(wave_counter);
+        double* A2 = ka->A;
+        const int64_t ld2 = ka->ld;
+        const int k2 = ka->kblk, nb2 = ka->nb, pb2 = (ka->swap ? blockIdx.x : blockIdx.y) + ka->pb_off;
+        pair_bridge(smem, pb2, A2, ld2, k2, nb2, ka->Pcopy, tid2);
+        potf2_body<double, ALONE && FI_LOOKAHEAD>(smem, pb2, A2, ld2, k2 + 1, ka->dinv_all, ka->dinvB_all, ka->logdet, ka->info, nb2,
+                                                  ka->col_off, ka->Tm != nullptr, tid2);
+    }
 }
 
 // Panel solve, one workgroup (4 waves) per 32-row strip of the block column below the diagonal block:
@@ -342,6 +366,157 @@ __global__ __launch_bounds__(512, 2) void panel_solve_diag_kernel(double* __rest
     for (int rg = 0; rg < 4; ++rg) C[(int64_t)(4 * rg) * ld] = cv[rg] - (acc0[rg] + acc1[rg]);
 }
 
+// FD2_j of the paired schedule, the strips: one workgroup (4 waves) per 32-row strip below block row kblk+1, both columns:
+//   L[i,kblk] = A[i,kblk] X_kblk^T,   L[i,kblk+1] = (A[i,kblk+1] - L[i,kblk] L[kblk+1,kblk]^T) X_{kblk+1}^T
+// panel_solve_kernel's arithmetic twice; in between the solved first strip is the A operand, from LDS, of the update of the
+// second.  LB: L[kblk+1,kblk] in B-operand order as the bridge of HH_j left it (pair_bridge).
+__global__ __launch_bounds__(256, 2) void panel_solve2_kernel(double* __restrict__ A, int64_t ld, int kblk, int nb,
+                                                             const double* __restrict__ dinvB_all,
+                                                             const double* __restrict__ LB_all, int b_off) {
+    constexpr int LDS_LD = 130, ROWS = 32, MTS = ROWS / 16;
+    __shared__ __attribute__((aligned(16))) double S[2 * ROWS * LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int by = blockIdx.y + b_off;
+    A += (int64_t)by * nb * NB * ld;
+    const d2* DB = reinterpret_cast<const d2*>(dinvB_all + ((int64_t)by * nb + kblk) * (NB * NB));
+    const d2* LB = reinterpret_cast<const d2*>(LB_all + (int64_t)by * (NB * NB));
+    double* P = A + ((int64_t)(kblk + 2) * NB + (int64_t)blockIdx.x * ROWS) * ld + (int64_t)kblk * NB;
+    double* S1 = S + ROWS * LDS_LD;
+#pragma unroll
+    for (int i = 0; i < ROWS / 4; ++i) {
+        const int row = wave * (ROWS / 4) + i;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(P + (int64_t)row * ld + lane * 2),
+                                         (__attribute__((address_space(3))) void*)(S + row * LDS_LD), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(P + (int64_t)row * ld + NB + lane * 2),
+                                         (__attribute__((address_space(3))) void*)(S1 + row * LDS_LD), 16, 0, 0);
+    }
+    const int t0 = wave, t1 = 7 - wave, n0 = 2 * t0 + 2;
+    const d4 zero = (d4){0.0, 0.0, 0.0, 0.0};
+    const double* Sa = S + (lane & 15) * LDS_LD + (lane >> 4);
+    // c = 0: column kblk from S; c = 1: column kblk+1 from S1 (the B fragments of X_{kblk+1} follow X_kblk's in dinvB)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        d2 bf[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) {
+            const int t = q < n0 ? t0 : t1, s2 = q < n0 ? q : q - n0;
+            bf[q] = DB[c * (NB * NB / 2) + (t * 16 + s2) * 64 + lane];
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        d4 acc[2][MTS];
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt) acc[x][mt] = zero;
+#pragma unroll
+        for (int q = 0; q < 18; ++q) {
+            const bool first = q < n0;          // wave-uniform
+            const int s2 = first ? q : q - n0;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int s = 2 * s2 + e;
+#pragma unroll
+                for (int mt = 0; mt < MTS; ++mt) {
+                    const double av = Sa[c * ROWS * LDS_LD + mt * 16 * LDS_LD + 4 * s];
+                    if (first) acc[0][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bf[q][e], acc[0][mt], 0, 0, 0);
+                    else acc[1][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bf[q][e], acc[1][mt], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int t = x == 0 ? t0 : t1;
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg)
+                    P[(int64_t)(mt * 16 + (lane >> 4) + 4 * rg) * ld + c * NB + t * 16 + (lane & 15)] = acc[x][mt][rg];
+        }
+        if (c == 1) break;
+        // the solved strip over the one it came from (every wave has read all of it: barrier first) ...
+        __syncthreads();
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int t = x == 0 ? t0 : t1;
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg)
+                    S[(mt * 16 + (lane >> 4) + 4 * rg) * LDS_LD + t * 16 + (lane & 15)] = acc[x][mt][rg];
+        }
+        __syncthreads();
+        // ... and S1 -= S LB^T: this wave's two column tiles, each element read and written by the lane that owns it
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int t = x == 0 ? t0 : t1;
+            d2 lb[16];
+#pragma unroll
+            for (int s2 = 0; s2 < 16; ++s2) lb[s2] = LB[(t * 16 + s2) * 64 + lane];
+            d4 u[MTS];
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt) u[mt] = zero;
+#pragma unroll
+            for (int s2 = 0; s2 < 16; ++s2)
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int mt = 0; mt < MTS; ++mt)
+                        u[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Sa[mt * 16 * LDS_LD + 4 * (2 * s2 + e)], lb[s2][e], u[mt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) S1[(mt * 16 + (lane >> 4) + 4 * rg) * LDS_LD + t * 16 + (lane & 15)] -= u[mt][rg];
+        }
+        // (the barrier at the top of the second pass makes S1 whole before any wave reads it)
+    }
+}
+
+// FD2_j, the next diagonal super-block: the tiles (jj,jj), (jj+1,jj), (jj+1,jj+1), jj = kblk+2, receive block columns kblk and
+// kblk+1 (256 contiguous k per row of A).  One workgroup per 32x32 block (a, b), a >= b, of the 256x256 lower triangle:
+// diag_update_kernel over two k-halves.
+__global__ __launch_bounds__(256, 2) void diag_update2_kernel(double* __restrict__ A, int64_t ld, int kblk, int nb, int b_off) {
+    constexpr int LDS_LD = 130;
+    __shared__ __attribute__((aligned(16))) double S[64 * LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    A += (int64_t)(blockIdx.y + b_off) * nb * NB * ld;
+    const int q = blockIdx.x;
+    int a = 0;
+    while ((a + 1) * (a + 2) / 2 <= q) ++a;
+    const int b = q - a * (a + 1) / 2;
+    const int64_t r0 = (int64_t)(kblk + 2) * NB;
+    const double* Pa = A + (r0 + a * 32) * ld + (int64_t)kblk * NB;
+    const double* Pb = A + (r0 + b * 32) * ld + (int64_t)kblk * NB;
+    const int wm = wave >> 1, wn = wave & 1;
+    double* C = A + (r0 + a * 32 + wm * 16 + (lane >> 4)) * ld + r0 + b * 32 + wn * 16 + (lane & 15);
+    double cv[4];
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) cv[rg] = C[(int64_t)(4 * rg) * ld];
+    d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
+    const double* Sa = S + (wm * 16 + (lane & 15)) * LDS_LD + (lane >> 4);
+    const double* Sb = S + (32 + wn * 16 + (lane & 15)) * LDS_LD + (lane >> 4);
+    for (int h = 0; h < 2; ++h) {
+        if (h) __syncthreads();                 // every wave has read the first half
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = wave * 8 + i;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Pa + (int64_t)row * ld + h * NB + lane * 2),
+                                             (__attribute__((address_space(3))) void*)(S + row * LDS_LD), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Pb + (int64_t)row * ld + h * NB + lane * 2),
+                                             (__attribute__((address_space(3))) void*)(S + (32 + row) * LDS_LD), 16, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 32; s += 2) {
+            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Sa[4 * s], Sb[4 * s], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Sa[4 * s + 4], Sb[4 * s + 4], acc1, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) C[(int64_t)(4 * rg) * ld] = cv[rg] - (acc0[rg] + acc1[rg]);
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -415,7 +590,16 @@ static double wg_cost(int depth, int q) { return q == 4 ? 0.14 * depth + 0.24 : 
 //     whatever else is pending;
 //   * once fewer than 64 block columns remain a panel's updates are less than one round per launch and everything
 //     pending is flushed at once, evenly over the panel's launches.
-static void plan_updates(int nb, std::vector<std::vector<TileDesc>>& fill) {
+//
+// lead != nullptr: the PAIRED schedule.  In the bulk regime a step launch HH_j factors block columns j and j+1 (the role
+// workgroup: role j, bridge -- L[j+1,j] and column j's term of A[j+1,j+1] -- role j+1) and FD2_j solves both columns below
+// block row j+1; lead[j] = 1, lead[j+1] = 2 and fill[j+1] stays empty.  What HH_j hosts reads only block columns < j:
+//   * the column updates of columns j and j+1, rows >= j+2, k-blocks [p0 - W, j) (column j+1's term k = j: FD2_j);
+//   * the tiles (j+2,j+2), (j+3,j+2), (j+3,j+3) of the next diagonal super-block with their window columns < j (FD2_j adds
+//     columns j and j+1, so they are final when HH_{j+2} starts and HH_{j+2} / H_{j+2} does not host (j+3,j+2) again);
+//   * the req / opt shares of both columns, planned for the launch of two roles and a bridge.
+// Panels outside the bulk regime keep one column per launch.
+static void plan_updates(int nb, std::vector<std::vector<TileDesc>>& fill, std::vector<uint8_t>* lead = nullptr) {
     // chain-bound matrices of at least 16 block columns: panels of THREE (column updates <= 5 k-blocks deep: a hosted quadrant
     // of depth 7 lasts 50 us, the factorisation role 28 since round 5 -- N = 4212 2.53 -> 2.47 ms per Adam iteration; the
     // ten-block slices of config C3 in one lock-step batch of 64 are 1.4 % slower with it, hence the lower bound)
@@ -437,15 +621,29 @@ static void plan_updates(int nb, std::vector<std::vector<TileDesc>>& fill) {
     // column j, the only one on the critical path.  (Rounds 3-4 had D_j update the next <= 7 diagonal tiles eagerly,
     // k = 128 each: the same flop as 10 quadrant workgroups per tile and step -- 2240 latency-shaped workgroups per launch
     // for a lock-step batch of 32, 28 us where the chip does 0.6 GFLOP.)
-    auto col_update = [&](std::vector<TileDesc>& tl, int p0, int j) {
+    // (after_pair: column j follows a pair, whose FD2 completed the tiles (j+1, j) and (j+1, j+1) up to column j - 1)
+    auto col_update = [&](std::vector<TileDesc>& tl, int p0, int j, bool after_pair = false) {
         const int kb0 = std::max(0, p0 - W);
         if (j > kb0)
-            for (int i = j + 1; i < nb; ++i) tl.push_back({i, j, kb0, j});
-        if (j + 1 < nb) {
+            for (int i = j + 1 + (after_pair ? 1 : 0); i < nb; ++i) tl.push_back({i, j, kb0, j});
+        if (j + 1 < nb && !after_pair) {
             const int kd = std::max(0, ((j + 1) / W) * W - W);
             if (j > kd) tl.push_back({j + 1, j + 1, kd, j});
         }
     };
+    // what HH_j hosts of the window (j + 3 < nb in the bulk regime)
+    auto col_update_pair = [&](std::vector<TileDesc>& tl, int p0, int j) {
+        const int kb0 = std::max(0, p0 - W);
+        if (j > kb0)
+            for (int c = j; c <= j + 1; ++c)
+                for (int i = j + 2; i < nb; ++i) tl.push_back({i, c, kb0, j});
+        for (int c = j + 2; c <= j + 3; ++c) {
+            const int kd = std::max(0, (c / W) * W - W);
+            if (j > kd)
+                for (int i = c; i <= j + 3; ++i) tl.push_back({i, c, kd, j});
+        }
+    };
+    if (lead) lead->assign(nb, 0);
     if (nb < 64) {
         for (int p = 0; p < npanel; ++p) {
             const int p0 = p * W, p1 = std::min(p0 + W, nb), ncol = p1 - p0;
@@ -494,10 +692,13 @@ static void plan_updates(int nb, std::vector<std::vector<TileDesc>>& fill) {
                 if (due(t)) { ++n_due; due_cost += HostSim::cost(t); }
         }
         size_t rtaken = 0, otaken = 0;
+        const bool paired = lead && bulk_regime;        // (rem >= 64: the panel has all W columns, W even)
         for (int j = p0; j < p1; ++j) {
-            const int left = p1 - j;
+            if (paired && ((j - p0) & 1)) { (*lead)[j] = 2; continue; }
+            const int left = paired ? (p1 - j + 1) / 2 : p1 - j;       // launches left in the panel, this one included
             std::vector<TileDesc>& tl = fill[j];
-            col_update(tl, p0, j);
+            if (paired) { (*lead)[j] = 1; col_update_pair(tl, p0, j); }
+            else col_update(tl, p0, j, lead && j == p0 && j >= 2 && (*lead)[j - 2] == 1);
             const size_t nreq = (req.size() - rtaken + left - 1) / left;
             for (size_t q = 0; q < nreq; ++q) tl.push_back(req[rtaken++]);
             if (!bulk_regime) {
@@ -505,7 +706,7 @@ static void plan_updates(int nb, std::vector<std::vector<TileDesc>>& fill) {
                 for (size_t q = 0; q < nopt; ++q) tl.push_back(opt[otaken++]);
             } else {
                 HostSim sim(S);
-                sim.add(1.0);                                               // the factorisation role
+                sim.add(paired ? 2.5 : 1.0);                                // the factorisation role (pair: two and the bridge)
                 std::stable_sort(tl.begin(), tl.end(), by_depth);
                 double base = 0.0;
                 for (auto& t : tl) { sim.add(HostSim::cost(t)); base += HostSim::cost(t); }
@@ -598,8 +799,10 @@ static int host_shape(int64_t update_kblocks, int quad_max = 2000) { return upda
 static bool pair_rule(size_t ntiles, int64_t kblocks) { return 4 * ntiles >= PAIR_MIN_QUADS && 10 * kblocks >= PAIR_MIN_DEPTH10 * (int64_t)ntiles; }
 // returns false if the plan did not close (every launch completes at least one phase of one node, so this cannot happen
 // with the dependency rule as it stands; a caller must not run a partial plan: A would be left a half-inverted factor)
+// lead (paired schedule, plan_updates): a launch index with lead[L] == 2 does not exist -- no budget, no operations -- and a
+// pair leader's chain is two roles and the bridge; "block columns < L are final at launch L" holds for leaders as it stands.
 static bool plan_inverse(int nb, std::vector<std::vector<TileDesc>>& fill, std::vector<std::vector<TileDesc>>& post,
-                         std::vector<uint8_t>& pair) {
+                         std::vector<uint8_t>& pair, const std::vector<uint8_t>* lead = nullptr) {
     std::vector<TriNodeS> nodes;
     tri_nodes(0, nb, nodes);
     std::vector<int> order(nodes.size());
@@ -613,6 +816,8 @@ static bool plan_inverse(int nb, std::vector<std::vector<TileDesc>>& fill, std::
     const double CHAIN = PLAN_CHAIN;                   // length of the factorisation role in cost units
     for (int L = 0; open_nodes > 0; ++L) {
         const bool hosted = L < nb;
+        if (hosted && lead && (*lead)[L] == 2) continue;
+        const bool leader = hosted && lead && (*lead)[L] == 1;
         if (!hosted) post.emplace_back();
         std::vector<TileDesc>& out = hosted ? fill[L] : post.back();
         int64_t upd = 0;
@@ -633,7 +838,7 @@ static bool plan_inverse(int nb, std::vector<std::vector<TileDesc>>& fill, std::
 #ifndef PLAN_PAIR_CHAIN
 #define PLAN_PAIR_CHAIN 0.3
 #endif
-        const double slow = two ? PLAN_PAIR_SLOW : 1.0, chain = two ? CHAIN + PLAN_PAIR_CHAIN : CHAIN;
+        const double slow = two ? PLAN_PAIR_SLOW : 1.0, chain = leader ? 2 * CHAIN + 0.5 : (two ? CHAIN + PLAN_PAIR_CHAIN : CHAIN);
         HostSim sim(q == 1 || two ? HOST_SLOTS : HOST_SLOTS / 2);
         double target = 1e30;
         if (hosted) {
@@ -734,7 +939,10 @@ static void plan_updates_f32(int nb, std::vector<std::vector<TileDesc>>& fill, s
     }
 }
 
-static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_inverse) {
+// the paired schedule applies from one bulk panel on: rem = nb - W >= 64
+static bool pair_steps_apply(int nb) { return nb >= 64 + STEP_W; }
+
+static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_inverse, bool paired = false) {
     const bool fp32 = h->fp32 != 0;
     if (P.nb == nb && P.fp32 == (int)fp32) return GPIMHIP_OK;
     if (P.d_tiles) { (void)hipFree(P.d_tiles); P.d_tiles = nullptr; }
@@ -742,8 +950,9 @@ static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_invers
     const int npanel = (nb + W - 1) / W;
     std::vector<std::vector<TileDesc>> fill(nb), post, rest(npanel);
     std::vector<int> ndiag32;
-    if (!fp32) plan_updates(nb, fill);
+    if (!fp32) plan_updates(nb, fill, paired ? &P.lead : nullptr);
     else plan_updates_f32(nb, fill, rest, ndiag32);
+    if (!paired) P.lead.assign(nb, 0);
     P.n_update.assign(nb, 0);
     for (int j = 0; j < nb; ++j)
         for (auto& t : fill[j]) P.n_update[j] += t.kb1 - t.kb0;
@@ -751,7 +960,7 @@ static int step_plan_build(gpimhip_ctx* h, int nb, StepPlan& P, bool with_invers
     if (with_inverse) {
         // plan_inverse decides pair[] from the update tiles alone (before it adds its own) and budgets its chunks for
         // the launch as it will then run: keep ITS decision
-        if (!plan_inverse(nb, fill, post, P.pair)) {
+        if (!plan_inverse(nb, fill, post, P.pair, paired ? &P.lead : nullptr)) {
             gpim_set_error("step plan: the inverse's tile operations did not all find a launch (nb = " + std::to_string(nb) + ")");
             return GPIMHIP_E_BADARG;
         }
@@ -824,6 +1033,36 @@ extern "C" int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t*
     return GPIMHIP_OK;
 }
 
+// The plan with the fused inverse as it RUNS for up to four problems: the paired schedule from nb = 68 (records as above,
+// a pair's hosted operations under its leader's index), the plan of gpimhip_step_plan_host below that.  pair_out (nb int32,
+// may be NULL): 1 = the launch factors block columns j and j+1, 2 = column j+1 of a pair (no launch), 0 = one column.  The
+// update terms FD2_j applies follow as records of kind 5 under the leader's index: k-block j to the tiles (i, j+1), i >= j+2,
+// and k-blocks [j, j+2) to the tiles (j+2,j+2), (j+3,j+2), (j+3,j+3).  (The bridge's term -- k-block j of tile (j+1,j+1) --
+// and the next diagonal tile of an unpaired column are the role's and D_j's, as in the per-column plan.)
+extern "C" int gpimhip_step_plan_host_paired(int32_t nb, int32_t* out, int64_t cap, int64_t* n_out, int32_t* pair_out) {
+    if (nb < 1 || nb > 4096 || !n_out) return GPIMHIP_E_BADARG;
+    std::vector<std::vector<TileDesc>> fill(nb), post;
+    std::vector<uint8_t> lead(nb, 0), pair(nb, 0);
+    const bool paired = pair_steps_apply(nb);
+    plan_updates(nb, fill, paired ? &lead : nullptr);
+    if (!plan_inverse(nb, fill, post, pair, paired ? &lead : nullptr)) return GPIMHIP_E_BADARG;
+    int64_t n = 0;
+    for (int j = 0; j < nb; ++j) n = emit_plan_records(j, fill[j], out, cap, n);
+    for (size_t q = 0; q < post.size(); ++q) n = emit_plan_records(nb + (int)q, post[q], out, cap, n);
+    for (int j = 0; j < nb; ++j) {
+        if (lead[j] != 1) continue;
+        std::vector<TileDesc> fd2;
+        for (int i = j + 2; i < nb; ++i) fd2.push_back({i, j + 1, j, (j + 1) | (5 << 16)});
+        for (int c = j + 2; c <= j + 3; ++c)
+            for (int i = c; i <= j + 3; ++i) fd2.push_back({i, c, j, (j + 2) | (5 << 16)});
+        n = emit_plan_records(j, fd2, out, cap, n);
+    }
+    if (pair_out)
+        for (int j = 0; j < nb; ++j) pair_out[j] = lead[j];
+    *n_out = n;
+    return GPIMHIP_OK;
+}
+
 // The single-precision plan (plan_updates_f32, with plan_inverse on top of it when with_inverse != 0 -- what
 // step_plan_build builds for a float handle), same records in the order of the uploaded tile list.  What the float
 // schedule adds: launch index -(p + 1) = the launch before the first step of outer panel p (bulk_rest), and
@@ -848,9 +1087,13 @@ extern "C" int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int3
 
 int step_plan_ensure(gpimhip_ctx* h, int nb) { return step_plan_build(h, nb, h->splan, false); }
 int step_plan_ensure_inv(gpimhip_ctx* h, int nb) { return step_plan_build(h, nb, h->splan_inv, true); }
+int step_plan_ensure_pair(gpimhip_ctx* h, int nb) {
+    if (h->fp32 || !pair_steps_apply(nb) || getenv("GPIMHIP_NO_PAIR_STEPS") != nullptr) return GPIMHIP_OK;
+    return step_plan_build(h, nb, h->splan_pair, true, true);
+}
 
 void step_plan_release(gpimhip_ctx* h) {
-    for (StepPlan* P : {&h->splan, &h->splan_inv}) {
+    for (StepPlan* P : {&h->splan, &h->splan_inv, &h->splan_pair}) {
         if (P->d_tiles) (void)hipFree(P->d_tiles);
         P->d_tiles = nullptr;
         P->nb = 0;
@@ -869,7 +1112,9 @@ static GemmArgs nt_update(double* A, int64_t ld, const TileDesc* tiles, int n, i
 // one launch of the step kernel: `potf2` = with the factorisation role for block a.kblk, n hosted tiles in shape q.
 // Batches: both roles on all problems of the handle's batch, or (split != nullptr) the factorisation role on problems
 // split[0] .. +split[1] and the hosted tiles on problems split[2] .. +split[3], problem index in blockIdx.x.
-static int launch_step(gpimhip_ctx* h, StepArgs& a, bool potf2, int n, int q, const int* split = nullptr, bool two_per_cu = false) {
+// lead: the launch HH_j of the paired schedule (the factorisation role does block columns a.kblk and a.kblk + 1).
+static int launch_step(gpimhip_ctx* h, StepArgs& a, bool potf2, int n, int q, const int* split = nullptr, bool two_per_cu = false,
+                       bool lead = false) {
     const int B = h->nbatch;
     a.potf2 = potf2 ? 1 : 0;
     if (!potf2 && n == 0) return GPIMHIP_OK;
@@ -887,7 +1132,23 @@ static int launch_step(gpimhip_ctx* h, StepArgs& a, bool potf2, int n, int q, co
         if (grid.x == 0) return GPIMHIP_OK;
         if (grid.y > 65535) { gpim_set_error("step launch: tile list too long for a split batch"); return GPIMHIP_E_BADARG; }
     }
-    if (a.g.rag && n) {           // ragged last block (GemmArgs::rag): the instantiations whose hosted tiles skip its padding
+    if (lead) {
+        if (!potf2 || split) { gpim_set_error("step launch: a pair leader is a single-batch launch with the factorisation role"); return GPIMHIP_E_BADARG; }
+        const bool rag = a.g.rag && n;
+        if (q == 4 && alone) {
+            if (rag) hipLaunchKernelGGL((chol_step_kernel<64, 64, true, true, true>), grid, dim3(NTH), 0, h->stream, a);
+            else hipLaunchKernelGGL((chol_step_kernel<64, 64, true, false, true>), grid, dim3(NTH), 0, h->stream, a);
+        } else if (q == 4) {
+            if (rag) hipLaunchKernelGGL((chol_step_kernel<64, 64, false, true, true>), grid, dim3(NTH), 0, h->stream, a);
+            else hipLaunchKernelGGL((chol_step_kernel<64, 64, false, false, true>), grid, dim3(NTH), 0, h->stream, a);
+        } else if (q == 2) {
+            if (rag) hipLaunchKernelGGL((chol_step_kernel<128, 64, false, true, true>), grid, dim3(NTH), 0, h->stream, a);
+            else hipLaunchKernelGGL((chol_step_kernel<128, 64, false, false, true>), grid, dim3(NTH), 0, h->stream, a);
+        } else {
+            if (rag) hipLaunchKernelGGL((chol_step_kernel<128, 128, false, true, true>), grid, dim3(NTH), 0, h->stream, a);
+            else hipLaunchKernelGGL((chol_step_kernel<128, 128, false, false, true>), grid, dim3(NTH), 0, h->stream, a);
+        }
+    } else if (a.g.rag && n) {           // ragged last block (GemmArgs::rag): the instantiations whose hosted tiles skip its padding
         if (q == 4 && alone) hipLaunchKernelGGL((chol_step_kernel<64, 64, true, true>), grid, dim3(NTH), 0, h->stream, a);
         else if (q == 4) hipLaunchKernelGGL((chol_step_kernel<64, 64, false, true>), grid, dim3(NTH), 0, h->stream, a);
         else if (q == 2) hipLaunchKernelGGL((chol_step_kernel<128, 64, false, true>), grid, dim3(NTH), 0, h->stream, a);
@@ -934,6 +1195,17 @@ static int launch_solve_diag(gpimhip_ctx* h, double* A, int64_t ld, int j, int n
     return GPIMHIP_OK;
 }
 
+// FD2_j of the paired schedule for the problems b_off .. b_off + cnt - 1: both columns' strips below block row j+1, then the
+// next diagonal super-block (j + 3 < nb: plan_updates pairs columns in the bulk regime only)
+static int launch_solve_diag2(gpimhip_ctx* h, double* A, int64_t ld, int j, int nb, int b_off, int cnt) {
+    hipLaunchKernelGGL(panel_solve2_kernel, dim3(4 * (nb - j - 2), cnt), dim3(256), 0, h->stream, A, ld, j, nb,
+                       (const double*)h->dinvB, (const double*)h->pcopy, b_off);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(diag_update2_kernel, dim3(36, cnt), dim3(256), 0, h->stream, A, ld, j, nb, b_off);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
 // Lower Cholesky of the np x np matrix A (np = nb * 128), in place, on h->stream; h->dinvB / h->logdet_part receive the
 // inverses of the diagonal blocks (MFMA operand order) and the log-determinant partials.
 // Tm == nullptr: A <- L, h->dinv <- the inverses of the diagonal blocks (gpimhip_potrf, the distributed driver).
@@ -943,11 +1215,14 @@ static int launch_solve_diag(gpimhip_ctx* h, double* A, int64_t ld, int j, int n
 int launch_potrf_steps(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info, double* Tm, int rag) {
     if (h->fp32) return launch_potrf_steps_f32(h, A, np, ld, info);
     const int nb = (int)(np / NB);
+    const int B = h->nbatch;
+    const int host_max_batch = 4;
+    // two block columns per step launch in the bulk regime (plan_updates): the fused inverse of up to host_max_batch problems
+    // from nb = 68.  The plan is there if ws_ensure built it (GPIMHIP_NO_PAIR_STEPS, read at plan build: the per-column schedule).
+    const bool paired = Tm && B <= host_max_batch && h->pcopy && h->splan_pair.d_tiles && h->splan_pair.nb == nb && h->splan_pair.fp32 == 0;
     if (Tm) GP_TRY(step_plan_ensure_inv(h, nb));
     else GP_TRY(step_plan_ensure(h, nb));
-    const StepPlan& P = Tm ? h->splan_inv : h->splan;
-    const int B = h->nbatch;
-    const int host_max_batch = 4;      // (2 / 8 measure the same on C3; 16, i.e. batches of 16 un-split: 0.998 vs 0.907 s)
+    const StepPlan& P = paired ? h->splan_pair : (Tm ? h->splan_inv : h->splan);      // (2 / 8 measure the same on C3; 16, i.e. batches of 16 un-split: 0.998 vs 0.907 s)
     StepArgs a;
     a.A = A; a.ld = ld; a.nb = nb; a.Tm = Tm;
     a.dinv_all = h->dinv; a.dinvB_all = h->dinvB; a.logdet = h->logdet_part; a.info = info;
@@ -994,11 +1269,16 @@ int launch_potrf_steps(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_
             }
         } else {
             for (int j = 0; j < nb; ++j) {
+                if (P.lead[j] == 2) continue;               // (factored and solved with column j - 1)
                 a.kblk = j;
                 int q;
                 const int nf = hosted_list(j, B, q);
-                GP_TRY(launch_step(h, a, true, nf, q, nullptr, P.pair[j] != 0));
-                GP_TRY(launch_solve_diag(h, A, ld, j, nb, P.diag[j].n, 0, B, fused(j)));
+                GP_TRY(launch_step(h, a, true, nf, q, nullptr, P.pair[j] != 0, P.lead[j] == 1));
+                if (P.lead[j] == 1) {
+                    GP_TRY(launch_solve_diag2(h, A, ld, j, nb, 0, B));
+                } else {
+                    GP_TRY(launch_solve_diag(h, A, ld, j, nb, P.diag[j].n, 0, B, fused(j)));
+                }
             }
         }
     }

@@ -117,6 +117,8 @@ struct StepPlan {
     std::vector<int32_t> n_all;         // per block column: all hosted k-blocks (shape of the launches of a large batch)
     std::vector<uint8_t> pair;          // per block column: its step launch runs hosted quadrants two per CU (cholstep.hip)
     std::vector<uint8_t> copy;          // per block column: its step launch leaves a copy of A[j+1, j] (TILE_COPY): F_j and D_j fuse
+    std::vector<uint8_t> lead;          // per block column: 1 = its step launch factors columns j and j+1 (paired schedule), 2 = column
+                                        // j+1 of such a pair (no launch of its own), 0 = one column per launch
 };
 
 // Launch plans of the distributed (block-column-cyclic, 1 x P) factorisation for one rank (api.hip: gpimhip_dist_*)
@@ -194,6 +196,7 @@ struct gpimhip_ctx {
     int64_t bytes = 0;
     LinalgPlan plan;
     StepPlan splan, splan_inv;      // factorisation alone / with the triangular inverse riding in its launches
+    StepPlan splan_pair;            // splan_inv with two block columns per step launch in the bulk regime (nb >= 68, <= 4 problems)
     DistPlan dplan;
     // optional stage timing (bench.py): HIP event pairs on the handle's stream
     bool timing = false;
@@ -362,6 +365,7 @@ int launch_potrf_steps_f32(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, in
 void step_plan_release(gpimhip_ctx* h);
 int step_plan_ensure(gpimhip_ctx* h, int nb);
 int step_plan_ensure_inv(gpimhip_ctx* h, int nb);
+int step_plan_ensure_pair(gpimhip_ctx* h, int nb);      // (nothing to do where the paired schedule does not apply)
 int launch_panel_chain(gpimhip_ctx* h, double* A, int64_t ld, int p0, int p1, int nb, const TileDesc* tiles,
                        const PlanRange* colfill, int32_t* info);
 // distops.hip

@@ -37,7 +37,7 @@ template <typename R, bool LA = false>
 __device__ __forceinline__ void potf2_body(double* __restrict__ smem, const int by, R* __restrict__ A, int64_t ld, int kblk,
                                            R* __restrict__ dinv_all, double* __restrict__ dinvB_all,
                                            double* __restrict__ logdet_out, int32_t* __restrict__ info, int nb PROF_ARG,
-                                           int col_off = 0, bool inv_to_A = false) {
+                                           int col_off = 0, bool inv_to_A = false, int tid_in = -1) {
     double* D = smem;
     double* invd = D + PL::DOUBLES;
     double* Xs = invd + NB;
@@ -49,7 +49,8 @@ __device__ __forceinline__ void potf2_body(double* __restrict__ smem, const int 
     A += (int64_t)by * nb * NB * ld;
     dinv_all += (int64_t)by * nb * NB * NB;
     logdet_out += (int64_t)by * nb;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (tid_in: the second role of a paired step launch numbers its threads afresh, pair_tid below)
+    const int tid = tid_in < 0 ? (int)threadIdx.x : tid_in, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     typedef R RV2 __attribute__((ext_vector_type(2)));
     R* Ablk = A + ((int64_t)kblk * NB) * ld + (int64_t)kblk * NB;
     if (tid == 0) s_bad = 0;
@@ -178,5 +179,102 @@ __device__ __forceinline__ void potf2_body(double* __restrict__ smem, const int 
         }
     }
     STAMP(5);
+}
+
+// A thread index for what follows the first role of a paired step launch: the lane number from the hardware and a wave number
+// drawn from a counter in LDS (zeroed before the first role; any numbering of the waves will do).  The first role runs at the
+// limit of the register file at two workgroups per CU: a thread index -- and everything derived from it -- that stays live
+// across it for the bridge and the second role costs it the registers it does not have.
+__device__ __forceinline__ int pair_tid(int* counter) {
+    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    int w = 0;
+    if (lane == 0) w = atomicAdd(counter, 1);
+    w = __builtin_amdgcn_readfirstlane(w);
+    int tid = w * 64 + lane;
+    asm volatile("" : "+v"(tid));
+    return tid;
+}
+
+// The bridge between the two factorisation roles of a paired step launch (cholstep.hip: HH_j).  The role's workgroup runs it
+// right after potf2_body(kblk), while the inverse X of block kblk is still in LDS (smem: D, LayTri):
+//   L[kblk+1, kblk] = A[kblk+1, kblk] X^T                        (every 16x16 tile in the k-order of panel_solve_kernel)
+//   A[kblk+1, kblk+1] -= L[kblk+1, kblk] L[kblk+1, kblk]^T       (the 36 lower tiles, two chains as diag_update_kernel)
+// Wave w solves rows 16 w .. 16 w + 15 of the block.  The solved block goes to A and, in the B-operand order of dinvB
+// (LB[t][s2][lane][e] = L[16 t + (lane & 15)][8 s2 + 4 e + (lane >> 4)]), to LB: what the product above and FD2's update of
+// column kblk+1 read as fragments of either operand, one 16-byte load per lane and two k-steps.
+// What this workgroup stored and reads back -- LB here, A[kblk+1, kblk+1] in the next role -- must not come from the CU's L1:
+// every wave drains its stores, the workgroup meets at a barrier, and an agent-scope acquire invalidates that L1.
+// tid: from pair_tid().
+__device__ __forceinline__ void pair_bridge(const double* smem, const int by, double* A, int64_t ld, int kblk, int nb, double* LB,
+                                            const int tid) {
+    const double* D = smem;
+    A += (int64_t)by * nb * NB * ld;
+    LB += (int64_t)by * (NB * NB);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, kq = lane >> 4;
+    double* P = A + ((int64_t)(kblk + 1) * NB) * ld + (int64_t)kblk * NB;
+    double* C = P + NB;
+    __syncthreads();                            // the inverse is complete in D
+    // the wave's A fragments stay in registers; the loop over the column tiles is NOT unrolled (the role's register budget is
+    // 128 at two workgroups per CU): tile t takes k-steps 0 .. 4 t + 3 in ascending order
+    {
+        double af[32];
+        const double* Pa = P + (int64_t)(16 * wave + n) * ld + kq;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) af[s] = Pa[4 * s];
+#pragma unroll 1
+        for (int t = 0; t < 8; ++t) {
+            d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+            const double* Dt = D + PL::tile(t, 0);
+#pragma unroll
+            for (int sc = 0; sc < 8; ++sc) {
+                if (sc <= t) {                                      // (wave-uniform) tile (t, sc) of X: k-steps 4 sc .. 4 sc + 3
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int kk = 4 * e + kq;
+                        double b = Dt[sc * 256 + (PL::XT ? PL::in(kk, n) : PL::in(n, kk))];
+                        if (sc == t && kk > n) b = 0.0;
+                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(af[4 * sc + e], b, acc, 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int rr = kq + 4 * rg, c = 16 * t + n;
+                P[(int64_t)(16 * wave + rr) * ld + c] = acc[rg];
+                LB[(((wave * 16 + (c >> 3)) * 64 + (((c & 3) << 4) | rr)) << 1) + ((c >> 2) & 1)] = acc[rg];
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const d2* LB2 = reinterpret_cast<const d2*>(LB);
+    for (int q = wave; q < 36; q += 8) {
+        int mt = 0;
+        while ((mt + 1) * (mt + 2) / 2 <= q) ++mt;
+        const int nt = q - mt * (mt + 1) / 2;
+        d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            d2 fa[8], fb[8];
+#pragma unroll
+            for (int s2 = 0; s2 < 8; ++s2) {
+                fa[s2] = LB2[(mt * 16 + 8 * h + s2) * 64 + lane];
+                fb[s2] = LB2[(nt * 16 + 8 * h + s2) * 64 + lane];
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 8; ++s2) {
+                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[s2][0], fb[s2][0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[s2][1], fb[s2][1], acc1, 0, 0, 0);
+            }
+        }
+        double* Cp = C + (int64_t)(16 * mt + kq) * ld + 16 * nt + n;
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) Cp[(int64_t)(4 * rg) * ld] = Cp[(int64_t)(4 * rg) * ld] - (acc0[rg] + acc1[rg]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 

@@ -787,6 +787,15 @@ int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat
  * -sum_k A[ci,k] Tm[k,cj]; k over block columns [kb0, kb1)).  *n_out = number of records of the plan. */
 int gpimhip_step_plan_host(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out);
 
+/* The plan with the inverse as it RUNS for at most four problems: from nb = 68 the step launches of the bulk regime factor
+ * two block columns each (a pair's hosted operations are recorded under its first column); below nb = 68 the records of
+ * gpimhip_step_plan_host(nb, 1, ...).  pair_out (nb int32, may be NULL): 1 = the launch of this column factors the next one
+ * too, 2 = second column of a pair (no launch of its own), 0 = one column per launch.  After the records of the launches,
+ * records of kind 5 under a pair's first column j list the update terms the launch AFTER its step launch applies besides
+ * solving both columns: k-block j to the tiles (i, j+1), i >= j+2, and k-blocks [j, j+2) to the tiles (j+2,j+2), (j+3,j+2),
+ * (j+3,j+3).  GPIMHIP_NO_PAIR_STEPS=1 (read when a handle builds its plans) runs the per-column schedule instead. */
+int gpimhip_step_plan_host_paired(int32_t nb, int32_t* out, int64_t cap, int64_t* n_out, int32_t* pair_out);
+
 /* The same for a single-precision handle (cholstep32.hip: hosted fill capped from 88 block columns, pair mode from 160),
  * records in the order of the tile list the handle uploads.  What the float schedule adds: launch index -(p + 1) = the
  * tile-engine launch before the first step of outer panel p (four block columns; the part of the panel's bulk update
