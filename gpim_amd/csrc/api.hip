@@ -1,6 +1,7 @@
 // api.hip -- host side of libgpimhip: workspace, launch plans, blocked-algorithm drivers and the
 // extern "C" entry points declared in include/gpimhip.h.  The posterior draws (gpimhip_sample_*, but gpimhip_sample_kron of
-// kron.hip) have their drivers and entries in draws.hip.
+// kron.hip) have their drivers and entries in draws.hip, the spectral-mixture GP (gpimhip_*_sm*) in smgp.hip and the
+// multi-output GP (gpimhip_*_vgp*) in vgpgp.hip.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -101,7 +102,7 @@ int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices) {
     return GPIMHIP_OK;
 }
 int ws_ensure(gpimhip_ctx* h, int64_t N) { return ws_ensure_b(h, N, h->nbatch, 0); }
-static int ws_ensure_padded(gpimhip_ctx* h, int64_t N) { return ws_ensure_b(h, N, h->nbatch, 1); }
+int ws_ensure_padded(gpimhip_ctx* h, int64_t N) { return ws_ensure_b(h, N, h->nbatch, 1); }
 
 static void ws_release_predict(gpimhip_ctx* h) {
     dev_release(h, h->Ks, h->colpart, h->mean_tmp);
@@ -397,7 +398,7 @@ static void border_release(gpimhip_ctx* h) {
 
 // buffers for the workspace's np and batch (outside any capture: allocations and tile-list uploads synchronise).
 // T: the borders in lock-step (the tasks of the multi-output GP: the batch is T 2^r blocks; otherwise 1)
-static int border_ensure(gpimhip_ctx* h, int T = 1) {
+int border_ensure(gpimhip_ctx* h, int T) {
     BorderWs* w = bws(h);
     const int64_t mp = pad_to(w->M, NB);
     if (!w->sub) GP_TRY(gpimhip_create(&w->sub, h->device, h->stream));
@@ -427,7 +428,7 @@ static int border_ensure(gpimhip_ctx* h, int T = 1) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return GPIMHIP_OK;
 }
-static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
+int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
     BorderWs* w = bws(h);
     if (w->r_cols >= cols && w->R) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -445,7 +446,7 @@ static int border_ensure_r(gpimhip_ctx* h, int64_t cols) {
 // After the blocks' inverses are in h->B (launch_lauum): S, L_S^-1, Y_b = C_b L_S^-T, the corrected alpha, the two loss
 // scalars, and (training) B_b^-1 -= Y_b Y_b^T on the lower tiles.  nq: the points of the fundamental domain.
 // With T borders (BorderWs::T) all of it runs per task in lock-step: sub factors the T matrices S_t as one batch.
-static int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
+int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse) {
     BorderWs* w = bws(h);
     gpimhip_ctx* sub = w->sub;
     sub->stream = h->stream;                // (the capture stream while run_fit_iterations records an iteration)
@@ -504,8 +505,7 @@ static int refine_passes() {
 // contraction adds up the entries it needs itself (launch_grad_reduce_fin), one launch less per iteration; h->alpha is
 // then NOT valid.
 static bool alpha_deferrable(const gpimhip_ctx* h) { return !h->fp32 && !h->refl.mask && h->np <= 8192 && !getenv("GPIMHIP_NO_FUSED_FINALIZE"); }
-static int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
-                         bool defer_alpha = false) {
+int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, bool defer_alpha) {
     const int64_t np = h->np, ld = h->ld;
     GP_TRY(launch_trmv_lower(h, h->A, ld, np, h->ypad, h->z));
     GP_TRY(launch_gemv_t_tri(h, h->A, ld, np, h->z, h->gemv_part, defer_alpha && !h->fp32 ? nullptr : h->alpha));
@@ -527,8 +527,8 @@ static int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double*
 
 // K(u) -> L -> L^-1 (in h->A), then z = L^-1 y and alpha = L^-T z
 // theta_current: h->theta already holds theta(u) -- the previous iteration's finalize step wrote it (fit_impl)
-static int factor_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
-                       const double* u, bool theta_current = false, bool defer_alpha = false) {
+int factor_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, const double* u,
+                bool theta_current, bool defer_alpha) {
     const int64_t np = h->np, ld = h->ld;
     if (!theta_current) GP_TRY(launch_theta(h, m, u));
     if (h->refl.mask)      // symmetry-reduced model: problem b of the batch is the block of sign pattern b (engine.hip)
@@ -708,9 +708,7 @@ int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<
     return rc;
 }
 
-static void vgp_release(gpimhip_ctx* h);
 static void pkron_release(gpimhip_ctx* h);
-static void sm_release(gpimhip_ctx* h);
 static void dist_plan_release(gpimhip_ctx* h);
 // the distributed entry points address the workspace (diagonal-block inverses, batch strides) through the plan's block
 // count: a handle whose workspace was re-sized after gpimhip_dist_setup must not be used with the stale plan
@@ -900,85 +898,103 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
 }
 
 
-// Multi-output GP in reflection mode (vgp.hip): the batch is T tasks of nrep = 2^r consecutive problems each; predict_cols
-// sums each task's blocks and mixes the tasks (vgp_group_combine_kernel) into M x T outputs
-struct VgpGroup { int T, nrep; const VgpDev* st; };
+// test-point columns per chunk of predict_cols: the K* slabs of all B problems together stay <= ~1 GiB
+// (C++ linkage, as model_state_at_u below: this and the next two are declared in common.hpp)
+extern "C++" int64_t predict_chunk_cols(int64_t np, int B, int64_t M) {
+    int64_t mc = std::min(pad_to(M, NB), std::max<int64_t>(NB, ((int64_t)1 << 27) / np / B / NB * NB));
+    // run-time knob for the tests: at most this many columns (rounded down to whole tiles), so that the second and the ragged
+    // last pass of the loop run at test sizes
+    if (const char* e = getenv("GPIMHIP_PREDICT_CHUNK")) mc = std::min(mc, std::max<int64_t>(NB, atoll(e) / NB * NB));
+    return mc;
+}
 
-// posterior mean / variance at M test points from the factorised model in the workspace (theta, L^-1, alpha)
-static int predict_cols(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, int B,
-                        const double* Xs, int64_t M, double* mean_out, double* var_out, const VgpGroup* vgrp = nullptr) {
-    const int64_t np = h->np;
+// posterior mean / variance at the family's test points from the factorised model in the workspace (L^-1, alpha; with a
+// border Y_b): per chunk the family's K* slab, mean_tmp = K*^T alpha, colpart = column sums of squares of L^-1 K* (and
+// rsq = those of R = sum_b Y_b^T K*_b), then the family's finisher
+extern "C++" int predict_cols(gpimhip_ctx* h, const PredictFamily& f, int64_t N, int B) {
+    const int64_t np = h->np, M = f.M;
     const int nb = (int)(np / NB);
     // few observations: one fused launch, K* stays in LDS (predict.hip)
-    if (!h->fp32 && fused_predict_fits(np) && !h->refl.mask)
-        return launch_predict_fused(h, m, X, x_bs, N, Xs, M, mean_out, var_out, nullptr, nullptr, -1, 0.0, nullptr, 0.0,
-                                    nullptr);
-    // chunk the test points so that the K* slabs of all problems together stay <= ~1 GiB
-    int64_t mc = pad_to(M, NB);
-    const int64_t cap = std::max<int64_t>(NB, ((int64_t)1 << 27) / np / B / NB * NB);
-    mc = std::min(mc, cap);
+    if (f.fused && !h->fp32 && fused_predict_fits(np)) return f.fused();
+    const int64_t mc = predict_chunk_cols(np, B, M);
     GP_TRY(ws_ensure_predict(h, np, mc));
-    const int64_t mcap = h->ks_cols, kld = mcap + 16;       // buffer strides follow the capacity
     const bool bd = border_on(h);
-    if (bd) GP_TRY(border_ensure_r(h, mcap));
+    if (bd) GP_TRY(border_ensure_r(h, h->ks_cols));
     for (int64_t m0 = 0; m0 < M; m0 += mc) {
-        const int64_t cnt = std::min(mc, M - m0);
-        const int64_t cpad = pad_to(cnt, NB);
-        // the test grid Xs is shared by all problems of the batch (z stride 0)
-        if (h->refl.mask)      // V_s^T k(X, x*): the block's rows against the test point and its mirror images, |G|^-1/2 each
-            GP_TRY(launch_kmat_refl(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, h->Ks, kld, np, cpad, 0, x_bs, 0, np * kld,
-                                    1.0 / sqrt((double)(vgrp ? vgrp->nrep : h->refl.nblocks_total > 0 ? h->refl.nblocks_total : B))));
-        else
-            GP_TRY(launch_kmat(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, x_bs, 0,
-                               np * kld));
-        GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
-        if (!h->refl.mask) GP_TRY(launch_copy_slice(h, h->mean_tmp, mean_out + m0, cnt, mcap, M));
+        const int64_t cnt = std::min(mc, M - m0), mcap = h->ks_cols;       // buffer strides follow the capacity
+        PredictChunk c{f.Xs + m0 * f.dim, m0, cnt, pad_to(cnt, NB), mcap, mcap + 16, cnt, nullptr};
+        GP_TRY(f.slab(c));
+        GP_TRY(launch_gemv_t(h, h->Ks, c.kld, np, c.cpad, h->alpha, h->mean_tmp, 0, np * c.kld, np, c.mcap));
+        if (f.mean) GP_TRY(f.mean(c));
         // reflection blocks: the variance may be wanted for the first var_count test points only (it is invariant under
         // the reflections: a caller predicting on the training grid asks for it on the fundamental domain)
         // (not with a border: the missing points break the symmetry of the variance)
-        const int64_t nvar = (h->refl.mask && h->refl.var_count > 0 && !bd && !vgrp) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
-        if (nvar == 0) {
-            GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, 0, mcap, mean_out, var_out));
-            continue;
+        if (f.var_on_domain && h->refl.var_count > 0 && !bd) c.nvar = std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0));
+        if (c.nvar > 0) {
+            GemmArgs g = gemm_args(h->A, h->ld, h->Ks, c.kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
+            if (c.nvar < c.cnt) g.cj_max = (int)((c.nvar + NB - 1) / NB);
+            g.sB = np * c.kld;
+            g.colpart = h->colpart;
+            g.ld_colpart = c.mcap;
+            g.sColpart = (int64_t)nb * c.mcap;
+            // a ragged last chunk still sweeps all column tiles of the slab (stale columns are ignored)
+            g.ntiles = (int)h->pred_ntiles;
+            g.chunk = deal_chunk(g.ntiles);
+            g.rag = h->fp32 ? 0 : rag_of(N, np);
+            { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
+            if (bd) {
+                // R = sum_b Y_b^T K*_b: the stacked blocks of Y and of the slab are (B np)-row matrices (TN, one problem per
+                // border: sub's batch -- the multi-output GP's tasks, each with its 2^r blocks and K* at its own variance)
+                BorderWs* w = bws(h);
+                w->sub->stream = h->stream;
+                const int64_t brows = (int64_t)(B / w->T) * np;
+                GemmArgs gr = gemm_args(w->Y, w->mp, h->Ks, c.kld, w->R, w->r_cols, 1.0, 0.0, nullptr, 0, 0);
+                gr.sA = brows * w->mp;
+                gr.sB = brows * c.kld;
+                gr.sC = w->mp * w->r_cols;
+                gr.rect_rows = (int)(w->mp / NB);
+                gr.rect_cols = (int)(c.cpad / NB);
+                gr.ntiles = gr.rect_rows * gr.rect_cols;
+                gr.kfix0 = 0;
+                gr.kfix1 = (int)(brows / NB);
+                gr.chunk = deal_chunk(gr.ntiles);
+                GP_TRY(launch_gemm(w->sub, true, true, EPI_STORE, gr));
+                GP_TRY(launch_border_colsumsq(h, w, c.cnt));
+                c.radd = w->rsq;
+            }
         }
-        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
-        if (nvar < cnt) g.cj_max = (int)((nvar + NB - 1) / NB);
-        g.sB = np * kld;
-        g.colpart = h->colpart;
-        g.ld_colpart = mcap;
-        g.sColpart = (int64_t)nb * mcap;
-        // a ragged last chunk still sweeps all column tiles of the slab (stale columns are ignored)
-        g.ntiles = (int)h->pred_ntiles;
-        g.chunk = deal_chunk(g.ntiles);
-        g.rag = h->fp32 ? 0 : rag_of(N, np);
-        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
-        const double* radd = nullptr;
-        if (bd) {
-            // R = sum_b Y_b^T K*_b: the stacked blocks of Y and of the slab are (B np)-row matrices (TN, one problem per
-            // border: sub's batch -- the multi-output GP's tasks, each with its 2^r blocks and K* at its own variance)
-            BorderWs* w = bws(h);
-            w->sub->stream = h->stream;
-            const int64_t brows = (int64_t)(B / w->T) * np;
-            GemmArgs gr = gemm_args(w->Y, w->mp, h->Ks, kld, w->R, w->r_cols, 1.0, 0.0, nullptr, 0, 0);
-            gr.sA = brows * w->mp;
-            gr.sB = brows * kld;
-            gr.sC = w->mp * w->r_cols;
-            gr.rect_rows = (int)(w->mp / NB);
-            gr.rect_cols = (int)(cpad / NB);
-            gr.ntiles = gr.rect_rows * gr.rect_cols;
-            gr.kfix0 = 0;
-            gr.kfix1 = (int)(brows / NB);
-            gr.chunk = deal_chunk(gr.ntiles);
-            GP_TRY(launch_gemm(w->sub, true, true, EPI_STORE, gr));
-            GP_TRY(launch_border_colsumsq(h, w, cnt));
-            radd = w->rsq;
-        }
-        if (vgrp) GP_TRY(launch_vgp_group_combine(h, vgrp->T, vgrp->nrep, nb, mcap, m0, cnt, vgrp->st, mean_out, var_out, radd,
-                                                 bd ? bws(h)->r_cols : 0));
-        else if (h->refl.mask) GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
-        else GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
+        GP_TRY(f.finish(c));
     }
     return GPIMHIP_OK;
+}
+
+// The stationary kernels (engine.hip) at the parameters in h->theta.  Dense: the fused launch where it fits, else the mean
+// copied out and the variance from colpart.  Reflection mode: V_s^T k(X, x*), the block's rows against the test point and
+// its mirror images, |G|^-1/2 each; the coupled finisher sums the blocks.  The test grid is shared by all problems of the
+// batch (z stride 0).
+extern "C++" PredictFamily stationary_family(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
+                                             int B, const double* Xs, int64_t M, double* mean_out, double* var_out) {
+    PredictFamily f{m->dim, Xs, M};
+    if (h->refl.mask) {
+        const double scale = 1.0 / sqrt((double)(h->refl.nblocks_total > 0 ? h->refl.nblocks_total : B));
+        f.var_on_domain = true;
+        f.slab = [=](const PredictChunk& c) {
+            return launch_kmat_refl(h, m, X, N, c.Z, c.cnt, h->theta, h->Ks, c.kld, h->np, c.cpad, 0, x_bs, 0, h->np * c.kld, scale);
+        };
+        f.finish = [=](const PredictChunk& c) {
+            return launch_predict_coupled(h, c.mcap, (int)(h->np / NB), c.m0, c.cnt, c.nvar, c.mcap, mean_out, var_out, c.radd);
+        };
+        return f;
+    }
+    f.fused = [=] {
+        return launch_predict_fused(h, m, X, x_bs, N, Xs, M, mean_out, var_out, nullptr, nullptr, -1, 0.0, nullptr, 0.0, nullptr);
+    };
+    f.slab = [=](const PredictChunk& c) {
+        return launch_kmat(h, m, X, N, c.Z, c.cnt, h->theta, 0.0, 0, h->Ks, c.kld, h->np, c.cpad, 0, 0, x_bs, 0, h->np * c.kld);
+    };
+    f.mean = [=](const PredictChunk& c) { return launch_copy_slice(h, h->mean_tmp, mean_out + c.m0, c.cnt, c.mcap, M); };
+    f.finish = [=](const PredictChunk& c) { return launch_predict_var(h, c.mcap, (int)(h->np / NB), c.m0, c.cnt, var_out, M); };
+    return f;
 }
 
 // The model's state at u, what a prediction and a draw through the border start from: theta, L^-1 (h->A), alpha and, with a
@@ -1005,7 +1021,7 @@ static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
                         int64_t N, int B, const double* u, const double* Xs, int64_t M, double* mean_out,
                         double* var_out) {
     GP_TRY(model_state_at_u(h, m, X, x_bs, y, N, B, u));
-    GP_TRY(predict_cols(h, m, X, x_bs, N, B, Xs, M, mean_out, var_out));
+    GP_TRY(predict_cols(h, stationary_family(h, m, X, x_bs, N, B, Xs, M, mean_out, var_out), N, B));
     return finish_and_check(h);
 }
 
@@ -1115,7 +1131,7 @@ int gpimhip_acquire_exact(gpimhip_handle h, const gpimhip_model_t* m, const doub
         if (fused) {
             GP_TRY(launch_predict_fused(h, m, X, 0, N, Xobs, Mobs, mo, nullptr, so, nullptr, -1, 0.0, nullptr, 0.0, nullptr));
         } else {
-            GP_TRY(predict_cols(h, m, X, 0, N, 1, Xobs, Mobs, mo, so));
+            GP_TRY(predict_cols(h, stationary_family(h, m, X, 0, N, 1, Xobs, Mobs, mo, so), N, 1));
             GP_TRY(launch_acq_from_var(h, kind, mo, so, Mobs, 0.0, nullptr, 0.0, nullptr, so, nullptr));
         }
         const int64_t nmax = (kind == GPIMHIP_ACQ_EI) ? Mobs : 2 * Mobs;
@@ -1131,7 +1147,7 @@ int gpimhip_acquire_exact(gpimhip_handle h, const gpimhip_model_t* m, const doub
         GP_TRY(launch_predict_fused(h, m, X, 0, N, Xs, M, mean_out, nullptr, sd_out, acq_out, kind, p0, inc, p1, mask));
     } else {
         // sd_out doubles as the variance buffer of the slab path
-        GP_TRY(predict_cols(h, m, X, 0, N, 1, Xs, M, mean_out, sd_out));
+        GP_TRY(predict_cols(h, stationary_family(h, m, X, 0, N, 1, Xs, M, mean_out, sd_out), N, 1));
         GP_TRY(launch_acq_from_var(h, kind, mean_out, sd_out, M, p0, inc, p1, mask, sd_out, acq_out));
     }
     return finish_and_check(h);
@@ -1654,162 +1670,6 @@ int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
-// multi-output GP (gpimhip_vgp_nll_grad / gpimhip_fit_vgp / gpimhip_predict_vgp): T single-task blocks of the batched
-// engine, x_stride 0, whose per-problem theta comes from vgp_setup_kernel (vgp.hip)
-// ------------------------------------------------------------------------------------------
-struct VgpWs {
-    DevBuf<VgpDev> st;
-    DevBuf<double> adam;            // 2 x VGP_MAXP: Adam m, v
-    DevBuf<int32_t> iter;
-    DevBuf<double> kb;              // T x np: K beta_t (reflection mode: T 2^r x np, K_b beta_{t,b})
-    DevBuf<double> pred;            // 2 x T x M: the blocks' mean and variance
-};
-static void vgp_release(gpimhip_ctx* h) {
-    VgpWs* w = (VgpWs*)h->vgp;
-    if (!w) return;
-    dev_release(h, w->st, w->adam, w->iter, w->kb, w->pred);
-    delete w;
-    h->vgp = nullptr;
-}
-static int vgp_ws(gpimhip_ctx* h, int nprob, int T, int64_t M, VgpWs** out) {
-    VgpWs* w = (VgpWs*)h->vgp;
-    if (!w) {
-        w = new VgpWs();
-        h->vgp = w;
-        GP_TRY(w->st.alloc(h, 1));
-        GP_TRY(w->adam.alloc(h, 2 * VGP_MAXP));
-        GP_TRY(w->iter.alloc(h, 1));
-    }
-    const int64_t kb = (int64_t)nprob * h->np, pr = 2 * (int64_t)T * M;
-    GP_TRY(w->kb.grow(h, kb));
-    GP_TRY(w->pred.grow(h, pr));
-    *out = w;
-    return GPIMHIP_OK;
-}
-// the problems per task: 2^r in reflection mode (r = the reflected axes), else 1
-static int vgp_nrep(const gpimhip_ctx* h) { return h->refl.mask ? 1 << __builtin_popcount(h->refl.mask) : 1; }
-int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y, int64_t N) {
-    if (!h || !m || !vg || !X || !Y || N < 1) return GPIMHIP_E_BADARG;
-    FP64_ONLY(h);
-    GP_TRY(check_model(m));
-    if (m->kernel != GPIMHIP_KERNEL_RBF && m->kernel != GPIMHIP_KERNEL_MATERN52) {
-        gpim_set_error("the multi-output GP takes the RBF or Matern52 kernel");
-        return GPIMHIP_E_BADARG;
-    }
-    if (vg->tasks < 1 || vg->tasks > GPIMHIP_VGP_MAX_TASKS || (!vg->independent && (vg->rank < 1 || vg->rank > vg->tasks)) ||
-        vgp_layout(*m, *vg).P > 256) {
-        gpim_set_error("the multi-output GP takes 1 .. 16 tasks and an IndexKernel rank of 1 .. tasks");
-        return GPIMHIP_E_BADARG;
-    }
-    if (h->refl.mask && (h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw)) {
-        gpim_set_error("the multi-output GP in reflection mode needs all 2^r blocks on one handle (unsharded)");
-        return GPIMHIP_E_BADARG;
-    }
-    return GPIMHIP_OK;
-}
-// Loss and gradient at u (and, fit mode, one Adam step): setup -> z -> the T blocks' K, L, L^-1, z, beta -> K^-1 ->
-// gradient contraction -> K beta -> finalize.  Every launch reads its iteration-dependent values from the device.
-// Reflection mode: the same sequence on the T 2^r blocks A_{t,b} of N = N_q points each.
-// With a border (gpimhip_set_border) the T borders S_t correct beta and the inverses after the K^-1
-// product; everything downstream reads the corrected ones.
-static int vgp_iter(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, VgpWs* w, const double* X,
-                    const double* Y, int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
-    const int64_t np = h->np;
-    const int T = vg->tasks;
-    const bool refl = h->refl.mask != 0;
-    const int nrep = vgp_nrep(h);
-    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, nrep));
-    const bool bd = border_on(h);
-    if (refl) GP_TRY(launch_vgp_project_refl(h, Y, N, T, nrep, bd ? bws(h)->uo : nullptr, w->st));
-    else GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
-    GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
-    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
-    if (bd) GP_TRY(border_iter(h, N, true));
-    if (refl) {
-        GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
-        GP_TRY(launch_vgp_kbeta_refl(h, m, X, N, T, nrep, w->kb));
-    } else {
-        GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
-        GP_TRY(launch_vgp_kbeta(h, m, X, N, T, w->kb));
-    }
-    const AdamStep st = adam_step_init();
-    return launch_vgp_finalize(h, m, vg, N, w->kb, w->st, u, w->adam, w->adam + VGP_MAXP, do_adam, st, loss_out, grad_out, fi,
-                               refl ? nrep : 0, bd ? bws(h)->scal : nullptr);
-}
-static int vgp_begin(gpimhip_ctx* h, const gpimhip_vgp_t* vg, int64_t N, int64_t M, VgpWs** w) {
-    HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = vg->tasks * vgp_nrep(h);
-    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(ws_ensure_padded(h, N));
-    GP_TRY(vgp_ws(h, h->nbatch, vg->tasks, M, w));
-    if (!border_on(h)) return GPIMHIP_OK;
-    // the T borders' buffers, and U 1_o for the task means (outside any capture; N = the points of the fundamental domain)
-    GP_TRY(border_ensure(h, vg->tasks));
-    BorderWs* b = bws(h);
-    const int nrep = vgp_nrep(h);
-    GP_TRY(b->uo.grow(h, (int64_t)nrep * N));
-    return launch_border_ones(h, b, N, nrep, b->uo);
-}
-
-extern "C" {
-
-int gpimhip_vgp_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
-                         const double* Y, int64_t N, const double* u, double* loss_out, double* grad_out) {
-    GP_TRY(vgp_check(h, m, vg, X, Y, N));
-    if (!u) return GPIMHIP_E_BADARG;
-    VgpWs* w = nullptr;
-    GP_TRY(vgp_begin(h, vg, N, 0, &w));
-    GP_TRY(vgp_iter(h, m, vg, w, X, Y, N, const_cast<double*>(u), 0, loss_out, grad_out, FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
-    return finish_and_check(h);
-}
-
-int gpimhip_fit_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y,
-                    int64_t N, double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out) {
-    GP_TRY(vgp_check(h, m, vg, X, Y, N));
-    if (!u_inout || T < 0) return GPIMHIP_E_BADARG;
-    VgpWs* w = nullptr;
-    GP_TRY(vgp_begin(h, vg, N, 0, &w));
-    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * VGP_MAXP * sizeof(double), w->iter));
-    if (T == 0) return finish_and_check(h);
-    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
-    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
-                              [&] { return vgp_iter(h, m, vg, w, X, Y, N, u_inout, 1, nullptr, nullptr, fi); });
-}
-
-int gpimhip_predict_vgp(gpimhip_handle h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X,
-                        const double* Y, int64_t N, const double* u, const double* Xs, int64_t M, double* mean_out,
-                        double* var_out) {
-    GP_TRY(vgp_check(h, m, vg, X, Y, N));
-    if (!u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
-    VgpWs* w = nullptr;
-    GP_TRY(vgp_begin(h, vg, N, M, &w));
-    const int T = vg->tasks;
-    if (h->refl.mask) {          // the blocks' posterior summed per task and mixed straight into the M x T outputs
-        const VgpGroup grp{T, vgp_nrep(h), w->st};
-        GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, grp.nrep));
-        const bool bd = border_on(h);
-        GP_TRY(launch_vgp_project_refl(h, Y, N, T, grp.nrep, bd ? bws(h)->uo : nullptr, w->st));
-        GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
-        if (bd) {       // the corrected beta and Y_{t,b} (the inverses themselves are not needed)
-            GP_TRY(launch_lauum(h, h->A, h->B, h->np, h->ld, rag_of(N, h->np)));
-            GP_TRY(border_iter(h, N, false));
-        }
-        GP_TRY(predict_cols(h, m, X, 0, N, h->nbatch, Xs, M, mean_out, var_out, &grp));
-        return finish_and_check(h);
-    }
-    GP_TRY(launch_vgp_setup(h, m, vg, u, w->st, 1));
-    GP_TRY(launch_vgp_project(h, Y, N, T, w->st));
-    GP_TRY(factor_at_u(h, m, X, 0, N, u, true, false));
-    double* mblk = w->pred;
-    double* vblk = w->pred + (int64_t)T * M;
-    GP_TRY(predict_cols(h, m, X, 0, N, T, Xs, M, mblk, vblk));
-    GP_TRY(launch_vgp_combine(h, T, M, w->st, mblk, vblk, mean_out, var_out));
-    return finish_and_check(h);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
 // dense-by-Kronecker blocks (gpimhip_pkron_nll_grad / gpimhip_fit_pkron / gpimhip_predict_pkron; pkron.hip, DESIGN.md section
 // 22): a grid whose missing points are whole columns.  J = prod n_i blocks s2 lambda_j K_s + sigma I of the N_s observed ragged
 // points run in lock-step through the batched engine (B = J, shared X_s); the complete axes are a KronAxes set of kron.hip.
@@ -2089,337 +1949,6 @@ int gpimhip_predict_pkron(gpimhip_handle h, const gpimhip_model_t* m, const doub
             GP_TRY(pkron_mode_chain(h, mp, n_test_c, bmat, raw[v], bufa, bufa + pmax * mc, 1, mc, v, &raw[v]));
         }
         GP_TRY(launch_pkron_post(h, w->th3, Mc, mc, m0, cnt, raw[0], raw[1], mean_out, var_out));
-    }
-    return finish_and_check(h);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// spectral-mixture kernel (gpimhip_sm_kmat / gpimhip_sm_nll_grad / gpimhip_fit_sm / gpimhip_predict_sm): the general padded
-// exact-GP path at every N (no fused small-N trainer, no fused predict), with the covariance, the gradient contraction and
-// the finalize step of sm.hip.  Parameters, Adam state and history live here: P = 2 + Q (2 D + 1) exceeds GPIMHIP_MAX_PARAMS.
-// ------------------------------------------------------------------------------------------
-struct SmWs {
-    DevBuf<SmDev> st;
-    DevBuf<double> adam;            // 2 x SM_MAXP: Adam m, v
-    DevBuf<int32_t> iter;
-    DevBuf<double> sums;            // SM_MAXP: the gradient records added up over the tiles
-    DevBuf<double> csx;             // 2 Q dim x np: phases of the training points
-    DevBuf<double> csz;             // 2 Q dim x (test chunk): phases of the test points
-    DevBuf<double> part;            // records x lower tiles
-};
-static void sm_release(gpimhip_ctx* h) {
-    SmWs* w = (SmWs*)h->sm;
-    if (!w) return;
-    dev_release(h, w->st, w->adam, w->iter, w->sums, w->csx, w->csz, w->part);
-    delete w;
-    h->sm = nullptr;
-}
-// np_x: phase slots of the training points (0: none), mz: of the test points, ntile: lower tiles of the gradient records
-static int sm_ws(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t np_x, int64_t mz, int64_t ntile, SmWs** out) {
-    SmWs* w = (SmWs*)h->sm;
-    if (!w) {       // the fixed buffers first; the workspace is published only once all of them exist
-        w = new SmWs();
-        int rc = w->st.alloc(h, 1);
-        if (rc == GPIMHIP_OK) rc = w->adam.alloc(h, 2 * SM_MAXP);
-        if (rc == GPIMHIP_OK) rc = w->iter.alloc(h, 1);
-        if (rc == GPIMHIP_OK) rc = w->sums.alloc(h, SM_MAXP);
-        h->sm = w;
-        if (rc != GPIMHIP_OK) {
-            sm_release(h);
-            return rc;
-        }
-    }
-    const int64_t per = 2 * (int64_t)sm->mixtures * sm->dim;
-    GP_TRY(w->csx.grow(h, per * np_x));
-    GP_TRY(w->csz.grow(h, per * mz));
-    GP_TRY(w->part.grow(h, (int64_t)sm_layout(*sm).P * ntile));
-    *out = w;
-    return GPIMHIP_OK;
-}
-// B = 0: a dense entry point (no reflection mode); B > 0: the blocks of a handle in reflection mode
-int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B) {
-    if (!h || !sm || !X || N < 1) return GPIMHIP_E_BADARG;
-    FP64_ONLY(h);
-    if (sm->dim < 1 || sm->dim > GPIMHIP_MAX_DIM || sm->mixtures < 1 || sm->mixtures > GPIMHIP_SM_MAX_MIXTURES) {
-        gpim_set_error("the spectral-mixture kernel takes 1 .. 4 dimensions and 1 .. 16 mixtures");
-        return GPIMHIP_E_BADARG;
-    }
-    if (h->refl.mask && B == 0) {
-        gpim_set_error("the spectral-mixture kernel on a handle in reflection mode runs through gpimhip_sm_nll_grad_batched / "
-                       "gpimhip_fit_sm_batched / gpimhip_predict_sm_batched (the dense entry points need gpimhip_set_reflection(h, 0, ...))");
-        return GPIMHIP_E_BADARG;
-    }
-    if (B > 0 && (!h->refl.mask || (h->refl.mask >> sm->dim) || B != (1 << __builtin_popcount(h->refl.mask)) ||
-                  h->refl.pb_stride != 1 || h->refl.pb_off != 0 || h->refl.raw || h->refl.n_total < 1)) {
-        gpim_set_error("the spectral-mixture blocks need a handle in reflection mode (gpimhip_set_reflection) with all B = 2^r "
-                       "blocks of the reflected axes on it (unsharded), the axes within the kernel's dimensions");
-        return GPIMHIP_E_BADARG;
-    }
-    return GPIMHIP_OK;
-}
-static int sm_begin(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, SmWs** w) {
-    HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = 1;
-    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(ws_ensure_padded(h, N));
-    const int64_t nb = h->np / NB;
-    return sm_ws(h, sm, h->np, 0, nb * (nb + 1) / 2, w);
-}
-// u -> parameters, r = y - c, phases; K -> L^-1; z = L^-1 r, alpha = K^-1 r
-static int sm_factor(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* y, int64_t N,
-                     const double* u) {
-    const int64_t np = h->np, ld = h->ld;
-    GP_TRY(launch_sm_setup(h, sm, u, X, N, np, w->csx, y, h->ypad, w->st, h->theta));
-    { StageTimer t(h, 4); GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, np, nullptr, N, nullptr, np, w->st, h->A, ld, np, np, 1, 1)); }
-    GP_TRY(launch_potrf_inv(h, h->A, h->Tm, np, ld, h->info, rag_of(N, np)));
-    return solve_vectors(h, nullptr, X, 0, N, false);
-}
-// loss and gradient at u (fit mode: and one Adam step); every launch reads its iteration-dependent values from the device
-static int sm_iter(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* y, int64_t N, double* u,
-                   int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
-    const int64_t np = h->np;
-    GP_TRY(sm_factor(h, sm, w, X, y, N, u));
-    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
-    { StageTimer t(h, 5); GP_TRY(launch_sm_grad(h, sm, h->B, h->ld, X, N, w->csx, np, h->alpha, w->st, w->part, w->sums)); }
-    const AdamStep st = adam_step_init();
-    return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi);
-}
-
-// ---- the reflection blocks of a grid: the handle is in reflection mode, the batch is its B = 2^r
-// blocks on the N points X of the fundamental domain, ys / ones (B x N) the targets and U 1 (U 1_o with a border) in the
-// adapted basis, ONE parameter vector.  The engine's batched factor + inverse, solves and K^-1 product; with a border
-// (gpimhip_set_border) the kernel-agnostic border stage of border.hip between the inverse and the contraction.
-static int sm_begin_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, int64_t N, int B, SmWs** w) {
-    HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = B;
-    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(ws_ensure_padded(h, N));
-    if (border_on(h)) GP_TRY(border_ensure(h));
-    const int64_t nb = h->np / NB;
-    return sm_ws(h, sm, h->np, 0, B * nb * (nb + 1) / 2, w);
-}
-static int sm_factor_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* ys, const double* ones,
-                          int64_t N, const double* u) {
-    const int64_t np = h->np, ld = h->ld;
-    GP_TRY(launch_sm_setup_refl(h, sm, u, X, N, np, w->csx, ys, ones, h->ypad, w->st, h->theta));
-    { StageTimer t(h, 4); GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, np, nullptr, N, nullptr, np, w->st, h->A, ld, np * ld, np, np, 1, 1, 1.0)); }
-    GP_TRY(launch_potrf_inv(h, h->A, h->Tm, np, ld, h->info, rag_of(N, np)));
-    return solve_vectors(h, nullptr, X, 0, N, false);
-}
-static int sm_iter_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, const double* ys, const double* ones,
-                        int64_t N, double* u, int do_adam, double* loss_out, double* grad_out, FinalizeIter fi) {
-    const int64_t np = h->np;
-    GP_TRY(sm_factor_refl(h, sm, w, X, ys, ones, N, u));
-    { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
-    const bool bd = border_on(h);
-    if (bd) GP_TRY(border_iter(h, N, true));
-    { StageTimer t(h, 5); GP_TRY(launch_sm_grad_refl(h, sm, h->B, h->ld, X, N, w->csx, np, h->alpha, w->st, w->part, w->sums)); }
-    const AdamStep st = adam_step_init();
-    return launch_sm_finalize(h, sm, N, w->sums, w->st, u, w->adam, w->adam + SM_MAXP, do_adam, st, loss_out, grad_out, fi, ones,
-                              h->refl.n_total, bd ? bws(h)->scal : nullptr);
-}
-// posterior of the blocks at M test points (predict_cols with the blocks' cross-covariance): mean = c + sum_b K*_b^T alpha_b,
-// var = sum w + noise - sum_b |L_b^-1 K*_b|^2 (+ |sum_b Y_b^T k*_b|^2 with a border)
-static int sm_predict_refl(gpimhip_ctx* h, const gpimhip_sm_t* sm, SmWs* w, const double* X, int64_t N, int B, const double* u,
-                           const double* Xs, int64_t M, double* mean_out, double* var_out) {
-    const int64_t np = h->np;
-    const int nb = (int)(np / NB);
-    int64_t mc = pad_to(M, NB);
-    mc = std::min(mc, std::max<int64_t>(NB, ((int64_t)1 << 27) / np / B / NB * NB));
-    GP_TRY(ws_ensure_predict(h, np, mc));
-    GP_TRY(sm_ws(h, sm, np, mc, (int64_t)B * nb * (nb + 1) / 2, &w));
-    const int64_t mcap = h->ks_cols, kld = mcap + 16;
-    const bool bd = border_on(h);
-    if (bd) GP_TRY(border_ensure_r(h, mcap));
-    for (int64_t m0 = 0; m0 < M; m0 += mc) {
-        const int64_t cnt = std::min(mc, M - m0);
-        const int64_t cpad = pad_to(cnt, NB);
-        const double* Zc = Xs + m0 * sm->dim;
-        GP_TRY(launch_sm_setup_refl(h, sm, u, Zc, cnt, cpad, w->csz, nullptr, nullptr, nullptr, nullptr, nullptr));
-        GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, np, Zc, cnt, w->csz, cpad, w->st, h->Ks, kld, np * kld, np, cpad, 0, 0,
-                                   1.0 / sqrt((double)B)));
-        GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
-        // (complete grids: the variance is invariant under the reflections -- ReflArgs::var_count, as predict_cols)
-        const int64_t nvar = (h->refl.var_count > 0 && !bd) ? std::max<int64_t>(0, std::min(cnt, h->refl.var_count - m0)) : cnt;
-        const double* radd = nullptr;
-        if (nvar > 0) {
-            GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
-            if (nvar < cnt) g.cj_max = (int)((nvar + NB - 1) / NB);
-            g.sB = np * kld;
-            g.colpart = h->colpart;
-            g.ld_colpart = mcap;
-            g.sColpart = (int64_t)nb * mcap;
-            g.ntiles = (int)h->pred_ntiles;
-            g.chunk = deal_chunk(g.ntiles);
-            g.rag = rag_of(N, np);
-            { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
-            if (bd) {       // R = sum_b Y_b^T K*_b over the stacked blocks (predict_cols)
-                BorderWs* bw = bws(h);
-                bw->sub->stream = h->stream;
-                const int64_t brows = (int64_t)B * np;
-                GemmArgs gr = gemm_args(bw->Y, bw->mp, h->Ks, kld, bw->R, bw->r_cols, 1.0, 0.0, nullptr, 0, 0);
-                gr.sA = brows * bw->mp;
-                gr.sB = brows * kld;
-                gr.sC = bw->mp * bw->r_cols;
-                gr.rect_rows = (int)(bw->mp / NB);
-                gr.rect_cols = (int)(cpad / NB);
-                gr.ntiles = gr.rect_rows * gr.rect_cols;
-                gr.kfix0 = 0;
-                gr.kfix1 = (int)(brows / NB);
-                gr.chunk = deal_chunk(gr.ntiles);
-                GP_TRY(launch_gemm(bw->sub, true, true, EPI_STORE, gr));
-                GP_TRY(launch_border_colsumsq(h, bw, cnt));
-                radd = bw->rsq;
-            }
-        }
-        GP_TRY(launch_predict_coupled(h, mcap, nb, m0, cnt, nvar, mcap, mean_out, var_out, radd));
-        GP_TRY(launch_sm_addc(h, mean_out + m0, cnt, w->st));
-    }
-    return GPIMHIP_OK;
-}
-
-extern "C" {
-
-int gpimhip_sm_kmat(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, int64_t N, const double* Z, int64_t M,
-                    const double* u, double* out, int64_t ld) {
-    const int B = (h && h->refl.mask) ? 1 << __builtin_popcount(h->refl.mask) : 0;
-    GP_TRY(sm_check(h, sm, X, N, B));
-    const bool sym = (Z == nullptr);
-    const int64_t Mv = sym ? N : M;
-    if (!u || !out || Mv < 1 || ld < Mv) return GPIMHIP_E_BADARG;
-    HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = 1;
-    if (B) {       // reflection mode: the B blocks K_s (or K_s(X, Z) / sqrt(B)) stacked, B N rows
-        BatchScope batch(h, B);
-        const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
-        SmWs* w = nullptr;
-        GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
-        GP_TRY(ws_ensure_predict(h, rp, cp));
-        const int64_t kld = h->ks_cols + 16;
-        GP_TRY(launch_sm_setup_refl(h, sm, u, X, N, rp, w->csx, nullptr, nullptr, nullptr, w->st, nullptr));
-        if (!sym) GP_TRY(launch_sm_setup_refl(h, sm, u, Z, M, cp, w->csz, nullptr, nullptr, nullptr, nullptr, nullptr));
-        GP_TRY(launch_sm_kmat_refl(h, sm, X, N, w->csx, rp, Z, Mv, w->csz, cp, w->st, h->Ks, kld, rp * kld, rp, cp, sym ? 1 : 0, 0,
-                                   sym ? 1.0 : 1.0 / sqrt((double)B)));
-        for (int b = 0; b < B; ++b)
-            HIP_TRY(hipMemcpy2DAsync(out + (int64_t)b * N * ld, (size_t)ld * sizeof(double), h->Ks + (int64_t)b * rp * kld,
-                                     (size_t)kld * sizeof(double), (size_t)Mv * sizeof(double), (size_t)N,
-                                     hipMemcpyDeviceToDevice, h->stream));
-        return GPIMHIP_OK;
-    }
-    const int64_t rp = pad_to(N, NB), cp = pad_to(Mv, NB);
-    SmWs* w = nullptr;
-    GP_TRY(sm_ws(h, sm, rp, sym ? 0 : cp, 0, &w));
-    GP_TRY(ws_ensure_predict(h, rp, cp));
-    const int64_t kld = h->ks_cols + 16;
-    GP_TRY(launch_sm_setup(h, sm, u, X, N, rp, w->csx, nullptr, nullptr, w->st, nullptr));
-    if (!sym) GP_TRY(launch_sm_setup(h, sm, u, Z, M, cp, w->csz, nullptr, nullptr, nullptr, nullptr));
-    GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, rp, Z, Mv, w->csz, cp, w->st, h->Ks, kld, rp, cp, sym ? 1 : 0, 0));
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), h->Ks, (size_t)kld * sizeof(double),
-                             (size_t)Mv * sizeof(double), (size_t)N, hipMemcpyDeviceToDevice, h->stream));
-    return GPIMHIP_OK;
-}
-
-int gpimhip_sm_nll_grad(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
-                        const double* u, double* loss_out, double* grad_out) {
-    GP_TRY(sm_check(h, sm, X, N));
-    if (!y || !u) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin(h, sm, N, &w));
-    GP_TRY(sm_iter(h, sm, w, X, y, N, const_cast<double*>(u), 0, loss_out, grad_out,
-                   FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
-    return finish_and_check(h);
-}
-
-int gpimhip_fit_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N, double* u_inout,
-                   double lr, int32_t T, double* hist_out, double* loss_out) {
-    GP_TRY(sm_check(h, sm, X, N));
-    if (!y || !u_inout || T < 0) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin(h, sm, N, &w));
-    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * SM_MAXP * sizeof(double), w->iter));
-    if (T == 0) return finish_and_check(h);
-    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
-    return run_fit_iterations(h, T, FIT_LOOP_DENSE, [&] { return sm_iter(h, sm, w, X, y, N, u_inout, 1, nullptr, nullptr, fi); });
-}
-
-int gpimhip_sm_nll_grad_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
-                                int64_t N, int32_t B, const double* u, double* loss_out, double* grad_out) {
-    if (B < 1) return GPIMHIP_E_BADARG;
-    GP_TRY(sm_check(h, sm, X, N, B));
-    if (!ys || !ones || !u) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
-    GP_TRY(sm_iter_refl(h, sm, w, X, ys, ones, N, const_cast<double*>(u), 0, loss_out, grad_out,
-                        FinalizeIter{nullptr, nullptr, 0, nullptr, nullptr}));
-    return finish_and_check(h);
-}
-
-int gpimhip_fit_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
-                           int64_t N, int32_t B, double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out) {
-    if (B < 1) return GPIMHIP_E_BADARG;
-    GP_TRY(sm_check(h, sm, X, N, B));
-    if (!ys || !ones || !u_inout || T < 0) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
-    GP_TRY(fit_prologue(h, lr, T, w->adam, nullptr, 2 * SM_MAXP * sizeof(double), w->iter));
-    if (T == 0) return finish_and_check(h);
-    const FinalizeIter fi{w->iter, h->bc, T, hist_out, loss_out};
-    return run_fit_iterations(h, T, FIT_LOOP_DENSE,
-                              [&] { return sm_iter_refl(h, sm, w, X, ys, ones, N, u_inout, 1, nullptr, nullptr, fi); });
-}
-
-int gpimhip_predict_sm_batched(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* ys, const double* ones,
-                               int64_t N, int32_t B, const double* u, const double* Xs, int64_t M, double* mean_out,
-                               double* var_out) {
-    if (B < 1) return GPIMHIP_E_BADARG;
-    GP_TRY(sm_check(h, sm, X, N, B));
-    if (!ys || !ones || !u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin_refl(h, sm, N, B, &w));
-    GP_TRY(sm_factor_refl(h, sm, w, X, ys, ones, N, u));
-    if (border_on(h)) {       // the state a prediction through the border starts from (model_state_at_u)
-        GP_TRY(launch_lauum(h, h->A, h->B, h->np, h->ld, rag_of(N, h->np)));
-        GP_TRY(border_iter(h, N, false));
-    }
-    GP_TRY(sm_predict_refl(h, sm, w, X, N, B, u, Xs, M, mean_out, var_out));
-    return finish_and_check(h);
-}
-
-int gpimhip_predict_sm(gpimhip_handle h, const gpimhip_sm_t* sm, const double* X, const double* y, int64_t N,
-                       const double* u, const double* Xs, int64_t M, double* mean_out, double* var_out) {
-    GP_TRY(sm_check(h, sm, X, N));
-    if (!y || !u || !Xs || M < 1 || !mean_out || !var_out) return GPIMHIP_E_BADARG;
-    SmWs* w = nullptr;
-    GP_TRY(sm_begin(h, sm, N, &w));
-    const int64_t np = h->np;
-    const int nb = (int)(np / NB);
-    GP_TRY(sm_factor(h, sm, w, X, y, N, u));
-    // chunks of test points: the K* slab stays <= ~1 GiB (predict_cols)
-    int64_t mc = pad_to(M, NB);
-    mc = std::min(mc, std::max<int64_t>(NB, ((int64_t)1 << 27) / np / NB * NB));
-    GP_TRY(ws_ensure_predict(h, np, mc));
-    GP_TRY(sm_ws(h, sm, np, mc, (int64_t)nb * (nb + 1) / 2, &w));
-    const int64_t mcap = h->ks_cols, kld = mcap + 16;
-    for (int64_t m0 = 0; m0 < M; m0 += mc) {
-        const int64_t cnt = std::min(mc, M - m0);
-        const int64_t cpad = pad_to(cnt, NB);
-        const double* Zc = Xs + m0 * sm->dim;
-        GP_TRY(launch_sm_setup(h, sm, u, Zc, cnt, cpad, w->csz, nullptr, nullptr, nullptr, nullptr));
-        GP_TRY(launch_sm_kmat(h, sm, X, N, w->csx, np, Zc, cnt, w->csz, cpad, w->st, h->Ks, kld, np, cpad, 0, 0));
-        GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
-        GP_TRY(launch_sm_mean(h, h->mean_tmp, cnt, w->st, mean_out + m0));
-        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, nullptr, 0, 1.0, 0.0, h->pred_tiles, 0, h->np);
-        g.sB = np * kld;
-        g.colpart = h->colpart;
-        g.ld_colpart = mcap;
-        g.sColpart = (int64_t)nb * mcap;
-        g.ntiles = (int)h->pred_ntiles;       // a ragged last chunk still sweeps all column tiles of the slab
-        g.chunk = deal_chunk(g.ntiles);
-        g.rag = rag_of(N, np);
-        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_COLSUMSQ, g)); }
-        GP_TRY(launch_predict_var(h, mcap, nb, m0, cnt, var_out, M));
     }
     return finish_and_check(h);
 }

@@ -1,4 +1,5 @@
-// border.hpp -- launches of the border form of the reflection blocks (border.hip; driven by api.hip: border_* and draws.hip: sample_border_impl).
+// border.hpp -- launches of the border form of the reflection blocks (border.hip; driven by api.hip: border_*, by the model
+// families' drivers in smgp.hip and vgpgp.hip, and by draws.hip: sample_border_impl).
 #pragma once
 #include "common.hpp"
 
@@ -29,6 +30,12 @@ struct BorderWs {
 // api.hip: the handle's border (null: none was ever set), and whether one is in force
 BorderWs* bws(const gpimhip_ctx* h);
 bool border_on(const gpimhip_ctx* h);
+// api.hip: the border's buffers for the workspace's np and batch (T: the borders in lock-step) and for `cols` test columns
+// (both outside any capture), and the border stage of one evaluation after the blocks' inverses (nq: the points of the
+// fundamental domain; update_inverse: training, B_b^-1 -= Y_b Y_b^T as well)
+int border_ensure(gpimhip_ctx* h, int T = 1);
+int border_ensure_r(gpimhip_ctx* h, int64_t cols);
+int border_iter(gpimhip_ctx* h, int64_t nq, bool update_inverse);
 
 int launch_border_gather_s(gpimhip_ctx* h, const BorderWs* w, const double* Binv, int64_t ld, double* S, int64_t lds);
 int launch_border_tidy(gpimhip_ctx* h, const BorderWs* w, double* Linv, int64_t lds);

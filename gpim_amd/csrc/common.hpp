@@ -217,11 +217,11 @@ struct gpimhip_ctx {
     void* vfe = nullptr;
     // structured (Kronecker) workspace, owned by kron.hip (KronWs*); released by kron_release()
     void* kron = nullptr;
-    // multi-output GP workspace, owned by api.hip (VgpWs); released by vgp_release()
+    // multi-output GP workspace, owned by vgpgp.hip (VgpWs); released by vgp_release()
     void* vgp = nullptr;
     // dense-by-Kronecker blocks (a grid whose missing points are whole columns), owned by api.hip (PkronWs); pkron_release()
     void* pkron = nullptr;
-    // spectral-mixture workspace, owned by api.hip (SmWs); released by sm_release()
+    // spectral-mixture workspace, owned by smgp.hip (SmWs); released by sm_release()
     void* sm = nullptr;
     // border of the reflection blocks (missing points of an incomplete grid), owned by api.hip (BorderWs); border_release()
     void* border = nullptr;
@@ -322,10 +322,37 @@ static inline int gemv_tri_chunks(int64_t np) { return (int)((np + gemv_tri_rc(n
 #define OUTER_W 4    // outer Cholesky panel = 4 x 128 columns
 int ws_ensure(gpimhip_ctx* h, int64_t N);
 int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices = true);
+int ws_ensure_padded(gpimhip_ctx* h, int64_t N);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
 int deal_chunk(int ntiles = 1 << 30);
 int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
                      int B, const double* u);
+// z = L^-1 ypad and alpha = L^-T z from L^-1 in h->A; K(u) -> L^-1 in h->A, then the two (api.hip has the details)
+int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, bool defer_alpha = false);
+int factor_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, const double* u,
+                bool theta_current = false, bool defer_alpha = false);
+// One chunk of predict_cols: test points [m0, m0 + cnt) starting at Z, cpad = cnt padded to 128.  The slab h->Ks has the
+// leading dimension kld (np * kld between problems); mean_tmp and colpart have the stride mcap.  For the finisher: the
+// variance is wanted for the first nvar points of the chunk (colpart holds no more; 0: none), and with a border radd holds
+// the column sums of squares to add back (BorderWs::rsq)
+struct PredictChunk { const double* Z; int64_t m0, cnt, cpad, mcap, kld, nvar; const double* radd; };
+// What a model family supplies to predict_cols: its M test points Xs of `dim` coordinates, and per chunk
+//   slab     K* of the chunk into h->Ks, for all problems of the batch
+//   mean     (optional) runs once mean_tmp = K*^T alpha is there, before the variance product is launched: the dense
+//            finishers write their mean here
+//   finish   the chunk's mean and variance into the caller's outputs from mean_tmp / colpart / radd
+// fused (optional): the family may take the single launch of predict.hip where it fits, this is it.  var_on_domain: the
+// finisher sums reflection blocks and honours ReflArgs::var_count
+struct PredictFamily {
+    int dim; const double* Xs; int64_t M;
+    bool var_on_domain = false;
+    std::function<int()> fused;
+    std::function<int(const PredictChunk&)> slab, mean, finish;
+};
+int64_t predict_chunk_cols(int64_t np, int B, int64_t M);
+int predict_cols(gpimhip_ctx* h, const PredictFamily& f, int64_t N, int B);
+PredictFamily stationary_family(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, int B,
+                                const double* Xs, int64_t M, double* mean_out, double* var_out);
 // draws.hip
 void sample_release(gpimhip_ctx* h);
 int64_t sample_bytes(const gpimhip_ctx* h);

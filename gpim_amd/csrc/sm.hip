@@ -1,6 +1,6 @@
 // sm.hip -- the spectral-mixture (SM) kernel of the reference's skreconstructor(kernel='Spectral') (gpim/gpreg/skgpr.py,
 // GPyTorch SpectralMixtureKernel) on the exact-GP engine: the factorisation, K^-1, the solves and the variance product are
-// the engine's own (api.hip: sm_iter); this file has the covariance-specific pieces.
+// the engine's own (smgp.hip: sm_iter); this file has the covariance-specific pieces.
 //
 //   k_q(tau) = E_q C_q,  E_q = exp(-2 pi^2 sum_d tau_d^2 s_qd^2),  C_q = prod_d cos(2 pi tau_d m_qd),  K = sum_q w_q k_q + noise I
 //

@@ -1,10 +1,11 @@
-// sm.hpp -- shared declarations of the spectral-mixture kernel (sm.hip kernels, api.hip drivers, draws.hip: sm_family).
+// sm.hpp -- shared declarations of the spectral-mixture kernel (sm.hip kernels, smgp.hip drivers, draws.hip: sm_family).
 #pragma once
 #include "common.hpp"
 
-// api.hip: the argument check of every spectral-mixture entry.  B = 0: a dense entry point (no reflection mode); B > 0: the
-// blocks of a handle in reflection mode
+// smgp.hip: the argument check of every spectral-mixture entry.  B = 0: a dense entry point (no reflection mode); B > 0: the
+// blocks of a handle in reflection mode.  sm_release: frees the handle's spectral-mixture workspace (gpimhip_destroy)
 int sm_check(gpimhip_ctx* h, const gpimhip_sm_t* sm, const double* X, int64_t N, int B = 0);
+void sm_release(gpimhip_ctx* h);
 
 #define SM_MAXQ GPIMHIP_SM_MAX_MIXTURES
 #define SM_MAXP (2 + SM_MAXQ * (2 * GPIMHIP_MAX_DIM + 1))

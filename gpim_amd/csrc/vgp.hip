@@ -1,5 +1,5 @@
 // vgp.hip -- the exact multi-output (vector-valued) GP of the reference's vreconstructor (gpim/gpreg/vgpr.py), reduced to
-// T ordinary single-task GPs that share X and run in lock-step on the batched engine (api.hip: vgp_iter).
+// T ordinary single-task GPs that share X and run in lock-step on the batched engine (vgpgp.hip: vgp_iter).
 //
 // Model (GPyTorch semantics, vgpr.py:286-354): C = B (x) K + S (x) I_N, task-major vec(Y - mu), S = diag(s).
 //   B~ = S^-1/2 B S^-1/2 = Q diag(lambda) Q^T,  P = S^-1/2 Q   ->   C = (S^1/2 Q (x) I)(diag(lambda) (x) K + I)(Q^T S^1/2 (x) I)

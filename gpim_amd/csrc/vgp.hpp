@@ -1,9 +1,11 @@
-// vgp.hpp -- shared declarations of the multi-output GP (vgp.hip kernels, api.hip drivers, draws.hip: sample_vgp_*).
+// vgp.hpp -- shared declarations of the multi-output GP (vgp.hip kernels, vgpgp.hip drivers, draws.hip: sample_vgp_*).
 #pragma once
 #include "common.hpp"
 
-// api.hip: the argument check of every multi-output entry
+// vgpgp.hip: the argument check of every multi-output entry; vgp_release frees the handle's multi-output workspace
+// (gpimhip_destroy)
 int vgp_check(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_vgp_t* vg, const double* X, const double* Y, int64_t N);
+void vgp_release(gpimhip_ctx* h);
 
 #define VGP_MAXT GPIMHIP_VGP_MAX_TASKS
 #define VGP_MAXR GPIMHIP_VGP_MAX_TASKS      // IndexKernel rank <= T

@@ -59,6 +59,17 @@ def predict(eng, X, y, spec, u, Xs):
 @pytest.mark.parametrize("kind", ["RBF", "Matern52", "RationalQuadratic"])
 @pytest.mark.parametrize("N,d,M", [(17, 1, 1), (60, 2, 1000), (128, 2, 33), (129, 3, 257), (300, 2, 4097), (384, 4, 640)])
 def test_fused_predict_vs_oracle_and_slab(eng, monkeypatch, kind, N, d, M):
+    check_fused_and_slab(eng, monkeypatch, kind, N, d, M)
+
+
+@pytest.mark.parametrize("kind", ["RBF", "Matern52", "RationalQuadratic"])
+@pytest.mark.parametrize("N,d,M", [(129, 3, 257), (200, 2, 300), (384, 4, 640)])
+def test_slab_predict_in_chunks(eng, monkeypatch, kind, N, d, M):
+    """The slab leg with GPIMHIP_PREDICT_CHUNK=128: three or more chunks with a ragged last one, two or three block rows."""
+    check_fused_and_slab(eng, monkeypatch, kind, N, d, M, chunk="128")
+
+
+def check_fused_and_slab(eng, monkeypatch, kind, N, d, M, chunk=None):
     from oracle import gpim_oracle as O
     X, y, kp, spec, u, side = make_problem(N, d, kind, seed=N + d)
     rng = np.random.default_rng(M)
@@ -73,6 +84,8 @@ def test_fused_predict_vs_oracle_and_slab(eng, monkeypatch, kind, N, d, M):
     assert_allclose(mean, mo, rtol=0, atol=1e-10 * scale, equal_nan=True)
     assert_allclose(var, vo, rtol=1e-9, atol=1e-10 * np.nanmax(vo), equal_nan=True)
     monkeypatch.setenv("GPIMHIP_NO_FUSED_PREDICT", "1")
+    if chunk:
+        monkeypatch.setenv("GPIMHIP_PREDICT_CHUNK", chunk)
     mean_s, var_s = predict(eng, X, y, spec, u, Xs)
     assert_allclose(mean, mean_s, rtol=0, atol=1e-12 * scale, equal_nan=True)
     assert_allclose(var, var_s, rtol=1e-11, atol=1e-12 * np.nanmax(vo), equal_nan=True)

@@ -145,8 +145,19 @@ def test_graph_replay_equals_eager_launches(monkeypatch):
 
 
 def test_predict_matches_oracle_with_nan_rows():
+    check_predict_with_nan_rows(400)
+
+
+@pytest.mark.parametrize("N", [400, 200])
+def test_predict_in_chunks_matches_oracle_with_nan_rows(monkeypatch, N):
+    """GPIMHIP_PREDICT_CHUNK=128: the 333 test rows in three chunks with a ragged last one; four and two block rows."""
+    monkeypatch.setenv("GPIMHIP_PREDICT_CHUNK", "128")
+    check_predict_with_nan_rows(N)
+
+
+def check_predict_with_nan_rows(N):
     Q, d = 4, 2
-    X, y = S.random_data(400, d, seed=9)
+    X, y = S.random_data(N, d, seed=9)
     Z, _ = S.random_data(333, d, seed=10)
     Z[[0, 17, 200]] = np.nan
     rec = make(X, y, Q, False)

@@ -141,8 +141,20 @@ def test_thirty_iterations_match_oracle_trajectory(shape, isotropic, missing):
 # ------------------------------------------------------------------ 5. prediction
 @pytest.mark.parametrize("missing", [0, 13])
 def test_predict_matches_oracle(missing):
+    check_predict(missing, (16, 15))
+
+
+@pytest.mark.parametrize("missing", [0, 13])
+def test_predict_in_chunks_matches_oracle(monkeypatch, missing):
+    """GPIMHIP_PREDICT_CHUNK=128 on a 16 x 16 grid reflected in both axes (64-point blocks, B = 4): on the training grid the
+    variance is wanted for the first 64 points, so chunk 1 has nvar < cnt and chunk 2 nvar == 0 (with a border: all of it)."""
+    monkeypatch.setenv("GPIMHIP_PREDICT_CHUNK", "128")
+    check_predict(missing, (16, 16))
+
+
+def check_predict(missing, shape):
     import gpim_amd
-    Q, shape = 3, (16, 15)
+    Q = 3
     X, y = image(shape, seed=9, missing=missing)
     rec = make(X, y, Q)
     assert rec.solver == ("border" if missing else "reflection")

@@ -11,7 +11,7 @@ import torch
 import vgp_oracle as V
 from problems import spiral_image
 from test_gpu_vgp import eels_twin, scattered
-from test_gpu_vgp_refl import grid_stack
+from test_gpu_vgp_refl import chunked_predict, grid_stack
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +135,17 @@ def test_training_history_against_dense_engine(independent):
 @pytest.mark.parametrize("kernel,shape,independent,missing", [("Matern52", (24, 19), False, 0.10), ("RBF", (17, 20), True, 0.05),
                                                               ("Matern52", (12, 10, 9), True, 0.10)])
 def test_prediction_against_dense_engine(kernel, shape, independent, missing):
+    check_prediction(kernel, shape, independent, missing, lambda rec, X: rec.predict(X))
+
+
+@pytest.mark.parametrize("kernel,shape,independent,missing", [("Matern52", (24, 19), False, 0.10), ("RBF", (17, 20), True, 0.05)])
+def test_prediction_in_chunks_against_dense_engine(monkeypatch, kernel, shape, independent, missing):
+    """The bordered blocks' prediction in chunks of 128 test columns (the border's R = sum_b Y_b^T K*_b per chunk): the
+    training grids of 456 and 340 points take four and three chunks with a ragged last one."""
+    check_prediction(kernel, shape, independent, missing, chunked_predict(monkeypatch))
+
+
+def check_prediction(kernel, shape, independent, missing, predict):
     import gpim_amd
     T = 4
     X, Y = grid_stack(shape, T, seed=21)
@@ -144,7 +155,7 @@ def test_prediction_against_dense_engine(kernel, shape, independent, missing):
     rb._u.copy_(torch.as_tensor(u))
     rd._u.copy_(torch.as_tensor(u))
     scale = np.abs(Y).max()
-    m1, s1 = rb.predict(X)                               # the training grid, missing pixels included
+    m1, s1 = predict(rb, X)                              # the training grid, missing pixels included
     m0, s0 = rd.predict(X)
     assert m1.shape == s1.shape == X.shape[1:] + (T,)
     print("vgp border predict grid: mean %.2e sd %.2e" % (np.abs(m1 - m0).max() / scale, np.abs(s1 - s0).max() / scale))
@@ -152,7 +163,7 @@ def test_prediction_against_dense_engine(kernel, shape, independent, missing):
     sd_miss = s1.reshape(-1, T)[miss]
     assert np.isfinite(sd_miss).all() and (sd_miss > 0).all()
     Xd = gpim_amd.utils.get_full_grid(Y[..., 0], dense_x=0.5)
-    m1, s1 = rb.predict(Xd)
+    m1, s1 = predict(rb, Xd)
     m0, s0 = rd.predict(Xd)
     assert m1.shape == s1.shape == Xd.shape[1:] + (T,)
     assert np.abs(m1 - m0).max() <= 1e-9 * scale and np.abs(s1 - s0).max() <= 1e-9 * scale
@@ -160,7 +171,7 @@ def test_prediction_against_dense_engine(kernel, shape, independent, missing):
     Xs = rng.uniform(-1.5, max(shape) + 1.5, size=(len(shape), 37))
     Xs[:, 5] = np.nan
     Xs[1, 20] = np.nan
-    m1, s1 = rb.predict(Xs)
+    m1, s1 = predict(rb, Xs)
     m0, s0 = rd.predict(Xs)
     nan = np.isnan(Xs).any(0)
     assert np.isnan(m1[nan]).all() and np.isnan(s1[nan]).all()

@@ -109,6 +109,28 @@ def test_training_history_against_dense_engine(independent):
 @pytest.mark.parametrize("kernel,shape,independent", [("Matern52", (12, 9), False), ("RBF", (7, 10), True),
                                                       ("Matern52", (6, 5, 4), True)])
 def test_prediction_against_dense_engine(kernel, shape, independent):
+    check_prediction(kernel, shape, independent, lambda rec, X: rec.predict(X))
+
+
+def chunked_predict(monkeypatch):
+    """predict() of the model under test with GPIMHIP_PREDICT_CHUNK=128 (the dense reference of the same test runs without)."""
+    def predict(rec, X):
+        monkeypatch.setenv("GPIMHIP_PREDICT_CHUNK", "128")
+        try:
+            return rec.predict(X)
+        finally:
+            monkeypatch.delenv("GPIMHIP_PREDICT_CHUNK")
+    return predict
+
+
+@pytest.mark.parametrize("kernel,shape,independent", [("Matern52", (12, 9), False), ("RBF", (16, 16), True)])
+def test_prediction_in_chunks_against_dense_engine(monkeypatch, kernel, shape, independent):
+    """The blocks' prediction in chunks of 128 test columns: the x2 grids of 391 and 961 points take four and eight chunks
+    with a ragged last one."""
+    check_prediction(kernel, shape, independent, chunked_predict(monkeypatch))
+
+
+def check_prediction(kernel, shape, independent, predict):
     import gpim_amd
     T = 4
     X, Y = grid_stack(shape, T, seed=21)
@@ -118,7 +140,7 @@ def test_prediction_against_dense_engine(kernel, shape, independent):
     rd._u.copy_(torch.as_tensor(u))
     scale = np.abs(Y).max()
     Xd = gpim_amd.utils.get_full_grid(Y[..., 0], dense_x=0.5)
-    m1, s1 = rr.predict(Xd)
+    m1, s1 = predict(rr, Xd)
     m0, s0 = rd.predict(Xd)
     assert m1.shape == s1.shape == Xd.shape[1:] + (T,)
     assert np.abs(m1 - m0).max() <= 1e-9 * scale and np.abs(s1 - s0).max() <= 1e-9 * scale
@@ -126,7 +148,7 @@ def test_prediction_against_dense_engine(kernel, shape, independent):
     Xs = rng.uniform(-1.5, max(shape) + 1.5, size=(len(shape), 37))
     Xs[:, 5] = np.nan
     Xs[1, 20] = np.nan
-    m1, s1 = rr.predict(Xs)
+    m1, s1 = predict(rr, Xs)
     m0, s0 = rd.predict(Xs)
     nan = np.isnan(Xs).any(0)
     assert np.isnan(m1[nan]).all() and np.isnan(s1[nan]).all()

@@ -5,8 +5,8 @@
 For refactors of the draw and prediction drivers that must not change a bit: run it on the commit before and on the commit
 after, on the same machine, and diff the two printouts by hand.  It compares nothing and stores nothing.  The models are
 not trained (the hyper-parameters are the seeded initial ones); every draw takes S = 9 samples, two draw groups (8 + 1).
-The cases, each for a branch of csrc/draws.hip, the prediction of the dense-by-Kronecker blocks in csrc/api.hip or the
-workspaces of csrc/kron.hip:
+The cases, each for a branch of csrc/draws.hip, the prediction loops of csrc/api.hip, the spectral-mixture and multi-output
+drivers or the workspaces of csrc/kron.hip:
   joint      N = 300, M = 340 (the training rows end in block row 3 of 5) with an explicit z; N = 40, M = 20 (one block)
   pathwise   48 x 48 grid, both axes reflected (576-point blocks: two panels), 600 observed pixels; with noise and noiseless
   blocks     the same grid, fully observed;  border: the same grid with 5 missing pixels
@@ -15,6 +15,10 @@ workspaces of csrc/kron.hip:
   columns    a (48, 6, 5) cube, 37 of the 48 rows along the first axis observed, drawn and predicted at 11 new rows times the
              training axes (the union axes are the training axes), and with new coordinates on one complete axis
   kron       a fully observed 12 x 10 grid
+  sm, vgp    Q = 2 mixtures / T = 2 outputs on a 16 x 16 grid in three regimes each (dense: 200 observed pixels for sm, the
+             dense solver for vgp; blocks: the complete grid; border: 3 missing pixels): predict, nll_grad, ten Adam
+             iterations; gpimhip_sm_kmat on a dense handle and in reflection mode; two predictions at M = 961 and the two
+             stationary dense ones through the slab path (GPIMHIP_NO_FUSED_PREDICT)
 """
 import hashlib
 import os
@@ -124,6 +128,71 @@ def cases():
     rk = gpim_amd.reconstructor(Xk, fk, Xk, kernel="RBF", structured=True, **kw)
     yield "kron sample 12x10", lambda: (rk.sample(S, seed=7, method="kron"),)
     yield "kron predict 12x10", lambda: rk.predict(verbose=0)
+    # ---- prediction and training of the spectral-mixture and the multi-output drivers, three regimes each
+    R3, X3 = f16.copy(), X16.astype(np.float64)
+    for hole in ((3, 4), (9, 2), (15, 15)):
+        R3[hole] = np.nan
+        X3[(slice(None),) + hole] = np.nan
+    fine = gpim_amd.utils.get_full_grid(f16, dense_x=0.5)
+    Z = np.random.default_rng(8).uniform(-1.0, 17.0, size=(70, 2))
+    for regime, X, y, solver in (("dense", Xs16, R16, "dense"), ("blocks", X16, f16, None), ("border", X3, R3, None)):
+        rec = gpim_amd.skreconstructor(X, y, X16, kernel="Spectral", n_mixtures=2, learning_rate=0.05, iterations=10, verbose=0,
+                                       solver=solver)
+        if regime != "border":
+            yield "sm %s kmat, symmetric and cross" % regime, lambda rec=rec: (sm_kmat(rec, None), sm_kmat(rec, Z))
+        yield from model_cases("sm %s Q=2 16x16 (%s)" % (regime, rec.solver), rec, ("weights", "means", "scales", "noise"),
+                               fine if regime != "blocks" else None)
+    Y3 = Y.copy()
+    Y3[np.isnan(R3)] = np.nan
+    for regime, X, y, solver in (("dense", X16.astype(np.float64), Y, "dense"), ("blocks", X16.astype(np.float64), Y, "reflection"),
+                                 ("border", X3, Y3, "border")):
+        rec = gpim_amd.vreconstructor(X, y, X16, kernel="Matern52", solver=solver, learning_rate=0.05, iterations=10, **kw)
+        if regime == "dense":
+            yield "vgp dense T=2 16x16 predict, slab path", lambda rec=rec: slab_predict(rec)
+        yield from model_cases("vgp %s T=2 16x16 (%s)" % (regime, rec.solver), rec, ("lengthscale",),
+                               fine if regime == "blocks" else None)
+    yield "predict N=300 M=340, slab path", lambda: slab_predict(r)
+
+
+def slab_predict(rec):
+    """predict() through the chunk loop at a size where the stationary dense model would take the fused launch"""
+    os.environ["GPIMHIP_NO_FUSED_PREDICT"] = "1"
+    try:
+        return rec.predict(verbose=0)
+    finally:
+        del os.environ["GPIMHIP_NO_FUSED_PREDICT"]
+
+
+def model_cases(name, rec, hyper, fine):
+    """predict (at the stored test grid and, where given, at the M = 961 points of `fine`: several column tiles in the default
+    chunk), loss and gradient, then ten Adam iterations (graph replay): losses, history and final raw parameters"""
+    yield name + " predict", lambda: rec.predict(verbose=0)
+    if fine is not None:
+        yield name + " predict M=961", lambda: rec.predict(fine, verbose=0)
+    yield name + " nll_grad", lambda: rec.nll_grad()
+
+    def train():
+        rec.train()
+        return [np.array(rec.loss_all), rec._u.cpu().numpy()] + [np.array(rec.hyperparams[k], dtype=np.float64) for k in hyper]
+    yield name + " train T=10", train
+
+
+def sm_kmat(rec, Z):
+    """gpimhip_sm_kmat at the model's raw parameters: K(X, X) (Z None) or K(X, Z); in reflection mode the stacked blocks"""
+    import contextlib
+    import ctypes
+    import torch
+    from gpim_amd import _lib
+    blocks = rec.solver != "dense"
+    with (rec._solver._mode(rec) if blocks else contextlib.nullcontext()) as D:
+        X = D.Xq if blocks else rec._Xd
+        N, B = X.shape[0], D.B if blocks else 1
+        M = N if Z is None else Z.shape[0]
+        Zd = None if Z is None else torch.as_tensor(Z, dtype=torch.float64, device=rec._dev).contiguous()
+        out = torch.zeros((B * N, M), dtype=torch.float64, device=rec._dev)
+        _lib.check(rec._handle.lib.gpimhip_sm_kmat(rec._handle.h, ctypes.byref(rec._sstruct), _lib.ptr(X), N,
+                                                   None if Zd is None else _lib.ptr(Zd), M, _lib.ptr(rec._u), _lib.ptr(out), M))
+        return out.cpu().numpy()
 
 
 def main():
