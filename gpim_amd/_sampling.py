@@ -341,7 +341,7 @@ class Columns:
     def plan(self, g, S, noiseless, z_on_device):
         Us, U, N, M = g["Us"], g["U"], g["N"], g["M"]
         W = Us * U + N + M
-        # z (as given and in the library's layout), the draws twice and the mean here; in the library (csrc/draws.hip:
+        # z (as given and in the library's layout), the draws twice and the mean here; in the library (csrc/pkrongp.hip:
         # gpimhip_sample_pkron) the prior factor, zeta and H, the mode products' and the blocks' buffers
         need = 8 * (S * ((1 if z_on_device else 2) * W + 2 * M) + 2 * M + _columns_library_doubles(S, *g["library"]))
         return (W, " for method='columns' ([zeta | z_e | z_n] = %d x %d union rows x union-axes points + %d observations + %d "

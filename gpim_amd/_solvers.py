@@ -402,7 +402,7 @@ class Columns(Dense):
 
     def sample_columns(self, o, taxes, z, noiseless, jitter, mean, out, geometry=None):
         """Joint posterior draws on the product grid of the axes ``taxes`` by Matheron's rule through the dense-by-Kronecker
-        blocks (csrc/api.hip: gpimhip_sample_pkron).  z: (S, U_s prod U_i + N + M) device tensor
+        blocks (csrc/pkrongp.hip: gpimhip_sample_pkron).  z: (S, U_s prod U_i + N + M) device tensor
         [zeta | z_e | z_n], z_e in the training points' row order and z_n in the test grid's own (C) order; mean (M) and out
         (S, M) come back in the test grid's order."""
         C = self.C

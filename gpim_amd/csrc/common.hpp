@@ -121,7 +121,7 @@ struct StepPlan {
                                         // j+1 of such a pair (no launch of its own), 0 = one column per launch
 };
 
-// Launch plans of the distributed (block-column-cyclic, 1 x P) factorisation for one rank (api.hip: gpimhip_dist_*)
+// Launch plans of the distributed (block-column-cyclic, 1 x P) factorisation for one rank (distgp.hip: gpimhip_dist_*)
 struct DistPlan {
     int nb = 0, world = 0, rank = 0;
     TileDesc* d_tiles = nullptr;
@@ -219,7 +219,7 @@ struct gpimhip_ctx {
     void* kron = nullptr;
     // multi-output GP workspace, owned by vgpgp.hip (VgpWs); released by vgp_release()
     void* vgp = nullptr;
-    // dense-by-Kronecker blocks (a grid whose missing points are whole columns), owned by api.hip (PkronWs); pkron_release()
+    // dense-by-Kronecker blocks (a grid whose missing points are whole columns), owned by pkrongp.hip (PkronWs); pkron_release()
     void* pkron = nullptr;
     // spectral-mixture workspace, owned by smgp.hip (SmWs); released by sm_release()
     void* sm = nullptr;
@@ -325,6 +325,7 @@ int ws_ensure_b(gpimhip_ctx* h, int64_t N, int B, int padded, bool matrices = tr
 int ws_ensure_padded(gpimhip_ctx* h, int64_t N);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
 int deal_chunk(int ntiles = 1 << 30);
+void tri_tiles(std::vector<TileDesc>& tl, int nbr, int nc, bool lower);     // (with the tile-list builders of api.hip)
 int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
                      int B, const double* u);
 // z = L^-1 ypad and alpha = L^-T z from L^-1 in h->A; K(u) -> L^-1 in h->A, then the two (api.hip has the details)
@@ -383,9 +384,10 @@ static const FitLoop FIT_LOOP_DENSE = {true, true}, FIT_LOOP_PLAIN = {false, fal
 // hipGraph replayed T times where FitLoop allows, else launch by launch -- and returns finish_and_check().  During the
 // capture h->stream is the capture stream: the body must not synchronise, allocate or touch the legacy stream.
 int run_fit_iterations(gpimhip_ctx* h, int T, FitLoop loop, const std::function<int()>& iteration);
-// vfe.hip, kron.hip
+// vfe.hip, kron.hip, pkrongp.hip
 void vfe_release(gpimhip_ctx* h);
 void kron_release(gpimhip_ctx* h);
+void pkron_release(gpimhip_ctx* h);
 // cholstep.hip, cholstep32.hip
 int launch_potrf_steps(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info, double* Tm = nullptr, int rag = 0);
 int launch_potrf_steps_f32(gpimhip_ctx* h, double* A, int64_t np, int64_t ld, int32_t* info);
@@ -395,6 +397,8 @@ int step_plan_ensure_inv(gpimhip_ctx* h, int nb);
 int step_plan_ensure_pair(gpimhip_ctx* h, int nb);      // (nothing to do where the paired schedule does not apply)
 int launch_panel_chain(gpimhip_ctx* h, double* A, int64_t ld, int p0, int p1, int nb, const TileDesc* tiles,
                        const PlanRange* colfill, int32_t* info);
+// distgp.hip
+void dist_plan_release(gpimhip_ctx* h);
 // distops.hip
 int launch_dist_pack(gpimhip_ctx* h, const double* P, int64_t ldp, int64_t r0, int64_t np, int w, const double* dinv,
                      int nblk, double* buf, int64_t ldb);

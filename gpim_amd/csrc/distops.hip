@@ -1,4 +1,4 @@
-// distops.hip -- small device kernels of the distributed (block-column-cyclic) exact GP (api.hip: gpimhip_dist_*).
+// distops.hip -- small device kernels of the distributed (block-column-cyclic) exact GP (distgp.hip: gpimhip_dist_*).
 #include "common.hpp"
 
 // Broadcast buffer of one factored panel: rows [r0, np) x w columns of L, and -- in the 128 rows after np -- the

@@ -1,13 +1,13 @@
 // draws.hip -- host side of the posterior draws: the workspace, the kernel families and the drivers of the draw methods, and
-// the extern "C" entries gpimhip_sample_* (gpimhip_sample_kron: kron.hip).  Host code only: the kernels are in sample.hip,
-// sm.hip, vgp.hip, pkron.hip and kron.hip; the engine's drivers (workspaces, factorisations, tile engine) in api.hip.
+// the extern "C" entries gpimhip_sample_* (gpimhip_sample_kron: kron.hip, gpimhip_sample_pkron: pkrongp.hip).  Host code only:
+// the kernels are in sample.hip, sm.hip and vgp.hip; the engine's drivers (workspaces, factorisations, tile engine) in api.hip.
 #include <math.h>
 #include <stdio.h>
 #include <algorithm>
 #include "common.hpp"
 #include "border.hpp"
 #include "vgp.hpp"
-#include "pkron.hpp"
+#include "kron.hpp"
 #include "sm.hpp"
 #include "sample.hpp"
 
@@ -38,9 +38,8 @@ struct SampleWs {
     DevBuf<double> vz;
     DevBuf<double> vH;
     DevBuf<double> vmom;
-    // draws of the dense-by-Kronecker blocks (gpimhip_sample_pkron): one arena carved per call (the
-    // prior factor, zeta and H, the mode products' buffers, the blocks' right-hand sides, the stacked solutions, root rows,
-    // index maps, tile lists) and the union of the complete axes when the training axes do not serve; `sub` factors L_P
+    // draws of the dense-by-Kronecker blocks (pkrongp.hip: gpimhip_sample_pkron, through sample_pkron_ws): one arena carved
+    // per call and the union of the complete axes when the training axes do not serve; `sub` factors L_P
     DevBuf<double> ck;
     KronAxes ck_un;
     // draws of the spectral-mixture model (sm_family): the two parameter sets of launch_sm_params, the
@@ -55,6 +54,10 @@ struct SampleWs {
 static SampleWs* sws(gpimhip_ctx* h) {
     if (!h->sample) h->sample = new SampleWs();
     return (SampleWs*)h->sample;
+}
+PkronDrawWs sample_pkron_ws(gpimhip_ctx* h) {
+    SampleWs* w = sws(h);
+    return PkronDrawWs{w->sub, w->ck, w->ck_un};
 }
 int64_t sample_bytes(const gpimhip_ctx* h) {
     const SampleWs* w = (const SampleWs*)h->sample;
@@ -205,9 +208,8 @@ static int sample_forward(gpimhip_ctx* sub, const double* L, int64_t ld, const d
     return forward_panels(sub, L, ld, (int)((N + NB - 1) / NB), sub->ypad, sub->z, t, piece);
 }
 
-// a factorisation context of the draws at the given matrix order: created on first use, on the model handle's stream, one
-// problem, no matrices (see SampleWs)
-static int draw_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order) {
+// (sample.hpp; see SampleWs)
+int draw_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order) {
     if (!*sub) GP_TRY(gpimhip_create(sub, h->device, h->stream));
     (*sub)->stream = h->stream;
     (*sub)->nbatch = 1;
@@ -831,265 +833,6 @@ int gpimhip_sample_pathwise(gpimhip_handle h, const gpimhip_model_t* m, const do
     GP_TRY(draw_grid("gpimhip_sample_pathwise", m->dim, shape, mask, &gd, &M));
     return sample_pathwise_impl(h, stationary_family(m, u), gd, twoc, G, M, idx, y, N, Z, S, noiseless ? 1 : 0, jitter, mean_out,
                                 samples_out);
-}
-
-// ------------------------------------------------------------------------------------------
-// posterior draws of the dense-by-Kronecker blocks: Matheron's rule with the prior drawn through
-// L_P = chol(s2 K_s(P, P) + d I) of the union P of the ragged training and test rows and the root rows of the union of the
-// complete axes (section 21), the update through the blocks' L_j^-1 for all draws of a group at once on the tile engine.
-// Stage timers: 6 the blocks as a whole (theta, eigen-decomposition, factorisation, the mean's beta; inside it the engine's
-// own intervals 0 / 1 of the blocks' factorisation and inverse), 4 the prior factor (covariance build, factorisation -- its
-// context records no intervals of its own), 2 the prior draws (the union axes' decomposition and root rows, zeta,
-// H = L_P zeta, gathers, mode products), 3 the update (cross factors, residual, projection, the blocks' solves, K*_s
-// products and mode products, the mean's among them), 5 the epilogue.
-// ------------------------------------------------------------------------------------------
-// doubles of the buffers that grow with the draws of one group (0.25 GiB): a call of more draws takes them group by group
-#define PKS_GROUP_BUDGET ((int64_t)1 << 25)
-static int pks_bad(const std::string& what) {
-    gpim_set_error("gpimhip_sample_pkron: " + what);
-    return GPIMHIP_E_BADARG;
-}
-// the nbr x nc tiles of a product with a triangular factor of nbr block rows, longest k-ranges first.  lower: the k-range
-// stops at the diagonal block, [0, ci], rows descending; else it starts there, [ci, nbr), rows ascending
-static void tri_tiles(std::vector<TileDesc>& tl, int nbr, int nc, bool lower) {
-    for (int r = 0; r < nbr; ++r) {
-        const int ci = lower ? nbr - 1 - r : r;
-        for (int cj = 0; cj < nc; ++cj) tl.push_back(lower ? TileDesc{ci, cj, 0, ci + 1} : TileDesc{ci, cj, ci, nbr});
-    }
-}
-
-int gpimhip_sample_pkron(gpimhip_handle h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
-                         const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, const double* u,
-                         const double* Xs_test, int64_t Ms, const int32_t* n_test_c, const double* axes_test_c,
-                         const double* P, int64_t Us, const int32_t* irow_train, const int32_t* irow_test,
-                         const int32_t* n_union, const double* axes_union, const int32_t* idx_train, const int32_t* idx_test,
-                         const double* Z, int32_t S, int32_t noiseless, double jitter, double* mean_out, double* samples_out) {
-    if (!h || !m || !Xs || !n_c || !axes_c || !Y || !u || !Xs_test || !n_test_c || !axes_test_c || !P || !irow_train ||
-        !irow_test || !n_union || !axes_union || !idx_train || !idx_test || !Z || !mean_out || !samples_out)
-        return pks_bad("a null argument (every pointer but perm is required)");
-    if (S < 1) return pks_bad("needs S >= 1");
-    if (!(jitter > 0.0) || !(jitter < HUGE_VAL))
-        return pks_bad("needs a finite jitter > 0 (the prior factor of the ragged rows is chol(s2 K_s(P, P) + jitter I))");
-    PkronMap mp;
-    GP_TRY(pkron_check(h, m, Xs, Ns, p, dc, n_c, perm, axes_c, Y, &mp));
-    if (Ms < 1 || Us < 1 || Us > Ns + Ms) return pks_bad("needs Ms >= 1 and 1 <= Us <= Ns + Ms union rows");
-    // the union axes and the index maps (host arrays), as gpimhip_sample_kron checks them; shared: the union axes ARE the
-    // training axes and the training decomposition serves
-    bool shared = true;
-    int64_t sum_n = 0, sum_m = 0, sum_u = 0, sum_nu = 0, sum_mu = 0, U = 1, maxX = 1, maxT = 1;
-    {
-        for (int i = 0, oc = 0, ot = 0; i < dc; ++i) {
-            if (n_test_c[i] < 1) return pks_bad("every complete axis of the test grid needs at least one coordinate");
-            if (n_union[i] > 4096) {
-                char msg[200];
-                snprintf(msg, sizeof(msg), "the union of the training and the test coordinates of complete axis %d has %d entries; "
-                         "the eigen-solver takes at most 4096", i, (int)n_union[i]);
-                return pks_bad(msg);
-            }
-            if (n_union[i] < n_c[i] || (int64_t)n_union[i] > (int64_t)n_c[i] + n_test_c[i])
-                return pks_bad("n_union[i] must lie between n_c[i] and n_c[i] + n_test_c[i]");
-            for (int a = 0; a < n_c[i]; ++a) {
-                const int32_t v = idx_train[oc + a];
-                if (v < 0 || v >= n_union[i]) return pks_bad("idx_train outside its union axis");
-                shared = shared && v == a;
-            }
-            for (int a = 0; a < n_test_c[i]; ++a) {
-                const int32_t v = idx_test[ot + a];
-                if (v < 0 || v >= n_union[i]) return pks_bad("idx_test outside its union axis");
-            }
-            shared = shared && n_union[i] == n_c[i];
-            oc += n_c[i]; ot += n_test_c[i];
-            sum_n += n_c[i]; sum_m += n_test_c[i]; sum_u += n_union[i];
-            sum_nu += (int64_t)n_c[i] * n_union[i];
-            sum_mu += (int64_t)n_test_c[i] * n_union[i];
-            U *= n_union[i];
-        }
-        // the largest tensor (per ragged row) the two chains of root rows pass through: U -> J and U -> Mc
-        int64_t cx = U, ct = U;
-        maxX = maxT = U;
-        for (int i = 0; i < dc; ++i) {
-            cx = cx / n_union[i] * n_c[i];
-            ct = ct / n_union[i] * n_test_c[i];
-            maxX = std::max(maxX, cx);
-            maxT = std::max(maxT, ct);
-        }
-    }
-    for (int64_t a = 0; a < Ns; ++a)
-        if (irow_train[a] < 0 || irow_train[a] >= Us) return pks_bad("irow_train outside the union rows");
-    for (int64_t a = 0; a < Ms; ++a)
-        if (irow_test[a] < 0 || irow_test[a] >= Us) return pks_bad("irow_test outside the union rows");
-    PkronTest tg;
-    (void)pkron_test_grid(mp, n_test_c, &tg);           // (every axis has a coordinate: checked above)
-    const int64_t Mc = tg.Mc, sum_mn = tg.sum_mn, pmax = tg.pmax;
-
-    PkronWs* w = nullptr;
-    GP_TRY(pkron_begin(h, mp, n_c, axes_c, Ns, &w));
-    const int64_t np = h->np;
-    const int J = mp.J, nb = (int)(np / NB);
-    const int64_t Jp = pad_to(J, NB), NJ = Ns * J, M = Ms * Mc, zw = Us * U + NJ + M;
-    const KronDev& dv = w->ax.dev;
-    const gpimhip_model_t ms = pkron_submodel(m, p);
-    const int rag = rag_of(Ns, np);
-    // the chunks of ragged test rows and the mean's buffers are gpimhip_predict_pkron's
-    const int64_t mc = pkron_chunk(Ms, J, nb);
-    {
-        BatchScope one(h, 1);
-        GP_TRY(ws_ensure_predict(h, np, mc));
-    }
-    const int64_t kld = h->ks_cols + 16;
-    GP_TRY(w->G.grow(h, Jp * mc));
-    GP_TRY(w->pp.grow(h, 4 * pmax * mc));
-    GP_TRY(w->cross.grow(h, 2 * sum_mn));
-    SampleWs* sw = sws(h);
-    GP_TRY(draw_sub(h, &sw->sub, Us));
-    gpimhip_ctx* sub = sw->sub;
-    const int64_t npU = sub->np, ldU = sub->ld;
-    const int nbU = (int)(npU / NB);
-    if (!shared) {
-        GP_TRY(kron_axes_ensure(h, sw->ck_un, dc, n_union, false));
-        HIP_TRY(hipMemcpyAsync(const_cast<double*>(sw->ck_un.dev.coords), axes_union, (size_t)sum_u * sizeof(double),
-                               hipMemcpyDeviceToDevice, h->stream));
-        GP_TRY(kron_plan_problems(h, sw->ck_un));
-        GP_TRY(kron_cold_start(h, sw->ck_un.dev));
-    }
-    const KronDev& du = shared ? dv : sw->ck_un.dev;
-    // draw groups: the buffers below that grow with the draws stay within PKS_GROUP_BUDGET; every draw's arithmetic is its
-    // own (one thread per element in the new kernels, one k-loop per element in the tile engine and the mode products), so
-    // the grouping does not reach the result
-    const int64_t big = std::max(Ns * maxX, Ms * maxT);
-    const int64_t per_draw = 2 * npU * U + 3 * big + 2 * pmax * mc + (int64_t)J * (3 * np + mc);
-    const int Sg_max = (int)std::max<int64_t>(1, std::min<int64_t>(S, PKS_GROUP_BUDGET / per_draw));
-    const int ngroups = (S + Sg_max - 1) / Sg_max, Sg0 = (S + ngroups - 1) / ngroups;
-    const int64_t cols = pad_to(Sg0 * U, NB), Sp = pad_to(Sg0, NB), rowsP = pad_to((int64_t)Sg0 * J, NB);
-    const int nct = (int)(cols / NB), nst = (int)(Sp / NB);
-    if ((int64_t)nbU * nct > (1 << 28) || (int64_t)nb * nst > (1 << 28)) return pks_bad("too many tiles in one launch");
-    // tile lists, longest k-ranges first: H = L_P zeta and T = L_j^-1 R stop at the diagonal block, beta = L_j^-T T starts there
-    std::vector<TileDesc> tl;
-    tl.reserve((size_t)nbU * nct + 2 * (size_t)nb * nst);
-    tri_tiles(tl, nbU, nct, true);
-    tri_tiles(tl, nb, nst, true);
-    tri_tiles(tl, nb, nst, false);
-    const int n_prior = nbU * nct, n_solve = nb * nst;
-    const int64_t th_d = (int64_t)((sizeof(ThetaDev) + 15) / 16 * 2);
-    const int64_t total = th_d + npU * ldU + 2 * npU * cols + 3 * Sg0 * big + 2 * J * np * Sp + rowsP * np + rowsP * mc +
-                          2 * Sg0 * pmax * mc + sum_nu + sum_mu + (Ns + Ms + sum_n + sum_m) / 2 + 2 * (int64_t)tl.size() + 64;
-    GP_TRY(sw->ck.grow(h, total));
-    Carve a(sw->ck);
-    ThetaDev* thp = a.take<ThetaDev>(th_d);
-    double* LP = a.take(npU * ldU);
-    double *Zg = a.take(npU * cols), *Hm = a.take(npU * cols);
-    double *g0 = a.take(Sg0 * big), *g1 = a.take(Sg0 * big), *g2 = a.take(Sg0 * big);
-    double *R0 = a.take((int64_t)J * np * Sp), *R1 = a.take((int64_t)J * np * Sp);
-    double *Bst = a.take(rowsP * np), *Gs = a.take(rowsP * mc);
-    double *pa = a.take(Sg0 * pmax * mc), *pb = a.take(Sg0 * pmax * mc);
-    double *RX = a.take(sum_nu), *RT = a.take(sum_mu);
-    int32_t* iX = a.take<int32_t>((Ns + 1) / 2);
-    int32_t* iT = a.take<int32_t>((Ms + 1) / 2);
-    int32_t* ic = a.take<int32_t>((sum_n + 1) / 2);
-    int32_t* it = a.take<int32_t>((sum_m + 1) / 2);
-    TileDesc* tiles = a.take<TileDesc>(2 * (int64_t)tl.size());
-    HIP_TRY(hipMemcpyAsync(iX, irow_train, (size_t)Ns * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(iT, irow_test, (size_t)Ms * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(ic, idx_train, (size_t)sum_n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(it, idx_test, (size_t)sum_m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(tiles, tl.data(), tl.size() * sizeof(TileDesc), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // the host arrays are the caller's
-    const TileDesc *t_prior = tiles, *t_nn = tiles + n_prior, *t_tn = t_nn + n_solve;
-
-    {   // the blocks: theta, the complete axes, L_j^-1, and the mean's beta as gpimhip_predict_pkron computes it
-        StageTimer t(h, 6);
-        GP_TRY(pkron_factor(h, m, &ms, mp, w, Xs, Y, Ns, u, false));
-        GP_TRY(launch_pkron_beta(h, Ns, J, w->Bp));
-    }
-    const double* bmat[KMAXD];
-    { StageTimer t(h, 3); GP_TRY(pkron_cross_factors(h, w, mp, n_test_c, axes_test_c, sum_mn, bmat)); }
-    const double *rxm[KMAXD], *rtm[KMAXD], *qtm[KMAXD];
-    int ldu[KMAXD], ldn[KMAXD];
-    {   // the union of the complete axes and the rows of its root at the training and at the test coordinates
-        StageTimer t(h, 2);
-        if (!shared) GP_TRY(kron_eig_axes(h, sw->ck_un, w->th3 + PK_TH_AXES));
-        int64_t xo = 0, to = 0;
-        for (int i = 0, oc = 0, ot = 0; i < dc; ++i) {
-            GP_TRY(kron_root_rows(h, du, i, ic + oc, n_c[i], RX + xo));
-            GP_TRY(kron_root_rows(h, du, i, it + ot, n_test_c[i], RT + to));
-            rxm[i] = RX + xo; rtm[i] = RT + to; qtm[i] = dv.Qt + dv.moff[i];
-            ldu[i] = n_union[i]; ldn[i] = n_c[i];
-            xo += (int64_t)n_c[i] * n_union[i]; to += (int64_t)n_test_c[i] * n_union[i];
-            oc += n_c[i]; ot += n_test_c[i];
-        }
-    }
-    {   // L_P = chol(s2 K_s(P, P) + d I); its status goes into the word of the call (NOT_PD at the closing check)
-        StageTimer t(h, 4);
-        GP_TRY(launch_pkron_prior_theta(h, w->th3, thp));
-        GP_TRY(launch_kmat(sub, &ms, P, Us, nullptr, Us, thp, jitter, 0, LP, ldU, npU, npU, 1, 1, 0, 0, 0));
-        GP_TRY(launch_potrf(sub, LP, npU, ldU, h->info));
-        // the factorisation leaves the strict upper triangle of the diagonal blocks as the covariance build wrote it
-        GP_TRY(launch_pkron_tril(h, LP, ldU, nbU));
-    }
-    const double* ze = Z + Us * U;
-    const double* zn = ze + NJ;
-    for (int s0 = 0; s0 < S; s0 += Sg0) {
-        const int Sg = std::min(Sg0, S - s0);
-        double *gX, *res, *gs;
-        {   // H = L_P zeta for the Sg U columns of the group, then g_X = H[i_X, :] x_i R_i[ic_i, :]
-            StageTimer t(h, 2);
-            GP_TRY(launch_pkron_zeta(h, Z, zw, Us, U, s0, Sg, npU, cols, Zg));
-            GemmArgs g = gemm_args(LP, ldU, Zg, cols, Hm, cols, 1.0, 0.0, t_prior, n_prior, 0);
-            g.chunk = deal_chunk(g.ntiles);
-            GP_TRY(launch_gemm(sub, false, true, EPI_STORE, g));
-            GP_TRY(launch_pkron_gather(h, Hm, cols, iX, Ns, U, Sg, g0));
-            GP_TRY(tensor_apply(h, dc, n_union, mp.nc, rxm, ldu, 0, 0, g0, g1, g2, &gX, (int64_t)Sg * Ns));
-        }
-        {   // r = -g_X - sqrt(sigma) z_e, r~ = r x_i Q_i^T, beta_j = L_j^-T (L_j^-1 r~_j) for the J blocks and all draws
-            StageTimer t(h, 3);
-            GP_TRY(launch_pkron_resid(h, ze, zw, s0, NJ, Sg, w->th3, gX));
-            double* other = gX == g1 ? g2 : g1;
-            GP_TRY(tensor_apply(h, dc, mp.nc, mp.nc, qtm, ldn, 0, 0, gX, other, gX, &res, (int64_t)Sg * Ns));
-            GP_TRY(launch_pkron_scatter_multi(h, res, Ns, J, Sg, Sp, R0));
-            // (a ragged launch stores no row of the padding of the last block: GemmArgs::rag)
-            if (rag) HIP_TRY(hipMemsetAsync(R1, 0, (size_t)((int64_t)J * np * Sp) * sizeof(double), h->stream));
-            GemmArgs g = gemm_args(h->A, h->ld, R0, Sp, R1, Sp, 1.0, 0.0, t_nn, n_solve, np);
-            g.chunk = deal_chunk(g.ntiles);
-            g.rag = rag;
-            GP_TRY(launch_gemm(h, false, true, EPI_STORE, g));
-            if (rag) HIP_TRY(hipMemsetAsync(R0, 0, (size_t)((int64_t)J * np * Sp) * sizeof(double), h->stream));
-            g = gemm_args(h->A, h->ld, R1, Sp, R0, Sp, 1.0, 0.0, t_tn, n_solve, np);
-            g.chunk = deal_chunk(g.ntiles);
-            g.krev = 1;
-            g.rag = rag;
-            GP_TRY(launch_gemm(h, true, true, EPI_STORE, g));
-            GP_TRY(launch_pkron_beta_stack(h, R0, Ns, J, Sg, Sp, rowsP, Bst));
-        }
-        {   // g_* = H[i_*, :] x_i R_i[it_i, :]
-            StageTimer t(h, 2);
-            GP_TRY(launch_pkron_gather(h, Hm, cols, iT, Ms, U, Sg, g0));
-            GP_TRY(tensor_apply(h, dc, n_union, n_test_c, rtm, ldu, 0, 0, g0, g1, g2, &gs, (int64_t)Sg * Ms));
-        }
-        for (int64_t m0 = 0; m0 < Ms; m0 += mc) {
-            const int64_t cnt = std::min(mc, Ms - m0), cpad = pad_to(cnt, NB);
-            const double* upd;
-            {
-                StageTimer t(h, 3);
-                {
-                    BatchScope one(h, 1);
-                    GP_TRY(launch_kmat(h, &ms, Xs, Ns, Xs_test + m0 * p, cnt, w->th3 + PK_TH_UNIT, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, 0));
-                }
-                if (s0 == 0) {      // the mean: the launches of gpimhip_predict_pkron's
-                    GP_TRY(pkron_times_b(h, w, J, h->Ks, kld, cpad, w->G, mc));
-                    const double* mraw;
-                    GP_TRY(pkron_mode_chain(h, mp, n_test_c, bmat, w->G, w->pp, w->pp + pmax * mc, 1, mc, 0, &mraw));
-                    GP_TRY(launch_pkron_mean(h, w->th3, Mc, mc, m0, cnt, mraw, mean_out));
-                }
-                // G = B K*_s with the draws' solutions stacked as rows, then the mode products with b_i, batch Sg
-                GP_TRY(pkron_rows_times(h, Bst, rowsP, h->Ks, kld, cpad, Gs, mc));
-                GP_TRY(pkron_mode_chain(h, mp, n_test_c, bmat, Gs, pa, pb, Sg, mc, 0, &upd));
-            }
-            StageTimer t(h, 5);
-            GP_TRY(launch_pkron_draw(h, w->th3, Mc, mc, m0, cnt, Ms, s0, Sg, gs, upd, mean_out, zn, zw, noiseless ? 1 : 0,
-                                     samples_out));
-        }
-    }
-    return finish_and_check(h);
 }
 
 int gpimhip_sample_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,

@@ -1091,7 +1091,7 @@ int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan,
 
 
 // ------------------------------------------------------------------------------------------
-// distributed training (api.hip: gpimhip_dist_grad_sums / gpimhip_dist_finalize): the gradient contraction over the
+// distributed training (distgp.hip: gpimhip_dist_grad_sums / gpimhip_dist_finalize): the gradient contraction over the
 // tiles of K^-1 a rank holds, reduced to the seven sums S[] in a fixed order; after the all-reduce of S across
 // the ranks the same finalize_step as the single-GPU path turns them into loss, gradient and Adam step.
 // ------------------------------------------------------------------------------------------

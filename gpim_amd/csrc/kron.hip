@@ -26,6 +26,9 @@
 //   posterior draws on any product test grid (gpimhip_sample_kron), all S draws per launch:
 //   kron_root_rows_kernel rows of the prior root of a union axis;  kron_zeta_kernel zeta out of z;  kron_resid_kernel the
 //   residual;  kron_dscale_kernel the 1 / D scaling;  kron_draw_kernel the epilogue
+// Host drivers: the four entries gpimhip_*_kron and the diagnostic gpimhip_kron_eigh, and what the dense-by-Kronecker blocks
+// (pkrongp.hip) build on (kron.hpp): the per-axis drivers and the union-axis steps the two draws share (kron_axes_load,
+// kron_union_check, kron_union_roots).
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -57,7 +60,6 @@ struct KronWs {
     int64_t s_key[3 + 3 * KMAXD] = {0};      // S, d, buffer size, n_union, n, n_test the workspace was carved for
     double *RG = nullptr, *RT = nullptr, *Zc = nullptr, *sa = nullptr, *sb = nullptr;
     int32_t *ic = nullptr, *it = nullptr;
-    int64_t rgoff[KMAXD] = {0, 0, 0, 0}, rtoff[KMAXD] = {0, 0, 0, 0};
     // the axis set of the diagnostic gpimhip_kron_eigh (its own: the rotations it leaves in Vr are no fit's warm start)
     KronAxes dg;
     bool dg_ready = false;       // dg holds the rotations of a completed call (what warm = 1 continues from)
@@ -101,13 +103,13 @@ int kron_axes_ensure(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, bool 
     return GPIMHIP_OK;
 }
 
+// the handle's workspace with the N-sized vectors of a grid of the orders n[]
 static int kron_ensure(gpimhip_ctx* h, int d, const int32_t* n, KronWs** out) {
     if (!h->kron) h->kron = new KronWs();
     KronWs& w = *static_cast<KronWs*>(h->kron);
     *out = &w;
     bool same = w.d == d && w.arena;
     for (int i = 0; i < d && same; ++i) same = w.n[i] == n[i];
-    GP_TRY(kron_axes_ensure(h, w.tr, d, n, true));
     if (same) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
     w.arena.release(h);
@@ -761,6 +763,63 @@ int kron_root_rows(gpimhip_ctx* h, const KronDev& dv, int ax, const int32_t* idx
     return GPIMHIP_OK;
 }
 
+int kron_axes_load(gpimhip_ctx* h, KronAxes& a, int d, const int32_t* n, const double* coords_dev, bool grad) {
+    GP_TRY(kron_axes_ensure(h, a, d, n, grad));
+    HIP_TRY(hipMemcpyAsync(const_cast<double*>(a.dev.coords), coords_dev, (size_t)a.sum_n * sizeof(double), hipMemcpyDeviceToDevice,
+                           h->stream));
+    GP_TRY(kron_plan_problems(h, a));
+    return kron_cold_start(h, a.dev);
+}
+
+int kron_union_check(const char* entry, int d, const int32_t* n, const int32_t* n_test, const int32_t* n_union,
+                     const int32_t* idx_train, const int32_t* idx_test, KronUnion* out) {
+    auto bad = [&](const char* what) {
+        gpim_set_error(std::string(entry) + ": " + what);
+        return GPIMHIP_E_BADARG;
+    };
+    KronUnion un = {true, 0, 0, 0, 0, 0, 1};
+    for (int i = 0, oc = 0, ot = 0; i < d; ++i) {
+        if (n[i] < 1 || n_test[i] < 1) return bad("every axis of the training and of the test grid needs at least one coordinate");
+        if (n_union[i] > 4096) {
+            char msg[200];
+            snprintf(msg, sizeof(msg), "the union of the training and the test coordinates of axis %d has %d entries; the "
+                     "eigen-solver takes at most 4096", i, (int)n_union[i]);
+            return bad(msg);
+        }
+        if (n_union[i] < n[i] || (int64_t)n_union[i] > (int64_t)n[i] + n_test[i])
+            return bad("n_union[i] must lie between n[i] and n[i] + n_test[i]");
+        for (int a = 0; a < n[i]; ++a) {
+            const int32_t v = idx_train[oc + a];
+            if (v < 0 || v >= n_union[i]) return bad("idx_train outside its union axis");
+            un.shared = un.shared && v == a;
+        }
+        for (int a = 0; a < n_test[i]; ++a) {
+            const int32_t v = idx_test[ot + a];
+            if (v < 0 || v >= n_union[i]) return bad("idx_test outside its union axis");
+        }
+        un.shared = un.shared && n_union[i] == n[i];
+        oc += n[i]; ot += n_test[i];
+        un.sum_n += n[i]; un.sum_m += n_test[i]; un.sum_u += n_union[i];
+        un.sum_nu += (int64_t)n[i] * n_union[i];
+        un.sum_mu += (int64_t)n_test[i] * n_union[i];
+        un.U *= n_union[i];
+    }
+    *out = un;
+    return GPIMHIP_OK;
+}
+
+int kron_union_roots(gpimhip_ctx* h, const KronDev& du, int d, const int32_t* n, const int32_t* n_test, const int32_t* ic,
+                     const int32_t* it, double* RX, double* RT, const double** rx, const double** rt) {
+    for (int i = 0; i < d; ++i) {
+        GP_TRY(kron_root_rows(h, du, i, ic, n[i], RX));
+        GP_TRY(kron_root_rows(h, du, i, it, n_test[i], RT));
+        rx[i] = RX; rt[i] = RT;
+        RX += (int64_t)n[i] * du.n[i]; RT += (int64_t)n_test[i] * du.n[i];
+        ic += n[i]; it += n_test[i];
+    }
+    return GPIMHIP_OK;
+}
+
 void kron_axes_free(gpimhip_ctx* h, KronAxes& a) {
     a.arena.release(h);
     a.d = 0;
@@ -822,11 +881,8 @@ static int kron_prepare(gpimhip_ctx* h, const gpimhip_model_t* m, int32_t d, con
     h->nbatch = 1;
     GP_TRY(ws_ensure(h, 1));                   // theta, Adam state, iteration counter
     GP_TRY(kron_ensure(h, d, n, w));
-    HIP_TRY(hipMemcpyAsync(const_cast<double*>((*w)->tr.dev.coords), axes, (size_t)(*w)->tr.sum_n * sizeof(double),
-                           hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(kron_plan_problems(h, (*w)->tr));
-    return kron_cold_start(h, (*w)->tr.dev);
+    return kron_axes_load(h, (*w)->tr, d, n, axes, true);
 }
 
 // the prediction workspace for the test grid of the orders n_test[] and its coordinates
@@ -867,50 +923,48 @@ static int kron_cross_factors(gpimhip_ctx* h, KronWs& w) {
     const KronDev& dv = w.tr.dev;
     int toff = 0;
     for (int i = 0; i < w.d; ++i) {
-        const int64_t cnt = (int64_t)w.m[i] * w.n[i];
-        hipLaunchKernelGGL(kron_cross_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, dv, h->theta,
-                           w.tcoords, toff, w.m[i], i, w.Ks + w.koff[i]);
+        GP_TRY(kron_cross(h, dv, h->theta, w.tcoords, toff, w.m[i], i, w.Ks + w.koff[i]));
         GP_TRY(modeprod(h, w.Ks + w.koff[i], w.Bs + w.koff[i], dv.Qt + dv.moff[i], w.n[i], w.n[i], w.n[i], 0, 0, w.m[i], 1));
         toff += w.m[i];
     }
-    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// mean_out = ((x) B_i) alpha~, the posterior mean before its factor s2 (B_i = Ks_i Q_i maps eigen-coordinates straight to
+// test points); mats / ld: the B_i as tensor_apply takes them.  The mean of a prediction and of a draw
+static int kron_mean_raw(gpimhip_ctx* h, KronWs& w, const double** mats, int* ld, double* mean_out) {
+    for (int i = 0; i < w.d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
+    double* res;
+    GP_TRY(tensor_apply(h, w.d, w.n, w.m, mats, ld, 0, 0, w.at, w.p1, w.p2, &res));
+    HIP_TRY(hipMemcpyAsync(mean_out, res, (size_t)w.M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return GPIMHIP_OK;
 }
 
 // the workspace of gpimhip_sample_kron: the gathered root rows, the index maps, zeta of every draw and two buffers of
 // S * smax doubles for the mode products (smax: the largest tensor any of the four chains U -> n, n -> n, n -> m, U -> m
 // passes through)
-static int kron_sample_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* nu, int64_t S, int64_t* PU_out) {
+static int kron_sample_ws(gpimhip_ctx* h, KronWs& w, int d, const int32_t* nu, const KronUnion& un, int64_t S) {
     const int32_t* lo[2] = {w.n, w.m};
-    int64_t PU = 1, smax = std::max(w.N, w.M), sum_gu = 0, sum_tu = 0;
-    for (int i = 0; i < d; ++i) { PU *= nu[i]; sum_gu += (int64_t)w.n[i] * nu[i]; sum_tu += (int64_t)w.m[i] * nu[i]; }
+    int64_t smax = std::max(w.N, w.M);
     for (int c = 0; c < 2; ++c) {
-        int64_t cur = PU;
+        int64_t cur = un.U;
         for (int i = 0; i < d; ++i) { cur = cur / nu[i] * lo[c][i]; smax = std::max(smax, cur); }
     }
     {
         int64_t cur = w.N;
         for (int i = 0; i < d; ++i) { cur = cur / w.n[i] * w.m[i]; smax = std::max(smax, cur); }
     }
-    *PU_out = PU;
     int64_t key[3 + 3 * KMAXD] = {S, d, smax};
     for (int i = 0; i < d; ++i) { key[3 + i] = nu[i]; key[3 + KMAXD + i] = w.n[i]; key[3 + 2 * KMAXD + i] = w.m[i]; }
     if (w.sarena && memcmp(key, w.s_key, sizeof(key)) == 0) return GPIMHIP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
     w.sarena.release(h);
-    int64_t sum_n = 0, sum_m = 0;
-    for (int i = 0; i < d; ++i) { sum_n += w.n[i]; sum_m += w.m[i]; }
-    const int64_t count = sum_gu + sum_tu + (sum_n + sum_m + 4) / 2 + S * PU + 2 * S * smax + 32;
+    const int64_t count = un.sum_nu + un.sum_mu + (un.sum_n + un.sum_m + 4) / 2 + S * un.U + 2 * S * smax + 32;
     GP_TRY(w.sarena.alloc(h, count, "hipMalloc failed (structured-GP posterior-draw workspace)"));
     Carve c(w.sarena);
-    w.RG = c.take(sum_gu); w.RT = c.take(sum_tu);
-    w.ic = c.take<int32_t>((sum_n + 1) / 2); w.it = c.take<int32_t>((sum_m + 1) / 2);
-    w.Zc = c.take(S * PU); w.sa = c.take(S * smax); w.sb = c.take(S * smax);
-    int64_t go = 0, to = 0;
-    for (int i = 0; i < KMAXD; ++i) {
-        w.rgoff[i] = go; w.rtoff[i] = to;
-        if (i < d) { go += (int64_t)w.n[i] * nu[i]; to += (int64_t)w.m[i] * nu[i]; }
-    }
+    w.RG = c.take(un.sum_nu); w.RT = c.take(un.sum_mu);
+    w.ic = c.take<int32_t>((un.sum_n + 1) / 2); w.it = c.take<int32_t>((un.sum_m + 1) / 2);
+    w.Zc = c.take(S * un.U); w.sa = c.take(S * smax); w.sb = c.take(S * smax);
     memcpy(w.s_key, key, sizeof(key));
     return GPIMHIP_OK;
 }
@@ -952,12 +1006,10 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
     GP_TRY(kron_decompose(h, w, m, u, y));
     hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
     GP_TRY(kron_cross_factors(h, w));
-    // mean = s2 * ((x) B_i) alpha~        (B_i = Ks_i Q_i maps eigen-coordinates straight to test points)
+    // mean = s2 * ((x) B_i) alpha~
     const double* mats[KMAXD]; int ld[KMAXD];
-    for (int i = 0; i < d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
+    GP_TRY(kron_mean_raw(h, w, mats, ld, mean_out));
     double* res;
-    GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 0, w.at, w.p1, w.p2, &res));
-    HIP_TRY(hipMemcpyAsync(mean_out, res, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     // var = s2 - s2^2 * ((x) B_i o B_i) (1 / D)
     hipLaunchKernelGGL(kron_invd_kernel, dim3((unsigned)((w.N + 255) / 256)), dim3(256), 0, h->stream, dv, h->theta, w.t1);
     GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 1, w.t1, w.p1, w.p2, &res));
@@ -970,133 +1022,92 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
 // Joint posterior draws on the product test grid by Matheron's rule with every factor a Kronecker product (DESIGN.md
 // section 21).  Stage timers: 0 the union axes' eigen-decomposition, 1 the training axes' (with y~), 2 the prior's root
 // rows and mode products, 3 the update's factors and mode products (the mean's among them), 5 the epilogue.
+// One call: the workspace, the union axes (the training axes where they serve), the caller's z (rows of zw doubles: zeta of
+// PU entries | z_e | z_n) and where every union axis' root rows at the training / test coordinates start
+struct KronDraw {
+    KronWs& w; const KronAxes& ua;
+    const double* z; int64_t PU, zw, S;
+    const double *rg[KMAXD], *rt[KMAXD];
+};
+// the prior on the training grid: *gG = g_G / sqrt(s2) = ((x) R_i[ic_i, :]) zeta
+static int kron_draw_prior_train(gpimhip_ctx* h, KronDraw& D, double** gG) {
+    KronWs& w = D.w;
+    StageTimer t(h, 2);
+    GP_TRY(kron_union_roots(h, D.ua.dev, w.d, w.n, w.m, w.ic, w.it, w.RG, w.RT, D.rg, D.rt));
+    hipLaunchKernelGGL(kron_zeta_kernel, dim3((unsigned)((D.S * D.PU + 255) / 256)), dim3(256), 0, h->stream, D.z, D.zw, D.PU,
+                       D.S * D.PU, w.Zc);
+    HIP_TRY(hipGetLastError());
+    return tensor_apply(h, w.d, D.ua.n, w.n, D.rg, D.ua.n, 0, 0, w.Zc, w.sa, w.sb, gG, D.S);
+}
+// the update: out <- ((x) Ks_i Q_i) D^-1 ((x) Q_i^T) (y - sqrt(s2) g_G - sqrt(sigma) z_e), and the mean as predict computes it
+static int kron_draw_update(gpimhip_ctx* h, KronDraw& D, const double* y, double* gG, double* mean_out, double* out) {
+    KronWs& w = D.w;
+    const KronDev& dv = w.tr.dev;
+    const int64_t N = w.N, S = D.S;
+    const double* mats[KMAXD]; int ld[KMAXD];
+    double *res, *upd;
+    StageTimer t(h, 3);
+    GP_TRY(kron_cross_factors(h, w));
+    hipLaunchKernelGGL(kron_resid_kernel, dim3((unsigned)((S * N + 255) / 256)), dim3(256), 0, h->stream, y, D.z + D.PU, D.zw, N,
+                       S * N, h->theta, gG);
+    double* other = gG == w.sa ? w.sb : w.sa;
+    for (int i = 0; i < w.d; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = w.n[i]; }
+    GP_TRY(tensor_apply(h, w.d, w.n, w.n, mats, ld, 0, 0, gG, other, gG, &res, S));
+    hipLaunchKernelGGL(kron_dscale_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)std::min<int64_t>(S, 64)), dim3(256), 0,
+                       h->stream, dv, h->theta, S, res);
+    HIP_TRY(hipGetLastError());
+    other = res == w.sa ? w.sb : w.sa;
+    for (int i = 0; i < w.d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
+    GP_TRY(tensor_apply(h, w.d, w.n, w.m, mats, ld, 0, 0, res, other, res, &upd, S));
+    HIP_TRY(hipMemcpyAsync(out, upd, (size_t)(S * w.M) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return kron_mean_raw(h, w, mats, ld, mean_out);
+}
+// the prior on the test grid, from the same zeta
+static int kron_draw_prior_test(gpimhip_ctx* h, KronDraw& D, double** gs) {
+    KronWs& w = D.w;
+    StageTimer t(h, 2);
+    return tensor_apply(h, w.d, D.ua.n, w.m, D.rt, D.ua.n, 0, 0, w.Zc, w.sa, w.sb, gs, D.S);
+}
+
 int gpimhip_sample_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
                         const double* y, const double* u, const int32_t* n_test, const double* axes_test,
                         const int32_t* n_union, const double* axes_union, const int32_t* idx_train, const int32_t* idx_test,
                         const double* z, int32_t S, int32_t noiseless, double jitter, double* mean_out, double* out) {
+    auto bad = [](const char* what) { gpim_set_error(what); return (int)GPIMHIP_E_BADARG; };
     if (!h || !m || !y || !u || !n || !n_test || !axes_test || !n_union || !axes_union || !idx_train || !idx_test || !z ||
-        !mean_out || !out) {
-        gpim_set_error("gpimhip_sample_kron: a null argument (every pointer of the entry point is required)");
-        return GPIMHIP_E_BADARG;
-    }
-    if (S < 1 || !(jitter >= 0.0) || !(jitter < HUGE_VAL)) {
-        gpim_set_error("gpimhip_sample_kron: needs S >= 1 and a finite jitter >= 0");
-        return GPIMHIP_E_BADARG;
-    }
-    if (d < 1 || d > KMAXD) {
-        gpim_set_error("gpimhip_sample_kron: d must be between 1 and 4");
-        return GPIMHIP_E_BADARG;
-    }
-    // the union axes and the index maps (host arrays): every index inside its union axis, which is no longer than the two
-    // axes together and no shorter than either; shared: the union axes ARE the training axes (the test grid is the training
-    // grid or a crop of it), the training decomposition serves as the union one
-    bool shared = true;
-    int64_t sum_n = 0, sum_m = 0, sum_u = 0;
-    for (int i = 0, oc = 0, ot = 0; i < d; ++i) {
-        if (n[i] < 1 || n_test[i] < 1) {
-            gpim_set_error("gpimhip_sample_kron: every axis of the training and of the test grid needs at least one coordinate");
-            return GPIMHIP_E_BADARG;
-        }
-        if (n_union[i] > 4096) {
-            char msg[200];
-            snprintf(msg, sizeof(msg), "gpimhip_sample_kron: the union of the training and the test coordinates of axis %d has "
-                     "%d entries; the eigen-solver takes at most 4096", i, (int)n_union[i]);
-            gpim_set_error(msg);
-            return GPIMHIP_E_BADARG;
-        }
-        if (n_union[i] < n[i] || (int64_t)n_union[i] > (int64_t)n[i] + n_test[i]) {
-            gpim_set_error("gpimhip_sample_kron: n_union[i] must lie between n[i] and n[i] + n_test[i]");
-            return GPIMHIP_E_BADARG;
-        }
-        for (int a = 0; a < n[i]; ++a) {
-            const int32_t v = idx_train[oc + a];
-            if (v < 0 || v >= n_union[i]) { gpim_set_error("gpimhip_sample_kron: idx_train outside its union axis"); return GPIMHIP_E_BADARG; }
-            shared = shared && v == a;
-        }
-        for (int a = 0; a < n_test[i]; ++a) {
-            const int32_t v = idx_test[ot + a];
-            if (v < 0 || v >= n_union[i]) { gpim_set_error("gpimhip_sample_kron: idx_test outside its union axis"); return GPIMHIP_E_BADARG; }
-        }
-        shared = shared && n_union[i] == n[i];
-        oc += n[i]; ot += n_test[i];
-        sum_n += n[i]; sum_m += n_test[i]; sum_u += n_union[i];
-    }
+        !mean_out || !out)
+        return bad("gpimhip_sample_kron: a null argument (every pointer of the entry point is required)");
+    if (S < 1 || !(jitter >= 0.0) || !(jitter < HUGE_VAL)) return bad("gpimhip_sample_kron: needs S >= 1 and a finite jitter >= 0");
+    if (d < 1 || d > KMAXD) return bad("gpimhip_sample_kron: d must be between 1 and 4");
+    KronUnion un;
+    GP_TRY(kron_union_check("gpimhip_sample_kron", d, n, n_test, n_union, idx_train, idx_test, &un));
     KronWs* wp;
     GP_TRY(kron_prepare(h, m, d, n, axes, &wp));
     KronWs& w = *wp;
-    const KronDev& dv = w.tr.dev;
     GP_TRY(kron_predict_ws(h, w, d, n_test, axes_test));
-    if (!shared) {
-        GP_TRY(kron_axes_ensure(h, w.un, d, n_union, false));
-        HIP_TRY(hipMemcpyAsync(const_cast<double*>(w.un.dev.coords), axes_union, (size_t)sum_u * sizeof(double),
-                               hipMemcpyDeviceToDevice, h->stream));
-        GP_TRY(kron_plan_problems(h, w.un));
-        GP_TRY(kron_cold_start(h, w.un.dev));
-    }
-    const KronAxes& ua = shared ? w.tr : w.un;
-    const KronDev& du = ua.dev;
-    int64_t PU = 0;
-    GP_TRY(kron_sample_ws(h, w, d, n_union, S, &PU));
-    HIP_TRY(hipMemcpyAsync(w.ic, idx_train, (size_t)sum_n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(w.it, idx_test, (size_t)sum_m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (!un.shared) GP_TRY(kron_axes_load(h, w.un, d, n_union, axes_union, false));
+    GP_TRY(kron_sample_ws(h, w, d, n_union, un, S));
+    HIP_TRY(hipMemcpyAsync(w.ic, idx_train, (size_t)un.sum_n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(w.it, idx_test, (size_t)un.sum_m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));          // the host arrays are the caller's
-    const int64_t N = w.N, M = w.M, zw = PU + N + M;
-    const double* mats[KMAXD]; int ld[KMAXD];
-    double* res;
+    const int64_t N = w.N, M = w.M;
+    KronDraw D = {w, un.shared ? w.tr : w.un, z, un.U, un.U + N + M, S, {}, {}};
     {
         StageTimer t(h, 1);
         GP_TRY(kron_decompose(h, w, m, u, y));
-        hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
+        hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, w.tr.dev, h->theta, w.yt, w.at, w.part);
     }
-    if (!shared) {
+    if (!un.shared) {
         StageTimer t(h, 0);
         GP_TRY(kron_eig_axes(h, w.un));
     }
-    double* gG;
-    {   // the prior on the training grid: g_G / sqrt(s2) = ((x) R_i[ic_i, :]) zeta
-        StageTimer t(h, 2);
-        for (int i = 0, oc = 0, ot = 0; i < d; ++i) {
-            const int U = ua.n[i];
-            hipLaunchKernelGGL(kron_root_rows_kernel, dim3((unsigned)(((int64_t)w.n[i] * U + 255) / 256)), dim3(256), 0, h->stream,
-                               du, i, w.ic + oc, w.n[i], w.RG + w.rgoff[i]);
-            hipLaunchKernelGGL(kron_root_rows_kernel, dim3((unsigned)(((int64_t)w.m[i] * U + 255) / 256)), dim3(256), 0, h->stream,
-                               du, i, w.it + ot, w.m[i], w.RT + w.rtoff[i]);
-            oc += w.n[i]; ot += w.m[i];
-        }
-        hipLaunchKernelGGL(kron_zeta_kernel, dim3((unsigned)((S * PU + 255) / 256)), dim3(256), 0, h->stream, z, zw, PU,
-                           (int64_t)S * PU, w.Zc);
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < d; ++i) { mats[i] = w.RG + w.rgoff[i]; ld[i] = ua.n[i]; }
-        GP_TRY(tensor_apply(h, d, ua.n, w.n, mats, ld, 0, 0, w.Zc, w.sa, w.sb, &gG, S));
-    }
-    {   // the update: out <- ((x) Ks_i Q_i) D^-1 ((x) Q_i^T) (y - sqrt(s2) g_G - sqrt(sigma) z_e), and the mean's
-        StageTimer t(h, 3);
-        GP_TRY(kron_cross_factors(h, w));
-        hipLaunchKernelGGL(kron_resid_kernel, dim3((unsigned)((S * N + 255) / 256)), dim3(256), 0, h->stream, y, z + PU, zw, N,
-                           (int64_t)S * N, h->theta, gG);
-        double* other = gG == w.sa ? w.sb : w.sa;
-        for (int i = 0; i < d; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = w.n[i]; }
-        GP_TRY(tensor_apply(h, d, w.n, w.n, mats, ld, 0, 0, gG, other, gG, &res, S));
-        hipLaunchKernelGGL(kron_dscale_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)std::min<int64_t>(S, 64)), dim3(256), 0,
-                           h->stream, dv, h->theta, S, res);
-        HIP_TRY(hipGetLastError());
-        other = res == w.sa ? w.sb : w.sa;
-        for (int i = 0; i < d; ++i) { mats[i] = w.Bs + w.koff[i]; ld[i] = w.n[i]; }
-        double* upd;
-        GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 0, res, other, res, &upd, S));
-        HIP_TRY(hipMemcpyAsync(out, upd, (size_t)S * M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        GP_TRY(tensor_apply(h, d, w.n, w.m, mats, ld, 0, 0, w.at, w.p1, w.p2, &res));     // the launches of predict's mean
-        HIP_TRY(hipMemcpyAsync(mean_out, res, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
-    double* gs;
-    {   // the prior on the test grid, from the same zeta
-        StageTimer t(h, 2);
-        for (int i = 0; i < d; ++i) { mats[i] = w.RT + w.rtoff[i]; ld[i] = ua.n[i]; }
-        GP_TRY(tensor_apply(h, d, ua.n, w.m, mats, ld, 0, 0, w.Zc, w.sa, w.sb, &gs, S));
-    }
+    double *gG, *gs;
+    GP_TRY(kron_draw_prior_train(h, D, &gG));
+    GP_TRY(kron_draw_update(h, D, y, gG, mean_out, out));
+    GP_TRY(kron_draw_prior_test(h, D, &gs));
     {
         StageTimer t(h, 5);
-        hipLaunchKernelGGL(kron_draw_kernel, dim3((unsigned)((S * M + 255) / 256)), dim3(256), 0, h->stream, gs, z + PU + N, zw,
+        hipLaunchKernelGGL(kron_draw_kernel, dim3((unsigned)((S * M + 255) / 256)), dim3(256), 0, h->stream, gs, z + D.PU + N, D.zw,
                            M, (int64_t)S * M, h->theta, noiseless, jitter, mean_out, out);
         HIP_TRY(hipGetLastError());
     }

@@ -6,7 +6,7 @@
 //     K = s2 K_s(X_s, X_s) (x) K_c,     K_c = (x) K_i = Q Lam Q^T   (Q = (x) Q_i, lambda_j = prod_i lambda_i[j_i])
 //     K + sigma I = (I (x) Q) blockdiag_j( s2 lambda_j K_s + sigma I ) (I (x) Q^T),     sigma = noise + jitter
 // i.e. J = prod n_i ordinary exact-GP blocks A_j of order N_s that share X_s: block j has kernel variance s2 max(lambda_j, 0)
-// and targets y~_j = column j of Y Q.  The blocks run in lock-step through the batched engine (api.hip: pkron_iter) the way
+// and targets y~_j = column j of Y Q.  The blocks run in lock-step through the batched engine (pkrongp.hip: pkron_iter) the way
 // the multi-output GP's do (vgp.hip); the complete axes are a KronAxes set of kron.hip.  Here:
 //   pkron_setup_kernel        u -> the model's theta, the complete axes' lengthscales, the ragged ones at variance 1
 //   pkron_blocks_theta_kernel lambda_j (each factor clamped at 0) and the J blocks' theta

@@ -1,5 +1,5 @@
-// pkron.hpp -- shared declarations of the dense-by-Kronecker blocks (pkron.hip kernels, api.hip drivers, draws.hip:
-// gpimhip_sample_pkron; DESIGN.md sections 22 and 23).
+// pkron.hpp -- shared declarations of the dense-by-Kronecker blocks (pkron.hip kernels and launchers, pkrongp.hip drivers;
+// DESIGN.md sections 22 and 23).
 #pragma once
 #include "common.hpp"
 #include "kron.hpp"
@@ -39,30 +39,7 @@ struct PkronWs {
     DevBuf<double> cross;           // 2 x sum m_i n_i: K*_i and K*_i Q_i
 };
 
-// ---- host drivers (api.hip), shared with the draws (draws.hip: gpimhip_sample_pkron) ----
-int pkron_check(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Xs, int64_t Ns, int32_t p, int32_t dc,
-                const int32_t* n_c, const int32_t* perm, const double* axes_c, const double* Y, PkronMap* mp);
-int pkron_begin(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_c, const double* axes_c, int64_t Ns, PkronWs** out);
-gpimhip_model_t pkron_submodel(const gpimhip_model_t* m, int p);
-int pkron_factor(gpimhip_ctx* h, const gpimhip_model_t* m, const gpimhip_model_t* ms, const PkronMap& mp, PkronWs* w,
-                 const double* Xs, const double* Y, int64_t Ns, const double* u, bool grad);
-int pkron_rows_times(gpimhip_ctx* h, const double* Bm, int64_t rows, const double* R, int64_t ldr, int64_t cols, double* C,
-                     int64_t ldc);
-int pkron_times_b(gpimhip_ctx* h, const PkronWs* w, int J, const double* R, int64_t ldr, int64_t cols, double* C, int64_t ldc);
-// the test grid on the complete axes: Mc = its points, sum_mn = sum m_i n_i (the cross factors), pmax = the largest tensor
-// (per ragged row) the chain of mode products n -> m passes through.  False: an axis without a coordinate
-struct PkronTest { int64_t Mc, sum_mn, pmax; };
-bool pkron_test_grid(const PkronMap& mp, const int32_t* n_test_c, PkronTest* out);
-// ragged test rows per chunk: the blocks' partial column sums (J x nb x mc doubles) stay <= ~0.5 GiB
-int64_t pkron_chunk(int64_t Ms, int J, int nb);
-// per complete axis: K*_i and bmat[i] = b_i = K*_i Q_i (eigen-coordinates straight to test points) in w->cross
-int pkron_cross_factors(gpimhip_ctx* h, PkronWs* w, const PkronMap& mp, const int32_t* n_test_c, const double* axes_test_c,
-                        int64_t sum_mn, const double** bmat);
-// the mode products with b_i (squared entries: square) over `lead` tensors (n_1, ..., n_dc, mc) in src, alternating between
-// bufa and bufb; *out = the (lead, m_1, ..., m_dc, mc) result
-int pkron_mode_chain(gpimhip_ctx* h, const PkronMap& mp, const int32_t* n_test_c, const double* const* bmat, const double* src,
-                     double* bufa, double* bufb, int64_t lead, int64_t mc, int square, const double** out);
-
+// ---- launchers (pkron.hip) ----
 int launch_pkron_setup(gpimhip_ctx* h, const gpimhip_model_t* m, const PkronMap& mp, const double* u, ThetaDev* th3);
 // lambda_j = prod_i max(lam_i[j_i], 0) into lamj and the J blocks' theta (variance s2 lambda_j, the ragged lengthscales,
 // noise, noise + jitter on the diagonal) into h->theta

@@ -12,6 +12,15 @@ int launch_sample_draws(gpimhip_ctx* h, const double* L, int64_t ld, int64_t N, 
                         int S, int s0, const ThetaDev* theta, int noiseless, double jitter_s, double* mean_ws,
                         double* mean_out, double* var_out, double* out);
 int sample_draw_group(int S);
+// a factorisation context of the draws at the given matrix order: created on first use, on the model handle's stream, one
+// problem, no matrices (draws.hip: SampleWs)
+int draw_sub(gpimhip_ctx* h, gpimhip_ctx** sub, int64_t order);
+// what the draws of the dense-by-Kronecker blocks (pkrongp.hip: gpimhip_sample_pkron) keep in the
+// handle's draw workspace: `sub` factors L_P, one arena carved per call, and the union of the complete axes when the training
+// axes do not serve
+struct KronAxes;
+struct PkronDrawWs { gpimhip_ctx*& sub; DevBuf<double>& ck; KronAxes& ck_un; };
+PkronDrawWs sample_pkron_ws(gpimhip_ctx* h);
 
 // ---- pathwise draws (gpimhip_sample_pathwise) ----
 // The complete product grid G of the draw: n[k] points along axis k (row-major, last axis fastest), mask = the reflected

@@ -46,7 +46,7 @@ import torch
 import torch.distributed as dist
 
 NB = 128
-PANEL = 4            # 128-blocks per panel (OUTER_W of csrc/api.hip)
+PANEL = 4            # 128-blocks per panel (OUTER_W of csrc/common.hpp)
 PW = NB * PANEL
 KINV_GROUP = int(os.environ.get("GPIM_DIST_KINV_GROUP", "8"))      # panels per launch of the K^-1 pass (1: one at a time)
 

@@ -174,6 +174,34 @@ def test_mean_bits_rows_and_grouping(name, grid):
     assert np.array_equal(mean1, mean0) and np.array_equal(sd1, sd0)
 
 
+@pytest.mark.parametrize("grid", ["half", None], ids=["own-union", "shared-union"])
+def test_draw_groups_inside_one_call(grid, monkeypatch):
+    """S = 10 draws in one group (GPIMHIP_PKRON_DRAW_GROUP unset: the budget holds thousands of draws of this cube) against
+    groups of 4, 4 and 2 inside one call: a group that starts at s0 > 0, the mean computed by the first group alone and read
+    by the later ones, a ragged last group.  The draws and the entry point's mean_out have the same bits."""
+    from gpim_amd import _lib
+    name = "6x5x4"
+    rec, params = build(name, 0)
+    taxes = axes_of(name, grid)
+    Us, U, N, M = oracle(rec, params, taxes, False)[4]
+    W = Us * U + N + M
+    z = torch.from_numpy(np.random.default_rng(7).standard_normal((10, W))).to(rec._dev)
+
+    def call(noiseless):
+        mean = torch.zeros(M, dtype=torch.float64, device=rec._dev)
+        out = torch.zeros((10, M), dtype=torch.float64, device=rec._dev)
+        _lib.check(rec._solver.sample_columns(rec, taxes, z, noiseless, CO.D, mean, out))
+        return out.cpu().numpy(), mean.cpu().numpy()
+
+    for noiseless in (False, True):
+        monkeypatch.delenv("GPIMHIP_PKRON_DRAW_GROUP", raising=False)
+        one_out, one_mean = call(noiseless)
+        monkeypatch.setenv("GPIMHIP_PKRON_DRAW_GROUP", "4")
+        out, mean = call(noiseless)
+        assert np.isfinite(one_out).all() and one_out.any() and not np.array_equal(one_out[0], one_out[9])
+        assert np.array_equal(out, one_out) and np.array_equal(mean, one_mean)
+
+
 def test_against_the_joint_draws_of_the_dense_model():
     """12 x 12 x 6: the dense engine's method='joint' on the same observations gives Sigma_post + (c_n + jitter) I; A A^T of
     method='columns' minus the oracle's extra term and c_n I must agree with it at 1e-7, the bar tests/test_gpu_columns.py

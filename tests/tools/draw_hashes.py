@@ -4,17 +4,23 @@
 
 For refactors of the draw and prediction drivers that must not change a bit: run it on the commit before and on the commit
 after, on the same machine, and diff the two printouts by hand.  It compares nothing and stores nothing.  The models are
-not trained (the hyper-parameters are the seeded initial ones); every draw takes S = 9 samples, two draw groups (8 + 1).
-The cases, each for a branch of csrc/draws.hip, the prediction loops of csrc/api.hip, the spectral-mixture and multi-output
-drivers or the workspaces of csrc/kron.hip:
+not trained before their draws and predictions (the hyper-parameters are the seeded initial ones; a model's training case
+comes last); every draw takes S = 9 samples, two draw groups (8 + 1), unless its line says otherwise.
+The cases, each for a branch of csrc/draws.hip, the prediction loops of csrc/api.hip, the spectral-mixture, multi-output and
+dense-by-Kronecker drivers (csrc/smgp.hip, vgpgp.hip, pkrongp.hip), the drivers and workspaces of csrc/kron.hip or the panel
+drivers of csrc/distgp.hip:
   joint      N = 300, M = 340 (the training rows end in block row 3 of 5) with an explicit z; N = 40, M = 20 (one block)
   pathwise   48 x 48 grid, both axes reflected (576-point blocks: two panels), 600 observed pixels; with noise and noiseless
   blocks     the same grid, fully observed;  border: the same grid with 5 missing pixels
   vgp        T = 2 outputs on a 16 x 16 grid: joint and blocks
   spectral   Q = 2 mixtures on a 16 x 16 grid: joint, pathwise and blocks
   columns    a (48, 6, 5) cube, 37 of the 48 rows along the first axis observed, drawn and predicted at 11 new rows times the
-             training axes (the union axes are the training axes), and with new coordinates on one complete axis
-  kron       a fully observed 12 x 10 grid
+             training axes (the union axes are the training axes), and with new coordinates on one complete axis; both draws
+             again with S = 10 and GPIMHIP_PKRON_DRAW_GROUP=4 (groups of 4, 4 and 2: the same bits as one group of 10);
+             nll_grad and ten Adam iterations
+  kron       a fully observed 12 x 10 grid: drawn and predicted on itself, drawn on the half-step grid (the union axes are
+             not the training axes: the second decomposition), nll_grad and ten Adam iterations
+  dist       N = 700 on one device: gpimhip_dist_begin to the factor, its log det and a forward / backward solve
   sm, vgp    Q = 2 mixtures / T = 2 outputs on a 16 x 16 grid in three regimes each (dense: 200 observed pixels for sm, the
              dense solver for vgp; blocks: the complete grid; border: 3 missing pixels): predict, nll_grad, ten Adam
              iterations; gpimhip_sm_kmat on a dense handle and in reflection mode; two predictions at M = 961 and the two
@@ -115,19 +121,27 @@ def cases():
     yield "spectral blocks Q=2 16x16 (%s)" % rsf.solver, lambda: (rsf.sample(S, seed=5, method="blocks"),)
     # ---- the dense-by-Kronecker blocks
     Xc, yc = columns_cube()
-    rc = gpim_amd.skreconstructor(Xc, yc, None, kernel="RBF", lengthscale=[[0.5] * 3, [20.0] * 3], verbose=0)
+    rc = gpim_amd.skreconstructor(Xc, yc, None, kernel="RBF", lengthscale=[[0.5] * 3, [20.0] * 3], learning_rate=0.05,
+                                  iterations=10, verbose=0)
     rows = np.arange(11) * 4.0 + 0.5
     for name, taxes in (("shared union", (rows, np.arange(6.0), np.arange(5.0))),
                         ("own union", (rows, np.arange(6.0) + 0.25, np.arange(5.0)))):
         Xt = grid(*taxes)
         yield "columns sample, %s (%s)" % (name, rc.solver), lambda Xt=Xt: (rc.sample(S, seed=6, Xtest=Xt, method="columns"),)
         yield "columns predict, %s" % name, lambda Xt=Xt: rc.predict(Xt, verbose=0)
+        yield "columns sample S=10 groups of 4, %s" % name, lambda Xt=Xt: with_env(
+            "GPIMHIP_PKRON_DRAW_GROUP", "4", lambda: (rc.sample(10, seed=6, Xtest=Xt, method="columns"),))
+    yield from training_cases("columns (48, 6, 5)", rc)
     # ---- the Kronecker model
     _, fk = image((12, 10))
     Xk = gpim_amd.utils.get_full_grid(fk)
-    rk = gpim_amd.reconstructor(Xk, fk, Xk, kernel="RBF", structured=True, **kw)
+    rk = gpim_amd.reconstructor(Xk, fk, Xk, kernel="RBF", structured=True, learning_rate=0.05, iterations=10, **kw)
     yield "kron sample 12x10", lambda: (rk.sample(S, seed=7, method="kron"),)
     yield "kron predict 12x10", lambda: rk.predict(verbose=0)
+    Xh = grid(np.arange(0, 11.25, 0.5), np.arange(0, 9.25, 0.5))
+    yield "kron sample 12x10, half-step test grid", lambda: (rk.sample(S, seed=7, Xtest=Xh, method="kron"),)
+    yield from training_cases("kron 12x10", rk)
+    yield "dist N=700, one device", dist_case
     # ---- prediction and training of the spectral-mixture and the multi-output drivers, three regimes each
     R3, X3 = f16.copy(), X16.astype(np.float64)
     for hole in ((3, 4), (9, 2), (15, 15)):
@@ -154,13 +168,47 @@ def cases():
     yield "predict N=300 M=340, slab path", lambda: slab_predict(r)
 
 
+def with_env(name, value, run):
+    os.environ[name] = value
+    try:
+        return run()
+    finally:
+        del os.environ[name]
+
+
+def training_cases(name, rec):
+    """loss and gradient at the initial parameters, then ten Adam iterations (graph replay); after the model's other cases:
+    training moves its parameters"""
+    def loss_grad():
+        loss, grad = rec.loss_and_grad()
+        return np.array([loss]), grad.numpy()
+    yield name + " nll_grad", loss_grad
+
+    def train():
+        rec.train()
+        return [np.array(rec.loss_all), rec._u.cpu().numpy()] + [np.array(rec.hyperparams[k], dtype=np.float64)
+                                                                 for k in ("lengthscale", "variance", "noise")]
+    yield name + " train T=10", train
+
+
+def dist_case():
+    """gpimhip_dist_begin to a factorisation and a forward / backward solve through DistributedCholesky on one device (the
+    smallest order of tests/test_gpu_dist.py): the factor, log det and the solution"""
+    import torch
+    from gpim_amd.dist_chol import DistributedCholesky
+    n = 700
+    rng = np.random.default_rng(n)
+    B = rng.standard_normal((n, n // 3))
+    A = torch.from_numpy(B @ B.T + n * np.eye(n)).cuda()
+    ch = DistributedCholesky(n)
+    ch.set_from_function(lambda c0, c1: A[:, c0:c1]).factor()
+    y = torch.from_numpy(rng.standard_normal(n)).cuda()
+    return ch.gather_lower().cpu().numpy(), np.array([ch.logdet()]), ch.solve(y).cpu().numpy()
+
+
 def slab_predict(rec):
     """predict() through the chunk loop at a size where the stationary dense model would take the fused launch"""
-    os.environ["GPIMHIP_NO_FUSED_PREDICT"] = "1"
-    try:
-        return rec.predict(verbose=0)
-    finally:
-        del os.environ["GPIMHIP_NO_FUSED_PREDICT"]
+    return with_env("GPIMHIP_NO_FUSED_PREDICT", "1", lambda: rec.predict(verbose=0))
 
 
 def model_cases(name, rec, hyper, fine):
