@@ -197,6 +197,14 @@ _PROTOS = {
     "gpimhip_set_border": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, c_dp]),
     "gpimhip_nll_grad_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, c_dp,
                                                 ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, c_dp]),
+    # leave-one-out cross-validation: the predict entry's head, then (mean_out, var_out, score_out); the batched form takes
+    # (rep, sgn, y_grid) in place of the test points
+    "gpimhip_loo_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
+                                         c_dp, c_dp, c_dp]),
+    "gpimhip_loo_exact_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, ctypes.c_int64, c_dp,
+                                                 ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "gpimhip_loo_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
+                                        ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "gpimhip_acquire_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
                                              c_dp, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_dp]),

@@ -6,8 +6,9 @@ _solvers.py -- the host layer between the reconstructors and the C ABI (include/
   * ``DeviceBlocks``: the device side of a blocks dict (gprutils.reflection_blocks* / border_blocks*), entered with
     ``_lib.reflection``.
   * ``Dense`` / ``Sparse`` / ``Kron`` / ``Columns`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
-    fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out), each returning the
-    library's status.  ``SpectralBlocks``: the reflection / border path of ``smreconstructor`` (one shared parameter vector).
+    fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out),
+    loo(o, mean, var, score), each returning the library's status (a path without an exact leave-one-out raises
+    NotImplementedError with its reason).  ``SpectralBlocks``: the reflection / border path of ``smreconstructor`` (one shared parameter vector).
     ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
     through the library handle) and reads ``o._Xd`` / ``o._yd`` / ``o._u`` as they are at the time of the call
     (boptimizer swaps the training data between trainings).  A new path is one more class here and one more arm where
@@ -163,6 +164,24 @@ class Dense:
     def nll_grad(self, o, out):
         return o._handle.lib.gpimhip_nll_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), *_loss_grad(out))
 
+    no_loo = None                                       # why a path has no exact leave-one-out (the paths that inherit Dense's)
+
+    def _loo_refused(self, why=None):
+        raise NotImplementedError("loo(): the %s solver has no exact leave-one-out -- %s" % (type(self).__name__, why or self.no_loo))
+
+    def loo(self, o, mean, var, score):
+        """Leave-one-out predictions of the N training rows, in their order, and score = [elpd, sse] from one factorisation
+        (csrc/engine.hip: colsq_tri_kernel, loo_finish_kernel).  Double- and single-precision models."""
+        if self.no_loo:
+            self._loo_refused()
+        return o._handle.lib.gpimhip_loo_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(mean), ptr(var),
+                                               ptr(score))
+
+    def _loo_double_only(self, o):
+        if o.precision == "single":
+            self._loo_refused("the structured solvers compute in double from float32 inputs, a mix that leave-one-out has no "
+                              "stated accuracy for: build the model with precision='double'")
+
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:
         the gate of _sampling.Joint refuses the other paths before a solver is asked."""
@@ -217,6 +236,8 @@ class Dense:
 class Sparse(Dense):
     """Sparse variational GP (VFE) with the ``o._n_ind`` trainable inducing inputs at the end of ``o._u`` (csrc/vfe.hip)."""
     sparse = True
+    no_loo = ("the variational (VFE) posterior conditions on inducing points, not on the observations: dropping one "
+              "observation has no closed form in its factors")
 
     def fit(self, o, lr, T, hist, loss):
         hist_xu = torch.empty((max(T, 1), o._n_ind, o._spec.dim), dtype=_F64, device=o._dev)
@@ -267,6 +288,11 @@ class Kron(Dense):
     def nll_grad(self, o, out):
         return o._handle.lib.gpimhip_kron_nll_grad(*self._grid(o), *_loss_grad(out))
 
+    def loo(self, o, mean, var, score):
+        """In the eigenbasis: diag(S^-1) = ((x) Q_i o Q_i)(1 / D) by mode products (csrc/kron.hip: gpimhip_loo_kron)."""
+        self._loo_double_only(o)
+        return o._handle.lib.gpimhip_loo_kron(*self._grid(o), ptr(mean), ptr(var), ptr(score))
+
     def sample_kron(self, o, taxes, union, z, noiseless, jitter, mean, out):
         """Joint posterior draws on the product grid of the axes ``taxes`` by Matheron's rule in Kronecker form (csrc/kron.hip:
         gpimhip_sample_kron).  union: what gprutils.union_axes returns for the training and the test
@@ -289,6 +315,8 @@ class Columns(Dense):
     and the posterior are those of ``Dense`` on the same observations."""
     structured = True
     _NO_DRAWS = "solver='columns' draws with method='columns' only"
+    no_loo = ("solver='columns': diag(S^-1) of the dense-by-Kronecker blocks mixes every block's diagonal through the "
+              "complete axes' eigenvectors, which is not built")
 
     def __init__(self, C):
         self.C = C
@@ -437,6 +465,7 @@ class Reflection(Dense):
 
     def __init__(self, S, border=False):
         self.S, self.border, self.blocks, self.perm_d = S, border, None, None
+        self.rep32 = self.sgn32 = None                  # the index maps of loo(), uploaded on first use
 
     @contextlib.contextmanager
     def _mode(self, o, var_count=0):
@@ -488,6 +517,23 @@ class Reflection(Dense):
         mean[self.perm_d] = mean_p
         torch.index_select(var_p[:nq], 0, self.rep_d, out=var)
         return rc
+
+    def loo(self, o, mean, var, score):
+        """The blocks' diagonals in one launch, combined in grid space with the weights |Stab_p| / B and the characters
+        chi_s(sgn_i) (csrc/api.hip: gpimhip_loo_exact_batched).  The training rows are the complete grid in its order."""
+        if self.border:
+            self._loo_refused("with a border the missing points couple the reflection blocks, and diag(S^-1) is no longer a "
+                              "weighted sum of the blocks' diagonals")
+        self._loo_double_only(o)
+        with self._mode(o) as D:
+            if self.rep32 is None:
+                i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(o._dev)
+                self.rep32, self.sgn32 = i32(self.S["rep"]), i32(self.S["sgn"])
+            u_b = o._u.repeat(D.B).contiguous()
+            return o._handle.lib.gpimhip_loo_exact_batched(*_head(o), ptr(D.Xq), 0, ptr(D.ys), D.Xq.shape[0], D.B, ptr(u_b),
+                                                           ctypes.c_void_p(self.rep32.data_ptr()),
+                                                           ctypes.c_void_p(self.sgn32.data_ptr()), ptr(o._yd), ptr(mean),
+                                                           ptr(var), ptr(score))
 
     def sample_border(self, o, Xs, P, miss_d, z, noiseless, jitter, mean, out):
         """Pathwise draws on the completed grid whose rows are Xs for a model with missing points, through the state a

@@ -1102,6 +1102,54 @@ int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const d
     return finish_and_check(h);
 }
 
+// Leave-one-out cross-validation (engine.hip: colsq_tri_kernel, loo_finish_kernel): the model's state at u, then the column
+// sums of squares of L^-1 of every problem in one launch and the finisher.  No K^-1 product, no gradient contraction.  The
+// row-chunk partial sums go to h->gemv_part (alpha has been summed out of it) and the score's to h->z (L^-1 y has served).
+static int loo_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N, int B,
+                    const double* u, const int32_t* rep, const int32_t* sgn, const double* y_grid, double* mean_out,
+                    double* var_out, double* score_out) {
+    GP_TRY(model_state_at_u(h, m, X, x_bs, y, N, B, u));
+    const int64_t np = h->np;
+    GP_TRY(launch_colsq_tri(h, h->A, h->ld, np, N, h->gemv_part));
+    LooSrc s{rep ? y_grid : y, h->gemv_part, gemv_tri_chunks(np), gemv_tri_rc(np), np, h->alpha, rep ? B : 0, h->refl.wts, rep, sgn, N};
+    GP_TRY(launch_loo_finish(h, s, rep ? h->refl.n_total : N, h->theta, h->z, mean_out, var_out, score_out));
+    return finish_and_check(h);
+}
+
+int gpimhip_loo_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                      double* mean_out, double* var_out, double* score_out) {
+    if (!h || !X || !y || !u || N < 1 || !mean_out || !var_out || !score_out) return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (h->refl.mask) {
+        gpim_set_error("gpimhip_loo_exact is the dense model's entry: in reflection mode use gpimhip_loo_exact_batched");
+        return GPIMHIP_E_BADARG;
+    }
+    return loo_impl(h, m, X, 0, y, N, 1, u, nullptr, nullptr, nullptr, mean_out, var_out, score_out);
+}
+
+int gpimhip_loo_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
+                              int64_t N, int32_t B, const double* u, const int32_t* rep, const int32_t* sgn,
+                              const double* y_grid, double* mean_out, double* var_out, double* score_out) {
+    if (!h || !X || !y || !u || N < 1 || B < 1 || B > (1 << GPIMHIP_MAX_DIM) || !rep || !sgn || !y_grid || !mean_out ||
+        !var_out || !score_out || (x_stride != 0 && x_stride < N * (m ? m->dim : 1)))
+        return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    if (!h->refl.mask || h->fp32 || h->refl.n_total < 1) {
+        gpim_set_error("gpimhip_loo_exact_batched combines the reflection blocks: needs reflection mode with n_total set on a double-precision handle");
+        return GPIMHIP_E_BADARG;
+    }
+    if (border_on(h)) {
+        gpim_set_error("gpimhip_loo_exact_batched: no leave-one-out through a border (the missing points couple the blocks: "
+                       "diag(S^-1) is no longer a weighted sum of the blocks' diagonals)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (h->refl.pb_off != 0 || h->refl.pb_stride != 1 || h->refl.raw || (h->refl.nblocks_total && h->refl.nblocks_total != B)) {
+        gpim_set_error("gpimhip_loo_exact_batched needs all blocks of the model on this handle (no shard)");
+        return GPIMHIP_E_BADARG;
+    }
+    return loo_impl(h, m, X, x_stride, y, N, B, u, rep, sgn, y_grid, mean_out, var_out, score_out);
+}
+
 int gpimhip_acq(gpimhip_handle h, int32_t kind, const double* mean, const double* sd, int64_t M, double p0,
                 double p1, const double* mask, double* acq_out) {
     if (!h || !mean || !sd || !acq_out || M < 1 || kind < 0 || kind > GPIMHIP_ACQ_POI) return GPIMHIP_E_BADARG;

@@ -472,6 +472,19 @@ int launch_dist_finalize_dev(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N
 int launch_dist_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, const double* S, double q2, double lg,
                          double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row);
 int launch_add_diag_theta(gpimhip_ctx* h, double* out, int64_t ld, int64_t row0, int64_t n, int64_t npad);
+// engine.hip (leave-one-out cross-validation).  What loo_finish_kernel reads for its n points: the observations y, and
+// per problem d = diag(S^-1) as the row-chunk partial sums of launch_colsq_tri (nR chunks of rc rows of a matrix of order
+// np; nR = 1 with rc = INT_MAX: d itself, np apart) and alpha (np apart).  B == 0: one problem, point i is its row i.
+// B > 0: the B reflection blocks of Nq points -- wts (B x Nq, or null), rep[i] the row of point i's representative and
+// sgn[i] the reflections that take the representative to i (bit j: the j-th reflected axis, the numbering of the blocks)
+struct LooSrc {
+    const double* y; const double* diag_part; int nR, rc; int64_t np; const double* alpha;
+    int B; const double* wts; const int32_t* rep; const int32_t* sgn; int64_t Nq;
+};
+static inline int loo_blocks(int64_t n) { return n > 1024 * 256 ? 1024 : (int)((n + 255) / 256); }
+int launch_colsq_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, int64_t N, double* part);
+int launch_loo_finish(gpimhip_ctx* h, const LooSrc& s, int64_t n, const ThetaDev* theta, double* part, double* mean_out,
+                      double* var_out, double* score_out);
 int launch_theta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* u);
 // select.hip
 int launch_topk_radix(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,

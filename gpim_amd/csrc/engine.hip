@@ -6,6 +6,7 @@
 //   finalize_kernel     loss, d loss/du, Adam step, history row                      (rows a7-a10)
 //   predict helpers     mean = K*^T alpha, var = clamp(s2 - colsumsq, 0) + noise     (row a11)
 //   acq / nanmax / topk acquisition sweep and ranking                                (rows a13, a14)
+//   colsq_tri / loo_*   diag(S^-1) from L^-1 and the leave-one-out predictions        
 // Row labels refer to SURVEY.md section 8(a).  All reductions use fixed-shape trees so results are
 // bit-reproducible run to run.
 #include "kfun.hpp"
@@ -1515,6 +1516,144 @@ __global__ void add_diag_theta_kernel(double* __restrict__ out, int64_t ld, int6
 int launch_add_diag_theta(gpimhip_ctx* h, double* out, int64_t ld, int64_t row0, int64_t n, int64_t npad) {
     hipLaunchKernelGGL(add_diag_theta_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, out, ld, row0, n,
                        npad, h->theta);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Leave-one-out cross-validation from one factorisation (gpimhip_loo_*).  With S = K + (noise +
+// jitter) I, alpha = S^-1 y and d_i = [S^-1]_ii the prediction of y_i from the other N - 1 observations is
+//     mu_i = y_i - alpha_i / d_i,    var_i = max(1 / d_i - (noise + jitter), 0) + noise      (predict()'s convention)
+// and d_i = sum_{k >= i} (L^-1)_ki^2: the column sums of squares of the triangular inverse that every model state already
+// holds in h->A -- one HBM-bound pass over N^2 / 2 entries, no O(N^3) product.
+// colsq_tri_kernel is gemv_t_tri_kernel with a * a in place of a * x: the same (column block, row chunk) workgroups, the
+// same two-rows-per-instruction loads, double accumulation, per-chunk partial sums that the consumer adds in increasing
+// chunk order (gemv_tri_alpha).  Rows >= N (the identity padding, which a ragged factorisation never writes) are not read:
+// a chunk that lies wholly in the padding writes zeros.
+// ------------------------------------------------------------------------------------------
+template <typename R>
+__global__ __launch_bounds__(256) void colsq_tri_kernel(const R* __restrict__ A, int64_t ld, int64_t np, int64_t N,
+                                                        double* __restrict__ part, int rc, int nR, int64_t a_bs) {
+    __shared__ d2 red[4][32];
+    const int cb = blockIdx.x / nR, r = blockIdx.x % nR;
+    const int64_t diag0 = ((int64_t)cb * 64 / NB) * NB;
+    int64_t i0 = (int64_t)r * rc, i1 = i0 + rc < np ? i0 + rc : np;
+    if (i1 <= diag0 || (int64_t)cb * 64 >= N) return;          // structurally zero / padding columns: never read by the sum
+    if (i0 < diag0) i0 = diag0;
+    if (i1 > N) i1 = N;
+    A += blockIdx.y * a_bs;
+    part += ((int64_t)blockIdx.y * nR + r) * np;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cp = lane & 31, rp = lane >> 5;
+    typedef typename Vec2<R>::T RV;
+    const R* col = A + (int64_t)cb * 64 + 2 * cp;
+    d2 s0 = (d2){0.0, 0.0}, s1 = s0, s2 = s0, s3 = s0;
+    int64_t i = i0 + 2 * wave + rp;                             // rows i, i + 8, i + 16, ... (8 = 4 waves x 2 rows)
+    for (; i + 24 < i1; i += 32) {
+        const RV a0 = *reinterpret_cast<const RV*>(col + i * ld), a1 = *reinterpret_cast<const RV*>(col + (i + 8) * ld);
+        const RV a2 = *reinterpret_cast<const RV*>(col + (i + 16) * ld), a3 = *reinterpret_cast<const RV*>(col + (i + 24) * ld);
+        s0[0] = fma((double)a0[0], (double)a0[0], s0[0]); s0[1] = fma((double)a0[1], (double)a0[1], s0[1]);
+        s1[0] = fma((double)a1[0], (double)a1[0], s1[0]); s1[1] = fma((double)a1[1], (double)a1[1], s1[1]);
+        s2[0] = fma((double)a2[0], (double)a2[0], s2[0]); s2[1] = fma((double)a2[1], (double)a2[1], s2[1]);
+        s3[0] = fma((double)a3[0], (double)a3[0], s3[0]); s3[1] = fma((double)a3[1], (double)a3[1], s3[1]);
+    }
+    for (; i < i1; i += 8) {
+        const RV a0 = *reinterpret_cast<const RV*>(col + i * ld);
+        s0[0] = fma((double)a0[0], (double)a0[0], s0[0]); s0[1] = fma((double)a0[1], (double)a0[1], s0[1]);
+    }
+    d2 v;
+    v[0] = (s0[0] + s1[0]) + (s2[0] + s3[0]);
+    v[1] = (s0[1] + s1[1]) + (s2[1] + s3[1]);
+    v[0] += __shfl_xor(v[0], 32);                               // the two row parities (both halves end with the same sum)
+    v[1] += __shfl_xor(v[1], 32);
+    if (rp == 0) red[wave][cp] = v;
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        d2 t = red[0][cp];
+        t[0] = ((t[0] + red[1][cp][0]) + red[2][cp][0]) + red[3][cp][0];
+        t[1] = ((t[1] + red[1][cp][1]) + red[2][cp][1]) + red[3][cp][1];
+        *reinterpret_cast<d2*>(part + (int64_t)cb * 64 + 2 * cp) = t;
+    }
+}
+// part: gemv_tri_chunks(np) * np doubles per problem, as launch_gemv_t_tri's (h->gemv_part once alpha has been summed);
+// all h->nbatch problems in one launch
+int launch_colsq_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, int64_t N, double* part) {
+    const int rc = gemv_tri_rc(np), nR = gemv_tri_chunks(np);
+    const dim3 grid((unsigned)((np / 64) * nR), h->nbatch);
+    if (h->fp32)
+        hipLaunchKernelGGL(colsq_tri_kernel<float>, grid, dim3(256), 0, h->stream, reinterpret_cast<const float*>(A), ld, np, N,
+                           part, rc, nR, np * ld);
+    else
+        hipLaunchKernelGGL(colsq_tri_kernel<double>, grid, dim3(256), 0, h->stream, A, ld, np, N, part, rc, nR, np * ld);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// The held-out predictions of the n points of s (common.hpp: LooSrc) and their score.  Thread by thread over the points
+// (grid stride): d_i and alpha_i -- the point's own entries, or in reflection mode the sums over the blocks that hold its
+// representative p,  d_i = sum_s (|Stab_p| / B) [S_s^-1]_pp  and  alpha_i = sum_s chi_s(g_i) sqrt(|Stab_p| / B) alpha_s[p]
+// with |Stab_p| = wts^-2 -- then mu, var, the squared residual and log N(y_i | mu, var).  The last two are summed per
+// workgroup (block_sum_256) into part[2 * workgroup ..]; loo_score_kernel adds the workgroups' sums in their order: no
+// atomics, the same bits on every call.  Only the n points are written.
+__global__ __launch_bounds__(256) void loo_finish_kernel(LooSrc s, int64_t n, const ThetaDev* __restrict__ th,
+                                                         double* __restrict__ mean_out, double* __restrict__ var_out,
+                                                         double* __restrict__ part) {
+    __shared__ double red[256];
+    const double noise = th->noise, dadd = th->diag_add;
+    double elpd = 0.0, sse = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double d = 0.0, a = 0.0;
+        if (s.B == 0) {
+            d = gemv_tri_alpha(s.diag_part, s.nR, s.rc, s.np, i);
+            a = s.alpha[i];
+        } else {
+            const int64_t p = s.rep[i];
+            const int g = s.sgn[i];
+            const double sb = sqrt((double)s.B);
+            for (int b = 0; b < s.B; ++b) {
+                const double w = s.wts ? s.wts[(int64_t)b * s.Nq + p] : 1.0;
+                if (w == 0.0) continue;                         // the point does not exist in this block (an identity row)
+                const double c = 1.0 / (w * sb);                // sqrt(|Stab_p| / B)
+                d = fma(c * c, gemv_tri_alpha(s.diag_part + (int64_t)b * s.nR * s.np, s.nR, s.rc, s.np, p), d);
+                const double t = c * s.alpha[(int64_t)b * s.np + p];
+                a += (__popc(b & g) & 1) ? -t : t;
+            }
+        }
+        const double yi = s.y[i];
+        const double mu = yi - a / d, v = clamp0_nan(1.0 / d - dadd) + noise;
+        const double res = yi - mu;
+        mean_out[i] = mu;
+        var_out[i] = v;
+        elpd -= 0.5 * (log(6.283185307179586476925 * v) + res * res / v);
+        sse = fma(res, res, sse);
+    }
+    elpd = block_sum_256(elpd, red);
+    sse = block_sum_256(sse, red);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = elpd;
+        part[2 * blockIdx.x + 1] = sse;
+    }
+}
+__global__ __launch_bounds__(256) void loo_score_kernel(const double* __restrict__ part, int nblk, double* __restrict__ score) {
+    __shared__ double red[256];
+    double elpd = 0.0, sse = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 256) {
+        elpd += part[2 * k];
+        sse += part[2 * k + 1];
+    }
+    elpd = block_sum_256(elpd, red);
+    sse = block_sum_256(sse, red);
+    if (threadIdx.x == 0) {
+        score[0] = elpd;
+        score[1] = sse;
+    }
+}
+// part: 2 * loo_blocks(n) doubles of scratch; theta: the (first) problem's; score_out = [elpd, sse]
+int launch_loo_finish(gpimhip_ctx* h, const LooSrc& s, int64_t n, const ThetaDev* theta, double* part, double* mean_out,
+                      double* var_out, double* score_out) {
+    const int nblk = loo_blocks(n);
+    hipLaunchKernelGGL(loo_finish_kernel, dim3(nblk), dim3(256), 0, h->stream, s, n, theta, mean_out, var_out, part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(loo_score_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)part, nblk, score_out);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }

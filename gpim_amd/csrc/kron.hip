@@ -26,9 +26,10 @@
 //   posterior draws on any product test grid (gpimhip_sample_kron), all S draws per launch:
 //   kron_root_rows_kernel rows of the prior root of a union axis;  kron_zeta_kernel zeta out of z;  kron_resid_kernel the
 //   residual;  kron_dscale_kernel the 1 / D scaling;  kron_draw_kernel the epilogue
-// Host drivers: the four entries gpimhip_*_kron and the diagnostic gpimhip_kron_eigh, and what the dense-by-Kronecker blocks
+// Host drivers: the five entries gpimhip_*_kron (gpimhip_loo_kron: leave-one-out) and the diagnostic gpimhip_kron_eigh, and what the dense-by-Kronecker blocks
 // (pkrongp.hip) build on (kron.hpp): the per-axis drivers and the union-axis steps the two draws share (kron_axes_load,
 // kron_union_check, kron_union_roots).
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1016,6 +1017,32 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
     hipLaunchKernelGGL(kron_post_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, mean_out, res, M,
                        h->theta, mean_out, var_out);
     HIP_TRY(hipGetLastError());
+    return finish_and_check(h);
+}
+
+// Leave-one-out cross-validation in the eigenbasis: alpha = Q (y~ / D) and diag(S^-1) = ((x) Q_i o Q_i)
+// (1 / D), the mode products of the squared eigenvector matrices with what kron_invd_kernel leaves; then the dense
+// model's finisher (engine.hip: loo_finish_kernel).  alpha waits in w.Z while 1 / D takes the place of alpha~.
+int gpimhip_loo_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
+                     const double* y, const double* u, double* mean_out, double* var_out, double* score_out) {
+    if (!h || !m || !y || !u || !mean_out || !var_out || !score_out) return GPIMHIP_E_BADARG;
+    FP64_ONLY(h);
+    KronWs* wp;
+    GP_TRY(kron_prepare(h, m, d, n, axes, &wp));
+    KronWs& w = *wp;
+    const KronDev& dv = w.tr.dev;
+    GP_TRY(kron_decompose(h, w, m, u, y));
+    hipLaunchKernelGGL(kron_dvec_kernel, dim3(w.nblk), dim3(256), 0, h->stream, dv, h->theta, w.yt, w.at, w.part);
+    // Qt holds Q_i^T: transposed, the mode products map eigen-coordinates back to grid points
+    const double* mats[KMAXD]; int ld[KMAXD];
+    for (int i = 0; i < w.d; ++i) { mats[i] = dv.Qt + dv.moff[i]; ld[i] = w.n[i]; }
+    double* res;
+    GP_TRY(tensor_apply(h, w.d, w.n, w.n, mats, ld, 1, 0, w.at, w.t1, w.t2, &res));
+    HIP_TRY(hipMemcpyAsync(w.Z, res, (size_t)w.N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    hipLaunchKernelGGL(kron_invd_kernel, dim3((unsigned)((w.N + 255) / 256)), dim3(256), 0, h->stream, dv, h->theta, w.at);
+    GP_TRY(tensor_apply(h, w.d, w.n, w.n, mats, ld, 1, 1, w.at, w.t1, w.t2, &res));
+    const LooSrc s{y, res, 1, INT_MAX, w.N, w.Z, 0, nullptr, nullptr, nullptr, 0};
+    GP_TRY(launch_loo_finish(h, s, w.N, h->theta, w.part, mean_out, var_out, score_out));
     return finish_and_check(h);
 }
 

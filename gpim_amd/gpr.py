@@ -74,6 +74,7 @@ class _ModelView:
     @X.setter
     def X(self, value):
         self._o._no_swap("X")
+        self._o._data_swapped = True
         self._o._Xd = self._o._to_device(value)
 
     @property
@@ -83,6 +84,7 @@ class _ModelView:
     @y.setter
     def y(self, value):
         self._o._no_swap("y")
+        self._o._data_swapped = True
         self._o._yd = self._o._to_device(value)
 
     @property
@@ -151,6 +153,9 @@ class reconstructor(_solvers.HostDriver):
         random.seed(seed)
         input_dim = np.ndim(y)
         self.X, self.y = gprutils.prepare_training_data(X, y, precision=self.precision)
+        # where the training rows sit in y as given (row-major): what loo(as_grid=True) scatters its results back to
+        self._obs_mask = ~np.isnan(np.asarray(y, dtype=np.float64))
+        self._data_swapped = False                      # model.X / model.y replaced: the rows no longer belong to that grid
         self._kernel_name = kernel
         structured = bool(kwargs.get("structured", False))
         border = kwargs.get("_border")       # set by skreconstructor on an incomplete grid (gprutils.border_blocks)
@@ -308,6 +313,37 @@ class reconstructor(_solvers.HostDriver):
         returns numpy arrays shaped like the grid (gpr.py:219-255)."""
         mean_h, sd_h, self._last_pred = self._predict_host(Xtest, kwargs, lambda: self._posterior(self._solver.predict_grid))
         return mean_h, sd_h
+
+    def loo(self, as_grid=True):
+        """Leave-one-out cross-validation at the current hyper-parameters, from ONE factorisation:
+        ``(mean, sd, score)`` with ``mean[i]``, ``sd[i]`` the prediction of observation i from all the others (noise
+        included, the convention of ``predict``) and ``score = {"elpd": sum_i log N(y_i | mean_i, sd_i^2), "rmse":
+        sqrt(sum_i (y_i - mean_i)^2 / n), "n": n}`` -- a held-out measure that, unlike the training loss, is comparable
+        across kernels and does not reward fitting the noise.  Costs less than one training iteration.
+
+        ``as_grid=True``: arrays of the shape of ``y`` as given to the constructor, NaN where ``y`` was NaN (ValueError once
+        the data were replaced through ``model.X`` / ``model.y``); ``as_grid=False``: flat arrays in the training rows'
+        order.  dtype as ``predict``.  Dense models in either precision, and double-precision structured models on a complete grid (Kronecker, reflection
+        blocks); sparse, border and column models raise NotImplementedError with the reason."""
+        self._check_data()
+        N = self._yd.shape[0]
+        if as_grid and (self._data_swapped or int(self._obs_mask.sum()) != N):
+            raise ValueError("loo(as_grid=True): the training data were replaced through model.X / model.y and no longer "
+                             "belong to the grid of the constructor's y; use as_grid=False")
+        mean = torch.empty((N,), dtype=_F64, device=self._dev)
+        var = torch.empty((N,), dtype=_F64, device=self._dev)
+        score = torch.empty((2,), dtype=_F64, device=self._dev)
+        _lib.check(self._solver.loo(self, mean, var, score))
+        elpd, sse = score.cpu().tolist()
+        out = []
+        for t in (mean, var.sqrt()):
+            flat = t.cpu().numpy().astype(self._np_out, copy=False)
+            if as_grid:
+                full = np.full(self._obs_mask.shape, np.nan, dtype=self._np_out)
+                full[self._obs_mask] = flat
+                flat = full
+            out.append(flat)
+        return out[0], out[1], {"elpd": elpd, "rmse": float(np.sqrt(sse / N)), "n": N}
 
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no

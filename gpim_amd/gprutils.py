@@ -256,8 +256,13 @@ def reflection_blocks(X, y, axes):
     fund_flat = np.ravel_multi_index(tuple(full[k][fund] for k in range(d)), y.shape).reshape(-1)
     rep_idx = tuple(np.minimum(full[k], y.shape[k] - 1 - full[k]) if k in dims else full[k] for k in range(d))
     rep = np.ravel_multi_index(rep_idx, fshape).reshape(-1)
+    # the reflections that take a grid point's representative to it: bit j = the j-th reflected axis (the numbering of the
+    # sign patterns b above); a point on that axis' mirror plane has 0 (leave-one-out combines the blocks with chi_b(sgn))
+    sgn = np.zeros(y.shape, dtype=np.int64)
+    for j, k in enumerate(dims):
+        sgn |= (full[k] > y.shape[k] - 1 - full[k]).astype(np.int64) << j
     return {"mask": mask, "twoc": twoc, "B": B, "Xq": Xq, "ys": ys, "wts": wts if nplanes.any() else None,
-            "n_total": int(y.size), "dims": dims, "fund_flat": fund_flat, "rep": rep}
+            "n_total": int(y.size), "dims": dims, "fund_flat": fund_flat, "rep": rep, "sgn": sgn.reshape(-1)}
 
 
 def reflection_blocks_multi(X, Y, axes):

@@ -769,6 +769,34 @@ int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const d
 int gpimhip_refl_sums(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, int32_t B,
                       const double* u, double* sums_out);
 
+/* Leave-one-out cross-validation from one factorisation.  With S = K + (noise + jitter) I,
+ * alpha = S^-1 y and d_i = [S^-1]_ii, the prediction of observation i from the other N - 1 is
+ *   mean_out[i] = y_i - alpha_i / d_i        var_out[i] = max(1 / d_i - (noise + jitter), 0) + noise
+ * (the convention of the predict entries: the jitter belongs to the training matrix, not to the reported variance) and
+ *   score_out = [ sum_i log N(y_i | mean_i, var_i),  sum_i (y_i - mean_i)^2 ].
+ * One factorisation and triangular inverse -- the state a prediction starts from -- then d = the column sums of squares of
+ * L^-1: one pass over N^2 / 2 entries.  No K^-1 product, no gradient contraction: less than one training iteration.  Fixed
+ * summation order: two calls give the same bits.  mean_out, var_out (N doubles) and score_out (2 doubles): device.
+ *   gpimhip_loo_exact           the dense model (arguments of gpimhip_predict_exact) on double- and single-precision
+ *                               handles, through the general engine at every N; not in reflection mode (E_BADARG)
+ *   gpimhip_loo_exact_batched   the reflection blocks (arguments of gpimhip_predict_exact_batched; reflection mode with
+ *                               n_total set): the blocks' diagonals in one launch, combined in grid space.  rep[i] (device
+ *                               int32, n_total): the row of grid point i's representative in the fundamental domain; sgn[i]:
+ *                               the reflections that take the representative to i, bit j = the j-th reflected dimension in
+ *                               ascending order (0 for a point on that mirror plane); y_grid: the n_total observations in
+ *                               grid order.  Outputs: n_total doubles.  With a border set (the missing points couple the
+ *                               blocks), a shard, or on a single-precision handle: E_BADARG with a message.
+ *   gpimhip_loo_kron            the Kronecker model (arguments of gpimhip_predict_kron without the test grid):
+ *                               diag(S^-1) = ((x) Q_i o Q_i) (1 / D) by mode products.  Double-precision handles.
+ * A matrix that is not positive definite: GPIMHIP_E_NOT_PD, as the predict entries. */
+int gpimhip_loo_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                      const double* u, double* mean_out, double* var_out, double* score_out);
+int gpimhip_loo_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t x_stride, const double* y,
+                              int64_t N, int32_t B, const double* u, const int32_t* rep, const int32_t* sgn,
+                              const double* y_grid, double* mean_out, double* var_out, double* score_out);
+int gpimhip_loo_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
+                     const double* y, const double* u, double* mean_out, double* var_out, double* score_out);
+
 /* Batch thinning of boptimizer.update_points (gpim/gpbayes/boptim.py:326-376): among n <= 1024 ranked
  * candidates (vals, flat grid indices into a d-dimensional grid of the given shape) repeatedly keep the
  * largest remaining value and drop every candidate within Euclidean index distance <= dscale of it
