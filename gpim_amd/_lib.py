@@ -205,6 +205,9 @@ _PROTOS = {
                                                  ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "gpimhip_loo_kron": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), ctypes.c_int32,
                                         ctypes.POINTER(ctypes.c_int32), c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    # integrated variance reduction: the predict entry's head, then (weights, mask, mean_out, sd_out, acq_out)
+    "gpimhip_ivr_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
+                                         c_dp, ctypes.c_int64, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "gpimhip_acquire_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
                                              c_dp, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_dp]),

@@ -182,6 +182,21 @@ class Dense:
             self._loo_refused("the structured solvers compute in double from float32 inputs, a mix that leave-one-out has no "
                               "stated accuracy for: build the model with precision='double'")
 
+    no_ivr = None                                       # why a path has no integrated variance reduction
+
+    def ivr(self, o, Xs, weights, mask, mean, sd, acq):
+        """Integrated variance reduction at the rows Xs: acq[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter) with C the
+        latent posterior covariance of the rows, and their posterior (mean, sd) (csrc/ivr.hip).
+        weights, mask: device tensors of Xs.shape[0] doubles or None.  Dense double-precision models only."""
+        if self.no_ivr:
+            raise NotImplementedError("ivr(): the %s solver has no integrated variance reduction -- %s"
+                                      % (type(self).__name__, self.no_ivr))
+        if o.precision == "single":
+            raise NotImplementedError("ivr(): C = K** - W^T W cancels to the posterior variance, which single precision does "
+                                      "not resolve: build the model with precision='double'")
+        return o._handle.lib.gpimhip_ivr_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                               Xs.shape[0], ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
+
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:
         the gate of _sampling.Joint refuses the other paths before a solver is asked."""
@@ -238,6 +253,7 @@ class Sparse(Dense):
     sparse = True
     no_loo = ("the variational (VFE) posterior conditions on inducing points, not on the observations: dropping one "
               "observation has no closed form in its factors")
+    no_ivr = "the posterior conditions on inducing points"
 
     def fit(self, o, lr, T, hist, loss):
         hist_xu = torch.empty((max(T, 1), o._n_ind, o._spec.dim), dtype=_F64, device=o._dev)
@@ -258,6 +274,7 @@ class Sparse(Dense):
 class Kron(Dense):
     """Exact GP through the Kronecker structure of the RBF covariance on a complete product grid (csrc/kron.hip)."""
     structured = True
+    no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
 
     def __init__(self, axes, axes_n):
         self.axes, self.axes_n = axes, axes_n
@@ -315,6 +332,7 @@ class Columns(Dense):
     and the posterior are those of ``Dense`` on the same observations."""
     structured = True
     _NO_DRAWS = "solver='columns' draws with method='columns' only"
+    no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
     no_loo = ("solver='columns': diag(S^-1) of the dense-by-Kronecker blocks mixes every block's diagonal through the "
               "complete axes' eigenvectors, which is not built")
 
@@ -462,6 +480,7 @@ class Reflection(Dense):
     hyper-parameters (gprutils.reflection_blocks; csrc/engine.hip: kmat_refl_kernel).  With ``border``: the blocks of the
     completed grid plus a border for its missing points (gprutils.border_blocks; csrc/border.hip)."""
     symm = True
+    no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
 
     def __init__(self, S, border=False):
         self.S, self.border, self.blocks, self.perm_d = S, border, None, None

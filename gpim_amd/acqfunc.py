@@ -186,3 +186,51 @@ def thompson_sampling(gpmodel, X_full, **kwargs):
     gpmodel._last_acq = acq_d
     host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(gpmodel._np_out, copy=False)
     return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))
+
+
+def ivr_on_device(gpmodel, Xf_d, weights_d=None, mask_d=None):
+    """Integrated variance reduction (ALC) over the device rows ``Xf_d``: device tensors (acq, mean, sd) with
+    ``acq[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter)``, C the latent posterior covariance of the rows -- how
+    much the (weighted) total posterior variance of the rows drops when row j is measured -- and (mean, sd) the posterior of
+    ``predict``.  ``weights_d``: (M,) device weights >= 0 of the integral (None: all 1); ``mask_d``: (M,) device mask of
+    1 / NaN multiplied into ``acq`` (it excludes candidates, it does not change the integral).  One library call
+    (gpimhip_ivr_exact).  Dense double-precision models only; the rows must be finite."""
+    gpmodel._check_data()
+    if not bool(torch.isfinite(Xf_d).all()):
+        raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+    M = Xf_d.shape[0]
+    for name, t in (("weights", weights_d), ("mask", mask_d)):
+        if t is not None and (t.dim() != 1 or t.numel() != M or t.dtype != _F64 or not t.is_contiguous()):
+            raise ValueError("ivr: %s must be a contiguous float64 device vector of %d entries" % (name, M))
+    mean_d = torch.empty((M,), dtype=_F64, device=Xf_d.device)
+    sd_d = torch.empty_like(mean_d)
+    acq_d = torch.empty_like(mean_d)
+    _lib.check(gpmodel._solver.ivr(gpmodel, Xf_d, weights_d, mask_d, mean_d, sd_d, acq_d))
+    return acq_d, mean_d, sd_d
+
+
+def _ivr_weights(weights, shape, dev):
+    """``weights`` (None or an array of the grid's shape, finite and >= 0) as a flat device vector."""
+    if weights is None:
+        return None
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != tuple(shape):
+        raise ValueError("ivr: weights must have the shape of the test grid %s; got %s" % (tuple(shape), w.shape))
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("ivr: weights must be finite and >= 0")
+    return torch.from_numpy(np.ascontiguousarray(w).reshape(-1)).to(dev)
+
+
+def integrated_variance_reduction(gpmodel, X_full, X_sparse=None, **kwargs):
+    """Integrated variance reduction (ALC): for every grid point, how much the total posterior variance of the whole grid
+    drops when that point is measured.  kwargs: ``weights`` (array of the grid's shape, >= 0: the integral's weights).
+    ``X_sparse`` is not used (the signature of the other acquisition functions, so that this one also serves as a custom
+    callable of ``boptimizer``).  ``gpmodel`` is a dense double-precision ``gpim_amd.reconstructor``."""
+    if not hasattr(gpmodel, "_solver") or not hasattr(gpmodel._solver, "ivr"):
+        raise NotImplementedError("integrated_variance_reduction needs a gpim_amd.reconstructor")
+    shape = tuple(np.shape(X_full)[1:])
+    Xf = gpmodel._to_device(_rows(X_full, gpmodel.precision))
+    acq_d, mean_d, sd_d = ivr_on_device(gpmodel, Xf, _ivr_weights(kwargs.get("weights"), shape, gpmodel._dev))
+    gpmodel._last_acq = acq_d
+    host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(gpmodel._np_out, copy=False)
+    return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))

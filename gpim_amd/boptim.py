@@ -76,7 +76,10 @@ class boptimizer:
     every observation), with (mean, sd) from the ordinary prediction.  With ``batch_update=True``, ``ts_batch='draws'``
     takes ``batch_size`` draws in one call and sends their maximisers -- a draw whose maximiser an earlier draw has taken
     contributes its best remaining point -- through ``update_points``; the default ``ts_batch='topk'`` keeps the top
-    ``batch_size`` of a single draw.  ``shard_candidates=True`` (with torch.distributed initialised, one process
+    ``batch_size`` of a single draw.  ``acquisition_function='ivr'`` is integrated variance reduction (ALC): every candidate's
+    value is the drop of the total posterior variance of the whole grid when it is measured (reconstructor.ivr); optional
+    ``ivr_weights`` (array of the grid's shape, >= 0) weights the integral, ``mask`` excludes candidates only; dense
+    double-precision surrogates only.  ``shard_candidates=True`` (with torch.distributed initialised, one process
     per GPU) makes every rank sweep only its contiguous block of the test grid; an all-gather of
     each rank's top-``batch_size`` (value, index) pairs gives all ranks the same global ranking
     (SURVEY 8(e)).  Training stays replicated -- it is deterministic, so all ranks hold the same
@@ -139,6 +142,15 @@ class boptimizer:
             self.surrogate_model._sample_supported()
             # the draws of all exploration steps come from this generator: a run is reproducible from `seed`
             self._ts_generator = torch.Generator(self.surrogate_model._dev).manual_seed(seed)
+        self._ivr_weights_d = None
+        if acquisition_function == 'ivr':
+            if self.shard_candidates:
+                raise NotImplementedError("acquisition_function='ivr' with shard_candidates=True: every candidate's value "
+                                          "integrates over the whole grid, the covariance does not split over candidate blocks")
+            sm = self.surrogate_model
+            if sm._solver.no_ivr or sm.precision == "single":
+                sm._solver.ivr(sm, None, None, None, None, None, None)        # raises NotImplementedError with the reason
+            self._ivr_weights_d = acqfunc._ivr_weights(kwargs.get("ivr_weights"), tuple(np.shape(X_full)[1:]), sm._dev)
         self.indices_all, self.vals_all = [], []
         self.target_func_vals, self.gp_predictions = [y_seed.copy()], _LazyMaps()
         self._mask_d = None
@@ -314,6 +326,17 @@ class boptimizer:
                 vals_list, indices_list = self._rank_draws(acq_d.reshape(int(self.batch_size), -1), grid_shape)
             else:
                 vals_list, indices_list = self._rank_device(acq_d, grid_shape)
+        elif af == 'ivr':
+            # integrated variance reduction: the map, mean and sd from one library call; the mask is multiplied in on the
+            # device (it excludes candidates, the integral runs over the whole grid) and the map is ranked there
+            if self._Xfull_d is None:
+                self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
+            grid_shape = tuple(np.shape(self.X_full)[1:])
+            acq_d, mean_d, sd_d = acqfunc.ivr_on_device(sm, self._Xfull_d, weights_d=self._ivr_weights_d,
+                                                        mask_d=self._device_mask(self._Xfull_d.shape[0]))
+            mean_d, sd_d = self._retain_maps(mean_d, sd_d)
+            self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
+            vals_list, indices_list = self._rank_device(acq_d, grid_shape, masked=True)
         elif isinstance(af, types.FunctionType):
             acq, pred = af(sm, self.X_full, self.X_sparse)
             sm._last_acq = None
@@ -321,7 +344,7 @@ class boptimizer:
             vals_list, indices_list = self._rank(np.asarray(acq))
         else:
             raise NotImplementedError(
-                "Choose between 'cb', 'ei', 'poi' and 'ts' acquisition functions or define your own")
+                "Choose between 'cb', 'ei', 'poi', 'ts' and 'ivr' acquisition functions or define your own")
         if not self.batch_update:
             return vals_list, indices_list
         radius = self.batch_dscale

@@ -766,6 +766,7 @@ int gpimhip_set_precision(gpimhip_handle h, int32_t bits) {
     ws_release_matrix(h);               // sized by the element type
     ws_release_predict(h);
     sample_release(h);
+    ivr_release(h);
     h->fp32 = want;
     return GPIMHIP_OK;
 }
@@ -781,6 +782,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     sm_release(h);
     border_release(h);
     sample_release(h);
+    ivr_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
     dev_release(h, h->keys, h->sel_scratch, h->acq_tmp, h->refine, h->bc, h->theta1, h->info);

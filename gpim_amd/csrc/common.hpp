@@ -227,6 +227,9 @@ struct gpimhip_ctx {
     void* border = nullptr;
     // joint posterior draws: the (N + M)^2 matrix and its factorisation context, owned by draws.hip (SampleWs); sample_release()
     void* sample = nullptr;
+    // integrated variance reduction: W = L^-1 K*, the lower tiles of the posterior covariance on the test grid and the partial
+    // column sums, owned by ivr.hip (IvrWs); ivr_release()
+    void* ivr = nullptr;
     DevBuf<double> refine;          // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
 };
@@ -357,6 +360,8 @@ PredictFamily stationary_family(gpimhip_ctx* h, const gpimhip_model_t* m, const 
 // draws.hip
 void sample_release(gpimhip_ctx* h);
 int64_t sample_bytes(const gpimhip_ctx* h);
+// ivr.hip
+void ivr_release(gpimhip_ctx* h);
 // The preamble of a fit call: info[1] = "completed" = huge until a failure, fit_completed = T and, for T > 0, the
 // bias-correction table, then the Adam state (adam_bytes at adam_m and, where the two halves are buffers of their own, at
 // adam_v) and the iteration counter zeroed.  What a fit of T == 0 returns is the caller's business.

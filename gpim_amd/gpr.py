@@ -345,6 +345,26 @@ class reconstructor(_solvers.HostDriver):
             out.append(flat)
         return out[0], out[1], {"elpd": elpd, "rmse": float(np.sqrt(sse / N)), "n": N}
 
+    def ivr(self, Xtest=None, weights=None):
+        """Integrated variance reduction (ALC, the active-learning criterion of Cohn) on the test grid, at the current
+        hyper-parameters: ``(ivr, mean, sd)``, numpy arrays of the grid's shape.  ``ivr[j] = sum_m w_m C_mj^2 / (C_jj +
+        noise + jitter)`` with C the latent posterior covariance of the grid: the drop of the (weighted) total posterior
+        variance of the whole grid when point j is measured -- the acquisition for the best reconstruction from the
+        fewest measurements (the largest sd sits at the edges, where a measurement tells about the fewest other pixels).
+        ``mean``, ``sd``: as ``predict``.  ``Xtest`` as in ``predict`` (finite); ``weights``: None or an array of the
+        grid's shape, finite and >= 0 (ValueError otherwise).  Costs one product of M^2 N flop and M^2 doubles of device
+        memory for M grid points.  Dense double-precision models only: sparse, structured and
+        single-precision models raise NotImplementedError with the reason."""
+        from . import acqfunc
+        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+            raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        self._resolve_test_grid(Xtest)
+        shape = tuple(self.fulldims)
+        acq_d, mean_d, sd_d = acqfunc.ivr_on_device(self, self._Xtest_d, acqfunc._ivr_weights(weights, shape, self._dev))
+        self._last_pred = (mean_d, sd_d)
+        host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(self._np_out, copy=False)
+        return host[0].reshape(shape), host[1].reshape(shape), host[2].reshape(shape)
+
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no
         change of the stored test grid.  Internal: the device-resident acquisition path of boptimizer."""

@@ -57,6 +57,10 @@ class skreconstructor(reconstructor):
                          _columns=blocks if solver == "columns" else None, **kwargs)
         self.solver = solver
 
+    def ivr(self, *args, **kwargs):
+        raise NotImplementedError("ivr(): integrated variance reduction belongs to the dense exact GP of reconstructor; "
+                                  "skreconstructor models grids through structured solvers")
+
     @staticmethod
     def _choose_solver(X, y, kernel):
         """('kronecker' | 'reflection', None) on a complete grid; on an incomplete one ('border', border_blocks(X, y)) when

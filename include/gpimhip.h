@@ -797,6 +797,28 @@ int gpimhip_loo_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, const 
 int gpimhip_loo_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
                      const double* y, const double* u, double* mean_out, double* var_out, double* score_out);
 
+/* Integrated variance reduction (ALC, the active-learning criterion of Cohn) over the M rows of a test grid Xs (M x d,
+ * finite: the caller's contract, as for gpimhip_sample_exact) -- DESIGN.md section 26.  With S = K + (noise + jitter) I,
+ * W = L^-1 K(X, Xs) and C = K(Xs, Xs) - W^T W, the latent posterior covariance on the grid,
+ *   acq_out[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter)
+ * = sum_m w_m (latent variance at m before - after measuring candidate j): a refit puts the jitter on the new point's
+ * diagonal too, so the identity is exact.  The model's state at u through the general engine at every N, W with the tile
+ * engine's NN store layout, the lower tiles of C by one TN launch (M^2 N flop, not done for the upper half), then one
+ * pass that reads every stored entry of C once.  Fixed summation order, no atomics: two calls give the same bits.
+ *   weights   M doubles >= 0 (device) or NULL (all 1): the integral's weight of grid point m
+ *   mask      M doubles of 1 / NaN (device) or NULL, multiplied in as gpimhip_acq does: excludes candidates only
+ *   mean_out, sd_out   M doubles each or NULL: the posterior of gpimhip_predict_exact at Xs (sd includes the noise,
+ *                      excludes the jitter)
+ *   acq_out   M doubles (device)
+ * W (N x M), C (M x M) and the partial sums belong to this entry point (grow-only, counted by gpimhip_workspace_bytes,
+ * released by gpimhip_destroy / gpimhip_set_precision); the matrices of fit / predict are not resized.  An allocation
+ * that fails: GPIMHIP_E_NOMEM, nothing enqueued.  Double-precision handles outside reflection, border and shard modes
+ * only; these, NULL arguments, N < 1 or M < 1 -> GPIMHIP_E_BADARG with a reason in gpimhip_last_error().
+ * Synchronises at the end (to report NOT_PD). */
+int gpimhip_ivr_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                      const double* u, const double* Xs, int64_t M, const double* weights, const double* mask,
+                      double* mean_out, double* sd_out, double* acq_out);
+
 /* Batch thinning of boptimizer.update_points (gpim/gpbayes/boptim.py:326-376): among n <= 1024 ranked
  * candidates (vals, flat grid indices into a d-dimensional grid of the given shape) repeatedly keep the
  * largest remaining value and drop every candidate within Euclidean index distance <= dscale of it
