@@ -208,6 +208,10 @@ _PROTOS = {
     # integrated variance reduction: the predict entry's head, then (weights, mask, mean_out, sd_out, acq_out)
     "gpimhip_ivr_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
                                          c_dp, ctypes.c_int64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    # the greedy batch: ... (weights, mask, q, mean_out, sd_out, maps_out, sd_after_out, idx_out, gain_out, count_out)
+    "gpimhip_ivr_greedy": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
+                                          c_dp, ctypes.c_int64, c_dp, c_dp, ctypes.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp,
+                                          c_dp]),
     "gpimhip_acquire_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
                                              c_dp, c_dp, ctypes.c_int64, c_dp, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_dp]),

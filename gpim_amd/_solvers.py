@@ -188,14 +188,26 @@ class Dense:
         """Integrated variance reduction at the rows Xs: acq[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter) with C the
         latent posterior covariance of the rows, and their posterior (mean, sd) (csrc/ivr.hip).
         weights, mask: device tensors of Xs.shape[0] doubles or None.  Dense double-precision models only."""
+        self._ivr_supported(o)
+        return o._handle.lib.gpimhip_ivr_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                               Xs.shape[0], ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
+
+    def _ivr_supported(self, o):
         if self.no_ivr:
             raise NotImplementedError("ivr(): the %s solver has no integrated variance reduction -- %s"
                                       % (type(self).__name__, self.no_ivr))
         if o.precision == "single":
             raise NotImplementedError("ivr(): C = K** - W^T W cancels to the posterior variance, which single precision does "
                                       "not resolve: build the model with precision='double'")
-        return o._handle.lib.gpimhip_ivr_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
-                                               Xs.shape[0], ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
+
+    def ivr_greedy(self, o, Xs, weights, mask, q, mean, sd, maps, sd_after, idx, gain, count):
+        """A greedy batch of q picks by integrated variance reduction at the rows Xs: pick r maximises the map of the
+        covariance conditioned on picks 0 .. r - 1 (csrc/ivr.hip: gpimhip_ivr_greedy).  maps (q, M),
+        sd_after (M), idx, gain (q), count (1): device tensors; the rest as ``ivr``.  Dense double-precision models only."""
+        self._ivr_supported(o)
+        return o._handle.lib.gpimhip_ivr_greedy(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                                Xs.shape[0], ptr(weights), ptr(mask), int(q), ptr(mean), ptr(sd), ptr(maps),
+                                                ptr(sd_after), ptr(idx), ptr(gain), ptr(count))
 
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:

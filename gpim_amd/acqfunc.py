@@ -195,6 +195,16 @@ def ivr_on_device(gpmodel, Xf_d, weights_d=None, mask_d=None):
     ``predict``.  ``weights_d``: (M,) device weights >= 0 of the integral (None: all 1); ``mask_d``: (M,) device mask of
     1 / NaN multiplied into ``acq`` (it excludes candidates, it does not change the integral).  One library call
     (gpimhip_ivr_exact).  Dense double-precision models only; the rows must be finite."""
+    M = _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d)
+    mean_d = torch.empty((M,), dtype=_F64, device=Xf_d.device)
+    sd_d = torch.empty_like(mean_d)
+    acq_d = torch.empty_like(mean_d)
+    _lib.check(gpmodel._solver.ivr(gpmodel, Xf_d, weights_d, mask_d, mean_d, sd_d, acq_d))
+    return acq_d, mean_d, sd_d
+
+
+def _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d):
+    """The checks of ``ivr_on_device`` and ``ivr_greedy_on_device``; returns the number of rows."""
     gpmodel._check_data()
     if not bool(torch.isfinite(Xf_d).all()):
         raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
@@ -202,11 +212,44 @@ def ivr_on_device(gpmodel, Xf_d, weights_d=None, mask_d=None):
     for name, t in (("weights", weights_d), ("mask", mask_d)):
         if t is not None and (t.dim() != 1 or t.numel() != M or t.dtype != _F64 or not t.is_contiguous()):
             raise ValueError("ivr: %s must be a contiguous float64 device vector of %d entries" % (name, M))
-    mean_d = torch.empty((M,), dtype=_F64, device=Xf_d.device)
-    sd_d = torch.empty_like(mean_d)
-    acq_d = torch.empty_like(mean_d)
-    _lib.check(gpmodel._solver.ivr(gpmodel, Xf_d, weights_d, mask_d, mean_d, sd_d, acq_d))
-    return acq_d, mean_d, sd_d
+    return M
+
+
+def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None):
+    """A greedy batch of ``q`` picks by integrated variance reduction over the device rows ``Xf_d``: device tensors
+    ``(idx, gain, count, maps, mean, sd, sd_after)``.  A GP's variance does not depend on the measured values, so pick r
+    is the maximiser of the map of the covariance conditioned on picks 0 .. r - 1 (C <- C - c c^T / (C_pp + noise + jitter),
+    c = C[:, p]): ``idx`` (q,) int64 flat indices in pick order, ``gain`` (q,) the map values -- the drop of the (weighted)
+    total posterior variance each pick adds to the batch's -- ``count`` (1,) int64 the picks made (fewer than q when the
+    unmasked candidates run out; then idx = -1 and gain = NaN behind them), ``maps`` (q, M) the map each pick was taken from
+    (NaN at masked candidates and earlier picks; row 0 is ``ivr_on_device``'s map, bit for bit), ``mean``, ``sd`` the posterior
+    before the batch, ``sd_after`` the sd once the batch is measured.  Arguments as ``ivr_on_device``; 1 <= q <= M.  One
+    library call (gpimhip_ivr_greedy).  Dense double-precision models only."""
+    M = _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d)
+    q = int(q)
+    if q < 1 or q > M:
+        raise ValueError("ivr: a batch of %d picks from %d candidates (1 <= q <= M)" % (q, M))
+    dev = Xf_d.device
+    mean_d, sd_d, sd_after_d = (torch.empty((M,), dtype=_F64, device=dev) for _ in range(3))
+    maps_d = torch.empty((q, M), dtype=_F64, device=dev)
+    gain_d = torch.empty((q,), dtype=_F64, device=dev)
+    idx_d = torch.empty((q,), dtype=torch.int64, device=dev)
+    count_d = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(gpmodel._solver.ivr_greedy(gpmodel, Xf_d, weights_d, mask_d, q, mean_d, sd_d, maps_d, sd_after_d, idx_d,
+                                          gain_d, count_d))
+    return idx_d, gain_d, count_d, maps_d, mean_d, sd_d, sd_after_d
+
+
+def _ivr_mask(mask, shape, dev):
+    """``mask`` (None or an array of the grid's shape holding 1 / NaN) as a flat device vector."""
+    if mask is None:
+        return None
+    k = np.asarray(mask, dtype=np.float64)
+    if k.shape != tuple(shape):
+        raise ValueError("ivr: mask must have the shape of the test grid %s; got %s" % (tuple(shape), k.shape))
+    if not (np.isnan(k) | (k == 1.0)).all():
+        raise ValueError("ivr: mask must hold 1 (a candidate) or NaN (excluded)")
+    return torch.from_numpy(np.ascontiguousarray(k).reshape(-1)).to(dev)
 
 
 def _ivr_weights(weights, shape, dev):

@@ -79,7 +79,12 @@ class boptimizer:
     ``batch_size`` of a single draw.  ``acquisition_function='ivr'`` is integrated variance reduction (ALC): every candidate's
     value is the drop of the total posterior variance of the whole grid when it is measured (reconstructor.ivr); optional
     ``ivr_weights`` (array of the grid's shape, >= 0) weights the integral, ``mask`` excludes candidates only; dense
-    double-precision surrogates only.  ``shard_candidates=True`` (with torch.distributed initialised, one process
+    double-precision surrogates only.  With ``batch_update=True``, ``ivr_batch='greedy'`` makes the batch the
+    ``batch_out_max`` greedy picks of reconstructor.ivr_batch: a GP's variance does not depend on the measured values, so
+    every pick maximises the map conditioned on the picks before it and the returned values are the drops each pick adds
+    to the batch's (no thinning by distance, no random padding; fewer points only when the unmasked candidates run out);
+    the default ``ivr_batch='thin'`` ranks one map and thins it through ``update_points`` like the other acquisition
+    functions.  ``shard_candidates=True`` (with torch.distributed initialised, one process
     per GPU) makes every rank sweep only its contiguous block of the test grid; an all-gather of
     each rank's top-``batch_size`` (value, index) pairs gives all ranks the same global ranking
     (SURVEY 8(e)).  Training stays replicated -- it is deterministic, so all ranks hold the same
@@ -143,7 +148,11 @@ class boptimizer:
             # the draws of all exploration steps come from this generator: a run is reproducible from `seed`
             self._ts_generator = torch.Generator(self.surrogate_model._dev).manual_seed(seed)
         self._ivr_weights_d = None
+        self.ivr_batch = kwargs.get("ivr_batch", "thin")
         if acquisition_function == 'ivr':
+            # (ivr_batch belongs to 'ivr' with batch_update=True alone)
+            if self.ivr_batch not in ("thin", "greedy"):
+                raise ValueError("ivr_batch must be 'thin' or 'greedy'; got %r" % (self.ivr_batch,))
             if self.shard_candidates:
                 raise NotImplementedError("acquisition_function='ivr' with shard_candidates=True: every candidate's value "
                                           "integrates over the whole grid, the covariance does not split over candidate blocks")
@@ -332,6 +341,8 @@ class boptimizer:
             if self._Xfull_d is None:
                 self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
             grid_shape = tuple(np.shape(self.X_full)[1:])
+            if self.batch_update and self.ivr_batch == 'greedy':
+                return self._next_batch_ivr_greedy(grid_shape)
             acq_d, mean_d, sd_d = acqfunc.ivr_on_device(sm, self._Xfull_d, weights_d=self._ivr_weights_d,
                                                         mask_d=self._device_mask(self._Xfull_d.shape[0]))
             mean_d, sd_d = self._retain_maps(mean_d, sd_d)
@@ -351,6 +362,23 @@ class boptimizer:
         if radius is None:
             radius = sm.model.kernel.lengthscale.mean().item()
         return self.update_points(vals_list, indices_list, radius)
+
+    def _next_batch_ivr_greedy(self, grid_shape):
+        """The ``batch_out_max`` greedy picks by integrated variance reduction and their gains, from one library call
+        (acqfunc.ivr_greedy_on_device); (mean, sd) of the step are the posterior before the batch."""
+        sm = self.surrogate_model
+        M = self._Xfull_d.shape[0]
+        q = int(min(self.batch_out_max, M))
+        idx_d, gain_d, count_d, _, mean_d, sd_d, _ = acqfunc.ivr_greedy_on_device(
+            sm, self._Xfull_d, q, weights_d=self._ivr_weights_d, mask_d=self._device_mask(M))
+        mean_d, sd_d = self._retain_maps(mean_d, sd_d)
+        self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
+        # one device-to-host copy: [count | q indices | q gains (as bits)]
+        host = torch.cat([count_d, idx_d, gain_d.view(torch.int64)]).cpu().numpy()
+        n = int(host[0])
+        flat = host[1:1 + n]
+        vals_list = host[q + 1:q + 1 + n].view(np.float64).tolist()
+        return vals_list, np.stack(np.unravel_index(flat, tuple(grid_shape)), axis=-1).tolist()
 
     def _next_point_sharded(self):
         """Acquisition sweep over this rank's block of candidates + global top-k (RCCL all-gather)."""

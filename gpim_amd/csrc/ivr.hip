@@ -1,4 +1,5 @@
-// ivr.hip -- integrated variance reduction (ALC) of the exact GP: gpimhip_ivr_exact.
+// ivr.hip -- integrated variance reduction (ALC) of the exact GP: gpimhip_ivr_exact and its greedy
+// batch, gpimhip_ivr_greedy (section 27).
 //
 // With S = K + (noise + jitter) I, W = L^-1 K(X, G) and C = K(G, G) - W^T W (the latent posterior covariance on the M rows
 // of the test grid G) measuring candidate j lowers the latent variance at grid point m by C_mj^2 / (C_jj + noise + jitter):
@@ -9,7 +10,16 @@
 //   colsq_sym_kernel   s_j = sum_m w_m C_mj^2 from lower-stored C, every stored entry read once
 //   ivr_finish_kernel  the partial sums added in their order, the quotient, sd and the mask
 // W, C and the partial sums belong to this entry (IvrWs; grow-only, charged to h->bytes).
+//
+// The greedy batch conditions C on each pick p: C <- C - g g^T with g = C[:, p] / sqrt(max(C_pp, 0) + noise + jitter) -- a
+// GP's variance does not depend on the measured value -- and takes the next map from the new C.  Per round:
+//   ivr_pick_kernel      arg-max of the round's map (NaN never, ties to the larger index), the pick leaves the live vector
+//   ivr_gather_kernel    g from lower-stored C, a launch of its own: the pass rewrites the entries it reads
+//   colsq_sym_kernel<true>   the downdate fused into the squared column sums: every stored entry read once, written once
+//   ivr_finish_kernel    with the live vector as its mask
+// All rounds are enqueued up front: the pick travels through device memory, no grid depends on it.
 #include <algorithm>
+#include <type_traits>
 #include "common.hpp"
 #include "border.hpp"
 #include "kfun.hpp"
@@ -21,6 +31,9 @@ struct IvrWs {
     DevBuf<double> C;               // mp x ldm: lower tiles of the latent posterior covariance
     DevBuf<double> part;            // (mp / 128) x mp: part[k][j] = sum over the rows m of block k of w_m C_mj^2
     DevBuf<TileDesc> tiles;         // lower tiles of an nt x nt block matrix
+    DevBuf<double> g;               // mp: the scaled column of the last pick, zero at rows >= M (gpimhip_ivr_greedy)
+    DevBuf<double> live;            // M: the user's mask or ones, NaN at the picks made so far
+    DevBuf<double> row;             // M: a round's map when the caller does not want the maps
     int nt = 0;
 };
 static IvrWs* iws(gpimhip_ctx* h) {
@@ -30,7 +43,7 @@ static IvrWs* iws(gpimhip_ctx* h) {
 void ivr_release(gpimhip_ctx* h) {
     IvrWs* w = (IvrWs*)h->ivr;
     if (!w) return;
-    dev_release(h, w->W, w->C, w->part, w->tiles);
+    dev_release(h, w->W, w->C, w->part, w->tiles, w->g, w->live, w->row);
     delete w;
     h->ivr = nullptr;
 }
@@ -45,10 +58,17 @@ void ivr_release(gpimhip_ctx* h) {
 // and both land in part[ti][ti * 128 + .].  So slot k of column j holds the contribution of the rows of block k, every
 // (k, block) slot is written by exactly one workgroup on every call, and the finisher adds the slots in increasing k: no
 // atomics, the same bits on every call.  Rows and columns >= M (the padding of C and W) are never added.
+// DOWNDATE: the entry becomes fma(-g_r, g_c, C(r, c)) before it is squared and is stored back where it was loaded from
+// (gvec: mp doubles, zero at rows >= M, so the identity padding of C survives).  Each stored entry belongs to one thread of
+// one workgroup: no race.  Of the diagonal tile the 32-column groups wholly above the diagonal stay unread and unwritten;
+// the entries above the diagonal inside the other groups are downdated with the rest and, as before, never added.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void colsq_sym_kernel(const double* __restrict__ C, int64_t ld, int64_t M, int64_t mp,
-                                                        const double* __restrict__ wts, double* __restrict__ part) {
+template <bool DOWNDATE>
+__global__ __launch_bounds__(256) void colsq_sym_kernel(std::conditional_t<DOWNDATE, double*, const double*> __restrict__ C,
+                                                        int64_t ld, int64_t M, int64_t mp, const double* __restrict__ wts,
+                                                        double* __restrict__ part, const double* __restrict__ gvec) {
     __shared__ double wr[128], wc[128];
+    __shared__ double gr[DOWNDATE ? 128 : 1], gc[DOWNDATE ? 128 : 1];   // (not allocated where they are not used)
     __shared__ double cred[16][128 + 1], rred[16][128 + 1];
     int ti, tj;
     {
@@ -66,6 +86,7 @@ __global__ __launch_bounds__(256) void colsq_sym_kernel(const double* __restrict
         const int64_t g = (tid < 128 ? r0 : c0) + loc;
         const double v = g < M ? (wts ? wts[g] : 1.0) : 0.0;
         (tid < 128 ? wr : wc)[loc] = v;
+        if constexpr (DOWNDATE) (tid < 128 ? gr : gc)[loc] = gvec[g];   // (g < mp: the tile lies inside the padded order)
     }
     __syncthreads();
     const bool diag = ti == tj;
@@ -73,7 +94,7 @@ __global__ __launch_bounds__(256) void colsq_sym_kernel(const double* __restrict
     double cs[8], rs[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) cs[k] = rs[k] = 0.0;
-    const double* base = C + r0 * ld + c0 + 2 * tx;
+    const auto base = C + r0 * ld + c0 + 2 * tx;
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
         const int r = ty + 16 * rr;
@@ -81,7 +102,14 @@ __global__ __launch_bounds__(256) void colsq_sym_kernel(const double* __restrict
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
             if (diag && 16 * rr + 15 < 32 * cc) continue;               // wholly above the diagonal (the whole workgroup)
-            const d2 v = *reinterpret_cast<const d2*>(base + (int64_t)r * ld + 32 * cc);
+            d2 v = *reinterpret_cast<const d2*>(base + (int64_t)r * ld + 32 * cc);
+            if constexpr (DOWNDATE) {
+                // the 16-byte store that matches the load; g = 0 on the padding, which so keeps what it holds
+                const double mg = -gr[r];
+                v[0] = fma(mg, gc[2 * tx + 32 * cc], v[0]);
+                v[1] = fma(mg, gc[2 * tx + 32 * cc + 1], v[1]);
+                *reinterpret_cast<d2*>(base + (int64_t)r * ld + 32 * cc) = v;
+            }
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int c = 2 * tx + 32 * cc + e;
@@ -148,6 +176,75 @@ __global__ __launch_bounds__(256) void ivr_finish_kernel(const double* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The greedy batch's three small kernels (gpimhip_ivr_greedy).
+// ------------------------------------------------------------------------------------------
+// live[j] = the user's mask, or 1
+__global__ __launch_bounds__(256) void ivr_live_init_kernel(const double* __restrict__ mask, int64_t M, double* __restrict__ live) {
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < M; j += (int64_t)gridDim.x * 256) live[j] = mask ? mask[j] : 1.0;
+}
+
+// Pick r: the largest entry of the round's map that is not NaN, ties to the larger flat index (gpimhip_topk's order).  One
+// workgroup; every thread scans its strided share in increasing index, the 1024 candidates are merged by the same rule, so the
+// result does not depend on the merge order.  idx_out[r] = the pick or -1, gain_out[r] = its value or NaN; a pick leaves the
+// live vector and sets count = r + 1 (round 0 always writes the count).  The later launches read the pick from idx_out[r].
+__global__ __launch_bounds__(1024) void ivr_pick_kernel(const double* __restrict__ map, int64_t M, int r, double* __restrict__ live,
+                                                        int64_t* __restrict__ idx_out, double* __restrict__ gain_out,
+                                                        int64_t* __restrict__ count_out) {
+    __shared__ double bv[1024];
+    __shared__ int64_t bi[1024];
+    const int tid = threadIdx.x;
+    double v = 0.0;
+    int64_t at = -1;
+    for (int64_t j = tid; j < M; j += 1024) {
+        const double a = map[j];
+        if (a == a && (at < 0 || a >= v)) { v = a; at = j; }
+    }
+    bv[tid] = v;
+    bi[tid] = at;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (tid < s) {
+            const double v2 = bv[tid + s];
+            const int64_t i2 = bi[tid + s], i1 = bi[tid];
+            if (i2 >= 0 && (i1 < 0 || v2 > bv[tid] || (v2 == bv[tid] && i2 > i1))) { bv[tid] = v2; bi[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int64_t p = bi[0];
+        idx_out[r] = p;
+        gain_out[r] = p >= 0 ? bv[0] : __builtin_nan("");
+        if (p >= 0) {
+            live[p] = __builtin_nan("");
+            *count_out = r + 1;
+        } else if (r == 0) {
+            *count_out = 0;
+        }
+    }
+}
+
+// g_m = C_mp / sqrt(max(C_pp, 0) + noise + jitter) for m < M from lower-stored C (C[m][p] for m >= p, C[p][m] for m < p),
+// 0 for M <= m < mp and everywhere when there was no pick (p < 0: the pass then leaves C as it is)
+__global__ __launch_bounds__(256) void ivr_gather_kernel(const double* __restrict__ C, int64_t ld, int64_t M, int64_t mp,
+                                                         const ThetaDev* __restrict__ th, const int64_t* __restrict__ pick,
+                                                         double* __restrict__ g) {
+    const int64_t p = *pick;
+    const bool on = p >= 0 && p < M;
+    const double den = on ? sqrt(clamp0_nan(C[p * ld + p]) + th->diag_add) : 1.0;
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < mp; m += (int64_t)gridDim.x * 256)
+        g[m] = on && m < M ? (m >= p ? C[m * ld + p] : C[p * ld + m]) / den : 0.0;
+}
+
+// after the last pick no pass is needed: sd_after_j = sqrt(max(C_jj - g_j^2, 0) + noise), the diagonal the pass would store
+__global__ __launch_bounds__(256) void ivr_sd_after_kernel(const double* __restrict__ C, int64_t ld, int64_t M,
+                                                           const ThetaDev* __restrict__ th, const double* __restrict__ g,
+                                                           double* __restrict__ sd_after) {
+    const double noise = th->noise;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < M; j += (int64_t)gridDim.x * 256)
+        sd_after[j] = sqrt(clamp0_nan(fma(-g[j], g[j], C[j * ld + j])) + noise);
+}
+
 // the lower tiles of an nt x nt block matrix in 8 x 8 patches (operand panels of the TN product shared in L2), every tile
 // with the k-range the launch fixes (kfix0 / kfix1)
 static int ivr_tiles_ensure(gpimhip_ctx* h, IvrWs* w, int nt) {
@@ -167,9 +264,20 @@ static int ivr_tiles_ensure(gpimhip_ctx* h, IvrWs* w, int nt) {
     return GPIMHIP_OK;
 }
 
-static int ivr_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
-                    const double* Xs, int64_t M, const double* weights, const double* mask, double* mean_out, double* sd_out,
-                    double* acq_out) {
+// what gpimhip_ivr_greedy adds to the map of round 0 (q picks; the outputs of the entry, device pointers)
+struct IvrGreedy {
+    int32_t q;
+    double *maps, *sd_after, *gain;
+    int64_t *idx, *count;
+};
+
+static inline dim3 ivr_grid(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)); }
+
+// The map of round 0 into acq_out (gpimhip_ivr_exact: greedy == nullptr, the mask multiplied in), then for a greedy batch
+// the q - 1 conditioned rounds, every launch enqueued before the one synchronisation at the end.
+static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                    const double* u, const double* Xs, int64_t M, const double* weights, const double* mask, double* mean_out,
+                    double* sd_out, double* acq_out, const IvrGreedy* greedy) {
     HIP_TRY(hipSetDevice(h->device));
     IvrWs* w = iws(h);
     const int64_t npn = pad_to(N, NB), mp = pad_to(M, NB), ldm = mp + 16;       // (no power-of-two row stride)
@@ -178,12 +286,20 @@ static int ivr_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, c
     GP_TRY(w->W.grow(h, npn * ldm));
     GP_TRY(w->C.grow(h, mp * ldm));
     GP_TRY(w->part.grow(h, (int64_t)nt * mp));
+    if (greedy) {
+        GP_TRY(w->g.grow(h, mp));
+        GP_TRY(w->live.grow(h, M));
+        if (!greedy->maps) {
+            GP_TRY(w->row.grow(h, M));
+            acq_out = w->row;
+        }
+    }
     GP_TRY(ivr_tiles_ensure(h, w, nt));
     GP_TRY(model_state_at_u(h, m, X, 0, y, N, 1, u));
     const int64_t np = h->np;
     const int nb = (int)(np / NB);
     if (np != npn) {                            // (W was sized for the padded order the workspace is expected to have)
-        gpim_set_error("gpimhip_ivr_exact: the workspace's padded order is not pad(N, 128)");
+        gpim_set_error(std::string(who) + ": the workspace's padded order is not pad(N, 128)");
         return GPIMHIP_E_BADARG;
     }
     // W = L^-1 K* chunk by chunk of the K* slab, and the mean K*^T alpha (predict_cols' launches, EPI_STORE for EPI_COLSUMSQ)
@@ -216,37 +332,97 @@ static int ivr_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, c
         g.chunk = deal_chunk(g.ntiles);
         GP_TRY(launch_gemm(h, true, true, EPI_STORE, g));
     }
-    hipLaunchKernelGGL(colsq_sym_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, h->stream, (const double*)w->C, ldm,
-                       M, mp, weights, (double*)w->part);
+    const dim3 tiles((unsigned)(nt * (nt + 1) / 2));
+    const ThetaDev* th = h->theta;
+    const double* Cc = w->C;
+    if (greedy) {
+        // the live vector stands in for the mask from round 0 on: 1 * a is a
+        hipLaunchKernelGGL(ivr_live_init_kernel, ivr_grid(M), dim3(256), 0, h->stream, mask, M, (double*)w->live);
+        HIP_TRY(hipGetLastError());
+        mask = w->live;
+    }
+    hipLaunchKernelGGL(colsq_sym_kernel<false>, tiles, dim3(256), 0, h->stream, Cc, ldm, M, mp, weights, (double*)w->part,
+                       (const double*)nullptr);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ivr_finish_kernel, dim3((unsigned)std::min<int64_t>((M + 255) / 256, 1024)), dim3(256), 0, h->stream,
-                       (const double*)w->part, nt, mp, (const double*)w->C, ldm, M, (const ThetaDev*)h->theta, mask, sd_out,
-                       acq_out);
+    hipLaunchKernelGGL(ivr_finish_kernel, ivr_grid(M), dim3(256), 0, h->stream, (const double*)w->part, nt, mp, Cc, ldm, M, th,
+                       mask, sd_out, acq_out);
     HIP_TRY(hipGetLastError());
+    for (int r = 0; greedy && r < greedy->q; ++r) {
+        double* map = greedy->maps ? greedy->maps + (int64_t)r * M : (double*)w->row;       // (round 0: acq_out)
+        if (r > 0) {
+            // the column of pick r - 1 before the pass that rewrites it, the downdate fused into the sums, the new map
+            hipLaunchKernelGGL(ivr_gather_kernel, ivr_grid(mp), dim3(256), 0, h->stream, Cc, ldm, M, mp, th,
+                               (const int64_t*)(greedy->idx + r - 1), (double*)w->g);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(colsq_sym_kernel<true>, tiles, dim3(256), 0, h->stream, (double*)w->C, ldm, M, mp, weights,
+                               (double*)w->part, (const double*)w->g);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(ivr_finish_kernel, ivr_grid(M), dim3(256), 0, h->stream, (const double*)w->part, nt, mp, Cc, ldm,
+                               M, th, mask, (double*)nullptr, map);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(ivr_pick_kernel, dim3(1), dim3(1024), 0, h->stream, (const double*)map, M, r, (double*)w->live,
+                           greedy->idx, greedy->gain, greedy->count);
+        HIP_TRY(hipGetLastError());
+    }
+    if (greedy && greedy->sd_after) {
+        hipLaunchKernelGGL(ivr_gather_kernel, ivr_grid(mp), dim3(256), 0, h->stream, Cc, ldm, M, mp, th,
+                           (const int64_t*)(greedy->idx + greedy->q - 1), (double*)w->g);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ivr_sd_after_kernel, ivr_grid(M), dim3(256), 0, h->stream, Cc, ldm, M, th, (const double*)w->g,
+                           greedy->sd_after);
+        HIP_TRY(hipGetLastError());
+    }
     return finish_and_check(h);
+}
+
+// what both entries refuse, with the reason
+static int ivr_check(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, bool pointers, int64_t N, int64_t M) {
+    if (!h || !pointers || N < 1 || M < 1) {
+        gpim_set_error(std::string(who) + ": null argument, N < 1 or M < 1");
+        return GPIMHIP_E_BADARG;
+    }
+    GP_TRY(check_model(m));
+    if (h->fp32) {
+        gpim_set_error(std::string(who) + ": C = K** - W^T W cancels to the posterior variance; needs a double-precision handle "
+                       "(gpimhip_set_precision(h, 64))");
+        return GPIMHIP_E_BADARG;
+    }
+    if (h->refl.mask || border_on(h)) {
+        gpim_set_error(std::string(who) + ": not available in reflection, border or shard mode (the cross-covariance of "
+                       "arbitrary grid points is not block-structured; the dense double-precision engine only)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (M > ((int64_t)1 << 20)) {
+        gpim_set_error(std::string(who) + ": M > 2^20 (C is M x M doubles)");
+        return GPIMHIP_E_BADARG;
+    }
+    return GPIMHIP_OK;
 }
 
 extern "C" int gpimhip_ivr_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
                                  const double* u, const double* Xs, int64_t M, const double* weights, const double* mask,
                                  double* mean_out, double* sd_out, double* acq_out) {
-    if (!h || !X || !y || !u || !Xs || !acq_out || N < 1 || M < 1) {
-        gpim_set_error("gpimhip_ivr_exact: null argument, N < 1 or M < 1");
-        return GPIMHIP_E_BADARG;
-    }
-    GP_TRY(check_model(m));
-    if (h->fp32) {
-        gpim_set_error("gpimhip_ivr_exact: C = K** - W^T W cancels to the posterior variance; needs a double-precision handle "
-                       "(gpimhip_set_precision(h, 64))");
-        return GPIMHIP_E_BADARG;
-    }
-    if (h->refl.mask || border_on(h)) {
-        gpim_set_error("gpimhip_ivr_exact: not available in reflection, border or shard mode (the cross-covariance of arbitrary "
-                       "grid points is not block-structured; the dense double-precision engine only)");
-        return GPIMHIP_E_BADARG;
-    }
-    if (M > ((int64_t)1 << 20)) {
-        gpim_set_error("gpimhip_ivr_exact: M > 2^20 (C is M x M doubles)");
-        return GPIMHIP_E_BADARG;
-    }
-    return ivr_impl(h, m, X, y, N, u, Xs, M, weights, mask, mean_out, sd_out, acq_out);
+    GP_TRY(ivr_check(h, "gpimhip_ivr_exact", m, X && y && u && Xs && acq_out, N, M));
+    return ivr_impl(h, "gpimhip_ivr_exact", m, X, y, N, u, Xs, M, weights, mask, mean_out, sd_out, acq_out, nullptr);
 }
+
+extern "C" int gpimhip_ivr_greedy(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                                  const double* u, const double* Xs, int64_t M, const double* weights, const double* mask,
+                                  int32_t q, double* mean_out, double* sd_out, double* maps_out, double* sd_after_out,
+                                  int64_t* idx_out, double* gain_out, int64_t* count_out) {
+    const char* who = "gpimhip_ivr_greedy";
+    GP_TRY(ivr_check(h, who, m, X && y && u && Xs, N, M));
+    if (q < 1 || q > M) {
+        gpim_set_error(std::string(who) + ": q = " + std::to_string(q) + " picks of M = " + std::to_string(M) +
+                       " candidates (1 <= q <= M)");
+        return GPIMHIP_E_BADARG;
+    }
+    if (!idx_out || !gain_out || !count_out) {
+        gpim_set_error(std::string(who) + ": idx_out, gain_out and count_out are not optional");
+        return GPIMHIP_E_BADARG;
+    }
+    const IvrGreedy greedy = {q, maps_out, sd_after_out, gain_out, idx_out, count_out};
+    return ivr_impl(h, who, m, X, y, N, u, Xs, M, weights, mask, mean_out, sd_out, maps_out, &greedy);      // (round 0: row 0)
+}
+

@@ -365,6 +365,38 @@ class reconstructor(_solvers.HostDriver):
         host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(self._np_out, copy=False)
         return host[0].reshape(shape), host[1].reshape(shape), host[2].reshape(shape)
 
+    def ivr_batch(self, n_points, Xtest=None, weights=None, mask=None):
+        """A batch of ``n_points`` measurements chosen greedily by integrated variance reduction (``ivr``), at the current
+        hyper-parameters: ``(points, gains, maps)``.  A GP's variance does not depend on the measured values, so the grid's
+        covariance after measuring a point is known before the measurement; every pick is the maximiser of the ``ivr`` map
+        conditioned on the picks before it, so two neighbouring maxima that explain the same pixels are not both taken.
+        ``points``: list of grid-index tuples in pick order (fewer than ``n_points`` when the unmasked candidates run out);
+        ``gains``: ndarray, the drop of the (weighted) total posterior variance each pick adds -- their sum is the batch's;
+        ``maps``: dict with ``'ivr'`` (q, *grid), q = min(n_points, grid points): the map each pick was taken from (NaN at
+        masked candidates and earlier picks, all NaN once the candidates have run out; ``maps['ivr'][0]`` is ``ivr()``'s
+        map), ``'mean'``, ``'sd'``: as ``predict``, and ``'sd_after'``: the sd once the batch is measured.  ``Xtest``, ``weights`` as in ``ivr``; ``mask``: None or an array of the grid's shape
+        holding 1 (a candidate) / NaN (excluded); it does not change the integral.  ValueError for n_points < 1, a grid that
+        is not finite, bad weights or a bad mask.  One ``ivr`` plus one pass over the stored half of the covariance per
+        further pick.  Dense double-precision models only, as ``ivr``."""
+        from . import acqfunc
+        if int(n_points) < 1:
+            raise ValueError("ivr_batch: n_points must be >= 1; got %r" % (n_points,))
+        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+            raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        self._resolve_test_grid(Xtest)
+        shape = tuple(self.fulldims)
+        q = min(int(n_points), int(self._Xtest_d.shape[0]))
+        idx_d, gain_d, count_d, maps_d, mean_d, sd_d, after_d = acqfunc.ivr_greedy_on_device(
+            self, self._Xtest_d, q, acqfunc._ivr_weights(weights, shape, self._dev), acqfunc._ivr_mask(mask, shape, self._dev))
+        self._last_pred = (mean_d, sd_d)
+        n = int(count_d.item())
+        flat = idx_d[:n].cpu().numpy()
+        points = [tuple(int(v) for v in p) for p in np.stack(np.unravel_index(flat, shape), axis=-1)]
+        host = torch.cat([maps_d, torch.stack([mean_d, sd_d, after_d])]).cpu().numpy().astype(self._np_out, copy=False)
+        maps = {"ivr": host[:q].reshape((q,) + shape), "mean": host[q].reshape(shape), "sd": host[q + 1].reshape(shape),
+                "sd_after": host[q + 2].reshape(shape)}
+        return points, gain_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
+
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no
         change of the stored test grid.  Internal: the device-resident acquisition path of boptimizer."""

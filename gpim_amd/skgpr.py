@@ -61,6 +61,8 @@ class skreconstructor(reconstructor):
         raise NotImplementedError("ivr(): integrated variance reduction belongs to the dense exact GP of reconstructor; "
                                   "skreconstructor models grids through structured solvers")
 
+    ivr_batch = ivr
+
     @staticmethod
     def _choose_solver(X, y, kernel):
         """('kronecker' | 'reflection', None) on a complete grid; on an incomplete one ('border', border_blocks(X, y)) when

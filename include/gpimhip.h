@@ -819,6 +819,32 @@ int gpimhip_ivr_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* 
                       const double* u, const double* Xs, int64_t M, const double* weights, const double* mask,
                       double* mean_out, double* sd_out, double* acq_out);
 
+/* Greedy batch of q picks by integrated variance reduction -- DESIGN.md section 27.  A GP's variance does not depend on the
+ * measured values, so after picking p the latent covariance of the grid is C - g g^T with
+ *   g = C[:, p] / sqrt(max(C_pp, 0) + noise + jitter)
+ * and the next map is gpimhip_ivr_exact's formula on the new C.  Round 0 is exactly that entry's map (mean_out, sd_out and
+ * row 0 of maps_out hold its bits); pick r is the largest entry of round r's map among the live candidates -- those the mask
+ * does not make NaN and no earlier round picked -- ties to the larger flat index, as gpimhip_topk, NaN never.  Between
+ * rounds one pass over the stored lower tiles of C applies the downdate and takes the squared column sums: every stored
+ * entry read once and written once, q - 1 passes for q picks, all launches enqueued up front (the pick travels through
+ * device memory), one synchronisation at the end.  Fixed summation order, no atomics: two calls give the same bits.
+ *   weights, mask      as gpimhip_ivr_exact: the weights weight the integral only, the mask excludes candidates only
+ *   q                  1 <= q <= M
+ *   mean_out, sd_out   M doubles each or NULL: as gpimhip_ivr_exact (the posterior BEFORE the batch)
+ *   maps_out           q x M doubles or NULL: row r = the map pick r was taken from, NaN at masked and earlier picks
+ *   sd_after_out       M doubles or NULL: sqrt(max(C_jj, 0) + noise) after all picks, the error bar once the batch is measured
+ *   idx_out, gain_out  q each (device): the flat index of pick r and its map value = the drop of the weighted total latent
+ *                      variance caused by pick r given picks 0 .. r - 1 (the gains add up to the batch's total drop)
+ *   count_out          1 int64 (device): picks made; < q when the live candidates ran out, then the remaining idx_out are -1
+ *                      and the remaining gain_out NaN
+ * The scaled column, the live vector and a scratch map row (O(M)) join gpimhip_ivr_exact's buffers under the same rules.
+ * Refuses what gpimhip_ivr_exact refuses, q < 1, q > M and NULL idx_out / gain_out / count_out: GPIMHIP_E_BADARG with a
+ * reason in gpimhip_last_error(). */
+int gpimhip_ivr_greedy(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                       const double* u, const double* Xs, int64_t M, const double* weights, const double* mask, int32_t q,
+                       double* mean_out, double* sd_out, double* maps_out, double* sd_after_out, int64_t* idx_out,
+                       double* gain_out, int64_t* count_out);
+
 /* Batch thinning of boptimizer.update_points (gpim/gpbayes/boptim.py:326-376): among n <= 1024 ranked
  * candidates (vals, flat grid indices into a d-dimensional grid of the given shape) repeatedly keep the
  * largest remaining value and drop every candidate within Euclidean index distance <= dscale of it
