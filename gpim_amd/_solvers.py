@@ -140,7 +140,7 @@ def _loss_grad(out):
 
 
 class Dense:
-    """The exact GP on the observed points (csrc/engine.hip)."""
+    """The exact GP on the observed points (csrc/engine.hip, grad.hip, predict.hip)."""
     sparse = structured = symm = border = False         # what reconstructor shows as do_sparse / do_structured / ...
     xu_rows = None                                      # host rows of the inducing-input history of the latest fit (Sparse)
 
@@ -171,7 +171,7 @@ class Dense:
 
     def loo(self, o, mean, var, score):
         """Leave-one-out predictions of the N training rows, in their order, and score = [elpd, sse] from one factorisation
-        (csrc/engine.hip: colsq_tri_kernel, loo_finish_kernel).  Double- and single-precision models."""
+        (csrc/predict.hip: colsq_tri_kernel, loo_finish_kernel).  Double- and single-precision models."""
         if self.no_loo:
             self._loo_refused()
         return o._handle.lib.gpimhip_loo_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(mean), ptr(var),

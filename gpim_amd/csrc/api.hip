@@ -513,7 +513,12 @@ static int refine_passes() {
 // defer_alpha (double precision only): alpha stays as the row-chunk partial sums in h->gemv_part -- the gradient
 // contraction adds up the entries it needs itself (launch_grad_reduce_fin), one launch less per iteration; h->alpha is
 // then NOT valid.
-static bool alpha_deferrable(const gpimhip_ctx* h) { return !h->fp32 && !h->refl.mask && h->np <= 8192 && !getenv("GPIMHIP_NO_FUSED_FINALIZE"); }
+static bool alpha_deferrable(const gpimhip_ctx* h) { return !h->fp32 && !h->refl.mask && h->np <= 8192 && !h->no_fused_finalize; }
+// GPIMHIP_NO_FUSED_FINALIZE (run-time knob: the finalize step as a launch of its own, theta launched every iteration -- the
+// same reductions in the same order, the same bits), read ONCE per public call, at the top of every entry that reaches
+// loss_grad_at_u; carry (fit_impl), modern / fused (loss_grad_at_u) and alpha_deferrable all follow this one read, so they
+// cannot disagree inside a call.  Per call, not per handle: the tests flip the knob on a live handle.
+static void read_finalize_knob(gpimhip_ctx* h) { h->no_fused_finalize = getenv("GPIMHIP_NO_FUSED_FINALIZE") != nullptr; }
 int solve_vectors(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, bool defer_alpha) {
     const int64_t np = h->np, ld = h->ld;
     GP_TRY(launch_trmv_lower(h, h->A, ld, np, h->ypad, h->z));
@@ -556,44 +561,27 @@ static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double
                           double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out,
                           double* hist_row, const IterTable* tab = nullptr) {
     const int64_t np = h->np;
-    // One launch for the gradient contraction and the finalize step (round 6; GPIMHIP_NO_FUSED_FINALIZE: the two launches
-    // of rounds 1-5 -- the same reductions in the same order, the same bits)
+    // One launch for the gradient contraction and the finalize step (unless the knob asks for the two launches: see
+    // read_finalize_knob)
     // ... up to np = 8192; beyond, the finalize step is a launch of its own again (the tail's device-scope loads of 8256 tiles'
     // sums take longer than a launch boundary costs: 530 us against 400 + 20 at N = 16384) -- it still leaves the next theta
-    const bool modern = !h->refl.mask && !getenv("GPIMHIP_NO_FUSED_FINALIZE");
+    const bool modern = !h->refl.mask && !h->no_fused_finalize;
     const bool fused = modern && np <= 8192;
     const bool carried = modern && tab && tab->theta_carried;
     const bool defer = fused && alpha_deferrable(h);
+    // a training loop leaves its results by the table, one evaluation where the caller said
+    const FinalizeOut out = tab ? FinalizeOut(*tab) : FinalizeOut(loss_out, grad_out, hist_row);
     GP_TRY(factor_at_u(h, m, X, x_bs, N, u, carried, defer));
     { StageTimer t(h, 2); GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np))); }
     if (h->refl.mask) {
         const bool bd = border_on(h);
         if (bd) GP_TRY(border_iter(h, N, true));
-        const double* bscal = bd ? bws(h)->scal : nullptr;
         GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, x_bs));
-        if (tab)
-            return launch_finalize_coupled(h, m, N, np, u, do_adam, st, nullptr, nullptr, nullptr, tab->iter, tab->bc, tab->T,
-                                           tab->hist_base, tab->loss_base, bscal);
-        return launch_finalize_coupled(h, m, N, np, u, do_adam, st, loss_out, grad_out, hist_row, nullptr, nullptr, 0, nullptr,
-                                       nullptr, bscal);
+        return launch_finalize_coupled(h, m, N, np, u, do_adam, st, out, bd ? bws(h)->scal.p : nullptr);
     }
-    if (fused) {
-        const double* ap = defer ? h->gemv_part : nullptr;
-        if (tab)
-            return launch_grad_reduce_fin(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, x_bs, ap, u, do_adam, st, nullptr,
-                                          nullptr, nullptr, tab->iter, tab->bc, tab->T, tab->hist_base, tab->loss_base,
-                                          carried ? 1 : 0);
-        return launch_grad_reduce_fin(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, x_bs, ap, u, do_adam, st, loss_out,
-                                      grad_out, hist_row, nullptr, nullptr, 0, nullptr, nullptr, 0);
-    }
+    if (fused) return launch_grad_reduce_fin(h, m, X, x_bs, N, defer, u, do_adam, st, out, carried ? 1 : 0);
     GP_TRY(launch_grad_reduce(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, x_bs));
-    if (tab)
-        GP_TRY(launch_finalize(h, m, N, np, u, do_adam, st, nullptr, nullptr, nullptr, tab->iter, tab->bc, tab->T,
-                               tab->hist_base, tab->loss_base, carried ? 1 : 0));
-    else
-        GP_TRY(launch_finalize(h, m, N, np, u, do_adam, st, loss_out, grad_out, hist_row, nullptr, nullptr, 0,
-                               nullptr, nullptr));
-    return GPIMHIP_OK;
+    return launch_finalize(h, m, N, np, u, do_adam, st, out, carried ? 1 : 0);
 }
 
 // Fill the device table of Adam bias corrections (same libm pow() values for every path).
@@ -873,6 +861,7 @@ int gpimhip_potrf(gpimhip_handle h, double* A, int64_t n, int64_t ld, int32_t* i
 
 static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
                     int64_t N, int B, double* u, double lr, int32_t T, double* hist_out, double* loss_out) {
+    read_finalize_knob(h);
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = B;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
@@ -894,7 +883,7 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
     GP_TRY(launch_pad_copy(h, y, N, h->ypad, h->np));
     // theta(u) once; after that every iteration's finalize step leaves the next theta behind (not for the symmetry-reduced
     // model, whose coupled finalize step is a launch of its own)
-    const bool carry = !h->refl.mask && !getenv("GPIMHIP_NO_FUSED_FINALIZE");
+    const bool carry = !h->refl.mask && !h->no_fused_finalize;
     if (carry) GP_TRY(launch_theta(h, m, u));
     const IterTable tab{{h->iter, h->bc, T, hist_out, loss_out}, carry};
     const AdamStep st = adam_step_init();
@@ -1034,6 +1023,7 @@ int gpimhip_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* X
                      const double* u, double* loss_out, double* grad_out) {
     if (!h || !X || !y || !u || N < 1) return GPIMHIP_E_BADARG;
     GP_TRY(check_model(m));
+    read_finalize_knob(h);
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = 1;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
@@ -1092,6 +1082,7 @@ int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const d
         gpim_set_error("gpimhip_nll_grad_batched evaluates the coupled reflection blocks: needs reflection mode on a double-precision handle");
         return GPIMHIP_E_BADARG;
     }
+    read_finalize_knob(h);
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = B;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
@@ -1104,7 +1095,7 @@ int gpimhip_nll_grad_batched(gpimhip_handle h, const gpimhip_model_t* m, const d
     return finish_and_check(h);
 }
 
-// Leave-one-out cross-validation (engine.hip: colsq_tri_kernel, loo_finish_kernel): the model's state at u, then the column
+// Leave-one-out cross-validation (predict.hip: colsq_tri_kernel, loo_finish_kernel): the model's state at u, then the column
 // sums of squares of L^-1 of every problem in one launch and the finisher.  No K^-1 product, no gradient contraction.  The
 // row-chunk partial sums go to h->gemv_part (alpha has been summed out of it) and the score's to h->z (L^-1 y has served).
 static int loo_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N, int B,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <utility>
 #include "../../include/gpimhip.h"
@@ -28,6 +29,17 @@ void gpim_set_error(const std::string& s);
         int _r = (expr);                  \
         if (_r != GPIMHIP_OK) return _r;  \
     } while (0)
+
+// The one dispatch on the covariance function: f(std::integral_constant<int, KIND>{}) for the model's kind -- the launchers
+// instantiate their kernel templates on decltype(K)::value -- and f's return code; any other kind is a bad argument.
+template <typename F> static inline int with_kind(int kind, F&& f) {
+    switch (kind) {
+        case GPIMHIP_KERNEL_RBF: return f(std::integral_constant<int, GPIMHIP_KERNEL_RBF>{});
+        case GPIMHIP_KERNEL_MATERN52: return f(std::integral_constant<int, GPIMHIP_KERNEL_MATERN52>{});
+        case GPIMHIP_KERNEL_RQ: return f(std::integral_constant<int, GPIMHIP_KERNEL_RQ>{});
+        default: gpim_set_error("unknown kernel kind"); return GPIMHIP_E_BADARG;
+    }
+}
 
 // A device buffer that knows its own size: cap elements, charged to h->bytes by alloc / grow and credited by release (the
 // members are defined below gpimhip_ctx).  Reads as a plain pointer wherever one is expected.
@@ -76,7 +88,7 @@ static inline AdamStep adam_step_init() {
     return st;
 }
 
-// Iteration-indexed form of a finalize kernel (engine.hip, vgp.hip, sm.hip, kron.hip): when `iter` is given the Adam bias
+// Iteration-indexed form of a finalize kernel (grad.hip, vgp.hip, sm.hip, kron.hip): when `iter` is given the Adam bias
 // corrections, the history row and the loss slot are looked up by the device-resident iteration counter, which the kernel
 // advances.  All T iterations then enqueue byte-identical launches, i.e. one captured hipGraph can be replayed
 // (run_fit_iterations).  Passed to the kernels by value: the members are the kernel-argument layout.
@@ -86,6 +98,15 @@ struct FinalizeIter {
     int32_t T;
     double* hist_base;          // T x (parameters of a history row) or null
     double* loss_base;          // T or null
+};
+
+// Where a finalize launch leaves its results.  One evaluation (gpimhip_nll_grad): the three by-value pointers, no table.  A
+// training loop: the table alone -- loss slot and history row are looked up by the iteration (theta.hpp: finalize_iter_begin).
+struct FinalizeOut {
+    double* loss_out; double* grad_out; double* hist_row;
+    FinalizeIter fi;
+    FinalizeOut(const FinalizeIter& tab) : loss_out(nullptr), grad_out(nullptr), hist_row(nullptr), fi(tab) {}
+    FinalizeOut(double* loss, double* grad, double* hist) : loss_out(loss), grad_out(grad), hist_row(hist), fi{nullptr, nullptr, 0, nullptr, nullptr} {}
 };
 
 // A cached launch plan: tile lists of the level-by-level triangular inverse and of the K^-1 product at a given nb.
@@ -176,7 +197,7 @@ struct gpimhip_ctx {
     DevBuf<double> logdet_part;     // nb
     DevBuf<double> grad_part;       // ntiles_lower x 8
     DevBuf<double> gemv_part;       // gemv_tri_chunks(np) x np: row-chunk partial sums of alpha = L^-T z (engine.hip: gemv_t_tri_kernel)
-    DevBuf<uint32_t> fin_counter;      // per problem: workgroups of grad_reduce_kernel that have finished (engine.hip: FinFused; the last
+    DevBuf<uint32_t> fin_counter;      // per problem: workgroups of grad_reduce_kernel that have finished (grad.hip: FinFused; the last
                                        // one runs the finalize step and resets it)
     DevBuf<ThetaDev> theta;         // [ws_batch]
     DevBuf<ThetaDev> theta1;        // single struct for the operator-level gpimhip_kmat
@@ -232,6 +253,9 @@ struct gpimhip_ctx {
     void* ivr = nullptr;
     DevBuf<double> refine;          // residual, correction and partial sums of the refinement (fp32 handles)
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
+    // GPIMHIP_NO_FUSED_FINALIZE as the current public call found it (api.hip: read_finalize_knob, at the top of every entry that
+    // reaches loss_grad_at_u): theta carry, fused finalize and deferred alpha all derive from this one read
+    bool no_fused_finalize = false;
 };
 
 template <typename T> int DevBuf<T>::alloc(gpimhip_ctx* h, int64_t count, const char* what) {
@@ -437,47 +461,44 @@ int launch_pad_matrix_out_lower(gpimhip_ctx* h, const double* src, int64_t np, d
 int launch_trmv_lower(gpimhip_ctx* h, const double* L, int64_t ld, int64_t np, const double* y, double* z);
 int launch_gemv_t(gpimhip_ctx* h, const double* A, int64_t ld, int64_t nrows, int64_t ncols, const double* x,
                   double* out, int tri, int64_t a_bs, int64_t x_bs, int64_t o_bs);
-int launch_grad_reduce(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld,
-                       const double* X, int64_t N, int nb, const double* alpha, int64_t x_bs);
 int launch_kres(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, double* scratch,
                 int S, double* res);
 int launch_axpy(gpimhip_ctx* h, double* x, const double* d, int64_t n);
 int launch_gemv_t_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, const double* x, double* part, double* out);
-int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
-                           int64_t N, int nb, const double* alpha, int64_t x_bs, const double* alpha_part, double* u,
-                           int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                           const double* bc, int T, double* hist_base, double* loss_base, int carry_theta);
-int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
-                    AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                    const double* bc, int T, double* hist_base, double* loss_base, int carry_theta = 0);
-int launch_predict_var(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, double* var_out, int64_t M);
-int launch_copy_slice(gpimhip_ctx* h, const double* src, double* dst, int64_t n, int64_t s_bs, int64_t d_bs);
-int launch_acq(gpimhip_ctx* h, int kind, const double* mean, const double* sd, int64_t M, double p0, double p1,
-               const double* mask, double* out);
-int launch_nanmax(gpimhip_ctx* h, const double* x, int64_t n, double* out);
-int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
-                int64_t* count);
-// engine.hip (distributed training, reflection blocks)
-int launch_grad_reduce_tiles(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
-                             int64_t N, int64_t np, const double* alpha, const TileDesc* tiles, int ntile, double* part);
-int launch_sum7(gpimhip_ctx* h, const double* part, int ntile, double* S);
 int launch_kmat_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Z, int64_t M,
                      const ThetaDev* theta, double* out, int64_t ld, int64_t rows_pad, int64_t cols_pad, int sym, int64_t x_bs,
                      int64_t z_bs, int64_t out_bs, double scale);
+int launch_add_diag_theta(gpimhip_ctx* h, double* out, int64_t ld, int64_t row0, int64_t n, int64_t npad);
+int launch_theta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* u);
+// grad.hip
+int launch_grad_reduce(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld,
+                       const double* X, int64_t N, int nb, const double* alpha, int64_t x_bs);
+// the gradient contraction with the finalize step in its last workgroup (grad.hip: FinFused), and the step as a launch of
+// its own.  carry_theta: the theta of the stepped parameters replaces h->theta (the next iteration skips its theta launch).
+// The fused form contracts K^-1 in h->B with alpha from h->alpha, or (alpha_deferred) from the row-chunk sums in h->gemv_part.
+int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
+                           bool alpha_deferred, double* u, int do_adam, AdamStep st, const FinalizeOut& out, int carry_theta);
+int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
+                    AdamStep st, const FinalizeOut& out, int carry_theta = 0);
+// grad.hip (distributed training, reflection blocks)
+int launch_grad_reduce_tiles(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
+                             int64_t N, int64_t np, const double* alpha, const TileDesc* tiles, int ntile, double* part);
+int launch_sum7(gpimhip_ctx* h, const double* part, int ntile, double* S);
 int launch_grad_reduce_refl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
                             int64_t N, int nb, const double* alpha, int64_t x_bs);
 int launch_finalize_coupled(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
-                            AdamStep st, double* loss_out, double* grad_out, double* hist_row, int32_t* iter,
-                            const double* bc, int T, double* hist_base, double* loss_base, const double* border_scal = nullptr);
+                            AdamStep st, const FinalizeOut& out, const double* border_scal = nullptr);
 int launch_coupled_sums(gpimhip_ctx* h, int64_t np, double* out11);
-int launch_predict_coupled(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, int64_t nvar, int64_t mean_bs,
-                           double* mean_out, double* var_out, const double* radd = nullptr);
 int launch_dist_finalize_dev(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, const double* red, const double* quad,
                              double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row);
 int launch_dist_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, const double* S, double q2, double lg,
                          double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out, double* hist_row);
-int launch_add_diag_theta(gpimhip_ctx* h, double* out, int64_t ld, int64_t row0, int64_t n, int64_t npad);
-// engine.hip (leave-one-out cross-validation).  What loo_finish_kernel reads for its n points: the observations y, and
+// predict.hip (epilogues of the slab path)
+int launch_predict_var(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, double* var_out, int64_t M);
+int launch_copy_slice(gpimhip_ctx* h, const double* src, double* dst, int64_t n, int64_t s_bs, int64_t d_bs);
+int launch_predict_coupled(gpimhip_ctx* h, int64_t ldp, int nb, int64_t m0, int64_t mcount, int64_t nvar, int64_t mean_bs,
+                           double* mean_out, double* var_out, const double* radd = nullptr);
+// predict.hip (leave-one-out cross-validation).  What loo_finish_kernel reads for its n points: the observations y, and
 // per problem d = diag(S^-1) as the row-chunk partial sums of launch_colsq_tri (nR chunks of rc rows of a matrix of order
 // np; nR = 1 with rc = INT_MAX: d itself, np apart) and alpha (np apart).  B == 0: one problem, point i is its row i.
 // B > 0: the B reflection blocks of Nq points -- wts (B x Nq, or null), rep[i] the row of point i's representative and
@@ -490,8 +511,12 @@ static inline int loo_blocks(int64_t n) { return n > 1024 * 256 ? 1024 : (int)((
 int launch_colsq_tri(gpimhip_ctx* h, const double* A, int64_t ld, int64_t np, int64_t N, double* part);
 int launch_loo_finish(gpimhip_ctx* h, const LooSrc& s, int64_t n, const ThetaDev* theta, double* part, double* mean_out,
                       double* var_out, double* score_out);
-int launch_theta(gpimhip_ctx* h, const gpimhip_model_t* m, const double* u);
 // select.hip
+int launch_acq(gpimhip_ctx* h, int kind, const double* mean, const double* sd, int64_t M, double p0, double p1,
+               const double* mask, double* out);
+int launch_nanmax(gpimhip_ctx* h, const double* x, int64_t n, double* out);
+int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
+                int64_t* count);
 int launch_topk_radix(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
                       int64_t* count);
 int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* out);

@@ -1,7 +1,7 @@
 // distgp.hip -- host drivers of the multi-GPU exact GP (gpimhip_dist_*, gpimhip_matvec_t; include/gpimhip.h, DESIGN.md
 // section 6): the building blocks of the block-column-cyclic (1 x P) factorisation, the panel-wise solves and the distributed
 // training passes that gpim_amd/dist_chol.py drives.  Host code only: the kernels and their launchers are in distops.hip,
-// cholstep.hip and engine.hip, the engine's drivers (workspaces, tile engine) in api.hip.
+// cholstep.hip, engine.hip and grad.hip, the engine's drivers (workspaces, tile engine) in api.hip.
 #include <math.h>
 #include <algorithm>
 #include <vector>

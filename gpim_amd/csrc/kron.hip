@@ -7,7 +7,7 @@
 // so with K_i = Q_i diag(lam_i) Q_i^T (n_i x n_i symmetric eigenproblems)
 //     K + (jitter + noise) I = Q diag(D) Q^T,   Q = (x) Q_i,   D = s2 * prod_i lam_i[j_i] + jitter + noise.
 // Everything the dense path gets from the N x N Cholesky factor and K^-1 -- the loss, the SAME reduced
-// gradient sums S[] that csrc/engine.hip:grad_reduce_kernel produces (so the chain rule, the Adam step and
+// gradient sums S[] that csrc/grad.hip:grad_reduce_kernel produces (so the chain rule, the Adam step and
 // the history row are the shared finalize_step of theta.hpp), the posterior mean and variance -- follows
 // from mode products with the small matrices: O(sum n_i^3 + N sum n_i) instead of O(N^3) work and
 // O(N + sum n_i^2) instead of O(N^2) memory.  Same model, same parameterisation, same results as
@@ -566,16 +566,7 @@ __global__ __launch_bounds__(256) void kron_finalize_kernel(gpimhip_model_t m, K
     AdamStep st;
     st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
     double* hist_row = nullptr;
-    if (fi.iter) {
-        const int it = *fi.iter;
-        if (*info != 0) { atomicMin(info + 1, it); return; }
-        const int P = 2 + m.n_ls;
-        st.lr_over_bc1 = fi.bc[it];
-        st.bc2_sqrt = fi.bc[fi.T + it];
-        loss_out = fi.loss_base ? fi.loss_base + it : nullptr;
-        hist_row = fi.hist_base ? fi.hist_base + (int64_t)it * P : nullptr;
-        *fi.iter = it + 1;
-    }
+    if (!finalize_iter_begin(fi, info, 2 + m.n_ls, st, loss_out, hist_row)) return;
     finalize_step(m, dv.N, S, tot[1], tot[0], t, u, adam_m, adam_v, do_adam, st, loss_out, grad_out, hist_row,
                   prior_constant(m));
 }
@@ -1022,7 +1013,7 @@ int gpimhip_predict_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, 
 
 // Leave-one-out cross-validation in the eigenbasis: alpha = Q (y~ / D) and diag(S^-1) = ((x) Q_i o Q_i)
 // (1 / D), the mode products of the squared eigenvector matrices with what kron_invd_kernel leaves; then the dense
-// model's finisher (engine.hip: loo_finish_kernel).  alpha waits in w.Z while 1 / D takes the place of alpha~.
+// model's finisher (predict.hip: loo_finish_kernel).  alpha waits in w.Z while 1 / D takes the place of alpha~.
 int gpimhip_loo_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
                      const double* y, const double* u, double* mean_out, double* var_out, double* score_out) {
     if (!h || !m || !y || !u || !mean_out || !var_out || !score_out) return GPIMHIP_E_BADARG;

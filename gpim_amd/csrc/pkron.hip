@@ -192,18 +192,7 @@ __global__ __launch_bounds__(256) void pkron_finalize_kernel(gpimhip_model_t m, 
     AdamStep st;
     st.beta1 = 0.9; st.beta2 = 0.999; st.eps = 1e-8; st.lr_over_bc1 = 0.0; st.bc2_sqrt = 1.0;
     double* hist_row = nullptr;
-    if (fi.iter) {
-        const int it = *fi.iter;
-        // a factorisation of this training loop failed: u, the Adam state and the history stay as the previous iteration
-        // left them (the reference raises inside torch.linalg.cholesky there)
-        if (*info != 0) { atomicMin(info + 1, it); return; }
-        const int P = 2 + m.n_ls;
-        st.lr_over_bc1 = fi.bc[it];
-        st.bc2_sqrt = fi.bc[fi.T + it];
-        loss_out = fi.loss_base ? fi.loss_base + it : nullptr;
-        hist_row = fi.hist_base ? fi.hist_base + (int64_t)it * P : nullptr;
-        *fi.iter = it + 1;
-    }
+    if (!finalize_iter_begin(fi, info, 2 + m.n_ls, st, loss_out, hist_row)) return;
     finalize_step(m, Ntot, S, E[6], E[7], t, u, adam_m, adam_v, do_adam, st, loss_out, grad_out, hist_row, prior_constant(m));
 }
 

@@ -1,4 +1,4 @@
-// refl.hpp -- the reflection helpers of the symmetry-reduced exact GP (engine.hip: kmat_refl_kernel, grad_reduce_refl_kernel;
+// refl.hpp -- the reflection helpers of the symmetry-reduced exact GP (engine.hip: kmat_refl_kernel; grad.hip: grad_reduce_refl_kernel;
 // vgp.hip: vgp_kbeta_refl_kernel).  See engine.hip for the model.
 #pragma once
 #include "kfun.hpp"

@@ -412,26 +412,19 @@ int launch_pw_cross_apply(gpimhip_ctx* h, const gpimhip_model_t* m, const double
                           int64_t zw, int64_t zn_off, int noiseless, double* mean_out, double* out) {
     const dim3 grid((unsigned)((M + 255) / 256)), block(256);
     const int rem = S - s0;
-#define CA_LAUNCH(KIND, SG)                                                                                              \
-    hipLaunchKernelGGL((cross_apply_kernel<KIND, SG>), grid, block, 0, h->stream, G, M, Xt, N, m->dim, theta, Al, npt, S, s0, g, \
-                       Z, zw, zn_off, noiseless, mean_out, out)
-#define CA_KIND(KIND)                    \
-    do {                                 \
-        if (rem >= 5) CA_LAUNCH(KIND, 8); \
-        else if (rem >= 3) CA_LAUNCH(KIND, 4); \
-        else if (rem == 2) CA_LAUNCH(KIND, 2); \
-        else CA_LAUNCH(KIND, 1);         \
-    } while (0)
-    switch (m->kernel) {
-        case GPIMHIP_KERNEL_RBF: CA_KIND(GPIMHIP_KERNEL_RBF); break;
-        case GPIMHIP_KERNEL_MATERN52: CA_KIND(GPIMHIP_KERNEL_MATERN52); break;
-        case GPIMHIP_KERNEL_RQ: CA_KIND(GPIMHIP_KERNEL_RQ); break;
-        default: gpim_set_error("unknown kernel kind"); return GPIMHIP_E_BADARG;
-    }
-#undef CA_KIND
-#undef CA_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return GPIMHIP_OK;
+    return with_kind(m->kernel, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        auto launch = [&](auto SG) {
+            hipLaunchKernelGGL((cross_apply_kernel<KIND, decltype(SG)::value>), grid, block, 0, h->stream, G, M, Xt, N, m->dim, theta,
+                               Al, npt, S, s0, g, Z, zw, zn_off, noiseless, mean_out, out);
+        };
+        if (rem >= 5) launch(std::integral_constant<int, 8>{});
+        else if (rem >= 3) launch(std::integral_constant<int, 4>{});
+        else if (rem == 2) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 1>{});
+        HIP_TRY(hipGetLastError());
+        return GPIMHIP_OK;
+    });
 }
 
 __global__ __launch_bounds__(256) void pw_scatter_kernel(const int64_t* __restrict__ idx, int64_t N, int64_t M,

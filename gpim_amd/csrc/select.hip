@@ -11,7 +11,8 @@
 //   thin_batch_kernel    boptimizer.update_points: greedy maximum + suppression of everything within
 //                        `dscale` (cKDTree.query_ball_point semantics: distance <= r), on the <= 1024 ranked
 //                        candidates, in one workgroup.
-// The single-workgroup kernels of engine.hip stay in use for small grids (M <= 2048: fewer launches).
+//   nanmax / topk        the single-workgroup forms, in use for small grids (M <= 2048: fewer launches)
+//   acq_kernel           the acquisition sweep CB / EI / POI over mean and sd
 #include "common.hpp"
 
 #define SEL_MAXK 1024
@@ -246,6 +247,130 @@ int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* 
     return GPIMHIP_OK;
 }
 size_t sel_scratch_bytes() { return 4096 + SEL_MAXK * sizeof(SelCand) + 1024 * sizeof(double); }
+
+// ------------------------------------------------------------------------------------------
+// small grids (M <= 2048; api.hip chooses): nanmax and the ranking by single workgroups -- fewer launches
+// ------------------------------------------------------------------------------------------
+// nanmax over n values, single workgroup (n is a grid size: <= a few 1e5)
+__global__ __launch_bounds__(1024) void nanmax_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ out) {
+    __shared__ double red[1024];
+    const int tid = threadIdx.x;
+    double best = -INFINITY;
+    bool any = false;
+    for (int64_t i = tid; i < n; i += 1024) {
+        const double v = x[i];
+        if (v == v) { best = fmax(best, v); any = true; }
+    }
+    red[tid] = any ? best : -INFINITY;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        // all-NaN input: np.nanmax returns NaN (with a warning)
+        out[0] = (red[0] == -INFINITY) ? __builtin_nan("") : red[0];
+    }
+}
+int launch_nanmax(gpimhip_ctx* h, const double* x, int64_t n, double* out) {
+    hipLaunchKernelGGL(nanmax_kernel, dim3(1), dim3(1024), 0, h->stream, x, n, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// descending top-k by repeated arg-max inside one workgroup.  Keys are the order-preserving 64-bit images of the doubles
+// (sel_order_key); NaN ranks above +inf when keep_nan (np.argsort puts NaN last, the caller reverses), and is excluded
+// otherwise.  Ties: larger flat index first (= reversed stable sort).
+__global__ void topk_keys_kernel(const double* __restrict__ x, int64_t M, int keep_nan,
+                                 unsigned long long* __restrict__ keys) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < M) keys[j] = sel_order_key(x[j], keep_nan);
+}
+__global__ __launch_bounds__(1024) void topk_select_kernel(const double* __restrict__ x,
+                                                           unsigned long long* __restrict__ keys, int64_t M, int k,
+                                                           double* __restrict__ vals, int64_t* __restrict__ idx,
+                                                           int64_t* __restrict__ count) {
+    __shared__ unsigned long long rk[1024];
+    __shared__ int64_t ri[1024];
+    const int tid = threadIdx.x;
+    int64_t found = 0;
+    for (int r = 0; r < k; ++r) {
+        unsigned long long bk = 0ull;
+        int64_t bi = -1;
+        for (int64_t j = tid; j < M; j += 1024) {
+            const unsigned long long kk = keys[j];
+            if (kk > bk || (kk == bk && kk != 0ull && j > bi)) { bk = kk; bi = j; }
+        }
+        rk[tid] = bk;
+        ri[tid] = bi;
+        __syncthreads();
+        for (int s = 512; s > 0; s >>= 1) {
+            if (tid < s) {
+                const unsigned long long ok = rk[tid + s];
+                const int64_t oi = ri[tid + s];
+                if (ok > rk[tid] || (ok == rk[tid] && oi > ri[tid])) { rk[tid] = ok; ri[tid] = oi; }
+            }
+            __syncthreads();
+        }
+        const unsigned long long wk = rk[0];
+        const int64_t wi = ri[0];
+        __syncthreads();
+        if (wk == 0ull || wi < 0) break;
+        if (tid == 0) {
+            vals[r] = x[wi];
+            idx[r] = wi;
+            keys[wi] = 0ull;
+        }
+        found = r + 1;
+        __threadfence_block();
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *count = found;
+        for (int r = (int)found; r < k; ++r) { vals[r] = __builtin_nan(""); idx[r] = -1; }
+    }
+}
+int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan, double* vals, int64_t* idx,
+                int64_t* count) {
+    hipLaunchKernelGGL(topk_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, x, M, keep_nan,
+                       h->keys);
+    hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, h->stream, x, h->keys, M, k, vals, idx, count);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// acquisition sweep (acqfunc.py:11-92).  Phi / phi as scipy.stats.norm: ndtr(z) = erfc(-z/sqrt2)/2.
+// ------------------------------------------------------------------------------------------
+__global__ void acq_kernel(int kind, const double* __restrict__ mean, const double* __restrict__ sd, int64_t M,
+                           double p0, double p1, const double* __restrict__ mask, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    const double mu = mean[j], s = sd[j];
+    double a;
+    if (kind == GPIMHIP_ACQ_CB) {
+        a = p0 * mu + p1 * s;
+    } else {
+        const double imp = mu - p0 - p1;
+        const double zz = imp / s;
+        const double cdf = 0.5 * erfc(-zz * 0.7071067811865476);
+        if (kind == GPIMHIP_ACQ_EI) {
+            const double pdf = exp(-0.5 * zz * zz) * 0.3989422804014327;
+            a = imp * cdf + s * pdf;
+        } else {
+            a = cdf;
+        }
+    }
+    if (mask) a = mask[j] * a;
+    out[j] = a;
+}
+int launch_acq(gpimhip_ctx* h, int kind, const double* mean, const double* sd, int64_t M, double p0, double p1,
+               const double* mask, double* out) {
+    hipLaunchKernelGGL(acq_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, kind, mean, sd, M,
+                       p0, p1, mask, out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // batch thinning (boptim.py:326-376): among n ranked candidates (values, d-dimensional grid indices) repeatedly

@@ -252,15 +252,9 @@ int launch_fit_small(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
     a.m = *m; a.X = X; a.x_bs = x_bs; a.y = y; a.N = N; a.T = T; a.u = u;
     a.lr_over_bc1 = lr_over_bc1; a.bc2_sqrt = bc2_sqrt;
     a.hist = hist; a.loss = loss; a.grad = grad; a.info = h->info; a.prof = nullptr;
-    switch (m->kernel) {
-        case GPIMHIP_KERNEL_RBF:
-            hipLaunchKernelGGL((fit_small_kernel<GPIMHIP_KERNEL_RBF>), dim3(h->nbatch), dim3(NTH), 0, h->stream, a); break;
-        case GPIMHIP_KERNEL_MATERN52:
-            hipLaunchKernelGGL((fit_small_kernel<GPIMHIP_KERNEL_MATERN52>), dim3(h->nbatch), dim3(NTH), 0, h->stream, a); break;
-        case GPIMHIP_KERNEL_RQ:
-            hipLaunchKernelGGL((fit_small_kernel<GPIMHIP_KERNEL_RQ>), dim3(h->nbatch), dim3(NTH), 0, h->stream, a); break;
-        default: gpim_set_error("unknown kernel kind"); return GPIMHIP_E_BADARG;
-    }
-    HIP_TRY(hipGetLastError());
-    return GPIMHIP_OK;
+    return with_kind(m->kernel, [&](auto K) {
+        hipLaunchKernelGGL((fit_small_kernel<decltype(K)::value>), dim3(h->nbatch), dim3(NTH), 0, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        return GPIMHIP_OK;
+    });
 }

@@ -1,5 +1,5 @@
 // theta.hpp -- hyper-parameter maps and the scalar tail of one training iteration (device side),
-// shared by the general path (engine.hip) and the fused small-N trainer (smalln.hip).
+// shared by the general path (engine.hip, grad.hip) and the fused small-N trainer (smalln.hip).
 //
 //   u -> theta : torch.distributions transform_to(interval) = Affine o Sigmoid with clipping,
 //                transform_to(positive) = exp  (pyro_kernels.py:81-94)
@@ -49,6 +49,29 @@ __device__ inline double prior_constant(const gpimhip_model_t& m) {
     double prior = log(m.amp_hi - m.amp_lo);
     for (int k = 0; k < m.n_ls; ++k) prior += log(m.ls_hi[k] - m.ls_lo[k]);
     return prior;
+}
+
+// The iteration slot of a finalize step, taken by the ONE thread that runs the step.  Without a table (fi.iter == null: one
+// evaluation) nothing changes.  With one: if a factorisation of this training loop has failed (this iteration's, or an
+// earlier one of any problem of the batch) the reference raises here (gpr.py:192) with u, the Adam state and the history
+// as the previous iteration left them -- record how far the loop got in info[1] and return false: the caller freezes them.
+// Otherwise the two bias corrections, the loss slot and the history row (P values) of this iteration, and the counter moves on.
+// (LossPtr / HistPtr: double*, or a kernel parameter's double* __restrict__)
+template <typename LossPtr, typename HistPtr>
+__device__ __forceinline__ bool finalize_iter_begin(const FinalizeIter& fi, int32_t* info, int P, AdamStep& st,
+                                                    LossPtr& loss_out, HistPtr& hist_row) {
+    if (!fi.iter) return true;
+    const int it = *fi.iter;
+    if (*info != 0) {
+        atomicMin(info + 1, it);
+        return false;
+    }
+    st.lr_over_bc1 = fi.bc[it];
+    st.bc2_sqrt = fi.bc[fi.T + it];
+    loss_out = fi.loss_base ? fi.loss_base + it : nullptr;
+    hist_row = fi.hist_base ? fi.hist_base + (int64_t)it * P : nullptr;
+    *fi.iter = it + 1;
+    return true;
 }
 
 // g (MAXP doubles) and tn: working storage -- private arrays in finalize_step, LDS where the step is the tail of a kernel

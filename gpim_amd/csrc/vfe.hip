@@ -608,17 +608,12 @@ static int launch_grad(gpimhip_ctx* h, const gpimhip_model_t* m, const double* G
                        double* xu_part, int64_t mp, int B) {
     dim3 grid(ntr * ntc, B), block(256);
     const int64_t part_bs = (int64_t)ntr * ntc * 8, xup_bs = (int64_t)ntc * mp * 4;
-#define VG_LAUNCH(KIND)                                                                                    \
-    hipLaunchKernelGGL((vfe_grad_kernel<KIND>), grid, block, 0, h->stream, G, ld, Xu, Mu, Z, Nz, m->dim,   \
-                       h->theta, ntc, part, xu_part, mp, g_bs, xu_bs, z_bs, part_bs, xup_bs)
-    switch (m->kernel) {
-        case GPIMHIP_KERNEL_RBF: VG_LAUNCH(GPIMHIP_KERNEL_RBF); break;
-        case GPIMHIP_KERNEL_MATERN52: VG_LAUNCH(GPIMHIP_KERNEL_MATERN52); break;
-        default: VG_LAUNCH(GPIMHIP_KERNEL_RQ); break;
-    }
-#undef VG_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return GPIMHIP_OK;
+    return with_kind(m->kernel, [&](auto K) {
+        hipLaunchKernelGGL((vfe_grad_kernel<decltype(K)::value>), grid, block, 0, h->stream, G, ld, Xu, Mu, Z, Nz, m->dim,
+                           h->theta, ntc, part, xu_part, mp, g_bs, xu_bs, z_bs, part_bs, xup_bs);
+        HIP_TRY(hipGetLastError());
+        return GPIMHIP_OK;
+    });
 }
 
 // The B models of a call: u holds B vectors [u_theta (P) | Xu (Mu x d)] one after the other, X advances by x_bs doubles per

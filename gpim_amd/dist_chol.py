@@ -48,7 +48,16 @@ import torch.distributed as dist
 NB = 128
 PANEL = 4            # 128-blocks per panel (OUTER_W of csrc/common.hpp)
 PW = NB * PANEL
-KINV_GROUP = int(os.environ.get("GPIM_DIST_KINV_GROUP", "8"))      # panels per launch of the K^-1 pass (1: one at a time)
+def _kinv_group():
+    """GPIM_DIST_KINV_GROUP: panels per launch of the K^-1 pass (1: one at a time).  Default 8; an empty or non-numeric
+    value falls back to it (the module must import whatever the environment holds), and the value is at least 1."""
+    try:
+        return max(1, int(os.environ.get("GPIM_DIST_KINV_GROUP", "8")))
+    except ValueError:
+        return 8
+
+
+KINV_GROUP = _kinv_group()
 
 
 def _force_collectives():

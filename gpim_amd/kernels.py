@@ -6,7 +6,7 @@ row a4): an RBF / Matern52 / RationalQuadratic kernel whose variance and lengths
 Uniform priors, which Pyro turns into interval-constrained MAP parameters INITIALISED BY ONE
 DRAW FROM EACH PRIOR (variance first, then lengthscale) with torch's CPU generator.  The
 draw is reproduced here bit for bit; the constrained<->unconstrained maps and all kernel
-arithmetic live on the device (csrc/engine.hip, csrc/kfun.hpp).
+arithmetic live on the device (csrc/engine.hip, csrc/grad.hip, csrc/kfun.hpp).
 """
 import ctypes
 import math

@@ -704,7 +704,8 @@ int gpimhip_dist_kinv_update(gpimhip_handle h, const double* xbuf, int64_t ldx, 
                              const double* Xloc, int64_t ldloc, double* Kinv, int64_t ldk);
 /* ... for `npanels` consecutive panels in ONE launch: xbuf holds them side by side (np rows x 512 * npanels, the first one
  * with global block index panel_glob_blk0).  Early panels have few tiles, each as deep as the whole matrix: one at a time
- * they leave most of the chip idle (round 6: four per launch). */
+ * they leave most of the chip idle (round 6: the Python driver groups 8 per launch, GPIM_DIST_KINV_GROUP).  npanels is
+ * clamped to the panels that remain behind panel_glob_blk0: a last group may ask for more than there are. */
 int gpimhip_dist_kinv_update_n(gpimhip_handle h, const double* xbuf, int64_t ldx, int32_t panel_glob_blk0, int32_t npanels,
                                const double* Xloc, int64_t ldloc, double* Kinv, int64_t ldk);
 int gpimhip_dist_grad_sums(gpimhip_handle h, const gpimhip_model_t* m, const double* X, int64_t N, const double* u,

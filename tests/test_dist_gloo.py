@@ -95,6 +95,17 @@ def test_single_process_paths():
     assert mean.shape == (3, 2, 2) and sd[2, 0, 0].item() == 4.0
 
 
+def test_kinv_group_env_is_parsed_defensively(monkeypatch):
+    """GPIM_DIST_KINV_GROUP is read at import: an empty or non-numeric value must not break the import (the default 8 then),
+    and the group is at least one panel."""
+    from gpim_amd import dist_chol
+    for value, want in (("", 8), ("many", 8), ("0", 1), ("-3", 1), ("3", 3)):
+        monkeypatch.setenv("GPIM_DIST_KINV_GROUP", value)
+        assert dist_chol._kinv_group() == want
+    monkeypatch.delenv("GPIM_DIST_KINV_GROUP")
+    assert dist_chol._kinv_group() == 8
+
+
 # ------------------------------------------------------------------------------------------------
 # block-column-cyclic Cholesky: ownership / broadcast schedule with a stubbed tile engine
 # ------------------------------------------------------------------------------------------------

@@ -490,3 +490,56 @@ def test_fused_finalize_equals_two_launches(gpim, monkeypatch, n, T, kernel, pre
     for a, b in ((outs[0], outs[1]), (outs[0], outs[2])):
         for x, y_ in zip(a, b):
             assert np.array_equal(x, y_)
+
+
+def _scattered_image(n, seed):
+    """An image with exactly n observed pixels (NaN elsewhere) on the smallest square grid of 4 n pixels."""
+    side = int(np.ceil(np.sqrt(n * 4)))
+    rng = np.random.default_rng(seed)
+    ii, jj = np.meshgrid(np.arange(side), np.arange(side), indexing="ij")
+    R = np.sin(ii / 7.0 + 0.3 * seed) * np.cos(jj / 5.0) + 0.05 * rng.standard_normal((side, side))
+    R.ravel()[rng.permutation(side * side)[n:]] = np.nan
+    return R
+
+
+def test_fused_finalize_batch_and_one_shot(gpim, monkeypatch):
+    """The two paths into the fused gradient-contraction / finalize launch that test_fused_finalize_equals_two_launches does
+    not reach, each bit-equal to the two launches of GPIMHIP_NO_FUSED_FINALIZE=1:
+      batch     three different data sets of N = 300 in lock-step (three block columns: six tiles and ONE counter per
+                problem), 8 iterations, i.e. a captured graph whose replays rely on every problem's last workgroup
+                resetting its counter; the default twice (a stale partial sum or a counter left over would show), then the knob;
+      one shot  gpimhip_nll_grad -- no iteration table, loss and gradient by value -- at N = 129 (two block columns, three
+                tiles, the last row and column of tiles all padding but one point) and N = 300, the three kernels in double
+                and RBF in single."""
+    from gpim_amd.batch import fit_predict_batch
+    ls = [[1., 1.], [20., 20.]]
+    images = [_scattered_image(300, seed) for seed in (1, 2, 3)]
+    Xs_list = [gpim.utils.get_sparse_grid(R) for R in images]
+    Xf = gpim.utils.get_full_grid(images[0])
+    shots = [(n, kernel, prec) for n in (129, 300)
+             for kernel, prec in (("RBF", "double"), ("Matern52", "double"), ("RationalQuadratic", "double"), ("RBF", "single"))]
+    runs = []
+    for knob in (None, None, "1"):
+        if knob:
+            monkeypatch.setenv("GPIMHIP_NO_FUSED_FINALIZE", knob)
+        else:
+            monkeypatch.delenv("GPIMHIP_NO_FUSED_FINALIZE", raising=False)
+        batch = [t.cpu().numpy() for t in fit_predict_batch(Xs_list, images, Xf, kernel="Matern52", lengthscale=ls,
+                                                             learning_rate=0.1, iterations=8)]
+        one = []
+        for n, kernel, prec in shots:
+            R = _scattered_image(n, n)
+            rec = gpim.reconstructor(gpim.utils.get_sparse_grid(R), R, gpim.utils.get_full_grid(R), kernel=kernel,
+                                     lengthscale=ls, verbose=0, precision=prec)
+            loss, grad = rec.loss_and_grad()
+            one.append((np.array([loss]), grad.numpy()))
+        runs.append((batch, one))
+    mean, sd, hist = runs[0][0]
+    assert hist.shape[:2] == (3, 8) and np.isfinite(mean).all() and np.isfinite(hist).all()
+    assert not np.array_equal(hist[0], hist[1]) and not np.array_equal(hist[1], hist[2])      # three problems, not one thrice
+    for other in (runs[1], runs[2]):
+        for x, y_ in zip(runs[0][0], other[0]):
+            assert np.array_equal(x, y_)
+        for (shot, a, b) in zip(shots, runs[0][1], other[1]):
+            assert np.isfinite(a[0]).all() and np.isfinite(a[1]).all(), shot
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), shot

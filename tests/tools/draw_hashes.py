@@ -25,6 +25,10 @@ drivers of csrc/distgp.hip:
              dense solver for vgp; blocks: the complete grid; border: 3 missing pixels): predict, nll_grad, ten Adam
              iterations; gpimhip_sm_kmat on a dense handle and in reflection mode; two predictions at M = 961 and the two
              stationary dense ones through the slab path (GPIMHIP_NO_FUSED_PREDICT)
+  stationary the training launches of csrc/grad.hip: the dense model at N = 300 (RBF, Matern52, RationalQuadratic in double,
+             RBF in single) and the reflection blocks of a 16 x 16 grid (Matern52, structured=True), nll_grad and ten Adam
+             iterations each; fit_predict_batch of three data sets of N = 300 (8 iterations); rec.loo() on the dense model;
+             expected improvement and gpimhip_topk at M = 340 (the single-workgroup ranking)
 """
 import hashlib
 import os
@@ -166,6 +170,19 @@ def cases():
         yield from model_cases("vgp %s T=2 16x16 (%s)" % (regime, rec.solver), rec, ("lengthscale",),
                                fine if regime == "blocks" else None)
     yield "predict N=300 M=340, slab path", lambda: slab_predict(r)
+    # ---- the stationary training paths (csrc/grad.hip), leave-one-out, the acquisition sweep and the small-grid ranking
+    Rd, _ = image((20, 17), 300)                  # (the data of the first case: N = 300 on a grid of M = 340)
+    Xsd, Xfd = sparse_and_full(Rd)
+    yield "acquisition EI + top-10, M=340", lambda: acq_topk(r, Xfd, Xsd)
+    tr = dict(learning_rate=0.05, iterations=10, **kw)
+    for kernel, precision in (("RBF", "double"), ("Matern52", "double"), ("RationalQuadratic", "double"), ("RBF", "single")):
+        rd = gpim_amd.reconstructor(Xsd, Rd, Xfd, kernel=kernel, precision=precision, **tr)
+        if kernel == "Matern52":
+            yield "loo dense N=300", lambda rd=rd: loo_arrays(rd)
+        yield from training_cases("dense N=300 %s %s" % (kernel, precision), rd)
+    rr = gpim_amd.reconstructor(X16, f16, X16, kernel="Matern52", structured=True, **tr)
+    yield from training_cases("reflection blocks 16x16 Matern52", rr)
+    yield "batch B=3 N=300 T=8", batch_fit
 
 
 def with_env(name, value, run):
@@ -204,6 +221,35 @@ def dist_case():
     ch.set_from_function(lambda c0, c1: A[:, c0:c1]).factor()
     y = torch.from_numpy(rng.standard_normal(n)).cuda()
     return ch.gather_lower().cpu().numpy(), np.array([ch.logdet()]), ch.solve(y).cpu().numpy()
+
+
+def loo_arrays(rec):
+    mean, sd, score = rec.loo(as_grid=False)
+    return mean, sd, np.array([score["elpd"], score["rmse"]])
+
+
+def acq_topk(rec, Xf, Xs):
+    """expected improvement over the grid (predictions, nanmax of the incumbent, the sweep), then the ten largest values by
+    gpimhip_topk: M = 340 takes the single-workgroup forms"""
+    import torch
+    from gpim_amd import _lib, acqfunc
+    acq, (mean, sd) = acqfunc.expected_improvement(rec, Xf, Xs)
+    H = rec._handle
+    xd = torch.as_tensor(np.ascontiguousarray(acq, dtype=np.float64).ravel()).to(H.device)
+    vals = torch.empty(10, dtype=torch.float64, device=H.device)
+    idx = torch.empty(10, dtype=torch.int64, device=H.device)
+    cnt = torch.zeros(1, dtype=torch.int64, device=H.device)
+    _lib.check(H.lib.gpimhip_topk(H.h, _lib.ptr(xd), xd.numel(), 10, 0, _lib.ptr(vals), _lib.ptr(idx), _lib.ptr(cnt)))
+    return acq, mean, sd, vals.cpu().numpy(), idx.cpu().numpy(), cnt.cpu().numpy()
+
+
+def batch_fit():
+    """three data sets of N = 300 on a 35 x 35 grid fitted in lock-step (8 iterations: graph replay) and predicted"""
+    from gpim_amd.batch import fit_predict_batch
+    images = [image((35, 35), 300, seed)[0] for seed in (1, 2, 3)]
+    out = fit_predict_batch([gpim_amd.utils.get_sparse_grid(R) for R in images], images, gpim_amd.utils.get_full_grid(images[0]),
+                            kernel="Matern52", lengthscale=LS2, learning_rate=0.1, iterations=8)
+    return [t.cpu().numpy() for t in out]
 
 
 def slab_predict(rec):
