@@ -209,6 +209,28 @@ class Dense:
                                                 Xs.shape[0], ptr(weights), ptr(mask), int(q), ptr(mean), ptr(sd), ptr(maps),
                                                 ptr(sd_after), ptr(idx), ptr(gain), ptr(count))
 
+    def believer(self, o, kind, Xs, Xobs, p0, p1, mask, q, mean, sd, maps, sd_after, idx, val, count):
+        """A believer batch of q picks for the acquisition function kind ('cb' / 'ei' / 'poi') at the rows Xs: pick r
+        maximises the acquisition function of the model conditioned on picks 0 .. r - 1 having been measured at their
+        posterior means (csrc/believer.hip: gpimhip_acquire_batch).  Xobs: the observed rows (EI /
+        POI) or None; (p0, p1) = (alpha, beta) for CB, (ignored, xi) else; the rest as ``ivr_greedy``.  Dense
+        double-precision models only."""
+        self._believer_supported(o)
+        return o._handle.lib.gpimhip_acquire_batch(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
+                                                   Xs.shape[0], ptr(Xobs), 0 if Xobs is None else Xobs.shape[0], _lib.ACQ_IDS[kind],
+                                                   float(p0), float(p1), ptr(mask), int(q), ptr(mean), ptr(sd), ptr(maps),
+                                                   ptr(sd_after), ptr(idx), ptr(val), ptr(count))
+
+    def _believer_supported(self, o):
+        # (the paths without integrated variance reduction have no conditioned columns either, for the same reasons)
+        if self.no_ivr:
+            raise NotImplementedError("acq_batch(): the %s solver has no believer batch -- %s"
+                                      % (type(self).__name__, self.no_ivr))
+        if o.precision == "single":
+            raise NotImplementedError("acq_batch(): v = s2 - sum W^2 and the conditioned columns cancel to the posterior "
+                                      "variance, which single precision does not resolve: build the model with "
+                                      "precision='double'")
+
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:
         the gate of _sampling.Joint refuses the other paths before a solver is asked."""

@@ -240,6 +240,40 @@ def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None):
     return idx_d, gain_d, count_d, maps_d, mean_d, sd_d, sd_after_d
 
 
+def believer_on_device(gpmodel, kind, Xf_d, q, p0=0., p1=1., xi=0.01, mask_d=None, Xobs_d=None):
+    """A believer batch of ``q`` picks for ``kind`` ('cb' / 'ei' / 'poi') over the device rows ``Xf_d``: device tensors
+    ``(idx, val, count, maps, mean, sd, sd_after)``.  After each pick the model is conditioned on the pick having been
+    measured at its posterior mean (kriging believer; GP-BUCB for 'cb'): the mean does not change, the variance drops as in
+    ``ivr_greedy_on_device``, and the next pick maximises the acquisition function of the conditioned model -- two
+    neighbouring maxima that explain the same pixels are not both taken.  ``idx`` (q,) int64 flat indices in pick order,
+    ``val`` (q,) the map values at the picks, ``count`` (1,) int64 the picks made (fewer than q when the unmasked candidates
+    run out; then idx = -1 and val = NaN behind them), ``maps`` (q, M) the map each pick was taken from (NaN at masked
+    candidates and earlier picks), ``mean``, ``sd`` the posterior before the batch, ``sd_after`` the sd once the batch is
+    measured.  ``p0``, ``p1``: alpha, beta of 'cb'; ``xi``: of 'ei' / 'poi', whose incumbent is the maximum of the posterior
+    at the observed rows ``Xobs_d`` (default: the model's training inputs) and of the believed values.  ``mask_d``: (M,)
+    device mask of 1 / NaN.  1 <= q <= M.  One library call (gpimhip_acquire_batch): one pass over
+    W = L^-1 K(X, Xf) per pick, no M x M matrix.  Dense double-precision models only."""
+    if kind not in _lib.ACQ_IDS:
+        raise ValueError("acq_batch: the acquisition function must be 'cb', 'ei' or 'poi'; got %r" % (kind,))
+    gpmodel._solver._believer_supported(gpmodel)
+    M = _ivr_check_args(gpmodel, Xf_d, None, mask_d)
+    q = int(q)
+    if q < 1 or q > M:
+        raise ValueError("acq_batch: a batch of %d picks from %d candidates (1 <= q <= M)" % (q, M))
+    if kind != "cb" and Xobs_d is None:
+        Xobs_d = gpmodel._Xd
+    a, b = (p0, p1) if kind == "cb" else (0.0, xi)
+    dev = Xf_d.device
+    mean_d, sd_d, sd_after_d = (torch.empty((M,), dtype=_F64, device=dev) for _ in range(3))
+    maps_d = torch.empty((q, M), dtype=_F64, device=dev)
+    val_d = torch.empty((q,), dtype=_F64, device=dev)
+    idx_d = torch.empty((q,), dtype=torch.int64, device=dev)
+    count_d = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(gpmodel._solver.believer(gpmodel, kind, Xf_d, None if kind == "cb" else Xobs_d, a, b, mask_d, q, mean_d, sd_d,
+                                        maps_d, sd_after_d, idx_d, val_d, count_d))
+    return idx_d, val_d, count_d, maps_d, mean_d, sd_d, sd_after_d
+
+
 def _ivr_mask(mask, shape, dev):
     """``mask`` (None or an array of the grid's shape holding 1 / NaN) as a flat device vector."""
     if mask is None:

@@ -84,7 +84,13 @@ class boptimizer:
     every pick maximises the map conditioned on the picks before it and the returned values are the drops each pick adds
     to the batch's (no thinning by distance, no random padding; fewer points only when the unmasked candidates run out);
     the default ``ivr_batch='thin'`` ranks one map and thins it through ``update_points`` like the other acquisition
-    functions.  ``shard_candidates=True`` (with torch.distributed initialised, one process
+    functions.  For 'cb', 'ei' and 'poi' with ``batch_update=True``, ``acq_batch='believer'`` makes the batch the
+    ``batch_out_max`` picks of reconstructor.acq_batch (kriging believer; GP-BUCB for 'cb'): after every pick the variance
+    is conditioned on it as if it had been measured at its posterior mean, and the next pick maximises the acquisition
+    function of that model; the returned values are the picks' map values (no thinning by distance, no random padding;
+    fewer points only when the unmasked candidates run out; dense double-precision surrogates, no ``shard_candidates``);
+    the default ``acq_batch='thin'`` ranks one map and thins it through ``update_points``.
+    ``shard_candidates=True`` (with torch.distributed initialised, one process
     per GPU) makes every rank sweep only its contiguous block of the test grid; an all-gather of
     each rank's top-``batch_size`` (value, index) pairs gives all ranks the same global ranking
     (SURVEY 8(e)).  Training stays replicated -- it is deterministic, so all ranks hold the same
@@ -160,6 +166,16 @@ class boptimizer:
             if sm._solver.no_ivr or sm.precision == "single":
                 sm._solver.ivr(sm, None, None, None, None, None, None)        # raises NotImplementedError with the reason
             self._ivr_weights_d = acqfunc._ivr_weights(kwargs.get("ivr_weights"), tuple(np.shape(X_full)[1:]), sm._dev)
+        self.acq_batch = kwargs.get("acq_batch", "thin")
+        if acquisition_function in ('cb', 'ei', 'poi'):
+            # (acq_batch belongs to 'cb' / 'ei' / 'poi' with batch_update=True alone)
+            if self.acq_batch not in ("thin", "believer"):
+                raise ValueError("acq_batch must be 'thin' or 'believer'; got %r" % (self.acq_batch,))
+            if self.acq_batch == "believer":
+                if self.shard_candidates:
+                    raise NotImplementedError("acq_batch='believer' with shard_candidates=True: every pick conditions the "
+                                              "variance of all candidates, the batch does not split over candidate blocks")
+                self.surrogate_model._solver._believer_supported(self.surrogate_model)
         self.indices_all, self.vals_all = [], []
         self.target_func_vals, self.gp_predictions = [y_seed.copy()], _LazyMaps()
         self._mask_d = None
@@ -311,6 +327,8 @@ class boptimizer:
             p0, p1 = (self.alpha, self.beta) if af == 'cb' else (0.0, 0.0)
             if self._Xfull_d is None:
                 self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
+            if self.batch_update and self.acq_batch == 'believer':
+                return self._next_batch_believer(tuple(np.shape(self.X_full)[1:]))
             acq_d, mean_d, sd_d = acqfunc.acquisition_on_device(sm, af, self.X_full, self.X_sparse, p0, p1, self.xi,
                                                                 Xf_d=self._Xfull_d,
                                                                 mask_d=self._device_mask(self._Xfull_d.shape[0]),
@@ -375,6 +393,24 @@ class boptimizer:
         self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
         # one device-to-host copy: [count | q indices | q gains (as bits)]
         host = torch.cat([count_d, idx_d, gain_d.view(torch.int64)]).cpu().numpy()
+        n = int(host[0])
+        flat = host[1:1 + n]
+        vals_list = host[q + 1:q + 1 + n].view(np.float64).tolist()
+        return vals_list, np.stack(np.unravel_index(flat, tuple(grid_shape)), axis=-1).tolist()
+
+    def _next_batch_believer(self, grid_shape):
+        """The ``batch_out_max`` believer picks of 'cb' / 'ei' / 'poi' and their values, from one library call
+        (acqfunc.believer_on_device); (mean, sd) of the step are the posterior before the batch."""
+        sm = self.surrogate_model
+        M = self._Xfull_d.shape[0]
+        q = int(min(self.batch_out_max, M))
+        idx_d, val_d, count_d, _, mean_d, sd_d, _ = acqfunc.believer_on_device(
+            sm, self.acquisition_function, self._Xfull_d, q, p0=self.alpha, p1=self.beta, xi=self.xi,
+            mask_d=self._device_mask(M), Xobs_d=self._observed_rows_d())
+        mean_d, sd_d = self._retain_maps(mean_d, sd_d)
+        self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
+        # one device-to-host copy: [count | q indices | q values (as bits)]
+        host = torch.cat([count_d, idx_d, val_d.view(torch.int64)]).cpu().numpy()
         n = int(host[0])
         flat = host[1:1 + n]
         vals_list = host[q + 1:q + 1 + n].view(np.float64).tolist()

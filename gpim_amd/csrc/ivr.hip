@@ -23,27 +23,18 @@
 #include "common.hpp"
 #include "border.hpp"
 #include "kfun.hpp"
+#include "ivr.hpp"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-struct IvrWs {
-    DevBuf<double> W;               // np x ldm: L^-1 K(X, G), rows >= N zero
-    DevBuf<double> C;               // mp x ldm: lower tiles of the latent posterior covariance
-    DevBuf<double> part;            // (mp / 128) x mp: part[k][j] = sum over the rows m of block k of w_m C_mj^2
-    DevBuf<TileDesc> tiles;         // lower tiles of an nt x nt block matrix
-    DevBuf<double> g;               // mp: the scaled column of the last pick, zero at rows >= M (gpimhip_ivr_greedy)
-    DevBuf<double> live;            // M: the user's mask or ones, NaN at the picks made so far
-    DevBuf<double> row;             // M: a round's map when the caller does not want the maps
-    int nt = 0;
-};
-static IvrWs* iws(gpimhip_ctx* h) {
+IvrWs* ivr_ws(gpimhip_ctx* h) {
     if (!h->ivr) h->ivr = new IvrWs();
     return (IvrWs*)h->ivr;
 }
 void ivr_release(gpimhip_ctx* h) {
     IvrWs* w = (IvrWs*)h->ivr;
     if (!w) return;
-    dev_release(h, w->W, w->C, w->part, w->tiles, w->g, w->live, w->row);
+    dev_release(h, w->W, w->C, w->part, w->tiles, w->g, w->live, w->row, w->bpart, w->v, w->gs, w->inc);
     delete w;
     h->ivr = nullptr;
 }
@@ -224,6 +215,18 @@ __global__ __launch_bounds__(1024) void ivr_pick_kernel(const double* __restrict
     }
 }
 
+int launch_ivr_live_init(gpimhip_ctx* h, const double* mask, int64_t M, double* live) {
+    hipLaunchKernelGGL(ivr_live_init_kernel, ivr_grid(M), dim3(256), 0, h->stream, mask, M, live);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+int launch_ivr_pick(gpimhip_ctx* h, const double* map, int64_t M, int r, double* live, int64_t* idx_out, double* val_out,
+                    int64_t* count_out) {
+    hipLaunchKernelGGL(ivr_pick_kernel, dim3(1), dim3(1024), 0, h->stream, map, M, r, live, idx_out, val_out, count_out);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
 // g_m = C_mp / sqrt(max(C_pp, 0) + noise + jitter) for m < M from lower-stored C (C[m][p] for m >= p, C[p][m] for m < p),
 // 0 for M <= m < mp and everywhere when there was no pick (p < 0: the pass then leaves C as it is)
 __global__ __launch_bounds__(256) void ivr_gather_kernel(const double* __restrict__ C, int64_t ld, int64_t M, int64_t mp,
@@ -264,6 +267,33 @@ static int ivr_tiles_ensure(gpimhip_ctx* h, IvrWs* w, int nt) {
     return GPIMHIP_OK;
 }
 
+// W = L^-1 K* chunk by chunk of the K* slab, and the mean K*^T alpha (predict_cols' launches, EPI_STORE for EPI_COLSUMSQ)
+int ivr_build_w(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, const double* Xs, int64_t M, double* W,
+                int64_t ldm, double* mean_out) {
+    const int64_t np = h->np;
+    const int64_t mc = predict_chunk_cols(np, 1, M);
+    GP_TRY(ws_ensure_predict(h, np, mc));
+    for (int64_t m0 = 0; m0 < M; m0 += mc) {
+        const int64_t cnt = std::min(mc, M - m0), cpad = pad_to(cnt, NB);
+        const int64_t mcap = h->ks_cols, kld = mcap + 16;                       // buffer strides follow the capacity
+        GP_TRY(launch_kmat(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, np * kld));
+        if (mean_out) {
+            GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
+            GP_TRY(launch_copy_slice(h, h->mean_tmp, mean_out + m0, cnt, mcap, M));
+        }
+        GP_TRY(ws_ensure_predict(h, np, cpad));                                 // (the tile list of this chunk's column blocks)
+        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, W, ldm, 1.0, 0.0, h->pred_tiles, (int)h->pred_ntiles, np);
+        g.c_coff = (int)(m0 / NB);
+        g.chunk = deal_chunk(g.ntiles);
+        g.rag = rag_of(N, np);
+        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_STORE, g)); }
+    }
+    // rows >= N of W: the identity padding of L^-1 gives zeros, but a ragged launch skips the rows >= 64 of the last block
+    // row (GemmArgs::rag) and W may hold what an earlier call left there
+    if (np > N) HIP_TRY(hipMemsetAsync(W + N * ldm, 0, (size_t)((np - N) * ldm) * sizeof(double), h->stream));
+    return GPIMHIP_OK;
+}
+
 // what gpimhip_ivr_greedy adds to the map of round 0 (q picks; the outputs of the entry, device pointers)
 struct IvrGreedy {
     int32_t q;
@@ -271,15 +301,13 @@ struct IvrGreedy {
     int64_t *idx, *count;
 };
 
-static inline dim3 ivr_grid(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)); }
-
 // The map of round 0 into acq_out (gpimhip_ivr_exact: greedy == nullptr, the mask multiplied in), then for a greedy batch
 // the q - 1 conditioned rounds, every launch enqueued before the one synchronisation at the end.
 static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
                     const double* u, const double* Xs, int64_t M, const double* weights, const double* mask, double* mean_out,
                     double* sd_out, double* acq_out, const IvrGreedy* greedy) {
     HIP_TRY(hipSetDevice(h->device));
-    IvrWs* w = iws(h);
+    IvrWs* w = ivr_ws(h);
     const int64_t npn = pad_to(N, NB), mp = pad_to(M, NB), ldm = mp + 16;       // (no power-of-two row stride)
     const int nt = (int)(mp / NB);
     // the entry's own buffers first: the model's state is not enqueued when they do not fit
@@ -302,27 +330,7 @@ static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, c
         gpim_set_error(std::string(who) + ": the workspace's padded order is not pad(N, 128)");
         return GPIMHIP_E_BADARG;
     }
-    // W = L^-1 K* chunk by chunk of the K* slab, and the mean K*^T alpha (predict_cols' launches, EPI_STORE for EPI_COLSUMSQ)
-    const int64_t mc = predict_chunk_cols(np, 1, M);
-    GP_TRY(ws_ensure_predict(h, np, mc));
-    for (int64_t m0 = 0; m0 < M; m0 += mc) {
-        const int64_t cnt = std::min(mc, M - m0), cpad = pad_to(cnt, NB);
-        const int64_t mcap = h->ks_cols, kld = mcap + 16;                       // buffer strides follow the capacity
-        GP_TRY(launch_kmat(h, m, X, N, Xs + m0 * m->dim, cnt, h->theta, 0.0, 0, h->Ks, kld, np, cpad, 0, 0, 0, 0, np * kld));
-        if (mean_out) {
-            GP_TRY(launch_gemv_t(h, h->Ks, kld, np, cpad, h->alpha, h->mean_tmp, 0, np * kld, np, mcap));
-            GP_TRY(launch_copy_slice(h, h->mean_tmp, mean_out + m0, cnt, mcap, M));
-        }
-        GP_TRY(ws_ensure_predict(h, np, cpad));                                 // (the tile list of this chunk's column blocks)
-        GemmArgs g = gemm_args(h->A, h->ld, h->Ks, kld, w->W, ldm, 1.0, 0.0, h->pred_tiles, (int)h->pred_ntiles, np);
-        g.c_coff = (int)(m0 / NB);
-        g.chunk = deal_chunk(g.ntiles);
-        g.rag = rag_of(N, np);
-        { StageTimer t(h, 3); GP_TRY(launch_gemm(h, false, true, EPI_STORE, g)); }
-    }
-    // rows >= N of W: the identity padding of L^-1 gives zeros, but a ragged launch skips the rows >= 64 of the last block
-    // row (GemmArgs::rag) and W may hold what an earlier call left there
-    if (np > N) HIP_TRY(hipMemsetAsync(w->W + N * ldm, 0, (size_t)((np - N) * ldm) * sizeof(double), h->stream));
+    GP_TRY(ivr_build_w(h, m, X, N, Xs, M, w->W, ldm, mean_out));
     // lower tiles of K(G, G), then C -= W^T W on them (TN; the product is not done for the upper half)
     GP_TRY(launch_kmat(h, m, Xs, M, nullptr, M, h->theta, 0.0, 0, w->C, ldm, mp, mp, 1, 1, 0, 0, 0));
     {
@@ -337,8 +345,7 @@ static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, c
     const double* Cc = w->C;
     if (greedy) {
         // the live vector stands in for the mask from round 0 on: 1 * a is a
-        hipLaunchKernelGGL(ivr_live_init_kernel, ivr_grid(M), dim3(256), 0, h->stream, mask, M, (double*)w->live);
-        HIP_TRY(hipGetLastError());
+        GP_TRY(launch_ivr_live_init(h, mask, M, w->live));
         mask = w->live;
     }
     hipLaunchKernelGGL(colsq_sym_kernel<false>, tiles, dim3(256), 0, h->stream, Cc, ldm, M, mp, weights, (double*)w->part,
@@ -361,9 +368,7 @@ static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, c
                                M, th, mask, (double*)nullptr, map);
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(ivr_pick_kernel, dim3(1), dim3(1024), 0, h->stream, (const double*)map, M, r, (double*)w->live,
-                           greedy->idx, greedy->gain, greedy->count);
-        HIP_TRY(hipGetLastError());
+        GP_TRY(launch_ivr_pick(h, map, M, r, w->live, greedy->idx, greedy->gain, greedy->count));
     }
     if (greedy && greedy->sd_after) {
         hipLaunchKernelGGL(ivr_gather_kernel, ivr_grid(mp), dim3(256), 0, h->stream, Cc, ldm, M, mp, th,
@@ -377,7 +382,7 @@ static int ivr_impl(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, c
 }
 
 // what both entries refuse, with the reason
-static int ivr_check(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, bool pointers, int64_t N, int64_t M) {
+int ivr_check(gpimhip_ctx* h, const char* who, const gpimhip_model_t* m, bool pointers, int64_t N, int64_t M) {
     if (!h || !pointers || N < 1 || M < 1) {
         gpim_set_error(std::string(who) + ": null argument, N < 1 or M < 1");
         return GPIMHIP_E_BADARG;

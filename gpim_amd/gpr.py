@@ -397,6 +397,43 @@ class reconstructor(_solvers.HostDriver):
                 "sd_after": host[q + 2].reshape(shape)}
         return points, gain_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
 
+    def acq_batch(self, n_points, acquisition_function='cb', Xtest=None, mask=None, alpha=0, beta=1, xi=0.01):
+        """A batch of ``n_points`` measurements for the acquisition function 'cb', 'ei' or 'poi' by the kriging believer
+        (GP-BUCB for 'cb'), at the current hyper-parameters: ``(points, values, maps)``.  After each pick the model is
+        conditioned on the pick having been measured at its posterior mean -- the mean map stays, the variance drops as in
+        ``ivr_batch`` -- and the next pick maximises the acquisition function of the conditioned model, so two neighbouring
+        maxima that explain the same pixels are not both taken.  ``points``: list of grid-index tuples in pick order (fewer
+        than ``n_points`` when the unmasked candidates run out); ``values``: ndarray, the map value each pick had when it
+        was taken; ``maps``: dict with ``'acq'`` (q, *grid), q = min(n_points, grid points): the map each pick was taken
+        from (NaN at masked candidates and earlier picks, all NaN once the candidates have run out), ``'mean'``, ``'sd'``:
+        as ``predict``, and ``'sd_after'``: the sd once the batch is measured.  ``alpha``, ``beta``: of 'cb'; ``xi``: of
+        'ei' / 'poi', whose incumbent is taken over the model's training inputs and the believed values.  ``Xtest``,
+        ``mask`` as in ``ivr_batch``.  ValueError for n_points < 1, a grid that is not finite, a bad mask or another
+        acquisition function.  One prediction plus one pass over L^-1 K(X, grid) per pick, no grid x grid matrix (DESIGN.md
+        section 28).  Dense double-precision models only, as ``ivr``."""
+        from . import acqfunc
+        if acquisition_function not in ("cb", "ei", "poi"):
+            raise ValueError("acq_batch: the acquisition function must be 'cb', 'ei' or 'poi'; got %r" % (acquisition_function,))
+        if int(n_points) < 1:
+            raise ValueError("acq_batch: n_points must be >= 1; got %r" % (n_points,))
+        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+            raise ValueError("acq_batch: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        self._solver._believer_supported(self)
+        self._resolve_test_grid(Xtest)
+        shape = tuple(self.fulldims)
+        q = min(int(n_points), int(self._Xtest_d.shape[0]))
+        idx_d, val_d, count_d, maps_d, mean_d, sd_d, after_d = acqfunc.believer_on_device(
+            self, acquisition_function, self._Xtest_d, q, p0=alpha, p1=beta, xi=xi,
+            mask_d=acqfunc._ivr_mask(mask, shape, self._dev))
+        self._last_pred = (mean_d, sd_d)
+        n = int(count_d.item())
+        flat = idx_d[:n].cpu().numpy()
+        points = [tuple(int(v) for v in p) for p in np.stack(np.unravel_index(flat, shape), axis=-1)]
+        host = torch.cat([maps_d, torch.stack([mean_d, sd_d, after_d])]).cpu().numpy().astype(self._np_out, copy=False)
+        maps = {"acq": host[:q].reshape((q,) + shape), "mean": host[q].reshape(shape), "sd": host[q + 1].reshape(shape),
+                "sd_after": host[q + 2].reshape(shape)}
+        return points, val_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
+
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no
         change of the stored test grid.  Internal: the device-resident acquisition path of boptimizer."""

@@ -63,6 +63,10 @@ class skreconstructor(reconstructor):
 
     ivr_batch = ivr
 
+    def acq_batch(self, *args, **kwargs):
+        raise NotImplementedError("acq_batch(): believer batches belong to the dense exact GP of reconstructor; "
+                                  "skreconstructor models grids through structured solvers")
+
     @staticmethod
     def _choose_solver(X, y, kernel):
         """('kronecker' | 'reflection', None) on a complete grid; on an incomplete one ('border', border_blocks(X, y)) when

@@ -846,6 +846,35 @@ int gpimhip_ivr_greedy(gpimhip_handle h, const gpimhip_model_t* m, const double*
                        double* mean_out, double* sd_out, double* maps_out, double* sd_after_out, int64_t* idx_out,
                        double* gain_out, int64_t* count_out);
 
+/* Believer batch of q picks for the acquisition functions CB / EI / POI (kriging believer; for CB: GP-BUCB) -- DESIGN.md
+ * section 28.  After picking p the model is conditioned on p having been measured at its posterior mean: the mean map does
+ * not change, the latent variance v drops as in gpimhip_ivr_greedy,
+ *   c = k(Xs, x_p) - W^T W[:, p] - sum_{s < r} g^(s) g^(s)[p],   g^(r) = c / sqrt(max(c_p, 0) + noise + jitter),   v -= g^(r) o g^(r)
+ * (W = L^-1 K(X, Xs); a pivoted partial Cholesky of the posterior covariance: no M x M matrix is formed), and the next
+ * pick maximises the acquisition function of (mean, sqrt(max(v, 0) + noise)).  Round 0 is gpimhip_acquire_exact's map on the
+ * general engine; the incumbent of EI / POI is that entry's (nanmax of the posterior at Xobs: means for EI, means and sds
+ * for POI) and takes in every believed value: b <- max(b, mean[p]) for EI, max(b, mean[p], sd[p] after the update) for POI.
+ * Pick r is the largest entry of round r's map among the live candidates, ties to the larger flat index, NaN never, as
+ * gpimhip_ivr_greedy.  One pass over W per pick, all launches enqueued up front, one synchronisation at the end; fixed
+ * summation order, no atomics: two calls give the same bits.
+ *   Xobs, Mobs         the observed rows (EI / POI; NULL / 0 for CB)
+ *   kind, p0, p1       GPIMHIP_ACQ_CB: p0 * mean + p1 * sd; GPIMHIP_ACQ_EI / _POI: p1 = xi, p0 is not read
+ *   mask               M doubles of 1 / NaN (device) or NULL: excludes candidates
+ *   q                  1 <= q <= M
+ *   mean_out, sd_out   M doubles each: the posterior BEFORE the batch (sd includes the noise, excludes the jitter)
+ *   maps_out           q x M doubles or NULL: row r = the map pick r was taken from, NaN at masked and earlier picks
+ *   sd_after_out       M doubles or NULL: sqrt(max(v, 0) + noise) after all picks
+ *   idx_out, val_out   q each (device): the flat index of pick r and its map value; -1 / NaN once no live candidate is left
+ *   count_out          1 int64 (device): picks made
+ * W is gpimhip_ivr_exact's buffer; the partial sums, v, the q x M scaled columns, the live vector, the incumbents and a
+ * scratch map row join it under the same rules (grow-only, counted, released with the handle, allocated before anything
+ * is enqueued).  Refuses what gpimhip_ivr_exact refuses, q < 1, q > M, a kind outside CB / EI / POI, EI / POI without
+ * Xobs, and NULL idx_out / val_out / count_out / mean_out / sd_out: GPIMHIP_E_BADARG with a reason in gpimhip_last_error(). */
+int gpimhip_acquire_batch(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                          const double* u, const double* Xs, int64_t M, const double* Xobs, int64_t Mobs, int32_t kind,
+                          double p0, double p1, const double* mask, int32_t q, double* mean_out, double* sd_out,
+                          double* maps_out, double* sd_after_out, int64_t* idx_out, double* val_out, int64_t* count_out);
+
 /* Batch thinning of boptimizer.update_points (gpim/gpbayes/boptim.py:326-376): among n <= 1024 ranked
  * candidates (vals, flat grid indices into a d-dimensional grid of the given shape) repeatedly keep the
  * largest remaining value and drop every candidate within Euclidean index distance <= dscale of it
