@@ -192,13 +192,17 @@ class Dense:
         return o._handle.lib.gpimhip_ivr_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
                                                Xs.shape[0], ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
 
-    def _ivr_supported(self, o):
+    def _needs_w(self, o, who, what, cancels):
+        """Refuses what is built on W = L^-1 K(X, grid) (integrated variance reduction, believer batches) where the path has
+        no such W (``no_ivr`` says why) or computes in single precision (``cancels``: what would cancel there)."""
         if self.no_ivr:
-            raise NotImplementedError("ivr(): the %s solver has no integrated variance reduction -- %s"
-                                      % (type(self).__name__, self.no_ivr))
+            raise NotImplementedError("%s: the %s solver has no %s -- %s" % (who, type(self).__name__, what, self.no_ivr))
         if o.precision == "single":
-            raise NotImplementedError("ivr(): C = K** - W^T W cancels to the posterior variance, which single precision does "
-                                      "not resolve: build the model with precision='double'")
+            raise NotImplementedError("%s: %s to the posterior variance, which single precision does not resolve: build the "
+                                      "model with precision='double'" % (who, cancels))
+
+    def _ivr_supported(self, o):
+        self._needs_w(o, "ivr()", "integrated variance reduction", "C = K** - W^T W cancels")
 
     def ivr_greedy(self, o, Xs, weights, mask, q, mean, sd, maps, sd_after, idx, gain, count):
         """A greedy batch of q picks by integrated variance reduction at the rows Xs: pick r maximises the map of the
@@ -223,13 +227,7 @@ class Dense:
 
     def _believer_supported(self, o):
         # (the paths without integrated variance reduction have no conditioned columns either, for the same reasons)
-        if self.no_ivr:
-            raise NotImplementedError("acq_batch(): the %s solver has no believer batch -- %s"
-                                      % (type(self).__name__, self.no_ivr))
-        if o.precision == "single":
-            raise NotImplementedError("acq_batch(): v = s2 - sum W^2 and the conditioned columns cancel to the posterior "
-                                      "variance, which single precision does not resolve: build the model with "
-                                      "precision='double'")
+        self._needs_w(o, "acq_batch()", "believer batch", "v = s2 - sum W^2 and the conditioned columns cancel")
 
     def sample(self, o, Xs, z, noiseless, jitter, mean, var, out):
         """Joint posterior draws out[s] = mean + chol(Sigma) z[s] at the rows Xs (csrc/sample.hip).  The dense model only:

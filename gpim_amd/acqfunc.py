@@ -226,18 +226,25 @@ def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None):
     before the batch, ``sd_after`` the sd once the batch is measured.  Arguments as ``ivr_on_device``; 1 <= q <= M.  One
     library call (gpimhip_ivr_greedy).  Dense double-precision models only."""
     M = _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d)
-    q = int(q)
-    if q < 1 or q > M:
-        raise ValueError("ivr: a batch of %d picks from %d candidates (1 <= q <= M)" % (q, M))
-    dev = Xf_d.device
-    mean_d, sd_d, sd_after_d = (torch.empty((M,), dtype=_F64, device=dev) for _ in range(3))
-    maps_d = torch.empty((q, M), dtype=_F64, device=dev)
-    gain_d = torch.empty((q,), dtype=_F64, device=dev)
-    idx_d = torch.empty((q,), dtype=torch.int64, device=dev)
-    count_d = torch.zeros((1,), dtype=torch.int64, device=dev)
+    q, out = _batch_outputs("ivr", q, M, Xf_d.device)
+    idx_d, gain_d, count_d, maps_d, mean_d, sd_d, sd_after_d = out
     _lib.check(gpmodel._solver.ivr_greedy(gpmodel, Xf_d, weights_d, mask_d, q, mean_d, sd_d, maps_d, sd_after_d, idx_d,
                                           gain_d, count_d))
-    return idx_d, gain_d, count_d, maps_d, mean_d, sd_d, sd_after_d
+    return out
+
+
+def _batch_outputs(who, q, M, dev):
+    """``q`` as an int, checked (1 <= q <= M; ``who`` opens the message), and the seven device tensors a batch entry fills:
+    ``(idx (q,) int64, val (q,), count (1,) int64 zero, maps (q, M), mean, sd, sd_after (M,))``."""
+    q = int(q)
+    if q < 1 or q > M:
+        raise ValueError("%s: a batch of %d picks from %d candidates (1 <= q <= M)" % (who, q, M))
+    mean_d, sd_d, sd_after_d = (torch.empty((M,), dtype=_F64, device=dev) for _ in range(3))
+    maps_d = torch.empty((q, M), dtype=_F64, device=dev)
+    val_d = torch.empty((q,), dtype=_F64, device=dev)
+    idx_d = torch.empty((q,), dtype=torch.int64, device=dev)
+    count_d = torch.zeros((1,), dtype=torch.int64, device=dev)
+    return q, (idx_d, val_d, count_d, maps_d, mean_d, sd_d, sd_after_d)
 
 
 def believer_on_device(gpmodel, kind, Xf_d, q, p0=0., p1=1., xi=0.01, mask_d=None, Xobs_d=None):
@@ -257,21 +264,14 @@ def believer_on_device(gpmodel, kind, Xf_d, q, p0=0., p1=1., xi=0.01, mask_d=Non
         raise ValueError("acq_batch: the acquisition function must be 'cb', 'ei' or 'poi'; got %r" % (kind,))
     gpmodel._solver._believer_supported(gpmodel)
     M = _ivr_check_args(gpmodel, Xf_d, None, mask_d)
-    q = int(q)
-    if q < 1 or q > M:
-        raise ValueError("acq_batch: a batch of %d picks from %d candidates (1 <= q <= M)" % (q, M))
+    q, out = _batch_outputs("acq_batch", q, M, Xf_d.device)
+    idx_d, val_d, count_d, maps_d, mean_d, sd_d, sd_after_d = out
     if kind != "cb" and Xobs_d is None:
         Xobs_d = gpmodel._Xd
     a, b = (p0, p1) if kind == "cb" else (0.0, xi)
-    dev = Xf_d.device
-    mean_d, sd_d, sd_after_d = (torch.empty((M,), dtype=_F64, device=dev) for _ in range(3))
-    maps_d = torch.empty((q, M), dtype=_F64, device=dev)
-    val_d = torch.empty((q,), dtype=_F64, device=dev)
-    idx_d = torch.empty((q,), dtype=torch.int64, device=dev)
-    count_d = torch.zeros((1,), dtype=torch.int64, device=dev)
     _lib.check(gpmodel._solver.believer(gpmodel, kind, Xf_d, None if kind == "cb" else Xobs_d, a, b, mask_d, q, mean_d, sd_d,
                                         maps_d, sd_after_d, idx_d, val_d, count_d))
-    return idx_d, val_d, count_d, maps_d, mean_d, sd_d, sd_after_d
+    return out
 
 
 def _ivr_mask(mask, shape, dev):

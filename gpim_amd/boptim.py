@@ -328,7 +328,9 @@ class boptimizer:
             if self._Xfull_d is None:
                 self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
             if self.batch_update and self.acq_batch == 'believer':
-                return self._next_batch_believer(tuple(np.shape(self.X_full)[1:]))
+                return self._next_batch_on_device(tuple(np.shape(self.X_full)[1:]), lambda sm, Xf_d, q, mask_d: (
+                    acqfunc.believer_on_device(sm, af, Xf_d, q, p0=self.alpha, p1=self.beta, xi=self.xi, mask_d=mask_d,
+                                               Xobs_d=self._observed_rows_d())))
             acq_d, mean_d, sd_d = acqfunc.acquisition_on_device(sm, af, self.X_full, self.X_sparse, p0, p1, self.xi,
                                                                 Xf_d=self._Xfull_d,
                                                                 mask_d=self._device_mask(self._Xfull_d.shape[0]),
@@ -360,7 +362,8 @@ class boptimizer:
                 self._Xfull_d = sm._to_device(gprutils.prepare_test_data(np.asarray(self.X_full), precision=self.precision))
             grid_shape = tuple(np.shape(self.X_full)[1:])
             if self.batch_update and self.ivr_batch == 'greedy':
-                return self._next_batch_ivr_greedy(grid_shape)
+                return self._next_batch_on_device(grid_shape, lambda sm, Xf_d, q, mask_d: acqfunc.ivr_greedy_on_device(
+                    sm, Xf_d, q, weights_d=self._ivr_weights_d, mask_d=mask_d))
             acq_d, mean_d, sd_d = acqfunc.ivr_on_device(sm, self._Xfull_d, weights_d=self._ivr_weights_d,
                                                         mask_d=self._device_mask(self._Xfull_d.shape[0]))
             mean_d, sd_d = self._retain_maps(mean_d, sd_d)
@@ -381,32 +384,14 @@ class boptimizer:
             radius = sm.model.kernel.lengthscale.mean().item()
         return self.update_points(vals_list, indices_list, radius)
 
-    def _next_batch_ivr_greedy(self, grid_shape):
-        """The ``batch_out_max`` greedy picks by integrated variance reduction and their gains, from one library call
-        (acqfunc.ivr_greedy_on_device); (mean, sd) of the step are the posterior before the batch."""
+    def _next_batch_on_device(self, grid_shape, call):
+        """The ``batch_out_max`` picks of a batch entry and their values, from one library call: ``call(sm, Xfull_d, q,
+        mask_d)`` is acqfunc.ivr_greedy_on_device or acqfunc.believer_on_device with the optimiser's settings; (mean, sd) of
+        the step are the posterior before the batch."""
         sm = self.surrogate_model
         M = self._Xfull_d.shape[0]
         q = int(min(self.batch_out_max, M))
-        idx_d, gain_d, count_d, _, mean_d, sd_d, _ = acqfunc.ivr_greedy_on_device(
-            sm, self._Xfull_d, q, weights_d=self._ivr_weights_d, mask_d=self._device_mask(M))
-        mean_d, sd_d = self._retain_maps(mean_d, sd_d)
-        self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
-        # one device-to-host copy: [count | q indices | q gains (as bits)]
-        host = torch.cat([count_d, idx_d, gain_d.view(torch.int64)]).cpu().numpy()
-        n = int(host[0])
-        flat = host[1:1 + n]
-        vals_list = host[q + 1:q + 1 + n].view(np.float64).tolist()
-        return vals_list, np.stack(np.unravel_index(flat, tuple(grid_shape)), axis=-1).tolist()
-
-    def _next_batch_believer(self, grid_shape):
-        """The ``batch_out_max`` believer picks of 'cb' / 'ei' / 'poi' and their values, from one library call
-        (acqfunc.believer_on_device); (mean, sd) of the step are the posterior before the batch."""
-        sm = self.surrogate_model
-        M = self._Xfull_d.shape[0]
-        q = int(min(self.batch_out_max, M))
-        idx_d, val_d, count_d, _, mean_d, sd_d, _ = acqfunc.believer_on_device(
-            sm, self.acquisition_function, self._Xfull_d, q, p0=self.alpha, p1=self.beta, xi=self.xi,
-            mask_d=self._device_mask(M), Xobs_d=self._observed_rows_d())
+        idx_d, val_d, count_d, _, mean_d, sd_d, _ = call(sm, self._Xfull_d, q, self._device_mask(M))
         mean_d, sd_d = self._retain_maps(mean_d, sd_d)
         self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
         # one device-to-host copy: [count | q indices | q values (as bits)]

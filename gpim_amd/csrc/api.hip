@@ -16,6 +16,7 @@
 #include "vgp.hpp"
 #include "sm.hpp"
 #include "sample.hpp"
+#include "acq.hpp"
 
 static thread_local std::string g_err;
 void gpim_set_error(const std::string& s) { g_err = s; }
@@ -980,9 +981,7 @@ extern "C++" PredictFamily stationary_family(gpimhip_ctx* h, const gpimhip_model
         };
         return f;
     }
-    f.fused = [=] {
-        return launch_predict_fused(h, m, X, x_bs, N, Xs, M, mean_out, var_out, nullptr, nullptr, -1, 0.0, nullptr, 0.0, nullptr);
-    };
+    f.fused = [=] { return launch_predict_fused(h, m, X, x_bs, N, Xs, M, mean_out, var_out); };
     f.slab = [=](const PredictChunk& c) {
         return launch_kmat(h, m, X, N, c.Z, c.cnt, h->theta, 0.0, 0, h->Ks, c.kld, h->np, c.cpad, 0, 0, x_bs, 0, h->np * c.kld);
     };
@@ -1143,87 +1142,6 @@ int gpimhip_loo_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, const 
     return loo_impl(h, m, X, x_stride, y, N, B, u, rep, sgn, y_grid, mean_out, var_out, score_out);
 }
 
-int gpimhip_acq(gpimhip_handle h, int32_t kind, const double* mean, const double* sd, int64_t M, double p0,
-                double p1, const double* mask, double* acq_out) {
-    if (!h || !mean || !sd || !acq_out || M < 1 || kind < 0 || kind > GPIMHIP_ACQ_POI) return GPIMHIP_E_BADARG;
-    HIP_TRY(hipSetDevice(h->device));
-    return launch_acq(h, kind, mean, sd, M, p0, p1, mask, acq_out);
-}
-
-static int sel_scratch_ensure(gpimhip_ctx* h);
-
-int gpimhip_acquire_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
-                          const double* u, const double* Xs, int64_t M, const double* Xobs, int64_t Mobs, int32_t kind,
-                          double p0, double p1, const double* mask, double* mean_out, double* sd_out, double* acq_out) {
-    if (!h || !X || !y || !u || !Xs || M < 1 || N < 1 || !mean_out || !sd_out || !acq_out || kind < 0 ||
-        kind > GPIMHIP_ACQ_POI || (kind != GPIMHIP_ACQ_CB && (!Xobs || Mobs < 1)))
-        return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
-    HIP_TRY(hipSetDevice(h->device));
-    h->nbatch = 1;
-    GP_TRY(ws_ensure_padded(h, N));
-    const int64_t np = h->np;
-    HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    GP_TRY(launch_pad_copy(h, y, N, h->ypad, np));
-    GP_TRY(factor_at_u(h, m, X, 0, N, u));
-    const bool fused = !h->fp32 && fused_predict_fits(np);
-    const double* inc = nullptr;
-    if (kind != GPIMHIP_ACQ_CB) {
-        // incumbent = nanmax of the posterior at the observed rows (EI: means; POI: means and sds), on device
-        GP_TRY(h->acq_tmp.grow(h, 2 * Mobs + 2));
-        double *mo = h->acq_tmp, *so = h->acq_tmp + Mobs, *best = h->acq_tmp + 2 * Mobs;
-        if (fused) {
-            GP_TRY(launch_predict_fused(h, m, X, 0, N, Xobs, Mobs, mo, nullptr, so, nullptr, -1, 0.0, nullptr, 0.0, nullptr));
-        } else {
-            GP_TRY(predict_cols(h, stationary_family(h, m, X, 0, N, 1, Xobs, Mobs, mo, so), N, 1));
-            GP_TRY(launch_acq_from_var(h, kind, mo, so, Mobs, 0.0, nullptr, 0.0, nullptr, so, nullptr));
-        }
-        const int64_t nmax = (kind == GPIMHIP_ACQ_EI) ? Mobs : 2 * Mobs;
-        if (nmax <= 4096) {
-            GP_TRY(launch_nanmax(h, mo, nmax, best));
-        } else {
-            GP_TRY(sel_scratch_ensure(h));
-            GP_TRY(launch_nanmax_two_stage(h, mo, nmax, best));
-        }
-        inc = best;
-    }
-    if (fused) {
-        GP_TRY(launch_predict_fused(h, m, X, 0, N, Xs, M, mean_out, nullptr, sd_out, acq_out, kind, p0, inc, p1, mask));
-    } else {
-        // sd_out doubles as the variance buffer of the slab path
-        GP_TRY(predict_cols(h, stationary_family(h, m, X, 0, N, 1, Xs, M, mean_out, sd_out), N, 1));
-        GP_TRY(launch_acq_from_var(h, kind, mean_out, sd_out, M, p0, inc, p1, mask, sd_out, acq_out));
-    }
-    return finish_and_check(h);
-}
-
-static int sel_scratch_ensure(gpimhip_ctx* h) {
-    if (h->sel_scratch) return GPIMHIP_OK;
-    return h->sel_scratch.alloc(h, (int64_t)sel_scratch_bytes());
-}
-
-int gpimhip_nanmax(gpimhip_handle h, const double* x, int64_t n, double* out) {
-    if (!h || !x || !out || n < 1) return GPIMHIP_E_BADARG;
-    HIP_TRY(hipSetDevice(h->device));
-    if (n <= 4096) return launch_nanmax(h, x, n, out);
-    GP_TRY(sel_scratch_ensure(h));
-    return launch_nanmax_two_stage(h, x, n, out);
-}
-
-int gpimhip_topk(gpimhip_handle h, const double* acq, int64_t M, int32_t k, int32_t keep_nan, double* vals_out,
-                 int64_t* idx_out, int64_t* count_out) {
-    if (!h || !acq || !vals_out || !idx_out || !count_out || M < 1 || k < 1) return GPIMHIP_E_BADARG;
-    HIP_TRY(hipSetDevice(h->device));
-    GP_TRY(h->keys.grow(h, M));
-    // large grids: multi-block radix selection (15 launches, O(M) each); small ones: k arg-max passes of one
-    // workgroup (2 launches)
-    if (M > 2048 && k <= 1024 && M < ((int64_t)1 << 32) && !getenv("GPIMHIP_NO_RADIX_TOPK")) {
-        GP_TRY(sel_scratch_ensure(h));
-        return launch_topk_radix(h, acq, M, k, keep_nan, vals_out, idx_out, count_out);
-    }
-    return launch_topk(h, acq, M, k, keep_nan, vals_out, idx_out, count_out);
-}
-
 int gpimhip_set_reflection(gpimhip_handle h, int32_t mask, const double* twoc, const double* wts, int64_t n_total,
                            int64_t var_count) {
     if (!h || mask < 0 || mask >= (1 << GPIMHIP_MAX_DIM) || (mask && !twoc) || n_total < 0 || var_count < 0) return GPIMHIP_E_BADARG;
@@ -1282,15 +1200,6 @@ int gpimhip_refl_sums(gpimhip_handle h, const gpimhip_model_t* m, const double* 
     GP_TRY(launch_lauum(h, h->A, h->B, np, h->ld, rag_of(N, np)));
     GP_TRY(launch_grad_reduce_refl(h, m, h->B, h->ld, X, N, (int)(np / NB), h->alpha, 0));
     return launch_coupled_sums(h, np, sums_out);
-}
-
-int gpimhip_thin_batch(gpimhip_handle h, const double* vals, const int64_t* flat_idx, int32_t n, int32_t d,
-                       const int64_t* shape, double dscale, int32_t max_out, int32_t* keep_out, int32_t* nkeep_out) {
-    if (!h || !vals || !flat_idx || !shape || !keep_out || !nkeep_out || n < 1 || n > 1024 || d < 1 ||
-        d > GPIMHIP_MAX_DIM || max_out < 1)
-        return GPIMHIP_E_BADARG;
-    HIP_TRY(hipSetDevice(h->device));
-    return launch_thin_batch(h, vals, flat_idx, n, d, shape, dscale, max_out, keep_out, nkeep_out);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@
 #include "common.hpp"
 #include "kfun.hpp"
 #include "ivr.hpp"
+#include "acq.hpp"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -124,17 +125,6 @@ __global__ __launch_bounds__(256) void believer_col_kernel(const double* __restr
     bel_pass<false>(W, ldm, np, mp, rc, p, part, colp, red);
 }
 
-// the acquisition sweep of acq_kernel (select.hip); a = alpha (CB) or the incumbent (EI / POI), b = beta or xi
-__device__ __forceinline__ double bel_acq(int kind, double mu, double s, double a, double b) {
-    if (kind == GPIMHIP_ACQ_CB) return a * mu + b * s;
-    const double imp = mu - a - b;
-    const double zz = imp / s;
-    const double cdf = 0.5 * erfc(-zz * 0.7071067811865476);
-    if (kind == GPIMHIP_ACQ_POI) return cdf;
-    const double pdf = exp(-0.5 * zz * zz) * 0.3989422804014327;
-    return imp * cdf + s * pdf;
-}
-
 // Round 0: v_j = s2 - sum of the chunks' squared column sums in increasing chunk order (predict_var_kernel's prior variance
 // and order of operations), sd = sqrt(max(v, 0) + noise), map_0 = live * acq.  inc: slot 0 of the incumbents (EI / POI).
 __global__ __launch_bounds__(256) void believer_init_kernel(const double* __restrict__ part, int nR, int64_t mp, int64_t M,
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(256) void believer_init_kernel(const double* __rest
         v_out[j] = v;
         const double sd = sqrt(clamp0_nan(v) + noise);
         sd_out[j] = sd;
-        map0[j] = live[j] * bel_acq(kind, mean[j], sd, a, p1);
+        map0[j] = live[j] * acq_value(kind, mean[j], sd, a, p1);
     }
 }
 
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(256) void believer_finish_kernel(const BelFinish a)
         a.v_out[j] = v;
         const double sd = sqrt(clamp0_nan(v) + t.noise);
         if (a.sd_after) a.sd_after[j] = sd;
-        if (a.map_next) a.map_next[j] = a.live[j] * bel_acq(a.kind, a.mean[j], sd, acq_a, a.p1);
+        if (a.map_next) a.map_next[j] = a.live[j] * acq_value(a.kind, a.mean[j], sd, acq_a, a.p1);
     }
 }
 
@@ -273,11 +263,7 @@ extern "C" int gpimhip_acquire_batch(gpimhip_handle h, const gpimhip_model_t* m,
     GP_TRY(w->inc.grow(h, (int64_t)q + 1));
     if (!maps_out) GP_TRY(w->row.grow(h, M));
     const bool has_inc = kind != GPIMHIP_ACQ_CB;
-    const int64_t nmax = kind == GPIMHIP_ACQ_EI ? Mobs : 2 * Mobs;
-    if (has_inc) {
-        GP_TRY(h->acq_tmp.grow(h, 2 * Mobs + 2));
-        if (nmax > 4096 && !h->sel_scratch) GP_TRY(h->sel_scratch.alloc(h, (int64_t)sel_scratch_bytes()));
-    }
+    if (has_inc) GP_TRY(acq_incumbent_reserve(h, kind, Mobs));
     GP_TRY(model_state_at_u(h, m, X, 0, y, N, 1, u));
     const int64_t np = h->np;
     if (np != npn) {
@@ -285,16 +271,8 @@ extern "C" int gpimhip_acquire_batch(gpimhip_handle h, const gpimhip_model_t* m,
         return GPIMHIP_E_BADARG;
     }
     double* inc = w->inc;
-    if (has_inc) {
-        // b_0 = nanmax of the posterior at the observed rows (EI: means; POI: means and sds), gpimhip_acquire_exact's slab path
-        double *mo = h->acq_tmp, *so = h->acq_tmp + Mobs;
-        PredictFamily f = stationary_family(h, m, X, 0, N, 1, Xobs, Mobs, mo, so);
-        f.fused = nullptr;
-        GP_TRY(predict_cols(h, f, N, 1));
-        GP_TRY(launch_acq_from_var(h, kind, mo, so, Mobs, 0.0, nullptr, 0.0, nullptr, so, nullptr));
-        if (nmax <= 4096) GP_TRY(launch_nanmax(h, mo, nmax, inc));
-        else GP_TRY(launch_nanmax_two_stage(h, mo, nmax, inc));
-    }
+    // b_0: gpimhip_acquire_exact's incumbent, always on the slab path
+    if (has_inc) GP_TRY(acq_incumbent(h, m, X, N, Xobs, Mobs, kind, false, inc));
     GP_TRY(ivr_build_w(h, m, X, N, Xs, M, w->W, ldm, mean_out));
     GP_TRY(launch_ivr_live_init(h, mask, M, w->live));
     const dim3 pass((unsigned)(mp / BEL_STRIP), (unsigned)nR);

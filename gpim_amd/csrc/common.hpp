@@ -523,18 +523,13 @@ int launch_nanmax_two_stage(gpimhip_ctx* h, const double* x, int64_t n, double* 
 int launch_thin_batch(gpimhip_ctx* h, const double* vals, const int64_t* flat, int n, int d, const int64_t* shape,
                       double dscale, int max_out, int32_t* keep_out, int32_t* nkeep_out);
 size_t sel_scratch_bytes();
+int sel_scratch_ensure(gpimhip_ctx* h);         // (acquire.hip) h->sel_scratch, allocated once
 // smalln.hip
 int launch_fit_small(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
                      int N, double* u, const double* lr_over_bc1, const double* bc2_sqrt, int T, double* hist,
                      double* loss, double* grad);
-// predict.hip
+// predict.hip (its fused launch and the sweep behind the slab path: acq.hpp)
 bool fused_predict_fits(int64_t np);
-int launch_predict_fused(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
-                         const double* Xs, int64_t M, double* mean_out, double* var_out, double* sd_out,
-                         double* acq_out, int acq_kind, double p0, const double* p0_dev, double p1,
-                         const double* mask);
-int launch_acq_from_var(gpimhip_ctx* h, int kind, const double* mean, const double* var, int64_t M, double p0,
-                        const double* p0_dev, double p1, const double* mask, double* sd_out, double* acq_out);
 
 
 enum GemmEpi { EPI_STORE = 0, EPI_COLSUMSQ = 1 };

@@ -21,6 +21,7 @@
 // from one factorisation (colsq_tri, loo_finish, loo_score).
 #include "kfun.hpp"
 #include "tile128.hpp"
+#include "acq.hpp"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -33,10 +34,8 @@ struct FusedPredictArgs {
     const ThetaDev* th;
     const double* Linv; int64_t ld; int64_t np;
     const double* alpha;
-    double* mean_out; double* var_out;           // M each (per problem), var_out may be null when sd_out is given
-    double* sd_out; double* acq_out;             // optional (single problem only)
-    const double* mask; const double* p0_dev;
-    int acq_kind; double p0, p1;
+    double* mean_out; double* var_out;           // M each (per problem), var_out may be null when acq.sd_out is given
+    AcqOut acq;                                  // optional outputs (single problem only)
 };
 
 template <int KIND>
@@ -148,65 +147,32 @@ __global__ __launch_bounds__(256, 2) void predict_fused_kernel(FusedPredictArgs 
         const double var = clamp0_nan(t.var - q) + t.noise;
         a.mean_out[(int64_t)b * a.M + j] = mu;
         if (a.var_out) a.var_out[(int64_t)b * a.M + j] = var;
-        if (a.sd_out || a.acq_out) {
+        const AcqOut& o = a.acq;
+        if (o.sd_out || o.acq_out) {
             const double s = sqrt(var);
-            if (a.sd_out) a.sd_out[j] = s;
-            if (a.acq_out) {
-                const double p0 = a.p0_dev ? *a.p0_dev : a.p0;
-                double v;
-                if (a.acq_kind == GPIMHIP_ACQ_CB) {
-                    v = p0 * mu + a.p1 * s;
-                } else {
-                    const double imp = mu - p0 - a.p1;
-                    const double zz = imp / s;
-                    const double cdf = 0.5 * erfc(-zz * 0.7071067811865476);
-                    if (a.acq_kind == GPIMHIP_ACQ_EI) {
-                        const double pdf = exp(-0.5 * zz * zz) * 0.3989422804014327;
-                        v = imp * cdf + s * pdf;
-                    } else {
-                        v = cdf;
-                    }
-                }
-                if (a.mask) v = a.mask[j] * v;
-                a.acq_out[j] = v;
+            if (o.sd_out) o.sd_out[j] = s;
+            if (o.acq_out) {
+                double v = acq_value(o.spec.kind, mu, s, o.spec.p0_dev ? *o.spec.p0_dev : o.spec.p0, o.spec.p1);
+                if (o.spec.mask) v = o.spec.mask[j] * v;
+                o.acq_out[j] = v;
             }
         }
     }
 }
 
-// sd = sqrt(var) and the acquisition sweep for the slab path (N > 384): same formulas as acq_kernel
-// (select.hip), incumbent from device memory
-__global__ void acq_from_var_kernel(int kind, const double* __restrict__ mean, const double* __restrict__ var, int64_t M,
-                                    double p0, const double* __restrict__ p0_dev, double p1,
-                                    const double* __restrict__ mask, double* __restrict__ sd_out,
-                                    double* __restrict__ acq_out) {
+// sd = sqrt(var) and the acquisition sweep for the slab path (N > 384), incumbent from device memory
+__global__ void acq_from_var_kernel(const double* __restrict__ mean, const double* __restrict__ var, int64_t M, AcqOut o) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
     const double mu = mean[j], s = sqrt(var[j]);
-    if (sd_out) sd_out[j] = s;
-    if (!acq_out) return;
-    if (p0_dev) p0 = *p0_dev;
-    double v;
-    if (kind == GPIMHIP_ACQ_CB) {
-        v = p0 * mu + p1 * s;
-    } else {
-        const double imp = mu - p0 - p1;
-        const double zz = imp / s;
-        const double cdf = 0.5 * erfc(-zz * 0.7071067811865476);
-        if (kind == GPIMHIP_ACQ_EI) {
-            const double pdf = exp(-0.5 * zz * zz) * 0.3989422804014327;
-            v = imp * cdf + s * pdf;
-        } else {
-            v = cdf;
-        }
-    }
-    if (mask) v = mask[j] * v;
-    acq_out[j] = v;
+    if (o.sd_out) o.sd_out[j] = s;
+    if (!o.acq_out) return;
+    double v = acq_value(o.spec.kind, mu, s, o.spec.p0_dev ? *o.spec.p0_dev : o.spec.p0, o.spec.p1);
+    if (o.spec.mask) v = o.spec.mask[j] * v;
+    o.acq_out[j] = v;
 }
-int launch_acq_from_var(gpimhip_ctx* h, int kind, const double* mean, const double* var, int64_t M, double p0,
-                        const double* p0_dev, double p1, const double* mask, double* sd_out, double* acq_out) {
-    hipLaunchKernelGGL(acq_from_var_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, kind, mean, var,
-                       M, p0, p0_dev, p1, mask, sd_out, acq_out);
+int launch_acq_from_var(gpimhip_ctx* h, const double* mean, const double* var, int64_t M, const AcqOut& acq) {
+    hipLaunchKernelGGL(acq_from_var_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, mean, var, M, acq);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
 }
@@ -215,18 +181,15 @@ bool fused_predict_fits(int64_t np) {
     return np <= 384 && !getenv("GPIMHIP_NO_FUSED_PREDICT");
 }
 
-// mean / var (and optionally sd, acquisition) at M test points from the factorised model held in the
-// workspace (theta, L^-1 in A, alpha).  acq_kind < 0: no acquisition.
-int launch_predict_fused(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
-                         const double* Xs, int64_t M, double* mean_out, double* var_out, double* sd_out,
-                         double* acq_out, int acq_kind, double p0, const double* p0_dev, double p1,
-                         const double* mask) {
+// (acq.hpp) no acq: mean and var only
+int launch_predict_fused(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N, const double* Xs,
+                         int64_t M, double* mean_out, double* var_out, const AcqOut* acq) {
     FusedPredictArgs a;
     a.X = X; a.N = N; a.x_bs = x_bs; a.d = m->dim;
     a.Xs = Xs; a.M = M; a.th = h->theta;
     a.Linv = h->A; a.ld = h->ld; a.np = h->np; a.alpha = h->alpha;
-    a.mean_out = mean_out; a.var_out = var_out; a.sd_out = sd_out; a.acq_out = acq_out;
-    a.mask = mask; a.p0_dev = p0_dev; a.acq_kind = acq_kind; a.p0 = p0; a.p1 = p1;
+    a.mean_out = mean_out; a.var_out = var_out;
+    a.acq = acq ? *acq : AcqOut{{-1, 0.0, nullptr, 0.0, nullptr}, nullptr, nullptr};
     const size_t lds = ((size_t)h->np * PF_LDK + std::max<size_t>((size_t)h->np * 5, 12 * PF_CT)) * sizeof(double);
     const dim3 grid((unsigned)((M + PF_CT - 1) / PF_CT), h->nbatch);
     return with_kind(m->kernel, [&](auto K) {

@@ -13,7 +13,7 @@
 //                        candidates, in one workgroup.
 //   nanmax / topk        the single-workgroup forms, in use for small grids (M <= 2048: fewer launches)
 //   acq_kernel           the acquisition sweep CB / EI / POI over mean and sd
-#include "common.hpp"
+#include "acq.hpp"
 
 #define SEL_MAXK 1024
 
@@ -340,27 +340,13 @@ int launch_topk(gpimhip_ctx* h, const double* x, int64_t M, int k, int keep_nan,
 }
 
 // ------------------------------------------------------------------------------------------
-// acquisition sweep (acqfunc.py:11-92).  Phi / phi as scipy.stats.norm: ndtr(z) = erfc(-z/sqrt2)/2.
+// acquisition sweep (acqfunc.py:11-92): acq_value (acq.hpp) over given means and sds, the copy the goldens pin
 // ------------------------------------------------------------------------------------------
 __global__ void acq_kernel(int kind, const double* __restrict__ mean, const double* __restrict__ sd, int64_t M,
                            double p0, double p1, const double* __restrict__ mask, double* __restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
-    const double mu = mean[j], s = sd[j];
-    double a;
-    if (kind == GPIMHIP_ACQ_CB) {
-        a = p0 * mu + p1 * s;
-    } else {
-        const double imp = mu - p0 - p1;
-        const double zz = imp / s;
-        const double cdf = 0.5 * erfc(-zz * 0.7071067811865476);
-        if (kind == GPIMHIP_ACQ_EI) {
-            const double pdf = exp(-0.5 * zz * zz) * 0.3989422804014327;
-            a = imp * cdf + s * pdf;
-        } else {
-            a = cdf;
-        }
-    }
+    double a = acq_value(kind, mean[j], sd[j], p0, p1);
     if (mask) a = mask[j] * a;
     out[j] = a;
 }

@@ -39,6 +39,12 @@ from .kernels import get_kernel
 _F64 = torch.float64
 
 
+def _finite_test_grid(Xtest, who):
+    """ValueError (its message opens with ``who``) for a test grid with NaN / inf entries; None is the stored grid."""
+    if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
+        raise ValueError("%s: the test grid must be finite (NaN / inf rows have no covariance with the others)" % who)
+
+
 class _KernelView:
     """``model.kernel`` facade: constrained values as tensors (boptim.py:319 reads
     ``model.kernel.lengthscale.mean().item()``)."""
@@ -356,8 +362,7 @@ class reconstructor(_solvers.HostDriver):
         memory for M grid points.  Dense double-precision models only: sparse, structured and
         single-precision models raise NotImplementedError with the reason."""
         from . import acqfunc
-        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-            raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        _finite_test_grid(Xtest, "ivr")
         self._resolve_test_grid(Xtest)
         shape = tuple(self.fulldims)
         acq_d, mean_d, sd_d = acqfunc.ivr_on_device(self, self._Xtest_d, acqfunc._ivr_weights(weights, shape, self._dev))
@@ -381,21 +386,24 @@ class reconstructor(_solvers.HostDriver):
         from . import acqfunc
         if int(n_points) < 1:
             raise ValueError("ivr_batch: n_points must be >= 1; got %r" % (n_points,))
-        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-            raise ValueError("ivr: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        _finite_test_grid(Xtest, "ivr")
         self._resolve_test_grid(Xtest)
         shape = tuple(self.fulldims)
         q = min(int(n_points), int(self._Xtest_d.shape[0]))
-        idx_d, gain_d, count_d, maps_d, mean_d, sd_d, after_d = acqfunc.ivr_greedy_on_device(
-            self, self._Xtest_d, q, acqfunc._ivr_weights(weights, shape, self._dev), acqfunc._ivr_mask(mask, shape, self._dev))
+        return self._batch_result("ivr", q, shape, *acqfunc.ivr_greedy_on_device(
+            self, self._Xtest_d, q, acqfunc._ivr_weights(weights, shape, self._dev), acqfunc._ivr_mask(mask, shape, self._dev)))
+
+    def _batch_result(self, key, q, shape, idx_d, val_d, count_d, maps_d, mean_d, sd_d, after_d):
+        """``(points, values, maps)`` of ``ivr_batch`` (key 'ivr') / ``acq_batch`` (key 'acq') from the device tensors of
+        their entry: the picks made, the maps in one stacked copy; (mean, sd) stay on the device as the last prediction."""
         self._last_pred = (mean_d, sd_d)
         n = int(count_d.item())
         flat = idx_d[:n].cpu().numpy()
         points = [tuple(int(v) for v in p) for p in np.stack(np.unravel_index(flat, shape), axis=-1)]
         host = torch.cat([maps_d, torch.stack([mean_d, sd_d, after_d])]).cpu().numpy().astype(self._np_out, copy=False)
-        maps = {"ivr": host[:q].reshape((q,) + shape), "mean": host[q].reshape(shape), "sd": host[q + 1].reshape(shape),
+        maps = {key: host[:q].reshape((q,) + shape), "mean": host[q].reshape(shape), "sd": host[q + 1].reshape(shape),
                 "sd_after": host[q + 2].reshape(shape)}
-        return points, gain_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
+        return points, val_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
 
     def acq_batch(self, n_points, acquisition_function='cb', Xtest=None, mask=None, alpha=0, beta=1, xi=0.01):
         """A batch of ``n_points`` measurements for the acquisition function 'cb', 'ei' or 'poi' by the kriging believer
@@ -416,23 +424,14 @@ class reconstructor(_solvers.HostDriver):
             raise ValueError("acq_batch: the acquisition function must be 'cb', 'ei' or 'poi'; got %r" % (acquisition_function,))
         if int(n_points) < 1:
             raise ValueError("acq_batch: n_points must be >= 1; got %r" % (n_points,))
-        if Xtest is not None and not np.isfinite(np.asarray(Xtest, dtype=np.float64)).all():
-            raise ValueError("acq_batch: the test grid must be finite (NaN / inf rows have no covariance with the others)")
+        _finite_test_grid(Xtest, "acq_batch")
         self._solver._believer_supported(self)
         self._resolve_test_grid(Xtest)
         shape = tuple(self.fulldims)
         q = min(int(n_points), int(self._Xtest_d.shape[0]))
-        idx_d, val_d, count_d, maps_d, mean_d, sd_d, after_d = acqfunc.believer_on_device(
+        return self._batch_result("acq", q, shape, *acqfunc.believer_on_device(
             self, acquisition_function, self._Xtest_d, q, p0=alpha, p1=beta, xi=xi,
-            mask_d=acqfunc._ivr_mask(mask, shape, self._dev))
-        self._last_pred = (mean_d, sd_d)
-        n = int(count_d.item())
-        flat = idx_d[:n].cpu().numpy()
-        points = [tuple(int(v) for v in p) for p in np.stack(np.unravel_index(flat, shape), axis=-1)]
-        host = torch.cat([maps_d, torch.stack([mean_d, sd_d, after_d])]).cpu().numpy().astype(self._np_out, copy=False)
-        maps = {"acq": host[:q].reshape((q,) + shape), "mean": host[q].reshape(shape), "sd": host[q + 1].reshape(shape),
-                "sd_after": host[q + 2].reshape(shape)}
-        return points, val_d[:n].cpu().numpy().astype(self._np_out, copy=False), maps
+            mask_d=acqfunc._ivr_mask(mask, shape, self._dev)))
 
     def _predict_device(self, Xrows_d):
         """Posterior (mean, sd) device tensors at the (M, d) device rows `Xrows_d`; no host copies and no

@@ -29,6 +29,11 @@ drivers of csrc/distgp.hip:
              RBF in single) and the reflection blocks of a 16 x 16 grid (Matern52, structured=True), nll_grad and ten Adam
              iterations each; fit_predict_batch of three data sets of N = 300 (8 iterations); rec.loo() on the dense model;
              expected improvement and gpimhip_topk at M = 340 (the single-workgroup ranking)
+  acquire    the N = 300 / M = 340 data again: gpimhip_acquire_exact for cb / ei / poi, with and without a 1 / NaN mask, fused
+             and through the slab path; gpimhip_acq for the three kinds; rec.ivr(), rec.ivr_batch(4) and rec.acq_batch(4, kind)
+             (points, values and the four maps); three boptimizer steps with batch_update=True for the thinned batch,
+             ivr_batch='greedy' and acq_batch='believer' (indices and values); gpimhip_topk at M = 5000, k = 10 (radix) and
+             gpimhip_nanmax at n = 5000 (two-stage) on a seeded vector
 """
 import hashlib
 import os
@@ -174,6 +179,7 @@ def cases():
     Rd, _ = image((20, 17), 300)                  # (the data of the first case: N = 300 on a grid of M = 340)
     Xsd, Xfd = sparse_and_full(Rd)
     yield "acquisition EI + top-10, M=340", lambda: acq_topk(r, Xfd, Xsd)
+    yield from acquisition_cases(r, Rd, Xfd, Xsd)
     tr = dict(learning_rate=0.05, iterations=10, **kw)
     for kernel, precision in (("RBF", "double"), ("Matern52", "double"), ("RationalQuadratic", "double"), ("RBF", "single")):
         rd = gpim_amd.reconstructor(Xsd, Rd, Xfd, kernel=kernel, precision=precision, **tr)
@@ -241,6 +247,70 @@ def acq_topk(rec, Xf, Xs):
     cnt = torch.zeros(1, dtype=torch.int64, device=H.device)
     _lib.check(H.lib.gpimhip_topk(H.h, _lib.ptr(xd), xd.numel(), 10, 0, _lib.ptr(vals), _lib.ptr(idx), _lib.ptr(cnt)))
     return acq, mean, sd, vals.cpu().numpy(), idx.cpu().numpy(), cnt.cpu().numpy()
+
+
+def acquisition_cases(rec, R, Xf, Xs):
+    """The acquisition layer on the N = 300 / M = 340 data (np = 384: the fused launch unless the line says slab path):
+    gpimhip_acquire_exact (map, mean, sd) and gpimhip_acq for the three kinds, rec.ivr(), the two batch entries, three
+    boptimizer steps per batch mode, and the multi-block ranking forms on a seeded vector of 5000"""
+    import torch
+    from gpim_amd import _lib, acqfunc
+    H = rec._handle
+    mask = np.where(np.random.default_rng(11).uniform(size=R.shape) < 0.2, np.nan, 1.0)
+    params = {"cb": (0.3, 1.5), "ei": (0.0, 0.0), "poi": (0.0, 0.0)}
+
+    def exact(kind, masked):
+        mask_d = torch.from_numpy(mask.ravel().copy()).to(H.device) if masked else None
+        return [t.cpu().numpy() for t in acqfunc.acquisition_on_device(rec, kind, Xf, Xs, *params[kind], xi=0.01, mask_d=mask_d)]
+    for kind in ("cb", "ei", "poi"):
+        for masked in (False, True):
+            name = "acquire_exact %s%s" % (kind, ", mask" if masked else "")
+            yield name, lambda kind=kind, masked=masked: exact(kind, masked)
+            yield name + ", slab path", lambda kind=kind, masked=masked: with_env(
+                "GPIMHIP_NO_FUSED_PREDICT", "1", lambda: exact(kind, masked))
+
+    def sweep(kind):
+        mean, sd = rec.predict(verbose=0)
+        md, sdd = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).ravel()).to(H.device) for a in (mean, sd))
+        p0, p1 = (0.3, 1.5) if kind == "cb" else (float(np.nanmax(mean)) - 0.1, 0.01)
+        return (acqfunc._sweep(H, kind, md, sdd, p0, p1, mean.shape)[0],)
+    for kind in ("cb", "ei", "poi"):
+        yield "gpimhip_acq %s" % kind, lambda kind=kind: sweep(kind)
+
+    def batch(out):
+        points, values, maps = out
+        return [np.array(points), values] + [maps[k] for k in sorted(maps)]
+    # (Xf again: the expected-improvement case above has left the rows of Xs, NaN included, as the stored test grid)
+    yield "rec.ivr()", lambda: rec.ivr(Xf)
+    yield "rec.ivr_batch(4)", lambda: batch(rec.ivr_batch(4, Xf))
+    for kind in ("cb", "ei", "poi"):
+        yield "rec.acq_batch(4, %s)" % kind, lambda kind=kind: batch(rec.acq_batch(4, kind, Xf, alpha=0.3, beta=1.5, mask=mask))
+
+    def campaign(af, **kw):
+        import tempfile
+        full = image(R.shape)[1]
+        np.random.seed(0)                           # (update_points pads a thinned batch from np.random)
+        bo = gpim_amd.boptimizer(Xs, R.copy(), Xf, lambda idx: full[tuple(idx)], acquisition_function=af, exploration_steps=3,
+                                 batch_size=50, batch_update=True, kernel="Matern52", lengthscale=LS2, gp_iterations=10,
+                                 batch_out_max=4, verbose=0, filename=os.path.join(tempfile.mkdtemp(), "bo"), **kw)
+        bo.run()
+        return np.array(bo.indices_all), np.array(bo.vals_all)
+    yield "boptimizer ei, 3 steps, thinned batch", lambda: campaign("ei")
+    yield "boptimizer ivr, 3 steps, ivr_batch=greedy", lambda: campaign("ivr", ivr_batch="greedy")
+    yield "boptimizer ei, 3 steps, acq_batch=believer", lambda: campaign("ei", acq_batch="believer")
+
+    def rank():
+        x = np.random.default_rng(12).standard_normal(5000)
+        x[::97] = np.nan
+        xd = torch.from_numpy(x).to(H.device)
+        vals = torch.empty(10, dtype=torch.float64, device=H.device)
+        idx = torch.empty(10, dtype=torch.int64, device=H.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=H.device)
+        best = torch.empty(1, dtype=torch.float64, device=H.device)
+        _lib.check(H.lib.gpimhip_topk(H.h, _lib.ptr(xd), 5000, 10, 0, _lib.ptr(vals), _lib.ptr(idx), _lib.ptr(cnt)))
+        _lib.check(H.lib.gpimhip_nanmax(H.h, _lib.ptr(xd), 5000, _lib.ptr(best)))
+        return [t.cpu().numpy() for t in (vals, idx, cnt, best)]
+    yield "topk M=5000 k=10 (radix), nanmax n=5000 (two-stage)", rank
 
 
 def batch_fit():
