@@ -212,6 +212,12 @@ _PROTOS = {
     "gpimhip_ivr_greedy": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64, c_dp,
                                           c_dp, ctypes.c_int64, c_dp, c_dp, ctypes.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp,
                                           c_dp]),
+    # the same two in bands of block columns: `band` (int32) behind M
+    "gpimhip_ivr_exact_banded": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
+                                                c_dp, c_dp, ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "gpimhip_ivr_greedy_banded": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
+                                                 c_dp, c_dp, ctypes.c_int64, ctypes.c_int32, c_dp, c_dp, ctypes.c_int32, c_dp,
+                                                 c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     # the believer batch of CB / EI / POI: gpimhip_acquire_exact's head through mask, then (q, mean_out, sd_out, maps_out,
     # sd_after_out, idx_out, val_out, count_out)
     "gpimhip_acquire_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,

@@ -184,13 +184,17 @@ class Dense:
 
     no_ivr = None                                       # why a path has no integrated variance reduction
 
-    def ivr(self, o, Xs, weights, mask, mean, sd, acq):
+    def ivr(self, o, Xs, weights, mask, mean, sd, acq, band=None):
         """Integrated variance reduction at the rows Xs: acq[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter) with C the
         latent posterior covariance of the rows, and their posterior (mean, sd) (csrc/ivr.hip).
-        weights, mask: device tensors of Xs.shape[0] doubles or None.  Dense double-precision models only."""
+        weights, mask: device tensors of Xs.shape[0] doubles or None.  band: None (C is stored) or the block columns of C
+        held at a time (gpimhip_ivr_exact_banded; section 30).  Dense double-precision models only."""
         self._ivr_supported(o)
-        return o._handle.lib.gpimhip_ivr_exact(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
-                                               Xs.shape[0], ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
+        head = (*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs), Xs.shape[0])
+        tail = (ptr(weights), ptr(mask), ptr(mean), ptr(sd), ptr(acq))
+        if band is None:
+            return o._handle.lib.gpimhip_ivr_exact(*head, *tail)
+        return o._handle.lib.gpimhip_ivr_exact_banded(*head, int(band), *tail)
 
     def _needs_w(self, o, who, what, cancels):
         """Refuses what is built on W = L^-1 K(X, grid) (integrated variance reduction, believer batches) where the path has
@@ -204,14 +208,17 @@ class Dense:
     def _ivr_supported(self, o):
         self._needs_w(o, "ivr()", "integrated variance reduction", "C = K** - W^T W cancels")
 
-    def ivr_greedy(self, o, Xs, weights, mask, q, mean, sd, maps, sd_after, idx, gain, count):
+    def ivr_greedy(self, o, Xs, weights, mask, q, mean, sd, maps, sd_after, idx, gain, count, band=None):
         """A greedy batch of q picks by integrated variance reduction at the rows Xs: pick r maximises the map of the
         covariance conditioned on picks 0 .. r - 1 (csrc/ivr.hip: gpimhip_ivr_greedy).  maps (q, M),
-        sd_after (M), idx, gain (q), count (1): device tensors; the rest as ``ivr``.  Dense double-precision models only."""
+        sd_after (M), idx, gain (q), count (1): device tensors; the rest as ``ivr`` (band: gpimhip_ivr_greedy_banded, where a
+        further pick costs a whole M^2 N product).  Dense double-precision models only."""
         self._ivr_supported(o)
-        return o._handle.lib.gpimhip_ivr_greedy(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs),
-                                                Xs.shape[0], ptr(weights), ptr(mask), int(q), ptr(mean), ptr(sd), ptr(maps),
-                                                ptr(sd_after), ptr(idx), ptr(gain), ptr(count))
+        head = (*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), ptr(Xs), Xs.shape[0])
+        tail = (ptr(weights), ptr(mask), int(q), ptr(mean), ptr(sd), ptr(maps), ptr(sd_after), ptr(idx), ptr(gain), ptr(count))
+        if band is None:
+            return o._handle.lib.gpimhip_ivr_greedy(*head, *tail)
+        return o._handle.lib.gpimhip_ivr_greedy_banded(*head, int(band), *tail)
 
     def believer(self, o, kind, Xs, Xobs, p0, p1, mask, q, mean, sd, maps, sd_after, idx, val, count):
         """A believer batch of q picks for the acquisition function kind ('cb' / 'ei' / 'poi') at the rows Xs: pick r

@@ -188,18 +188,37 @@ def thompson_sampling(gpmodel, X_full, **kwargs):
     return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))
 
 
-def ivr_on_device(gpmodel, Xf_d, weights_d=None, mask_d=None):
+def _ivr_band(band, M):
+    """``band`` of the ivr entries as what the solver hooks take: None (the M x M covariance is stored) or the number of
+    128-column block columns of it held at a time.  None and an int >= 1 pass through.  'auto': None
+    up to pad(M, 128) = 16384 -- the largest grid measured with the covariance stored -- and beyond it the widest band whose
+    buffer stays within 2 GiB, ``max(1, 2**28 // (128 * pad(M, 128)))``: 32 at M = 65536, 8 at M = 262144.  ValueError for
+    anything else.  A pure host function."""
+    if band is None:
+        return None
+    if isinstance(band, str) and band == "auto":
+        mp = -(-int(M) // 128) * 128
+        return None if mp <= 16384 else max(1, 2 ** 28 // (128 * mp))
+    if isinstance(band, (int, np.integer)) and not isinstance(band, bool) and band >= 1:
+        return int(band)
+    raise ValueError("ivr: band must be None, 'auto' or an int >= 1 (block columns of 128 held at a time); got %r" % (band,))
+
+
+def ivr_on_device(gpmodel, Xf_d, weights_d=None, mask_d=None, band=None):
     """Integrated variance reduction (ALC) over the device rows ``Xf_d``: device tensors (acq, mean, sd) with
     ``acq[j] = sum_m w_m C_mj^2 / (max(C_jj, 0) + noise + jitter)``, C the latent posterior covariance of the rows -- how
     much the (weighted) total posterior variance of the rows drops when row j is measured -- and (mean, sd) the posterior of
     ``predict``.  ``weights_d``: (M,) device weights >= 0 of the integral (None: all 1); ``mask_d``: (M,) device mask of
     1 / NaN multiplied into ``acq`` (it excludes candidates, it does not change the integral).  One library call
-    (gpimhip_ivr_exact).  Dense double-precision models only; the rows must be finite."""
+    (gpimhip_ivr_exact).  ``band``: None, 'auto' or an int >= 1 (``_ivr_band``) -- the covariance in
+    bands of that many block columns instead of M^2 doubles of device memory, the same map (gpimhip_ivr_exact_banded;
+    section 30).  Dense double-precision models only; the rows must be finite."""
     M = _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d)
+    band = _ivr_band(band, M)
     mean_d = torch.empty((M,), dtype=_F64, device=Xf_d.device)
     sd_d = torch.empty_like(mean_d)
     acq_d = torch.empty_like(mean_d)
-    _lib.check(gpmodel._solver.ivr(gpmodel, Xf_d, weights_d, mask_d, mean_d, sd_d, acq_d))
+    _lib.check(gpmodel._solver.ivr(gpmodel, Xf_d, weights_d, mask_d, mean_d, sd_d, acq_d, band=band))
     return acq_d, mean_d, sd_d
 
 
@@ -215,7 +234,7 @@ def _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d):
     return M
 
 
-def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None):
+def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None, band=None):
     """A greedy batch of ``q`` picks by integrated variance reduction over the device rows ``Xf_d``: device tensors
     ``(idx, gain, count, maps, mean, sd, sd_after)``.  A GP's variance does not depend on the measured values, so pick r
     is the maximiser of the map of the covariance conditioned on picks 0 .. r - 1 (C <- C - c c^T / (C_pp + noise + jitter),
@@ -224,12 +243,15 @@ def ivr_greedy_on_device(gpmodel, Xf_d, q, weights_d=None, mask_d=None):
     unmasked candidates run out; then idx = -1 and gain = NaN behind them), ``maps`` (q, M) the map each pick was taken from
     (NaN at masked candidates and earlier picks; row 0 is ``ivr_on_device``'s map, bit for bit), ``mean``, ``sd`` the posterior
     before the batch, ``sd_after`` the sd once the batch is measured.  Arguments as ``ivr_on_device``; 1 <= q <= M.  One
-    library call (gpimhip_ivr_greedy).  Dense double-precision models only."""
+    library call (gpimhip_ivr_greedy).  ``band`` as in ``ivr_on_device`` (gpimhip_ivr_greedy_banded):
+    without the stored covariance a further pick costs a whole M^2 N product instead of one M^2 pass -- the price of the
+    memory.  Dense double-precision models only."""
     M = _ivr_check_args(gpmodel, Xf_d, weights_d, mask_d)
+    band = _ivr_band(band, M)
     q, out = _batch_outputs("ivr", q, M, Xf_d.device)
     idx_d, gain_d, count_d, maps_d, mean_d, sd_d, sd_after_d = out
     _lib.check(gpmodel._solver.ivr_greedy(gpmodel, Xf_d, weights_d, mask_d, q, mean_d, sd_d, maps_d, sd_after_d, idx_d,
-                                          gain_d, count_d))
+                                          gain_d, count_d, band=band))
     return out
 
 
@@ -300,14 +322,16 @@ def _ivr_weights(weights, shape, dev):
 
 def integrated_variance_reduction(gpmodel, X_full, X_sparse=None, **kwargs):
     """Integrated variance reduction (ALC): for every grid point, how much the total posterior variance of the whole grid
-    drops when that point is measured.  kwargs: ``weights`` (array of the grid's shape, >= 0: the integral's weights).
+    drops when that point is measured.  kwargs: ``weights`` (array of the grid's shape, >= 0: the integral's weights),
+    ``band`` (None, 'auto' or an int >= 1: the covariance in bands of block columns, as ``reconstructor.ivr``).
     ``X_sparse`` is not used (the signature of the other acquisition functions, so that this one also serves as a custom
     callable of ``boptimizer``).  ``gpmodel`` is a dense double-precision ``gpim_amd.reconstructor``."""
     if not hasattr(gpmodel, "_solver") or not hasattr(gpmodel._solver, "ivr"):
         raise NotImplementedError("integrated_variance_reduction needs a gpim_amd.reconstructor")
     shape = tuple(np.shape(X_full)[1:])
     Xf = gpmodel._to_device(_rows(X_full, gpmodel.precision))
-    acq_d, mean_d, sd_d = ivr_on_device(gpmodel, Xf, _ivr_weights(kwargs.get("weights"), shape, gpmodel._dev))
+    acq_d, mean_d, sd_d = ivr_on_device(gpmodel, Xf, _ivr_weights(kwargs.get("weights"), shape, gpmodel._dev),
+                                        band=kwargs.get("band"))
     gpmodel._last_acq = acq_d
     host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(gpmodel._np_out, copy=False)
     return host[0].reshape(shape), (host[1].reshape(shape), host[2].reshape(shape))

@@ -84,7 +84,9 @@ class boptimizer:
     every pick maximises the map conditioned on the picks before it and the returned values are the drops each pick adds
     to the batch's (no thinning by distance, no random padding; fewer points only when the unmasked candidates run out);
     the default ``ivr_batch='thin'`` ranks one map and thins it through ``update_points`` like the other acquisition
-    functions.  For 'cb', 'ei' and 'poi' with ``batch_update=True``, ``acq_batch='believer'`` makes the batch the
+    functions.  ``ivr_band`` (None, 'auto' or an int >= 1; read for 'ivr' only, in both batch modes) keeps the covariance in
+    bands of that many block columns instead of M^2 doubles of device memory (reconstructor.ivr); a greedy pick then costs
+    a whole M^2 N product.  For 'cb', 'ei' and 'poi' with ``batch_update=True``, ``acq_batch='believer'`` makes the batch the
     ``batch_out_max`` picks of reconstructor.acq_batch (kriging believer; GP-BUCB for 'cb'): after every pick the variance
     is conditioned on it as if it had been measured at its posterior mean, and the next pick maximises the acquisition
     function of that model; the returned values are the picks' map values (no thinning by distance, no random padding;
@@ -155,8 +157,9 @@ class boptimizer:
             self._ts_generator = torch.Generator(self.surrogate_model._dev).manual_seed(seed)
         self._ivr_weights_d = None
         self.ivr_batch = kwargs.get("ivr_batch", "thin")
+        self.ivr_band = kwargs.get("ivr_band")
         if acquisition_function == 'ivr':
-            # (ivr_batch belongs to 'ivr' with batch_update=True alone)
+            # (ivr_batch belongs to 'ivr' with batch_update=True alone, ivr_band to 'ivr')
             if self.ivr_batch not in ("thin", "greedy"):
                 raise ValueError("ivr_batch must be 'thin' or 'greedy'; got %r" % (self.ivr_batch,))
             if self.shard_candidates:
@@ -166,6 +169,7 @@ class boptimizer:
             if sm._solver.no_ivr or sm.precision == "single":
                 sm._solver.ivr(sm, None, None, None, None, None, None)        # raises NotImplementedError with the reason
             self._ivr_weights_d = acqfunc._ivr_weights(kwargs.get("ivr_weights"), tuple(np.shape(X_full)[1:]), sm._dev)
+            acqfunc._ivr_band(self.ivr_band, int(np.prod(np.shape(X_full)[1:])))      # (ValueError for a bad one)
         self.acq_batch = kwargs.get("acq_batch", "thin")
         if acquisition_function in ('cb', 'ei', 'poi'):
             # (acq_batch belongs to 'cb' / 'ei' / 'poi' with batch_update=True alone)
@@ -363,9 +367,9 @@ class boptimizer:
             grid_shape = tuple(np.shape(self.X_full)[1:])
             if self.batch_update and self.ivr_batch == 'greedy':
                 return self._next_batch_on_device(grid_shape, lambda sm, Xf_d, q, mask_d: acqfunc.ivr_greedy_on_device(
-                    sm, Xf_d, q, weights_d=self._ivr_weights_d, mask_d=mask_d))
+                    sm, Xf_d, q, weights_d=self._ivr_weights_d, mask_d=mask_d, band=self.ivr_band))
             acq_d, mean_d, sd_d = acqfunc.ivr_on_device(sm, self._Xfull_d, weights_d=self._ivr_weights_d,
-                                                        mask_d=self._device_mask(self._Xfull_d.shape[0]))
+                                                        mask_d=self._device_mask(self._Xfull_d.shape[0]), band=self.ivr_band)
             mean_d, sd_d = self._retain_maps(mean_d, sd_d)
             self.gp_predictions.append(_LazyMaps._Pending(mean_d, sd_d, grid_shape, sm._np_out))
             vals_list, indices_list = self._rank_device(acq_d, grid_shape, masked=True)

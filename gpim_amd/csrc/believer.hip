@@ -125,6 +125,15 @@ __global__ __launch_bounds__(256) void believer_col_kernel(const double* __restr
     bel_pass<false>(W, ldm, np, mp, rc, p, part, colp, red);
 }
 
+// (ivr.hpp: the same pass for the banded greedy IVR, over W and the g rows behind it)
+int launch_believer_col(gpimhip_ctx* h, const double* W, int64_t ldm, int64_t rows, int64_t M, int64_t mp, const int64_t* pick,
+                        double* part) {
+    const dim3 pass((unsigned)(mp / BEL_STRIP), (unsigned)gemv_tri_chunks(rows));
+    hipLaunchKernelGGL(believer_col_kernel, pass, dim3(256), 0, h->stream, W, ldm, rows, M, mp, gemv_tri_rc(rows), pick, part);
+    HIP_TRY(hipGetLastError());
+    return GPIMHIP_OK;
+}
+
 // Round 0: v_j = s2 - sum of the chunks' squared column sums in increasing chunk order (predict_var_kernel's prior variance
 // and order of operations), sd = sqrt(max(v, 0) + noise), map_0 = live * acq.  inc: slot 0 of the incumbents (EI / POI).
 __global__ __launch_bounds__(256) void believer_init_kernel(const double* __restrict__ part, int nR, int64_t mp, int64_t M,
@@ -157,16 +166,6 @@ struct BelFinish {
     double* map_next;                                   // row r + 1 of the maps, or null after the last pick
     double* sd_after;                                   // M, or null: the sd after this (the last) pick
 };
-
-// the candidate's coordinates over the lengthscales and their squared norm (tile_stage's arithmetic, the norm in the
-// order of the dot product below: a point against itself gives r2 = 0 exactly)
-__device__ __forceinline__ void bel_point(const double* __restrict__ Xs, int64_t j, int d, const ThetaDev& t, double* a, double& n2) {
-#pragma unroll
-    for (int k = 0; k < GPIMHIP_MAX_DIM; ++k) a[k] = k < d ? Xs[j * d + k] / t.ls[k] : 0.0;
-    n2 = a[0] * a[0];
-#pragma unroll
-    for (int k = 1; k < GPIMHIP_MAX_DIM; ++k) n2 = fma(a[k], a[k], n2);
-}
 
 // After pick r = p: the conditioned column c_j = k(g_j, g_p) - sum of the chunks (increasing) - sum_{s < r} g^(s)_j g^(s)_p
 // (increasing s), g^(r)_j = c_j / sqrt(max(c_p, 0) + noise + jitter), v_j -= g_j^2, the incumbent with the believed value

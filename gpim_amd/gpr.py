@@ -351,7 +351,7 @@ class reconstructor(_solvers.HostDriver):
             out.append(flat)
         return out[0], out[1], {"elpd": elpd, "rmse": float(np.sqrt(sse / N)), "n": N}
 
-    def ivr(self, Xtest=None, weights=None):
+    def ivr(self, Xtest=None, weights=None, band=None):
         """Integrated variance reduction (ALC, the active-learning criterion of Cohn) on the test grid, at the current
         hyper-parameters: ``(ivr, mean, sd)``, numpy arrays of the grid's shape.  ``ivr[j] = sum_m w_m C_mj^2 / (C_jj +
         noise + jitter)`` with C the latent posterior covariance of the grid: the drop of the (weighted) total posterior
@@ -359,18 +359,22 @@ class reconstructor(_solvers.HostDriver):
         fewest measurements (the largest sd sits at the edges, where a measurement tells about the fewest other pixels).
         ``mean``, ``sd``: as ``predict``.  ``Xtest`` as in ``predict`` (finite); ``weights``: None or an array of the
         grid's shape, finite and >= 0 (ValueError otherwise).  Costs one product of M^2 N flop and M^2 doubles of device
-        memory for M grid points.  Dense double-precision models only: sparse, structured and
+        memory for M grid points.  ``band``: None keeps the covariance on the device; an int >= 1
+        holds only that many of its 128-column block columns at a time -- M x (128 band + 16) doubles in place of M^2, the
+        same product, the same map (section 30) -- and 'auto' chooses: None up to M = 16384, beyond it the widest band
+        within 2 GiB (ValueError for anything else).  Dense double-precision models only: sparse, structured and
         single-precision models raise NotImplementedError with the reason."""
         from . import acqfunc
         _finite_test_grid(Xtest, "ivr")
         self._resolve_test_grid(Xtest)
         shape = tuple(self.fulldims)
-        acq_d, mean_d, sd_d = acqfunc.ivr_on_device(self, self._Xtest_d, acqfunc._ivr_weights(weights, shape, self._dev))
+        acq_d, mean_d, sd_d = acqfunc.ivr_on_device(self, self._Xtest_d, acqfunc._ivr_weights(weights, shape, self._dev),
+                                                    band=band)
         self._last_pred = (mean_d, sd_d)
         host = torch.stack([acq_d, mean_d, sd_d]).cpu().numpy().astype(self._np_out, copy=False)
         return host[0].reshape(shape), host[1].reshape(shape), host[2].reshape(shape)
 
-    def ivr_batch(self, n_points, Xtest=None, weights=None, mask=None):
+    def ivr_batch(self, n_points, Xtest=None, weights=None, mask=None, band=None):
         """A batch of ``n_points`` measurements chosen greedily by integrated variance reduction (``ivr``), at the current
         hyper-parameters: ``(points, gains, maps)``.  A GP's variance does not depend on the measured values, so the grid's
         covariance after measuring a point is known before the measurement; every pick is the maximiser of the ``ivr`` map
@@ -382,7 +386,9 @@ class reconstructor(_solvers.HostDriver):
         map), ``'mean'``, ``'sd'``: as ``predict``, and ``'sd_after'``: the sd once the batch is measured.  ``Xtest``, ``weights`` as in ``ivr``; ``mask``: None or an array of the grid's shape
         holding 1 (a candidate) / NaN (excluded); it does not change the integral.  ValueError for n_points < 1, a grid that
         is not finite, bad weights or a bad mask.  One ``ivr`` plus one pass over the stored half of the covariance per
-        further pick.  Dense double-precision models only, as ``ivr``."""
+        further pick.  ``band`` as in ``ivr``: without the stored covariance every further pick
+        costs a whole M^2 N product instead of one M^2 pass -- the price of the memory (section 30).  Dense
+        double-precision models only, as ``ivr``."""
         from . import acqfunc
         if int(n_points) < 1:
             raise ValueError("ivr_batch: n_points must be >= 1; got %r" % (n_points,))
@@ -391,7 +397,8 @@ class reconstructor(_solvers.HostDriver):
         shape = tuple(self.fulldims)
         q = min(int(n_points), int(self._Xtest_d.shape[0]))
         return self._batch_result("ivr", q, shape, *acqfunc.ivr_greedy_on_device(
-            self, self._Xtest_d, q, acqfunc._ivr_weights(weights, shape, self._dev), acqfunc._ivr_mask(mask, shape, self._dev)))
+            self, self._Xtest_d, q, acqfunc._ivr_weights(weights, shape, self._dev), acqfunc._ivr_mask(mask, shape, self._dev),
+            band=band))
 
     def _batch_result(self, key, q, shape, idx_d, val_d, count_d, maps_d, mean_d, sd_d, after_d):
         """``(points, values, maps)`` of ``ivr_batch`` (key 'ivr') / ``acq_batch`` (key 'acq') from the device tensors of

@@ -846,6 +846,27 @@ int gpimhip_ivr_greedy(gpimhip_handle h, const gpimhip_model_t* m, const double*
                        double* mean_out, double* sd_out, double* maps_out, double* sd_after_out, int64_t* idx_out,
                        double* gain_out, int64_t* count_out);
 
+/* The same two without the M x M covariance -- DESIGN.md section 30.  C is built, summed and thrown away one band of
+ * `band` block columns (of 128 columns) at a time: a band buffer of M_pad x (128 band + 16) doubles, M_pad = M rounded up
+ * to 128, takes the place of C; W and the partial sums (M_pad^2 / 128 doubles) stay.  The launches are those of the
+ * stored entries over the band's tiles, every partial sum is written by the same tile's walk and added in the same
+ * order: gpimhip_ivr_exact_banded returns the bits of gpimhip_ivr_exact for every band.
+ *   band   block columns per band, >= 1, clipped to M_pad / 128 (one band: the whole lower half at once)
+ * gpimhip_ivr_greedy_banded conditions on pick r by appending g^(r) = c / sqrt(max(c_p, 0) + noise + jitter), c the
+ * conditioned column of the pick, to W as one more row (W holds pad(q, 128) more rows; C^(r+1) = K(Xs, Xs) - W_aug^T W_aug,
+ * every squared sum stays a sum of squares), so round r + 1 is the banded pass again: a further pick costs a whole
+ * M^2 N product where gpimhip_ivr_greedy pays one M^2 pass -- the price of the memory.  Its picks are those of
+ * gpimhip_ivr_greedy up to rounding (other operations, not other mathematics); q = 1 returns gpimhip_ivr_exact_banded's bits.
+ * Every other argument, the buffers' rules and the refusals as in the stored entries (M > 2^20: the partial sums are
+ * M^2 / 128 doubles); band < 1 -> GPIMHIP_E_BADARG with a reason, nothing allocated. */
+int gpimhip_ivr_exact_banded(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                             const double* u, const double* Xs, int64_t M, int32_t band, const double* weights,
+                             const double* mask, double* mean_out, double* sd_out, double* acq_out);
+int gpimhip_ivr_greedy_banded(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                              const double* u, const double* Xs, int64_t M, int32_t band, const double* weights,
+                              const double* mask, int32_t q, double* mean_out, double* sd_out, double* maps_out,
+                              double* sd_after_out, int64_t* idx_out, double* gain_out, int64_t* count_out);
+
 /* Believer batch of q picks for the acquisition functions CB / EI / POI (kriging believer; for CB: GP-BUCB) -- DESIGN.md
  * section 28.  After picking p the model is conditioned on p having been measured at its posterior mean: the mean map does
  * not change, the latent variance v drops as in gpimhip_ivr_greedy,
