@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpimhip.so")
-SOURCES = ["gemm.hip", "gemm32.hip", "cholstep.hip", "cholstep32.hip", "distops.hip", "engine.hip", "grad.hip", "smalln.hip", "vfe.hip", "kron.hip", "pkron.hip", "select.hip", "predict.hip", "vgp.hip", "sm.hip", "border.hip", "sample.hip", "draws.hip", "ivr.hip", "believer.hip", "acquire.hip", "smgp.hip", "vgpgp.hip", "pkrongp.hip", "distgp.hip", "api.hip"]
+SOURCES = ["gemm.hip", "gemm32.hip", "cholstep.hip", "cholstep32.hip", "distops.hip", "engine.hip", "grad.hip", "smalln.hip", "vfe.hip", "kron.hip", "pkron.hip", "select.hip", "predict.hip", "vgp.hip", "sm.hip", "border.hip", "sample.hip", "draws.hip", "ivr.hip", "believer.hip", "loograd.hip", "acquire.hip", "smgp.hip", "vgpgp.hip", "pkrongp.hip", "distgp.hip", "api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 

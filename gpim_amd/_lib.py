@@ -88,6 +88,10 @@ _PROTOS = {
                                         c_dp, c_dp, c_dp]),
     "gpimhip_fit_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
                                          c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
+    "gpimhip_loo_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
+                                        c_dp, c_dp, c_dp]),
+    "gpimhip_fit_exact_loo": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,
+                                             c_dp, ctypes.c_double, ctypes.c_int32, c_dp, c_dp]),
     "gpimhip_predict_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp,
                                              ctypes.c_int64, c_dp, c_dp, ctypes.c_int64, c_dp, c_dp]),
     "gpimhip_sample_exact": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ModelStruct), c_dp, c_dp, ctypes.c_int64,

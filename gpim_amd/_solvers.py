@@ -7,7 +7,7 @@ _solvers.py -- the host layer between the reconstructors and the C ABI (include/
     ``_lib.reflection``.
   * ``Dense`` / ``Sparse`` / ``Kron`` / ``Columns`` / ``Reflection``: the engine paths of ``reconstructor``, one interface --
     fit(o, lr, T, hist, loss), predict(o, Xs, mean, var), predict_grid(o, mean, var), nll_grad(o, out),
-    loo(o, mean, var, score), each returning the library's status (a path without an exact leave-one-out raises
+    loo(o, mean, var, score), loo_fit / loo_grad (fit / nll_grad for ``objective='loo'``), each returning the library's status (a path without an exact leave-one-out raises
     NotImplementedError with its reason).  ``SpectralBlocks``: the reflection / border path of ``smreconstructor`` (one shared parameter vector).
     ``o`` is the owning reconstructor, passed per call: a solver never stores it (no reference cycle
     through the library handle) and reads ``o._Xd`` / ``o._yd`` / ``o._u`` as they are at the time of the call
@@ -40,7 +40,8 @@ class HostDriver:
         pass
 
     def train(self, **kwargs):
-        """Adam on the negative log marginal likelihood; every call starts a fresh optimiser while the hyper-parameters
+        """Adam on the model's objective (the negative log marginal likelihood; ``reconstructor(objective='loo')``: the
+        leave-one-out pseudo-likelihood); every call starts a fresh optimiser while the hyper-parameters
         persist (warm start), like the reference's train()."""
         for k in ("learning_rate", "iterations", "verbose"):
             if kwargs.get(k) is not None:
@@ -131,6 +132,26 @@ class DeviceBlocks:
         self.border = (len(self.S["miss"]), self.q, self.coef)
 
 
+OBJECTIVES = ("nll", "loo")
+
+
+def check_objective(objective):
+    """'nll' (the negative log marginal likelihood) or 'loo' (the leave-one-out pseudo-likelihood); ValueError otherwise."""
+    if objective not in OBJECTIVES:
+        raise ValueError("objective must be 'nll' or 'loo'; got %r" % (objective,))
+    return objective
+
+
+def refuse_loo_objective(who, why=None, precision="double"):
+    """NotImplementedError with the reason where objective='loo' cannot be trained: ``why`` (a model family's), or single
+    precision."""
+    if why is None and precision == "single":
+        why = ("single precision does not resolve d = diag(S^-1) and the loss's log d (float matrices lose eps32 x the "
+               "condition number): build the model with precision='double'")
+    if why:
+        raise NotImplementedError("objective='loo': the %s cannot train on the leave-one-out objective -- %s" % (who, why))
+
+
 def _head(o):
     return o._handle.h, ctypes.byref(o._mstruct)
 
@@ -163,6 +184,24 @@ class Dense:
 
     def nll_grad(self, o, out):
         return o._handle.lib.gpimhip_nll_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), *_loss_grad(out))
+
+    # why a path cannot train on the leave-one-out objective (the paths that inherit Dense's methods below)
+    no_loo_objective = None
+
+    def _loo_objective_supported(self, o):
+        refuse_loo_objective(type(self).__name__ + " solver", self.no_loo_objective, o.precision)
+
+    def loo_fit(self, o, lr, T, hist, loss):
+        """``fit`` on the leave-one-out pseudo-likelihood (csrc/loograd.hip): the dense
+        double-precision model only."""
+        self._loo_objective_supported(o)
+        return o._handle.lib.gpimhip_fit_exact_loo(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), lr, T,
+                                                   ptr(hist), ptr(loss))
+
+    def loo_grad(self, o, out):
+        """``nll_grad`` for the leave-one-out pseudo-likelihood."""
+        self._loo_objective_supported(o)
+        return o._handle.lib.gpimhip_loo_grad(*_head(o), ptr(o._Xd), ptr(o._yd), o._Xd.shape[0], ptr(o._u), *_loss_grad(out))
 
     no_loo = None                                       # why a path has no exact leave-one-out (the paths that inherit Dense's)
 
@@ -293,6 +332,8 @@ class Sparse(Dense):
     no_loo = ("the variational (VFE) posterior conditions on inducing points, not on the observations: dropping one "
               "observation has no closed form in its factors")
     no_ivr = "the posterior conditions on inducing points"
+    no_loo_objective = ("sparse=True: the variational (VFE) bound conditions on inducing points, not on the observations, and "
+                        "has no held-out terms to sum")
 
     def fit(self, o, lr, T, hist, loss):
         hist_xu = torch.empty((max(T, 1), o._n_ind, o._spec.dim), dtype=_F64, device=o._dev)
@@ -314,6 +355,8 @@ class Kron(Dense):
     """Exact GP through the Kronecker structure of the RBF covariance on a complete product grid (csrc/kron.hip)."""
     structured = True
     no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
+    no_loo_objective = ("structured=True (Kronecker): the gradient needs S^-1 diag(omega) S^-1 contracted with dS, which does "
+                        "not factorise over the axes' eigenbases; only the score rec.loo() does")
 
     def __init__(self, axes, axes_n):
         self.axes, self.axes_n = axes, axes_n
@@ -372,6 +415,8 @@ class Columns(Dense):
     structured = True
     _NO_DRAWS = "solver='columns' draws with method='columns' only"
     no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
+    no_loo_objective = ("solver='columns': diag(S^-1) of the dense-by-Kronecker blocks mixes every block's diagonal through "
+                        "the complete axes' eigenvectors, which is not built")
     no_loo = ("solver='columns': diag(S^-1) of the dense-by-Kronecker blocks mixes every block's diagonal through the "
               "complete axes' eigenvectors, which is not built")
 
@@ -520,6 +565,8 @@ class Reflection(Dense):
     completed grid plus a border for its missing points (gprutils.border_blocks; csrc/border.hip)."""
     symm = True
     no_ivr = "the cross-covariance of arbitrary grid points is not block-structured"
+    no_loo_objective = ("structured=True (reflection blocks): a held-out term mixes the diagonals of all blocks that hold its "
+                        "point, so the objective is no sum over the blocks and the lock-step batch has no gradient for it")
 
     def __init__(self, S, border=False):
         self.S, self.border, self.blocks, self.perm_d = S, border, None, None

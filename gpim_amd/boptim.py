@@ -66,7 +66,8 @@ class boptimizer:
     acquisition_function='cb', exploration_steps=10, batch_size=100, batch_update=False,
     kernel='RBF', lengthscale=None, sparse=False, indpoints=None, gp_iterations=1000, seed=0,
     **kwargs)`` with kwargs verbose, use_gpu (ignored), learning_rate, jitter (default 1e-6),
-    isotropic, precision, alpha, beta, xi, dscale, batch_dscale, batch_out_max, gamma, memory,
+    isotropic, precision, objective (gpim_amd extension: 'nll' or 'loo', what the surrogate is retrained on at every step --
+    ``reconstructor(objective=...)``), alpha, beta, xi, dscale, batch_dscale, batch_out_max, gamma, memory,
     exit_strategy, mask, extent, simulate_measurement, y_true, save_checkpoints, filename.
 
     gpim_amd extension: ``acquisition_function='ts'`` is Thompson sampling -- one noiseless joint draw of the
@@ -112,7 +113,7 @@ class boptimizer:
         self.surrogate_model = reconstructor(
             X_seed, y_seed, X_full, kernel, lengthscale, sparse, indpoints,
             learning_rate, gp_iterations, self.use_gpu, self.verbose, seed,
-            isotropic=isotropic, precision=self.precision, jitter=jitter)
+            isotropic=isotropic, precision=self.precision, jitter=jitter, objective=kwargs.get("objective", "nll"))
         self.X_sparse = X_seed.copy()
         self.surrogate_model._trained_on = self.X_sparse        # same content as X_seed (see _observed_rows_d)
         self.y_sparse = y_seed.copy()

@@ -2,7 +2,8 @@
 // extern "C" entry points declared in include/gpimhip.h.  The posterior draws (gpimhip_sample_*) have their drivers and entries
 // in draws.hip, the spectral-mixture GP (gpimhip_*_sm*) in smgp.hip, the multi-output GP (gpimhip_*_vgp*) in vgpgp.hip, the
 // Kronecker model (gpimhip_*_kron) in kron.hip, the dense-by-Kronecker blocks (gpimhip_*_pkron) in pkrongp.hip and the
-// multi-GPU panel drivers (gpimhip_dist_*, gpimhip_matvec_t) in distgp.hip.
+// multi-GPU panel drivers (gpimhip_dist_*, gpimhip_matvec_t) in distgp.hip; the iteration of the leave-one-out objective
+// (loo_grad_at_u, behind loss_grad_at_u) is in loograd.hip.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -38,7 +39,7 @@ static inline int64_t mat_doubles(const gpimhip_ctx* h, int64_t elements) { retu
 
 static void ws_release_matrix(gpimhip_ctx* h) {
     dev_release(h, h->A, h->B, h->Tm, h->dinv, h->dinvB, h->pcopy, h->ypad, h->z, h->alpha, h->logdet_part, h->grad_part,
-                h->gemv_part, h->fin_counter, h->theta, h->adam_m, h->adam_v, h->iter);
+                h->gemv_part, h->fin_counter, h->theta, h->adam_m, h->adam_v, h->iter, h->loo_vec);
     h->np = 0;
     h->ws_batch = 0;
 }
@@ -165,7 +166,7 @@ int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc) {
 // ------------------------------------------------------------------------------------------
 // launch plans (tile lists) for a matrix of nb x nb blocks
 // ------------------------------------------------------------------------------------------
-static void lower_patch_order(std::vector<TileDesc>& out, int lo, int hi, int kb0, int kb1) {
+void lower_patch_order(std::vector<TileDesc>& out, int lo, int hi, int kb0, int kb1) {
     // lower-triangular tile set {(i,j): lo <= j <= i < hi} in 8x8 patches (operand-panel reuse in L2)
     for (int ig = lo / 8; ig <= (hi - 1) / 8; ++ig)
         for (int jg = lo / 8; jg <= ig; ++jg)
@@ -557,11 +558,17 @@ int factor_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64
 // theta_carried: the training loop launched theta(u) once before its first iteration; every finalize step then leaves the
 // theta of the stepped parameters in h->theta (no theta launch inside the loop)
 struct IterTable : FinalizeIter { bool theta_carried; };
+// what a training iteration minimises: the negative log marginal likelihood, or the leave-one-out pseudo-likelihood
+// (loograd.hip; one double-precision problem of the dense engine: loo_objective_refused)
+enum Objective { OBJ_NLL = 0, OBJ_LOO = 1 };
 
 static int loss_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, int64_t N,
                           double* u, int do_adam, AdamStep st, double* loss_out, double* grad_out,
-                          double* hist_row, const IterTable* tab = nullptr) {
+                          double* hist_row, const IterTable* tab = nullptr, Objective obj = OBJ_NLL) {
     const int64_t np = h->np;
+    if (obj == OBJ_LOO)     // (its finalize step is always a launch of its own; theta is carried as for the other objective)
+        return loo_grad_at_u(h, m, X, N, u, do_adam, st, tab ? FinalizeOut(*tab) : FinalizeOut(loss_out, grad_out, hist_row),
+                             !h->no_fused_finalize && tab && tab->theta_carried);
     // One launch for the gradient contraction and the finalize step (unless the knob asks for the two launches: see
     // read_finalize_knob)
     // ... up to np = 8192; beyond, the finalize step is a launch of its own again (the tail's device-scope loads of 8256 tiles'
@@ -774,7 +781,7 @@ int gpimhip_destroy(gpimhip_handle h) {
     ivr_release(h);
     ws_release_matrix(h);
     ws_release_predict(h);
-    dev_release(h, h->keys, h->sel_scratch, h->acq_tmp, h->refine, h->bc, h->theta1, h->info);
+    dev_release(h, h->keys, h->sel_scratch, h->acq_tmp, h->refine, h->bc, h->theta1, h->info, h->loo_tiles);
     if (h->plan.d_tiles) (void)hipFree(h->plan.d_tiles);
     step_plan_release(h);
     dist_plan_release(h);
@@ -861,7 +868,8 @@ int gpimhip_potrf(gpimhip_handle h, double* A, int64_t n, int64_t ld, int32_t* i
 }
 
 static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y,
-                    int64_t N, int B, double* u, double lr, int32_t T, double* hist_out, double* loss_out) {
+                    int64_t N, int B, double* u, double lr, int32_t T, double* hist_out, double* loss_out,
+                    Objective obj = OBJ_NLL) {
     read_finalize_knob(h);
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = B;
@@ -870,12 +878,13 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
     h->fit_completed = T;
     if (T == 0) return GPIMHIP_OK;
     GP_TRY(upload_bc_table(h, lr, T));
-    if (use_small_path(N) && !h->refl.mask) {
-        // fused single-launch trainer, one workgroup per problem
+    if (use_small_path(N) && !h->refl.mask && obj == OBJ_NLL) {
+        // fused single-launch trainer, one workgroup per problem (it knows the marginal likelihood only)
         GP_TRY(launch_fit_small(h, m, X, x_bs, y, (int)N, u, h->bc, h->bc + T, T, hist_out, loss_out, nullptr));
         return finish_and_check(h);
     }
     GP_TRY(ws_ensure_padded(h, N));
+    if (obj == OBJ_LOO) GP_TRY(loo_obj_ensure(h));
     if (border_on(h)) GP_TRY(border_ensure(h));
     HIP_TRY(hipMemsetAsync(h->adam_m, 0, (size_t)B * MAXP * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->adam_v, 0, (size_t)B * MAXP * sizeof(double), h->stream));
@@ -889,7 +898,7 @@ static int fit_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, i
     const IterTable tab{{h->iter, h->bc, T, hist_out, loss_out}, carry};
     const AdamStep st = adam_step_init();
     return run_fit_iterations(h, T, FIT_LOOP_DENSE,
-                              [&] { return loss_grad_at_u(h, m, X, x_bs, N, u, 1, st, nullptr, nullptr, nullptr, &tab); });
+                              [&] { return loss_grad_at_u(h, m, X, x_bs, N, u, 1, st, nullptr, nullptr, nullptr, &tab, obj); });
 }
 
 
@@ -1018,25 +1027,61 @@ static int predict_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* 
     return finish_and_check(h);
 }
 
-int gpimhip_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
-                     const double* u, double* loss_out, double* grad_out) {
-    if (!h || !X || !y || !u || N < 1) return GPIMHIP_E_BADARG;
-    GP_TRY(check_model(m));
+// one evaluation of the objective and its gradient at u (one problem)
+static int loss_grad_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                          double* loss_out, double* grad_out, Objective obj) {
     read_finalize_knob(h);
     HIP_TRY(hipSetDevice(h->device));
     h->nbatch = 1;
     HIP_TRY(hipMemsetAsync(h->info, 0, sizeof(int32_t), h->stream));
-    if (use_small_path(N)) {
+    if (use_small_path(N) && obj == OBJ_NLL) {
         GP_TRY(launch_fit_small(h, m, X, 0, y, (int)N, const_cast<double*>(u), nullptr, nullptr, 0, nullptr,
                                 loss_out, grad_out));
         return finish_and_check(h);
     }
     GP_TRY(ws_ensure_padded(h, N));
+    if (obj == OBJ_LOO) GP_TRY(loo_obj_ensure(h));
     GP_TRY(launch_pad_copy(h, y, N, h->ypad, h->np));
     AdamStep st;
     memset(&st, 0, sizeof(st));
-    GP_TRY(loss_grad_at_u(h, m, X, 0, N, const_cast<double*>(u), 0, st, loss_out, grad_out, nullptr));
+    GP_TRY(loss_grad_at_u(h, m, X, 0, N, const_cast<double*>(u), 0, st, loss_out, grad_out, nullptr, nullptr, obj));
     return finish_and_check(h);
+}
+
+int gpimhip_nll_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                     const double* u, double* loss_out, double* grad_out) {
+    if (!h || !X || !y || !u || N < 1) return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    return loss_grad_impl(h, m, X, y, N, u, loss_out, grad_out, OBJ_NLL);
+}
+
+// The leave-one-out objective is built for ONE double-precision problem of the dense engine
+static int loo_objective_refused(const gpimhip_ctx* h, const char* who) {
+    const char* why = h->fp32 ? "a single-precision handle (d = diag(S^-1) and the loss's log d cancel in float matrices: gpimhip_set_precision(h, 64))"
+                    : border_on(h) ? "a border (the missing points couple the blocks: diag(S^-1) is no sum of the blocks' diagonals)"
+                    : (h->refl.pb_off != 0 || h->refl.pb_stride != 1 || h->refl.raw || h->refl.nblocks_total) && h->refl.mask
+                        ? "a shard of reflection blocks (the objective is not a sum over the blocks)"
+                    : h->refl.mask ? "reflection mode (a lock-step batch of blocks: the held-out terms mix the blocks' diagonals)"
+                                   : nullptr;
+    if (!why) return GPIMHIP_OK;
+    gpim_set_error(std::string(who) + ": the leave-one-out objective is the dense double-precision model's, one problem per call; refused on " + why);
+    return GPIMHIP_E_BADARG;
+}
+
+int gpimhip_loo_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N, const double* u,
+                     double* loss_out, double* grad_out) {
+    if (!h || !X || !y || !u || N < 1) return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    GP_TRY(loo_objective_refused(h, "gpimhip_loo_grad"));
+    return loss_grad_impl(h, m, X, y, N, u, loss_out, grad_out, OBJ_LOO);
+}
+
+int gpimhip_fit_exact_loo(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                          double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out) {
+    if (!h || !X || !y || !u_inout || N < 1 || T < 0) return GPIMHIP_E_BADARG;
+    GP_TRY(check_model(m));
+    GP_TRY(loo_objective_refused(h, "gpimhip_fit_exact_loo"));
+    return fit_impl(h, m, X, 0, y, N, 1, u_inout, lr, T, hist_out, loss_out, OBJ_LOO);
 }
 
 int gpimhip_fit_exact(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,

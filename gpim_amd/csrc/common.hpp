@@ -252,6 +252,11 @@ struct gpimhip_ctx {
     // column sums, owned by ivr.hip (IvrWs); ivr_release()
     void* ivr = nullptr;
     DevBuf<double> refine;          // residual, correction and partial sums of the refinement (fp32 handles)
+    // leave-one-out objective (loograd.hip: loo_obj_ensure): q, sqrt(omega), r -- 3 x np, released with the matrices -- and the
+    // tile list of C C^T for loo_tiles_nb block rows
+    DevBuf<double> loo_vec;
+    DevBuf<TileDesc> loo_tiles;
+    int loo_tiles_nb = 0;
     int fp32 = 0;                   // 1: the N x N matrices of the exact-GP path are float (gpimhip_set_precision)
     // GPIMHIP_NO_FUSED_FINALIZE as the current public call found it (api.hip: read_finalize_knob, at the top of every entry that
     // reaches loss_grad_at_u): theta carry, fused finalize and deferred alpha all derive from this one read
@@ -353,6 +358,7 @@ int ws_ensure_padded(gpimhip_ctx* h, int64_t N);
 int ws_ensure_predict(gpimhip_ctx* h, int64_t np, int64_t mc);
 int deal_chunk(int ntiles = 1 << 30);
 void tri_tiles(std::vector<TileDesc>& tl, int nbr, int nc, bool lower);     // (with the tile-list builders of api.hip)
+void lower_patch_order(std::vector<TileDesc>& out, int lo, int hi, int kb0, int kb1);
 int model_state_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t x_bs, const double* y, int64_t N,
                      int B, const double* u);
 // z = L^-1 ypad and alpha = L^-T z from L^-1 in h->A; K(u) -> L^-1 in h->A, then the two (api.hip has the details)
@@ -480,6 +486,14 @@ int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const doubl
                            bool alpha_deferred, double* u, int do_adam, AdamStep st, const FinalizeOut& out, int carry_theta);
 int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
                     AdamStep st, const FinalizeOut& out, int carry_theta = 0);
+int launch_finalize_vec(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam, AdamStep st,
+                        const FinalizeOut& out, int carry_theta, const double* z, const double* zb);
+// grad.hip, loograd.hip (the leave-one-out objective: one double-precision problem of the dense engine)
+int launch_grad_reduce_loo(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X, int64_t N,
+                           int nb, const double* alpha, const double* rvec);
+int loo_obj_ensure(gpimhip_ctx* h);
+int loo_grad_at_u(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, int64_t N, double* u, int do_adam, AdamStep st,
+                  const FinalizeOut& out, bool theta_carried);
 // grad.hip (distributed training, reflection blocks)
 int launch_grad_reduce_tiles(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
                              int64_t N, int64_t np, const double* alpha, const TileDesc* tiles, int ntile, double* part);

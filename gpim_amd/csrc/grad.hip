@@ -1,7 +1,8 @@
 // grad.hip -- from K^-1 and alpha to the loss, its gradient and the Adam step: the launches of a training iteration behind
 // the O(N^3) stages.
 //   grad_reduce_kernel       fused  sum_ij (K^-1 - alpha alpha^T)_ij dK_ij/dtheta over the lower tiles   
-//                            -- a full matrix, or the tiles a rank of a distributed job holds (launch_grad_reduce_tiles)
+//                            -- a full matrix, or the tiles a rank of a distributed job holds (launch_grad_reduce_tiles); its LOO
+//                            form contracts G2 - (r alpha^T + alpha r^T) for the leave-one-out objective (loograd.hip)
 //   grad_reduce_refl_kernel  the same for one reflection block K_s
 //   finalize_block           loss, d loss/du, Adam step, history row, next theta (rows a7-a10): finalize_kernel, or the
 //                            last workgroup of grad_reduce_kernel (FinFused)
@@ -153,21 +154,28 @@ struct FinFused {
 // alpha_part != nullptr: alpha is given as the row-chunk partial sums of gemv_t_tri_kernel (nR chunks of rc rows) and
 // every workgroup adds up the 256 entries it needs itself (no sum launch).  fin.enabled: the last workgroup of a problem to
 // finish runs the finalize step (FinFused).
-template <int KIND, typename R>
+// LOO (the leave-one-out objective, loograd.hip): Kinv holds G2 = S^-1 diag(omega) S^-1 and rvec = S^-1 (alpha / d); the entry's
+// weight is G2_ij - (r_i alpha_j + alpha_i r_j) where the marginal likelihood has Kinv_ij - alpha_i alpha_j.  Its finalize
+// step is a launch of its own (fin is ignored).
+template <int KIND, typename R, bool LOO = false>
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ Kinv, int64_t ld,
                                                           const double* __restrict__ X, int64_t N, int d,
                                                           const double* __restrict__ alpha,
                                                           ThetaDev* __restrict__ th,
                                                           double* __restrict__ part, int64_t x_bs, int64_t np,
                                                           const TileDesc* __restrict__ tiles,
-                                                          const double* __restrict__ alpha_part, int nR, int rc, FinFused fin) {
+                                                          const double* __restrict__ alpha_part, int nR, int rc, FinFused fin,
+                                                          const double* __restrict__ rvec) {
     // one buffer, carved: the staging of the tile phase, then (last workgroup only) the reduction scratch of the finalize step
-    __shared__ double sh[2 * 128 * 5 + 2 * 128 + 4 * 8 + 16];
+    // (LOO: the second vector's rows and columns behind it)
+    __shared__ double sh[2 * 128 * 5 + 2 * 128 + 4 * 8 + 16 + (LOO ? 2 * 128 : 0)];
     double (*xa)[5] = reinterpret_cast<double (*)[5]>(sh);
     double (*xz)[5] = reinterpret_cast<double (*)[5]>(sh + 128 * 5);
     double* al_r = sh + 2 * 128 * 5;
     double* al_c = al_r + 128;
     double (*red)[8] = reinterpret_cast<double (*)[8]>(al_c + 128);
+    double* rv_r = sh + 2 * 128 * 5 + 2 * 128 + 4 * 8 + 16;
+    double* rv_c = rv_r + 128;
     const int tid = threadIdx.x;
     double* part_all = part;
     Kinv += blockIdx.y * np * ld;
@@ -192,6 +200,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ 
         double av = 0.0;
         if (s.valid) av = alpha_part ? gemv_tri_alpha(alpha_part, nR, rc, np, s.g) : alpha[s.g];
         tile_put(s, al_r, al_c, av);
+        if (LOO) tile_put(s, rv_r, rv_c, s.valid ? rvec[blockIdx.y * np + s.g] : 0.0);
     }
     __syncthreads();
     double S[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -204,6 +213,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ 
         const int64_t gi = (int64_t)ci * 128 + r;
         const double a0 = xa[r][0], a1 = xa[r][1], a2 = xa[r][2], a3 = xa[r][3], an = xa[r][4];
         const double ali = al_r[r];
+        const double rvi = LOO ? rv_r[r] : 0.0;
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
             const typename Vec2<R>::T kv = *reinterpret_cast<const typename Vec2<R>::T*>(Kinv + gi * ld + ccol + tx * 2 + 32 * cc);
@@ -212,7 +222,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ 
                 const int c = tx * 2 + 32 * cc + e;
                 const int64_t gj = (int64_t)cj * 128 + c;
                 if (!decltype(INTERIOR)::value && (gi >= N || gj > gi)) continue;
-                const double g = (double)kv[e] - ali * al_c[c];
+                const double g = LOO ? (double)kv[e] - fma(rvi, al_c[c], ali * rv_c[c]) : (double)kv[e] - ali * al_c[c];
                 const double w = (!decltype(INTERIOR)::value && gi == gj) ? g : 2.0 * g;
                 double dot = a0 * xz[c][0];
                 dot = fma(a1, xz[c][1], dot);
@@ -235,7 +245,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ 
     };
     if (interior) body(std::true_type{});
     else body(std::false_type{});
-    if (!fin.enabled) {
+    if (LOO || !fin.enabled) {
         tile_sums_store<false>(S, red, part);
         return;
     }
@@ -277,7 +287,8 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const R* __restrict__ 
 // row-chunk partial sums of launch_gemv_t_tri.  fin: nullptr, or the finalize step to run in each problem's last workgroup.
 static int launch_grad_reduce_impl(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X,
                                    int64_t x_bs, int64_t N, int64_t np, const double* alpha, const double* alpha_part,
-                                   const TileDesc* tiles, int ntile, int nbatch, double* part, const FinFused* fin) {
+                                   const TileDesc* tiles, int ntile, int nbatch, double* part, const FinFused* fin,
+                                   const double* rvec = nullptr) {
     const dim3 grid(ntile, nbatch), block(256);
     const FinFused ff = fin ? *fin : FinFused();
     const int nR = alpha_part ? gemv_tri_chunks(np) : 0, rc = alpha_part ? gemv_tri_rc(np) : 0;
@@ -286,9 +297,12 @@ static int launch_grad_reduce_impl(gpimhip_ctx* h, const gpimhip_model_t* m, con
         auto launch = [&](auto* kinv) {
             typedef std::remove_const_t<std::remove_pointer_t<decltype(kinv)>> R;
             hipLaunchKernelGGL((grad_reduce_kernel<KIND, R>), grid, block, 0, h->stream, kinv, ld, X, N, m->dim, alpha, h->theta,
-                               part, x_bs, np, tiles, alpha_part, nR, rc, ff);
+                               part, x_bs, np, tiles, alpha_part, nR, rc, ff, rvec);
         };
-        if (h->fp32) launch(reinterpret_cast<const float*>(Kinv));
+        if (rvec)
+            hipLaunchKernelGGL((grad_reduce_kernel<KIND, double, true>), grid, block, 0, h->stream, Kinv, ld, X, N, m->dim, alpha,
+                               h->theta, part, x_bs, np, tiles, alpha_part, nR, rc, ff, rvec);
+        else if (h->fp32) launch(reinterpret_cast<const float*>(Kinv));
         else launch(Kinv);
         HIP_TRY(hipGetLastError());
         return GPIMHIP_OK;
@@ -298,6 +312,13 @@ int launch_grad_reduce(gpimhip_ctx* h, const gpimhip_model_t* m, const double* K
                        const double* X, int64_t N, int nb, const double* alpha, int64_t x_bs) {
     return launch_grad_reduce_impl(h, m, Kinv, ld, X, x_bs, N, (int64_t)nb * NB, alpha, nullptr, nullptr, nb * (nb + 1) / 2,
                                    h->nbatch, h->grad_part, nullptr);
+}
+// the leave-one-out form (loograd.hip): Kinv holds the lower tiles of G2, rvec = S^-1 (alpha / d); one double-precision problem
+int launch_grad_reduce_loo(gpimhip_ctx* h, const gpimhip_model_t* m, const double* Kinv, int64_t ld, const double* X, int64_t N,
+                           int nb, const double* alpha, const double* rvec) {
+    FP64_ONLY(h);
+    return launch_grad_reduce_impl(h, m, Kinv, ld, X, 0, N, (int64_t)nb * NB, alpha, nullptr, nullptr, nb * (nb + 1) / 2, 1,
+                                   h->grad_part, nullptr, rvec);
 }
 // the tiles of K^-1 a rank of a distributed job holds (distgp.hip: gpimhip_dist_grad_sums).  The distributed layouts are
 // double: a single-precision handle would send the shared launch to the float kernel.
@@ -330,14 +351,19 @@ int launch_grad_reduce_fin(gpimhip_ctx* h, const gpimhip_model_t* m, const doubl
                                    nullptr, nb * (nb + 1) / 2, h->nbatch, h->grad_part, &ff);
 }
 
-int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
-                    AdamStep st, const FinalizeOut& out, int carry_theta) {
+// z, zb: the two vectors whose dot product is the loss's quadratic term
+int launch_finalize_vec(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam, AdamStep st,
+                        const FinalizeOut& out, int carry_theta, const double* z, const double* zb) {
     const int nb = (int)(np / NB);
     hipLaunchKernelGGL(finalize_kernel, dim3(1, h->nbatch), dim3(256), 0, h->stream, *m, N, np, nb, nb * (nb + 1) / 2,
-                       h->grad_part, h->fp32 ? h->ypad : h->z, h->fp32 ? h->alpha : h->z, h->logdet_part, h->theta, u, h->adam_m,
-                       h->adam_v, do_adam, st, out, h->info, carry_theta);
+                       h->grad_part, z, zb, h->logdet_part, h->theta, u, h->adam_m, h->adam_v, do_adam, st, out, h->info,
+                       carry_theta);
     HIP_TRY(hipGetLastError());
     return GPIMHIP_OK;
+}
+int launch_finalize(gpimhip_ctx* h, const gpimhip_model_t* m, int64_t N, int64_t np, double* u, int do_adam,
+                    AdamStep st, const FinalizeOut& out, int carry_theta) {
+    return launch_finalize_vec(h, m, N, np, u, do_adam, st, out, carry_theta, h->fp32 ? h->ypad : h->z, h->fp32 ? h->alpha : h->z);
 }
 
 // ------------------------------------------------------------------------------------------

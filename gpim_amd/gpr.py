@@ -140,6 +140,15 @@ class reconstructor(_solvers.HostDriver):
             batch with shared hyper-parameters (csrc/engine.hip: kmat_refl_kernel) -- 4^-r of the dense model's O(N^3)
             work (1/16 for a 2-D image), the same model and results to rounding; predictions at arbitrary points.  Axes of
             odd length are reflected too (their mirror plane belongs to the fundamental domain, with weights).
+        **objective (str): gpim_amd extension -- what ``train`` / ``run`` minimise and ``loss_and_grad`` evaluates: 'nll'
+            (default), the negative log marginal likelihood, or 'loo', the leave-one-out pseudo-likelihood (Rasmussen &
+            Williams 5.4.2) ``-sum_i log N(y_i | mu_-i, 1 / d_i)`` plus the same prior constant, with
+            ``mu_-i`` the prediction of y_i from the other observations and ``d = diag(S^-1)``, S = K + (noise + jitter) I:
+            the quantity ``loo()["elpd"]`` scores, as a training objective for a kernel that is only approximately right.
+            The held-out variance is ``1 / d_i``, that of the matrix that is trained: ``loo()``'s reported variance plus
+            the jitter wherever ``loo()`` did not clamp.  About twice the cost of an iteration on 'nll' (one more N^3
+            product).  Dense double-precision models only: ``sparse=True``, ``structured=True`` and ``precision='single'``
+            raise NotImplementedError with the reason; any other value raises ValueError.
     """
 
     def __init__(self, X, y, Xtest=None, kernel='RBF', lengthscale=None, sparse=False,
@@ -147,6 +156,14 @@ class reconstructor(_solvers.HostDriver):
                  verbose=1, seed=0, **kwargs):
         self.precision = kwargs.get("precision", "double")
         self._np_out = np.float32 if self.precision == "single" else np.float64
+        self.objective = _solvers.check_objective(kwargs.get("objective", "nll"))
+        if self.objective == "loo":         # (before anything touches the device: the refusals need none)
+            family = _solvers.Sparse if sparse else None
+            if kwargs.get("structured", False):
+                family = _solvers.Kron if kernel == "RBF" and kwargs.get("_border") is None and kwargs.get("_columns") is None \
+                    else _solvers.Columns if kwargs.get("_columns") is not None else _solvers.Reflection
+            _solvers.refuse_loo_objective("%s solver" % family.__name__ if family else "dense model",
+                                          family.no_loo_objective if family else None, self.precision)
         # raises if there is no GPU / no library; single precision applies to the exact dense engine only
         single_engine = self.precision == "single" and not sparse and not kwargs.get("structured", False)
         self._handle = _lib.Handle(precision="single" if single_engine else "double")
@@ -275,7 +292,8 @@ class reconstructor(_solvers.HostDriver):
         return self._spec.n_params
 
     def _fit(self, T, hist, loss):
-        return self._solver.fit(self, float(self.learning_rate), T, hist, loss)
+        fit = self._solver.loo_fit if self.objective == "loo" else self._solver.fit
+        return fit(self, float(self.learning_rate), T, hist, loss)
 
     def _record(self, i, row, loss_i, show):
         n_ls = self._spec.n_ls
@@ -547,9 +565,9 @@ class reconstructor(_solvers.HostDriver):
 
     # ------------------------------------------------------------------ operator-level hooks
     def loss_and_grad(self):
-        """(loss, d loss/du) at the current hyper-parameters; used by the parity tests."""
+        """(loss, d loss/du) of the model's objective at the current hyper-parameters; used by the parity tests."""
         self._check_data()
         out = torch.empty((1 + self._u.numel(),), dtype=_F64, device=self._dev)
-        _lib.check(self._solver.nll_grad(self, out))
+        _lib.check((self._solver.loo_grad if self.objective == "loo" else self._solver.nll_grad)(self, out))
         o = out.cpu()
         return o[0].item(), o[1:].clone()

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import _sampling
+from . import _sampling, _solvers
 from . import gprutils
 from ._solvers import HostDriver, SpectralBlocks
 
@@ -106,6 +106,11 @@ class smreconstructor(HostDriver):
         if self.precision == "single":
             raise NotImplementedError("skreconstructor(kernel='Spectral'): precision='single' is not implemented by the "
                                       "MI355X engine (the spectral-mixture path runs in double precision)")
+        self.objective = _solvers.check_objective(kwargs.get("objective", "nll"))
+        if self.objective == "loo":
+            _solvers.refuse_loo_objective("spectral-mixture GP (kernel='Spectral')",
+                                          "its gradient contraction has a kernel and a constant mean of its own (csrc/sm.hip), "
+                                          "for which the leave-one-out form is not built")
         self._handle = _lib.Handle()
         self._dev = self._handle.device
         self.fulldims = Xtest.shape[1:] if Xtest is not None else X.shape[1:]

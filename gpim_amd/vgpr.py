@@ -39,7 +39,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, _sampling
+from . import _lib, _sampling, _solvers
 from . import gprutils
 from ._solvers import DeviceBlocks, HostDriver
 from .skgpr import BORDER_FACTOR
@@ -120,6 +120,11 @@ class vreconstructor(HostDriver):
         if kernel not in _KERNELS:
             raise NotImplementedError("vreconstructor: kernel %r is not implemented by the MI355X engine "
                                       "('RBF' or 'Matern52'; the spectral-mixture kernel is out of scope)" % (kernel,))
+        self.objective = _solvers.check_objective(kwargs.get("objective", "nll"))
+        if self.objective == "loo":
+            _solvers.refuse_loo_objective("multi-output GP (vreconstructor)",
+                                          "a held-out point is a vector of T correlated outputs: its predictive density needs "
+                                          "the T x T diagonal blocks of S^-1, which the dense engine's scalar diagonal is not")
         self._handle = _lib.Handle()
         self._dev = self._handle.device
         torch.manual_seed(seed)

@@ -798,6 +798,25 @@ int gpimhip_loo_exact_batched(gpimhip_handle h, const gpimhip_model_t* m, const 
 int gpimhip_loo_kron(gpimhip_handle h, const gpimhip_model_t* m, int32_t d, const int32_t* n, const double* axes,
                      const double* y, const double* u, double* mean_out, double* var_out, double* score_out);
 
+/* The leave-one-out pseudo-likelihood as a training objective (Rasmussen & Williams 5.4.2).  With
+ * S = K + (noise + jitter) I, alpha = S^-1 y and d_i = [S^-1]_ii
+ *   loss = sum_i [ -1/2 log d_i + alpha_i^2 / (2 d_i) ] + N/2 log 2 pi + prior constant
+ *        = - sum_i log N(y_i | y_i - alpha_i / d_i, 1 / d_i) + prior constant
+ * The held-out variance is 1 / d_i, that of the matrix that is trained: gpimhip_loo_exact's var_out plus the jitter wherever
+ * that entry did not clamp.  The prior constant is the one gpimhip_nll_grad carries.  The gradient takes the form of the
+ * marginal likelihood's, 1/2 sum_ij dS_ij/dtheta (G2_ij - (r_i alpha_j + alpha_i r_j)) with q = alpha / d, r = S^-1 q,
+ * omega = 1 / d + q^2 and G2 = S^-1 diag(omega) S^-1: one more N^3 product on the tile engine for all hyper-parameters
+ * together, about twice the cost of an iteration on the marginal likelihood.  Through the general engine at every N; fixed
+ * summation order: two calls give the same bits.
+ *   gpimhip_loo_grad        loss and d loss / d u at u: the arguments of gpimhip_nll_grad
+ *   gpimhip_fit_exact_loo   T Adam iterations on it: the arguments, outputs and failure report of gpimhip_fit_exact
+ * One problem per call on a double-precision handle of the dense model (there is no batched form): a single-precision
+ * handle, reflection mode, a border or a shard return GPIMHIP_E_BADARG with a message. */
+int gpimhip_loo_grad(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                     const double* u, double* loss_out, double* grad_out);
+int gpimhip_fit_exact_loo(gpimhip_handle h, const gpimhip_model_t* m, const double* X, const double* y, int64_t N,
+                          double* u_inout, double lr, int32_t T, double* hist_out, double* loss_out);
+
 /* Integrated variance reduction (ALC, the active-learning criterion of Cohn) over the M rows of a test grid Xs (M x d,
  * finite: the caller's contract, as for gpimhip_sample_exact) -- DESIGN.md section 26.  With S = K + (noise + jitter) I,
  * W = L^-1 K(X, Xs) and C = K(Xs, Xs) - W^T W, the latent posterior covariance on the grid,
