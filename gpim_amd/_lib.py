@@ -246,6 +246,7 @@ _PROTOS = {
     "gpimhip_step_plan_host_f32": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                   ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                                   ctypes.POINTER(ctypes.c_int32)]),
+    "gpimhip_fi_plan_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
     "gpimhip_gemm_tiles": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GemmTestStruct)]),
     "gpimhip_gemm_shape_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),

@@ -258,3 +258,13 @@ int launch_fit_small(gpimhip_ctx* h, const gpimhip_model_t* m, const double* X, 
         return GPIMHIP_OK;
     });
 }
+
+// The plan words of lds_factor_inv as host data, for tests (no GPU involved): make_fi_plan() -- the constexpr function
+// the device table c_fi_plan is initialised from -- evaluated on the host; the seven words of step p of an npan-panel
+// block (workers 0-5 = waves 1, 2, 3, 5, 6, 7; worker 6 = wave 0).
+extern "C" int gpimhip_fi_plan_host(int32_t npan, int32_t p, uint64_t* out) {
+    if (npan < 1 || npan > 8 || p < 0 || p >= npan || !out) return GPIMHIP_E_BADARG;
+    static const FiPlan plan = make_fi_plan();
+    for (int w = 0; w < 7; ++w) out[w] = plan.w[npan][p][w];
+    return GPIMHIP_OK;
+}

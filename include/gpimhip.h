@@ -950,6 +950,15 @@ int gpimhip_step_plan_host_paired(int32_t nb, int32_t* out, int64_t cap, int64_t
 int gpimhip_step_plan_host_f32(int32_t nb, int32_t with_inverse, int32_t* out, int64_t cap, int64_t* n_out,
                                int32_t* diag_out);
 
+/* The work plan of the Cholesky-with-inverse of an LDS-resident block of npan 16-column panels (blocklds.hpp:
+ * lds_factor_inv -- the fused trainer for N <= 128 at npan = ceil(N / 16), the diagonal blocks of the blocked Cholesky at
+ * npan = 8), as HOST data: out[0..6] = the plan words of step p for workers 0-5 (waves 1, 2, 3, 5, 6, 7) and worker 6
+ * (wave 0), from the function the device table is initialised from.  A word: bits 0-3 / 4-7 the tiles j of row p of the
+ * inverse the worker forms (15 = none), bits 8-11 its number of trailing items, then 12 bits per item
+ * (rtA << 9) | (ctA << 6) | (rtB << 3) | ctB (rtB = 0: one tile).  tests/test_fi_plan_host.py replays it on small blocks.
+ * GPIMHIP_E_BADARG outside 1 <= npan <= 8, 0 <= p < npan. */
+int gpimhip_fi_plan_host(int32_t npan, int32_t p, uint64_t* out);
+
 /* DIAGNOSTIC: the MFMA tile engine behind every O(N^3) stage, by itself (tests/test_gemm_host.py, tests/test_gpu_gemm.py).
  * Nothing in the product path calls these four.
  *

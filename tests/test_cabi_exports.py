@@ -18,6 +18,7 @@ def declared_symbols():
 def test_header_declares_something():
     syms = declared_symbols()
     assert "gpimhip_fit_exact" in syms and "gpimhip_predict_exact" in syms and len(syms) >= 12
+    assert "gpimhip_fi_plan_host" in syms
 
 
 def test_library_exports_header(ensure_built):
